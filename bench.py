@@ -26,6 +26,14 @@ with N > 1 and no RANK in the environment spawns the N ranks itself (fresh child
 this process touches a GPU); under torch.distributed.run it reads RANK / LOCAL_RANK / WORLD_SIZE as usual.
 
 Prints ONE JSON line on rank 0 (see the keys below).
+
+A plain run (`--gpus N --steps K --warmup W`) does only what the headline needs: set-up, W warm-up steps, K timed steps, and the line
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds per timed step).  Every other record - sustained
+timing, the other GEMM engines, the roofline leg and per-kernel figures, the matcher / streaming / mid-size / 24-joint records, the CPU
+baseline, at N > 1 the C-ABI bank broadcast and the configs[3] sub-record; with `--workload bank4k` the index checksum and the pipelined
+record - runs with `--full` only; its keys are null or absent otherwise.
+`--dump-outputs DIR` writes what the last timed step returned (poses `Y`, matched indices `idx`) as DIR/<name>.npy; the inputs are
+seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -58,6 +66,13 @@ def parse():
     ap.add_argument("--chunk", type=int, default=0, help="windows per internal chunk (0 = library default)")
     ap.add_argument("--joints", type=int, default=22, choices=(24, 22),
                     help="22 = BASELINE.json's metric (the reference's 'mixamo' layout); 24 = the shipped 'mocha' model")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, every other record: sustained timing with board power, the other GEMM engines, the roofline "
+                         "leg with per-kernel figures, the matcher / streaming / mid-size / 24-joint records, the CPU baseline; at N > 1 the C-ABI "
+                         "bank broadcast and the bank4k sub-record; with --workload bank4k the index checksum and the pipelined record "
+                         "(--no-extras, --no-cpu-baseline, --no-bank4k and --sustained-s trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's outputs of the last timed step as DIR/<name>.npy (float32 / float64, at most 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--three-calls", action="store_true",
                     help="run the step as encode(cha) + ContextBank + characterize(src) instead of the fused characterize_pair")
@@ -67,14 +82,14 @@ def parse():
     ap.add_argument("--cpu-sample", type=int, default=64, help="windows per clip of the CPU baseline leg's bounded sample (thread sweep, BASELINE.md section 3)")
     ap.add_argument("--cpu-full", type=int, default=-1, help="windows per clip of the ONE run of the full workload at the sweep's best configuration that cpu_baseline.value reports "
                     "(-1 = --windows, i.e. exactly the GPU workload: about 6 s at 585; 0 = skip it and report the best of the sample sweep)")
-    ap.add_argument("--sustained-s", type=float, default=2.5, help="seconds of the extra back-to-back timing of the same step (0 = skip)")
+    ap.add_argument("--sustained-s", type=float, default=2.5, help="with --full: seconds of the extra back-to-back timing of the same step (0 = skip)")
     ap.add_argument("--launch-timeout", type=float, default=3600.0,
                     help="seconds after which `--gpus N`'s own launcher stops ranks that have not finished (0 = never)")
-    ap.add_argument("--no-bank4k", action="store_true", help="N > 1: skip the configs[3] sub-record of the default line")
+    ap.add_argument("--no-bank4k", action="store_true", help="N > 1 with --full: skip the configs[3] sub-record of the default line")
     ap.add_argument("--options", default="", help="context options for the measured model, name=value[,name=value...] (mocha_set_option); "
                     "recorded in config.options - e.g. gemm_f16x2=1 (the opt-in two-plane fp16 GEMM engine: NOT the default line's arithmetic)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra records of the default N=1 line (matcher roofline, bank4k, streaming)")
+                    help="with --full: skip the extra records of the N=1 line (matcher roofline, bank4k, streaming)")
     return ap.parse_args()
 
 
@@ -402,6 +417,33 @@ def parse_options(text):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6 - (1 << 16)      # --dump-outputs: 64 MB in all, the .npy headers included
+
+
+def dump_outputs(path, **arrays):
+    """`--dump-outputs`: every array as <path>/<name>.npy - float32 stays float32, anything else becomes float64 (integer indices are exact
+    there).  If they come to more than DUMP_LIMIT_BYTES together, the largest one keeps a fixed, seeded sample of its rows (first axis), in
+    ascending order, and the sampled row numbers are written as <name>_rows.npy: the same arguments give the same sample."""
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for k, v in arrays.items():
+        v = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        host[k] = np.ascontiguousarray(v, dtype=np.float32 if v.dtype == np.float32 else np.float64)
+    total = sum(v.nbytes for v in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        big = max(host, key=lambda k: host[k].nbytes)
+        n = host[big].shape[0]
+        row_bytes = host[big].nbytes // n + 8                     # + the row number itself, float64
+        keep = (DUMP_LIMIT_BYTES - (total - host[big].nbytes)) // row_bytes
+        if keep < 1:
+            raise SystemExit(f"bench.py --dump-outputs: the outputs other than {big!r} already exceed {DUMP_LIMIT_BYTES} bytes")
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        host[big] = np.ascontiguousarray(host[big][rows])
+        host[big + "_rows"] = rows.astype(np.float64)
+    for k, v in host.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def comm_record(model, backend, world):
     """The `rccl` record of an N > 1 line: what the C ABI's communicator REALLY is on every rank (mocha_comm_info: ncclCommCount,
     ncclGetVersion, the file the entry points came from, device and PCI bus id), gathered over the side channel - plus every
@@ -505,7 +547,7 @@ def projected_scaling_record(a, model, dev, V, sd=None, layout=None):
                     "a mid-size step is a latency chain that leaves most of the chip idle, independent steps fill each other's gaps"}
 
 
-def bank4k_record(a, model, dev, V, rank, world, backend, sd=None, layout=None):
+def bank4k_record(a, model, dev, V, rank, world, backend, sd=None, layout=None, dump_dir=None):
     """BASELINE configs[2] / [3]: 1024 synthetic source windows against a 4096-entry character bank stored bf16 for matching; with N
     GPUs the windows are split by shard_bounds (128 per GPU at N = 8: strong scaling) and rank 0's bank reaches every rank
     through the C ABI (mocha_bank_broadcast: RCCL scatter + all-gather over xGMI), timed on its own.  One step = encode, z-score, 1-NN
@@ -572,16 +614,25 @@ def bank4k_record(a, model, dev, V, rank, world, backend, sd=None, layout=None):
         vals = [None] * world
         torch.distributed.all_gather_object(vals, per_rank[0])
         per_rank = [float(v) for v in vals]
-    # after the timed region: every rank's indices, in window order, as one checksum - the N-way split must reproduce the 1-GPU one
-    idx_all = D.all_gather_rows(idx, W).cpu().numpy().astype(np.int32)
-    y_abs = D.max_over_ranks(float(Y.abs().max()), dev)
-    # ... and a per-window fingerprint of the poses (sum |Y| of 16 windows spread over all shards): a split that mixed windows up
-    # would keep the index CRC when the indices happen to coincide, not this
-    fp_all = D.all_gather_rows(Y.abs().sum(dim=(1, 2, 3)), W).cpu().numpy()
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, Y=Y, idx=idx)
+    checks = {}
+    if a.full:
+        # after the timed region: every rank's indices, in window order, as one checksum - the N-way split must reproduce the 1-GPU one
+        idx_all = D.all_gather_rows(idx, W).cpu().numpy().astype(np.int32)
+        y_abs = D.max_over_ranks(float(Y.abs().max()), dev)
+        # ... and a per-window fingerprint of the poses (sum |Y| of 16 windows spread over all shards): a split that mixed windows up
+        # would keep the index CRC when the indices happen to coincide, not this
+        fp_all = D.all_gather_rows(Y.abs().sum(dim=(1, 2, 3)), W).cpu().numpy()
+        crc = zlib.crc32(idx_all.tobytes())
+        known = BANK4K_IDX_CRC32_N1.get(kernel_source_sha16(), {}).get(V)
+        checks = {"idx_crc32": crc, "idx_crc32_n1_known": known, "idx_matches_n1": (crc == known) if known is not None else None,
+                  "idx_head": idx_all[:8].tolist(), "idx_distinct": int(len(np.unique(idx_all))),
+                  "max_abs_Y": y_abs, "y_fingerprint": [float(v) for v in fp_all[:: W // 16][:16]]}
     # extra: the same per-rank share with consecutive steps overlapped on three contexts / streams (BatchPipeline over the bank every rank
     # now holds); the poses of the last step must equal the serial ones
     pipelined = None
-    if sd is not None and not os.environ.get("MOCHA_BENCH_NO_PIPELINE"):
+    if a.full and sd is not None and not os.environ.get("MOCHA_BENCH_NO_PIPELINE"):
         from mocha_sigasia2023_amd import BatchPipeline
         pipe, perr = None, None
         with torch.no_grad():
@@ -610,8 +661,6 @@ def bank4k_record(a, model, dev, V, rank, world, backend, sd=None, layout=None):
     del bank, bank_nm, bank_enc
     if rank != 0:
         return None
-    crc = zlib.crc32(idx_all.tobytes())
-    known = BANK4K_IDX_CRC32_N1.get(kernel_source_sha16(), {}).get(V)
     return {"value": W * a.steps / elapsed, "unit": "frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": elapsed / a.steps * 1e3, "scaling": "strong", "dtype": "f32 (bf16 bank for matching)",
             "config": {"workload": f"BASELINE configs[2]/[3]: 1024 windows x 4096-entry bank (bf16 cnt), V={V}, "
@@ -620,9 +669,7 @@ def bank4k_record(a, model, dev, V, rank, world, backend, sd=None, layout=None):
                        "parallelism": f"dp{world}, bank broadcast from rank 0, no in-step collective"},
             "per_rank_frames_per_s": per_rank,
             "bank_broadcast": bcast, "bank_broadcast_ms": bcast["ms"] if bcast else None, "bank_bytes": 2 * NB * 90 * 256 * 4,
-            "idx_crc32": crc, "idx_crc32_n1_known": known, "idx_matches_n1": (crc == known) if known is not None else None,
-            "idx_head": idx_all[:8].tolist(), "idx_distinct": int(len(np.unique(idx_all))),
-            "max_abs_Y": y_abs, "y_fingerprint": [float(v) for v in fp_all[:: W // 16][:16]],
+            **checks,
             "pipelined_3_contexts": pipelined}
 
 
@@ -642,7 +689,7 @@ def bank4k(a):
     model = Generator(layout=layout, device=dev).load_state_dict(sd).eval()
     for k, v in parse_options(a.options).items():
         model.set_option(k, v)
-    rec = bank4k_record(a, model, dev, V, rank, world, backend, sd, layout)
+    rec = bank4k_record(a, model, dev, V, rank, world, backend, sd, layout, dump_dir=a.dump_outputs)
     if rec is not None and parse_options(a.options):       # bank4k_record returns the record on rank 0 only: every other rank goes straight on to the collective below
         rec["config"]["options"] = parse_options(a.options)
     rccl = comm_record(model, backend, world) if torch.distributed.is_initialized() else None
@@ -975,6 +1022,7 @@ def main():
         D.broadcast_([cha, mean, std], src=0)     # RCCL over xGMI, set-up only: rank 0 owns the character clip
         torch.cuda.synchronize()
         clip_bcast_ms = (time.perf_counter() - t0) * 1e3
+    if dist_on and a.full:
         # north star: "RCCL broadcast of the character feature bank over xGMI".  Rank 0 builds the bank of the character clip and
         # hands it to every rank through the C ABI (mocha_bank_broadcast: scatter + all-gather); every rank checks what it got.
         # (The timed step below does not depend on this bank - every rank builds the pair's bank itself, as at N = 1 - so a failure
@@ -1028,6 +1076,8 @@ def main():
             Y, idx = step()
         sync_all()
         elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, Y=Y, idx=idx)
     my_elapsed = elapsed
     elapsed = D.max_over_ranks(elapsed, dev)
     ms_per_step = elapsed / a.steps * 1e3
@@ -1041,7 +1091,7 @@ def main():
     # extra (not the headline): the same step back to back for >= --sustained-s seconds (the plane GEMMs run at the board's
     # power limit: the clock a 0.1 s burst holds is not the one a long run holds)
     sustained = None
-    if a.sustained_s > 0 and world == 1:
+    if a.full and a.sustained_s > 0 and world == 1:
         n_sus = max(a.steps, int(a.sustained_s / (ms_per_step * 1e-3)) + 1)
         with torch.no_grad(), PowerSampler() as ps:
             sync_all()
@@ -1072,7 +1122,7 @@ def main():
 
     # extra (not the headline): the same step on the exact-f32 MFMA engine (mocha_set_option("gemm_bf16x3", 0))
     exact_f32 = None
-    if world == 1 and not a.no_extras:
+    if a.full and world == 1 and not a.no_extras:
         model.set_option("gemm_bf16x3", 0)
         model.set_option("attention_bf16x3", 0)
         with torch.no_grad():
@@ -1093,7 +1143,7 @@ def main():
     # extra (not the headline): the same step with the encoder's, decoder's and to_mot's plane GEMMs on two fp16 planes / three passes
     # (mocha_set_option("gemm_f16x2", 1), csrc/gemm_h2.hip); the poses are compared with the default engine's of the same inputs
     f16x2 = None
-    if world == 1 and not a.no_extras and not opts.get("gemm_f16x2"):
+    if a.full and world == 1 and not a.no_extras and not opts.get("gemm_f16x2"):
         with torch.no_grad():
             Y0, i0 = model.characterize_pair(src, cha, mean, std, return_index=True)
             model.set_option("gemm_f16x2", 1)
@@ -1119,12 +1169,34 @@ def main():
     # N > 1: BASELINE configs[3] beside the weak-scaled headline - the same 1024 windows split over the ranks, the 4096-entry bank
     # through mocha_bank_broadcast (collective: every rank takes part; the record comes back on rank 0)
     bank4k_rec = None
-    if dist_on and world > 1 and not a.no_bank4k and not bcast_err:
+    if a.full and dist_on and world > 1 and not a.no_bank4k and not bcast_err:
         with torch.no_grad():
             bank4k_rec = bank4k_record(a, model, dev, V, rank, world, backend, sd, layout)
 
     out = None
     if rank == 0:
+        out = {
+            "metric": METRIC[V],
+            "value": value, "unit": "frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32" if not opts.get("gemm_f16x2") else "f32 in / out / accumulate; GEMM operands as two fp16 planes = 22 bits (--options gemm_f16x2=1)",
+            "data": "synthetic",
+            "config": {"options": opts, "workload": f"demo pair (BASELINE configs[1]): {W} src x {W} cha windows, T=60, V={V}, C=15, "
+                                   f"bank build + encode/match/decode/to_mot per step "
+                                   f"({'encode + ContextBank + characterize' if step is step_three_calls else 'characterize_pair'})",
+                       "windows_per_gpu": W,
+                       "joints": V, "bank_entries": W, "parallelism": f"dp{world} (independent windows, no in-step collective)"},
+            "roofline": None, "kernel_breakdown": None, "match_sites": None,      # --full: the roofline leg below
+            "bank_broadcast_ms": bcast_ms, "bank_broadcast_error": bcast_err, "clip_broadcast_ms": clip_bcast_ms,
+            "per_rank_frames_per_s": per_rank,
+            "rccl": rccl,
+            "bank4k": bank4k_rec,
+            "sustained": sustained,
+            "dual_stream": dual,
+            "exact_f32_engine": exact_f32,
+            "f16x2_engine": f16x2,
+        }
+    if rank == 0 and a.full:
         # ---- roofline leg: the same step once more with a HIP-event pair around every launch
         with torch.no_grad():
             for _ in range(max(a.warmup, 5)):       # the extras above ran other engines / workloads: bring the board back to this step's state first
@@ -1179,29 +1251,7 @@ def main():
                          "tflops": (v["flops"] / (v["ms"] * 1e-3) / 1e12) if v["ms"] > 0 else 0.0,
                          "gbs": (v["bytes"] / (v["ms"] * 1e-3) / 1e9) if v["ms"] > 0 else 0.0}
                      for k, v in sorted(kern.items(), key=lambda kv: -kv[1]["ms"])}
-        out = {
-            "metric": METRIC[V],
-            "value": value, "unit": "frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32" if not opts.get("gemm_f16x2") else "f32 in / out / accumulate; GEMM operands as two fp16 planes = 22 bits (--options gemm_f16x2=1)",
-            "data": "synthetic",
-            "config": {"options": opts, "workload": f"demo pair (BASELINE configs[1]): {W} src x {W} cha windows, T=60, V={V}, C=15, "
-                                   f"bank build + encode/match/decode/to_mot per step "
-                                   f"({'encode + ContextBank + characterize' if step is step_three_calls else 'characterize_pair'})",
-                       "windows_per_gpu": W,
-                       "joints": V, "bank_entries": W, "parallelism": f"dp{world} (independent windows, no in-step collective)"},
-            "roofline": roofline,
-            "kernel_breakdown": breakdown,
-            "match_sites": {k: {"ms_per_step": v["ms"] / 3} for k, v in mk.items()},
-            "bank_broadcast_ms": bcast_ms, "bank_broadcast_error": bcast_err, "clip_broadcast_ms": clip_bcast_ms,
-            "per_rank_frames_per_s": per_rank,
-            "rccl": rccl,
-            "bank4k": bank4k_rec,
-            "sustained": sustained,
-            "dual_stream": dual,
-            "exact_f32_engine": exact_f32,
-            "f16x2_engine": f16x2,
-        }
+        out.update(roofline=roofline, kernel_breakdown=breakdown, match_sites={k: {"ms_per_step": v["ms"] / 3} for k, v in mk.items()})
         if world == 1 and not a.no_extras:
             # extra records measured in the same process (not the headline): the matcher's own roofline on the shapes the
             # north star's ">= 50 % HBM in the context-matching kernel" is evaluated on, the streamed configs[4] step, the
@@ -1235,6 +1285,7 @@ def main():
             out["speedup_vs_cpu"] = value / out["cpu_baseline"]["value"]
             out["config"]["cpu_baseline_sample"] = (f"value: {cpu_full} + {cpu_full} windows once (the GPU workload is {W} + {W}); " if cpu_full else "") + \
                                                    f"thread sweep on {a.cpu_sample} + {a.cpu_sample} windows"
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if dist_on:
         D.barrier()

@@ -171,9 +171,20 @@ def run_match():
     print("match", {k: v for k, v in out.items() if k.endswith("idx")})
 
 
+CVAE_ARITHMETIC = {"MKL_CBWR": "COMPATIBLE", "ATEN_CPU_CAPABILITY": "default", "OMP_NUM_THREADS": "1", "MKL_NUM_THREADS": "1"}
+
+
 def run_cvae():
     """CVAE.sample(c, deterministic=True) of the reference (model_CVAE.py:44-46) with synthetic weights,
-    constructed as the demo does (test_fullframework.py:52-58)."""
+    constructed as the demo does (test_fullframework.py:52-58).  Recorded on the arithmetic tests/test_cvae_oracle.py
+    re-runs the oracle on: MKL's reproducible COMPATIBLE path, ATen's non-vectorised kernels, one thread - the same bits
+    on any x86-64 CPU, where the default dispatch picks AVX2 or AVX-512 code by CPU and moves `out` by up to 1e-5.  Both
+    libraries read these settings when they load, so they are set in the environment of the whole run:
+        env MKL_CBWR=COMPATIBLE ATEN_CPU_CAPABILITY=default OMP_NUM_THREADS=1 MKL_NUM_THREADS=1 python tests/golden/make_golden.py run_cvae"""
+    unset = {k: v for k, v in CVAE_ARITHMETIC.items() if os.environ.get(k) != v}
+    if unset:
+        raise SystemExit(f"run_cvae: set {unset} in the environment (see the docstring)")
+    torch.set_num_threads(1)
     cwd = os.getcwd(); os.chdir(REF)
     try:
         if REF not in sys.path:
@@ -195,7 +206,7 @@ def run_cvae():
         mu, logvar = net.prior(c)
         out = net.sample(c, deterministic=True)
     np.savez(os.path.join(HERE, "cvae_sample.npz"), c=c.numpy(), mu=mu.numpy(), logvar=logvar.numpy(), out=out.numpy(),
-             meta=np.array(repr(dict(seed=99, gain=1.0, torch=torch.__version__))))
+             meta=np.array(repr(dict(seed=99, gain=1.0, torch=torch.__version__, arithmetic=CVAE_ARITHMETIC))))
     print("cvae", {k: float(np.abs(v).max()) for k, v in dict(mu=mu.numpy(), logvar=logvar.numpy(), out=out.numpy()).items()})
 
 

@@ -1,22 +1,48 @@
 """Pins the CVAE oracle against the fixture produced by the reference CVAE (tests/golden/make_golden.py)."""
+import ast
 import os
+import subprocess
+import sys
 
 import numpy as np
-import torch
 
+from mocha_sigasia2023_amd import weights
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# The fixture's arithmetic (make_golden.py run_cvae): MKL's reproducible COMPATIBLE path, ATen's non-vectorised kernels, one thread.
+# It gives the same bits on any x86-64 CPU; the default dispatch picks AVX2 or AVX-512 code by CPU and moves `out` by up to 1e-5,
+# more than the bound below.  Both libraries read these settings when they load: the oracle runs in a child process that has them.
+ARITHMETIC = {"MKL_CBWR": "COMPATIBLE", "ATEN_CPU_CAPABILITY": "default", "OMP_NUM_THREADS": "1", "MKL_NUM_THREADS": "1"}
+_CHILD = """
+import sys
+import numpy as np
+import torch
+sys.path.insert(0, sys.argv[1])
 from mocha_sigasia2023_amd import weights
 from oracle import cvae_oracle as CO
 from oracle.mocha_oracle import to_torch_state
+torch.set_num_threads(1)
+z = np.load(sys.argv[2])
+sd = to_torch_state(weights.synthetic_cvae_state_dict(99, 1.0))
+with torch.no_grad():
+    out, mu, logvar = CO.sample(sd, torch.from_numpy(z["c"]))
+np.savez(sys.argv[3], out=out.numpy(), mu=mu.numpy(), logvar=logvar.numpy())
+"""
 
 
-def test_cvae_oracle_matches_reference(golden_dir):
-    z = np.load(os.path.join(golden_dir, "cvae_sample.npz"))
-    sd = to_torch_state(weights.synthetic_cvae_state_dict(99, 1.0))
-    with torch.no_grad():
-        out, mu, logvar = CO.sample(sd, torch.from_numpy(z["c"]))
-    assert np.abs(mu.numpy() - z["mu"]).max() < 5e-6
-    assert np.abs(logvar.numpy() - z["logvar"]).max() < 5e-6
-    assert np.abs(out.numpy() - z["out"]).max() < 5e-6
+def test_cvae_oracle_matches_reference(golden_dir, tmp_path):
+    fixture = os.path.join(golden_dir, "cvae_sample.npz")
+    z = np.load(fixture)
+    assert ast.literal_eval(str(z["meta"]))["arithmetic"] == ARITHMETIC
+    py = [sys.executable] + (["-s"] if sys.flags.no_user_site else [])
+    r = subprocess.run(py + ["-c", _CHILD, REPO, fixture, str(tmp_path / "oracle.npz")], env=dict(os.environ, **ARITHMETIC),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    o = np.load(tmp_path / "oracle.npz")
+    out, mu, logvar = o["out"], o["mu"], o["logvar"]
+    assert np.abs(mu - z["mu"]).max() < 5e-6
+    assert np.abs(logvar - z["logvar"]).max() < 5e-6
+    assert np.abs(out - z["out"]).max() < 5e-6
 
 
 def test_cvae_schema():

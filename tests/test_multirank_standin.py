@@ -140,7 +140,7 @@ def _bench(standin, args, **env):
 @pytest.fixture(scope="module")
 def bank4k_one_rank(standin):
     """ONE 1-rank run of `bench.py --workload bank4k` shared by the tests that compare an N-rank split with it."""
-    return _bench(standin, ["--workload", "bank4k", "--steps", "1", "--warmup", "1"])
+    return _bench(standin, ["--workload", "bank4k", "--full", "--steps", "1", "--warmup", "1"])
 
 
 @pytest.mark.timeout(3000)
@@ -150,7 +150,7 @@ def test_bench_bank4k_split_two_ways_reproduces_the_one_rank_indices(standin, ba
     --options (ranks other than 0 used to raise on the options record before the rccl collective) - an option at its default
     value, so the arithmetic is the 1-rank run's."""
     one = bank4k_one_rank
-    two = _bench(standin, ["--workload", "bank4k", "--gpus", "2", "--steps", "1", "--warmup", "1", "--options", "gemm_persistent=768"],
+    two = _bench(standin, ["--workload", "bank4k", "--full", "--gpus", "2", "--steps", "1", "--warmup", "1", "--options", "gemm_persistent=768"],
                  MOCHA_BENCH_ONE_GPU="1", MOCHA_BENCH_BACKEND="gloo")
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2
     assert two["config"]["options"] == {"gemm_persistent": 768} and two["rccl"]["nranks"] == 2
@@ -167,7 +167,7 @@ def test_bench_bank4k_split_two_ways_reproduces_the_one_rank_indices(standin, ba
 def test_bench_demo_two_ranks_runs_the_broadcast_and_probe(standin):
     """bench.py's default workload with N = 2 (bench.py: clip broadcast, C-ABI bank broadcast, probe of the received bank,
     max-over-ranks timing, per-rank rates)."""
-    rec = _bench(standin, ["--gpus", "2", "--windows", "96", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras"],
+    rec = _bench(standin, ["--full", "--gpus", "2", "--windows", "96", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras"],
                  MOCHA_BENCH_ONE_GPU="1", MOCHA_BENCH_BACKEND="gloo")
     assert rec["n_gpus"] == 2 and rec["scaling"] == "weak"
     assert rec.get("bank_broadcast_error") is None and rec["bank_broadcast_ms"] > 0
@@ -209,7 +209,7 @@ def test_bench_default_line_eight_ranks_is_configs3(standin, bank4k_one_rank):
     """`python bench.py --gpus 8` - the last point of the driver's 1 -> 8 curve - through the stand-in: the weak-scaled headline over eight
     ranks AND the configs[3] sub-record exactly as BASELINE words it (1024 windows = 128 per GPU, the 4096-entry bank broadcast from rank 0),
     with the index checksum of the 1-rank run of the same build (the split: test_fullframework.py:148-158, 440-443)."""
-    rec = _bench(standin, ["--gpus", "8", "--windows", "64", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extras"],
+    rec = _bench(standin, ["--full", "--gpus", "8", "--windows", "64", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extras"],
                  MOCHA_BENCH_ONE_GPU="1", MOCHA_BENCH_BACKEND="gloo")
     assert rec["n_gpus"] == 8 and rec["bank_broadcast_error"] is None and rec["scaling"] == "weak"
     assert len(rec["per_rank_frames_per_s"]) == 8 and all(v > 0 for v in rec["per_rank_frames_per_s"])
@@ -225,7 +225,7 @@ def test_bench_default_line_eight_ranks_is_configs3(standin, bank4k_one_rank):
 @pytest.mark.timeout(3000)
 def test_bench_bank4k_four_ranks_uneven_free_split(standin, bank4k_one_rank):
     """`bench.py --workload bank4k --gpus 4` (256 windows per GPU): the second interior point of the driver's curve, same checksum."""
-    rec = _bench(standin, ["--workload", "bank4k", "--gpus", "4", "--steps", "1", "--warmup", "1"], MOCHA_BENCH_ONE_GPU="1", MOCHA_BENCH_BACKEND="gloo")
+    rec = _bench(standin, ["--workload", "bank4k", "--full", "--gpus", "4", "--steps", "1", "--warmup", "1"], MOCHA_BENCH_ONE_GPU="1", MOCHA_BENCH_BACKEND="gloo")
     assert rec["n_gpus"] == 4 and rec["config"]["windows_per_gpu"] == [256] * 4 and rec["rccl"]["nranks"] == 4
     assert rec["idx_crc32"] == bank4k_one_rank["idx_crc32"] and len(rec["per_rank_frames_per_s"]) == 4
 
@@ -255,7 +255,7 @@ def test_bench_under_torch_distributed_run_two_ranks(standin):
     --master-port P bench.py --gpus N ...` - with two ranks on GPU 0: bench.py reads RANK / LOCAL_RANK / WORLD_SIZE from the
     launcher's environment, prints ONE line on rank 0, whole-job value = sum over the ranks."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_port()), os.path.join(REPO, "bench.py"), "--gpus", "2", "--windows", "64", "--steps", "2", "--warmup", "1"]
+           "--master-port", str(_port()), os.path.join(REPO, "bench.py"), "--full", "--gpus", "2", "--windows", "64", "--steps", "2", "--warmup", "1"]
     out = subprocess.run(cmd, env=_env(standin, MOCHA_BENCH_ONE_GPU="1", MOCHA_BENCH_BACKEND="gloo"), capture_output=True, text=True, timeout=1200)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

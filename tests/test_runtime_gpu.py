@@ -158,7 +158,7 @@ def test_bench_one_rank_over_rccl_and_launcher_refuses_missing_gpus():
     timing all run; `--gpus N` beyond the node's GPUs is refused by the launcher before any rank starts."""
     env = dict(os.environ, MOCHA_FORCE_DIST="1")
     env.pop("RANK", None); env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
                         "--no-extras", "--windows", "64"], env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])      # RCCL prints its banner to stdout
@@ -202,6 +202,33 @@ def test_bank4k_workload_runs():
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["scaling"] == "strong" and line["value"] > 1e4 and line["n_gpus"] == 1
+
+
+@pytest.mark.timeout(900)
+def test_bench_plain_run_times_the_headline_and_dumps_its_last_step(tmp_path):
+    """A plain bench.py run times --steps steps of the headline and runs no other record; --dump-outputs writes what the last timed step
+    returned: the poses and indices of one characterize_pair call on the bench's seeded inputs."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MOCHA_FORCE_DIST")}
+    W = 64
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--windows", str(W),
+                        "--dump-outputs", str(tmp_path / "out")], env=env, capture_output=True, text=True, timeout=800)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["n_gpus"] == 1 and line["unit"] == "frames/s" and line["dtype"] == "f32"
+    assert line["ms_per_step"] > 0 and abs(line["value"] - W * 1e3 / line["ms_per_step"]) < 1e-6 * line["value"]
+    assert all(line[k] is None for k in ("roofline", "kernel_breakdown", "sustained", "exact_f32_engine", "f16x2_engine", "bank4k"))
+    assert "cpu_baseline" not in line and "match" not in line
+    assert sorted(os.listdir(tmp_path / "out")) == ["Y.npy", "idx.npy"]
+    Y, idx = np.load(tmp_path / "out" / "Y.npy"), np.load(tmp_path / "out" / "idx.npy")
+    assert Y.dtype == np.float32 and Y.shape == (W, 60, 22, 15) and idx.dtype == np.float64 and idx.shape == (W,)
+    m = Generator(layout="mixamo", device="cuda:0").load_state_dict(weights.synthetic_state_dict(seed=1777, gain=1.0, layout="mixamo")).eval()
+    src = torch.from_numpy(synthetic.pose_windows(1777, W, 22)).cuda()
+    cha = torch.from_numpy(synthetic.pose_windows(4242, W, 22)).cuda()
+    mean, std = (torch.from_numpy(x).cuda() for x in synthetic.cnt_norm(7))
+    with torch.no_grad():
+        Y0, i0 = m.characterize_pair(src, cha, mean, std, return_index=True)
+    assert np.array_equal(idx, i0.cpu().numpy().astype(np.float64))
+    assert float(np.abs(Y - Y0.cpu().numpy()).max()) <= 1e-5
 
 
 def _two_contexts(flag, priority=0, reps=6):
