@@ -15,7 +15,8 @@
  *   - `stream` is a hipStream_t passed as void*; all work is enqueued on it.  Steady-state calls do not synchronise
  *     the device and are graph-capture safe; device allocations (and the device synchronisation that replacing a
  *     buffer needs) only happen in mocha_finalize_weights, mocha_reserve, mocha_bank_set (both also size the match
- *     scratch for every query count the workspace admits), mocha_bank_broadcast, mocha_set_option and the first call
+ *     scratch for every query count the workspace admits), mocha_bank_set_segments (also the segmented calls' scratch),
+ *     mocha_bank_broadcast, mocha_set_option and the first call
  *     with a batch larger than any before.  Each such replacement bumps mocha_generation(ctx): a caller that captured
  *     calls into its own HIP graph compares the generation before replaying (mocha_step_graph does so itself);
  *   - a NULL where a required device pointer belongs is MOCHA_ERR_ARG ("... null argument"), never a launch; with an empty batch
@@ -138,6 +139,9 @@ int mocha_forward_features(mocha_ctx* ctx, const float* src_X, const float* cha_
  * re-evaluates on the fp32 rows, exactly, every row the copy's rounding cannot exclude (triangle inequality on the measured
  * residuals): the indices and distances of the fp32 search, not of a bf16 bank. */
 #define MOCHA_BANK_BF16 2
+/* flags bit 2: do not compute the per-entry decoder constants of option "bank_dec_cache" for this bank (+ 92 KB per entry saved; the decoder
+ * then derives them per call, as with the option off) - the option itself is left as it is. */
+#define MOCHA_BANK_NO_DEC_CACHE 4
 int mocha_bank_set(mocha_ctx* ctx, const float* cnt_nm, const float* encoded, int64_t N, int flags, void* stream);
 /* tree.query(q, k=1), test_fullframework.py:296,443: exact Euclidean 1-NN of each z-scored
  * query row (Q, 90*256) in the bank.  idx (Q,) int32; dist (Q,) fp32 Euclidean distance to the
@@ -177,6 +181,35 @@ int mocha_step_graph(mocha_ctx* ctx, const float* X1, const float* cnt_mean, con
  * that stream as usual.  Weights and the bank are shared and read-only. */
 int mocha_step_graph_lane(mocha_ctx* ctx, int lane, const float* X1, const float* cnt_mean, const float* cnt_std, float* Y1,
                           int32_t* idx, int raw, void* stream);
+
+/* Several characters served per call from ONE multi-character bank.  The characters' banks (each z-scored with the same global
+ * cnt_mean / cnt_std) are concatenated into N rows; segment s = rows [seg_start[s], seg_start[s + 1]) is character s's bank.
+ *   mocha_bank_set_segments : mocha_bank_set over the N rows (same flags, same derived data and decoder-constant cache), plus the segment
+ *                             table.  seg_start (HOST, S + 1 entries) runs from 0 to N and every segment holds at least one row, else
+ *                             MOCHA_ERR_ARG.  Sizes all the scratch of the segmented calls below (graph-capture safe: they never allocate).
+ *                             mocha_bank_set and mocha_bank_broadcast clear the table; a segmented call without one is MOCHA_ERR_STATE.
+ *                             Every other call on a segmented bank (mocha_match, mocha_match_topk, mocha_characterize, mocha_step_graph,
+ *                             gathers) searches / reads the UNION of all rows, as after mocha_bank_set of the concatenation.
+ *   mocha_match_segmented   : exact 1-NN of each query (Q, 90*256) within its own segment seg[q] (DEVICE, Q int32): idx (Q,) the row LOCAL
+ *                             to the segment (BallTree(that character's cnt_nm).query(k=1)), ties to the lowest row; dist (Q,) or NULL, the
+ *                             Euclidean distance in the bank's arithmetic (fp32 rows; MOCHA_BANK_BF16: the bf16 copy centred on the union's
+ *                             centroid, with centred queries).  An id outside [0, S): idx -1, dist +inf, and no bank row is read for it.
+ *                             Cost: one pass over rows(segment) x 90*256 values per block of up to 8 queries sharing a segment.
+ *   mocha_characterize_segmented : mocha_characterize (raw != 0: mocha_characterize_raw) with every window matched in its own segment;
+ *                             idx (B,) local rows or NULL.  A window with an invalid id gets idx -1 and an unspecified Y (its decoder reads
+ *                             row 0).
+ *   mocha_step_graph_segmented : that call for S_w windows (1 <= S_w <= 16; X (S_w,T,V,C_in) device, one window per stream of the caller),
+ *                             captured into a HIP graph on first use and replayed, as mocha_step_graph.  The graph is keyed on the buffer
+ *                             pointers, S_w, raw and the generation; new ids written into seg between calls are read by the replay and do
+ *                             not re-capture.  Uses workspace set 0 (as mocha_characterize and mocha_step_graph): drive the context from
+ *                             one stream at a time. */
+int mocha_bank_set_segments(mocha_ctx* ctx, const float* cnt_nm, const float* encoded, int64_t N, const int64_t* seg_start, int S, int flags,
+                            void* stream);
+int mocha_match_segmented(mocha_ctx* ctx, const float* query_nm, int Q, const int32_t* seg, int32_t* idx, float* dist, void* stream);
+int mocha_characterize_segmented(mocha_ctx* ctx, const float* src_X, int B, const int32_t* seg, const float* cnt_mean, const float* cnt_std,
+                                 float* Y, int32_t* idx, int raw, void* stream);
+int mocha_step_graph_segmented(mocha_ctx* ctx, const float* X, int S_w, const int32_t* seg, const float* cnt_mean, const float* cnt_std,
+                               float* Y, int32_t* idx, int raw, void* stream);
 
 /* Multi-GPU set-up: one process per GPU, windows sharded across ranks, the character bank replicated.
  * The reference has no counterpart (trainer.py:45-47 is nn.DataParallel); the only exchange on the path is this one-time

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmocha_hip.so")
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 class mocha_cfg(C.Structure):
@@ -74,6 +74,10 @@ SIGNATURES = {
     "mocha_generation": (_i64, [_vp]),
     "mocha_step_graph": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "mocha_step_graph_lane": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "mocha_bank_set_segments": (_i, [_vp, _vp, _vp, _i64, C.POINTER(_i64), _i, _i, _vp]),
+    "mocha_match_segmented": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "mocha_characterize_segmented": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "mocha_step_graph_segmented": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "mocha_set_rccl_library": (_i, [C.c_char_p]),
     "mocha_comm_unique_id": (_i, [_vp, _vp]),
     "mocha_comm_init": (_i, [_vp, _vp, _i, _i]),

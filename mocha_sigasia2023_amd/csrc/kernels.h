@@ -273,6 +273,16 @@ hipError_t launch_rowresid(const float* x, const float* centre, const void* x16,
 hipError_t launch_match_scan16(const void* bank16, const float* rho, const float* bank, const float* qc, const float* query, int Q, int64_t N,
                                int D, unsigned long long* scratch, int32_t* idx, float* dist, hipStream_t s);
 hipError_t launch_rownorm2_bf16(const void* x, float* out, int64_t rows, int cols, hipStream_t s);
+// multi-character bank (match_segmented.hip): every query's exact 1-NN within its own row segment [seg_start[seg[q]], seg_start[seg[q] + 1]),
+// the segment chosen by device data; bank fp32 rows or the centred bf16 copy (then centred queries).  idx: local row (-1 for an id outside
+// [0, S)), gidx: global row (0 for such an id), dist (or null): direct-form distance (+inf for such an id).  Q <= SEG_MAX_Q per launch;
+// partial = match_seg_scratch_words(Q, largest segment) u64 words, plan = seg_plan_ints(Q, S) ints.
+static constexpr int SEG_MAX_Q = 4096;
+size_t match_seg_scratch_words(int Q, int64_t max_rows);
+size_t seg_plan_ints(int Q, int S);
+hipError_t launch_match_segmented(const void* bank, int bank_bf16, const float* query, const int32_t* seg, int Q, const int* seg_start, int S,
+                                  int64_t max_rows, int D, unsigned long long* partial, int* plan, int32_t* idx, int32_t* gidx, float* dist,
+                                  hipStream_t s);
 // out[q] = src[idx[q]] rows of `cols` floats
 hipError_t launch_gather_rows(const float* src, const int32_t* idx, float* out, int Q, int cols, int64_t nrows, hipStream_t s);
 

@@ -243,12 +243,28 @@ struct mocha_ctx {
     int match_nt = 1;                  // applied to launches with ONE query tile (Q <= 128): the bank is then read exactly once per launch
     DevBuf match_qstat[MAX_SETS];
 
+    // multi-character bank (mocha_bank_set_segments): the current bank's rows as S segments, on the host and on the device; cleared by
+    // every other way of setting the bank.  Per workspace set: the segmented matcher's partial minima and plan for up to seg_q queries
+    // per launch (sized at mocha_bank_set_segments: the segmented calls never allocate)
+    std::vector<int64_t> seg_start;                   // S + 1 entries; empty = no table
+    int64_t seg_max_rows = 0;
+    int* seg_dev = nullptr; size_t seg_dev_cap = 0;
+    int seg_q = 0;
+    unsigned long long* seg_partial[MAX_SETS] = {nullptr, nullptr, nullptr}; size_t seg_partial_n[MAX_SETS] = {0, 0, 0};
+    int* seg_plan[MAX_SETS] = {nullptr, nullptr, nullptr}; size_t seg_plan_n[MAX_SETS] = {0, 0, 0};
+
     // captured per-window step (mocha_step_graph): one executable graph, re-captured when its key changes
+    struct StepKey {
+        const void *x = nullptr, *mean = nullptr, *sd = nullptr; void *y = nullptr, *idx = nullptr; const void* seg = nullptr;
+        int windows = 1; bool raw = false;
+        bool operator==(const StepKey& o) const {
+            return x == o.x && mean == o.mean && sd == o.sd && y == o.y && idx == o.idx && seg == o.seg && windows == o.windows && raw == o.raw;
+        }
+    };
     struct StepGraph {
         hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr;
-        const void *x = nullptr, *mean = nullptr, *sd = nullptr; void *y = nullptr, *idx = nullptr;
-        int64_t generation = -1; bool raw = false;
-    } step[MAX_SETS];
+        StepKey key; int64_t generation = -1;
+    } step[MAX_SETS], seg_step;                       // seg_step: mocha_step_graph_segmented (workspace set 0)
     hipStream_t cap_stream = nullptr;                 // capture happens on this internal stream (the caller's may be the null stream)
     ncclComm_t comm = nullptr; int comm_rank = 0, comm_size = 1;      // mocha_comm_init
     long long* bcast_hdr = nullptr;                                     // device: {entries, bf16?} header of mocha_bank_broadcast
@@ -1279,12 +1295,56 @@ int do_match(mocha_ctx* c, const float* qnm, int Q, int32_t* idx, float* dist, h
     return 0;
 }
 
+// Scratch of the segmented matcher in workspace set `set` for launches of up to c->seg_q queries against the current table (mocha_bank_set_segments
+// sizes it for every set that exists, so that no segmented call allocates)
+int ensure_seg_scratch(mocha_ctx* c, int set) {
+    const int S = (int)c->seg_start.size() - 1;
+    const size_t need_p = match_seg_scratch_words(c->seg_q, c->seg_max_rows), need_l = seg_plan_ints(c->seg_q, S);
+    if (c->seg_partial_n[set] < need_p) {
+        HIPCHK(c, hipDeviceSynchronize());
+        dev_free(c, reinterpret_cast<float*>(c->seg_partial[set])); c->seg_partial[set] = nullptr; c->seg_partial_n[set] = 0;
+        float* p = nullptr; int rc;
+        if ((rc = dev_alloc(c, &p, 2 * need_p))) return rc;
+        c->seg_partial[set] = reinterpret_cast<unsigned long long*>(p); c->seg_partial_n[set] = need_p;
+        c->generation++;
+    }
+    if (c->seg_plan_n[set] < need_l) {
+        HIPCHK(c, hipDeviceSynchronize());
+        dev_free(c, reinterpret_cast<float*>(c->seg_plan[set])); c->seg_plan[set] = nullptr; c->seg_plan_n[set] = 0;
+        float* p = nullptr; int rc;
+        if ((rc = dev_alloc(c, &p, need_l))) return rc;
+        c->seg_plan[set] = reinterpret_cast<int*>(p); c->seg_plan_n[set] = need_l;
+        c->generation++;
+    }
+    return 0;
+}
+
+// Exact 1-NN of every query within its own segment (match_segmented.hip), in launches of up to c->seg_q queries.  q: the z-scored queries
+// (fp32 bank) or the queries minus the union's centroid (bf16 bank).  idx: local rows (or null), gidx: global rows (or null).
+int seg_match(mocha_ctx* c, const float* q, int Q, const int32_t* seg, int32_t* idx, int32_t* gidx, float* dist, hipStream_t s) {
+    if (c->seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    const int set = c->cur, S = (int)c->seg_start.size() - 1;
+    const int D = 90 * 256;
+    if (!c->seg_partial[set] || !c->seg_plan[set])
+        return fail(c, MOCHA_ERR_STATE, "workspace set %d has no segmented-match scratch: call mocha_bank_set_segments after changing the workspaces", set);
+    const void* bank = c->bank_is_bf16 ? (const void*)c->bank_bf16 : (const void*)c->bank_cnt;
+    for (int q0 = 0; q0 < Q; q0 += c->seg_q) {
+        const int n = std::min(c->seg_q, Q - q0);
+        LAUNCH(c, s, c->bank_is_bf16 ? "mocha_match_seg_scan<bf16>" : "mocha_match_seg_scan<f32>", "match.segmented", 3.0 * n * c->seg_max_rows * D,
+               (double)n * c->seg_max_rows * D * (c->bank_is_bf16 ? 2.0 : 4.0) + 4.0 * n * D,
+               launch_match_segmented(bank, c->bank_is_bf16 ? 1 : 0, q + (size_t)q0 * D, seg + q0, n, c->seg_dev, S, c->seg_max_rows, D,
+                                      c->seg_partial[set], c->seg_plan[set], idx ? idx + q0 : nullptr, gidx ? gidx + q0 : nullptr,
+                                      dist ? dist + q0 : nullptr, s));
+    }
+    return 0;
+}
+
 }  // namespace
 
 // =========================================================================================== C ABI
 extern "C" {
 
-int mocha_abi_version(void) { return 5; }
+int mocha_abi_version(void) { return 6; }
 
 #define MOCHA_STR2(x) #x
 #define MOCHA_STR(x) MOCHA_STR2(x)
@@ -1359,9 +1419,9 @@ void mocha_destroy(mocha_ctx* c) {
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->bone_parents) (void)hipFree(c->bone_parents);
-    for (auto& g : c->step) {
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        if (g.graph) (void)hipGraphDestroy(g.graph);
+    for (auto* g : {&c->step[0], &c->step[1], &c->step[2], &c->seg_step}) {
+        if (g->exec) (void)hipGraphExecDestroy(g->exec);
+        if (g->graph) (void)hipGraphDestroy(g->graph);
     }
     if (c->cap_stream) (void)hipStreamDestroy(c->cap_stream);
     (void)mocha_comm_destroy(c);
@@ -1776,6 +1836,7 @@ static int bank_set_impl(mocha_ctx* c, const float* cnt_nm, const float* encoded
     }
     c->bank_N = N;
     c->bank_is_bf16 = (flags & MOCHA_BANK_BF16) != 0;
+    if (current) { c->seg_start.clear(); c->seg_max_rows = 0; }      // a plain bank has no segment table (mocha_bank_set_segments sets it after)
     c->bank_tiled_valid = false; c->bank_tile32_valid = false;
     if (current) c->generation++;                         // a captured step has the previous bank's pointers and row count baked in
     // match scratch for every query count the workspace admits: a later match never allocates (capture-safe)
@@ -1855,7 +1916,7 @@ static int bank_set_impl(mocha_ctx* c, const float* cnt_nm, const float* encoded
     // decoder constants of every entry (round 5): IN(entry) and its AdaIN gamma / beta, read in place through frame_index by the decoder
     if (current) {
         c->bank_dec_valid = false;
-        if (dec_cache_ok(c)) {
+        if (dec_cache_ok(c) && !(flags & MOCHA_BANK_NO_DEC_CACHE)) {
             const int L = c->cfg.dec_depth;
             if (c->bank_dec_cap < (size_t)N) {
                 for (float** p : {&c->bank_kin, &c->bank_gb})
@@ -1967,10 +2028,13 @@ int mocha_bank_gather(mocha_ctx* c, const int32_t* idx, int Q, float* out, void*
     return 0;
 }
 
+// seg != null (mocha_characterize_segmented): every window is matched within its own segment of a multi-character bank; idx then receives
+// the local rows and the decoder gathers through the global rows the matcher leaves in the workspace's index buffer
 static int characterize_impl(mocha_ctx* c, const float* src_X, int B, const float* cnt_mean, const float* cnt_std, float* Y,
-                             int32_t* idx, void* stream, bool raw) {
+                             int32_t* idx, void* stream, bool raw, const int32_t* seg = nullptr) {
     int rc = ready(c, B); if (rc) return rc;
     if (!c->bank_cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
+    if (seg && c->seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
     if (B == 0) return 0;
     if (!cnt_mean || !cnt_std || !src_X || !Y) return fail(c, MOCHA_ERR_ARG, "null argument");
     const size_t ys = (size_t)60 * c->cfg.V * c->cfg.C_in;
@@ -1980,6 +2044,17 @@ static int characterize_impl(mocha_ctx* c, const float* src_X, int B, const floa
         int32_t* ix = idx ? idx + b0 : c->idx_ws[c->cur];
         if ((r = run_embed(c, src_X + b0 * xs, b, WS(c, "x5"), true, s, raw))) return r;
         if ((r = run_encoder(c, WS(c, "x5"), b, WS(c, "enc_s"), s))) return r;
+        if (seg) {
+            // cnt and its z-score (and, bf16 bank, the queries centred on the union's centroid), the segmented matcher, the decoder on the global rows
+            InormExtra ex = IEX(c);
+            if (c->bank_is_bf16) { ex.centre = c->bank_center; ex.zc = WS(c, "qc"); }
+            LAUNCH(c, s, "mocha_instnorm", "mvn", 0.0, b * 90.0 * 256 * 4 * (c->bank_is_bf16 ? 3.0 : 2.0), launch_instnorm(WS(c, "enc_s"), nullptr, nullptr, cnt_mean, cnt_std, WS(c, "qnm"), b, 90, s, &ex));
+            int32_t* gx = c->idx_ws[c->cur];
+            if ((r = seg_match(c, WS(c, c->bank_is_bf16 ? "qc" : "qnm"), b, seg + b0, idx ? idx + b0 : nullptr, gx, nullptr, s))) return r;
+            if ((r = run_decoder(c, WS(c, "enc_s"), nullptr, b, WS(c, "dec"), s, c->bank_enc, gx, c->bank_N,
+                                 c->bank_dec_valid ? c->bank_kin : nullptr, c->bank_dec_valid ? c->bank_gb : nullptr))) return r;
+            return run_to_mot(c, WS(c, "dec"), b, Y + b0 * ys, s, raw);
+        }
         // cnt, its z-score and - the bank's centroid is known - the matcher's centred queries in one pass
         // (as one bf16 plane where the many-query pass against a bf16 bank will read them: no mocha_center_bf16 launch)
         const bool q16 = c->bank_is_bf16 && b > 8;
@@ -2102,30 +2177,22 @@ int mocha_characterize_pair_raw(mocha_ctx* c, const float* src_X_raw, int B_src,
 // BASELINE configs[4]: a clip streamed one 60-frame window per step.  The whole step (mot_embedding, +pos_emb, encoder, cnt,
 // z-score, bank scan, gather, decoder, to_mot: test_fullframework.py:438-443, 465-467) is captured once into a HIP graph and
 // replayed; the graph is keyed on the buffer pointers and on the context generation, and re-captured when either changes.
-int mocha_step_graph_lane(mocha_ctx* c, int lane, const float* X1, const float* cnt_mean, const float* cnt_std, float* Y1, int32_t* idx,
-                          int raw, void* stream) {
-    if (!c) return MOCHA_ERR_ARG;
-    if (lane < 0 || lane >= c->lanes) return fail(c, MOCHA_ERR_ARG, "lane %d: the context has %d lane(s) (mocha_set_option \"lanes\")", lane, c->lanes);
-    int rc = ready(c, 1); if (rc) return rc;
-    if (!X1 || !cnt_mean || !cnt_std || !Y1 || !idx) return fail(c, MOCHA_ERR_ARG, "null argument");
-    if (!c->bank_cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
-    if (c->wss[lane].empty()) return fail(c, MOCHA_ERR_STATE, "lane %d has no workspace", lane);
-    hipStream_t s = (hipStream_t)stream;
-    auto& g = c->step[lane];
-    const bool hit = g.exec && g.x == X1 && g.mean == cnt_mean && g.sd == cnt_std && g.y == Y1 && g.idx == idx &&
-                     g.generation == c->generation && g.raw == (raw != 0);
+}  // extern "C"
+
+namespace {
+// Replay `g`, capturing it first when its key or the context generation changed: `body(stream)` enqueues the step's launches on the capture
+// stream (mocha_step_graph_lane, mocha_step_graph_segmented).  The caller made sure that nothing inside `body` allocates.
+template <class F>
+int step_replay(mocha_ctx* c, mocha_ctx::StepGraph& g, const mocha_ctx::StepKey& key, hipStream_t s, F&& body) {
+    const bool hit = g.exec && g.key == key && g.generation == c->generation;
     if (!hit) {
         if (c->prof_on) return fail(c, MOCHA_ERR_STATE, "mocha_step_graph: stop profiling before capturing");
-        // make sure nothing inside the captured region allocates (scratch for one query against the current bank)
-        if ((rc = ensure_match_scratch(c, lane, 8, c->bank_N, true))) return rc;
         if (!c->cap_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking));
         if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
         if (g.graph) { (void)hipGraphDestroy(g.graph); g.graph = nullptr; }
         const int64_t gen0 = c->generation;
         HIPCHK(c, hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeRelaxed));
-        c->lane = lane;                                   // the step's kernels use this lane's workspace set and match scratch
-        rc = characterize_impl(c, X1, 1, cnt_mean, cnt_std, Y1, idx, c->cap_stream, raw != 0);
-        c->lane = 0; c->cur = 0;
+        int rc = body(c->cap_stream);
         hipGraph_t graph = nullptr;
         const hipError_t ee = hipStreamEndCapture(c->cap_stream, &graph);
         if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
@@ -2134,16 +2201,127 @@ int mocha_step_graph_lane(mocha_ctx* c, int lane, const float* X1, const float* 
         hipGraphExec_t exec = nullptr;
         const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
         if (ei != hipSuccess) { (void)hipGraphDestroy(graph); return fail(c, MOCHA_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ei)); }
-        g.exec = exec; g.graph = graph; g.x = X1; g.mean = cnt_mean; g.sd = cnt_std; g.y = Y1; g.idx = idx;
-        g.generation = c->generation; g.raw = raw != 0;
+        g.exec = exec; g.graph = graph; g.key = key; g.generation = c->generation;
     }
     HIPCHK(c, hipGraphLaunch(g.exec, s));
     return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int mocha_step_graph_lane(mocha_ctx* c, int lane, const float* X1, const float* cnt_mean, const float* cnt_std, float* Y1, int32_t* idx,
+                          int raw, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (lane < 0 || lane >= c->lanes) return fail(c, MOCHA_ERR_ARG, "lane %d: the context has %d lane(s) (mocha_set_option \"lanes\")", lane, c->lanes);
+    int rc = ready(c, 1); if (rc) return rc;
+    if (!X1 || !cnt_mean || !cnt_std || !Y1 || !idx) return fail(c, MOCHA_ERR_ARG, "null argument");
+    if (!c->bank_cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
+    if (c->wss[lane].empty()) return fail(c, MOCHA_ERR_STATE, "lane %d has no workspace", lane);
+    mocha_ctx::StepKey key; key.x = X1; key.mean = cnt_mean; key.sd = cnt_std; key.y = Y1; key.idx = idx; key.raw = raw != 0;
+    const auto& g = c->step[lane];
+    if (!(g.exec && g.key == key && g.generation == c->generation)) {
+        // make sure nothing inside the captured region allocates (scratch for one query against the current bank)
+        if ((rc = ensure_match_scratch(c, lane, 8, c->bank_N, true))) return rc;
+    }
+    return step_replay(c, c->step[lane], key, (hipStream_t)stream, [&](hipStream_t cs) -> int {
+        c->lane = lane;                                   // the step's kernels use this lane's workspace set and match scratch
+        const int r = characterize_impl(c, X1, 1, cnt_mean, cnt_std, Y1, idx, cs, raw != 0);
+        c->lane = 0; c->cur = 0;
+        return r;
+    });
 }
 
 int mocha_step_graph(mocha_ctx* c, const float* X1, const float* cnt_mean, const float* cnt_std, float* Y1, int32_t* idx,
                      int raw, void* stream) {
     return mocha_step_graph_lane(c, 0, X1, cnt_mean, cnt_std, Y1, idx, raw, stream);
+}
+
+// ------------------------------------------------------------------------------------------- multi-character bank
+// N characters' banks as N row segments of one bank (rows z-scored with the same global cnt_mean / cnt_std); a batch names, per window,
+// the segment it is matched against (device data).  Encoding, z-score, gather, decoder and to_mot are those of mocha_characterize; only
+// the matcher is segmented (match_segmented.hip).
+int mocha_bank_set_segments(mocha_ctx* c, const float* cnt_nm, const float* encoded, int64_t N, const int64_t* seg_start, int S, int flags,
+                            void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (!seg_start || S < 1) return fail(c, MOCHA_ERR_ARG, "bank_set_segments: needs S >= 1 segments and seg_start (S + 1 entries)");
+    if (seg_start[0] != 0 || seg_start[S] != N) return fail(c, MOCHA_ERR_ARG, "bank_set_segments: seg_start must run from 0 to N = %lld", (long long)N);
+    for (int i = 0; i < S; ++i)
+        if (seg_start[i + 1] <= seg_start[i]) return fail(c, MOCHA_ERR_ARG, "bank_set_segments: segment %d is empty or seg_start decreases", i);
+    int rc = bank_set_impl(c, cnt_nm, encoded, N, flags, stream, true);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    rc = [&]() -> int {
+        int64_t mx = 0;
+        std::vector<int> dev32(S + 1);
+        for (int i = 0; i <= S; ++i) dev32[i] = (int)seg_start[i];
+        for (int i = 0; i < S; ++i) mx = std::max<int64_t>(mx, seg_start[i + 1] - seg_start[i]);
+        if (c->seg_dev_cap < (size_t)S + 1) {
+            HIPCHK(c, hipDeviceSynchronize());
+            dev_free(c, reinterpret_cast<float*>(c->seg_dev)); c->seg_dev = nullptr; c->seg_dev_cap = 0;
+            float* p = nullptr; int r;
+            if ((r = dev_alloc(c, &p, (size_t)S + 1))) return r;
+            c->seg_dev = reinterpret_cast<int*>(p); c->seg_dev_cap = (size_t)S + 1;
+        }
+        HIPCHK(c, hipMemcpyAsync(c->seg_dev, dev32.data(), sizeof(int) * (S + 1), hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipStreamSynchronize(s));                  // (the host vector goes out of scope)
+        c->seg_start.assign(seg_start, seg_start + S + 1);
+        c->seg_max_rows = mx;
+        // launches of up to seg_q queries: the workspace's windows, and at least the 16 windows of mocha_step_graph_segmented
+        c->seg_q = std::min(SEG_MAX_Q, std::max(set_windows(c, 0), 16));
+        for (int set = 0; set < mocha_ctx::MAX_SETS; ++set) {
+            int r;
+            if ((set == 0 || !c->wss[set].empty()) && (r = ensure_seg_scratch(c, set))) return r;
+        }
+        return 0;
+    }();
+    if (rc) { c->seg_start.clear(); c->seg_max_rows = 0; }
+    return rc;
+}
+
+int mocha_match_segmented(mocha_ctx* c, const float* query_nm, int Q, const int32_t* seg, int32_t* idx, float* dist, void* stream) {
+    int rc = ready(c, 0); if (rc) return rc;
+    if (!query_nm || !seg || !idx || Q < 0) return fail(c, MOCHA_ERR_ARG, "bad match_segmented arguments");
+    if (c->seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (Q == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int D = 90 * 256;
+    c->cur = 0;
+    if (!c->bank_is_bf16) return seg_match(c, query_nm, Q, seg, idx, nullptr, dist, s);
+    // the bf16 copy holds bf16(b - centroid of the union): centred queries, as many at a time as the centred-query buffer holds
+    const int per = (int)std::min<size_t>((size_t)c->seg_q, c->match_qc[0].n / D);
+    for (int q0 = 0; q0 < Q; q0 += per) {
+        const int n = std::min(per, Q - q0);
+        LAUNCH(c, s, "mocha_sub_rows", "match.center", 0.0, 8.0 * n * D, launch_sub_rows(query_nm + (size_t)q0 * D, c->bank_center, c->match_qc[0].p, n, D, s));
+        if ((rc = seg_match(c, c->match_qc[0].p, n, seg + q0, idx + q0, nullptr, dist ? dist + q0 : nullptr, s))) return rc;
+    }
+    return 0;
+}
+
+int mocha_characterize_segmented(mocha_ctx* c, const float* src_X, int B, const int32_t* seg, const float* cnt_mean, const float* cnt_std,
+                                 float* Y, int32_t* idx, int raw, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (B > 0 && !seg) return fail(c, MOCHA_ERR_ARG, "characterize_segmented: null argument");
+    return characterize_impl(c, src_X, B, cnt_mean, cnt_std, Y, idx, stream, raw != 0, seg);
+}
+
+int mocha_step_graph_segmented(mocha_ctx* c, const float* X, int S_w, const int32_t* seg, const float* cnt_mean, const float* cnt_std, float* Y,
+                               int32_t* idx, int raw, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (S_w < 1 || S_w > 16) return fail(c, MOCHA_ERR_ARG, "step_graph_segmented: 1 <= S_w <= 16 windows");
+    int rc = ready(c, S_w); if (rc) return rc;
+    if (!X || !seg || !cnt_mean || !cnt_std || !Y || !idx) return fail(c, MOCHA_ERR_ARG, "null argument");
+    if (!c->bank_cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
+    if (c->seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    mocha_ctx::StepKey key; key.x = X; key.mean = cnt_mean; key.sd = cnt_std; key.y = Y; key.idx = idx; key.seg = seg; key.windows = S_w;
+    key.raw = raw != 0;
+    // the ids are read by the captured kernels on every replay: new ids in `seg` are not part of the key
+    return step_replay(c, c->seg_step, key, (hipStream_t)stream, [&](hipStream_t cs) -> int {
+        c->lane = 0;
+        const int r = characterize_impl(c, X, S_w, cnt_mean, cnt_std, Y, idx, cs, raw != 0, seg);
+        c->cur = 0;
+        return r;
+    });
 }
 
 // ------------------------------------------------------------------------------------------- RCCL (multi-GPU set-up)
