@@ -3,6 +3,7 @@
 // caller's stream.  Reference citations are relative to the reference repository root.
 #include "../../include/mocha_hip.h"
 #include "kernels.h"
+#include "host_buffer.h"
 
 #include <rccl/rccl.h>      // types only: the RCCL entry points are resolved at run time (see Rccl below)
 #include <dlfcn.h>
@@ -92,9 +93,64 @@ static bool make_skeleton(int layout, Skeleton& sk) {
     return true;
 }
 
-struct DevBuf {
-    float* p = nullptr;
-    size_t n = 0;
+// Scratch of workspace set k: the named workspaces of ensure_ws, the matchers' scratch (ensure_match_scratch, ensure_seg_scratch) and the
+// two-plane fp16 engine's "output pointer -> its bound slot" notes
+struct SetScratch {
+    std::map<std::string, DeviceBuffer<float>> ws;
+    DeviceBuffer<int32_t> idx_ws;                              // one index per window of the set: replaced with the workspaces (ensure_ws)
+    DeviceBuffer<float> match_S{BUF_MOVES_GENERATION};         // the many-query GEMM's score slabs
+    DeviceBuffer<float> match_qc{BUF_MOVES_GENERATION};        // queries minus the centroid
+    DeviceBuffer<float> match_qstat{BUF_MOVES_GENERATION};     // row statistics of the round-4 selection (see select2 below)
+    DeviceBuffer<unsigned long long> best_ws{BUF_MOVES_GENERATION};                    // the streaming scan's partial minima
+    // every row's coarse key of 8 queries behind a head (slice winners, arrival tickets of mocha_match_refine) that starts at zero; the
+    // tickets only ever count up
+    DeviceBuffer<unsigned long long> scan_keys{BUF_MOVES_GENERATION | BUF_ZEROED};
+    DeviceBuffer<unsigned> fold_tickets{BUF_MOVES_GENERATION | BUF_ZEROED};            // option "match_fold": arrival tickets per score tile
+    // the segmented matcher's partial minima and plan for up to seg_q queries per launch (sized at mocha_bank_set_segments: the
+    // segmented calls never allocate)
+    DeviceBuffer<unsigned long long> seg_partial{BUF_MOVES_GENERATION};
+    DeviceBuffer<int> seg_plan{BUF_MOVES_GENERATION};
+    const float* amax_enc_of = nullptr; float* amax_enc = nullptr;     // encoder output pointer -> its slot
+    const float* amax_dec_of = nullptr; float* amax_dec = nullptr;     // decoder output pointer -> its slot
+    const float* amax_tok_of = nullptr; float* amax_tok = nullptr;     // embedding output pointer -> its slot
+};
+
+// A character bank and everything mocha_bank_set derives from it.  The context keeps two: `bank`, the user's current bank, and `pair`,
+// the transient bank of mocha_characterize_pair (centroid, row norms and plane image only).  None of these buffers moves the generation
+// on its own: setting the current bank does.
+struct Bank {
+    const float* cnt = nullptr;                        // the rows matched against / the rows the decoder gathers: the caller's memory
+    const float* enc = nullptr;                        // (MOCHA_BANK_BORROW, never freed here) or the owned copies below
+    int64_t N = 0;
+    DeviceBuffer<float> cnt_own, enc_own;
+    bool is_bf16 = false;
+    DeviceBuffer<float> norm;
+    DeviceBuffer<float> center;                        // centroid of the bank (90*256), see do_match
+    DeviceBuffer<unsigned short> bf16;                 // MOCHA_BANK_BF16: bf16(row - centroid)
+    // the bf16 bank once more as the many-query coarse pass's own tiled image (contiguous 16 KB blocks), made at the first such match
+    DeviceBuffer<unsigned short> tiled; bool tiled_valid = false;
+    // match_pass = 2: mocha_match_pass256 reading the bank from its operand-order image (every wave-level load 1 KB contiguous), built at
+    // the first such match (+ 2 B per bank value)
+    DeviceBuffer<unsigned short> tile32; bool tile32_valid = false;
+    // fp32 banks of up to X3_BANK_MAX rows also keep the plane engine's packed image of the centred bank (many-query matching)
+    DeviceBuffer<unsigned short> x3; bool x3_valid = false;
+    // fp32 banks of at least SCAN16_MIN rows also keep their centred bf16 copy and the rounding residual's norm per row: the
+    // few-query matcher scans the copy (half the bytes) and re-ranks exactly what the rounding cannot exclude (match_stream.hip)
+    DeviceBuffer<unsigned short> b16f; DeviceBuffer<float> rho; bool b16f_valid = false;
+    // option "scan8" (default 0): the centred rows of an fp32 bank as biased bytes + per-row scale + residual bound - an adaptive 1 B / value first
+    // stage of the few-query scan (match_scan8.hip); + N x 23 040 B
+    DeviceBuffer<unsigned char> b8; DeviceBuffer<float> b8_scale, b8_rho; bool b8_valid = false;
+    // Round 5: what the decoder derives from a bank ENTRY alone - IN(cha) (the folded decoder's keys, net/transformer.py:49-56) and every
+    // layer's AdaIN gamma / beta (the style MLP of the entry's token mean, :98-107) - is computed once at mocha_bank_set, in float64 for
+    // the MLP, and read through frame_index by the decoder (adain: gb_idx, attention: kv_idx) instead of being recomputed per step from
+    // a gathered copy: + 92 KB + 4 KB per entry.  Option "bank_dec_cache" (0: recompute per call, the round-4 flow).
+    DeviceBuffer<float> kin, gb; bool dec_valid = false;
+    DeviceBuffer<float> amax; bool amax_ok = false;    // per entry: the largest magnitude of its encoded rows (two-plane fp16 engine)
+    // multi-character bank (mocha_bank_set_segments): the rows as S segments, on the host and on the device; cleared by every other way
+    // of setting the bank
+    std::vector<int64_t> seg_start;                    // S + 1 entries; empty = no table
+    int64_t seg_max_rows = 0;
+    DeviceBuffer<int> seg_dev;
 };
 
 }  // namespace
@@ -108,9 +164,7 @@ struct mocha_ctx {
     std::map<std::string, std::vector<int64_t>> expect;
     bool finalized = false;
 
-    std::vector<float*> owned;                 // every hipMalloc'ed pointer
-    std::map<std::string, float*> w;           // repacked device weights by short name
-    std::map<std::string, size_t> wsize, cwsize;   // element counts of w / cw entries (re-loading reuses the allocation)
+    std::map<std::string, DeviceBuffer<float>> w;          // repacked device weights by short name (re-loading reuses the allocation)
     // Bumped whenever a device buffer that a captured graph may have baked in is replaced (workspaces, match scratch,
     // CVAE workspace) or the current bank changes: graph holders compare mocha_generation() before replaying.
     int64_t generation = 1;
@@ -123,7 +177,7 @@ struct mocha_ctx {
     // `aux`), so that the prologue / epilogue / tail of one half's kernels overlaps the other half's MFMA phases
     // (+5..10 % measured); `cur` selects the set the pipelines below write to.
     static constexpr int MAX_SETS = 3;
-    std::map<std::string, DevBuf> wss[MAX_SETS];
+    SetScratch sets[MAX_SETS];
     int cur = 0;
     // Lanes: up to three per-window steps in flight at once (mocha_step_graph_lane; BASELINE configs[4] pipelined).  Lane k
     // owns workspace set k (sets beyond the first are sized for a handful of windows unless dual_stream needs set 1 whole) and
@@ -139,28 +193,11 @@ struct mocha_ctx {
     bool attn_kv = false;
     bool attn_kv_pairs = false;                       // ... with a six-wave workgroup per head pair instead of twelve waves per window (diagnostic)
     hipStream_t aux = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    DevBuf match_S[MAX_SETS];
-    int32_t* idx_ws[MAX_SETS] = {nullptr, nullptr, nullptr}; size_t idx_ws_n = 0;
 
-    // bank
-    const float* bank_cnt = nullptr;
-    const float* bank_enc = nullptr;
-    float* bank_cnt_own = nullptr; float* bank_enc_own = nullptr; size_t bank_cap = 0;
-    float* bank_norm = nullptr; size_t bank_norm_cap = 0;
-    float* bank_center = nullptr;                           // centroid of the matching bank (90*256), see do_match
-    float* center_scratch = nullptr;                        // fp64 partial column sums of launch_column_mean
-    DevBuf match_qc[MAX_SETS];                                     // queries minus the centroid
-    float* pair_norm = nullptr; size_t pair_norm_cap = 0;
-    float* pair_center = nullptr;                           // row norms / centroid of the transient bank of mocha_characterize_pair
-    unsigned short* pair_x3 = nullptr; size_t pair_x3_cap = 0;     // ... and its packed plane image (never the user's bank_x3)
-    int64_t bank_N = 0;
-    // Round 5: what the decoder derives from a bank ENTRY alone - IN(cha) (the folded decoder's keys, net/transformer.py:49-56) and every
-    // layer's AdaIN gamma / beta (the style MLP of the entry's token mean, :98-107) - is computed once at mocha_bank_set, in float64 for
-    // the MLP, and read through frame_index by the decoder (adain: gb_idx, attention: kv_idx) instead of being recomputed per step from
-    // a gathered copy: + 92 KB + 4 KB per entry.  Option "bank_dec_cache" (0: recompute per call, the round-4 flow).
-    bool bank_dec_cache = true;
-    float* bank_kin = nullptr; float* bank_gb = nullptr; size_t bank_dec_cap = 0; bool bank_dec_valid = false;
-    double* style_scratch = nullptr; size_t style_scratch_rows = 0;     // float64 token means + hidden activations of the style MLP, bank build
+    Bank bank, pair;                                        // the user's current bank; the transient bank of mocha_characterize_pair
+    DeviceBuffer<double> center_scratch;                    // fp64 partial column sums of launch_column_mean
+    bool bank_dec_cache = true;                             // option "bank_dec_cache": see Bank::kin
+    DeviceBuffer<double> style_scratch;                     // float64 token means + hidden activations of the style MLP, bank build
     // launch tuning, per context (round 4 kept these as process-wide globals: a second context, or another host thread, changed them underfoot)
     int inorm_split_max = 1 << 30, embed_max_wgs = 512, gemm_persistent = 768, gemm_persistent_max_n = 512; bool embed_sums = true;
     int gemm_x3r_min_n = 0;            // plane GEMM with the activations resident in registers (gemm_x3r.hip) for K = 256 launches at least this wide (0 = never); option "gemm_x3r_min_n"
@@ -168,63 +205,45 @@ struct mocha_ctx {
     bool pair_overlap = true;          // characterize_pair: the transient bank's decoder constants on the internal stream, beside the matching
     bool adain_closed = true;          // mocha_adain: qin from the first statistics in closed form (pointwise.hip); 0 = the literal two-pass order
     bool style_f64 = true;             // the style MLP in float64 (mocha_linear_f64); 0 = the fp32 GEMM engines
-    std::map<std::string, double*> w64;                     // float64 copies of the style MLP's weights
+    std::map<std::string, DeviceBuffer<double>> w64;        // float64 copies of the style MLP's weights
     // CVAE sampler (row N1): weights under "cvae.<reference key>", workspace for cvae_B conditions
     std::map<std::string, std::vector<int64_t>> cvae_expect;
     std::map<std::string, HostTensor> cvae_host;
-    std::map<std::string, float*> cw;
+    std::map<std::string, DeviceBuffer<float>> cw;
     bool cvae_ready = false;
     int cvae_depth = 2, cvae_heads = 4, cvae_nc = 180, cvae_nq = 90;
-    std::map<std::string, DevBuf> cws; int cvae_B = 0;
+    std::map<std::string, DeviceBuffer<float>> cws; int cvae_B = 0;
     // fp32 GEMMs on the bf16 matrix pipe (gemm_x3.hip): packed three-plane images of the weights, made on first use
     bool gemm_x3 = true;
     bool attn_x3 = true;               // the Generator's attention as plane products on the bf16 pipe (attention_x3.hip)
-    std::map<std::tuple<const float*, int, int>, unsigned short*> x3w;
+    std::map<std::tuple<const float*, int, int>, DeviceBuffer<unsigned short>> x3w;
     // fp32 GEMMs on the fp16 matrix pipe with two planes / three passes (gemm_h2.hip; option "gemm_f16x2", default off): packed images and
     // per-row inverse scales of the weights (made on first use), and the PER-WINDOW activation bounds the launches scale by: vectors of
     // AMAX_WIN floats in `amax` (entry w = window w of the chunk), AMAX_SLOTS per workspace set and stage (0 encoder, 1 decoder, 2 to_mot,
     // 3 embedding; a stage zeroes the slots it can take when it starts, so a later stage may read an earlier one's), `amax_ok` = the slot was
     // really written by a launch of that engine or by mocha_absmax (host-side bookkeeping)
     bool gemm_h2 = false;
-    struct H2Img { unsigned short* img; float* w_inv; };
+    struct H2Img { DeviceBuffer<unsigned short> img; DeviceBuffer<float> w_inv; };
     std::map<std::tuple<const float*, int, int>, H2Img> h2w;
     static constexpr int AMAX_SLOTS = 40, AMAX_STAGES = 4;             // stages: 0 encoder, 1 decoder, 2 to_mot, 3 embedding
     static constexpr int AMAX_USED[4] = {2 + 4 * 8, 1 + 3 * 8, 5, 5};      // slots a stage can take (depth <= 8): what its start zeroes
     static constexpr int AMAX_WIN = 4096;                             // windows per chunk the bound vectors cover (larger chunks: the option stays off for them)
-    float* amax = nullptr;                                            // MAX_SETS x AMAX_STAGES x AMAX_SLOTS vectors of AMAX_WIN floats, then amax_in
+    DeviceBuffer<float> amax{BUF_ZEROED};                                          // MAX_SETS x AMAX_STAGES x AMAX_SLOTS vectors of AMAX_WIN floats, then amax_in
     std::vector<char> amax_ok = std::vector<char>(MAX_SETS * AMAX_STAGES * AMAX_SLOTS, 0);
     int amax_stage = 0, amax_next = 0; bool amax_idle = true;
     float* amax_in = nullptr;                                         // constant vector: the bound of an instance-normalised token, (n - 1) / sqrt(n) < 9.5 for 90 tokens
-    float* amax_bank = nullptr; size_t amax_bank_cap = 0; bool amax_bank_ok = false;     // per entry of the current bank: the largest magnitude of its encoded rows (mocha_bank_set)
-    const float* amax_enc_of[MAX_SETS] = {nullptr, nullptr, nullptr}; float* amax_enc[MAX_SETS] = {nullptr, nullptr, nullptr};   // encoder output pointer -> its slot
-    const float* amax_dec_of[MAX_SETS] = {nullptr, nullptr, nullptr}; float* amax_dec[MAX_SETS] = {nullptr, nullptr, nullptr};   // decoder output pointer -> its slot
-    const float* amax_tok_of[MAX_SETS] = {nullptr, nullptr, nullptr}; float* amax_tok[MAX_SETS] = {nullptr, nullptr, nullptr};   // embedding output pointer -> its slot
     float emb_l1 = 0.f, emb_bmax = 0.f;                               // largest row L1 norm / bias magnitude of the input 1x1 conv (model.py:44): |conv(x)| <= emb_l1 max|x| + emb_bmax
     bool fold_decoder = true;          // decoder key / value projections folded into the query / output weights
     int upsample_split_min = 256;      // windows from which that conv runs as two 2-tap launches (no zero weight blocks)
     bool fold_upsample = true;         // to_mot: the k=5 temporal conv over the x4-upsampled frames as a 3-tap conv over the SOURCE frames with per-phase summed weights
     bool fold_joint = true;            // embedding joint block: gcn 1x1 conv folded into the k=5 temporal conv (one K = 960 GEMM)
-    int* bone_parents = nullptr;       // device: parents of the (V+1)-bone skeleton with the root bone in front
-    float* pose_norm = nullptr;        // [x_mean | x_std | y_mean | y_std], (V+1)*C_in each (norm.npz of the reference)
-    void* bank_bf16 = nullptr; size_t bank_bf16_cap = 0; bool bank_is_bf16 = false;
-    // the bf16 bank once more as the many-query coarse pass's own tiled image (contiguous 16 KB blocks), made at the first such match
-    void* bank_tiled = nullptr; size_t bank_tiled_cap = 0; bool bank_tiled_valid = false;
+    DeviceBuffer<int> bone_parents;    // device: parents of the (V+1)-bone skeleton with the root bone in front
+    DeviceBuffer<float> pose_norm;     // [x_mean | x_std | y_mean | y_std], (V+1)*C_in each (norm.npz of the reference)
     bool use_tiled = false;            // option "bank_tiled": -4 % on the cold pass for 2 x the bf16 copy's memory (profiles/r04/c_tiled_loader_ab.txt): off
-    // fp32 banks of up to X3_BANK_MAX rows also keep the plane engine's packed image of the centred bank (many-query matching)
-    unsigned short* bank_x3 = nullptr; size_t bank_x3_cap = 0; bool bank_x3_valid = false;
-    unsigned long long* best_ws[MAX_SETS] = {nullptr, nullptr, nullptr}; size_t best_ws_n[MAX_SETS] = {0, 0, 0};
-    unsigned long long* topk_keys = nullptr; size_t topk_keys_n = 0;       // every row's key of up to 8 queries (mocha_match_topk)
-    // fp32 banks of at least SCAN16_MIN rows also keep their centred bf16 copy and the rounding residual's norm per row: the
-    // few-query matcher scans the copy (half the bytes) and re-ranks exactly what the rounding cannot exclude (match_stream.hip)
-    bool scan16 = true;                // mocha_set_option("scan16", 0) scans the fp32 rows themselves
-    void* bank16f = nullptr; size_t bank16f_cap = 0; float* bank_rho = nullptr; size_t bank_rho_cap = 0; bool bank16f_valid = false;
-    unsigned long long* scan_keys[MAX_SETS] = {nullptr, nullptr, nullptr}; size_t scan_keys_n[MAX_SETS] = {0, 0, 0};
-    // option "scan8" (default 0): the centred rows of an fp32 bank as biased bytes + per-row scale + residual bound - an adaptive 1 B / value first
-    // stage of the few-query scan (match_scan8.hip); + N x 23 040 B
+    DeviceBuffer<unsigned long long> topk_keys{BUF_MOVES_GENERATION};      // every row's key of up to 8 queries (mocha_match_topk)
+    bool scan16 = true;                // mocha_set_option("scan16", 0) scans the fp32 rows themselves (see Bank::b16f)
     bool match_fold = false;           // option "match_fold": the bf16 coarse pass's last K-slab workgroup per tile sums the slabs; the selection reads one (round 6 experiment)
-    unsigned* fold_tickets[MAX_SETS] = {nullptr, nullptr, nullptr}; size_t fold_tickets_n[MAX_SETS] = {0, 0, 0};
-    bool scan8 = false;
-    void* bank8 = nullptr; size_t bank8_cap = 0; float* bank8_scale = nullptr; float* bank8_rho = nullptr; bool bank8_valid = false;
+    bool scan8 = false;                // see Bank::b8
     // many-query matching, round 4 (match_select2.hip): the producer of the centred queries hands over the row statistics of the selection's
     // error bound (match_qstat: ||q - c||^2 and the planes' residual per query), the bf16 coarse pass takes two query planes
     // Used for fp32 banks (demo pair 585 x 585: centre + select 44 us against 68; 128 x 4096: 23 against 30).  bf16 banks stay on
@@ -237,21 +256,9 @@ struct mocha_ctx {
     // round 5: the one-plane coarse pass as mocha_match_pass256 (match_pass.hip: 256-row tiles, bank operands straight into registers) for
     // up to match_pass_max_q queries; 0 = round 4's mocha_match_gemm_bf16_dma.  match_pass_variant: launch_match_pass256's variant bits.
     int match_pass = 0, match_pass_variant = 0, match_pass_max_q = 256;
-    // match_pass = 2: mocha_match_pass256 reading the bank from its operand-order image (every wave-level load 1 KB contiguous), built at
-    // the first such match (+ 2 B per bank value); match_nt: round 4's kernel with non-temporal bank loads
-    void* bank_tile32 = nullptr; size_t bank_tile32_cap = 0; bool bank_tile32_valid = false;
+    // match_pass = 2: the pass reads the bank from Bank::tile32; match_nt: round 4's kernel with non-temporal bank loads
     int match_nt = 1;                  // applied to launches with ONE query tile (Q <= 128): the bank is then read exactly once per launch
-    DevBuf match_qstat[MAX_SETS];
-
-    // multi-character bank (mocha_bank_set_segments): the current bank's rows as S segments, on the host and on the device; cleared by
-    // every other way of setting the bank.  Per workspace set: the segmented matcher's partial minima and plan for up to seg_q queries
-    // per launch (sized at mocha_bank_set_segments: the segmented calls never allocate)
-    std::vector<int64_t> seg_start;                   // S + 1 entries; empty = no table
-    int64_t seg_max_rows = 0;
-    int* seg_dev = nullptr; size_t seg_dev_cap = 0;
-    int seg_q = 0;
-    unsigned long long* seg_partial[MAX_SETS] = {nullptr, nullptr, nullptr}; size_t seg_partial_n[MAX_SETS] = {0, 0, 0};
-    int* seg_plan[MAX_SETS] = {nullptr, nullptr, nullptr}; size_t seg_plan_n[MAX_SETS] = {0, 0, 0};
+    int seg_q = 0;                     // queries per launch of the segmented matcher (mocha_bank_set_segments)
 
     // captured per-window step (mocha_step_graph): one executable graph, re-captured when its key changes
     struct StepKey {
@@ -267,7 +274,7 @@ struct mocha_ctx {
     } step[MAX_SETS], seg_step;                       // seg_step: mocha_step_graph_segmented (workspace set 0)
     hipStream_t cap_stream = nullptr;                 // capture happens on this internal stream (the caller's may be the null stream)
     ncclComm_t comm = nullptr; int comm_rank = 0, comm_size = 1;      // mocha_comm_init
-    long long* bcast_hdr = nullptr;                                     // device: {entries, bf16?} header of mocha_bank_broadcast
+    DeviceBuffer<long long> bcast_hdr;                                  // device: {entries, bf16?} header of mocha_bank_broadcast
 
     // per-launch HIP-event profiling (mocha_profile_start/stop); off in normal operation
     struct ProfRec { std::string kernel, site; hipEvent_t e0, e1; double flops, bytes; };
@@ -291,37 +298,28 @@ int fail(mocha_ctx* c, int code, const char* fmt, ...) {
             return fail((c), MOCHA_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
     } while (0)
 
-int dev_alloc(mocha_ctx* c, float** out, size_t nfloats) {
-    void* p = nullptr;
-    HIPCHK(c, hipMalloc(&p, std::max<size_t>(nfloats, 4) * sizeof(float)));
-    *out = (float*)p;
-    c->owned.push_back((float*)p);
+// Room for `need` elements in a context buffer (grow-only, no-op when they fit: DeviceBuffer::reserve); a new allocation moves the
+// generation where the buffer's declaration says so
+template <class T>
+int reserve(mocha_ctx* c, DeviceBuffer<T>& b, size_t need) {
+    bool grew = false;
+    HIPCHK(c, b.reserve(need, &grew));
+    if (grew && (b.policy & BUF_MOVES_GENERATION)) c->generation++;
     return 0;
-}
-
-void dev_free(mocha_ctx* c, float* p) {
-    if (!p) return;
-    (void)hipFree(p);
-    c->owned.erase(std::remove(c->owned.begin(), c->owned.end(), p), c->owned.end());
 }
 
 // host -> device copy of one named tensor; a re-load (second load_state_dict on the same context) reuses the
 // existing allocation when the size is unchanged and frees it otherwise, so repeated loads do not leak
-int upload_to(mocha_ctx* c, std::map<std::string, float*>& tab, std::map<std::string, size_t>& sizes, const std::string& name,
-              const std::vector<float>& v) {
-    float* d = nullptr;
-    auto it = tab.find(name);
-    if (it != tab.end() && sizes[name] == v.size()) d = it->second;
-    else {
-        if (it != tab.end()) { HIPCHK(c, hipDeviceSynchronize()); dev_free(c, it->second); tab.erase(it); }
-        int rc = dev_alloc(c, &d, v.size());
-        if (rc) return rc;
-    }
-    HIPCHK(c, hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
-    tab[name] = d; sizes[name] = v.size();
+template <class T>
+int upload_to(mocha_ctx* c, std::map<std::string, DeviceBuffer<T>>& tab, const std::string& name, const std::vector<T>& v) {
+    DeviceBuffer<T>& d = tab[name];
+    if (d.n != v.size()) d.release();
+    int rc = reserve(c, d, v.size());
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpy(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return 0;
 }
-int upload(mocha_ctx* c, const std::string& name, const std::vector<float>& v) { return upload_to(c, c->w, c->wsize, name, v); }
+int upload(mocha_ctx* c, const std::string& name, const std::vector<float>& v) { return upload_to(c, c->w, name, v); }
 
 void build_expectations(mocha_ctx* c) {
     const mocha_cfg& g = c->cfg;
@@ -434,38 +432,27 @@ int ensure_ws(mocha_ctx* c, int B) {
         {"kvimg", c->attn_kv ? (size_t)ATTN_KV_IMG_BYTES / 4 : (size_t)4},
     };
     // free old workspaces
-    for (int set = 0; set < mocha_ctx::MAX_SETS; ++set) {
-        for (auto& kv : c->wss[set]) {
-            dev_free(c, kv.second.p);
-        }
-        c->wss[set].clear();
-        if (c->idx_ws[set]) { (void)hipFree(c->idx_ws[set]); c->idx_ws[set] = nullptr; }
-    }
+    for (SetScratch& st : c->sets) { st.ws.clear(); st.idx_ws.release(); }
     const bool dual_sets = c->dual_stream && want >= c->dual_min / 2;
     const int nsets = std::max(dual_sets ? 2 : 1, c->lanes);
     for (int set = 0; set < nsets; ++set) {
         // a lane's set serves per-window steps: a handful of windows; dual_stream's second set takes half of every large batch
         const int wset = (set == 0 || (set == 1 && dual_sets)) ? want : std::min(want, 8);
-        for (auto& pl : plan) {
-            DevBuf b; b.n = pl.second * (size_t)wset;
-            int rc = dev_alloc(c, &b.p, b.n);
-            if (rc) return rc;
-            c->wss[set][pl.first] = b;
-        }
-        void* ip = nullptr;
-        HIPCHK(c, hipMalloc(&ip, sizeof(int32_t) * (size_t)wset));
-        c->idx_ws[set] = (int32_t*)ip;
+        int rc;
+        for (auto& pl : plan)
+            if ((rc = reserve(c, c->sets[set].ws[pl.first], pl.second * (size_t)wset))) return rc;
+        if ((rc = reserve(c, c->sets[set].idx_ws, (size_t)wset))) return rc;
     }
-    c->idx_ws_n = want;
     c->chunk = want;
     c->dual_ready = dual_sets;
     c->generation++;
     return 0;
 }
 
-float* WS(mocha_ctx* c, const char* n) { return c->wss[c->cur].at(n).p; }
+SetScratch& SET(mocha_ctx* c) { return c->sets[c->cur]; }                // the workspace set the pipelines write to
+float* WS(mocha_ctx* c, const char* n) { return SET(c).ws.at(n).p; }
 InormExtra IEX(const mocha_ctx* c) { InormExtra e; e.split_max = c->inorm_split_max; return e; }     // the instance norm's extras with this context's launch tuning
-float* DW(mocha_ctx* c, const std::string& n) { return c->w.at(n); }
+float* DW(mocha_ctx* c, const std::string& n) { return c->w.at(n).p; }
 
 // Every kernel launch goes through LAUNCH: error check, and when profiling is on a HIP event
 // pair on the launch stream around it, tagged with the kernel symbol and the call site.
@@ -500,16 +487,15 @@ int x3_image(mocha_ctx* c, hipStream_t s, const GemmParams& p, const unsigned sh
     *out = nullptr;
     const auto key = std::make_tuple(p.W, p.N, p.K);
     auto it = c->x3w.find(key);
-    if (it != c->x3w.end()) { *out = it->second; return 0; }
+    if (it != c->x3w.end()) { *out = it->second.p; return 0; }
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &st) != hipSuccess || st != hipStreamCaptureStatusNone) return 0;
-    float* d = nullptr;
-    int rc = dev_alloc(c, &d, (gemm_x3_packed_elems(p.N, p.K) + 1) / 2);
+    DeviceBuffer<unsigned short> d;
+    int rc = reserve(c, d, gemm_x3_packed_elems(p.N, p.K));
     if (rc) return rc;
-    HIPCHK(c, launch_pack_x3(p.W, p.N, p.K, reinterpret_cast<unsigned short*>(d), s));
+    HIPCHK(c, launch_pack_x3(p.W, p.N, p.K, d.p, s));
     HIPCHK(c, hipStreamSynchronize(s));             // once per weight: the image may be read from the other stream of a dual-stream step
-    c->x3w[key] = reinterpret_cast<unsigned short*>(d);
-    *out = c->x3w[key];
+    *out = c->x3w.emplace(key, std::move(d)).first->second.p;
     return 0;
 }
 
@@ -517,42 +503,38 @@ int x3_image(mocha_ctx* c, hipStream_t s, const GemmParams& p, const unsigned sh
 // replacement like any other, so the generation moves and every holder re-captures.
 void x3_drop_images(mocha_ctx* c) {
     if (!c->x3w.empty()) c->generation++;
-    for (auto& kv : c->x3w) dev_free(c, reinterpret_cast<float*>(kv.second));
     c->x3w.clear();
 }
 
 // packed two-plane fp16 image + per-row inverse scales of (W, N, K) for gemm_h2.hip; made on first use like x3_image
-int h2_image(mocha_ctx* c, hipStream_t s, const GemmParams& p, mocha_ctx::H2Img* out) {
-    *out = mocha_ctx::H2Img{nullptr, nullptr};
+int h2_image(mocha_ctx* c, hipStream_t s, const GemmParams& p, const mocha_ctx::H2Img** out) {
+    *out = nullptr;
     const auto key = std::make_tuple(p.W, p.N, p.K);
     auto it = c->h2w.find(key);
-    if (it != c->h2w.end()) { *out = it->second; return 0; }
+    if (it != c->h2w.end()) { *out = &it->second; return 0; }
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &st) != hipSuccess || st != hipStreamCaptureStatusNone) return 0;
-    float *d = nullptr, *wi = nullptr;
-    int rc = dev_alloc(c, &d, (gemm_h2_packed_elems(p.N, p.K) + 1) / 2);
-    if (!rc) rc = dev_alloc(c, &wi, (size_t)p.N);
+    mocha_ctx::H2Img d;
+    int rc = reserve(c, d.img, gemm_h2_packed_elems(p.N, p.K));
+    if (!rc) rc = reserve(c, d.w_inv, (size_t)p.N);
     if (rc) return rc;
-    HIPCHK(c, launch_pack_h2(p.W, p.N, p.K, reinterpret_cast<unsigned short*>(d), wi, s));
+    HIPCHK(c, launch_pack_h2(p.W, p.N, p.K, d.img.p, d.w_inv.p, s));
     HIPCHK(c, hipStreamSynchronize(s));
-    c->h2w[key] = mocha_ctx::H2Img{reinterpret_cast<unsigned short*>(d), wi};
+    *out = &c->h2w.emplace(key, std::move(d)).first->second;
     c->generation++;            // a step graph captured before this image existed took the three-plane kernels for this weight: its holder re-captures
-    *out = c->h2w[key];
     return 0;
 }
 void h2_drop_images(mocha_ctx* c) {
     if (!c->h2w.empty()) c->generation++;
-    for (auto& kv : c->h2w) { dev_free(c, reinterpret_cast<float*>(kv.second.img)); dev_free(c, kv.second.w_inv); }
     c->h2w.clear();
 }
 // activation bounds of the two-plane fp16 engine (see mocha_ctx::amax): a stage's slots are zeroed when the stage starts
 int amax_alloc(mocha_ctx* c) {                                       // once, when the option is switched on (never inside a capture)
-    if (c->amax) return 0;
+    if (c->amax.p) return 0;
     const size_t n = (size_t)mocha_ctx::MAX_SETS * mocha_ctx::AMAX_STAGES * mocha_ctx::AMAX_SLOTS;
-    int rc = dev_alloc(c, &c->amax, (n + 1) * mocha_ctx::AMAX_WIN);
+    int rc = reserve(c, c->amax, (n + 1) * mocha_ctx::AMAX_WIN);       // (zeroed)
     if (rc) return rc;
-    c->amax_in = c->amax + n * mocha_ctx::AMAX_WIN;
-    HIPCHK(c, hipMemset(c->amax, 0, n * mocha_ctx::AMAX_WIN * sizeof(float)));
+    c->amax_in = c->amax.p + n * mocha_ctx::AMAX_WIN;
     const std::vector<float> k(mocha_ctx::AMAX_WIN, 9.5f);
     HIPCHK(c, hipMemcpy(c->amax_in, k.data(), k.size() * sizeof(float), hipMemcpyHostToDevice));
     return 0;
@@ -560,27 +542,27 @@ int amax_alloc(mocha_ctx* c) {                                       // once, wh
 // b: windows of this chunk - up to 4 every GEMM of the path runs on the few-rows kernels (gemm_is_skinny), which neither read nor leave
 // bounds: the stage then hands out no slots (no memset / absmax launches in the streamed per-window step)
 int amax_begin(mocha_ctx* c, int stage, hipStream_t s, int b) {
-    c->amax_idle = !c->gemm_h2 || !c->amax || b < 5 || b > mocha_ctx::AMAX_WIN;
+    c->amax_idle = !c->gemm_h2 || !c->amax.p || b < 5 || b > mocha_ctx::AMAX_WIN;
     if (c->amax_idle) return 0;
     c->amax_stage = stage; c->amax_next = 0;
     const size_t base = ((size_t)c->cur * mocha_ctx::AMAX_STAGES + stage) * mocha_ctx::AMAX_SLOTS;
     std::fill(c->amax_ok.begin() + base, c->amax_ok.begin() + base + mocha_ctx::AMAX_SLOTS, 0);
     // the first b entries of every slot the stage can take: one strided memset
-    HIPCHK(c, hipMemset2DAsync(c->amax + base * mocha_ctx::AMAX_WIN, mocha_ctx::AMAX_WIN * sizeof(float), 0, (size_t)b * sizeof(float),
+    HIPCHK(c, hipMemset2DAsync(c->amax.p + base * mocha_ctx::AMAX_WIN, mocha_ctx::AMAX_WIN * sizeof(float), 0, (size_t)b * sizeof(float),
                                (size_t)mocha_ctx::AMAX_USED[stage], s));
     return 0;
 }
 float* amax_slot(mocha_ctx* c) {                                      // a fresh (zero) bound vector of the current stage, or null when the engine is off
-    if (c->amax_idle || !c->gemm_h2 || !c->amax || c->amax_next >= mocha_ctx::AMAX_USED[c->amax_stage]) return nullptr;
-    return c->amax + (((size_t)c->cur * mocha_ctx::AMAX_STAGES + c->amax_stage) * mocha_ctx::AMAX_SLOTS + c->amax_next++) * mocha_ctx::AMAX_WIN;
+    if (c->amax_idle || !c->gemm_h2 || !c->amax.p || c->amax_next >= mocha_ctx::AMAX_USED[c->amax_stage]) return nullptr;
+    return c->amax.p + (((size_t)c->cur * mocha_ctx::AMAX_STAGES + c->amax_stage) * mocha_ctx::AMAX_SLOTS + c->amax_next++) * mocha_ctx::AMAX_WIN;
 }
 ptrdiff_t amax_index(const mocha_ctx* c, const float* slot) {         // slot number inside the arena, or -1 (amax_in / foreign)
-    if (!c->amax || !slot || slot < c->amax) return -1;
-    const ptrdiff_t i = (slot - c->amax) / mocha_ctx::AMAX_WIN;
+    if (!c->amax.p || !slot || slot < c->amax.p) return -1;
+    const ptrdiff_t i = (slot - c->amax.p) / mocha_ctx::AMAX_WIN;
     return i < (ptrdiff_t)c->amax_ok.size() ? i : -1;
 }
 const float* amax_use(const mocha_ctx* c, const float* slot) {        // the bound if a launch wrote it (or it lies outside the arena: the caller checked), else null
-    if (!c->gemm_h2 || !slot || !c->amax) return nullptr;
+    if (!c->gemm_h2 || !slot || !c->amax.p) return nullptr;
     const ptrdiff_t i = amax_index(c, slot);
     if (i >= 0) return c->amax_ok[i] ? slot : nullptr;
     return slot;
@@ -598,11 +580,11 @@ int gemm(mocha_ctx* c, hipStream_t s, const char* site, const GemmParams& p0) {
     GemmParams p = p0; p.tile64_below = c->gemm_tile64_below; p.persistent = c->gemm_persistent; p.persistent_max_n = c->gemm_persistent_max_n;
     if (p.rows_per_win <= 0) p.rows_per_win = 90;      // rows of a launch per window: 90 tokens unless the site says otherwise (to_mot's joint rows)
     if (c->gemm_h2 && p.a_amax && gemm_h2_supports(p)) {
-        mocha_ctx::H2Img img;
+        const mocha_ctx::H2Img* img = nullptr;
         int rc = h2_image(c, s, p, &img);
         if (rc) return rc;
-        if (img.img) {
-            GemmParams q = p; q.Wh2 = img.img; q.w_inv = img.w_inv;
+        if (img) {
+            GemmParams q = p; q.Wh2 = img->img.p; q.w_inv = img->w_inv.p;
             const double fl = 2.0 * p.M * (double)p.N * p.K;
             const double by = 4.0 * ((double)p.M * p.K / (p.gather ? p.ntaps : 1) * (p.R) + (double)p.N * p.K + (double)p.M * p.N + (p.residual ? (double)p.M * p.N : 0.0));
             LAUNCH(c, s, "mocha_gemm_h2", site, fl, by, launch_gemm_h2(q, s));
@@ -658,13 +640,13 @@ int run_embed(mocha_ctx* c, const float* X, int b, float* tokens, bool add_pos, 
               const float* X2 = nullptr, int b2 = 0) {
     const int V = c->cfg.V;
     const int nn = (V + 1) * c->cfg.C_in;
-    if (raw && !c->pose_norm) return fail(c, MOCHA_ERR_STATE, "raw input needs mocha_set_pose_norm first");
+    if (raw && !c->pose_norm.p) return fail(c, MOCHA_ERR_STATE, "raw input needs mocha_set_pose_norm first");
     // two-plane fp16 engine (z-scored input, fused path): |u| <= |conv1(x)| <= emb_l1 max|x| + emb_bmax (LeakyReLU, the column-normalised
     // adjacency x pool mix and the 4-frame means do not raise a magnitude) - one pass over the poses gives the first launch's bound,
     // every GEMM's epilogue the next one's; the tokens' bound goes on to the encoder
     { int rc = amax_begin(c, 3, s, b + b2); if (rc) return rc; }
     float* u_amax = nullptr;
-    c->amax_tok_of[c->cur] = nullptr;
+    SET(c).amax_tok_of = nullptr;
     if (c->gemm_h2 && !c->amax_idle && !raw && c->fold_joint && c->gemm_x3 && c->embed_sums && c->emb_l1 > 0.f && (u_amax = amax_slot(c))) {
         const long long per = 60ll * V * c->cfg.C_in;
         LAUNCH(c, s, "mocha_absmax", "h2.absmax", 0.0, 4.0 * b * per, launch_absmax(X, b, per, u_amax, s, c->emb_l1, c->emb_bmax));
@@ -677,12 +659,12 @@ int run_embed(mocha_ctx* c, const float* X, int b, float* tokens, bool add_pos, 
         LAUNCH(c, s, "mocha_embed_sums_x3", "emb.front_sums", b * 60.0 * V * 64 * (2.0 * 15 + 2.0 * 18) + b * 90.0 * 960 * 4,
                b * 4.0 * (60.0 * V * 15 + 90.0 * 960),
                launch_embed_sums(X, DW(c, "emb.W1"), DW(c, "emb.b1"), DW(c, "AP"), WS(c, "u"), b, V, c->cfg.C_in,
-                                 raw ? c->pose_norm : nullptr, raw ? c->pose_norm + nn : nullptr, raw ? 1 : 0, s, c->embed_max_wgs));
+                                 raw ? c->pose_norm.p : nullptr, raw ? c->pose_norm.p + nn : nullptr, raw ? 1 : 0, s, c->embed_max_wgs));
         if (X2 && b2 > 0) {
             LAUNCH(c, s, "mocha_embed_sums_x3", "emb.front_sums", b2 * 60.0 * V * 64 * (2.0 * 15 + 2.0 * 18) + b2 * 90.0 * 960 * 4,
                    b2 * 4.0 * (60.0 * V * 15 + 90.0 * 960),
                    launch_embed_sums(X2, DW(c, "emb.W1"), DW(c, "emb.b1"), DW(c, "AP"), WS(c, "u") + (size_t)b * 90 * 960, b2, V, c->cfg.C_in,
-                                     raw ? c->pose_norm : nullptr, raw ? c->pose_norm + nn : nullptr, raw ? 1 : 0, s, c->embed_max_wgs));
+                                     raw ? c->pose_norm.p : nullptr, raw ? c->pose_norm.p + nn : nullptr, raw ? 1 : 0, s, c->embed_max_wgs));
             b += b2;
         }
         GemmParams gf = plain(WS(c, "u"), 960, DW(c, "emb.Wc"), WS(c, "x5"), 256, b * 90, 256, 960);
@@ -694,11 +676,11 @@ int run_embed(mocha_ctx* c, const float* X, int b, float* tokens, bool add_pos, 
     const char* efk = c->gemm_x3 ? "mocha_embed_front_x3" : "mocha_embed_front";
     LAUNCH(c, s, efk, "emb.front", b * 60.0 * V * 64 * (2.0 * 15 + 2.0 * 18), b * 60.0 * (V * 15 + 6 * 192) * 4,
            launch_embed_front(X, DW(c, "emb.W1"), DW(c, "emb.b1"), DW(c, "AP"), WS(c, "hbar"), b * 60, V, c->cfg.C_in,
-                              raw ? c->pose_norm : nullptr, raw ? c->pose_norm + nn : nullptr, raw ? 1 : 0, s, c->gemm_x3, c->embed_max_wgs));
+                              raw ? c->pose_norm.p : nullptr, raw ? c->pose_norm.p + nn : nullptr, raw ? 1 : 0, s, c->gemm_x3, c->embed_max_wgs));
     if (X2 && b2 > 0) {
         LAUNCH(c, s, efk, "emb.front", b2 * 60.0 * V * 64 * (2.0 * 15 + 2.0 * 18), b2 * 60.0 * (V * 15 + 6 * 192) * 4,
                launch_embed_front(X2, DW(c, "emb.W1"), DW(c, "emb.b1"), DW(c, "AP"), WS(c, "hbar") + (size_t)b * 360 * 192, b2 * 60, V,
-                                  c->cfg.C_in, raw ? c->pose_norm : nullptr, raw ? c->pose_norm + nn : nullptr, raw ? 1 : 0, s, c->gemm_x3, c->embed_max_wgs));
+                                  c->cfg.C_in, raw ? c->pose_norm.p : nullptr, raw ? c->pose_norm.p + nn : nullptr, raw ? 1 : 0, s, c->gemm_x3, c->embed_max_wgs));
         b += b2;
     }
     if (c->fold_joint) {
@@ -736,7 +718,7 @@ int run_embed(mocha_ctx* c, const float* X, int b, float* tokens, bool add_pos, 
     if (add_pos) { g4.rowbias = DW(c, "pos_emb"); g4.rb_mod = 90; }           // model.py:88
     g4.a_amax = amax_use(c, g3.c_amax); g4.c_amax = amax_slot(c);
     GEMM(c, s, "emb.tcn_body", g4);
-    if (amax_use(c, g4.c_amax)) { c->amax_tok_of[c->cur] = tokens; c->amax_tok[c->cur] = g4.c_amax; }
+    if (amax_use(c, g4.c_amax)) { SET(c).amax_tok_of = tokens; SET(c).amax_tok = g4.c_amax; }
     return 0;
 }
 
@@ -769,10 +751,10 @@ int run_encoder(mocha_ctx* c, const float* tokens, int b, float* encoded, hipStr
     int rc0 = amax_begin(c, 0, s, b); if (rc0) return rc0;
     float* x_amax = nullptr;
     if (c->gemm_h2 && !c->amax_idle) {
-        if (tokens == c->amax_tok_of[c->cur] && amax_use(c, c->amax_tok[c->cur])) x_amax = c->amax_tok[c->cur];      // the embedding's last GEMM left it
+        if (tokens == SET(c).amax_tok_of && amax_use(c, SET(c).amax_tok)) x_amax = SET(c).amax_tok;      // the embedding's last GEMM left it
         else { rc0 = amax_measure(c, s, tokens, b, 90ll * 256, &x_amax); if (rc0) return rc0; }
     }
-    c->amax_enc_of[c->cur] = nullptr;
+    SET(c).amax_enc_of = nullptr;
     for (int l = 0; l < c->cfg.enc_depth; ++l) {
         const std::string p = "enc" + std::to_string(l);
         GemmParams q = plain(x, 256, DW(c, p + ".Wqkv"), WS(c, "qkv"), 3 * inner, M, 3 * inner, 256);
@@ -787,7 +769,7 @@ int run_encoder(mocha_ctx* c, const float* tokens, int b, float* encoded, hipStr
         if (rc) return rc;
         x = out;
     }
-    if (amax_use(c, x_amax)) { c->amax_enc_of[c->cur] = encoded; c->amax_enc[c->cur] = x_amax; }
+    if (amax_use(c, x_amax)) { SET(c).amax_enc_of = encoded; SET(c).amax_enc = x_amax; }
     return 0;
 }
 
@@ -796,9 +778,9 @@ int run_encoder(mocha_ctx* c, const float* tokens, int b, float* encoded, hipStr
 int run_style_f64(mocha_ctx* c, const double* mean64, double* hidden, float* gb, int rows, hipStream_t s) {
     const int L = c->cfg.dec_depth;
     LAUNCH(c, s, "mocha_linear_f64", "dec.style1", 2.0 * rows * 512.0 * L * 256, rows * 8.0 * (256 + 512 * L) + 8.0 * 512 * L * 256,
-           launch_linear_f64(mean64, 256, 0, c->w64.at("dec.Ws1_all"), c->w64.at("dec.bs1_all"), hidden, nullptr, 512 * L, rows, 512 * L, 256, 1, 2, s));
+           launch_linear_f64(mean64, 256, 0, c->w64.at("dec.Ws1_all").p, c->w64.at("dec.bs1_all").p, hidden, nullptr, 512 * L, rows, 512 * L, 256, 1, 2, s));
     LAUNCH(c, s, "mocha_linear_f64", "dec.style2", 2.0 * rows * 512.0 * L * 512, rows * (8.0 + 4.0) * 512 * L + 8.0 * L * 512 * 512,
-           launch_linear_f64(hidden, 512 * L, 512, c->w64.at("dec.Ws2_all"), c->w64.at("dec.bs2_all"), nullptr, gb, 512 * L, rows, 512, 512, L, 0, s));
+           launch_linear_f64(hidden, 512 * L, 512, c->w64.at("dec.Ws2_all").p, c->w64.at("dec.bs2_all").p, nullptr, gb, 512 * L, rows, 512, 512, L, 0, s));
     return 0;
 }
 
@@ -872,8 +854,8 @@ int run_decoder(mocha_ctx* c, const float* src, const float* cha, int b, float* 
         const float* vsrc = gather_table ? gather_table : cha;
         // per source window: its matched entry's bound (gathered through the indices), or the same window's character features
         const float* table = nullptr;
-        if (vsrc && vsrc == c->bank_enc && c->amax_bank_ok) table = c->amax_bank;
-        else if (vsrc && vsrc == c->amax_enc_of[c->cur]) table = amax_use(c, c->amax_enc[c->cur]);
+        if (vsrc && vsrc == c->bank.enc && c->bank.amax_ok) table = c->bank.amax.p;
+        else if (vsrc && vsrc == SET(c).amax_enc_of) table = amax_use(c, SET(c).amax_enc);
         if (table && gather_table) {
             float* slot = amax_slot(c);
             if (slot) {
@@ -889,7 +871,7 @@ int run_decoder(mocha_ctx* c, const float* src, const float* cha, int b, float* 
         }
     }
     float* x_amax = nullptr;
-    c->amax_dec_of[c->cur] = nullptr;
+    SET(c).amax_dec_of = nullptr;
     if (!cached) {
         InormExtra ex = IEX(c);
         if (gather_table) { ex.table = gather_table; ex.row_idx = gather_idx; ex.table_rows = gather_rows; ex.copy_out = use_kv ? nullptr : WS(c, "sel"); }
@@ -932,7 +914,7 @@ int run_decoder(mocha_ctx* c, const float* src, const float* cha, int b, float* 
             float* out = (l == c->cfg.dec_depth - 1) ? outp : WS(c, "xa");
             int rc = run_out_ff(c, p, WS(c, "ao"), inner, WS(c, "xad"), M, c->cfg.dec_mlp, out, s, ".Wvo", use_kv ? nullptr : v_amax, &x_amax);
             if (rc) return rc;
-            if (l == c->cfg.dec_depth - 1 && amax_use(c, x_amax)) { c->amax_dec_of[c->cur] = outp; c->amax_dec[c->cur] = x_amax; }
+            if (l == c->cfg.dec_depth - 1 && amax_use(c, x_amax)) { SET(c).amax_dec_of = outp; SET(c).amax_dec = x_amax; }
             x = out;
             continue;
         }
@@ -957,13 +939,13 @@ int run_decoder(mocha_ctx* c, const float* src, const float* cha, int b, float* 
 int run_to_mot(mocha_ctx* c, const float* tokens, int b, float* Y, hipStream_t s, bool denorm = false) {
     const int V = c->cfg.V, M = b * 90;
     const int nn = (V + 1) * c->cfg.C_in;
-    if (denorm && !c->pose_norm) return fail(c, MOCHA_ERR_STATE, "de-normalised output needs mocha_set_pose_norm first");
+    if (denorm && !c->pose_norm.p) return fail(c, MOCHA_ERR_STATE, "de-normalised output needs mocha_set_pose_norm first");
     // two-plane fp16 engine: LeakyReLU and the column-normalised adjacency mixes (body_front, joint_expand: non-negative coefficients that sum
     // to at most one per output) do not raise the largest magnitude, so each GEMM's bound is its predecessor's output bound
     { int rc = amax_begin(c, 2, s, b); if (rc) return rc; }
     float* t_amax = nullptr;
     if (c->gemm_h2 && !c->amax_idle) {
-        if (tokens == c->amax_dec_of[c->cur] && amax_use(c, c->amax_dec[c->cur])) t_amax = c->amax_dec[c->cur];
+        if (tokens == SET(c).amax_dec_of && amax_use(c, SET(c).amax_dec)) t_amax = SET(c).amax_dec;
         else { int rc = amax_measure(c, s, tokens, b, 90ll * 256, &t_amax); if (rc) return rc; }
     }
     LAUNCH(c, s, "mocha_body_front", "mot.body_front", b * 90.0 * 512 * 12, b * 90.0 * (256 + 512) * 4, launch_body_front(tokens, DW(c, "A_b"), WS(c, "xA"), b * 15, s));
@@ -1004,7 +986,7 @@ int run_to_mot(mocha_ctx* c, const float* tokens, int b, float* Y, hipStream_t s
     GEMM(c, s, "mot.tcn_joint", g4);
     }
     LAUNCH(c, s, "mocha_final_proj", "mot.final_proj", b * 60.0 * V * 64 * 15 * 2, b * 60.0 * V * (64 + 15) * 4, launch_final_proj(WS(c, "z"), DW(c, "mot.W6"), DW(c, "mot.b6"), Y, b * 60 * V, c->cfg.C_in, V,
-                             denorm ? c->pose_norm + 2 * nn : nullptr, denorm ? c->pose_norm + 3 * nn : nullptr, s, c->fold_upsample ? 1 : 0));
+                             denorm ? c->pose_norm.p + 2 * nn : nullptr, denorm ? c->pose_norm.p + 3 * nn : nullptr, s, c->fold_upsample ? 1 : 0));
     return 0;
 }
 
@@ -1014,7 +996,7 @@ int run_to_mot(mocha_ctx* c, const float* tokens, int b, float* Y, hipStream_t s
 template <class F>
 int for_chunks(mocha_ctx* c, int B, hipStream_t s, F&& fn) {
     // set 1 must be a FULL-size set: with lanes >= 2 it exists at 8 windows whenever dual_sets was false at allocation
-    const bool dual = c->dual_stream && B >= c->dual_min && c->dual_ready && !c->wss[1].empty();
+    const bool dual = c->dual_stream && B >= c->dual_min && c->dual_ready && !c->sets[1].ws.empty();
     if (!dual) {
         c->cur = c->lane;
         for (int b0 = 0; b0 < B; b0 += c->chunk) { int rc = fn(b0, std::min(c->chunk, B - b0), s); if (rc) return rc; }
@@ -1058,18 +1040,6 @@ int ready(mocha_ctx* c, int B) {
 // sum (q-b)^2 directly.  Many queries: the GEMM runs on operands centred on the bank centroid c (distances are
 // translation invariant; the centred norms are of the size of the distances themselves) and the arg-min re-ranks its
 // four best candidates by their exact direct distances.
-int grow(mocha_ctx* c, DevBuf& b, size_t need) {
-    if (b.n >= need) return 0;
-    HIPCHK(c, hipDeviceSynchronize());
-    dev_free(c, b.p);
-    b = DevBuf{};
-    int rc = dev_alloc(c, &b.p, need);
-    if (rc) return rc;
-    b.n = need;
-    c->generation++;
-    return 0;
-}
-
 static constexpr int64_t SCAN16_MIN = 4096;        // rows from which an fp32 bank is scanned through its bf16 copy (few queries)
 static constexpr int64_t X3_BANK_MAX = 4096;       // rows: the packed image of a 4096-row bank (BASELINE configs[2]) is 566 MB
 
@@ -1087,98 +1057,84 @@ int set_windows(const mocha_ctx* c, int set) {
 // Scratch of do_match for up to Q queries against N bank rows, in workspace set `set`: centred queries, the streaming
 // scan's partial minima, the GEMM's score slabs.  mocha_reserve and mocha_bank_set call it for the workspace chunk, so
 // that a steady-state match never allocates (graph-capture safe); do_match itself calls it for exactly its Q.
-int ensure_match_scratch(mocha_ctx* c, int set, int Q, int64_t N, bool every_q_up_to) {
+int ensure_match_scratch(mocha_ctx* c, int set, int Q, const Bank& b, bool every_q_up_to) {
     const size_t D = 90 * 256;
+    const int64_t N = b.N;
+    SetScratch& st = c->sets[set];
     int rc;
-    if ((rc = grow(c, c->match_qc[set], (size_t)std::max(Q, 8) * D))) return rc;
-    const size_t need_ws = match_stream_scratch(8, N);
-    if (c->best_ws_n[set] < need_ws) {
-        HIPCHK(c, hipDeviceSynchronize());
-        if (c->best_ws[set]) (void)hipFree(c->best_ws[set]);
-        c->best_ws[set] = nullptr; c->best_ws_n[set] = 0;
-        void* bp = nullptr;
-        HIPCHK(c, hipMalloc(&bp, sizeof(unsigned long long) * need_ws));
-        c->best_ws[set] = (unsigned long long*)bp; c->best_ws_n[set] = need_ws;
-        c->generation++;
-    }
+    if ((rc = reserve(c, st.match_qc, (size_t)std::max(Q, 8) * D))) return rc;
+    if ((rc = reserve(c, st.best_ws, match_stream_scratch(8, N)))) return rc;
     if (Q > 8) {
         size_t need = 0;
         for (int q = every_q_up_to ? 9 : Q; q <= Q; ++q)
             need = std::max(need, (size_t)std::max(match_ksplit(q, N), match_pass256_ksplit(q, N)) * q * (size_t)N);
-        if ((rc = grow(c, c->match_S[set], need))) return rc;
-        if ((rc = grow(c, c->match_qstat[set], (size_t)2 * QSTAT_PARTS * std::max(Q, 256)))) return rc;
+        if ((rc = reserve(c, st.match_S, need))) return rc;
+        if ((rc = reserve(c, st.match_qstat, (size_t)2 * QSTAT_PARTS * std::max(Q, 256)))) return rc;
+        // option "match_fold": a ticket per 128 x 128 score tile of the bf16 coarse pass
+        if (c->match_fold && b.is_bf16 && (rc = reserve(c, st.fold_tickets, (size_t)((Q + 127) / 128) * (size_t)((N + 127) / 128)))) return rc;
     }
-    if (c->scan16 && !c->bank_is_bf16 && N >= SCAN16_MIN && c->scan_keys_n[set] < (size_t)8 * N) {      // every row's coarse key, 8 queries
-        HIPCHK(c, hipDeviceSynchronize());
-        if (c->scan_keys[set]) (void)hipFree(c->scan_keys[set]);
-        c->scan_keys[set] = nullptr; c->scan_keys_n[set] = 0;
-        void* kp = nullptr;
-        HIPCHK(c, hipMalloc(&kp, sizeof(unsigned long long) * match_scan16_scratch_words(N)));
-        // the head (slice winners, arrival tickets of mocha_match_refine) starts at zero; the tickets only ever count up
-        HIPCHK(c, hipMemset(kp, 0, sizeof(unsigned long long) * match_scan16_scratch_head_words()));
-        c->scan_keys[set] = (unsigned long long*)kp; c->scan_keys_n[set] = (size_t)8 * N;
-        c->generation++;
-    }
+    if (c->scan16 && !b.is_bf16 && N >= SCAN16_MIN && (rc = reserve(c, st.scan_keys, match_scan16_scratch_words(N)))) return rc;
     return 0;
 }
 
 // qc_pre: the queries minus the current bank's centroid, fp32, when the caller's producer already wrote them (mocha_instnorm's zc)
 // (fp32; bf16 where the many-query pass against a bf16 bank wants them so: qc_pre_bf16, mocha_instnorm's zc16)
 // the round-4 selection (match_select2.hip) serves this many queries against the current bank?
-bool use_select2(const mocha_ctx* c, int Q) { return c->select2 && Q > 8 && (!c->bank_is_bf16 || c->match_planes == 2); }
+bool use_select2(const mocha_ctx* c, const Bank& b, int Q) { return c->select2 && Q > 8 && (!b.is_bf16 || c->match_planes == 2); }
 
 // qstat_pre: with select2 and Q > 8, the producer also left the row statistics in match_qstat[set] (and, bf16: BOTH query planes in qc_pre)
-int do_match(mocha_ctx* c, const float* qnm, int Q, int32_t* idx, float* dist, hipStream_t s, const void* qc_pre_any = nullptr,
+int do_match(mocha_ctx* c, Bank& b, const float* qnm, int Q, int32_t* idx, float* dist, hipStream_t s, const void* qc_pre_any = nullptr,
              bool qc_pre_bf16 = false, bool qstat_pre = false) {
-    if (!c->bank_cnt || c->bank_N <= 0) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
+    if (!b.cnt || b.N <= 0) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
     const int D = 90 * 256;
-    const int64_t N = c->bank_N;
+    const int64_t N = b.N;
     const int set = c->cur;
+    SetScratch& st = c->sets[set];
     int rc;
-    if ((rc = ensure_match_scratch(c, set, Q, N, false))) return rc;
+    if ((rc = ensure_match_scratch(c, set, Q, b, false))) return rc;
     // centred queries: the bf16 bank holds bf16(b - c) and the GEMMs work on centred operands.  The many-query bf16 pass takes
     // them as bf16 (match_qc holds Q x D bf16 then), everything else as fp32.
-    const bool via16 = Q <= 8 && !c->bank_is_bf16 && c->bank16f_valid && c->scan16 && c->scan_keys_n[set] >= (size_t)8 * N;
-    const bool need_qc = c->bank_is_bf16 || Q > 8 || via16;
+    const bool via16 = Q <= 8 && !b.is_bf16 && b.b16f_valid && c->scan16 && st.scan_keys.n >= match_scan16_scratch_words(N);
+    const bool need_qc = b.is_bf16 || Q > 8 || via16;
     // the many-query pass against a bf16 bank takes the centred queries as bf16, everything else as fp32: a precomputed copy of the
     // other kind is of no use (mocha_center_bf16 / mocha_sub_rows then make the right one)
-    const bool sel2 = use_select2(c, Q);                       // many-query path with the round-4 selection: row statistics from the producer
-    const float* qc_pre = (qc_pre_any && qc_pre_bf16 == (c->bank_is_bf16 && Q > 8) && (!sel2 || qstat_pre)) ? static_cast<const float*>(qc_pre_any) : nullptr;
+    const bool sel2 = use_select2(c, b, Q);                       // many-query path with the round-4 selection: row statistics from the producer
+    const float* qc_pre = (qc_pre_any && qc_pre_bf16 == (b.is_bf16 && Q > 8) && (!sel2 || qstat_pre)) ? static_cast<const float*>(qc_pre_any) : nullptr;
     if (need_qc && !qc_pre) {
-        if (sel2 && c->bank_is_bf16)
-            LAUNCH(c, s, "mocha_center_rows", "match.center", 0.0, 8.0 * Q * D, launch_center_rows(qnm, c->bank_center, c->match_qc[set].p, c->match_planes, nullptr, c->match_qstat[set].p, Q, D, s));
+        if (sel2 && b.is_bf16)
+            LAUNCH(c, s, "mocha_center_rows", "match.center", 0.0, 8.0 * Q * D, launch_center_rows(qnm, b.center.p, st.match_qc.p, c->match_planes, nullptr, st.match_qstat.p, Q, D, s));
         else if (sel2)
-            LAUNCH(c, s, "mocha_center_rows", "match.center", 0.0, 8.0 * Q * D, launch_center_rows(qnm, c->bank_center, nullptr, 0, c->match_qc[set].p, c->match_qstat[set].p, Q, D, s));
-        else if (c->bank_is_bf16 && Q > 8)
-            LAUNCH(c, s, "mocha_center_bf16", "match.center", 0.0, 6.0 * Q * D, launch_center_bf16(qnm, c->bank_center, c->match_qc[set].p, Q, D, s));
+            LAUNCH(c, s, "mocha_center_rows", "match.center", 0.0, 8.0 * Q * D, launch_center_rows(qnm, b.center.p, nullptr, 0, st.match_qc.p, st.match_qstat.p, Q, D, s));
+        else if (b.is_bf16 && Q > 8)
+            LAUNCH(c, s, "mocha_center_bf16", "match.center", 0.0, 6.0 * Q * D, launch_center_bf16(qnm, b.center.p, st.match_qc.p, Q, D, s));
         else
-            LAUNCH(c, s, "mocha_sub_rows", "match.center", 0.0, 8.0 * Q * D, launch_sub_rows(qnm, c->bank_center, c->match_qc[set].p, Q, D, s));
+            LAUNCH(c, s, "mocha_sub_rows", "match.center", 0.0, 8.0 * Q * D, launch_sub_rows(qnm, b.center.p, st.match_qc.p, Q, D, s));
     }
-    const float* qc = need_qc ? (qc_pre ? qc_pre : c->match_qc[set].p) : nullptr;
+    const float* qc = need_qc ? (qc_pre ? qc_pre : st.match_qc.p) : nullptr;
     if (via16) {
         // fp32 bank through its centred bf16 copy: every row's coarse distance from half the bytes, then the exact fp32 distances of
         // the rows the rounding bound cannot exclude - the result of the fp32 search
-        if (c->scan8 && c->bank8_valid && Q <= 4) {
+        if (c->scan8 && b.b8_valid && Q <= 4) {
             // the adaptive byte stage: 1 B per value while the queries sit close to a few rows, the bf16 scan otherwise (decided on the device)
             LAUNCH(c, s, "mocha_match_scan_adaptive+refine", "match.stream8", 3.0 * Q * N * D, (double)N * D * 1.0 + 4.0 * Q * D + 16.0 * Q * N,
-                   launch_match_scan8(c->bank8, c->bank8_scale, c->bank8_rho, c->bank16f, c->bank_rho, c->bank_cnt, qc, qnm, Q, N, D, c->scan_keys[set], idx, dist, s));
+                   launch_match_scan8(b.b8.p, b.b8_scale.p, b.b8_rho.p, b.b16f.p, b.rho.p, b.cnt, qc, qnm, Q, N, D, st.scan_keys.p, idx, dist, s));
             return 0;
         }
         LAUNCH(c, s, "mocha_match_stream<bf16>+refine", "match.stream16", 3.0 * Q * N * D,
                ((Q + 7) / 8) * (double)N * D * 2.0 + 4.0 * Q * D + 16.0 * Q * N,
-               launch_match_scan16(c->bank16f, c->bank_rho, c->bank_cnt, qc, qnm, Q, N, D, c->scan_keys[set], idx, dist, s));
+               launch_match_scan16(b.b16f.p, b.rho.p, b.cnt, qc, qnm, Q, N, D, st.scan_keys.p, idx, dist, s));
         return 0;
     }
     if (Q <= 8) {
-        const void* bank = c->bank_is_bf16 ? (const void*)c->bank_bf16 : (const void*)c->bank_cnt;
+        const void* bank = b.is_bf16 ? (const void*)b.bf16.p : (const void*)b.cnt;
         const double passes = (Q + 7) / 8;
-        LAUNCH(c, s, c->bank_is_bf16 ? "mocha_match_stream<bf16>" : "mocha_match_stream<f32>", "match.stream", 3.0 * Q * N * D,
-               passes * N * D * (c->bank_is_bf16 ? 2.0 : 4.0) + 4.0 * Q * D,
-               launch_match_stream(bank, c->bank_is_bf16 ? 1 : 0, c->bank_is_bf16 ? qc : qnm, Q, N, D, c->best_ws[set], idx, dist, s));
+        LAUNCH(c, s, b.is_bf16 ? "mocha_match_stream<bf16>" : "mocha_match_stream<f32>", "match.stream", 3.0 * Q * N * D,
+               passes * N * D * (b.is_bf16 ? 2.0 : 4.0) + 4.0 * Q * D,
+               launch_match_stream(bank, b.is_bf16 ? 1 : 0, b.is_bf16 ? qc : qnm, Q, N, D, st.best_ws.p, idx, dist, s));
         return 0;
     }
-    DevBuf& mS = c->match_S[set];
-    if (c->bank_is_bf16) {
+    DeviceBuffer<float>& mS = st.match_S;
+    if (b.is_bf16) {
         // bf16 bank: one bf16 plane of the centred queries against the centred bf16 bank; the select kernel re-evaluates every
         // row whose coarse score is within the query rounding's error bound of the best one - 2 ||dq|| (||b|| + ||b0||) with the query's
         // measured rounding residual dq, plus 5e-5 (2||q||^2 + ||b||^2 + ||b0||^2) of slack for the pass's fp32 accumulation - exactly
@@ -1189,96 +1145,70 @@ int do_match(mocha_ctx* c, const float* qnm, int Q, int32_t* idx, float* dist, h
         const void* tiled = nullptr;
         if (c->use_tiled && (size_t)N * D * 2 <= ((size_t)4 << 30)) {          // up to 4 GB of image (N = 93 k rows)
             const size_t need = match_tiled_elems(N, D);
-            if (!c->bank_tiled_valid) {
-                if (c->bank_tiled_cap < need) {
-                    HIPCHK(c, hipDeviceSynchronize());
-                    if (c->bank_tiled) (void)hipFree(c->bank_tiled);
-                    c->bank_tiled = nullptr; c->bank_tiled_cap = 0;
-                    HIPCHK(c, hipMalloc(&c->bank_tiled, need * 2));
-                    c->bank_tiled_cap = need;
-                }
-                LAUNCH(c, s, "mocha_tile_bf16", "bank.tile", 0.0, 4.0 * N * D, launch_tile_bf16(c->bank_bf16, c->bank_tiled, N, D, s));
-                c->bank_tiled_valid = true;
+            if (!b.tiled_valid) {
+                if ((rc = reserve(c, b.tiled, need))) return rc;
+                LAUNCH(c, s, "mocha_tile_bf16", "bank.tile", 0.0, 4.0 * N * D, launch_tile_bf16(b.bf16.p, b.tiled.p, N, D, s));
+                b.tiled_valid = true;
             }
-            tiled = c->bank_tiled;
+            tiled = b.tiled.p;
         }
         if (pass256) {
             const void* t32 = nullptr;
             if (c->match_pass == 2 && (size_t)N * D * 2 <= ((size_t)4 << 30)) {
                 const size_t need = match_tile32_elems(N, D);
-                if (!c->bank_tile32_valid) {
-                    if (c->bank_tile32_cap < need) {
-                        HIPCHK(c, hipDeviceSynchronize());
-                        if (c->bank_tile32) (void)hipFree(c->bank_tile32);
-                        c->bank_tile32 = nullptr; c->bank_tile32_cap = 0;
-                        HIPCHK(c, hipMalloc(&c->bank_tile32, need * 2));
-                        c->bank_tile32_cap = need;
-                    }
-                    LAUNCH(c, s, "mocha_tile32_bf16", "bank.tile32", 0.0, 4.0 * N * D, launch_tile32_bf16(c->bank_bf16, c->bank_tile32, N, D, s));
-                    c->bank_tile32_valid = true;
+                if (!b.tile32_valid) {
+                    if ((rc = reserve(c, b.tile32, need))) return rc;
+                    LAUNCH(c, s, "mocha_tile32_bf16", "bank.tile32", 0.0, 4.0 * N * D, launch_tile32_bf16(b.bf16.p, b.tile32.p, N, D, s));
+                    b.tile32_valid = true;
                 }
-                t32 = c->bank_tile32;
+                t32 = b.tile32.p;
             }
             LAUNCH(c, s, "mocha_match_pass256", "match.qk_bf16", 2.0 * npl * Q * (double)N * D, 2.0 * npl * Q * D + 2.0 * N * D + 4.0 * Q * N * ksplit,
-                   launch_match_pass256(qc, c->bank_bf16, mS.p, Q, N, D, ksplit, s, c->match_pass_variant, npl, t32));
+                   launch_match_pass256(qc, b.bf16.p, mS.p, Q, N, D, ksplit, s, c->match_pass_variant, npl, t32));
         } else
         {
-        unsigned* tk = nullptr;
-        if (c->match_fold && ksplit > 1) {
-            const size_t need = (size_t)((Q + 127) / 128) * (size_t)((N + 127) / 128);
-            if (c->fold_tickets_n[set] < need) {
-                HIPCHK(c, hipDeviceSynchronize());
-                if (c->fold_tickets[set]) (void)hipFree(c->fold_tickets[set]);
-                c->fold_tickets[set] = nullptr; c->fold_tickets_n[set] = 0;
-                void* tp = nullptr;
-                HIPCHK(c, hipMalloc(&tp, need * sizeof(unsigned)));
-                HIPCHK(c, hipMemset(tp, 0, need * sizeof(unsigned)));
-                c->fold_tickets[set] = (unsigned*)tp; c->fold_tickets_n[set] = need;
-                c->generation++;
-            }
-            tk = c->fold_tickets[set];
-        }
+        unsigned* tk = (c->match_fold && ksplit > 1) ? st.fold_tickets.p : nullptr;      // (sized and zeroed by ensure_match_scratch)
         LAUNCH(c, s, "mocha_match_gemm_bf16", "match.qk_bf16", 2.0 * npl * Q * (double)N * D, 2.0 * npl * Q * D + 2.0 * N * D + 4.0 * Q * N * ksplit,
-               launch_match_gemm_bf16(qc, c->bank_bf16, mS.p, Q, N, D, ksplit, s, npl, tiled, (c->match_nt && Q <= 128) ? 1 : 0, tk));
+               launch_match_gemm_bf16(qc, b.bf16.p, mS.p, Q, N, D, ksplit, s, npl, tiled, (c->match_nt && Q <= 128) ? 1 : 0, tk));
         if (tk) {                                        // slab 0 holds the sum: the selection reads one slab
             if (sel2)
                 LAUNCH(c, s, "mocha_match_select2", "match.select", 0.0, 4.0 * Q * N + 4.0 * N + 8.0 * Q,
-                       launch_match_select2(mS.p, 1, (long long)Q * N, (int)N, c->bank_norm, qnm, c->bank_center, nullptr, c->bank_bf16,
-                                            c->match_qstat[set].p, 5e-5f, Q, N, D, idx, dist, s));
+                       launch_match_select2(mS.p, 1, (long long)Q * N, (int)N, b.norm.p, qnm, b.center.p, nullptr, b.bf16.p,
+                                            st.match_qstat.p, 5e-5f, Q, N, D, idx, dist, s));
             else
                 LAUNCH(c, s, "mocha_match_select", "match.select", 0.0, 4.0 * Q * N + Q * (8.0 * D + 8 * 2.0 * D),
-                       launch_match_select(mS.p, 1, (long long)Q * N, (int)N, c->bank_norm, qnm, c->bank_center, nullptr, c->bank_bf16, 5e-5f,
+                       launch_match_select(mS.p, 1, (long long)Q * N, (int)N, b.norm.p, qnm, b.center.p, nullptr, b.bf16.p, 5e-5f,
                                            Q, N, D, idx, dist, s));
             return 0;
         }
         }
         if (sel2)
             LAUNCH(c, s, "mocha_match_select2", "match.select", 0.0, 4.0 * ksplit * Q * N + 4.0 * N + 8.0 * Q,
-                   launch_match_select2(mS.p, ksplit, (long long)Q * N, (int)N, c->bank_norm, qnm, c->bank_center, nullptr, c->bank_bf16,
-                                        c->match_qstat[set].p, 5e-5f, Q, N, D, idx, dist, s));
+                   launch_match_select2(mS.p, ksplit, (long long)Q * N, (int)N, b.norm.p, qnm, b.center.p, nullptr, b.bf16.p,
+                                        st.match_qstat.p, 5e-5f, Q, N, D, idx, dist, s));
         else
         LAUNCH(c, s, "mocha_match_select", "match.select", 0.0, 4.0 * ksplit * Q * N + Q * (8.0 * D + 8 * 2.0 * D),
-               launch_match_select(mS.p, ksplit, (long long)Q * N, (int)N, c->bank_norm, qnm, c->bank_center, nullptr, c->bank_bf16, 5e-5f,
+               launch_match_select(mS.p, ksplit, (long long)Q * N, (int)N, b.norm.p, qnm, b.center.p, nullptr, b.bf16.p, 5e-5f,
                                    Q, N, D, idx, dist, s));
         return 0;
     }
     const int ksplit = match_ksplit(Q, N);
-    GemmParams g = plain(qc, D, c->bank_cnt, mS.p, (int)N, Q, (int)N, D);
+    GemmParams g = plain(qc, D, b.cnt, mS.p, (int)N, Q, (int)N, D);
     g.ksplit = ksplit; g.slab_stride = (long long)Q * N;
-    if (c->bank_x3_valid && c->gemm_x3) {
+    if (b.x3_valid && c->gemm_x3) {
         // the plane engine wants an even number of K steps in every slab: the largest split <= ksplit that divides 23040 / 32
         int kx = ksplit;
         while (kx > 1 && (D / 32) % kx != 0) --kx;
         g.ksplit = kx;
     }
-    if (c->bank_x3_valid && c->gemm_x3 && gemm_x3_supports(g)) {
-        g.Wsplit = c->bank_x3;                          // the centred bank as planes (bank_set_impl); same coarse-score accuracy as below
+    if (b.x3_valid && c->gemm_x3 && gemm_x3_supports(g)) {
+        g.Wsplit = b.x3.p;                          // the centred bank as planes (bank_set_impl); same coarse-score accuracy as below
         g.persistent = c->gemm_persistent; g.persistent_max_n = c->gemm_persistent_max_n;
         LAUNCH(c, s, "mocha_gemm_x3", "match.qk", 2.0 * Q * (double)N * D, 4.0 * ((double)Q * D + (double)Q * N * g.ksplit) + 6.0 * N * D,
                launch_gemm_x3(g, s));
     } else {
         g.ksplit = ksplit;
-        g.wsub = c->bank_center;
+        g.wsub = b.center.p;
         GEMM(c, s, "match.qk", g);
     }
     const int nslab = g.ksplit;
@@ -1286,11 +1216,11 @@ int do_match(mocha_ctx* c, const float* qnm, int Q, int32_t* idx, float* dist, h
     // times that of the best are re-evaluated in the direct form
     if (sel2)
         LAUNCH(c, s, "mocha_match_select2", "match.select", 0.0, 4.0 * nslab * Q * N + 4.0 * N + 8.0 * Q,
-               launch_match_select2(mS.p, nslab, (long long)Q * N, (int)N, c->bank_norm, qnm, c->bank_center, c->bank_cnt, nullptr,
-                                    c->match_qstat[set].p, 4e-6f, Q, N, D, idx, dist, s));
+               launch_match_select2(mS.p, nslab, (long long)Q * N, (int)N, b.norm.p, qnm, b.center.p, b.cnt, nullptr,
+                                    st.match_qstat.p, 4e-6f, Q, N, D, idx, dist, s));
     else
     LAUNCH(c, s, "mocha_match_select", "match.select", 0.0, 4.0 * nslab * Q * N + Q * 16.0 * D,
-           launch_match_select(mS.p, nslab, (long long)Q * N, (int)N, c->bank_norm, qnm, c->bank_center, c->bank_cnt, nullptr, 4e-6f,
+           launch_match_select(mS.p, nslab, (long long)Q * N, (int)N, b.norm.p, qnm, b.center.p, b.cnt, nullptr, 4e-6f,
                                Q, N, D, idx, dist, s));
     return 0;
 }
@@ -1298,42 +1228,27 @@ int do_match(mocha_ctx* c, const float* qnm, int Q, int32_t* idx, float* dist, h
 // Scratch of the segmented matcher in workspace set `set` for launches of up to c->seg_q queries against the current table (mocha_bank_set_segments
 // sizes it for every set that exists, so that no segmented call allocates)
 int ensure_seg_scratch(mocha_ctx* c, int set) {
-    const int S = (int)c->seg_start.size() - 1;
-    const size_t need_p = match_seg_scratch_words(c->seg_q, c->seg_max_rows), need_l = seg_plan_ints(c->seg_q, S);
-    if (c->seg_partial_n[set] < need_p) {
-        HIPCHK(c, hipDeviceSynchronize());
-        dev_free(c, reinterpret_cast<float*>(c->seg_partial[set])); c->seg_partial[set] = nullptr; c->seg_partial_n[set] = 0;
-        float* p = nullptr; int rc;
-        if ((rc = dev_alloc(c, &p, 2 * need_p))) return rc;
-        c->seg_partial[set] = reinterpret_cast<unsigned long long*>(p); c->seg_partial_n[set] = need_p;
-        c->generation++;
-    }
-    if (c->seg_plan_n[set] < need_l) {
-        HIPCHK(c, hipDeviceSynchronize());
-        dev_free(c, reinterpret_cast<float*>(c->seg_plan[set])); c->seg_plan[set] = nullptr; c->seg_plan_n[set] = 0;
-        float* p = nullptr; int rc;
-        if ((rc = dev_alloc(c, &p, need_l))) return rc;
-        c->seg_plan[set] = reinterpret_cast<int*>(p); c->seg_plan_n[set] = need_l;
-        c->generation++;
-    }
-    return 0;
+    const int S = (int)c->bank.seg_start.size() - 1;
+    int rc = reserve(c, c->sets[set].seg_partial, match_seg_scratch_words(c->seg_q, c->bank.seg_max_rows));
+    if (!rc) rc = reserve(c, c->sets[set].seg_plan, seg_plan_ints(c->seg_q, S));
+    return rc;
 }
 
 // Exact 1-NN of every query within its own segment (match_segmented.hip), in launches of up to c->seg_q queries.  q: the z-scored queries
 // (fp32 bank) or the queries minus the union's centroid (bf16 bank).  idx: local rows (or null), gidx: global rows (or null).
 int seg_match(mocha_ctx* c, const float* q, int Q, const int32_t* seg, int32_t* idx, int32_t* gidx, float* dist, hipStream_t s) {
-    if (c->seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
-    const int set = c->cur, S = (int)c->seg_start.size() - 1;
+    if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    const int set = c->cur, S = (int)c->bank.seg_start.size() - 1;
     const int D = 90 * 256;
-    if (!c->seg_partial[set] || !c->seg_plan[set])
+    if (!c->sets[set].seg_partial.p || !c->sets[set].seg_plan.p)
         return fail(c, MOCHA_ERR_STATE, "workspace set %d has no segmented-match scratch: call mocha_bank_set_segments after changing the workspaces", set);
-    const void* bank = c->bank_is_bf16 ? (const void*)c->bank_bf16 : (const void*)c->bank_cnt;
+    const void* bank = c->bank.is_bf16 ? (const void*)c->bank.bf16.p : (const void*)c->bank.cnt;
     for (int q0 = 0; q0 < Q; q0 += c->seg_q) {
         const int n = std::min(c->seg_q, Q - q0);
-        LAUNCH(c, s, c->bank_is_bf16 ? "mocha_match_seg_scan<bf16>" : "mocha_match_seg_scan<f32>", "match.segmented", 3.0 * n * c->seg_max_rows * D,
-               (double)n * c->seg_max_rows * D * (c->bank_is_bf16 ? 2.0 : 4.0) + 4.0 * n * D,
-               launch_match_segmented(bank, c->bank_is_bf16 ? 1 : 0, q + (size_t)q0 * D, seg + q0, n, c->seg_dev, S, c->seg_max_rows, D,
-                                      c->seg_partial[set], c->seg_plan[set], idx ? idx + q0 : nullptr, gidx ? gidx + q0 : nullptr,
+        LAUNCH(c, s, c->bank.is_bf16 ? "mocha_match_seg_scan<bf16>" : "mocha_match_seg_scan<f32>", "match.segmented", 3.0 * n * c->bank.seg_max_rows * D,
+               (double)n * c->bank.seg_max_rows * D * (c->bank.is_bf16 ? 2.0 : 4.0) + 4.0 * n * D,
+               launch_match_segmented(bank, c->bank.is_bf16 ? 1 : 0, q + (size_t)q0 * D, seg + q0, n, c->bank.seg_dev.p, S, c->bank.seg_max_rows, D,
+                                      c->sets[set].seg_partial.p, c->sets[set].seg_plan.p, idx ? idx + q0 : nullptr, gidx ? gidx + q0 : nullptr,
                                       dist ? dist + q0 : nullptr, s));
     }
     return 0;
@@ -1402,30 +1317,16 @@ int mocha_create(const mocha_cfg* cfg, int device, mocha_ctx** out) {
 void mocha_destroy(mocha_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    for (float* p : c->owned) (void)hipFree(p);
-    for (int set = 0; set < mocha_ctx::MAX_SETS; ++set) { if (c->idx_ws[set]) (void)hipFree(c->idx_ws[set]); if (c->best_ws[set]) (void)hipFree(c->best_ws[set]); }
-    if (c->bank_bf16) (void)hipFree(c->bank_bf16);
-    if (c->bank_tiled) (void)hipFree(c->bank_tiled);
-    if (c->bank_tile32) (void)hipFree(c->bank_tile32);
-    if (c->bank_x3) (void)hipFree(c->bank_x3);
-    if (c->pair_x3) (void)hipFree(c->pair_x3);
-    if (c->bank16f) (void)hipFree(c->bank16f);
-    if (c->bank8) (void)hipFree(c->bank8);
-    for (auto* k : c->fold_tickets) if (k) (void)hipFree(k);
-    for (auto* k : c->scan_keys) if (k) (void)hipFree(k);
-    if (c->bcast_hdr) (void)hipFree(c->bcast_hdr);
-    if (c->topk_keys) (void)hipFree(c->topk_keys);
     if (c->aux) (void)hipStreamDestroy(c->aux);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->bone_parents) (void)hipFree(c->bone_parents);
     for (auto* g : {&c->step[0], &c->step[1], &c->step[2], &c->seg_step}) {
         if (g->exec) (void)hipGraphExecDestroy(g->exec);
         if (g->graph) (void)hipGraphDestroy(g->graph);
     }
     if (c->cap_stream) (void)hipStreamDestroy(c->cap_stream);
     (void)mocha_comm_destroy(c);
-    delete c;
+    delete c;                                             // every device buffer is a DeviceBuffer member: freed here
 }
 
 int mocha_load_weight(mocha_ctx* c, const char* name, const float* host, const int64_t* shape, int ndim) {
@@ -1618,13 +1519,11 @@ int mocha_finalize_weights(mocha_ctx* c) {
         }
         auto up64 = [&](const std::string& n, const std::vector<double>& v) {
             if (rc) return;
-            double*& d = c->w64[n];
-            if (!d) { float* f = nullptr; rc = dev_alloc(c, &f, 2 * v.size()); d = reinterpret_cast<double*>(f); }
-            if (!rc && hipMemcpy(d, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, MOCHA_ERR_HIP, "upload of %s failed", n.c_str());
+            if (!rc) rc = upload_to(c, c->w64, n, v);
         };
         up64("dec.Ws1_all", std::vector<double>(w1.begin(), w1.end())); up64("dec.bs1_all", std::vector<double>(b1v.begin(), b1v.end()));
         up64("dec.Ws2_all", w2d); up64("dec.bs2_all", std::vector<double>(b2v.begin(), b2v.end()));
-        c->bank_dec_valid = false;                          // cached bank constants were made with the previous weights
+        c->bank.dec_valid = false;                          // cached bank constants were made with the previous weights
     }
     // ---- to_mot joint block + head
     up("mot.Wg2", W(c, "to_mot.4.blk.gcn.conv.weight")); up("mot.bg2", W(c, "to_mot.4.blk.gcn.conv.bias"));
@@ -1671,9 +1570,9 @@ int mocha_reserve(mocha_ctx* c, int max_batch) {
     }
     int rc = ensure_ws(c, max_batch);
     if (rc) return rc;
-    if (c->bank_N > 0)                                    // ... and the match scratch of the current bank for that many queries
+    if (c->bank.N > 0)                                    // ... and the match scratch of the current bank for that many queries
         for (int set = 0; set < mocha_ctx::MAX_SETS; ++set)
-            if (!c->wss[set].empty() && (rc = ensure_match_scratch(c, set, set_windows(c, set), c->bank_N, true))) return rc;
+            if (!c->sets[set].ws.empty() && (rc = ensure_match_scratch(c, set, set_windows(c, set), c->bank, true))) return rc;
     return 0;
 }
 
@@ -1707,7 +1606,7 @@ int mocha_encoder(mocha_ctx* c, const float* tokens, int B, float* encoded, void
     int rc = ready(c, B); if (rc) return rc;
     NEED_PTRS(c, B, "mocha_encoder", tokens, encoded);
     const size_t ts = 90 * 256;
-    for (int i = 0; i < mocha_ctx::MAX_SETS; ++i) c->amax_tok_of[i] = nullptr;      // caller-supplied tokens (the reference adds pos_emb itself): measured, not carried
+    for (int i = 0; i < mocha_ctx::MAX_SETS; ++i) c->sets[i].amax_tok_of = nullptr;      // caller-supplied tokens (the reference adds pos_emb itself): measured, not carried
     return for_chunks(c, B, (hipStream_t)stream, [&](int b0, int b, hipStream_t s) -> int {
         return run_encoder(c, tokens + b0 * ts, b, encoded + b0 * ts, s);
     });
@@ -1752,7 +1651,7 @@ int mocha_decoder(mocha_ctx* c, const float* src_enc, const float* cha_enc, int 
     int rc = ready(c, B); if (rc) return rc;
     NEED_PTRS(c, B, "mocha_decoder", src_enc, cha_enc, out);
     const size_t ts = 90 * 256;
-    for (int i = 0; i < mocha_ctx::MAX_SETS; ++i) c->amax_enc_of[i] = c->amax_dec_of[i] = c->amax_tok_of[i] = nullptr;     // external activations: no carried bounds
+    for (int i = 0; i < mocha_ctx::MAX_SETS; ++i) c->sets[i].amax_enc_of = c->sets[i].amax_dec_of = c->sets[i].amax_tok_of = nullptr;     // external activations: no carried bounds
     return for_chunks(c, B, (hipStream_t)stream, [&](int b0, int b, hipStream_t s) -> int {
         return run_decoder(c, src_enc + b0 * ts, cha_enc + b0 * ts, b, out + b0 * ts, s);
     });
@@ -1778,7 +1677,7 @@ int mocha_to_mot(mocha_ctx* c, const float* tokens, int B, float* Y, void* strea
     int rc = ready(c, B); if (rc) return rc;
     NEED_PTRS(c, B, "mocha_to_mot", tokens, Y);
     const size_t ts = 90 * 256, ys = (size_t)60 * c->cfg.V * c->cfg.C_in;
-    for (int i = 0; i < mocha_ctx::MAX_SETS; ++i) c->amax_enc_of[i] = c->amax_dec_of[i] = c->amax_tok_of[i] = nullptr;     // external activations: no carried bounds
+    for (int i = 0; i < mocha_ctx::MAX_SETS; ++i) c->sets[i].amax_enc_of = c->sets[i].amax_dec_of = c->sets[i].amax_tok_of = nullptr;     // external activations: no carried bounds
     return for_chunks(c, B, (hipStream_t)stream, [&](int b0, int b, hipStream_t s) -> int {
         return run_to_mot(c, tokens + b0 * ts, b, Y + b0 * ys, s);
     });
@@ -1806,167 +1705,109 @@ int mocha_forward_features(mocha_ctx* c, const float* src_X, const float* cha_X,
     return mocha_encode(c, cha_X, B, cha_enc, cha_cnt, nullptr, nullptr, nullptr, stream);
 }
 
-// `current`: the bank becomes the context's current bank (mocha_bank_set); false for the transient bank of
-// mocha_characterize_pair, which is swapped out again before the call returns and must not invalidate captured graphs
-static int bank_set_impl(mocha_ctx* c, const float* cnt_nm, const float* encoded, int64_t N, int flags, void* stream, bool current) {
+// Owned storage for the rows of a bank of N entries (mocha_bank_set without MOCHA_BANK_BORROW, the receiving ranks of mocha_bank_broadcast)
+static int bank_own_rows(mocha_ctx* c, Bank& b, int64_t N) {
+    const size_t need = (size_t)N * 90 * 256;
+    if (b.cnt_own.n >= need && b.enc_own.n >= need) return 0;
+    // the current bank may be the copy that is about to be freed: no dangling pointers if an allocation below fails
+    if (b.cnt == b.cnt_own.p || b.enc == b.enc_own.p) { b.cnt = nullptr; b.enc = nullptr; b.N = 0; c->generation++; }
+    int rc = reserve(c, b.cnt_own, need);
+    return rc ? rc : reserve(c, b.enc_own, need);
+}
+
+// Sets bank `b` and derives what matching against it needs.  b = c->bank (mocha_bank_set): it becomes the context's current bank, with every
+// derived image and cache.  b = c->pair, the transient bank of mocha_characterize_pair: centroid, row norms and the plane image only, and
+// captured graphs stay valid (no generation bump, the current bank's segment table, bounds, copies and decoder cache are not its business)
+static int bank_set_impl(mocha_ctx* c, Bank& b, const float* cnt_nm, const float* encoded, int64_t N, int flags, void* stream) {
     int rc = ready(c, 0); if (rc) return rc;
     if (!cnt_nm || !encoded || N < 1 || N > (int64_t)1 << 30) return fail(c, MOCHA_ERR_ARG, "bad bank arguments");
+    const bool current = &b == &c->bank;
     hipStream_t s = (hipStream_t)stream;
     const size_t D = 90 * 256;
     if (flags & MOCHA_BANK_BORROW) {
-        c->bank_cnt = cnt_nm; c->bank_enc = encoded;
+        b.cnt = cnt_nm; b.enc = encoded;
     } else {
-        if (c->bank_cap < (size_t)N) {
-            if (c->bank_cnt == c->bank_cnt_own || c->bank_enc == c->bank_enc_own) { c->bank_cnt = nullptr; c->bank_enc = nullptr; c->bank_N = 0; c->generation++; }
-            c->bank_cap = 0;
-            for (float** p : {&c->bank_cnt_own, &c->bank_enc_own})
-                if (*p) { dev_free(c, *p); *p = nullptr; }
-            if ((rc = dev_alloc(c, &c->bank_cnt_own, (size_t)N * D))) return rc;
-            if ((rc = dev_alloc(c, &c->bank_enc_own, (size_t)N * D))) return rc;
-            c->bank_cap = (size_t)N;
-        }
-        HIPCHK(c, hipMemcpyAsync(c->bank_cnt_own, cnt_nm, (size_t)N * D * sizeof(float), hipMemcpyDeviceToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(c->bank_enc_own, encoded, (size_t)N * D * sizeof(float), hipMemcpyDeviceToDevice, s));
-        c->bank_cnt = c->bank_cnt_own; c->bank_enc = c->bank_enc_own;
+        if ((rc = bank_own_rows(c, b, N))) return rc;
+        HIPCHK(c, hipMemcpyAsync(b.cnt_own.p, cnt_nm, (size_t)N * D * sizeof(float), hipMemcpyDeviceToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(b.enc_own.p, encoded, (size_t)N * D * sizeof(float), hipMemcpyDeviceToDevice, s));
+        b.cnt = b.cnt_own.p; b.enc = b.enc_own.p;
     }
-    if (c->bank_norm_cap < (size_t)N) {
-        if (c->bank_norm) { dev_free(c, c->bank_norm); c->bank_norm = nullptr; }
-        if ((rc = dev_alloc(c, &c->bank_norm, (size_t)N))) return rc;
-        c->bank_norm_cap = (size_t)N;
-    }
-    c->bank_N = N;
-    c->bank_is_bf16 = (flags & MOCHA_BANK_BF16) != 0;
-    if (current) { c->seg_start.clear(); c->seg_max_rows = 0; }      // a plain bank has no segment table (mocha_bank_set_segments sets it after)
-    c->bank_tiled_valid = false; c->bank_tile32_valid = false;
+    if ((rc = reserve(c, b.norm, (size_t)N))) return rc;
+    b.N = N;
+    b.is_bf16 = (flags & MOCHA_BANK_BF16) != 0;
+    b.seg_start.clear(); b.seg_max_rows = 0;              // a plain bank has no segment table (mocha_bank_set_segments sets it after)
+    b.tiled_valid = false; b.tile32_valid = false;
     if (current) c->generation++;                         // a captured step has the previous bank's pointers and row count baked in
     // match scratch for every query count the workspace admits: a later match never allocates (capture-safe)
     for (int set = 0; set < mocha_ctx::MAX_SETS; ++set)
-        if ((set == 0 || !c->wss[set].empty()) && (rc = ensure_match_scratch(c, set, set_windows(c, set), N, true))) return rc;
+        if ((set == 0 || !c->sets[set].ws.empty()) && (rc = ensure_match_scratch(c, set, set_windows(c, set), b, true))) return rc;
     // centroid of the bank: the many-query GEMM and the bf16 copy work on b - centroid (see do_match)
-    if (!c->bank_center && (rc = dev_alloc(c, &c->bank_center, D))) return rc;
-    if (!c->center_scratch && (rc = dev_alloc(c, &c->center_scratch, 2 * column_mean_scratch_doubles((int)D)))) return rc;
-    LAUNCH(c, s, "mocha_column_mean", "bank.center", 0.0, 4.0 * N * D,
-           launch_column_mean(c->bank_cnt, N, (int)D, c->bank_center, reinterpret_cast<double*>(c->center_scratch), s));
-    if (c->bank_is_bf16) {
-        if (c->bank_bf16_cap < (size_t)N) {
-            if (c->bank_bf16) (void)hipFree(c->bank_bf16);
-            c->bank_bf16 = nullptr;
-            HIPCHK(c, hipMalloc(&c->bank_bf16, (size_t)N * D * 2));
-            c->bank_bf16_cap = (size_t)N;
-        }
-        LAUNCH(c, s, "mocha_to_bf16", "bank.to_bf16", 0.0, 6.0 * N * D, launch_to_bf16(c->bank_cnt, c->bank_center, (int)D, c->bank_bf16, (int64_t)N * D, s));
-        LAUNCH(c, s, "mocha_rownorm2_bf16", "bank.norms", 2.0 * N * D, 2.0 * N * D, launch_rownorm2_bf16(c->bank_bf16, c->bank_norm, N, (int)D, s));
+    if ((rc = reserve(c, b.center, D))) return rc;
+    if ((rc = reserve(c, c->center_scratch, column_mean_scratch_doubles((int)D)))) return rc;
+    LAUNCH(c, s, "mocha_column_mean", "bank.center", 0.0, 4.0 * N * D, launch_column_mean(b.cnt, N, (int)D, b.center.p, c->center_scratch.p, s));
+    if (b.is_bf16) {
+        if ((rc = reserve(c, b.bf16, (size_t)N * D))) return rc;
+        LAUNCH(c, s, "mocha_to_bf16", "bank.to_bf16", 0.0, 6.0 * N * D, launch_to_bf16(b.cnt, b.center.p, (int)D, b.bf16.p, (int64_t)N * D, s));
+        LAUNCH(c, s, "mocha_rownorm2_bf16", "bank.norms", 2.0 * N * D, 2.0 * N * D, launch_rownorm2_bf16(b.bf16.p, b.norm.p, N, (int)D, s));
     } else {
-        LAUNCH(c, s, "mocha_rownorm2", "bank.norms", 2.0 * N * D, 4.0 * N * D, launch_rownorm2(c->bank_cnt, c->bank_center, c->bank_norm, N, (int)D, s));
+        LAUNCH(c, s, "mocha_rownorm2", "bank.norms", 2.0 * N * D, 4.0 * N * D, launch_rownorm2(b.cnt, b.center.p, b.norm.p, N, (int)D, s));
     }
+    b.amax_ok = false; b.b16f_valid = false; b.b8_valid = false; b.dec_valid = false;
     // two-plane fp16 engine: the decoder's attention rows are bounded by the matched entries' largest magnitude, taken once here
-    if (current) {
-        c->amax_bank_ok = false;
-        if (c->gemm_h2) {
-            if (c->amax_bank_cap < (size_t)N) {
-                HIPCHK(c, hipDeviceSynchronize());
-                if (c->amax_bank) { dev_free(c, c->amax_bank); c->amax_bank = nullptr; c->amax_bank_cap = 0; }
-                if ((rc = dev_alloc(c, &c->amax_bank, (size_t)N))) return rc;
-                c->amax_bank_cap = (size_t)N;
-            }
-            HIPCHK(c, hipMemsetAsync(c->amax_bank, 0, (size_t)N * sizeof(float), s));
-            for (int64_t n0 = 0; n0 < N; n0 += 65535)      // (the kernel's grid.y)
-                LAUNCH(c, s, "mocha_absmax", "bank.absmax", 0.0, 4.0 * std::min<int64_t>(65535, N - n0) * D,
-                       launch_absmax(c->bank_enc + (size_t)n0 * D, std::min<int64_t>(65535, N - n0), (long long)D, c->amax_bank + n0, s));
-            c->amax_bank_ok = true;
-        }
+    if (current && c->gemm_h2) {
+        if ((rc = reserve(c, b.amax, (size_t)N))) return rc;
+        HIPCHK(c, hipMemsetAsync(b.amax.p, 0, (size_t)N * sizeof(float), s));
+        for (int64_t n0 = 0; n0 < N; n0 += 65535)      // (the kernel's grid.y)
+            LAUNCH(c, s, "mocha_absmax", "bank.absmax", 0.0, 4.0 * std::min<int64_t>(65535, N - n0) * D,
+                   launch_absmax(b.enc + (size_t)n0 * D, std::min<int64_t>(65535, N - n0), (long long)D, b.amax.p + n0, s));
+        b.amax_ok = true;
     }
     // few-query matching against a large fp32 bank scans its centred bf16 copy (half the bytes) and re-ranks exactly
-    if (current) c->bank16f_valid = false;
-    if (current && !c->bank_is_bf16 && c->scan16 && N >= SCAN16_MIN) {
-        if (c->bank16f_cap < (size_t)N) {
-            if (c->bank16f) (void)hipFree(c->bank16f);
-            c->bank16f = nullptr; c->bank16f_cap = 0;
-            HIPCHK(c, hipMalloc(&c->bank16f, (size_t)N * D * 2));
-            c->bank16f_cap = (size_t)N;
-        }
-        if (c->bank_rho_cap < (size_t)N) {
-            if (c->bank_rho) { dev_free(c, c->bank_rho); c->bank_rho = nullptr; }
-            if ((rc = dev_alloc(c, &c->bank_rho, (size_t)N))) return rc;
-            c->bank_rho_cap = (size_t)N;
-        }
-        LAUNCH(c, s, "mocha_to_bf16", "bank.to_bf16", 0.0, 6.0 * N * D, launch_to_bf16(c->bank_cnt, c->bank_center, (int)D, c->bank16f, (int64_t)N * D, s));
-        LAUNCH(c, s, "mocha_rowresid", "bank.resid", 3.0 * N * D, 6.0 * N * D, launch_rowresid(c->bank_cnt, c->bank_center, c->bank16f, c->bank_rho, N, (int)D, s));
-        c->bank16f_valid = true;
+    if (current && !b.is_bf16 && c->scan16 && N >= SCAN16_MIN) {
+        if ((rc = reserve(c, b.b16f, (size_t)N * D))) return rc;
+        if ((rc = reserve(c, b.rho, (size_t)N))) return rc;
+        LAUNCH(c, s, "mocha_to_bf16", "bank.to_bf16", 0.0, 6.0 * N * D, launch_to_bf16(b.cnt, b.center.p, (int)D, b.b16f.p, (int64_t)N * D, s));
+        LAUNCH(c, s, "mocha_rowresid", "bank.resid", 3.0 * N * D, 6.0 * N * D, launch_rowresid(b.cnt, b.center.p, b.b16f.p, b.rho.p, N, (int)D, s));
+        b.b16f_valid = true;
     }
-    if (current) c->bank8_valid = false;
-    if (current && c->bank16f_valid && c->scan8) {
-        if (c->bank8_cap < (size_t)N) {
-            HIPCHK(c, hipStreamSynchronize(s));                 // (a call still reading the old image)
-            if (c->bank8) HIPCHK(c, hipFree(c->bank8));
-            c->bank8 = nullptr; c->bank8_cap = 0;
-            if (c->bank8_scale) { dev_free(c, c->bank8_scale); c->bank8_scale = nullptr; }
-            if (c->bank8_rho) { dev_free(c, c->bank8_rho); c->bank8_rho = nullptr; }
-            HIPCHK(c, hipMalloc(&c->bank8, (size_t)N * D));
-            if ((rc = dev_alloc(c, &c->bank8_scale, (size_t)N))) return rc;
-            if ((rc = dev_alloc(c, &c->bank8_rho, (size_t)N))) return rc;
-            c->bank8_cap = (size_t)N;
-        }
-        LAUNCH(c, s, "mocha_to_i8", "bank.to_i8", 4.0 * N * D, 9.0 * N * D, launch_to_i8(c->bank_cnt, c->bank_center, c->bank8, c->bank8_scale, c->bank8_rho, N, (int)D, s));
+    if (current && b.b16f_valid && c->scan8) {
+        if ((rc = reserve(c, b.b8, (size_t)N * D))) return rc;
+        if ((rc = reserve(c, b.b8_scale, (size_t)N))) return rc;
+        if ((rc = reserve(c, b.b8_rho, (size_t)N))) return rc;
+        LAUNCH(c, s, "mocha_to_i8", "bank.to_i8", 4.0 * N * D, 9.0 * N * D, launch_to_i8(b.cnt, b.center.p, b.b8.p, b.b8_scale.p, b.b8_rho.p, N, (int)D, s));
         // a new bank: the byte stage gets another chance (its mode words, in every workspace set's scratch that exists)
-        for (int st = 0; st < mocha_ctx::MAX_SETS; ++st)
-            if (c->scan_keys[st]) HIPCHK(c, hipMemsetAsync(c->scan_keys[st] + match_scan8_mode_word(), 0, sizeof(unsigned long long), s));
-        c->bank8_valid = true;
+        for (SetScratch& st : c->sets)
+            if (st.scan_keys.p) HIPCHK(c, hipMemsetAsync(st.scan_keys.p + match_scan8_mode_word(), 0, sizeof(unsigned long long), s));
+        b.b8_valid = true;
     }
     // decoder constants of every entry (round 5): IN(entry) and its AdaIN gamma / beta, read in place through frame_index by the decoder
-    if (current) {
-        c->bank_dec_valid = false;
-        if (dec_cache_ok(c) && !(flags & MOCHA_BANK_NO_DEC_CACHE)) {
-            const int L = c->cfg.dec_depth;
-            if (c->bank_dec_cap < (size_t)N) {
-                for (float** p : {&c->bank_kin, &c->bank_gb})
-                    if (*p) { dev_free(c, *p); *p = nullptr; }
-                c->bank_dec_cap = 0;
-                // + N x (92 KB + 2 KB per decoder layer): about +50 % of the bank's footprint.  If the memory is not there the bank is set all
-                // the same and the decoder computes its constants per call (the round-4 flow), instead of failing mocha_bank_set
-                void* pk = nullptr; void* pg = nullptr;
-                if (hipMalloc(&pk, (size_t)N * D * sizeof(float)) == hipSuccess && hipMalloc(&pg, (size_t)N * 512 * L * sizeof(float)) == hipSuccess) {
-                    c->bank_kin = (float*)pk; c->bank_gb = (float*)pg;
-                    c->owned.push_back(c->bank_kin); c->owned.push_back(c->bank_gb);
-                    c->bank_dec_cap = (size_t)N;
-                } else {
-                    (void)hipGetLastError();                   // the failed allocation's sticky error
-                    if (pk) (void)hipFree(pk);
-                    if (pg) (void)hipFree(pg);
-                }
-            }
-            if (c->bank_dec_cap >= (size_t)N) {
+    if (current && dec_cache_ok(c) && !(flags & MOCHA_BANK_NO_DEC_CACHE)) {
+        const int L = c->cfg.dec_depth;
+        // + N x (92 KB + 2 KB per decoder layer): about +50 % of the bank's footprint.  If the memory is not there the bank is set all
+        // the same and the decoder computes its constants per call (the round-4 flow), instead of failing mocha_bank_set
+        if (b.kin.reserve((size_t)N * D) != hipSuccess || b.gb.reserve((size_t)N * 512 * L) != hipSuccess) {
+            (void)hipGetLastError();                   // the failed allocation's sticky error
+            b.kin.release(); b.gb.release();
+        } else {
             const size_t rows = (size_t)std::min<int64_t>(N, 4096);
-            if (c->style_scratch_rows < rows) {
-                if (c->style_scratch) dev_free(c, reinterpret_cast<float*>(c->style_scratch));
-                c->style_scratch = nullptr; c->style_scratch_rows = 0;
-                float* f = nullptr;
-                if ((rc = dev_alloc(c, &f, 2 * rows * (256 + (size_t)512 * L)))) return rc;
-                c->style_scratch = reinterpret_cast<double*>(f); c->style_scratch_rows = rows;
-            }
-            if ((rc = build_dec_consts(c, c->bank_enc, N, c->bank_kin, c->bank_gb, c->style_scratch, c->style_scratch + rows * 256, (int64_t)rows, s))) return rc;
-            c->bank_dec_valid = true;
-            }
+            if ((rc = reserve(c, c->style_scratch, rows * (256 + (size_t)512 * L)))) return rc;
+            if ((rc = build_dec_consts(c, b.enc, N, b.kin.p, b.gb.p, c->style_scratch.p, c->style_scratch.p + rows * 256, (int64_t)rows, s))) return rc;
+            b.dec_valid = true;
         }
     }
     // many-query matching against a small fp32 bank runs on the plane engine: centred bank as its packed image (6 B per value)
-    c->bank_x3_valid = false;
-    if (!c->bank_is_bf16 && c->gemm_x3 && N <= X3_BANK_MAX) {
-        const size_t need = gemm_x3_packed_elems((int)N, (int)D);
-        if (c->bank_x3_cap < need) {
-            if (c->bank_x3) (void)hipFree(c->bank_x3);
-            c->bank_x3 = nullptr; c->bank_x3_cap = 0;
-            HIPCHK(c, hipMalloc((void**)&c->bank_x3, need * sizeof(unsigned short)));
-            c->bank_x3_cap = need;
-        }
-        LAUNCH(c, s, "mocha_pack_x3", "bank.pack_x3", 0.0, 10.0 * N * D, launch_pack_x3(c->bank_cnt, (int)N, (int)D, c->bank_x3, s, c->bank_center));
-        c->bank_x3_valid = true;
+    b.x3_valid = false;
+    if (!b.is_bf16 && c->gemm_x3 && N <= X3_BANK_MAX) {
+        if ((rc = reserve(c, b.x3, gemm_x3_packed_elems((int)N, (int)D)))) return rc;
+        LAUNCH(c, s, "mocha_pack_x3", "bank.pack_x3", 0.0, 10.0 * N * D, launch_pack_x3(b.cnt, (int)N, (int)D, b.x3.p, s, b.center.p));
+        b.x3_valid = true;
     }
     return 0;
 }
 
 int mocha_bank_set(mocha_ctx* c, const float* cnt_nm, const float* encoded, int64_t N, int flags, void* stream) {
-    return bank_set_impl(c, cnt_nm, encoded, N, flags, stream, true);
+    if (!c) return MOCHA_ERR_ARG;
+    return bank_set_impl(c, c->bank, cnt_nm, encoded, N, flags, stream);
 }
 
 int mocha_match(mocha_ctx* c, const float* query_nm, int Q, int32_t* idx, float* dist, void* stream) {
@@ -1974,57 +1815,48 @@ int mocha_match(mocha_ctx* c, const float* query_nm, int Q, int32_t* idx, float*
     if (Q == 0) return 0;
     if (!query_nm || !idx || Q < 0) return fail(c, MOCHA_ERR_ARG, "bad match arguments");
     if (Q == 0) return 0;
-    return do_match(c, query_nm, Q, idx, dist, (hipStream_t)stream);
+    return do_match(c, c->bank, query_nm, Q, idx, dist, (hipStream_t)stream);
 }
 
 int mocha_match_topk(mocha_ctx* c, const float* query_nm, int Q, int k, int32_t* idx, float* dist, void* stream) {
     int rc = ready(c, 0); if (rc) return rc;
     if (Q == 0) return 0;
     if (!query_nm || !idx || Q < 0 || k < 1 || k > 64) return fail(c, MOCHA_ERR_ARG, "bad top-k arguments (1 <= k <= 64)");
-    if (!c->bank_cnt || c->bank_N <= 0) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
+    if (!c->bank.cnt || c->bank.N <= 0) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
     hipStream_t s = (hipStream_t)stream;
     const int D = 90 * 256;
-    const int64_t N = c->bank_N;
-    const size_t need = (size_t)8 * N;
-    if (c->topk_keys_n < need) {                            // not on the per-frame path: allocated on first use
-        HIPCHK(c, hipDeviceSynchronize());
-        if (c->topk_keys) (void)hipFree(c->topk_keys);
-        c->topk_keys = nullptr; c->topk_keys_n = 0;
-        void* kp = nullptr;
-        HIPCHK(c, hipMalloc(&kp, need * sizeof(unsigned long long)));
-        c->topk_keys = (unsigned long long*)kp; c->topk_keys_n = need;
-        c->generation++;
-    }
+    const int64_t N = c->bank.N;
+    if ((rc = reserve(c, c->topk_keys, (size_t)8 * N))) return rc;      // not on the per-frame path: allocated on first use
     const float* q = query_nm;
-    if (c->bank_is_bf16) {                                  // the bf16 bank holds bf16(b - centroid): centred queries
-        if ((rc = grow(c, c->match_qc[0], (size_t)std::max(Q, 8) * D))) return rc;
-        LAUNCH(c, s, "mocha_sub_rows", "match.center", 0.0, 8.0 * Q * D, launch_sub_rows(query_nm, c->bank_center, c->match_qc[0].p, Q, D, s));
-        q = c->match_qc[0].p;
+    if (c->bank.is_bf16) {                                  // the bf16 bank holds bf16(b - centroid): centred queries
+        if ((rc = reserve(c, c->sets[0].match_qc, (size_t)std::max(Q, 8) * D))) return rc;
+        LAUNCH(c, s, "mocha_sub_rows", "match.center", 0.0, 8.0 * Q * D, launch_sub_rows(query_nm, c->bank.center.p, c->sets[0].match_qc.p, Q, D, s));
+        q = c->sets[0].match_qc.p;
     }
-    const void* bank = c->bank_is_bf16 ? (const void*)c->bank_bf16 : (const void*)c->bank_cnt;
-    LAUNCH(c, s, "mocha_match_topk", "match.topk", 3.0 * Q * N * D, ((Q + 7) / 8) * (double)N * D * (c->bank_is_bf16 ? 2.0 : 4.0),
-           launch_match_topk(bank, c->bank_is_bf16 ? 1 : 0, q, Q, N, D, k, c->topk_keys, idx, dist, s));
+    const void* bank = c->bank.is_bf16 ? (const void*)c->bank.bf16.p : (const void*)c->bank.cnt;
+    LAUNCH(c, s, "mocha_match_topk", "match.topk", 3.0 * Q * N * D, ((Q + 7) / 8) * (double)N * D * (c->bank.is_bf16 ? 2.0 : 4.0),
+           launch_match_topk(bank, c->bank.is_bf16 ? 1 : 0, q, Q, N, D, k, c->topk_keys.p, idx, dist, s));
     return 0;
 }
 
 int mocha_bank_gather_blend(mocha_ctx* c, const int32_t* idx, const float* dist, float temperature, int Q, int k, float* out, void* stream) {
     int rc = ready(c, 0); if (rc) return rc;
-    if (!c->bank_enc) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
+    if (!c->bank.enc) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
     if (Q == 0) return 0;
     if (!idx || !dist || !out || Q < 0 || k < 1 || k > 64 || !(temperature > 0.f)) return fail(c, MOCHA_ERR_ARG, "bad gather_blend arguments");
     hipStream_t s = (hipStream_t)stream;
     LAUNCH(c, s, "mocha_gather_blend", "bank.gather_blend", 2.0 * Q * k * 90 * 256, Q * (k + 1.0) * 90 * 256 * 4,
-           launch_gather_blend(c->bank_enc, idx, dist, temperature, out, Q, k, 90 * 256, c->bank_N, s));
+           launch_gather_blend(c->bank.enc, idx, dist, temperature, out, Q, k, 90 * 256, c->bank.N, s));
     return 0;
 }
 
 int mocha_bank_gather(mocha_ctx* c, const int32_t* idx, int Q, float* out, void* stream) {
     int rc = ready(c, 0); if (rc) return rc;
-    if (!c->bank_enc) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
+    if (!c->bank.enc) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
     if (Q == 0) return 0;
     if (!idx || !out || Q < 0) return fail(c, MOCHA_ERR_ARG, "bad gather arguments");
     hipStream_t s = (hipStream_t)stream;
-    LAUNCH(c, s, "mocha_gather_rows", "bank.gather", 0.0, Q * 90.0 * 256 * 8, launch_gather_rows(c->bank_enc, idx, out, Q, 90 * 256, c->bank_N, s));
+    LAUNCH(c, s, "mocha_gather_rows", "bank.gather", 0.0, Q * 90.0 * 256 * 8, launch_gather_rows(c->bank.enc, idx, out, Q, 90 * 256, c->bank.N, s));
     return 0;
 }
 
@@ -2033,41 +1865,41 @@ int mocha_bank_gather(mocha_ctx* c, const int32_t* idx, int Q, float* out, void*
 static int characterize_impl(mocha_ctx* c, const float* src_X, int B, const float* cnt_mean, const float* cnt_std, float* Y,
                              int32_t* idx, void* stream, bool raw, const int32_t* seg = nullptr) {
     int rc = ready(c, B); if (rc) return rc;
-    if (!c->bank_cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
-    if (seg && c->seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
+    if (seg && c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
     if (B == 0) return 0;
     if (!cnt_mean || !cnt_std || !src_X || !Y) return fail(c, MOCHA_ERR_ARG, "null argument");
     const size_t ys = (size_t)60 * c->cfg.V * c->cfg.C_in;
     const size_t xs = raw ? (size_t)60 * (c->cfg.V + 1) * c->cfg.C_in : ys;
     return for_chunks(c, B, (hipStream_t)stream, [&](int b0, int b, hipStream_t s) -> int {
         int r;
-        int32_t* ix = idx ? idx + b0 : c->idx_ws[c->cur];
+        int32_t* ix = idx ? idx + b0 : SET(c).idx_ws.p;
         if ((r = run_embed(c, src_X + b0 * xs, b, WS(c, "x5"), true, s, raw))) return r;
         if ((r = run_encoder(c, WS(c, "x5"), b, WS(c, "enc_s"), s))) return r;
         if (seg) {
             // cnt and its z-score (and, bf16 bank, the queries centred on the union's centroid), the segmented matcher, the decoder on the global rows
             InormExtra ex = IEX(c);
-            if (c->bank_is_bf16) { ex.centre = c->bank_center; ex.zc = WS(c, "qc"); }
-            LAUNCH(c, s, "mocha_instnorm", "mvn", 0.0, b * 90.0 * 256 * 4 * (c->bank_is_bf16 ? 3.0 : 2.0), launch_instnorm(WS(c, "enc_s"), nullptr, nullptr, cnt_mean, cnt_std, WS(c, "qnm"), b, 90, s, &ex));
-            int32_t* gx = c->idx_ws[c->cur];
-            if ((r = seg_match(c, WS(c, c->bank_is_bf16 ? "qc" : "qnm"), b, seg + b0, idx ? idx + b0 : nullptr, gx, nullptr, s))) return r;
-            if ((r = run_decoder(c, WS(c, "enc_s"), nullptr, b, WS(c, "dec"), s, c->bank_enc, gx, c->bank_N,
-                                 c->bank_dec_valid ? c->bank_kin : nullptr, c->bank_dec_valid ? c->bank_gb : nullptr))) return r;
+            if (c->bank.is_bf16) { ex.centre = c->bank.center.p; ex.zc = WS(c, "qc"); }
+            LAUNCH(c, s, "mocha_instnorm", "mvn", 0.0, b * 90.0 * 256 * 4 * (c->bank.is_bf16 ? 3.0 : 2.0), launch_instnorm(WS(c, "enc_s"), nullptr, nullptr, cnt_mean, cnt_std, WS(c, "qnm"), b, 90, s, &ex));
+            int32_t* gx = SET(c).idx_ws.p;
+            if ((r = seg_match(c, WS(c, c->bank.is_bf16 ? "qc" : "qnm"), b, seg + b0, idx ? idx + b0 : nullptr, gx, nullptr, s))) return r;
+            if ((r = run_decoder(c, WS(c, "enc_s"), nullptr, b, WS(c, "dec"), s, c->bank.enc, gx, c->bank.N,
+                                 c->bank.dec_valid ? c->bank.kin.p : nullptr, c->bank.dec_valid ? c->bank.gb.p : nullptr))) return r;
             return run_to_mot(c, WS(c, "dec"), b, Y + b0 * ys, s, raw);
         }
         // cnt, its z-score and - the bank's centroid is known - the matcher's centred queries in one pass
         // (as one bf16 plane where the many-query pass against a bf16 bank will read them: no mocha_center_bf16 launch)
-        const bool q16 = c->bank_is_bf16 && b > 8;
-        const bool sel2 = use_select2(c, b);                     // the selection's row statistics (and the second bf16 plane) come from this pass too
-        if (sel2 && (r = ensure_match_scratch(c, c->cur, b, c->bank_N, false))) return r;
-        InormExtra ex = IEX(c); ex.centre = c->bank_center;
+        const bool q16 = c->bank.is_bf16 && b > 8;
+        const bool sel2 = use_select2(c, c->bank, b);                   // the selection's row statistics (and the second bf16 plane) come from this pass too
+        if (sel2 && (r = ensure_match_scratch(c, c->cur, b, c->bank, false))) return r;
+        InormExtra ex = IEX(c); ex.centre = c->bank.center.p;
         if (q16) ex.zc16 = reinterpret_cast<unsigned short*>(WS(c, "qc")); else ex.zc = WS(c, "qc");
-        if (sel2) { ex.qstat = c->match_qstat[c->cur].p; if (q16 && c->match_planes == 2) ex.plane_stride = (long long)b * 90 * 256; }
+        if (sel2) { ex.qstat = SET(c).match_qstat.p; if (q16 && c->match_planes == 2) ex.plane_stride = (long long)b * 90 * 256; }
         LAUNCH(c, s, "mocha_instnorm", "mvn", 0.0, b * 90.0 * 256 * 4 * (q16 ? (sel2 ? 3.0 : 2.5) : 3.0), launch_instnorm(WS(c, "enc_s"), nullptr, nullptr, cnt_mean, cnt_std, WS(c, "qnm"), b, 90, s, &ex));
-        if ((r = do_match(c, WS(c, "qnm"), b, ix, nullptr, s, WS(c, "qc"), q16, sel2))) return r;
+        if ((r = do_match(c, c->bank, WS(c, "qnm"), b, ix, nullptr, s, WS(c, "qc"), q16, sel2))) return r;
         // decoder on cha_encoded[frame_index]: its first kernel gathers the rows itself
-        if ((r = run_decoder(c, WS(c, "enc_s"), nullptr, b, WS(c, "dec"), s, c->bank_enc, ix, c->bank_N,
-                             c->bank_dec_valid ? c->bank_kin : nullptr, c->bank_dec_valid ? c->bank_gb : nullptr))) return r;
+        if ((r = run_decoder(c, WS(c, "enc_s"), nullptr, b, WS(c, "dec"), s, c->bank.enc, ix, c->bank.N,
+                             c->bank.dec_valid ? c->bank.kin.p : nullptr, c->bank.dec_valid ? c->bank.gb.p : nullptr))) return r;
         return run_to_mot(c, WS(c, "dec"), b, Y + b0 * ys, s, raw);
     });
 }
@@ -2137,24 +1969,12 @@ static int characterize_pair_impl(mocha_ctx* c, const float* src_X, int B_src, c
     }();
     if (rc) { (void)join(); return rc; }
     if (B_src == 0) return 0;
-    // transient bank: swap the context's bank state out, borrow the workspace rows, restore afterwards
-    // (everything bank_set_impl derives from a bank has a pair_* twin: norms, centroid, packed plane image - the user's
-    // current bank and what was derived from it are exactly as before when the call returns)
-    struct Saved { const float *cnt, *enc; int64_t N; bool bf16; float* norm; size_t norm_cap; float* center;
-                   unsigned short* x3; size_t x3_cap; bool x3_valid; bool v16; } sv{
-        c->bank_cnt, c->bank_enc, c->bank_N, c->bank_is_bf16, c->bank_norm, c->bank_norm_cap, c->bank_center,
-        c->bank_x3, c->bank_x3_cap, c->bank_x3_valid, c->bank16f_valid};
-    c->bank16f_valid = false;                             // the bf16 copy belongs to the user's bank, not to the transient one
-    c->bank_norm = c->pair_norm; c->bank_norm_cap = c->pair_norm_cap; c->bank_center = c->pair_center;
-    c->bank_x3 = c->pair_x3; c->bank_x3_cap = c->pair_x3_cap; c->bank_x3_valid = false;
-    rc = bank_set_impl(c, WS(c, "qnm"), WS(c, "enc_s"), B_cha, MOCHA_BANK_BORROW, stream, false);
-    int32_t* ix = idx ? idx : c->idx_ws[0];
-    if (!rc) rc = do_match(c, WS(c, "qnm") + (size_t)B_cha * T, B_src, ix, nullptr, s);
-    c->pair_norm = c->bank_norm; c->pair_norm_cap = c->bank_norm_cap; c->pair_center = c->bank_center;
-    c->pair_x3 = c->bank_x3; c->pair_x3_cap = c->bank_x3_cap;
-    c->bank_x3 = sv.x3; c->bank_x3_cap = sv.x3_cap; c->bank_x3_valid = sv.x3_valid; c->bank16f_valid = sv.v16;
-    c->bank_cnt = sv.cnt; c->bank_enc = sv.enc; c->bank_N = sv.N; c->bank_is_bf16 = sv.bf16; c->bank_norm = sv.norm; c->bank_norm_cap = sv.norm_cap;
-    c->bank_center = sv.center;
+    // transient bank: c->pair borrows the workspace rows and keeps its own norms, centroid and packed plane image - the user's current
+    // bank (c->bank) and what was derived from it are not touched
+    rc = bank_set_impl(c, c->pair, WS(c, "qnm"), WS(c, "enc_s"), B_cha, MOCHA_BANK_BORROW, stream);
+    int32_t* ix = idx ? idx : c->sets[0].idx_ws.p;
+    if (!rc) rc = do_match(c, c->pair, WS(c, "qnm") + (size_t)B_cha * T, B_src, ix, nullptr, s);
+    c->pair.cnt = c->pair.enc = nullptr; c->pair.N = 0;   // the workspace rows were lent for this call only
     { const int rj = join(); if (!rc) rc = rj; }          // the decoder constants are complete (the caller's stream is never left forked)
     if (rc) return rc;
     // decoder on the matched character rows: the transient bank's encoded rows are rows [0, B_cha) of the workspace, their decoder
@@ -2216,13 +2036,13 @@ int mocha_step_graph_lane(mocha_ctx* c, int lane, const float* X1, const float* 
     if (lane < 0 || lane >= c->lanes) return fail(c, MOCHA_ERR_ARG, "lane %d: the context has %d lane(s) (mocha_set_option \"lanes\")", lane, c->lanes);
     int rc = ready(c, 1); if (rc) return rc;
     if (!X1 || !cnt_mean || !cnt_std || !Y1 || !idx) return fail(c, MOCHA_ERR_ARG, "null argument");
-    if (!c->bank_cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
-    if (c->wss[lane].empty()) return fail(c, MOCHA_ERR_STATE, "lane %d has no workspace", lane);
+    if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
+    if (c->sets[lane].ws.empty()) return fail(c, MOCHA_ERR_STATE, "lane %d has no workspace", lane);
     mocha_ctx::StepKey key; key.x = X1; key.mean = cnt_mean; key.sd = cnt_std; key.y = Y1; key.idx = idx; key.raw = raw != 0;
     const auto& g = c->step[lane];
     if (!(g.exec && g.key == key && g.generation == c->generation)) {
         // make sure nothing inside the captured region allocates (scratch for one query against the current bank)
-        if ((rc = ensure_match_scratch(c, lane, 8, c->bank_N, true))) return rc;
+        if ((rc = ensure_match_scratch(c, lane, 8, c->bank, true))) return rc;
     }
     return step_replay(c, c->step[lane], key, (hipStream_t)stream, [&](hipStream_t cs) -> int {
         c->lane = lane;                                   // the step's kernels use this lane's workspace set and match scratch
@@ -2248,7 +2068,7 @@ int mocha_bank_set_segments(mocha_ctx* c, const float* cnt_nm, const float* enco
     if (seg_start[0] != 0 || seg_start[S] != N) return fail(c, MOCHA_ERR_ARG, "bank_set_segments: seg_start must run from 0 to N = %lld", (long long)N);
     for (int i = 0; i < S; ++i)
         if (seg_start[i + 1] <= seg_start[i]) return fail(c, MOCHA_ERR_ARG, "bank_set_segments: segment %d is empty or seg_start decreases", i);
-    int rc = bank_set_impl(c, cnt_nm, encoded, N, flags, stream, true);
+    int rc = bank_set_impl(c, c->bank, cnt_nm, encoded, N, flags, stream);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     rc = [&]() -> int {
@@ -2256,44 +2076,38 @@ int mocha_bank_set_segments(mocha_ctx* c, const float* cnt_nm, const float* enco
         std::vector<int> dev32(S + 1);
         for (int i = 0; i <= S; ++i) dev32[i] = (int)seg_start[i];
         for (int i = 0; i < S; ++i) mx = std::max<int64_t>(mx, seg_start[i + 1] - seg_start[i]);
-        if (c->seg_dev_cap < (size_t)S + 1) {
-            HIPCHK(c, hipDeviceSynchronize());
-            dev_free(c, reinterpret_cast<float*>(c->seg_dev)); c->seg_dev = nullptr; c->seg_dev_cap = 0;
-            float* p = nullptr; int r;
-            if ((r = dev_alloc(c, &p, (size_t)S + 1))) return r;
-            c->seg_dev = reinterpret_cast<int*>(p); c->seg_dev_cap = (size_t)S + 1;
-        }
-        HIPCHK(c, hipMemcpyAsync(c->seg_dev, dev32.data(), sizeof(int) * (S + 1), hipMemcpyHostToDevice, s));
+        { int r = reserve(c, c->bank.seg_dev, (size_t)S + 1); if (r) return r; }
+        HIPCHK(c, hipMemcpyAsync(c->bank.seg_dev.p, dev32.data(), sizeof(int) * (S + 1), hipMemcpyHostToDevice, s));
         HIPCHK(c, hipStreamSynchronize(s));                  // (the host vector goes out of scope)
-        c->seg_start.assign(seg_start, seg_start + S + 1);
-        c->seg_max_rows = mx;
+        c->bank.seg_start.assign(seg_start, seg_start + S + 1);
+        c->bank.seg_max_rows = mx;
         // launches of up to seg_q queries: the workspace's windows, and at least the 16 windows of mocha_step_graph_segmented
         c->seg_q = std::min(SEG_MAX_Q, std::max(set_windows(c, 0), 16));
         for (int set = 0; set < mocha_ctx::MAX_SETS; ++set) {
             int r;
-            if ((set == 0 || !c->wss[set].empty()) && (r = ensure_seg_scratch(c, set))) return r;
+            if ((set == 0 || !c->sets[set].ws.empty()) && (r = ensure_seg_scratch(c, set))) return r;
         }
         return 0;
     }();
-    if (rc) { c->seg_start.clear(); c->seg_max_rows = 0; }
+    if (rc) { c->bank.seg_start.clear(); c->bank.seg_max_rows = 0; }
     return rc;
 }
 
 int mocha_match_segmented(mocha_ctx* c, const float* query_nm, int Q, const int32_t* seg, int32_t* idx, float* dist, void* stream) {
     int rc = ready(c, 0); if (rc) return rc;
     if (!query_nm || !seg || !idx || Q < 0) return fail(c, MOCHA_ERR_ARG, "bad match_segmented arguments");
-    if (c->seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
     if (Q == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const int D = 90 * 256;
     c->cur = 0;
-    if (!c->bank_is_bf16) return seg_match(c, query_nm, Q, seg, idx, nullptr, dist, s);
+    if (!c->bank.is_bf16) return seg_match(c, query_nm, Q, seg, idx, nullptr, dist, s);
     // the bf16 copy holds bf16(b - centroid of the union): centred queries, as many at a time as the centred-query buffer holds
-    const int per = (int)std::min<size_t>((size_t)c->seg_q, c->match_qc[0].n / D);
+    const int per = (int)std::min<size_t>((size_t)c->seg_q, c->sets[0].match_qc.n / D);
     for (int q0 = 0; q0 < Q; q0 += per) {
         const int n = std::min(per, Q - q0);
-        LAUNCH(c, s, "mocha_sub_rows", "match.center", 0.0, 8.0 * n * D, launch_sub_rows(query_nm + (size_t)q0 * D, c->bank_center, c->match_qc[0].p, n, D, s));
-        if ((rc = seg_match(c, c->match_qc[0].p, n, seg + q0, idx + q0, nullptr, dist ? dist + q0 : nullptr, s))) return rc;
+        LAUNCH(c, s, "mocha_sub_rows", "match.center", 0.0, 8.0 * n * D, launch_sub_rows(query_nm + (size_t)q0 * D, c->bank.center.p, c->sets[0].match_qc.p, n, D, s));
+        if ((rc = seg_match(c, c->sets[0].match_qc.p, n, seg + q0, idx + q0, nullptr, dist ? dist + q0 : nullptr, s))) return rc;
     }
     return 0;
 }
@@ -2311,8 +2125,8 @@ int mocha_step_graph_segmented(mocha_ctx* c, const float* X, int S_w, const int3
     if (S_w < 1 || S_w > 16) return fail(c, MOCHA_ERR_ARG, "step_graph_segmented: 1 <= S_w <= 16 windows");
     int rc = ready(c, S_w); if (rc) return rc;
     if (!X || !seg || !cnt_mean || !cnt_std || !Y || !idx) return fail(c, MOCHA_ERR_ARG, "null argument");
-    if (!c->bank_cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
-    if (c->seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
+    if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
     mocha_ctx::StepKey key; key.x = X; key.mean = cnt_mean; key.sd = cnt_std; key.y = Y; key.idx = idx; key.seg = seg; key.windows = S_w;
     key.raw = raw != 0;
     // the ids are read by the captured kernels on every replay: new ids in `seg` are not part of the key
@@ -2498,13 +2312,13 @@ int mocha_bank_broadcast(mocha_ctx* c, void* comm_, int root, int64_t N, int fla
     // every rank checks all of them before any payload moves.  All ranks see the same headers, so a disagreement fails loudly on
     // ALL ranks instead of leaving some of them inside a collective the others never enter.
     if (world > 4096) return fail(c, MOCHA_ERR_ARG, "bank_broadcast: %d ranks", world);
-    if (!c->bcast_hdr) HIPCHK(c, hipMalloc((void**)&c->bcast_hdr, 2 * 4096 * sizeof(long long)));
+    if ((rc = reserve(c, c->bcast_hdr, 2 * 4096))) return rc;
     std::vector<long long> hdr((size_t)2 * world, 0);
     long long mine[2] = {(long long)N, want_bf16 ? 1 : 0};
-    if (rank == root) { mine[0] = (c->bank_cnt && c->bank_N == N) ? (long long)N : -1; mine[1] = c->bank_is_bf16 ? 1 : 0; }
-    HIPCHK(c, hipMemcpyAsync(c->bcast_hdr + 2 * rank, mine, sizeof mine, hipMemcpyHostToDevice, s));
-    if (world > 1) NCCLCHK(c, g_rccl.AllGather(c->bcast_hdr + 2 * rank, c->bcast_hdr, 2, ncclInt64, comm, s));
-    HIPCHK(c, hipMemcpyAsync(hdr.data(), c->bcast_hdr, hdr.size() * sizeof(long long), hipMemcpyDeviceToHost, s));
+    if (rank == root) { mine[0] = (c->bank.cnt && c->bank.N == N) ? (long long)N : -1; mine[1] = c->bank.is_bf16 ? 1 : 0; }
+    HIPCHK(c, hipMemcpyAsync(c->bcast_hdr.p + 2 * rank, mine, sizeof mine, hipMemcpyHostToDevice, s));
+    if (world > 1) NCCLCHK(c, g_rccl.AllGather(c->bcast_hdr.p + 2 * rank, c->bcast_hdr.p, 2, ncclInt64, comm, s));
+    HIPCHK(c, hipMemcpyAsync(hdr.data(), c->bcast_hdr.p, hdr.size() * sizeof(long long), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     if (hdr[2 * root] != (long long)N || hdr[2 * root] < 0) {
         if (hdr[2 * root] < 0)
@@ -2520,27 +2334,15 @@ int mocha_bank_broadcast(mocha_ctx* c, void* comm_, int root, int64_t N, int fla
             return fail(c, MOCHA_ERR_ARG, "bank_broadcast: the root's bank was set %s MOCHA_BANK_BF16 but rank %d asks for the opposite: every "
                         "rank must match against the same bank", hdr[2 * root + 1] ? "with" : "without", r);
     }
-    if (rank != root) {
-        if (c->bank_cap < (size_t)N) {
-            HIPCHK(c, hipDeviceSynchronize());
-            // the current bank may be the copy that is about to be freed: no dangling pointers if an allocation below fails
-            if (c->bank_cnt == c->bank_cnt_own || c->bank_enc == c->bank_enc_own) { c->bank_cnt = nullptr; c->bank_enc = nullptr; c->bank_N = 0; c->generation++; }
-            c->bank_cap = 0;
-            for (float** p : {&c->bank_cnt_own, &c->bank_enc_own})
-                if (*p) { dev_free(c, *p); *p = nullptr; }
-            if ((rc = dev_alloc(c, &c->bank_cnt_own, (size_t)N * D))) return rc;
-            if ((rc = dev_alloc(c, &c->bank_enc_own, (size_t)N * D))) return rc;
-            c->bank_cap = (size_t)N;
-        }
-    }
+    if (rank != root && (rc = bank_own_rows(c, c->bank, N))) return rc;
     // the root's own chunks are rewritten in place with identical values by the all-gather (a borrowed bank stays unchanged)
-    float* cnt = rank == root ? const_cast<float*>(c->bank_cnt) : c->bank_cnt_own;
-    float* enc = rank == root ? const_cast<float*>(c->bank_enc) : c->bank_enc_own;
+    float* cnt = rank == root ? const_cast<float*>(c->bank.cnt) : c->bank.cnt_own.p;
+    float* enc = rank == root ? const_cast<float*>(c->bank.enc) : c->bank.enc_own.p;
     if ((rc = bcast_chunked(c, comm, world, rank, root, cnt, (size_t)N * D, s))) return rc;
     if ((rc = bcast_chunked(c, comm, world, rank, root, enc, (size_t)N * D, s))) return rc;
     if (rank == root) return 0;
     // derived data (centroid, norms, bf16 copy) is recomputed locally: deterministic kernels, same result on every rank
-    return bank_set_impl(c, c->bank_cnt_own, c->bank_enc_own, N, (flags & MOCHA_BANK_BF16) | MOCHA_BANK_BORROW, stream, true);
+    return bank_set_impl(c, c->bank, c->bank.cnt_own.p, c->bank.enc_own.p, N, (flags & MOCHA_BANK_BF16) | MOCHA_BANK_BORROW, stream);
 }
 
 int mocha_set_pose_norm(mocha_ctx* c, const float* x_mean, const float* x_std, const float* y_mean, const float* y_std) {
@@ -2549,9 +2351,9 @@ int mocha_set_pose_norm(mocha_ctx* c, const float* x_mean, const float* x_std, c
     const size_t nn = (size_t)(c->cfg.V + 1) * c->cfg.C_in;
     for (size_t i = 0; i < nn; ++i)
         if (!(x_std[i] != 0.f)) return fail(c, MOCHA_ERR_ARG, "x_std[%zu] is zero", i);
-    if (!c->pose_norm) { int rc = dev_alloc(c, &c->pose_norm, 4 * nn); if (rc) return rc; }
+    { int rc = reserve(c, c->pose_norm, 4 * nn); if (rc) return rc; }
     const float* src[4] = {x_mean, x_std, y_mean, y_std};
-    for (int k = 0; k < 4; ++k) HIPCHK(c, hipMemcpy(c->pose_norm + k * nn, src[k], nn * sizeof(float), hipMemcpyHostToDevice));
+    for (int k = 0; k < 4; ++k) HIPCHK(c, hipMemcpy(c->pose_norm.p + k * nn, src[k], nn * sizeof(float), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -2639,7 +2441,7 @@ int mocha_cvae_finalize(mocha_ctx* c) {
     x3_drop_images(c);
     h2_drop_images(c);
     for (auto& kv : c->cvae_host) {
-        int rc = upload_to(c, c->cw, c->cwsize, kv.first, kv.second.data); if (rc) return rc;
+        int rc = upload_to(c, c->cw, kv.first, kv.second.data); if (rc) return rc;
     }
     if (c->cw.count("pe")) { c->cvae_ready = true; return 0; }     // table came with the state_dict (pos_encoder.pe)
     // sin/cos positional encoding rows 0..191 (model_CVAE.py:168-178), float32 arithmetic like torch
@@ -2652,7 +2454,7 @@ int mocha_cvae_finalize(mocha_ctx* c) {
             pe[t * 256 + 2 * i + 1] = cosf(a);
         }
     }
-    int rc = upload_to(c, c->cw, c->cwsize, "pe", pe); if (rc) return rc;
+    int rc = upload_to(c, c->cw, "pe", pe); if (rc) return rc;
     c->cvae_ready = true;
     return 0;
 }
@@ -2660,12 +2462,11 @@ int mocha_cvae_finalize(mocha_ctx* c) {
 static int cvae_ws(mocha_ctx* c, int B) {
     if (c->cvae_B >= B) return 0;
     if (c->cvae_B > 0) HIPCHK(c, hipDeviceSynchronize());
-    for (auto& kv : c->cws) dev_free(c, kv.second.p);
     c->cws.clear();
     c->generation++;
     const std::pair<const char*, size_t> plan[] = {{"t0", 182 * 256}, {"t1", 182 * 256}, {"t2", 182 * 256}, {"qkv", 182 * 768},
                                                    {"hff", 182 * 512}, {"mem", 181 * 256}, {"kv", 181 * 512}};
-    for (auto& pl : plan) { DevBuf b; b.n = pl.second * (size_t)B; int rc = dev_alloc(c, &b.p, b.n); if (rc) return rc; c->cws[pl.first] = b; }
+    for (auto& pl : plan) { int rc = reserve(c, c->cws[pl.first], pl.second * (size_t)B); if (rc) return rc; }
     c->cvae_B = B;
     return 0;
 }
@@ -2674,7 +2475,7 @@ static int cvae_ws(mocha_ctx* c, int B) {
 static int cvae_attn_block(mocha_ctx* c, hipStream_t s, const std::string& p, const std::string& norm, float* x /*in/out*/, int nq,
                            const float* kvsrc /*nullptr: self*/, int nk, int B) {
     float* qkv = c->cws.at("qkv").p; float* t1 = c->cws.at("t1").p; float* t2 = c->cws.at("t2").p; float* kvb = c->cws.at("kv").p;
-    const float* Win = c->cw.at(p + ".in_proj_weight"); const float* bin = c->cw.at(p + ".in_proj_bias");
+    const float* Win = c->cw.at(p + ".in_proj_weight").p; const float* bin = c->cw.at(p + ".in_proj_bias").p;
     const int H = c->cvae_heads, DH = 256 / H;
     AttnParams a{};
     if (!kvsrc) {
@@ -2690,24 +2491,24 @@ static int cvae_attn_block(mocha_ctx* c, hipStream_t s, const std::string& p, co
     }
     LAUNCH(c, s, "mocha_attention_f32<64>", "cvae.attn", 4.0 * B * H * (double)a.nq * a.nk * DH, 4.0 * B * (a.nq + 2.0 * a.nk) * 256,
            launch_attention(a, s));
-    GemmParams o = plain(t1, 256, c->cw.at(p + ".out_proj.weight"), t2, 256, B * nq, 256, 256);
-    o.bias = c->cw.at(p + ".out_proj.bias"); o.residual = x; o.ldr = 256;
+    GemmParams o = plain(t1, 256, c->cw.at(p + ".out_proj.weight").p, t2, 256, B * nq, 256, 256);
+    o.bias = c->cw.at(p + ".out_proj.bias").p; o.residual = x; o.ldr = 256;
     GEMM(c, s, "cvae.out_proj", o);
     LAUNCH(c, s, "mocha_layernorm256", "cvae.norm", 0.0, B * nq * 256.0 * 8,
-           launch_layernorm256(t2, c->cw.at(norm + ".weight"), c->cw.at(norm + ".bias"), x, B * nq, s));
+           launch_layernorm256(t2, c->cw.at(norm + ".weight").p, c->cw.at(norm + ".bias").p, x, B * nq, s));
     return 0;
 }
 
 static int cvae_ff_block(mocha_ctx* c, hipStream_t s, const std::string& p, const std::string& norm, float* x, float* out, int n, int B) {
     float* hff = c->cws.at("hff").p; float* t2 = c->cws.at("t2").p;
-    GemmParams f1 = plain(x, 256, c->cw.at(p + ".linear1.weight"), hff, 512, B * n, 512, 256);
-    f1.bias = c->cw.at(p + ".linear1.bias"); f1.act = 3;
+    GemmParams f1 = plain(x, 256, c->cw.at(p + ".linear1.weight").p, hff, 512, B * n, 512, 256);
+    f1.bias = c->cw.at(p + ".linear1.bias").p; f1.act = 3;
     GEMM(c, s, "cvae.ff1", f1);
-    GemmParams f2 = plain(hff, 512, c->cw.at(p + ".linear2.weight"), t2, 256, B * n, 256, 512);
-    f2.bias = c->cw.at(p + ".linear2.bias"); f2.residual = x; f2.ldr = 256;
+    GemmParams f2 = plain(hff, 512, c->cw.at(p + ".linear2.weight").p, t2, 256, B * n, 256, 512);
+    f2.bias = c->cw.at(p + ".linear2.bias").p; f2.residual = x; f2.ldr = 256;
     GEMM(c, s, "cvae.ff2", f2);
     LAUNCH(c, s, "mocha_layernorm256", "cvae.norm", 0.0, B * n * 256.0 * 8,
-           launch_layernorm256(t2, c->cw.at(norm + ".weight"), c->cw.at(norm + ".bias"), out, B * n, s));
+           launch_layernorm256(t2, c->cw.at(norm + ".weight").p, c->cw.at(norm + ".bias").p, out, B * n, s));
     return 0;
 }
 
@@ -2723,7 +2524,7 @@ int mocha_cvae_sample(mocha_ctx* c, const float* cond, int B, float* out, float*
     float* t0 = c->cws.at("t0").p; float* mem = c->cws.at("mem").p;
     // PriorNet.encode (model_CVAE.py:69-79)
     LAUNCH(c, s, "mocha_cvae_prior_tokens", "cvae.tokens", 0.0, B * ntok * 256.0 * 8,
-           launch_cvae_prior_tokens(cond, c->cw.at("prior_net.mu_token"), c->cw.at("prior_net.logvar_token"), c->cw.at("pe"), t0, B, nc, s));
+           launch_cvae_prior_tokens(cond, c->cw.at("prior_net.mu_token").p, c->cw.at("prior_net.logvar_token").p, c->cw.at("pe").p, t0, B, nc, s));
     for (int l = 0; l < c->cvae_depth; ++l) {
         const std::string p = "prior_net.encoder.layers." + std::to_string(l);
         if ((rc = cvae_attn_block(c, s, p + ".self_attn", p + ".norm1", t0, ntok, nullptr, ntok, B))) return rc;
@@ -2733,7 +2534,7 @@ int mocha_cvae_sample(mocha_ctx* c, const float* cond, int B, float* out, float*
     float* xq = c->cws.at("t1").p;     // free until the first attention writes it: use hff as query buffer instead
     xq = c->cws.at("hff").p;           // (B, nq, 256) fits in (B, 182, 512)
     LAUNCH(c, s, "mocha_cvae_latent", "cvae.latent", 0.0, B * (nc + nq + 2) * 256.0 * 4,
-           launch_cvae_latent(t0, ntok, eps, cond, nc, c->cw.at("pe"), nq, mem, xq, mu, logvar, B, s));
+           launch_cvae_latent(t0, ntok, eps, cond, nc, c->cw.at("pe").p, nq, mem, xq, mu, logvar, B, s));
     HIPCHK(c, hipMemcpyAsync(t0, xq, (size_t)B * nq * 256 * sizeof(float), hipMemcpyDeviceToDevice, s));
     for (int l = 0; l < c->cvae_depth; ++l) {
         const std::string p = "decoder.decoder.layers." + std::to_string(l);
@@ -2771,18 +2572,16 @@ int mocha_featurize(mocha_ctx* c, const float* Yrot, const float* Ypos, const fl
     if (!c || !Yrot || !Ypos || !Yvel || !Yang || !X_raw || B < 0) return fail(c, MOCHA_ERR_ARG, "bad featurize arguments");
     HIPCHK(c, hipSetDevice(c->device));
     const int J = c->cfg.V + 1;
-    if (!c->bone_parents) {                       // parents = [-1] + (joint parents + 1), test_fullframework.py:101-102
+    if (!c->bone_parents.p) {                       // parents = [-1] + (joint parents + 1), test_fullframework.py:101-102
         std::vector<int> par(J);
         par[0] = -1;
         for (int i = 0; i < c->cfg.V; ++i) par[i + 1] = c->sk.parents[i] + 1;
-        void* dp = nullptr;
-        HIPCHK(c, hipMalloc(&dp, sizeof(int) * J));
-        HIPCHK(c, hipMemcpy(dp, par.data(), sizeof(int) * J, hipMemcpyHostToDevice));
-        c->bone_parents = (int*)dp;
+        int rc = reserve(c, c->bone_parents, (size_t)J); if (rc) return rc;
+        HIPCHK(c, hipMemcpy(c->bone_parents.p, par.data(), sizeof(int) * J, hipMemcpyHostToDevice));
     }
     hipStream_t s = (hipStream_t)stream;
     LAUNCH(c, s, "mocha_featurize", "featurize", B * 60.0 * J * 150, B * 60.0 * J * (13 + 15) * 4,
-           launch_featurize(Yrot, Ypos, Yvel, Yang, c->bone_parents, X_raw, B, c->cfg.T, J, s));
+           launch_featurize(Yrot, Ypos, Yvel, Yang, c->bone_parents.p, X_raw, B, c->cfg.T, J, s));
     return 0;
 }
 
@@ -2888,7 +2687,7 @@ int mocha_set_option(mocha_ctx* c, const char* name, int value) {
     if (n == "fold_upsample") { c->fold_upsample = value != 0; c->generation++; return 0; }
     if (n == "fold_joint") { c->fold_joint = value != 0; c->generation++; return 0; }
     if (n == "match_fold") { c->match_fold = value != 0; c->generation++; return 0; }
-    if (n == "scan8") { c->scan8 = value != 0; if (!value) c->bank8_valid = false; c->generation++; return 0; }     // the image is built at the next mocha_bank_set
+    if (n == "scan8") { c->scan8 = value != 0; if (!value) c->bank.b8_valid = false; c->generation++; return 0; }     // the image is built at the next mocha_bank_set
     if (n == "scan16") { c->scan16 = value != 0; c->generation++; return 0; }             // bank side takes effect at the next mocha_bank_set
     if (n == "attention_split_max") { c->attn_split_max = value < 0 ? 0 : value; c->generation++; return 0; }      // this context only
     if (n == "gemm_persistent_max_n") { c->gemm_persistent_max_n = value < 128 ? 128 : value; c->generation++; return 0; }
@@ -2900,8 +2699,8 @@ int mocha_set_option(mocha_ctx* c, const char* name, int value) {
     if (n == "inorm_split_max") { c->inorm_split_max = value < 0 ? 0 : value; c->generation++; return 0; }
     if (n == "pair_overlap") { c->pair_overlap = value != 0; c->generation++; return 0; }
     if (n == "adain_closed_form") { c->adain_closed = value != 0; c->generation++; return 0; }
-    if (n == "style_f64") { c->style_f64 = value != 0; c->bank_dec_valid = false; c->generation++; return 0; }     // cached bank constants: rebuilt at the next mocha_bank_set
-    if (n == "bank_dec_cache") { c->bank_dec_cache = value != 0; if (!value) c->bank_dec_valid = false; c->generation++; return 0; }     // takes effect at the next mocha_bank_set
+    if (n == "style_f64") { c->style_f64 = value != 0; c->bank.dec_valid = false; c->generation++; return 0; }     // cached bank constants: rebuilt at the next mocha_bank_set
+    if (n == "bank_dec_cache") { c->bank_dec_cache = value != 0; if (!value) c->bank.dec_valid = false; c->generation++; return 0; }     // takes effect at the next mocha_bank_set
     if (n == "bank_tiled") { c->use_tiled = value != 0; c->generation++; return 0; }
     if (n == "match_planes") { if (value != 1 && value != 2) return fail(c, MOCHA_ERR_ARG, "match_planes must be 1 or 2"); c->match_planes = value; c->generation++; return 0; }
     if (n == "select2") { c->select2 = value != 0; c->generation++; return 0; }
@@ -2921,8 +2720,8 @@ int mocha_set_option(mocha_ctx* c, const char* name, int value) {
     if (n == "gemm_f16x2") {                        // encoder / decoder / to_mot GEMMs on two fp16 planes, three passes (gemm_h2.hip); the bank's bound: next mocha_bank_set
         HIPCHK(c, hipSetDevice(c->device));
         if (value) { int rc = amax_alloc(c); if (rc) return rc; }
-        c->gemm_h2 = value != 0; c->amax_bank_ok = false;
-        for (int i = 0; i < mocha_ctx::MAX_SETS; ++i) c->amax_enc_of[i] = c->amax_dec_of[i] = c->amax_tok_of[i] = nullptr;
+        c->gemm_h2 = value != 0; c->bank.amax_ok = false;
+        for (int i = 0; i < mocha_ctx::MAX_SETS; ++i) c->sets[i].amax_enc_of = c->sets[i].amax_dec_of = c->sets[i].amax_tok_of = nullptr;
         c->generation++; return 0;
     }
     if (n == "attention_bf16x3") { c->attn_x3 = value != 0; c->generation++; return 0; }
@@ -2942,13 +2741,14 @@ int mocha_linear(mocha_ctx* c, const float* x, const float* w, const float* bias
     if (engine == 3) {                              // two fp16 planes, three passes: the activation bound is measured here (mocha_absmax)
         p.rows_per_win = 1024;
         if (!gemm_h2_supports(p)) return fail(c, MOCHA_ERR_ARG, "mocha_linear: M=%lld N=%d K=%d is outside the f16x2 engine", (long long)M, N, K);
-        void* img = nullptr; float* aux = nullptr;       // aux: [N] inverse weight scales, then the activation bounds of the "windows" (blocks of 1 024 rows here)
-        HIPCHK(c, hipMalloc(&img, gemm_h2_packed_elems(N, K) * sizeof(unsigned short)));
+        DeviceBuffer<unsigned short> img; DeviceBuffer<float> auxb;       // aux: [N] inverse weight scales, then the activation bounds of the "windows" (blocks of 1 024 rows here)
+        HIPCHK(c, img.reserve(gemm_h2_packed_elems(N, K)));
         const size_t n4 = ((size_t)N + 3) / 4 * 4;
         const int rpw = 1024; const long long nwin = (M + rpw - 1) / rpw;
-        hipError_t e = hipMalloc((void**)&aux, (n4 + (size_t)nwin) * sizeof(float));
+        hipError_t e = auxb.reserve(n4 + (size_t)nwin);
+        float* aux = auxb.p;
         if (e == hipSuccess) e = hipMemsetAsync(aux + n4, 0, (size_t)nwin * sizeof(float), s);
-        if (e == hipSuccess) e = launch_pack_h2(w, N, K, (unsigned short*)img, aux, s);
+        if (e == hipSuccess) e = launch_pack_h2(w, N, K, img.p, aux, s);
         for (long long w0 = 0; w0 < nwin && e == hipSuccess; w0 += 65535) {
             const long long nw = std::min<long long>(65535, nwin - w0);
             // the last block may be short: measured on its own
@@ -2956,10 +2756,9 @@ int mocha_linear(mocha_ctx* c, const float* x, const float* w, const float* bias
             if (full > 0) e = launch_absmax(x + (size_t)w0 * rpw * K, full, (long long)rpw * K, aux + n4 + w0, s);
             if (e == hipSuccess && full < nw) e = launch_absmax(x + (size_t)(w0 + full) * rpw * K, 1, (long long)(M % rpw) * K, aux + n4 + w0 + full, s);
         }
-        p.Wh2 = (const unsigned short*)img; p.w_inv = aux; p.a_amax = aux + n4; p.rows_per_win = rpw;
+        p.Wh2 = img.p; p.w_inv = aux; p.a_amax = aux + n4; p.rows_per_win = rpw;
         if (e == hipSuccess) e = launch_gemm_h2(p, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        (void)hipFree(img); if (aux) (void)hipFree(aux);
         if (e != hipSuccess) return fail(c, MOCHA_ERR_HIP, "mocha_linear: %s", hipGetErrorString(e));
         return 0;
     }
@@ -2970,13 +2769,12 @@ int mocha_linear(mocha_ctx* c, const float* x, const float* w, const float* bias
         return 0;
     }
     if (!gemm_x3_supports(p)) return fail(c, MOCHA_ERR_ARG, "mocha_linear: M=%lld N=%d K=%d is outside the bf16x3 engine", (long long)M, N, K);
-    void* img = nullptr;
-    HIPCHK(c, hipMalloc(&img, gemm_x3_packed_elems(N, K) * sizeof(unsigned short)));
-    hipError_t e = launch_pack_x3(w, N, K, (unsigned short*)img, s);
-    p.Wsplit = (const unsigned short*)img; p.persistent = c->gemm_persistent; p.persistent_max_n = c->gemm_persistent_max_n;
+    DeviceBuffer<unsigned short> img;
+    HIPCHK(c, img.reserve(gemm_x3_packed_elems(N, K)));
+    hipError_t e = launch_pack_x3(w, N, K, img.p, s);
+    p.Wsplit = img.p; p.persistent = c->gemm_persistent; p.persistent_max_n = c->gemm_persistent_max_n;
     if (e == hipSuccess) e = (c->gemm_x3r_min_n > 0 && N >= c->gemm_x3r_min_n && gemm_x3r_supports(p)) ? launch_gemm_x3r(p, s) : launch_gemm_x3(p, s);      // option "gemm_x3r_min_n": same bits
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(img);
     if (e != hipSuccess) return fail(c, MOCHA_ERR_HIP, "mocha_linear: %s", hipGetErrorString(e));
     return 0;
 }
@@ -2984,13 +2782,13 @@ int mocha_linear(mocha_ctx* c, const float* x, const float* w, const float* bias
 int mocha_scan_byte_state(mocha_ctx* c, int set, int32_t* state, void* stream) {
     if (!c || !state || set < 0 || set >= mocha_ctx::MAX_SETS) return fail(c, MOCHA_ERR_ARG, "mocha_scan_byte_state: bad argument");
     HIPCHK(c, hipSetDevice(c->device));
-    state[0] = c->scan8 && c->bank8_valid ? 1 : 0;
+    state[0] = c->scan8 && c->bank.b8_valid ? 1 : 0;
     state[1] = -1;
-    if (c->scan_keys[set]) {
+    if (c->sets[set].scan_keys.p) {
         unsigned w[2] = {0, 0};
         (void)stream;
         HIPCHK(c, hipDeviceSynchronize());                     // introspection: whatever stream the calls ran on
-        HIPCHK(c, hipMemcpy(w, c->scan_keys[set] + match_scan8_mode_word(), sizeof(w), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(w, c->sets[set].scan_keys.p + match_scan8_mode_word(), sizeof(w), hipMemcpyDeviceToHost));
         state[1] = (int32_t)w[1];
     }
     return 0;
@@ -2999,23 +2797,23 @@ int mocha_scan_byte_state(mocha_ctx* c, int set, int32_t* state, void* stream) {
 int mocha_bank_view(mocha_ctx* c, const float** cnt_nm, const float** encoded, const float** centroid, const float** row_norm2,
                     const void** cnt_bf16, int64_t* N) {
     if (!c) return MOCHA_ERR_ARG;
-    if (!c->bank_cnt || c->bank_N <= 0) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
-    if (cnt_nm) *cnt_nm = c->bank_cnt;
-    if (encoded) *encoded = c->bank_enc;
-    if (centroid) *centroid = c->bank_center;
-    if (row_norm2) *row_norm2 = c->bank_norm;
-    if (cnt_bf16) *cnt_bf16 = c->bank_is_bf16 ? c->bank_bf16 : nullptr;
-    if (N) *N = c->bank_N;
+    if (!c->bank.cnt || c->bank.N <= 0) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
+    if (cnt_nm) *cnt_nm = c->bank.cnt;
+    if (encoded) *encoded = c->bank.enc;
+    if (centroid) *centroid = c->bank.center.p;
+    if (row_norm2) *row_norm2 = c->bank.norm.p;
+    if (cnt_bf16) *cnt_bf16 = c->bank.is_bf16 ? c->bank.bf16.p : nullptr;
+    if (N) *N = c->bank.N;
     return 0;
 }
 
 int mocha_bank_export(mocha_ctx* c, float* cnt_nm, float* encoded, void* stream) {
     int rc = ready(c, 0); if (rc) return rc;
-    if (!c->bank_cnt || !c->bank_enc || c->bank_N <= 0) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set or mocha_bank_broadcast first");
-    const size_t bytes = (size_t)c->bank_N * 90 * 256 * sizeof(float);
+    if (!c->bank.cnt || !c->bank.enc || c->bank.N <= 0) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set or mocha_bank_broadcast first");
+    const size_t bytes = (size_t)c->bank.N * 90 * 256 * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
-    if (cnt_nm) HIPCHK(c, hipMemcpyAsync(cnt_nm, c->bank_cnt, bytes, hipMemcpyDeviceToDevice, s));
-    if (encoded) HIPCHK(c, hipMemcpyAsync(encoded, c->bank_enc, bytes, hipMemcpyDeviceToDevice, s));
+    if (cnt_nm) HIPCHK(c, hipMemcpyAsync(cnt_nm, c->bank.cnt, bytes, hipMemcpyDeviceToDevice, s));
+    if (encoded) HIPCHK(c, hipMemcpyAsync(encoded, c->bank.enc, bytes, hipMemcpyDeviceToDevice, s));
     return 0;
 }
 
