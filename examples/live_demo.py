@@ -1,0 +1,76 @@
+#!/usr/bin/env python3
+"""The synthetic demo of examples/demo_pair.py driven frame by frame: two live streams, each against its own character, pushed one
+mocap frame at a time through ``LiveSession`` - ring push + featurize, segmented characterize, pose heads and one post-processing
+frame per push, one captured graph - and written as two BVH files.
+
+    python examples/live_demo.py [--frames 180] [--out bench_outputs/live_demo]
+
+Weights, norms and motions are synthetic (see demo_pair.py for what to replace with real assets).
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from mocha_sigasia2023_amd import (Generator, LiveSession, MultiCharacterBank, PostProcessor, build_bank, synthetic,  # noqa: E402
+                                   synthetic_state_dict, write_bvh)
+from mocha_sigasia2023_amd.skeleton import LAYOUTS  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--frames", type=int, default=180, help="mocap frames pushed per stream (the first 59 fill the window)")
+ap.add_argument("--out", default="bench_outputs/live_demo")
+a = ap.parse_args()
+if a.frames < 60:
+    raise SystemExit("--frames must be at least 60: a stream's first pose comes with its 60th frame")
+os.makedirs(a.out, exist_ok=True)
+dev = torch.device("cuda:0")
+F, J, C, S = a.frames, 25, 15, 2
+
+# ---- model and (synthetic) statistics                                                        test_fullframework.py:40-98
+model = Generator(device=dev).load_state_dict(synthetic_state_dict(1777, 1.0)).eval()
+rng = np.random.Generator(np.random.PCG64(0))
+X_mean = (0.05 * rng.standard_normal((J, C))).astype(np.float32); X_std = rng.uniform(0.5, 1.5, (J, C)).astype(np.float32)
+Y_mean = (0.05 * rng.standard_normal((J, C))).astype(np.float32); Y_std = rng.uniform(0.2, 0.6, (J, C)).astype(np.float32)
+model.set_pose_norm(X_mean, X_std, Y_mean, Y_std)
+cnt_mean, cnt_std = (torch.from_numpy(x).to(dev) for x in synthetic.cnt_norm(7))
+
+# ---- two characters' banks from two clips, one multi-character bank                          :203-222, 271-277
+banks = []
+for seed in (12, 13):
+    clip = synthetic.smooth_bone_clip(seed, 60 + 200 - 1)
+    b = build_bank(model, model.featurize(*[synthetic.slide_windows(x) for x in clip]), raw=True)
+    banks.append((((b["cnt"] - cnt_mean) / cnt_std).reshape(-1, 90 * 256), b["encoded"]))
+bank = MultiCharacterBank(model, banks)
+
+# ---- two source clips arriving frame by frame, stream s retargeted to character s
+src = [[torch.from_numpy(x).to(dev) for x in synthetic.smooth_bone_clip(30 + s, F, phase=0.4 * s)] for s in range(S)]
+per = []
+for s in range(S):
+    _, rvel, rang, hipvel, contact = synthetic.postprocess_inputs(5 + s, F)
+    per.append([torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in
+                (rvel, rang, np.linalg.norm(hipvel, axis=-1).mean(-1).astype(np.float32), contact)])
+sess = LiveSession(bank, cnt_mean, cnt_std, streams=S, post=PostProcessor(model))
+sess.push(*[torch.stack([src[s][k][0] for s in range(S)]) for k in range(4)], *[torch.stack([per[s][k][0] for s in range(S)]) for k in range(4)],
+          characters=[0, 1])                                          # the first push captures the step
+sess.reset()
+torch.cuda.synchronize(); t0 = time.perf_counter()
+pos, eul = [], []
+for f in range(F):
+    o = sess.push(*[torch.stack([src[s][k][f] for s in range(S)]) for k in range(4)],
+                  *[torch.stack([per[s][k][f] for s in range(S)]) for k in range(4)])
+    if f >= 59:                                                       # both streams started together: both are valid from here on
+        pos.append(o["bvh_pos"].clone()); eul.append(o["bvh_euler"].clone())
+torch.cuda.synchronize(); dt = time.perf_counter() - t0
+pos, eul = torch.stack(pos, 1), torch.stack(eul, 1)                   # (S, F - 59, V, 3)
+
+names = ["Joint%02d" % i for i in range(24)]
+for s in range(S):
+    p = os.path.join(a.out, f"live_stream{s}.bvh")
+    write_bvh(p, names, LAYOUTS["mocha"]["parents"], pos[s], eul[s])
+    print(f"  {p}: {os.path.getsize(p)} bytes, {pos.shape[1]} frames")
+print(f"{F} pushes of {S} streams in {dt * 1e3:.1f} ms ({dt / F * 1e3:.3f} ms per push, host loop included)")
+assert bool(torch.isfinite(pos).all()) and bool(torch.isfinite(eul).all())

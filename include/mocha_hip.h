@@ -323,6 +323,62 @@ int mocha_postprocess(mocha_ctx* ctx, const mocha_post_cfg* cfg, const float* he
                       const float* src_rang, const float* src_speed, const unsigned char* contact, int n_clips, int n_frames,
                       double* pos, double* rot, double* ik_rot, double* bvh_pos, double* bvh_euler, void* stream);
 
+/* Resumable post-processing: ONE frame per clip and call, the loop's state in caller-owned device memory (the reference keeps it in
+ * Python objects across the iterations of its frame loop, test_fullframework.py:338-437 for the first frame, :492-632 after it, and
+ * :677-681 for the BVH channels - this call is one iteration of that loop).
+ *   mocha_post_state_bytes : bytes of state per clip (private layout, float64; the same for every configuration of a context).
+ *                            Host-side, no synchronisation.
+ *   mocha_postprocess_step : heads (n_clips,V,13), speed / src_speed (n_clips), src_rvel / src_rang (n_clips,3), contact
+ *                            (n_clips,n_contact) uint8 of the CURRENT frame -> pos (n_clips,V+1,3), rot / ik_rot (n_clips,V+1,4),
+ *                            bvh_pos / bvh_euler (n_clips,V,3; both or neither) of that frame, and the state advanced by one frame.
+ *                            state: n_clips * mocha_post_state_bytes device bytes.  ALL-ZERO BYTES MEAN "no frame seen yet": the next
+ *                            call takes the first-frame branch (root from identity, contact reset from the toe's global position and
+ *                            velocity, no blending, ik_rot = rot).  So a reset is a hipMemsetAsync of a clip's bytes and a snapshot /
+ *                            rollback is a device copy.  The frame counter lives in the state, not in an argument: the call may be
+ *                            captured into a HIP graph once and replayed for every frame, the first included.  The kernels are
+ *                            mocha_postprocess's own, run on one frame with the state loaded and stored around it: stepping a clip
+ *                            frame by frame from a zeroed state gives the bits of mocha_postprocess on the whole clip.  cfg as for mocha_postprocess, and
+ *                            the same cfg must be passed for every frame of a clip.  n_clips == 0 is a no-op; a NULL required pointer
+ *                            is MOCHA_ERR_ARG, never a launch.  No allocation, no synchronisation. */
+int64_t mocha_post_state_bytes(const mocha_ctx* ctx);
+int mocha_postprocess_step(mocha_ctx* ctx, const mocha_post_cfg* cfg, void* state, const float* heads, const float* speed,
+                           const float* src_rvel, const float* src_rang, const float* src_speed, const unsigned char* contact, int n_clips,
+                           double* pos, double* rot, double* ik_rot, double* bvh_pos, double* bvh_euler, void* stream);
+
+/* Live sessions: one mocap frame in, one characterized, root-integrated, foot-locked pose out, for 1..16 streams at once, every
+ * stream against its own character of a multi-character bank.  The reference builds every 60-frame window from the whole loaded clip
+ * (test_fullframework.py:126-186) and runs its frame loop over all windows afterwards (:338-437, 492-632, 677-681); here the window is
+ * a device-resident ring per stream and the frame loop advances one iteration per call.
+ *   mocha_live_state_bytes : bytes of the session buffer `live` for `streams` streams (caller-owned device memory, private layout: per
+ *                            stream the ring of the last 60 frames of local bone data, its head / fill counters, the state of
+ *                            mocha_postprocess_step, and the step's staging - X_raw, Y, heads, speed, effective ids).  Host-side.
+ *   mocha_live_reset       : zeroes the ring counters and the post state of the streams named in `which` (HOST array of n stream ids;
+ *                            NULL = all streams): they warm up again and their next valid frame takes the first-frame branch.
+ *                            Enqueued on `stream`, graph-safe, no synchronisation.  A freshly zeroed buffer is a reset session.
+ *   mocha_live_step        : pushes the NEW frame of every stream - Yrot (S,V+1,4) quaternions (w,x,y,z), Ypos / Yvel / Yang (S,V+1,3),
+ *                            root bone first, the per-frame slices of what mocha_featurize takes - into its ring, featurises the window
+ *                            "oldest ring frame ... newest ring frame" re-rooted on the newest one (bit-identical to mocha_featurize on
+ *                            the materialised window), runs the segmented characterize of the S windows (mocha_step_graph_segmented's
+ *                            kernels, raw = 1), mocha_pose_heads and one frame of mocha_postprocess_step with src_rvel / src_rang
+ *                            (S,3), src_speed (S), contact (S,n_contact) of that frame.  seg (S) device: the character of each stream.
+ *                            A stream whose ring holds fewer than 60 frames is WARMING: valid[s] = 0, idx[s] = -1 (it is matched against
+ *                            no bank row), its post state is not advanced and its rows of pos / rot / ik_rot / bvh_* are left untouched;
+ *                            its 60th push gives valid[s] = 1 and its first frame.  Otherwise idx[s] is the matched row local to the
+ *                            character's segment.  The whole step is captured into a HIP graph on first use and replayed, keyed on every
+ *                            pointer argument, `streams`, the contents of cfg (NULL = the demo's constants) and the generation: new ids
+ *                            in seg, new frame data, resets and the warming -> running transition are device data and do not re-capture;
+ *                            a new bank does.  While mocha_profile_start is active the step runs eagerly instead, launch by launch.
+ *                            Needs mocha_set_pose_norm and a segment table (mocha_bank_set_segments; one segment serves a single
+ *                            character), else MOCHA_ERR_STATE; streams outside 1..16 or a NULL required pointer (bvh_pos / bvh_euler:
+ *                            both or neither) is MOCHA_ERR_ARG, and nothing is launched.  Uses workspace set 0 like the other graph
+ *                            steps: one stream at a time per context. */
+int64_t mocha_live_state_bytes(const mocha_ctx* ctx, int streams);
+int mocha_live_reset(mocha_ctx* ctx, void* live, int streams, const int32_t* which, int n, void* stream);
+int mocha_live_step(mocha_ctx* ctx, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos,
+                    const float* Yvel, const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed,
+                    const unsigned char* contact, const int32_t* seg, const float* cnt_mean, const float* cnt_std, double* pos,
+                    double* rot, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx, int32_t* valid, void* stream);
+
 /* Bank build statistics: cnt_mean, cnt_std = np.mean(cnt, 0), np.std(cnt, 0) over the N bank entries
  * (compute_cnt_norm.py:174-175; population std), x (N, 90*256) -> mean, std (90*256). */
 int mocha_column_stats(mocha_ctx* ctx, const float* x, int64_t N, float* mean, float* std_, void* stream);

@@ -67,6 +67,11 @@ SIGNATURES = {
     "mocha_post_cfg_default": (None, [_vp]),
     "mocha_pose_heads": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "mocha_postprocess": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocha_post_state_bytes": (_i64, [_vp]),
+    "mocha_postprocess_step": (_i, [_vp] * 9 + [_i] + [_vp] * 6),
+    "mocha_live_state_bytes": (_i64, [_vp, _i]),
+    "mocha_live_reset": (_i, [_vp, _vp, _i, C.POINTER(C.c_int32), _i, _vp]),
+    "mocha_live_step": (_i, [_vp, _vp, _vp, _i] + [_vp] * 19),
     "mocha_column_stats": (_i, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "mocha_set_option": (_i, [_vp, C.c_char_p, _i]),
     "mocha_linear": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp]),

@@ -180,10 +180,20 @@ hipError_t launch_scale_shift(const float* x, const float* mean, const float* sd
 hipError_t featurize_init();
 hipError_t launch_featurize(const float* Yrot, const float* Ypos, const float* Yvel, const float* Yang, const int* parents /*J, device*/,
                             float* X, int B, int T, int J, hipStream_t s);
+// live sessions (live.hip): per stream a ring of the last LIVE_WINDOW frames of local bone data (rot (S,60,J,4), pos / vel / ang (S,60,J,3))
+// and counters (S,2) = {head, fill}, all device memory.  One call pushes the new frame (Yrot (S,J,4), Ypos / Yvel / Yang (S,J,3)) of
+// every stream, writes X (S,60,J,15) bit-identical to launch_featurize on the materialised windows (frames a filling ring does not hold
+// yet: identity / zeros), eff[s] = seg[s] once stream s holds 60 frames, else -1, and valid[s] = 1 / 0.
+static constexpr int LIVE_WINDOW = 60;
+struct LiveRing { int32_t* counters; float *rot, *pos, *vel, *ang; };
+hipError_t live_init();
+hipError_t launch_live_push(const LiveRing& r, const float* Yrot, const float* Ypos, const float* Yvel, const float* Yang, const int32_t* seg,
+                            const int* parents /*J, device*/, float* X, int32_t* eff, int32_t* valid, int S, int J, hipStream_t s);
 // post-processing of decoded windows (postprocess.hip)
 #define MOCHA_MAX_CONTACT 4
 #define MOCHA_MAX_CHAIN 8
 #define MOCHA_MAX_BONES 32
+static constexpr int POST_STATE_DOUBLES = 8 + MOCHA_MAX_BONES * 3 + MOCHA_MAX_CONTACT * 19;
 struct PostParams {
     const float* heads;             // (clips, frames, V, 13)
     const float* speed;             // (clips, frames)
@@ -197,9 +207,14 @@ struct PostParams {
     int parents[MOCHA_MAX_BONES];
     int contact_bones[MOCHA_MAX_CONTACT];
     double dt, max_length_buffer, foot_height, unlock_radius, halflife;
+    double* state;                  // resumable form only: (clips, POST_STATE_DOUBLES), else null
+    const int32_t* valid;           // resumable form only: (clips) or null; clips whose entry is 0 are skipped whole
 };
 hipError_t launch_pose_heads(const float* Y, float* heads, float* speed, int B, int T, int V, hipStream_t s);
 hipError_t launch_post_clip(const PostParams& p, hipStream_t s);
+// one frame per clip with the clip's state (p.state: POST_STATE_DOUBLES float64 words per clip, all-zero = no frame seen yet) in device
+// memory: p as for launch_post_clip with n_frames = 1, the same kernels
+hipError_t launch_post_step(const PostParams& p, hipStream_t s);
 // per-column mean and population std over N rows (bank build: cnt_norm)
 size_t column_mean_scratch_doubles(int cols);
 hipError_t launch_column_mean(const float* x, int64_t N, int cols, float* mean, double* scratch, hipStream_t s);

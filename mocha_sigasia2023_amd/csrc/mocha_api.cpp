@@ -264,14 +264,25 @@ struct mocha_ctx {
     struct StepKey {
         const void *x = nullptr, *mean = nullptr, *sd = nullptr; void *y = nullptr, *idx = nullptr; const void* seg = nullptr;
         int windows = 1; bool raw = false;
+        // mocha_live_step only: the session buffer, the new frame's arrays, the source's per-frame inputs, the outputs - and the
+        // post-processing constants, which the captured launch carries by value
+        const void* live[17] = {};
+        mocha_post_cfg post{};
         bool operator==(const StepKey& o) const {
-            return x == o.x && mean == o.mean && sd == o.sd && y == o.y && idx == o.idx && seg == o.seg && windows == o.windows && raw == o.raw;
+            if (!(x == o.x && mean == o.mean && sd == o.sd && y == o.y && idx == o.idx && seg == o.seg && windows == o.windows && raw == o.raw))
+                return false;
+            for (int i = 0; i < 17; ++i) if (live[i] != o.live[i]) return false;
+            const mocha_post_cfg &a = post, &b = o.post;
+            for (int i = 0; i < 4; ++i) if (a.contact_bones[i] != b.contact_bones[i]) return false;
+            return a.dt == b.dt && a.ik_max_length_buffer == b.ik_max_length_buffer && a.ik_foot_height == b.ik_foot_height &&
+                   a.ik_unlock_radius == b.ik_unlock_radius && a.ik_blending_halflife == b.ik_blending_halflife &&
+                   a.ik_enabled == b.ik_enabled && a.n_contact == b.n_contact && a.blend_enabled == b.blend_enabled;
         }
     };
     struct StepGraph {
         hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr;
         StepKey key; int64_t generation = -1;
-    } step[MAX_SETS], seg_step;                       // seg_step: mocha_step_graph_segmented (workspace set 0)
+    } step[MAX_SETS], seg_step, live_step;            // seg_step: mocha_step_graph_segmented, live_step: mocha_live_step (workspace set 0)
     hipStream_t cap_stream = nullptr;                 // capture happens on this internal stream (the caller's may be the null stream)
     ncclComm_t comm = nullptr; int comm_rank = 0, comm_size = 1;      // mocha_comm_init
     DeviceBuffer<long long> bcast_hdr;                                  // device: {entries, bf16?} header of mocha_bank_broadcast
@@ -1306,6 +1317,7 @@ int mocha_create(const mocha_cfg* cfg, int device, mocha_ctx** out) {
     if (e == hipSuccess) e = match_mfma_init();
     if (e == hipSuccess) e = match_refine_init();
     if (e == hipSuccess) e = featurize_init();
+    if (e == hipSuccess) e = live_init();
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming);
@@ -1320,7 +1332,7 @@ void mocha_destroy(mocha_ctx* c) {
     if (c->aux) (void)hipStreamDestroy(c->aux);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    for (auto* g : {&c->step[0], &c->step[1], &c->step[2], &c->seg_step}) {
+    for (auto* g : {&c->step[0], &c->step[1], &c->step[2], &c->seg_step, &c->live_step}) {
         if (g->exec) (void)hipGraphExecDestroy(g->exec);
         if (g->graph) (void)hipGraphDestroy(g->graph);
     }
@@ -2566,19 +2578,25 @@ int mocha_scale_shift(mocha_ctx* c, const float* x, const float* mean, const flo
     return 0;
 }
 
+// the (V+1)-bone skeleton's parents on the device, uploaded once (mocha_featurize, mocha_live_step)
+static int ensure_bone_parents(mocha_ctx* c) {
+    if (c->bone_parents.p) return 0;
+    const int J = c->cfg.V + 1;
+    std::vector<int> par(J);                        // parents = [-1] + (joint parents + 1), test_fullframework.py:101-102
+    par[0] = -1;
+    for (int i = 0; i < c->cfg.V; ++i) par[i + 1] = c->sk.parents[i] + 1;
+    int rc = reserve(c, c->bone_parents, (size_t)J); if (rc) return rc;
+    HIPCHK(c, hipMemcpy(c->bone_parents.p, par.data(), sizeof(int) * J, hipMemcpyHostToDevice));
+    return 0;
+}
+
 int mocha_featurize(mocha_ctx* c, const float* Yrot, const float* Ypos, const float* Yvel, const float* Yang, int B, float* X_raw,
                     void* stream) {
     if (c && B == 0) return 0;
     if (!c || !Yrot || !Ypos || !Yvel || !Yang || !X_raw || B < 0) return fail(c, MOCHA_ERR_ARG, "bad featurize arguments");
     HIPCHK(c, hipSetDevice(c->device));
     const int J = c->cfg.V + 1;
-    if (!c->bone_parents.p) {                       // parents = [-1] + (joint parents + 1), test_fullframework.py:101-102
-        std::vector<int> par(J);
-        par[0] = -1;
-        for (int i = 0; i < c->cfg.V; ++i) par[i + 1] = c->sk.parents[i] + 1;
-        int rc = reserve(c, c->bone_parents, (size_t)J); if (rc) return rc;
-        HIPCHK(c, hipMemcpy(c->bone_parents.p, par.data(), sizeof(int) * J, hipMemcpyHostToDevice));
-    }
+    { int rc = ensure_bone_parents(c); if (rc) return rc; }
     hipStream_t s = (hipStream_t)stream;
     LAUNCH(c, s, "mocha_featurize", "featurize", B * 60.0 * J * 150, B * 60.0 * J * (13 + 15) * 4,
            launch_featurize(Yrot, Ypos, Yvel, Yang, c->bone_parents.p, X_raw, B, c->cfg.T, J, s));
@@ -2610,23 +2628,16 @@ void mocha_post_cfg_default(mocha_post_cfg* cfg) {
     cfg->contact_bones[1] = 24;
 }
 
-int mocha_postprocess(mocha_ctx* c, const mocha_post_cfg* cfg, const float* heads, const float* speed, const float* src_rvel,
-                      const float* src_rang, const float* src_speed, const unsigned char* contact, int n_clips, int n_frames,
-                      double* pos, double* rot, double* ik_rot, double* bvh_pos, double* bvh_euler, void* stream) {
-    if (c && (n_clips == 0 || n_frames == 0)) return 0;
-    if (!c || !heads || !speed || !src_rvel || !src_rang || !src_speed || !contact || !pos || !rot || !ik_rot || n_clips < 0 ||
-        n_frames < 0 || (!bvh_pos) != (!bvh_euler))
-        return fail(c, MOCHA_ERR_ARG, "bad postprocess arguments");
+// The skeleton and the constants of a post-processing launch from cfg (NULL = the demo's), validated: what mocha_postprocess,
+// mocha_postprocess_step and mocha_live_step share.  The caller adds the arrays and the clip / frame counts.
+static int post_params(mocha_ctx* c, const mocha_post_cfg* cfg, PostParams& p) {
     mocha_post_cfg d;
     if (!cfg) { mocha_post_cfg_default(&d); cfg = &d; }
     const int J = c->cfg.V + 1;
     if (J > MOCHA_MAX_BONES) return fail(c, MOCHA_ERR_ARG, "postprocess: too many bones");
     if (cfg->n_contact < 0 || cfg->n_contact > MOCHA_MAX_CONTACT) return fail(c, MOCHA_ERR_ARG, "postprocess: n_contact must be 0..4");
     if (!(cfg->dt > 0.0)) return fail(c, MOCHA_ERR_ARG, "postprocess: dt must be positive");
-    PostParams p{};
-    p.heads = heads; p.speed = speed; p.src_rvel = src_rvel; p.src_rang = src_rang; p.src_speed = src_speed; p.contact = contact;
-    p.pos = pos; p.rot = rot; p.ik_rot = ik_rot; p.bvh_pos = bvh_pos; p.bvh_euler = bvh_euler;
-    p.n_clips = n_clips; p.n_frames = n_frames; p.V = c->cfg.V; p.n_contact = cfg->n_contact; p.ik_enabled = cfg->ik_enabled;
+    p.V = c->cfg.V; p.n_contact = cfg->n_contact; p.ik_enabled = cfg->ik_enabled;
     p.blend_enabled = cfg->blend_enabled;
     p.parents[0] = -1;                       // parents = [-1] + (joint parents + 1), test_fullframework.py:101-102
     for (int i = 0; i < c->cfg.V; ++i) p.parents[i + 1] = c->sk.parents[i] + 1;
@@ -2640,11 +2651,188 @@ int mocha_postprocess(mocha_ctx* c, const mocha_post_cfg* cfg, const float* head
     }
     p.dt = cfg->dt; p.max_length_buffer = cfg->ik_max_length_buffer; p.foot_height = cfg->ik_foot_height;
     p.unlock_radius = cfg->ik_unlock_radius; p.halflife = cfg->ik_blending_halflife;
+    return 0;
+}
+
+int mocha_postprocess(mocha_ctx* c, const mocha_post_cfg* cfg, const float* heads, const float* speed, const float* src_rvel,
+                      const float* src_rang, const float* src_speed, const unsigned char* contact, int n_clips, int n_frames,
+                      double* pos, double* rot, double* ik_rot, double* bvh_pos, double* bvh_euler, void* stream) {
+    if (c && (n_clips == 0 || n_frames == 0)) return 0;
+    if (!c || !heads || !speed || !src_rvel || !src_rang || !src_speed || !contact || !pos || !rot || !ik_rot || n_clips < 0 ||
+        n_frames < 0 || (!bvh_pos) != (!bvh_euler))
+        return fail(c, MOCHA_ERR_ARG, "bad postprocess arguments");
+    PostParams p{};
+    { int rc = post_params(c, cfg, p); if (rc) return rc; }
+    p.heads = heads; p.speed = speed; p.src_rvel = src_rvel; p.src_rang = src_rang; p.src_speed = src_speed; p.contact = contact;
+    p.pos = pos; p.rot = rot; p.ik_rot = ik_rot; p.bvh_pos = bvh_pos; p.bvh_euler = bvh_euler;
+    p.n_clips = n_clips; p.n_frames = n_frames;
+    const int J = c->cfg.V + 1;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     LAUNCH(c, s, "mocha_post_clip", "post.clip", 0.0, (double)n_clips * n_frames * (c->cfg.V * 13.0 * 4 + J * 11.0 * 8),
            launch_post_clip(p, s));
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------- resumable post-processing, live sessions
+int64_t mocha_post_state_bytes(const mocha_ctx* c) {
+    if (!c) return MOCHA_ERR_ARG;
+    return (int64_t)POST_STATE_DOUBLES * (int64_t)sizeof(double);
+}
+
+int mocha_postprocess_step(mocha_ctx* c, const mocha_post_cfg* cfg, void* state, const float* heads, const float* speed, const float* src_rvel,
+                           const float* src_rang, const float* src_speed, const unsigned char* contact, int n_clips, double* pos, double* rot,
+                           double* ik_rot, double* bvh_pos, double* bvh_euler, void* stream) {
+    if (c && n_clips == 0) return 0;
+    if (!c || !state || !heads || !speed || !src_rvel || !src_rang || !src_speed || !contact || !pos || !rot || !ik_rot || n_clips < 0 ||
+        (!bvh_pos) != (!bvh_euler))
+        return fail(c, MOCHA_ERR_ARG, "bad postprocess_step arguments: null argument");
+    PostParams p{};
+    { int rc = post_params(c, cfg, p); if (rc) return rc; }
+    p.heads = heads; p.speed = speed; p.src_rvel = src_rvel; p.src_rang = src_rang; p.src_speed = src_speed; p.contact = contact;
+    p.pos = pos; p.rot = rot; p.ik_rot = ik_rot; p.bvh_pos = bvh_pos; p.bvh_euler = bvh_euler;
+    p.n_clips = n_clips; p.n_frames = 1; p.state = static_cast<double*>(state);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    LAUNCH(c, s, "mocha_post_clip", "post.step", 0.0, (double)n_clips * (c->cfg.V * 13.0 * 4 + (c->cfg.V + 1) * 11.0 * 8 + 2.0 * POST_STATE_DOUBLES * 8),
+           launch_post_step(p, s));
+    return 0;
+}
+
+}  // extern "C"
+
+namespace {
+// A live session's buffer (caller-owned device memory, private layout): per stream the ring counters, the post state, the ring and the
+// step's staging.  Every section starts on a 256-byte boundary.
+struct LiveLayout {
+    size_t counters, post, rot, pos, vel, ang, xraw, y, heads, speed, eff, bytes;
+};
+LiveLayout live_layout(const mocha_ctx* c, int S) {
+    const size_t J = (size_t)c->cfg.V + 1, V = (size_t)c->cfg.V, T = LIVE_WINDOW, n = (size_t)S;
+    LiveLayout l{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) / 256 * 256; return at; };
+    l.counters = take(n * 2 * sizeof(int32_t));
+    l.post = take(n * POST_STATE_DOUBLES * sizeof(double));
+    l.rot = take(n * T * J * 4 * sizeof(float));
+    l.pos = take(n * T * J * 3 * sizeof(float));
+    l.vel = take(n * T * J * 3 * sizeof(float));
+    l.ang = take(n * T * J * 3 * sizeof(float));
+    l.xraw = take(n * T * J * (size_t)c->cfg.C_in * sizeof(float));
+    l.y = take(n * T * V * (size_t)c->cfg.C_in * sizeof(float));
+    l.heads = take(n * V * 13 * sizeof(float));
+    l.speed = take(n * sizeof(float));
+    l.eff = take(n * sizeof(int32_t));
+    l.bytes = off;
+    return l;
+}
+}  // namespace
+
+extern "C" {
+
+int64_t mocha_live_state_bytes(const mocha_ctx* c, int streams) {
+    if (!c || streams < 1 || streams > 16) return MOCHA_ERR_ARG;
+    return (int64_t)live_layout(c, streams).bytes;
+}
+
+int mocha_live_reset(mocha_ctx* c, void* live, int streams, const int32_t* which, int n, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (streams < 1 || streams > 16) return fail(c, MOCHA_ERR_ARG, "live_reset: 1 <= streams <= 16");
+    if (!live) return fail(c, MOCHA_ERR_ARG, "live_reset: null argument");
+    if (which && (n < 0 || n > streams)) return fail(c, MOCHA_ERR_ARG, "live_reset: n must be 0..streams");
+    for (int i = 0; which && i < n; ++i)
+        if (which[i] < 0 || which[i] >= streams) return fail(c, MOCHA_ERR_ARG, "live_reset: stream %d out of range 0..%d", (int)which[i], streams - 1);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const LiveLayout l = live_layout(c, streams);
+    char* base = static_cast<char*>(live);
+    const size_t pb = POST_STATE_DOUBLES * sizeof(double), cb = 2 * sizeof(int32_t);
+    if (!which) {
+        HIPCHK(c, hipMemsetAsync(base + l.counters, 0, cb * streams, s));
+        HIPCHK(c, hipMemsetAsync(base + l.post, 0, pb * streams, s));
+        return 0;
+    }
+    for (int i = 0; i < n; ++i) {
+        HIPCHK(c, hipMemsetAsync(base + l.counters + cb * which[i], 0, cb, s));
+        HIPCHK(c, hipMemsetAsync(base + l.post + pb * which[i], 0, pb, s));
+    }
+    return 0;
+}
+
+int mocha_live_step(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos, const float* Yvel,
+                    const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed, const unsigned char* contact,
+                    const int32_t* seg, const float* cnt_mean, const float* cnt_std, double* pos, double* rot, double* ik_rot, double* bvh_pos,
+                    double* bvh_euler, int32_t* idx, int32_t* valid, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (streams < 1 || streams > 16) return fail(c, MOCHA_ERR_ARG, "live_step: 1 <= streams <= 16");
+    if (!live || !Yrot || !Ypos || !Yvel || !Yang || !src_rvel || !src_rang || !src_speed || !contact || !seg || !cnt_mean || !cnt_std || !pos ||
+        !rot || !ik_rot || !idx || !valid || (!bvh_pos) != (!bvh_euler))
+        return fail(c, MOCHA_ERR_ARG, "live_step: null argument");
+    if (!c->finalized) return fail(c, MOCHA_ERR_STATE, "weights not finalised: call mocha_finalize_weights first");
+    if (!c->pose_norm.p) return fail(c, MOCHA_ERR_STATE, "live_step: no pose norm: call mocha_set_pose_norm first");
+    if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set_segments first");
+    if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    mocha_post_cfg d;
+    if (!cfg) { mocha_post_cfg_default(&d); cfg = &d; }
+    PostParams p{};
+    int rc = post_params(c, cfg, p); if (rc) return rc;
+    // everything the captured region needs exists before capture begins: the workspaces, the skeleton's parents (the segmented matcher's
+    // scratch was sized by mocha_bank_set_segments)
+    if ((rc = ready(c, streams))) return rc;
+    if ((rc = ensure_bone_parents(c))) return rc;
+
+    const LiveLayout l = live_layout(c, streams);
+    char* base = static_cast<char*>(live);
+    LiveRing ring;
+    ring.counters = reinterpret_cast<int32_t*>(base + l.counters);
+    ring.rot = reinterpret_cast<float*>(base + l.rot); ring.pos = reinterpret_cast<float*>(base + l.pos);
+    ring.vel = reinterpret_cast<float*>(base + l.vel); ring.ang = reinterpret_cast<float*>(base + l.ang);
+    float* xraw = reinterpret_cast<float*>(base + l.xraw);
+    float* ystage = reinterpret_cast<float*>(base + l.y);
+    float* heads = reinterpret_cast<float*>(base + l.heads);
+    float* speed = reinterpret_cast<float*>(base + l.speed);
+    int32_t* eff = reinterpret_cast<int32_t*>(base + l.eff);
+    double* pstate = reinterpret_cast<double*>(base + l.post);
+    p.heads = heads; p.speed = speed; p.src_rvel = src_rvel; p.src_rang = src_rang; p.src_speed = src_speed; p.contact = contact;
+    p.pos = pos; p.rot = rot; p.ik_rot = ik_rot; p.bvh_pos = bvh_pos; p.bvh_euler = bvh_euler;
+    p.n_clips = streams; p.n_frames = 1; p.state = pstate; p.valid = valid;
+    const int J = c->cfg.V + 1, V = c->cfg.V;
+
+    // ring push + featurize -> segmented characterize of the S windows with the effective ids -> pose heads -> one post-processing frame
+    auto body = [&](hipStream_t cs) -> int {
+        LAUNCH(c, cs, "mocha_live_push", "live.push", streams * 60.0 * J * 150, streams * (60.0 * J * (13 + 15) + J * 26.0) * 4,
+               launch_live_push(ring, Yrot, Ypos, Yvel, Yang, seg, c->bone_parents.p, xraw, eff, valid, streams, J, cs));
+        c->lane = 0;
+        const int r = characterize_impl(c, xraw, streams, cnt_mean, cnt_std, ystage, idx, cs, true, eff);
+        c->cur = 0;
+        if (r) return r;
+        LAUNCH(c, cs, "mocha_pose_heads", "live.heads", 0.0, streams * (60.0 * 12 + V * 28.0 * 4), launch_pose_heads(ystage, heads, speed, streams, c->cfg.T, V, cs));
+        LAUNCH(c, cs, "mocha_post_clip", "live.post", 0.0, (double)streams * (V * 13.0 * 4 + J * 11.0 * 8 + 2.0 * POST_STATE_DOUBLES * 8),
+               launch_post_step(p, cs));
+        return 0;
+    };
+    hipStream_t s = (hipStream_t)stream;
+    // while profiling (mocha_profile_start) the step runs eagerly, launch by launch, so that every kernel of it is timed
+    if (c->prof_on) return body(s);
+
+    mocha_ctx::StepKey key;
+    key.x = live; key.mean = cnt_mean; key.sd = cnt_std; key.idx = idx; key.seg = seg; key.windows = streams; key.raw = true;
+    const void* ptrs[17] = {Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, pos, rot, ik_rot, bvh_pos, bvh_euler, valid, nullptr, nullptr, nullptr};
+    for (int i = 0; i < 17; ++i) key.live[i] = ptrs[i];
+    key.post = *cfg;
+    const auto& g = c->live_step;
+    if (!(g.exec && g.key == key && g.generation == c->generation)) {
+        // Before a capture: one eager characterize of the staging windows with every id -1 (no bank row is matched, no state of the
+        // session moves), so that whatever the kernels of the step make on first use - the plane GEMMs' weight images - exists and the
+        // captured step takes the kernels every later step takes.
+        HIPCHK(c, hipMemsetAsync(xraw, 0, (size_t)streams * 60 * J * c->cfg.C_in * sizeof(float), s));
+        HIPCHK(c, hipMemsetAsync(eff, 0xFF, (size_t)streams * sizeof(int32_t), s));
+        c->lane = 0;
+        rc = characterize_impl(c, xraw, streams, cnt_mean, cnt_std, ystage, nullptr, s, true, eff);
+        c->cur = 0;
+        if (rc) return rc;
+    }
+    return step_replay(c, c->live_step, key, s, body);
 }
 
 int mocha_column_stats(mocha_ctx* c, const float* x, int64_t N, float* mean, float* std_, void* stream) {

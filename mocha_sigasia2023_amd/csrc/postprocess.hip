@@ -8,8 +8,8 @@
 //                      and the two-bone IK (motion/quat.py:295-343), then the root merge + Euler channels the BVH
 //                      writer consumes.  float64, because the reference's state arrays are NumPy float64.
 //
-// The previous frame's pose is read back from the output arrays, so the per-lane state is only the root transform and
-// the contact records.
+// Both kernels also serve the resumable form (launch_post_step, live sessions): ONE frame per clip and launch, the per-lane state (root
+// transform, the bone's previous position, the contact record) loaded from and stored to device memory around it.
 #include "kernels.h"
 
 namespace mocha {
@@ -113,6 +113,12 @@ struct ContactRec {
     bool state, lock;
     d3 position, velocity, point, target, off_x, off_v;
 };
+// State of one clip between two launches of the resumable form, POST_STATE_DOUBLES 8-byte words: [0] frames seen (int64; 0 = none: the
+// next frame takes the first-frame branch, so all-zero bytes are a reset clip), [1..3] root position, [4..7] root rotation,
+// [8 + 3 j ..] bone j's previous position, then per contact [flags (int64: bit 0 state, bit 1 lock) | position | velocity | point |
+// target | off_x | off_v].
+static constexpr int POST_STATE_CONTACT0 = 8 + MOCHA_MAX_BONES * 3, POST_STATE_CONTACT = 19;
+static_assert(POST_STATE_CONTACT0 + MOCHA_MAX_CONTACT * POST_STATE_CONTACT == POST_STATE_DOUBLES, "post state layout");
 
 // One WAVE per clip (round 3; the first version ran a clip in one lane, 64 clips per wave): the frame loop is sequential, but inside a
 // frame the work has width - lane j owns bone j (its blended position is a per-bone recurrence over frames, kept in a register), lane 0
@@ -126,6 +132,7 @@ __global__ __launch_bounds__(64) void mocha_post_clip(PostParams p) {
     __shared__ double sh_ikq[MOCHA_MAX_CONTACT][2][4];
     __shared__ int sh_ikv[MOCHA_MAX_CONTACT];
     const int clip = blockIdx.x, lane = threadIdx.x;
+    if (p.valid && p.valid[clip] == 0) return;                  // resumable form: a clip that is not stepped (uniform over the workgroup)
     const int V = p.V, J = V + 1, N = p.n_frames;
     const float* heads = p.heads + (size_t)clip * N * V * 13;
     const float* speed = p.speed + (size_t)clip * N;
@@ -169,6 +176,24 @@ __global__ __launch_bounds__(64) void mocha_post_clip(PostParams p) {
     float hn[13];                                               // bone lanes
     float r_speed = 0.f, r_sspeed = 1.f, r_rv[3] = {0, 0, 0}, r_ra[3] = {0, 0, 0};            // lane 0
     unsigned char c_flag = 0;                                   // contact lanes
+    // Resumable form (launch_post_step): the frames seen so far and the per-lane state come from / go back to device memory.  The
+    // first-frame branch below is taken by frame 0 of a clip that has seen no frame yet; without a state that is frame 0 of the launch.
+    double* S = p.state ? p.state + (size_t)clip * POST_STATE_DOUBLES : nullptr;
+    double* cs = S ? S + POST_STATE_CONTACT0 + (is_contact ? ci : 0) * POST_STATE_CONTACT : nullptr;
+    long long seen = 0;
+    if (S) {
+        seen = *reinterpret_cast<const long long*>(S);
+        if (seen != 0) {
+            if (lane == 0) { root_pos = ld3(S + 1); root_rot = ldq(S + 4); }
+            if (is_joint) prev_p = ld3(S + 8 + lane * 3);
+            if (is_contact) {
+                const long long fl = *reinterpret_cast<const long long*>(cs);
+                cr.state = (fl & 1) != 0; cr.lock = (fl & 2) != 0;
+                cr.position = ld3(cs + 1); cr.velocity = ld3(cs + 4); cr.point = ld3(cs + 7);
+                cr.target = ld3(cs + 10); cr.off_x = ld3(cs + 13); cr.off_v = ld3(cs + 16);
+            }
+        }
+    }
     auto fetch = [&](int i) __attribute__((always_inline)) {
         if (i >= N) return;
         if (is_bone) {
@@ -186,6 +211,7 @@ __global__ __launch_bounds__(64) void mocha_post_clip(PostParams p) {
     fetch(0);
 
     for (int i = 0; i < N; ++i) {
+        const bool first = i == 0 && seen == 0;
         // this frame's inputs into locals, the next frame's on their way
         float h[13];
 #pragma unroll
@@ -219,7 +245,7 @@ __global__ __launch_bounds__(64) void mocha_post_clip(PostParams p) {
         }
         if (is_joint) {
             // positions (blended with the previous frame's after the first one, :537/:627), rotations
-            if (i && p.blend_enabled) pj = (prev_p + vj * dt) * 0.5 + pj * 0.5;
+            if (!first && p.blend_enabled) pj = (prev_p + vj * dt) * 0.5 + pj * 0.5;
             prev_p = pj;
             st3(pos + lane * 3, pj);
             stq(rot + lane * 4, rj);
@@ -230,7 +256,7 @@ __global__ __launch_bounds__(64) void mocha_post_clip(PostParams p) {
         __syncthreads();
 
         if (is_contact) {
-            if (i == 0) {
+            if (first) {
                 // contact reset with the global position / velocity of the toe (fk_vel_bone, quat.py:207-238)
                 const d3 wv = ld3(sh_w), wa = ld3(sh_w + 3);
                 d3 gv = {0, 0, 0}, ga = {0, 0, 0}, gpp = {0, 0, 0};
@@ -240,7 +266,7 @@ __global__ __launch_bounds__(64) void mocha_post_clip(PostParams p) {
                     d3 lv, la;
                     if (b == 0) { lv = wv; la = wa; }
                     else {
-                        const float* hb = heads + (size_t)(b - 1) * 13;                        // frame 0
+                        const float* hb = heads + (size_t)(b - 1) * 13;                        // frame 0 (the reset happens in the launch's first frame only)
                         lv = {(double)hb[7], (double)hb[8], (double)hb[9]};
                         la = {(double)hb[10], (double)hb[11], (double)hb[12]};
                     }
@@ -328,6 +354,18 @@ __global__ __launch_bounds__(64) void mocha_post_clip(PostParams p) {
         }
         __syncthreads();                                        // the LDS exchange is rewritten by the next frame
     }
+    if (S) {
+        if (lane == 0) {
+            *reinterpret_cast<long long*>(S) = seen + N;
+            st3(S + 1, root_pos); stq(S + 4, root_rot);
+        }
+        if (is_joint) st3(S + 8 + lane * 3, prev_p);
+        if (is_contact) {
+            *reinterpret_cast<long long*>(cs) = (cr.state ? 1 : 0) | (cr.lock ? 2 : 0);
+            st3(cs + 1, cr.position); st3(cs + 4, cr.velocity); st3(cs + 7, cr.point);
+            st3(cs + 10, cr.target); st3(cs + 13, cr.off_x); st3(cs + 16, cr.off_v);
+        }
+    }
 }
 
 // BVH channels (test_fullframework.py:677-681; quat.py:346-355): fold the synthetic root into bone 1, Euler angles in degrees.  No
@@ -339,6 +377,7 @@ __global__ __launch_bounds__(256) void mocha_post_bvh(PostParams p) {
     if (t >= (long long)p.n_clips * N * V) return;
     const int j = (int)(t % V) + 1;
     const long long ci = t / V;                     // clip * N + frame
+    if (p.valid && p.valid[ci / N] == 0) return;    // resumable form: a clip that is not stepped keeps its rows
     const double* pos = p.pos + (size_t)ci * J * 3;
     const double* ikr = p.ik_rot + (size_t)ci * J * 4;
     double* bp = p.bvh_pos + ((size_t)ci * V + (j - 1)) * 3;
@@ -365,6 +404,14 @@ hipError_t launch_post_clip(const PostParams& p, hipStream_t s) {
         hipLaunchKernelGGL(mocha_post_bvh, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p);
     }
     return hipGetLastError();
+}
+
+// The resumable form: the SAME two kernels on one frame per clip (p.n_frames = 1), the frame loop's state loaded from / stored to
+// p.state around it and clips with valid[clip] == 0 skipped - so stepping a clip frame by frame executes, frame for frame, the
+// instructions mocha_postprocess executes on the whole clip.
+hipError_t launch_post_step(const PostParams& p, hipStream_t s) {
+    if (p.n_frames != 1 || !p.state) return hipErrorInvalidValue;
+    return launch_post_clip(p, s);
 }
 
 }  // namespace mocha

@@ -1,0 +1,132 @@
+"""Live sessions: one mocap frame in, one characterized, root-integrated, foot-locked pose out (``mocha_live_step``).
+
+A ``LiveSession`` keeps, per stream, the last 60 frames of local bone data in a ring on the device, and the state of the demo's frame
+loop (root transform, blended positions, contact records).  ``push`` copies the new frame of every stream into fixed buffers and
+replays ONE captured HIP graph: ring push + featurize -> segmented characterize of the streams' windows, every stream against its own
+character of a ``MultiCharacterBank`` -> pose heads -> one post-processing frame.  Nothing is computed on the host and nothing
+synchronises; a stream that has not seen 60 frames yet is reported as ``valid == 0`` and its output rows are left as they were.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from .generator import DIM, NTOK, _dev_f32, _ptr, _stream
+from .multi_character import MultiCharacterBank
+from .postprocess import PostProcessor
+
+
+class LiveSession:
+    """``streams`` live streams (1..16) on ``bank``'s context.  ``post``: the post-processing constants (default: the demo's);
+    ``bvh``: also produce the BVH writer's channels.  Needs ``Generator.set_pose_norm``."""
+
+    def __init__(self, bank: MultiCharacterBank, cnt_mean, cnt_std, streams: int = 1, post: Optional[PostProcessor] = None, bvh: bool = True):
+        if not 1 <= int(streams) <= 16:
+            raise ValueError("streams must be 1..16")
+        self.bank, self.model = bank, bank.model
+        m, dev = self.model, bank.model.device
+        if post is not None and post.model is not m:
+            raise ValueError("LiveSession: post belongs to another model")
+        self.post = post or PostProcessor(m)
+        self.streams = S = int(streams)
+        self.bvh = bool(bvh)
+        self.mean = _dev_f32(cnt_mean, dev, (NTOK, DIM), "cnt_mean")
+        self.std = _dev_f32(cnt_std, dev, (NTOK, DIM), "cnt_std")
+        J, V = m.V + 1, m.V
+        self.n_contact = max(int(self.post.cfg.n_contact), 1)
+        nbytes = int(m._ctx.lib.mocha_live_state_bytes(m._ctx.h, S))
+        if nbytes <= 0:
+            raise RuntimeError("mocha_live_state_bytes failed")
+        self.live = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)          # zeroed = a reset session
+
+        def f32(*shape):
+            return torch.zeros(shape, dtype=torch.float32, device=dev)
+        # the fixed input buffers the captured step reads ...
+        self.rot, self.pos, self.vel, self.ang = f32(S, J, 4), f32(S, J, 3), f32(S, J, 3), f32(S, J, 3)
+        self.rvel, self.rang, self.speed = f32(S, 3), f32(S, 3), f32(S)
+        self.contact = torch.zeros((S, self.n_contact), dtype=torch.uint8, device=dev)
+        self.ids = torch.zeros((S,), dtype=torch.int32, device=dev)
+        # ... and the outputs it writes
+        f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)   # noqa: E731
+        self.out = {"pos": f64(S, J, 3), "rot": f64(S, J, 4), "ik_rot": f64(S, J, 4)}
+        if self.bvh:
+            self.out["bvh_pos"], self.out["bvh_euler"] = f64(S, V, 3), f64(S, V, 3)
+        self.out["idx"] = torch.full((S,), -1, dtype=torch.int32, device=dev)
+        self.out["valid"] = torch.zeros((S,), dtype=torch.int32, device=dev)
+        bank._ensure()
+
+    @property
+    def characters(self) -> torch.Tensor:
+        """The step's own character ids (streams,) int32 on the device: a producer may write them in place."""
+        return self.ids
+
+    def _frame(self, a, buf, name):
+        t = _dev_f32(a, buf.device, None, name)
+        if t.numel() != buf.numel():
+            raise ValueError(f"LiveSession.push: {name} has {t.numel()} values, expected {tuple(buf.shape)}")
+        buf.copy_(t.reshape(buf.shape), non_blocking=True)
+
+    def push(self, Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, characters=None):
+        """The new frame of every stream: Yrot (S,V+1,4) (w,x,y,z), Ypos / Yvel / Yang (S,V+1,3), root bone first; src_rvel / src_rang
+        (S,3), src_speed (S,), contact (S,n_contact) of that frame [, characters: one id per stream; default: the ids already set].
+        Returns the session's own device tensors - pos (S,V+1,3), rot / ik_rot (S,V+1,4), (bvh_pos / bvh_euler (S,V,3)), idx (S,) the
+        matched row local to the stream's character (-1 while warming up), valid (S,) - overwritten by the next push.  Rows of a stream
+        with valid == 0 are not written.  No host synchronisation."""
+        if characters is not None:
+            self.ids.copy_(self.bank._ids(characters, self.streams), non_blocking=True)
+        for a, buf, name in ((Yrot, self.rot, "Yrot"), (Ypos, self.pos, "Ypos"), (Yvel, self.vel, "Yvel"), (Yang, self.ang, "Yang"),
+                             (src_rvel, self.rvel, "src_rvel"), (src_rang, self.rang, "src_rang")):
+            self._frame(a, buf, name)
+        self._frame(torch.as_tensor(src_speed, dtype=torch.float32).reshape(-1), self.speed, "src_speed")
+        ct = torch.as_tensor(contact).to(device=self.contact.device, dtype=torch.uint8)
+        if ct.numel() != self.contact.numel():
+            raise ValueError(f"LiveSession.push: contact has {ct.numel()} values, expected {tuple(self.contact.shape)}")
+        self.contact.copy_(ct.reshape(self.contact.shape), non_blocking=True)
+        return self.replay()
+
+    def replay(self):
+        """The step on what the fixed buffers hold (a producer on the device may have written them in place)."""
+        self.bank._ensure()
+        o = self.out
+        self.model._ctx.call("mocha_live_step", C.byref(self.post.cfg), _ptr(self.live), self.streams, _ptr(self.rot), _ptr(self.pos), _ptr(self.vel),
+                             _ptr(self.ang), _ptr(self.rvel), _ptr(self.rang), _ptr(self.speed), _ptr(self.contact), _ptr(self.ids),
+                             _ptr(self.mean), _ptr(self.std), _ptr(o["pos"]), _ptr(o["rot"]), _ptr(o["ik_rot"]),
+                             _ptr(o["bvh_pos"]) if self.bvh else None, _ptr(o["bvh_euler"]) if self.bvh else None, _ptr(o["idx"]), _ptr(o["valid"]),
+                             _stream())
+        return o
+
+    def reset(self, streams: Optional[Sequence[int]] = None):
+        """All streams, or the listed ones, start over: their rings warm up again and their next valid frame is a first frame."""
+        ctx = self.model._ctx
+        if streams is None:
+            ctx.call("mocha_live_reset", _ptr(self.live), self.streams, None, 0, _stream())
+        else:
+            ids = [int(s) for s in streams]
+            arr = (C.c_int32 * max(len(ids), 1))(*ids)
+            ctx.call("mocha_live_reset", _ptr(self.live), self.streams, arr, len(ids), _stream())
+        return self
+
+    def run_clip(self, Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, characters=None):
+        """Convenience: pushes the F frames of every stream's clip - Yrot (S,F,V+1,4), Ypos / Yvel / Yang (S,F,V+1,3); src_rvel /
+        src_rang (S,F,3), src_speed (S,F), contact (S,F,n_contact), frame f being the inputs of the push of frame f - into a RESET
+        session and returns the stacked valid frames: a dict of (S, F - 59, ...) tensors (idx (S, F - 59))."""
+        dev, S = self.model.device, self.streams
+        to = lambda a, dt: torch.as_tensor(a).to(device=dev, dtype=dt)             # noqa: E731
+        rot, pos, vel, ang, rv, ra = (to(a, torch.float32) for a in (Yrot, Ypos, Yvel, Yang, src_rvel, src_rang))
+        sp = to(src_speed, torch.float32).reshape(S, -1)
+        F = rot.shape[1]
+        ct = to(contact, torch.uint8).reshape(S, F, -1)
+        if F < 60:
+            raise ValueError("run_clip: a clip needs at least 60 frames")
+        self.reset()
+        keep = [k for k in self.out if k != "valid"]
+        frames = {k: [] for k in keep}
+        for f in range(F):
+            o = self.push(rot[:, f], pos[:, f], vel[:, f], ang[:, f], rv[:, f], ra[:, f], sp[:, f], ct[:, f], characters if f == 0 else None)
+            if f >= 59:
+                for k in keep:
+                    frames[k].append(o[k].clone())
+        return {k: torch.stack(v, dim=1) for k, v in frames.items()}

@@ -1,6 +1,6 @@
 """Host mirror of the demo's post-processing: decoded windows -> animated skeleton -> BVH.
 
-``pose_heads`` and ``PostProcessor.run`` call the HIP kernels of csrc/postprocess.hip through the C ABI; nothing here
+``pose_heads``, ``PostProcessor.run`` and ``PostProcessor.step`` call the HIP kernels of csrc/postprocess.hip through the C ABI; nothing here
 computes on the host except the final text formatting of ``write_bvh`` (the reference's motion/bvh.py:179-224 layout).
 """
 from __future__ import annotations
@@ -32,7 +32,8 @@ def pose_heads(model: Generator, Y):
 
 
 class PostProcessor:
-    """Root integration + blending + foot-lock IK of whole clips on the device, one lane per clip."""
+    """Root integration + blending + foot-lock IK on the device, one wave per clip: whole clips (``run``) or one frame per call with
+    the loop's state kept in a device tensor (``state`` / ``step``)."""
 
     def __init__(self, model: Generator, contact_bones: Optional[Sequence[int]] = None, ik_enabled: bool = True, blend: bool = True, **ik):
         self.model = model
@@ -84,6 +85,56 @@ class PostProcessor:
         return out
 
 
+    def state(self, n_clips: int = 1) -> torch.Tensor:
+        """A zeroed state for ``step``: (n_clips, mocha_post_state_bytes) uint8 on the device.  All-zero bytes mean "no frame seen
+        yet", so ``state.zero_()`` (or zeroing one clip's row) is a reset, and ``state.clone()`` / ``state.copy_`` a snapshot / rollback."""
+        ctx = self.model._ctx
+        nbytes = int(ctx.lib.mocha_post_state_bytes(ctx.h))
+        if nbytes <= 0:
+            raise RuntimeError("mocha_post_state_bytes failed")
+        return torch.zeros((int(n_clips), nbytes), dtype=torch.uint8, device=self.model.device)
+
+    def step(self, state, heads, speed, src_rvel, src_rang, src_speed, contact, bvh: bool = True, out: Optional[dict] = None):
+        """ONE frame of every clip of ``state`` (``mocha_postprocess_step``): heads (V,13) or (C,V,13), speed / src_speed () or (C,),
+        src_rvel / src_rang (3,) or (C,3), contact (n_contact,) or (C,n_contact) of the current frame.  Advances ``state`` in place and
+        returns the same dict as ``run`` for that one frame: pos (.., V+1, 3), rot / ik_rot (.., V+1, 4), bvh_pos / bvh_euler (.., V, 3).
+        Stepping a clip frame by frame from a zeroed state gives exactly what ``run`` gives for the whole clip.  ``out``: a dict of
+        tensors from an earlier call to write into (fixed buffers, e.g. under graph capture)."""
+        m, dev, V = self.model, self.model.device, self.model.V
+        if not (isinstance(state, torch.Tensor) and state.dtype == torch.uint8 and state.dim() == 2 and state.is_contiguous()
+                and state.device == dev):
+            raise ValueError("postprocess step: state must come from PostProcessor.state()")
+        nclip = state.shape[0]
+        heads = torch.as_tensor(heads)
+        single = heads.dim() == 2
+        if single and nclip != 1:
+            raise ValueError(f"postprocess step: heads of one clip for a state of {nclip}")
+        lead = () if single else (nclip,)
+
+        def f32(a, tail, name):
+            return _dev_f32(torch.as_tensor(a).reshape((-1,) + tail), dev, None, name)
+        h = f32(heads, (V, 13), "heads")
+        sp, ssp = f32(speed, (), "speed"), f32(src_speed, (), "src_speed")
+        rv, ra = f32(src_rvel, (3,), "src_rvel"), f32(src_rang, (3,), "src_rang")
+        nc = self.cfg.n_contact
+        ct = torch.as_tensor(contact).to(device=dev, dtype=torch.uint8).reshape(-1, max(nc, 1)).contiguous()
+        for t, name in ((h, "heads"), (sp, "speed"), (ssp, "src_speed"), (rv, "src_rvel"), (ra, "src_rang"), (ct, "contact")):
+            if t.shape[0] != nclip:
+                raise ValueError(f"postprocess step: {name} has {t.shape[0]} rows, expected {nclip}")
+        if out is None:
+            out = {"pos": torch.empty(lead + (V + 1, 3), dtype=torch.float64, device=dev),
+                   "rot": torch.empty(lead + (V + 1, 4), dtype=torch.float64, device=dev),
+                   "ik_rot": torch.empty(lead + (V + 1, 4), dtype=torch.float64, device=dev)}
+            if bvh:
+                out["bvh_pos"] = torch.empty(lead + (V, 3), dtype=torch.float64, device=dev)
+                out["bvh_euler"] = torch.empty(lead + (V, 3), dtype=torch.float64, device=dev)
+        bvh = "bvh_pos" in out
+        m._ctx.call("mocha_postprocess_step", C.byref(self.cfg), _ptr(state), _ptr(h), _ptr(sp), _ptr(rv), _ptr(ra), _ptr(ssp), _ptr(ct), nclip,
+                    _ptr(out["pos"]), _ptr(out["rot"]), _ptr(out["ik_rot"]),
+                    _ptr(out["bvh_pos"]) if bvh else None, _ptr(out["bvh_euler"]) if bvh else None, _stream())
+        return out
+
+
 def retarget_clip(bank, src_X, cnt_mean, cnt_std, src_rvel, src_rang, src_speed, contact, raw: bool = False,
                   post: Optional[PostProcessor] = None, bvh: bool = True):
     """The NN branch of the demo from featurised source windows to the animated skeleton, all on the device:
@@ -114,6 +165,22 @@ def retarget_clip_ours(session, src_encoded, src_cnt, src_rvel, src_rang, src_sp
         Y = Y * std + mean
     heads, speed = pose_heads(m, Y)
     return (post or PostProcessor(m)).run(heads, speed, src_rvel, src_rang, src_speed, contact, bvh=bvh)
+
+
+def retarget_frame_ours(session, post_state, src_encoded, src_cnt, src_rvel, src_rang, src_speed, contact, eps=None,
+                        deterministic: bool = False, post: Optional[PostProcessor] = None, bvh: bool = True, denorm=None):
+    """``retarget_clip_ours`` one frame at a time: one ``OursSession.step`` (test_fullframework.py:446-457), the pose heads of the
+    decoded window and ONE frame of the post-processing (:492-632, 677-681) whose state lives in ``post_state``
+    (``PostProcessor.state(B)``, zeroed before the clip's first frame) - a posed frame per call, no decoded window is kept.
+    src_encoded / src_cnt (90,256) or (B,90,256); the per-frame inputs as for ``PostProcessor.step``; the result has a leading
+    clip dimension B (1 for a single clip).  The same frames through ``retarget_clip_ours`` give the same poses."""
+    m = session.model
+    Y, _ = session.step(src_encoded, src_cnt, eps=eps, deterministic=deterministic)
+    if denorm is not None:
+        mean, std = (torch.as_tensor(a, dtype=torch.float32, device=m.device) for a in denorm)
+        Y = Y * std + mean
+    heads, speed = pose_heads(m, Y)
+    return (post or PostProcessor(m)).step(post_state, heads, speed, src_rvel, src_rang, src_speed, contact, bvh=bvh)
 
 
 _CHANNEL = {"x": "Xrotation", "y": "Yrotation", "z": "Zrotation"}

@@ -1,0 +1,125 @@
+#!/usr/bin/env python3
+"""Latency of the live step (LiveSession.push = mocha_live_step: ring push + featurize -> segmented characterize -> pose heads -> one
+post-processing frame, one captured graph) on one MI355X, next to the step it is built on (MultiStreamCharacterizer.step =
+mocha_step_graph_segmented alone), for S = 1 and S = 8 streams against an 8 x 2 048-row fp32 segmented bank.
+
+Both steps are timed in ONE process with HIP events around single replays, alternating live / baseline replay by replay after a
+warm-up, so that both see the same clocks and the same neighbours; p50 and p99 over --reps replays each.  Clocks are not touched.
+The three launches the live step adds (mocha_live_push, mocha_pose_heads, the post-processing frame = mocha_post_clip + mocha_post_bvh on one
+frame) are then timed one launch at a time with
+mocha_profile_start / stop, during which the step runs eagerly.
+
+    python tools/live_latency.py [--reps 1000] [--out profiles/r08/live_step.json]
+    python tools/live_latency.py --baseline-only      only the segmented step (runs on a build without the live step, too)
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from mocha_sigasia2023_amd import Generator, MultiCharacterBank, MultiStreamCharacterizer, synthetic, synthetic_state_dict  # noqa: E402
+
+D = 90 * 256
+ADDED = ("live.push", "live.heads", "live.post")       # profiling sites of the launches the live step adds to the segmented step
+
+
+def event_ms(fn, reps):
+    out = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); fn(); e1.record()
+        e1.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return np.asarray(out)
+
+
+def pct(a):
+    return {"p50_ms": float(np.percentile(a, 50)), "p99_ms": float(np.percentile(a, 99)), "replays": int(len(a))}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=1000)
+    ap.add_argument("--warmup", type=int, default=100)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08", "live_step.json"))
+    ap.add_argument("--baseline-only", action="store_true")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("live_latency.py measures on the GPU: no ROCm device found")
+    dev = torch.device("cuda:0")
+    J = 25
+    model = Generator(device=dev).load_state_dict(synthetic_state_dict(1777, 1.0)).eval()
+    rng = np.random.Generator(np.random.PCG64(0))
+    model.set_pose_norm((0.05 * rng.standard_normal((J, 15))).astype(np.float32), rng.uniform(0.5, 1.5, (J, 15)).astype(np.float32),
+                        (0.05 * rng.standard_normal((J, 15))).astype(np.float32), rng.uniform(0.2, 0.6, (J, 15)).astype(np.float32))
+    g = torch.Generator(device=dev); g.manual_seed(3)
+    nm = torch.randn((8 * 2048, D), device=dev, generator=g)
+    enc = torch.randn((8 * 2048, 90, 256), device=dev, generator=g)
+    mb = MultiCharacterBank(model, [(nm[c * 2048:(c + 1) * 2048], enc[c * 2048:(c + 1) * 2048]) for c in range(8)])
+    m_, s_ = synthetic.cnt_norm(7)
+    mean, std = torch.from_numpy(m_).to(dev), torch.from_numpy(s_).to(dev)
+    clip = [torch.from_numpy(x).to(dev) for x in synthetic.smooth_bone_clip(21, 644, J)]
+    _, rvel, rang, hipvel, contact = synthetic.postprocess_inputs(5, 644)
+    per = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (rvel, rang, np.linalg.norm(hipvel, axis=-1).mean(-1).astype(np.float32), contact)]
+    res = {"bank": "8 characters x 2048 rows, fp32, segmented", "layout": "mocha (24 joints)", "timing": "HIP events around single graph replays, live and baseline alternating",
+           "streams": {}}
+    for S in (1, 8):
+        ids = [(k * 3) % 8 for k in range(S)]
+        mb.characterize(torch.zeros((S, 60, J, 15), device=dev), ids, mean, std, raw=True)      # eager first: everything made on first use exists
+        ms = MultiStreamCharacterizer(mb, mean, std, streams=S, raw=True)
+        ms.characters.copy_(torch.tensor(ids, dtype=torch.int32))
+        ms.input.copy_(model.featurize(*[x[:60][None].expand(S, -1, -1, -1).contiguous() for x in clip]))
+        base = lambda: ms.step()                                                   # noqa: E731
+        entry = {}
+        if a.baseline_only:
+            event_ms(base, a.warmup)
+            entry["segmented_step"] = pct(event_ms(base, a.reps))
+        else:
+            from mocha_sigasia2023_amd import LiveSession
+            sess = LiveSession(mb, mean, std, streams=S)
+            frame = [0]
+
+            def push():
+                f = frame[0] % 644; frame[0] += 1
+                sess.rot.copy_(clip[0][f]); sess.pos.copy_(clip[1][f]); sess.vel.copy_(clip[2][f]); sess.ang.copy_(clip[3][f])
+                sess.rvel.copy_(per[0][f]); sess.rang.copy_(per[1][f]); sess.speed.copy_(per[2][f]); sess.contact.copy_(per[3][f])
+            sess.characters.copy_(torch.tensor(ids, dtype=torch.int32))
+            for _ in range(max(a.warmup, 70)):                                     # past the ring's warm-up: every stream is running
+                push(); sess.replay(); base()
+            torch.cuda.synchronize()
+            assert bool((sess.out["valid"] == 1).all())
+            live_t, base_t = [], []
+            for _ in range(a.reps):                                                # alternating, inputs staged outside the timed region
+                push(); torch.cuda.synchronize()
+                live_t.append(event_ms(sess.replay, 1)[0])
+                base_t.append(event_ms(base, 1)[0])
+            entry["live_step"], entry["segmented_step"] = pct(np.asarray(live_t)), pct(np.asarray(base_t))
+            entry["live_minus_segmented_p50_ms"] = entry["live_step"]["p50_ms"] - entry["segmented_step"]["p50_ms"]
+            # the added kernels, one launch at a time (the step runs eagerly while profiling is on)
+            n = 200
+            model.profile_start()
+            for _ in range(n):
+                sess.replay()
+            prof = model.profile_stop()
+            entry["added_kernels_us"] = {k: 1e3 * v["ms"] / v["launches"] for k, v in prof["sites"].items() if k.split("|")[0] in ADDED}
+            entry["added_kernels_sum_us"] = float(sum(entry["added_kernels_us"].values()))
+            entry["eager_step_launches"] = int(sum(v["launches"] for v in prof["kernels"].values()) // n)
+            assert bool(torch.isfinite(sess.out["pos"]).all())
+            del sess
+        res["streams"][str(S)] = entry
+        del ms
+    print(json.dumps(res, indent=1))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
