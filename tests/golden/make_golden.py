@@ -210,15 +210,15 @@ def run_cvae():
     print("cvae", {k: float(np.abs(v).max()) for k, v in dict(mu=mu.numpy(), logvar=logvar.numpy(), out=out.numpy()).items()})
 
 
-def run_featurize():
+def run_featurize(layout="mocha", seed=321, name="featurize.npz"):
     """test_fullframework.py:141-185 executed with the reference's own quaternion library (motion/quat.py)
     on synthetic local bone features; only the X features are stored."""
     sys.path.insert(0, os.path.join(REF, "motion"))
     import quat                                           # the reference's motion/quat.py
     from mocha_sigasia2023_amd.skeleton import LAYOUTS
-    parents = np.concatenate([[-1], np.asarray(LAYOUTS["mocha"]["parents"]) + 1])   # :101-102
+    parents = np.concatenate([[-1], np.asarray(LAYOUTS[layout]["parents"]) + 1])   # :101-102
     window = 60
-    Yrot, Ypos, Yvel, Yang = synthetic.bone_windows(321, 3)
+    Yrot, Ypos, Yvel, Yang = synthetic.bone_windows(seed, 3, J=len(parents))
     Grot, Gpos, Gvel, Gang = quat.fk_vel(Yrot, Ypos, Yvel, Yang, parents)
     Gpos[:, :, 0:1] = np.repeat(Gpos[:, -1:, 0:1], window, axis=1)
     Grot[:, :, 0:1] = np.repeat(Grot[:, -1:, 0:1], window, axis=1)
@@ -231,8 +231,13 @@ def run_featurize():
     Xang = quat.inv_mul_vec(Grot[:, :, 0:1], Gang)
     b, ns, nj, _, _ = Xtxy.shape
     X = np.concatenate([Xpos, Xtxy.reshape(b, ns, nj, -1), Xvel, Xang], axis=-1)
-    np.savez(os.path.join(HERE, "featurize.npz"), X=X.astype(np.float32), seed=np.array([321, 3]))
-    print("featurize", X.shape, X.dtype, float(np.abs(X).max()))
+    np.savez(os.path.join(HERE, name), X=X.astype(np.float32), seed=np.array([seed, 3]))
+    print(name, X.shape, X.dtype, float(np.abs(X).max()))
+
+
+def run_featurize_mixamo():
+    """The second layout (23 bones): the one live sessions run on."""
+    run_featurize("mixamo", 322, "featurize_mixamo.npz")
 
 
 def run_database():
@@ -303,7 +308,7 @@ def run_database():
     print("database", {k: getattr(v, "shape", v) for k, v in out.items() if not k.startswith("db_")})
 
 
-def run_postprocess():
+def run_postprocess(layout="mocha", contact_bones=(5, 24), seed=77, cm_seed=78, name="postprocess.npz"):
     """The demo's per-frame post-processing, produced by EXECUTING THE REFERENCE'S OWN LINES: test_fullframework.py:289-641 (the body
     of its `with torch.no_grad():` block - frame 0 at :289-437, the frame loop at :438-641) and :643-694 (stacking, root merge),
     taken from its source text and run in a prepared namespace, as run_database does for collect_CVAE_feature_action.py.
@@ -322,8 +327,10 @@ def run_postprocess():
     from sklearn.neighbors import BallTree
     from mocha_sigasia2023_amd.skeleton import LAYOUTS
     N = 120
-    Y, rvel, rang, hipvel, contact = synthetic.postprocess_inputs(77, N)         # "Ours" branch windows + the source's signals
-    Ycm = synthetic.postprocess_inputs(78, N)[0]                                 # NN ("cm_") branch windows
+    par0 = np.asarray(LAYOUTS[layout]["parents"])
+    J = len(par0) + 1
+    Y, rvel, rang, hipvel, contact = synthetic.postprocess_inputs(seed, N, V=J - 1)   # "Ours" branch windows + the source's signals
+    Ycm = synthetic.postprocess_inputs(cm_seed, N, V=J - 1)[0]                        # NN ("cm_") branch windows
     r = np.random.Generator(np.random.PCG64(123))
 
     class _Tokens:                                        # what model.decoder returns: which window to_mot must hand out
@@ -342,8 +349,6 @@ def run_postprocess():
         def sample(self, condition, deterministic=False):
             return condition[:, condition.shape[1] // 2:]
 
-    par0 = np.asarray(LAYOUTS["mocha"]["parents"])
-    J = len(par0) + 1
     src_Yrvel = r.standard_normal((N, 60, 3)).astype(np.float32); src_Yrvel[:, -1] = rvel
     src_Yrang = r.standard_normal((N, 60, 3)).astype(np.float32); src_Yrang[:, -1] = rang
     src_Yvel = r.standard_normal((N, 60, J, 3)).astype(np.float32); src_Yvel[:, :, 1] = hipvel
@@ -361,7 +366,7 @@ def run_postprocess():
         "src_Ypos": r.standard_normal((N, 60, J, 3)).astype(np.float32), "src_Yvel": src_Yvel,
         "src_Yrot": np.tile(np.array([1, 0, 0, 0], np.float32), (N, 60, J, 1)), "src_Yang": r.standard_normal((N, 60, J, 3)).astype(np.float32),
         "src_Yrvel": src_Yrvel, "src_Yrang": src_Yrang, "src_contact": src_contact,
-        "parents": np.concatenate([[-1], par0 + 1]), "contact_bones": np.array([5, 24]), "dt": 1.0 / 60.0,
+        "parents": np.concatenate([[-1], par0 + 1]), "contact_bones": np.array(contact_bones), "dt": 1.0 / 60.0,
         "ik_enabled": True, "ik_max_length_buffer": 0.015, "ik_foot_height": 0.02, "ik_toe_length": 0.15,
         "ik_unlock_radius": 0.2, "ik_blending_halflife": 0.1,
         "animation_plot": lambda *a, **k: None,
@@ -380,14 +385,22 @@ def run_postprocess():
     heads_rot = np.stack([quat.from_xform_xy(Y[i][-1, :, 3:9].reshape(-1, 3, 2)) for i in range(N)])
     speed = np.array([np.linalg.norm(Y[i][..., 9:12][:, 0], axis=1).mean() for i in range(N)], np.float32)
     cm_speed = np.array([np.linalg.norm(Ycm[i][..., 9:12][:, 0], axis=1).mean() for i in range(N)], np.float32)
-    np.savez(os.path.join(HERE, "postprocess.npz"), seed=np.array([77, N]), cm_seed=np.array([78, N]),
+    np.savez(os.path.join(HERE, name), seed=np.array([seed, N]), cm_seed=np.array([cm_seed, N]),
              pos=pre["ik_trans_Ypos"], rot=pre["trans_Yrot"], ik_rot=pre["ik_trans_Yrot"],
              cm_pos=pre["cm_trans_Ypos"], cm_rot=pre["cm_trans_Yrot"],
              heads_rot=heads_rot.astype(np.float32), speed=speed, cm_speed=cm_speed,
              bvh_pos=ns["ik_trans_Ypos"], bvh_euler=np.degrees(quat.to_euler(ns["ik_trans_Yrot"])),          # :706-707
              cm_bvh_pos=ns["cm_trans_Ypos"], cm_bvh_euler=np.degrees(quat.to_euler(ns["cm_trans_Yrot"])))
-    print("postprocess", pre["ik_trans_Ypos"].shape, float(np.abs(pre["ik_trans_Ypos"]).max()), "ik changed rotations on",
+    print(name, pre["ik_trans_Ypos"].shape, float(np.abs(pre["ik_trans_Ypos"]).max()), "ik changed rotations on",
           int((np.abs(pre["ik_trans_Yrot"] - pre["trans_Yrot"]).max(axis=(1, 2)) > 1e-9).sum()), "frames")
+
+
+MIXAMO_POST_SEEDS = (170, 171)          # "Ours" / "cm_" inputs: 170 reaches every contact transition on this skeleton (tests/test_live_oracle.py)
+
+
+def run_postprocess_mixamo():
+    """The second layout: parents of LAYOUTS["mixamo"], the toes (bones 18 and 22 of the 23-bone skeleton) as contact bones."""
+    run_postprocess("mixamo", (18, 22), *MIXAMO_POST_SEEDS, name="postprocess_mixamo.npz")
 
 
 def run_bvh():
@@ -459,7 +472,9 @@ if __name__ == "__main__":
     run_match()
     run_cvae()
     run_featurize()
+    run_featurize_mixamo()
     run_database()
     run_postprocess()
+    run_postprocess_mixamo()
     run_bvh()
     run_checkpoint_schema()
