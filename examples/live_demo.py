@@ -3,7 +3,11 @@
 mocap frame at a time through ``LiveSession`` - ring push + featurize, segmented characterize, pose heads and one post-processing
 frame per push, one captured graph - and written as two BVH files.
 
-    python examples/live_demo.py [--frames 180] [--out bench_outputs/live_demo]
+    python examples/live_demo.py [--frames 180] [--out bench_outputs/live_demo] [--ours [--seed 7]]
+
+``--ours`` runs the CVAE ("Ours") branch inside the same graph (``LiveOursSession``): each stream's character feature is seeded with
+its matched bank row on the first pose and sampled from the previous one afterwards, the noise drawn on the device; the files are then
+named ``Ours_stream<s>.bvh`` as the reference names its result ``Ours.bvh``.
 
 Weights, norms and motions are synthetic (see demo_pair.py for what to replace with real assets).
 """
@@ -16,13 +20,15 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mocha_sigasia2023_amd import (Generator, LiveSession, MultiCharacterBank, PostProcessor, build_bank, synthetic,  # noqa: E402
+from mocha_sigasia2023_amd import (Generator, LiveOursSession, LiveSession, MultiCharacterBank, PostProcessor, build_bank, synthetic,  # noqa: E402
                                    synthetic_state_dict, write_bvh)
 from mocha_sigasia2023_amd.skeleton import LAYOUTS  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--frames", type=int, default=180, help="mocap frames pushed per stream (the first 59 fill the window)")
 ap.add_argument("--out", default="bench_outputs/live_demo")
+ap.add_argument("--ours", action="store_true", help="the CVAE branch inside the live step (synthetic CVAE weights and statistics)")
+ap.add_argument("--seed", type=int, default=7, help="--ours: seed of the device's noise")
 a = ap.parse_args()
 if a.frames < 60:
     raise SystemExit("--frames must be at least 60: a stream's first pose comes with its 60th frame")
@@ -53,7 +59,15 @@ for s in range(S):
     _, rvel, rang, hipvel, contact = synthetic.postprocess_inputs(5 + s, F)
     per.append([torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in
                 (rvel, rang, np.linalg.norm(hipvel, axis=-1).mean(-1).astype(np.float32), contact)])
-sess = LiveSession(bank, cnt_mean, cnt_std, streams=S, post=PostProcessor(model))
+if a.ours:                                                            # test_fullframework.py:52-58, 80-87: the CVAE and its statistics
+    from mocha_sigasia2023_amd.weights import synthetic_cvae_state_dict
+    r3 = np.random.Generator(np.random.PCG64(3))
+    stats = [(0.1 * r3.standard_normal((90, 256))).astype(np.float32), r3.uniform(0.5, 1.5, (90, 256)).astype(np.float32),
+             (0.1 * r3.standard_normal((90, 256))).astype(np.float32), r3.uniform(0.5, 1.5, (90, 256)).astype(np.float32)]
+    sess = LiveOursSession(bank, cnt_mean, cnt_std, synthetic_cvae_state_dict(99, 1.0), *stats, streams=S, post=PostProcessor(model),
+                           noise="device", seed=a.seed)
+else:
+    sess = LiveSession(bank, cnt_mean, cnt_std, streams=S, post=PostProcessor(model))
 sess.push(*[torch.stack([src[s][k][0] for s in range(S)]) for k in range(4)], *[torch.stack([per[s][k][0] for s in range(S)]) for k in range(4)],
           characters=[0, 1])                                          # the first push captures the step
 sess.reset()
@@ -69,7 +83,7 @@ pos, eul = torch.stack(pos, 1), torch.stack(eul, 1)                   # (S, F - 
 
 names = ["Joint%02d" % i for i in range(24)]
 for s in range(S):
-    p = os.path.join(a.out, f"live_stream{s}.bvh")
+    p = os.path.join(a.out, f"{'Ours' if a.ours else 'live'}_stream{s}.bvh")
     write_bvh(p, names, LAYOUTS["mocha"]["parents"], pos[s], eul[s])
     print(f"  {p}: {os.path.getsize(p)} bytes, {pos.shape[1]} frames")
 print(f"{F} pushes of {S} streams in {dt * 1e3:.1f} ms ({dt / F * 1e3:.3f} ms per push, host loop included)")

@@ -379,6 +379,63 @@ int mocha_live_step(mocha_ctx* ctx, const mocha_post_cfg* cfg, void* live, int s
                     const unsigned char* contact, const int32_t* seg, const float* cnt_mean, const float* cnt_std, double* pos,
                     double* rot, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx, int32_t* valid, void* stream);
 
+/* The CVAE ("Ours") branch inside the live step (test_fullframework.py:446-457; a stream's first frame is :290-298): mocha_live_step
+ * with the decoder's character feature sampled from the previous one instead of taken from the matched bank row.  The autoregressive
+ * state of every stream lives in a second caller-owned device buffer `ours`, every decision of a frame is device data, and the noise can
+ * be drawn on the device, so the step is ONE captured graph for 1..16 streams and needs no host arithmetic.
+ *   mocha_live_ours_state_bytes : bytes of `ours` for `streams` streams (S below).  ALL-ZERO BYTES ARE A RESET BUFFER.  Sections in this
+ *                            order, each starting on a 256-byte boundary:
+ *                              counters (S,3) int32  {chain: steps since the stream's seed frame, last: the character id of its last
+ *                                                     step, mode: what its latest step was - 0 warming, 1 seed, 2 chain}
+ *                              prev    (S,90,256)    the stream's character feature: what the decoder of the latest step read
+ *                              cnt     (S,90,256)    staging: the instance-normalised source feature of the step
+ *                              cond    (S,180,256)   staging: the sampler's condition
+ *                              vae     (S,90,256)    staging: the sampler's output
+ *                              eps, mu, logvar (S,256 each)  staging: the noise used, the prior's mean and log-variance
+ *                            The session buffer `live` of mocha_live_step is used as it is (same layout, same size).
+ *   mocha_live_ours_reset  : mocha_live_reset plus zeroed counters of the named streams in `ours`: their next valid frame is a seed
+ *                            frame.  Enqueued on `stream`, graph-safe.
+ *   mocha_live_step_ours   : the arguments of mocha_live_step, plus `ours`, the CVAE's statistics and noise source, and seeded (S).
+ *                            Per stream, from device data alone:
+ *                              warming - the ring holds fewer than 60 frames (valid[s] = 0): the stream's counters and `prev` are not
+ *                                        written and its `cond` rows are zeros, seeded[s] = 0, outputs untouched as in mocha_live_step
+ *                                        (the staging sections cnt, vae, eps, mu, logvar are rewritten for EVERY stream on every step:
+ *                                        the instance norm and the sampler run on the whole batch);
+ *                              seed    - the stream's chain counter is 0 (first valid frame after a reset) or its character id differs
+ *                                        from the one of its last step: the character feature is the matched bank row, i.e. the frame is
+ *                                        mocha_live_step's frame; seeded[s] = 1.  The sampler still runs for the batch; the stream's
+ *                                        sample is discarded;
+ *                              chain   - cond = cat[(cnt - src_cnt_mean)/src_cnt_std, (prev - cha_encoded_mean)/cha_encoded_std],
+ *                                        vae = CVAE.sample(cond), prev = vae * cha_encoded_std + cha_encoded_mean, decoder(encoded,
+ *                                        prev); seeded[s] = 0.
+ *                            idx[s] is the matched row of every valid frame (the reference searches on every frame).
+ *                            noise 0: z = mu.  noise 1: eps (S,256) device, read on every step.  noise 2: drawn on the device with
+ *                            Philox4x32-10, key = (low, high) 32-bit words of `seed`, counter = (j, chain counter of the stream, s, 0)
+ *                            for j = 0..63; the block's words x0..x3 give u_k = ((x_k >> 8) + 0.5) * 2^-24, every operation in fp32
+ *                            and rounded to nearest even (from 2^23 on the sum rounds to an integer: u_k lies in (0,1]), and, by Box-Muller,
+ *                            eps[4j] = r cos(2 pi u1), eps[4j+1] = r sin(2 pi u1), r = sqrt(-2 log u0); eps[4j+2], eps[4j+3] likewise
+ *                            from u2, u3.  A stream's noise depends on (seed, s, chain counter) alone: a replayed session repeats it.
+ *                            ONE CVAE PER CONTEXT: its weights (mocha_cvae_load_weight / mocha_cvae_finalize ON THIS context, else
+ *                            MOCHA_ERR_STATE) and the four statistics serve every stream - the reference trains one CVAE per target
+ *                            character.  Streams may still name different segments; a seed row comes from the stream's own segment.
+ *                            Captured into its own HIP graph, keyed as mocha_live_step's plus `ours`, the pointers in ocfg, noise, seed
+ *                            and seeded.  Other refusals as mocha_live_step; a NULL `ours`, ocfg or statistic, noise outside 0..2, or
+ *                            noise 1 without eps is MOCHA_ERR_ARG, as are more streams than the workspace limit (mocha_reserve): the
+ *                            branch runs its stages on all the streams in one piece.  Nothing is launched on a refusal. */
+typedef struct mocha_ours_cfg {
+    const float *src_cnt_mean, *src_cnt_std, *cha_encoded_mean, *cha_encoded_std;    /* device, (90,256) each */
+    int noise;                 /* 0 none (z = mu), 1 eps given by the caller, 2 drawn on the device from seed */
+    const float* eps;          /* device (S,256); noise 1 only */
+    uint64_t seed;             /* noise 2 only */
+} mocha_ours_cfg;
+int64_t mocha_live_ours_state_bytes(const mocha_ctx* ctx, int streams);
+int mocha_live_ours_reset(mocha_ctx* ctx, void* live, void* ours, int streams, const int32_t* which, int n, void* stream);
+int mocha_live_step_ours(mocha_ctx* ctx, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos,
+                         const float* Yvel, const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed,
+                         const unsigned char* contact, const int32_t* seg, const float* cnt_mean, const float* cnt_std, void* ours,
+                         const mocha_ours_cfg* ocfg, double* pos, double* rot, double* ik_rot, double* bvh_pos, double* bvh_euler,
+                         int32_t* idx, int32_t* valid, int32_t* seeded, void* stream);
+
 /* Bank build statistics: cnt_mean, cnt_std = np.mean(cnt, 0), np.std(cnt, 0) over the N bank entries
  * (compute_cnt_norm.py:174-175; population std), x (N, 90*256) -> mean, std (90*256). */
 int mocha_column_stats(mocha_ctx* ctx, const float* x, int64_t N, float* mean, float* std_, void* stream);

@@ -26,6 +26,11 @@ class mocha_comm_info_t(C.Structure):
                 ("pci_bus_id", C.c_char * 32), ("library", C.c_char * 512)]
 
 
+class mocha_ours_cfg(C.Structure):
+    _fields_ = [("src_cnt_mean", C.c_void_p), ("src_cnt_std", C.c_void_p), ("cha_encoded_mean", C.c_void_p), ("cha_encoded_std", C.c_void_p),
+                ("noise", C.c_int), ("eps", C.c_void_p), ("seed", C.c_uint64)]
+
+
 _vp, _i, _i64 = C.c_void_p, C.c_int, C.c_int64
 
 # name -> (restype, argtypes); every symbol include/mocha_hip.h declares
@@ -72,6 +77,9 @@ SIGNATURES = {
     "mocha_live_state_bytes": (_i64, [_vp, _i]),
     "mocha_live_reset": (_i, [_vp, _vp, _i, C.POINTER(C.c_int32), _i, _vp]),
     "mocha_live_step": (_i, [_vp, _vp, _vp, _i] + [_vp] * 19),
+    "mocha_live_ours_state_bytes": (_i64, [_vp, _i]),
+    "mocha_live_ours_reset": (_i, [_vp, _vp, _vp, _i, C.POINTER(C.c_int32), _i, _vp]),
+    "mocha_live_step_ours": (_i, [_vp, _vp, _vp, _i] + [_vp] * 11 + [_vp, _vp] + [_vp] * 8 + [_vp]),
     "mocha_column_stats": (_i, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "mocha_set_option": (_i, [_vp, C.c_char_p, _i]),
     "mocha_linear": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp]),

@@ -189,6 +189,18 @@ struct LiveRing { int32_t* counters; float *rot, *pos, *vel, *ang; };
 hipError_t live_init();
 hipError_t launch_live_push(const LiveRing& r, const float* Yrot, const float* Ypos, const float* Yvel, const float* Yang, const int32_t* seg,
                             const int* parents /*J, device*/, float* X, int32_t* eff, int32_t* valid, int S, int J, hipStream_t s);
+// the CVAE branch of a live step (live_ours.hip).  counters (S,3) = {chain: steps since the stream's seed frame, last: the character id of
+// its last step, mode}; cnt / prev / vae (S,90,256), cond (S,180,256), eps (S,256); sm / ss / cm / cs (90,256) the CVAE's statistics.
+// condition: mode[s] = 0 (eff[s] outside 0..nseg-1: warming) / 1 (chain == 0 or eff[s] != last: seed) / 2 (chain) into the counters;
+//   cond[s] = 0 (mode 0), [(cnt - sm)/ss, 0] (mode 1), [(cnt - sm)/ss, (prev - cm)/cs] (mode 2); eps_out[s] = eps_in[s] (noise 1) or
+//   Philox4x32-10 (key = the seed's low / high word, counter (block 0..63, chain, s, 0)) + Box-Muller (noise 2); noise 0: not written.
+// update: mode 2: prev[s] = vae[s] * cs + cm; mode 1: prev[s] = bank_enc[gidx[s]]; modes 1, 2: chain + 1, last = eff[s]; seeded[s] = mode == 1.
+hipError_t launch_live_ours_condition(int32_t* counters, const int32_t* eff, int nseg, const float* cnt, const float* prev, const float* sm,
+                                      const float* ss, const float* cm, const float* cs, float* cond, int noise, const float* eps_in,
+                                      unsigned long long seed, float* eps_out, int S, hipStream_t s);
+hipError_t launch_live_ours_update(int32_t* counters, const int32_t* eff, const float* vae, const float* cm, const float* cs,
+                                   const float* bank_enc, const int32_t* gidx, long long bank_rows, float* prev, int32_t* seeded, int S,
+                                   hipStream_t s);
 // post-processing of decoded windows (postprocess.hip)
 #define MOCHA_MAX_CONTACT 4
 #define MOCHA_MAX_CHAIN 8

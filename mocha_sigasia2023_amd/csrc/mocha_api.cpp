@@ -268,10 +268,15 @@ struct mocha_ctx {
         // post-processing constants, which the captured launch carries by value
         const void* live[17] = {};
         mocha_post_cfg post{};
+        // mocha_live_step_ours only: the state buffer, the four statistics, the caller's noise and the seeded output; the noise mode and seed
+        const void* ours[7] = {};
+        int noise = 0; unsigned long long seed = 0;
         bool operator==(const StepKey& o) const {
             if (!(x == o.x && mean == o.mean && sd == o.sd && y == o.y && idx == o.idx && seg == o.seg && windows == o.windows && raw == o.raw))
                 return false;
             for (int i = 0; i < 17; ++i) if (live[i] != o.live[i]) return false;
+            for (int i = 0; i < 7; ++i) if (ours[i] != o.ours[i]) return false;
+            if (noise != o.noise || seed != o.seed) return false;
             const mocha_post_cfg &a = post, &b = o.post;
             for (int i = 0; i < 4; ++i) if (a.contact_bones[i] != b.contact_bones[i]) return false;
             return a.dt == b.dt && a.ik_max_length_buffer == b.ik_max_length_buffer && a.ik_foot_height == b.ik_foot_height &&
@@ -282,7 +287,7 @@ struct mocha_ctx {
     struct StepGraph {
         hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr;
         StepKey key; int64_t generation = -1;
-    } step[MAX_SETS], seg_step, live_step;            // seg_step: mocha_step_graph_segmented, live_step: mocha_live_step (workspace set 0)
+    } step[MAX_SETS], seg_step, live_step, ours_step; // seg_step: mocha_step_graph_segmented, live_step: mocha_live_step, ours_step: mocha_live_step_ours (workspace set 0)
     hipStream_t cap_stream = nullptr;                 // capture happens on this internal stream (the caller's may be the null stream)
     ncclComm_t comm = nullptr; int comm_rank = 0, comm_size = 1;      // mocha_comm_init
     DeviceBuffer<long long> bcast_hdr;                                  // device: {entries, bf16?} header of mocha_bank_broadcast
@@ -1332,7 +1337,7 @@ void mocha_destroy(mocha_ctx* c) {
     if (c->aux) (void)hipStreamDestroy(c->aux);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    for (auto* g : {&c->step[0], &c->step[1], &c->step[2], &c->seg_step, &c->live_step}) {
+    for (auto* g : {&c->step[0], &c->step[1], &c->step[2], &c->seg_step, &c->live_step, &c->ours_step}) {
         if (g->exec) (void)hipGraphExecDestroy(g->exec);
         if (g->graph) (void)hipGraphDestroy(g->graph);
     }
@@ -2524,14 +2529,10 @@ static int cvae_ff_block(mocha_ctx* c, hipStream_t s, const std::string& p, cons
     return 0;
 }
 
-int mocha_cvae_sample(mocha_ctx* c, const float* cond, int B, float* out, float* mu, float* logvar, const float* eps, void* stream) {
-    if (c && B == 0) return 0;
-    if (!c || !cond || !out || B < 0) return fail(c, MOCHA_ERR_ARG, "bad CVAE arguments");
-    if (!c->cvae_ready) return fail(c, MOCHA_ERR_STATE, "CVAE weights not finalised: call mocha_cvae_finalize first");
-    if (B == 0) return 0;
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc = cvae_ws(c, B); if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
+// CVAE.sample for B conditions on stream s: the body of mocha_cvae_sample and of the live step's CVAE branch.  The caller checked the
+// arguments, the weights (cvae_ready) and the workspace (cvae_ws(c, B)).
+static int cvae_sample_impl(mocha_ctx* c, const float* cond, int B, float* out, float* mu, float* logvar, const float* eps, hipStream_t s) {
+    int rc;
     const int nc = c->cvae_nc, nq = c->cvae_nq, ntok = nc + 2;
     float* t0 = c->cws.at("t0").p; float* mem = c->cws.at("mem").p;
     // PriorNet.encode (model_CVAE.py:69-79)
@@ -2556,6 +2557,16 @@ int mocha_cvae_sample(mocha_ctx* c, const float* cond, int B, float* out, float*
         if ((rc = cvae_ff_block(c, s, p, p + ".norm3", t0, last ? out : t0, nq, B))) return rc;
     }
     return 0;
+}
+
+int mocha_cvae_sample(mocha_ctx* c, const float* cond, int B, float* out, float* mu, float* logvar, const float* eps, void* stream) {
+    if (c && B == 0) return 0;
+    if (!c || !cond || !out || B < 0) return fail(c, MOCHA_ERR_ARG, "bad CVAE arguments");
+    if (!c->cvae_ready) return fail(c, MOCHA_ERR_STATE, "CVAE weights not finalised: call mocha_cvae_finalize first");
+    if (B == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = cvae_ws(c, B); if (rc) return rc;
+    return cvae_sample_impl(c, cond, B, out, mu, logvar, eps, (hipStream_t)stream);
 }
 
 int mocha_cvae_condition(mocha_ctx* c, const float* src_cnt, const float* src_mean, const float* src_std, const float* prev_cha,
@@ -2833,6 +2844,174 @@ int mocha_live_step(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, int str
         if (rc) return rc;
     }
     return step_replay(c, c->live_step, key, s, body);
+}
+
+}  // extern "C"
+
+namespace {
+// The state of the CVAE branch of a live session (caller-owned device memory, layout documented in mocha_hip.h): per stream the counters
+// {chain, last id, mode}, the character feature `prev`, and the branch's staging.  Every section starts on a 256-byte boundary.
+struct OursLayout {
+    size_t counters, prev, cnt, cond, vae, eps, mu, logvar, bytes;
+};
+OursLayout ours_layout(int S) {
+    const size_t n = (size_t)S, T = 90 * 256 * sizeof(float);
+    OursLayout l{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) / 256 * 256; return at; };
+    l.counters = take(n * 3 * sizeof(int32_t));
+    l.prev = take(n * T);
+    l.cnt = take(n * T);
+    l.cond = take(n * 2 * T);
+    l.vae = take(n * T);
+    l.eps = take(n * 256 * sizeof(float));
+    l.mu = take(n * 256 * sizeof(float));
+    l.logvar = take(n * 256 * sizeof(float));
+    l.bytes = off;
+    return l;
+}
+}  // namespace
+
+extern "C" {
+
+int64_t mocha_live_ours_state_bytes(const mocha_ctx* c, int streams) {
+    if (!c || streams < 1 || streams > 16) return MOCHA_ERR_ARG;
+    return (int64_t)ours_layout(streams).bytes;
+}
+
+int mocha_live_ours_reset(mocha_ctx* c, void* live, void* ours, int streams, const int32_t* which, int n, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (!ours) return fail(c, MOCHA_ERR_ARG, "live_ours_reset: null argument");
+    int rc = mocha_live_reset(c, live, streams, which, n, stream); if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    char* base = static_cast<char*>(ours) + ours_layout(streams).counters;
+    const size_t cb = 3 * sizeof(int32_t);
+    if (!which) { HIPCHK(c, hipMemsetAsync(base, 0, cb * streams, s)); return 0; }
+    for (int i = 0; i < n; ++i) HIPCHK(c, hipMemsetAsync(base + cb * which[i], 0, cb, s));
+    return 0;
+}
+
+int mocha_live_step_ours(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos, const float* Yvel,
+                         const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed, const unsigned char* contact,
+                         const int32_t* seg, const float* cnt_mean, const float* cnt_std, void* ours, const mocha_ours_cfg* ocfg, double* pos,
+                         double* rot, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx, int32_t* valid, int32_t* seeded,
+                         void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (streams < 1 || streams > 16) return fail(c, MOCHA_ERR_ARG, "live_step_ours: 1 <= streams <= 16");
+    if (!live || !Yrot || !Ypos || !Yvel || !Yang || !src_rvel || !src_rang || !src_speed || !contact || !seg || !cnt_mean || !cnt_std || !pos ||
+        !rot || !ik_rot || !idx || !valid || !seeded || (!bvh_pos) != (!bvh_euler))
+        return fail(c, MOCHA_ERR_ARG, "live_step_ours: null argument");
+    if (!ours || !ocfg) return fail(c, MOCHA_ERR_ARG, "live_step_ours: null state buffer or configuration");
+    if (!ocfg->src_cnt_mean || !ocfg->src_cnt_std || !ocfg->cha_encoded_mean || !ocfg->cha_encoded_std)
+        return fail(c, MOCHA_ERR_ARG, "live_step_ours: null statistic");
+    if (ocfg->noise < 0 || ocfg->noise > 2) return fail(c, MOCHA_ERR_ARG, "live_step_ours: noise must be 0 (none), 1 (given) or 2 (device)");
+    if (ocfg->noise == 1 && !ocfg->eps) return fail(c, MOCHA_ERR_ARG, "live_step_ours: noise 1 needs eps");
+    // the branch's stages run on all the streams in one piece (the sampler needs the whole batch between the encoder and the decoder), so
+    // the workspace must hold them: mocha_live_step walks a smaller workspace chunk by chunk, this step refuses
+    if (streams > c->max_chunk)
+        return fail(c, MOCHA_ERR_ARG, "live_step_ours: %d streams exceed the workspace limit of %d windows (raise it with mocha_reserve)", streams, c->max_chunk);
+    if (!c->finalized) return fail(c, MOCHA_ERR_STATE, "weights not finalised: call mocha_finalize_weights first");
+    if (!c->cvae_ready) return fail(c, MOCHA_ERR_STATE, "live_step_ours: no CVAE on this context: call mocha_cvae_load_weight and mocha_cvae_finalize first");
+    if (!c->pose_norm.p) return fail(c, MOCHA_ERR_STATE, "live_step_ours: no pose norm: call mocha_set_pose_norm first");
+    if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set_segments first");
+    if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    mocha_post_cfg d;
+    if (!cfg) { mocha_post_cfg_default(&d); cfg = &d; }
+    PostParams p{};
+    int rc = post_params(c, cfg, p); if (rc) return rc;
+    // everything the captured region needs exists before capture begins: both workspaces, the skeleton's parents
+    if ((rc = ready(c, streams))) return rc;
+    if ((rc = ensure_bone_parents(c))) return rc;
+    if ((rc = cvae_ws(c, streams))) return rc;
+
+    const LiveLayout l = live_layout(c, streams);
+    char* base = static_cast<char*>(live);
+    LiveRing ring;
+    ring.counters = reinterpret_cast<int32_t*>(base + l.counters);
+    ring.rot = reinterpret_cast<float*>(base + l.rot); ring.pos = reinterpret_cast<float*>(base + l.pos);
+    ring.vel = reinterpret_cast<float*>(base + l.vel); ring.ang = reinterpret_cast<float*>(base + l.ang);
+    float* xraw = reinterpret_cast<float*>(base + l.xraw);
+    float* ystage = reinterpret_cast<float*>(base + l.y);
+    float* heads = reinterpret_cast<float*>(base + l.heads);
+    float* speed = reinterpret_cast<float*>(base + l.speed);
+    int32_t* eff = reinterpret_cast<int32_t*>(base + l.eff);
+    p.heads = heads; p.speed = speed; p.src_rvel = src_rvel; p.src_rang = src_rang; p.src_speed = src_speed; p.contact = contact;
+    p.pos = pos; p.rot = rot; p.ik_rot = ik_rot; p.bvh_pos = bvh_pos; p.bvh_euler = bvh_euler;
+    p.n_clips = streams; p.n_frames = 1; p.state = reinterpret_cast<double*>(base + l.post); p.valid = valid;
+    const OursLayout ol = ours_layout(streams);
+    char* ob = static_cast<char*>(ours);
+    int32_t* ocnt = reinterpret_cast<int32_t*>(ob + ol.counters);
+    float* prev = reinterpret_cast<float*>(ob + ol.prev);
+    float* cnt_o = reinterpret_cast<float*>(ob + ol.cnt);
+    float* cond = reinterpret_cast<float*>(ob + ol.cond);
+    float* vae = reinterpret_cast<float*>(ob + ol.vae);
+    float* eps_o = reinterpret_cast<float*>(ob + ol.eps);
+    float* mu = reinterpret_cast<float*>(ob + ol.mu);
+    float* logvar = reinterpret_cast<float*>(ob + ol.logvar);
+    const mocha_ours_cfg oc = *ocfg;
+    const int J = c->cfg.V + 1, V = c->cfg.V, S = streams;
+    const int nseg = (int)c->bank.seg_start.size() - 1;
+
+    // sampler -> literal decoder on `cha` -> to_mot (de-normalised) into the staging: the tail of the step, and of the warm pass
+    auto tail = [&](const float* cha, hipStream_t cs) -> int {
+        int r = run_decoder(c, WS(c, "enc_s"), cha, S, WS(c, "dec"), cs);
+        if (r) return r;
+        return run_to_mot(c, WS(c, "dec"), S, ystage, cs, true);
+    };
+    // ring push + featurize -> embed, encoder, cnt and the z-scored query -> segmented match -> condition (mode per stream, noise) -> CVAE
+    // sampler -> state update -> decoder on the streams' character features -> to_mot -> pose heads -> one post-processing frame
+    auto body = [&](hipStream_t cs) -> int {
+        LAUNCH(c, cs, "mocha_live_push", "live.push", S * 60.0 * J * 150, S * (60.0 * J * (13 + 15) + J * 26.0) * 4,
+               launch_live_push(ring, Yrot, Ypos, Yvel, Yang, seg, c->bone_parents.p, xraw, eff, valid, S, J, cs));
+        c->lane = 0; c->cur = 0;
+        int r;
+        if ((r = run_embed(c, xraw, S, WS(c, "x5"), true, cs, true))) return r;
+        if ((r = run_encoder(c, WS(c, "x5"), S, WS(c, "enc_s"), cs))) return r;
+        InormExtra ex = IEX(c);
+        if (c->bank.is_bf16) { ex.centre = c->bank.center.p; ex.zc = WS(c, "qc"); }
+        LAUNCH(c, cs, "mocha_instnorm", "mvn", 0.0, S * 90.0 * 256 * 4 * (c->bank.is_bf16 ? 4.0 : 3.0),
+               launch_instnorm(WS(c, "enc_s"), cnt_o, nullptr, cnt_mean, cnt_std, WS(c, "qnm"), S, 90, cs, &ex));
+        int32_t* gx = SET(c).idx_ws.p;
+        if ((r = seg_match(c, WS(c, c->bank.is_bf16 ? "qc" : "qnm"), S, eff, idx, gx, nullptr, cs))) return r;
+        LAUNCH(c, cs, "mocha_live_ours_condition", "ours.condition", 0.0, S * 180.0 * 256 * 8,
+               launch_live_ours_condition(ocnt, eff, nseg, cnt_o, prev, oc.src_cnt_mean, oc.src_cnt_std, oc.cha_encoded_mean, oc.cha_encoded_std,
+                                          cond, oc.noise, oc.eps, oc.seed, eps_o, S, cs));
+        if ((r = cvae_sample_impl(c, cond, S, vae, mu, logvar, oc.noise ? eps_o : nullptr, cs))) return r;
+        LAUNCH(c, cs, "mocha_live_ours_update", "ours.update", 0.0, S * 90.0 * 256 * 12,
+               launch_live_ours_update(ocnt, eff, vae, oc.cha_encoded_mean, oc.cha_encoded_std, c->bank.enc, gx, c->bank.N, prev, seeded, S, cs));
+        if ((r = tail(prev, cs))) return r;
+        LAUNCH(c, cs, "mocha_pose_heads", "live.heads", 0.0, S * (60.0 * 12 + V * 28.0 * 4), launch_pose_heads(ystage, heads, speed, S, c->cfg.T, V, cs));
+        LAUNCH(c, cs, "mocha_post_clip", "live.post", 0.0, (double)S * (V * 13.0 * 4 + J * 11.0 * 8 + 2.0 * POST_STATE_DOUBLES * 8),
+               launch_post_step(p, cs));
+        return 0;
+    };
+    hipStream_t s = (hipStream_t)stream;
+    if (c->prof_on) return body(s);
+
+    mocha_ctx::StepKey key;
+    key.x = live; key.mean = cnt_mean; key.sd = cnt_std; key.idx = idx; key.seg = seg; key.windows = streams; key.raw = true;
+    const void* ptrs[17] = {Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, pos, rot, ik_rot, bvh_pos, bvh_euler, valid, nullptr, nullptr, nullptr};
+    for (int i = 0; i < 17; ++i) key.live[i] = ptrs[i];
+    const void* optrs[7] = {ours, oc.src_cnt_mean, oc.src_cnt_std, oc.cha_encoded_mean, oc.cha_encoded_std, oc.noise == 1 ? oc.eps : nullptr, seeded};
+    for (int i = 0; i < 7; ++i) key.ours[i] = optrs[i];
+    key.noise = oc.noise; key.seed = oc.noise == 2 ? oc.seed : 0;
+    key.post = *cfg;
+    const auto& g = c->ours_step;
+    if (!(g.exec && g.key == key && g.generation == c->generation)) {
+        // Before a capture: one eager pass over staging alone - mocha_live_step's characterize of zeroed windows with every id -1, then the
+        // sampler on a zeroed condition and the literal decoder on its sample - so that whatever the kernels of the step make on first
+        // use (the plane GEMMs' weight images, the style MLP's float64 weights) exists.  No counter, ring, `prev` or post state moves.
+        HIPCHK(c, hipMemsetAsync(xraw, 0, (size_t)S * 60 * J * c->cfg.C_in * sizeof(float), s));
+        HIPCHK(c, hipMemsetAsync(eff, 0xFF, (size_t)S * sizeof(int32_t), s));
+        HIPCHK(c, hipMemsetAsync(cond, 0, (size_t)S * 180 * 256 * sizeof(float), s));
+        c->lane = 0;
+        rc = characterize_impl(c, xraw, S, cnt_mean, cnt_std, ystage, nullptr, s, true, eff);
+        c->cur = 0;
+        if (rc) return rc;
+        if ((rc = cvae_sample_impl(c, cond, S, vae, mu, logvar, nullptr, s))) return rc;
+        if ((rc = tail(vae, s))) return rc;
+    }
+    return step_replay(c, c->ours_step, key, s, body);
 }
 
 int mocha_column_stats(mocha_ctx* c, const float* x, int64_t N, float* mean, float* std_, void* stream) {

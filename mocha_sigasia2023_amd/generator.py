@@ -194,6 +194,13 @@ class Generator:
         self._loaded = True
         return self
 
+    def load_cvae(self, state_dict: Mapping, strict: bool = True):
+        """The CVAE's ``state_dict`` (as ``CVAE.load_state_dict`` takes it) into THIS model's context: what the CVAE branch of a live
+        session (``LiveOursSession``, ``mocha_live_step_ours``) samples with.  One CVAE per model."""
+        _load_cvae_weights(self._ctx, state_dict, strict)
+        self._cvae_loaded = True          # LiveOursSession(cvae_state_dict=None) reuses it
+        return self
+
     def reserve(self, max_batch: int):
         """Pre-allocate workspaces for chunks of ``max_batch`` windows."""
         self._ctx.call("mocha_reserve", int(max_batch))
@@ -591,6 +598,37 @@ class StreamingCharacterizer:
         return Y, idx
 
 
+def _load_cvae_weights(ctx: "_Context", state_dict: Mapping, strict: bool = True):
+    """A CVAE ``state_dict`` into ``ctx`` (``mocha_cvae_load_weight`` per tensor, then ``mocha_cvae_finalize``): the loader of
+    ``CVAE.load_state_dict`` and ``Generator.load_cvae``."""
+    from .weights import cvae_param_shapes
+    want = cvae_param_shapes()
+    seen = set()
+    has_pe = False
+    for k0, v in state_dict.items():
+        k = k0[len("module."):] if k0.startswith("module.") else k0
+        a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if k not in want and not k.startswith("encoder.") and not k.endswith("pos_encoder.pe"):
+            if strict:
+                raise KeyError(f"unexpected key in CVAE state_dict: {k0}")
+            continue
+        shape = (C.c_int64 * a.ndim)(*a.shape)
+        ctx.call("mocha_cvae_load_weight", k.encode(), a.ctypes.data_as(C.c_void_p), shape, a.ndim)
+        seen.add(k)
+        has_pe = has_pe or k == "prior_net.pos_encoder.pe"
+    missing = [k for k in want if k not in seen]
+    if missing and strict:
+        raise KeyError(f"missing keys in CVAE state_dict: {missing[:4]}{'...' if len(missing) > 4 else ''}")
+    if not has_pe:
+        # regenerate the registered buffer exactly as torch builds it (model_CVAE.py:168-178)
+        from .weights import sincos_pe
+        pe = np.ascontiguousarray(sincos_pe(192)[None], dtype=np.float32)
+        ctx.call("mocha_cvae_load_weight", b"prior_net.pos_encoder.pe", pe.ctypes.data_as(C.c_void_p),
+                 (C.c_int64 * 3)(*pe.shape), 3)
+    ctx.call("mocha_cvae_finalize")
+
+
 class CVAE:
     """Drop-in for the reference ``CVAE`` sampler (model_CVAE.py:8-46) as the demo uses it
     (test_fullframework.py:52-58, 446-449): ``CVAE(...).load_state_dict(sd).eval().sample(condition)``.
@@ -617,32 +655,7 @@ class CVAE:
         ndarrays by the reference's names.  The training-only posterior ``encoder.*`` entries and the ``pos_encoder.pe`` buffers
         are accepted; ``module.``-prefixed keys (a DataParallel-wrapped save) too.  ``strict=False`` skips unknown keys and lets a
         re-load bring only some tensors (a context that never saw a tensor still fails, in ``mocha_cvae_finalize``)."""
-        from .weights import cvae_param_shapes
-        want = cvae_param_shapes()
-        seen = set()
-        has_pe = False
-        for k0, v in state_dict.items():
-            k = k0[len("module."):] if k0.startswith("module.") else k0
-            a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            if k not in want and not k.startswith("encoder.") and not k.endswith("pos_encoder.pe"):
-                if strict:
-                    raise KeyError(f"unexpected key in CVAE state_dict: {k0}")
-                continue
-            shape = (C.c_int64 * a.ndim)(*a.shape)
-            self._ctx.call("mocha_cvae_load_weight", k.encode(), a.ctypes.data_as(C.c_void_p), shape, a.ndim)
-            seen.add(k)
-            has_pe = has_pe or k == "prior_net.pos_encoder.pe"
-        missing = [k for k in want if k not in seen]
-        if missing and strict:
-            raise KeyError(f"missing keys in CVAE state_dict: {missing[:4]}{'...' if len(missing) > 4 else ''}")
-        if not has_pe:
-            # regenerate the registered buffer exactly as torch builds it (model_CVAE.py:168-178)
-            from .weights import sincos_pe
-            pe = np.ascontiguousarray(sincos_pe(192)[None], dtype=np.float32)
-            self._ctx.call("mocha_cvae_load_weight", b"prior_net.pos_encoder.pe", pe.ctypes.data_as(C.c_void_p),
-                           (C.c_int64 * 3)(*pe.shape), 3)
-        self._ctx.call("mocha_cvae_finalize")
+        _load_cvae_weights(self._ctx, state_dict, strict)
         self._loaded = True
         return self
 

@@ -5,6 +5,9 @@ loop (root transform, blended positions, contact records).  ``push`` copies the 
 replays ONE captured HIP graph: ring push + featurize -> segmented characterize of the streams' windows, every stream against its own
 character of a ``MultiCharacterBank`` -> pose heads -> one post-processing frame.  Nothing is computed on the host and nothing
 synchronises; a stream that has not seen 60 frames yet is reported as ``valid == 0`` and its output rows are left as they were.
+
+A ``LiveOursSession`` is the same loop with the CVAE ("Ours") branch inside the graph (``mocha_live_step_ours``): the decoder reads a
+character feature sampled from the stream's previous one, the autoregressive state and the sampler's noise staying on the device.
 """
 from __future__ import annotations
 
@@ -14,6 +17,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
+from . import _C
 from .generator import DIM, NTOK, _dev_f32, _ptr, _stream
 from .multi_character import MultiCharacterBank
 from .postprocess import PostProcessor
@@ -130,3 +134,70 @@ class LiveSession:
                 for k in keep:
                     frames[k].append(o[k].clone())
         return {k: torch.stack(v, dim=1) for k, v in frames.items()}
+
+
+class LiveOursSession(LiveSession):
+    """A ``LiveSession`` whose decoder reads the CVAE ("Ours") branch's character feature (``mocha_live_step_ours``;
+    test_fullframework.py:446-457): per stream the feature is seeded with the matched bank row on the first valid frame - that frame is
+    ``LiveSession``'s frame - and from then on sampled from the previous one, the autoregressive state staying on the device.  A stream
+    that is reset, or whose character changes, seeds again.
+
+    ``cvae_state_dict`` is loaded into the model's own context (``Generator.load_cvae``): ONE CVAE, with its four (90,256) statistics,
+    serves every stream of the model, while streams may still name different characters of the bank.  ``cvae_state_dict=None`` keeps
+    the CVAE the model already has: loading one synchronises the device and makes every captured graph of the model capture again,
+    so further sessions on a model should pass None.  ``noise``: ``"device"`` draws the
+    sampler's noise on the device from ``seed`` (Philox4x32-10 counted by stream and frame: the same seed repeats the session),
+    ``"given"`` reads ``sess.eps`` (S,256), which the caller writes before a push, ``"none"`` takes z = mu.  ``push`` / ``replay`` /
+    ``run_clip`` / ``reset`` as in ``LiveSession``; the outputs gain ``seeded`` (S,) int32: 1 where the frame was a seed frame."""
+
+    NOISE = {"none": 0, "given": 1, "device": 2}
+
+    def __init__(self, bank: MultiCharacterBank, cnt_mean, cnt_std, cvae_state_dict, src_cnt_mean, src_cnt_std, cha_encoded_mean,
+                 cha_encoded_std, streams: int = 1, post: Optional[PostProcessor] = None, bvh: bool = True, noise: str = "device",
+                 seed: int = 0):
+        if noise not in self.NOISE:
+            raise ValueError(f"noise must be one of {sorted(self.NOISE)}")
+        super().__init__(bank, cnt_mean, cnt_std, streams=streams, post=post, bvh=bvh)
+        m, dev, S = self.model, self.model.device, self.streams
+        if cvae_state_dict is not None:
+            m.load_cvae(cvae_state_dict)
+        elif not getattr(m, "_cvae_loaded", False):
+            raise RuntimeError("LiveOursSession: cvae_state_dict=None needs a CVAE on the model (Generator.load_cvae)")
+        self.stats = [_dev_f32(a, dev, (NTOK, DIM), n) for a, n in ((src_cnt_mean, "src_cnt_mean"), (src_cnt_std, "src_cnt_std"),
+                                                                   (cha_encoded_mean, "cha_encoded_mean"), (cha_encoded_std, "cha_encoded_std"))]
+        nbytes = int(m._ctx.lib.mocha_live_ours_state_bytes(m._ctx.h, S))
+        if nbytes <= 0:
+            raise RuntimeError("mocha_live_ours_state_bytes failed")
+        self.ours = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)          # zeroed = every stream seeds on its first valid frame
+        self.eps = torch.zeros((S, DIM), dtype=torch.float32, device=dev)
+        self.noise, self.seed = noise, int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.ocfg = _C.mocha_ours_cfg(*[t.data_ptr() for t in self.stats], self.NOISE[noise], self.eps.data_ptr(), self.seed)
+        self.out["seeded"] = torch.zeros((S,), dtype=torch.int32, device=dev)
+        at = ((S * 12 + 255) // 256) * 256                                          # `prev` follows the counters (include/mocha_hip.h)
+        self._prev = self.ours[at: at + S * NTOK * DIM * 4].view(torch.float32).reshape(S, NTOK, DIM)
+
+    @property
+    def cha_encoded(self) -> torch.Tensor:
+        """The streams' current character features (S,90,256): a view of the state the next step conditions on."""
+        return self._prev
+
+    def replay(self):
+        self.bank._ensure()
+        o = self.out
+        self.model._ctx.call("mocha_live_step_ours", C.byref(self.post.cfg), _ptr(self.live), self.streams, _ptr(self.rot), _ptr(self.pos),
+                             _ptr(self.vel), _ptr(self.ang), _ptr(self.rvel), _ptr(self.rang), _ptr(self.speed), _ptr(self.contact),
+                             _ptr(self.ids), _ptr(self.mean), _ptr(self.std), _ptr(self.ours), C.byref(self.ocfg), _ptr(o["pos"]),
+                             _ptr(o["rot"]), _ptr(o["ik_rot"]), _ptr(o["bvh_pos"]) if self.bvh else None,
+                             _ptr(o["bvh_euler"]) if self.bvh else None, _ptr(o["idx"]), _ptr(o["valid"]), _ptr(o["seeded"]), _stream())
+        return o
+
+    def reset(self, streams: Optional[Sequence[int]] = None):
+        """All streams, or the listed ones, start over: they warm up again and their next valid frame is a seed frame."""
+        ctx = self.model._ctx
+        if streams is None:
+            ctx.call("mocha_live_ours_reset", _ptr(self.live), _ptr(self.ours), self.streams, None, 0, _stream())
+        else:
+            ids = [int(s) for s in streams]
+            arr = (C.c_int32 * max(len(ids), 1))(*ids)
+            ctx.call("mocha_live_ours_reset", _ptr(self.live), _ptr(self.ours), self.streams, arr, len(ids), _stream())
+        return self

@@ -11,6 +11,10 @@ mocha_profile_start / stop, during which the step runs eagerly.
 
     python tools/live_latency.py [--reps 1000] [--out profiles/r08/live_step.json]
     python tools/live_latency.py --baseline-only      only the segmented step (runs on a build without the live step, too)
+    python tools/live_latency.py --ours [--out profiles/r09/live_ours_step.json]
+        the CVAE ("Ours") branch: (a) LiveSession.replay, (b) LiveOursSession.replay with device noise, (c) the same frame without the
+        live step - featurize + encode + segmented match + OursSession.step + pose heads + PostProcessor.step on a window the caller
+        keeps (its upkeep is not timed) - alternating replay by replay in one process, S = 1 and S = 8
 """
 import argparse
 import json
@@ -42,13 +46,77 @@ def pct(a):
     return {"p50_ms": float(np.percentile(a, 50)), "p99_ms": float(np.percentile(a, 99)), "replays": int(len(a))}
 
 
+def ours(a, dev, model, mb, mean, std, clip, per, J):
+    """--ours: the three routes to a posed frame of the CVAE branch, alternating in one process."""
+    from mocha_sigasia2023_amd import CVAE, LiveOursSession, LiveSession, OursSession, PostProcessor, pose_heads
+    from mocha_sigasia2023_amd.weights import synthetic_cvae_state_dict
+    csd = synthetic_cvae_state_dict(99, 1.0)
+    rng = np.random.Generator(np.random.PCG64(3))
+    stats = [(0.1 * rng.standard_normal((90, 256))).astype(np.float32), rng.uniform(0.5, 1.5, (90, 256)).astype(np.float32),
+             (0.1 * rng.standard_normal((90, 256))).astype(np.float32), rng.uniform(0.5, 1.5, (90, 256)).astype(np.float32)]
+    cvae = CVAE(device=dev).load_state_dict(csd).eval()
+    res = {"bank": "8 characters x 2048 rows, fp32, segmented", "layout": "mocha (24 joints)",
+           "timing": "HIP events around single steps; (a) live step, (b) live step with the CVAE branch and device noise, (c) featurize + encode + "
+                     "match + OursSession.step + pose_heads + PostProcessor.step, alternating", "streams": {}}
+    for S in (1, 8):
+        ids = torch.tensor([(k * 3) % 8 for k in range(S)], dtype=torch.int32)
+        live = LiveSession(mb, mean, std, streams=S)
+        lo = LiveOursSession(mb, mean, std, csd, *stats, streams=S, noise="device", seed=11)
+        old = OursSession(model, cvae, *stats)
+        post = PostProcessor(model)
+        state = post.state(S)
+        frame = [0]
+
+        def push():
+            f = frame[0] % 644; frame[0] += 1
+            for sess in (live, lo):
+                sess.rot.copy_(clip[0][f]); sess.pos.copy_(clip[1][f]); sess.vel.copy_(clip[2][f]); sess.ang.copy_(clip[3][f])
+                sess.rvel.copy_(per[0][f]); sess.rang.copy_(per[1][f]); sess.speed.copy_(per[2][f]); sess.contact.copy_(per[3][f])
+            return f
+        window = [x[:60][None].expand(S, -1, -1, -1).contiguous() for x in clip]     # (c)'s window: kept by the caller, not timed
+        ids_d = ids.to(dev)
+        f_now = [0]
+
+        def parent_way():
+            f = f_now[0]
+            enc, cnt, nm = model.encode(model.featurize(*window), mean, std, raw=True)
+            _, idx = mb.query(nm, ids_d)
+            if old.prev is None:
+                # any (S,90,256) feature starts the chain: every timed step is a chain step, whose cost does not depend on the values
+                # (the demo seeds with the matched row)
+                old.reset(enc)
+            Y, _ = old.step(enc, cnt)
+            heads, speed = pose_heads(model, Y)
+            return post.step(state, heads, speed, per[0][f].expand(S, 3), per[1][f].expand(S, 3), per[2][f].expand(S), per[3][f].expand(S, -1))
+        for sess in (live, lo):
+            sess.characters.copy_(ids)
+        for _ in range(max(a.warmup, 70)):
+            f_now[0] = push(); live.replay(); lo.replay(); parent_way()
+        torch.cuda.synchronize()
+        assert bool((lo.out["valid"] == 1).all()) and not bool(lo.out["seeded"].any())
+        ta, tb, tc = [], [], []
+        for _ in range(a.reps):
+            f_now[0] = push(); torch.cuda.synchronize()
+            ta.append(event_ms(live.replay, 1)[0]); tb.append(event_ms(lo.replay, 1)[0]); tc.append(event_ms(parent_way, 1)[0])
+        e = {"a_live_step": pct(np.asarray(ta)), "b_live_step_ours": pct(np.asarray(tb)), "c_parent_route": pct(np.asarray(tc))}
+        e["b_minus_a_p50_ms"] = e["b_live_step_ours"]["p50_ms"] - e["a_live_step"]["p50_ms"]
+        e["c_minus_b_p50_ms"] = e["c_parent_route"]["p50_ms"] - e["b_live_step_ours"]["p50_ms"]
+        assert bool(torch.isfinite(lo.out["pos"]).all())
+        res["streams"][str(S)] = e
+        del live, lo, old
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08", "live_step.json"))
     ap.add_argument("--baseline-only", action="store_true")
+    ap.add_argument("--ours", action="store_true", help="the CVAE branch: live step / live step with the branch / the route without the live step")
     a = ap.parse_args()
+    if a.ours and a.out == ap.get_default("out"):
+        a.out = os.path.join(ROOT, "profiles", "r09", "live_ours_step.json")
     if not torch.cuda.is_available():
         raise SystemExit("live_latency.py measures on the GPU: no ROCm device found")
     dev = torch.device("cuda:0")
@@ -68,6 +136,8 @@ def main():
     per = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (rvel, rang, np.linalg.norm(hipvel, axis=-1).mean(-1).astype(np.float32), contact)]
     res = {"bank": "8 characters x 2048 rows, fp32, segmented", "layout": "mocha (24 joints)", "timing": "HIP events around single graph replays, live and baseline alternating",
            "streams": {}}
+    if a.ours:
+        return write_out(a, ours(a, dev, model, mb, mean, std, clip, per, J))
     for S in (1, 8):
         ids = [(k * 3) % 8 for k in range(S)]
         mb.characterize(torch.zeros((S, 60, J, 15), device=dev), ids, mean, std, raw=True)      # eager first: everything made on first use exists
@@ -113,6 +183,10 @@ def main():
             del sess
         res["streams"][str(S)] = entry
         del ms
+    write_out(a, res)
+
+
+def write_out(a, res):
     print(json.dumps(res, indent=1))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
