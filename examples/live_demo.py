@@ -29,7 +29,12 @@ ap.add_argument("--frames", type=int, default=180, help="mocap frames pushed per
 ap.add_argument("--out", default="bench_outputs/live_demo")
 ap.add_argument("--ours", action="store_true", help="the CVAE branch inside the live step (synthetic CVAE weights and statistics)")
 ap.add_argument("--seed", type=int, default=7, help="--ours: seed of the device's noise")
+ap.add_argument("--soft", nargs=2, metavar=("K", "T"), help="soft matching: the decoder reads the softmax(-dist / T) blend of each stream's K nearest "
+                "entries (1..8) instead of the nearest one")
 a = ap.parse_args()
+if a.ours and a.soft:
+    raise SystemExit("--soft does not apply to --ours: its decoder already reads a sampled character feature")
+soft = (int(a.soft[0]), float(a.soft[1])) if a.soft else None
 if a.frames < 60:
     raise SystemExit("--frames must be at least 60: a stream's first pose comes with its 60th frame")
 os.makedirs(a.out, exist_ok=True)
@@ -67,7 +72,7 @@ if a.ours:                                                            # test_ful
     sess = LiveOursSession(bank, cnt_mean, cnt_std, synthetic_cvae_state_dict(99, 1.0), *stats, streams=S, post=PostProcessor(model),
                            noise="device", seed=a.seed)
 else:
-    sess = LiveSession(bank, cnt_mean, cnt_std, streams=S, post=PostProcessor(model))
+    sess = LiveSession(bank, cnt_mean, cnt_std, streams=S, post=PostProcessor(model), soft=soft)
 sess.push(*[torch.stack([src[s][k][0] for s in range(S)]) for k in range(4)], *[torch.stack([per[s][k][0] for s in range(S)]) for k in range(4)],
           characters=[0, 1])                                          # the first push captures the step
 sess.reset()
@@ -83,7 +88,7 @@ pos, eul = torch.stack(pos, 1), torch.stack(eul, 1)                   # (S, F - 
 
 names = ["Joint%02d" % i for i in range(24)]
 for s in range(S):
-    p = os.path.join(a.out, f"{'Ours' if a.ours else 'live'}_stream{s}.bvh")
+    p = os.path.join(a.out, f"{'Ours' if a.ours else 'soft' if soft else 'live'}_stream{s}.bvh")
     write_bvh(p, names, LAYOUTS["mocha"]["parents"], pos[s], eul[s])
     print(f"  {p}: {os.path.getsize(p)} bytes, {pos.shape[1]} frames")
 print(f"{F} pushes of {S} streams in {dt * 1e3:.1f} ms ({dt / F * 1e3:.3f} ms per push, host loop included)")

@@ -189,7 +189,8 @@ int mocha_step_graph_lane(mocha_ctx* ctx, int lane, const float* X1, const float
  *                             MOCHA_ERR_ARG.  Sizes all the scratch of the segmented calls below (graph-capture safe: they never allocate).
  *                             mocha_bank_set and mocha_bank_broadcast clear the table; a segmented call without one is MOCHA_ERR_STATE.
  *                             Every other call on a segmented bank (mocha_match, mocha_match_topk, mocha_characterize, mocha_step_graph,
- *                             gathers) searches / reads the UNION of all rows, as after mocha_bank_set of the concatenation.
+ *                             gathers) searches / reads the UNION of all rows, as after mocha_bank_set of the concatenation (the soft
+ *                             calls further down are segmented).
  *   mocha_match_segmented   : exact 1-NN of each query (Q, 90*256) within its own segment seg[q] (DEVICE, Q int32): idx (Q,) the row LOCAL
  *                             to the segment (BallTree(that character's cnt_nm).query(k=1)), ties to the lowest row; dist (Q,) or NULL, the
  *                             Euclidean distance in the bank's arithmetic (fp32 rows; MOCHA_BANK_BF16: the bf16 copy centred on the union's
@@ -210,6 +211,44 @@ int mocha_characterize_segmented(mocha_ctx* ctx, const float* src_X, int B, cons
                                  float* Y, int32_t* idx, int raw, void* stream);
 int mocha_step_graph_segmented(mocha_ctx* ctx, const float* X, int S_w, const int32_t* seg, const float* cnt_mean, const float* cnt_std,
                                float* Y, int32_t* idx, int raw, void* stream);
+
+/* Soft context matching on a multi-character bank: the decoder's character feature as the softmax-weighted blend of the k nearest entries
+ * of the window's OWN segment instead of the one nearest entry - tree.query(q, k) on that character's BallTree and a blend of
+ * cha_encoded[frame_index[:, j]], which the reference (k = 1 only, test_fullframework.py:296,443) does not have.  With a hard 1-NN the
+ * nearest row of a live stream flips whenever two entries are nearly equidistant and the pose pops; the blend moves continuously and needs
+ * nothing trained.  1 <= k <= MOCHA_SOFT_MAX_K, temperature > 0 (else MOCHA_ERR_ARG, before anything is launched); a NULL required pointer is
+ * MOCHA_ERR_ARG and a bank without a segment table MOCHA_ERR_STATE, as in the hard calls.  Nothing here allocates: mocha_bank_set_segments
+ * also reserves the key buffer (16 queries x the largest segment's rows rounded up to 16, 8 bytes each, per workspace set: 2 MB at 16 384
+ * rows).  The matcher therefore takes 16 queries at a time: a larger batch walks its windows 16 at a time inside the workspace chunk, ONE
+ * PASS OVER THE QUERIES' SEGMENTS PER 16 WINDOWS at worst (the hard matcher: per 8 windows of one segment in a launch of up to 4 096).
+ *   mocha_match_topk_segmented : replaces BallTree(character seg[q]'s cnt_nm).query(q, k) per character.  idx (Q,k) int32 rows LOCAL to the
+ *                             segment, nearest first, ties to the lower row, -1 where the segment has fewer than k rows; dist (Q,k) or NULL,
+ *                             the Euclidean distance in the bank's arithmetic as mocha_match_segmented reports it (column 0 is that call's
+ *                             answer to the bit), +inf for a missing neighbour.  The order is that of the scan's squared distances, which
+ *                             are mocha_match_segmented's to the bit (one scan body).  An id outside [0, S): idx -1, dist +inf, no bank row
+ *                             read.  Cost: the scan of mocha_match_segmented (the same bytes; + 8 bytes written per row and query), one
+ *                             read of the query's keys, and k bank rows re-read per query for the reported distances.
+ *   mocha_characterize_soft_segmented : mocha_characterize_segmented with, per window, w = softmax_j(-dist_j / temperature) over the
+ *                             neighbours present (max-subtracted as in mocha_bank_gather_blend: exp(-(dist_j - dist_min) / temperature), normalised) and the decoder run on
+ *                             sum_j w_j encoded[segment start + idx_j] (j ascending, fp32, every product and sum rounded on its own).
+ *                             idx_k / w_k (B,k) or NULL; a missing neighbour has weight 0.  k = 1 is mocha_characterize_segmented bit for bit
+ *                             (weight 1).  A window with an invalid id: idx -1, w 0, an unspecified Y (its decoder reads row 0).  Cost over
+ *                             the hard call: k encoded rows read per window for the blend, and the decoder's per-call flow (instance norm
+ *                             and style MLP of the blended feature) - the bank's per-entry decoder constants do not apply to a blend.
+ *   mocha_step_graph_soft_segmented : that call for 1 <= S_w <= 16 windows captured into a HIP graph and replayed, as
+ *                             mocha_step_graph_segmented; idx_k / w_k required.  Keyed on the buffer pointers, S_w, raw, k, the temperature
+ *                             and the generation: new k or temperature re-captures, new ids in seg are read by the replay.  Before a capture
+ *                             the step runs once eagerly (first-use images of its kernels must exist before capture).
+ *   mocha_live_step_soft    : mocha_live_step with that characterize in place of the hard one: the same session buffer, mocha_live_reset,
+ *                             warming rule and refusals; idx (S) receives column 0 of idx_k (S,k); idx_k / w_k required, a warming stream
+ *                             gets -1 / 0.  Its own captured graph, keyed as mocha_live_step's plus k, the temperature, idx_k and w_k. */
+#define MOCHA_SOFT_MAX_K 8
+int mocha_match_topk_segmented(mocha_ctx* ctx, const float* query_nm, int Q, const int32_t* seg, int k, int32_t* idx, float* dist, void* stream);
+int mocha_characterize_soft_segmented(mocha_ctx* ctx, const float* src_X, int B, const int32_t* seg, int k, float temperature,
+                                      const float* cnt_mean, const float* cnt_std, float* Y, int32_t* idx_k, float* w_k, int raw, void* stream);
+int mocha_step_graph_soft_segmented(mocha_ctx* ctx, const float* X, int S_w, const int32_t* seg, int k, float temperature, const float* cnt_mean,
+                                    const float* cnt_std, float* Y, int32_t* idx_k, float* w_k, int raw, void* stream);
+/* (mocha_live_step_soft is declared below, after mocha_live_step.) */
 
 /* Multi-GPU set-up: one process per GPU, windows sharded across ranks, the character bank replicated.
  * The reference has no counterpart (trainer.py:45-47 is nn.DataParallel); the only exchange on the path is this one-time
@@ -378,6 +417,12 @@ int mocha_live_step(mocha_ctx* ctx, const mocha_post_cfg* cfg, void* live, int s
                     const float* Yvel, const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed,
                     const unsigned char* contact, const int32_t* seg, const float* cnt_mean, const float* cnt_std, double* pos,
                     double* rot, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx, int32_t* valid, void* stream);
+/* mocha_live_step with the soft characterize (see "Soft context matching on a multi-character bank" above). */
+int mocha_live_step_soft(mocha_ctx* ctx, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos,
+                         const float* Yvel, const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed,
+                         const unsigned char* contact, const int32_t* seg, const float* cnt_mean, const float* cnt_std, int k, float temperature,
+                         double* pos, double* rot, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx, int32_t* valid,
+                         int32_t* idx_k, float* w_k, void* stream);
 
 /* The CVAE ("Ours") branch inside the live step (test_fullframework.py:446-457; a stream's first frame is :290-298): mocha_live_step
  * with the decoder's character feature sampled from the previous one instead of taken from the matched bank row.  The autoregressive

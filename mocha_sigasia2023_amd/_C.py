@@ -91,6 +91,10 @@ SIGNATURES = {
     "mocha_match_segmented": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "mocha_characterize_segmented": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "mocha_step_graph_segmented": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "mocha_match_topk_segmented": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "mocha_characterize_soft_segmented": (_i, [_vp, _vp, _i, _vp, _i, C.c_float, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "mocha_step_graph_soft_segmented": (_i, [_vp, _vp, _i, _vp, _i, C.c_float, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "mocha_live_step_soft": (_i, [_vp, _vp, _vp, _i] + [_vp] * 11 + [_i, C.c_float] + [_vp] * 10),
     "mocha_set_rccl_library": (_i, [C.c_char_p]),
     "mocha_comm_unique_id": (_i, [_vp, _vp]),
     "mocha_comm_init": (_i, [_vp, _vp, _i, _i]),

@@ -310,6 +310,19 @@ size_t seg_plan_ints(int Q, int S);
 hipError_t launch_match_segmented(const void* bank, int bank_bf16, const float* query, const int32_t* seg, int Q, const int* seg_start, int S,
                                   int64_t max_rows, int D, unsigned long long* partial, int* plan, int32_t* idx, int32_t* gidx, float* dist,
                                   hipStream_t s);
+hipError_t launch_seg_plan(const int32_t* seg, int Q, int S, int* plan, hipStream_t s);      // the matcher's first kernel alone (plan = seg_plan_ints(Q, S) ints)
+// soft matching on a multi-character bank (match_seg_topk.hip): per query the k <= SEG_TOPK_MAX_K nearest rows of its own segment - idx_k
+// (Q,k) local rows ascending by distance, ties to the lower row, -1 where the segment has fewer than k rows; dist_k (Q,k) the distance
+// launch_match_segmented reports for that row (+inf); w_k (Q,k) = softmax_j(-dist / temperature) over the neighbours present (0) - and
+// out (Q,D) = sum_j w_k[j] enc[segment start + idx_k[j]].  idx0 (Q) = column 0 of idx_k.  Any of the five outputs may be null.  An id
+// outside [0, S): -1 / +inf / 0 and out = enc[0].  Any Q: the queries are walked SEG_TOPK_Q at a time through keys =
+// match_seg_keys_words(largest segment) u64 words; plan = seg_plan_ints(SEG_TOPK_Q, S) ints.
+static constexpr int SEG_TOPK_MAX_K = 8;
+static constexpr int SEG_TOPK_Q = 16;
+size_t match_seg_keys_words(int64_t max_rows);
+hipError_t launch_match_seg_topk(const void* bank, int bank_bf16, const float* query, const int32_t* seg, int Q, const int* seg_start, int S,
+                                 int64_t max_rows, int D, unsigned long long* keys, int* plan, const float* enc, int k, float temperature,
+                                 int32_t* idx0, int32_t* idx_k, float* dist_k, float* w_k, float* out, hipStream_t s);
 // out[q] = src[idx[q]] rows of `cols` floats
 hipError_t launch_gather_rows(const float* src, const int32_t* idx, float* out, int Q, int cols, int64_t nrows, hipStream_t s);
 

@@ -23,21 +23,12 @@
 //    in-bank row for the decoder's gather).  No kernel ever indexes the bank with an id: only with rows inside [0, N).
 // The bank may be fp32 rows or the centred bf16 copy (then with centred queries), as mocha_match_stream<f32|bf16>.
 #include "kernels.h"
-#include "match_stream_body.h"
+#include "match_seg_body.h"
 
 namespace mocha {
 
-static constexpr int SEG_ROWS = MS_WAVES * MS_ROWS_PER_WAVE;     // rows per scan workgroup
 static constexpr int SEG_PLAN_T = 1024;
 
-__host__ __device__ inline int seg_blocks_bound(int Q, int S) {      // sum_s ceil(c_s / 8) <= (Q + 7 min(S, Q)) / 8, and <= Q
-    const int k = S < Q ? S : Q;
-    const int b = (Q + 7 * k) / 8;
-    return b < Q ? b : Q;
-}
-
-// plan layout (ints): [0] block count, then per block: segment, query count, 8 query indices
-static constexpr int PLAN_STRIDE = 10;
 size_t seg_plan_ints(int Q, int S) { return 1 + (size_t)PLAN_STRIDE * seg_blocks_bound(Q, S); }
 
 __global__ __launch_bounds__(SEG_PLAN_T) void mocha_seg_plan(const int32_t* __restrict__ seg, int Q, int S, int* __restrict__ plan) {
@@ -82,139 +73,11 @@ __global__ __launch_bounds__(SEG_PLAN_T) void mocha_seg_plan(const int32_t* __re
     }
 }
 
-// rows [row0, row0 + 4) of this wave, clamped to the segment's last row; qidx: the block's query indices (LDS)
-template <int Q, bool BF16>
-__device__ __forceinline__ void seg_scan_body(const void* __restrict__ bank, const float* __restrict__ query, const int* qidx, int nq,
-                                              long long seg_lo, long long seg_n, long long row0, int D, float* __restrict__ qs,
-                                              unsigned long long (*wbest)[8], unsigned long long* __restrict__ partial, int pstride) {
-    constexpr int MS_CHUNK = BF16 ? MS_CHUNK_BF16 : MS_CHUNK_F32;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    ms_f32x2 acc[MS_ROWS_PER_WAVE][Q];
-#pragma unroll
-    for (int r = 0; r < MS_ROWS_PER_WAVE; ++r)
-#pragma unroll
-        for (int q = 0; q < Q; ++q) acc[r][q] = ms_f32x2{0.f, 0.f};
-    const int nchunks = D / MS_CHUNK;
-    for (int ch = 0; ch < nchunks; ++ch) {
-        __syncthreads();
-        for (int i = tid; i < Q * (MS_CHUNK / 4); i += 256) {
-            const int q = i / (MS_CHUNK / 4), o = i - q * (MS_CHUNK / 4);
-            ms_f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (q < nq) v = reinterpret_cast<const ms_f32x4*>(query + (size_t)qidx[q] * D + (size_t)ch * MS_CHUNK)[o];
-            reinterpret_cast<ms_f32x4*>(qs)[i] = v;
-        }
-        __syncthreads();
-        if (!BF16) {
-            ms_f32x4 bv[MS_ROWS_PER_WAVE][5];
-#pragma unroll
-            for (int r = 0; r < MS_ROWS_PER_WAVE; ++r) {
-                long long row = row0 + r;
-                row = seg_lo + (row < seg_n ? row : seg_n - 1);
-                const ms_f32x4* bp = reinterpret_cast<const ms_f32x4*>(reinterpret_cast<const float*>(bank) + (size_t)row * D + (size_t)ch * MS_CHUNK);
-#pragma unroll
-                for (int i = 0; i < 5; ++i) bv[r][i] = __builtin_nontemporal_load(bp + lane + 64 * i);
-            }
-#pragma unroll
-            for (int i = 0; i < 5; ++i)
-#pragma unroll
-                for (int q = 0; q < Q; ++q) {
-                    const ms_f32x4 qv = reinterpret_cast<const ms_f32x4*>(qs)[q * (MS_CHUNK / 4) + lane + 64 * i];
-#pragma unroll
-                    for (int r = 0; r < MS_ROWS_PER_WAVE; ++r) {
-                        const ms_f32x4 d = bv[r][i] - qv;
-                        const ms_f32x2 dl = {d[0], d[1]}, dh = {d[2], d[3]};
-                        acc[r][q] = __builtin_elementwise_fma(dl, dl, acc[r][q]);
-                        acc[r][q] = __builtin_elementwise_fma(dh, dh, acc[r][q]);
-                    }
-                }
-        } else {
-            ms_u32x4 bv[MS_ROWS_PER_WAVE][3];
-#pragma unroll
-            for (int r = 0; r < MS_ROWS_PER_WAVE; ++r) {
-                long long row = row0 + r;
-                row = seg_lo + (row < seg_n ? row : seg_n - 1);
-                const ms_u32x4* bp = reinterpret_cast<const ms_u32x4*>(reinterpret_cast<const unsigned short*>(bank) + (size_t)row * D + (size_t)ch * MS_CHUNK);
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    const int piece = lane + 64 * i;
-                    ms_u32x4 z = {0u, 0u, 0u, 0u};
-                    bv[r][i] = piece < MS_CHUNK / 8 ? __builtin_nontemporal_load(bp + piece) : z;
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const int piece = lane + 64 * i;
-                if (piece < MS_CHUNK / 8) {
-#pragma unroll
-                    for (int q = 0; q < Q; ++q) {
-                        const ms_f32x4 q0 = reinterpret_cast<const ms_f32x4*>(qs)[q * (MS_CHUNK / 4) + piece * 2];
-                        const ms_f32x4 q1 = reinterpret_cast<const ms_f32x4*>(qs)[q * (MS_CHUNK / 4) + piece * 2 + 1];
-#pragma unroll
-                        for (int r = 0; r < MS_ROWS_PER_WAVE; ++r) {
-                            const ms_u32x4 w = bv[r][i];
-                            ms_f32x2 d;
-                            d = ms_f32x2{__uint_as_float(w[0] << 16), __uint_as_float(w[0] & 0xffff0000u)} - ms_f32x2{q0[0], q0[1]};
-                            acc[r][q] = __builtin_elementwise_fma(d, d, acc[r][q]);
-                            d = ms_f32x2{__uint_as_float(w[1] << 16), __uint_as_float(w[1] & 0xffff0000u)} - ms_f32x2{q0[2], q0[3]};
-                            acc[r][q] = __builtin_elementwise_fma(d, d, acc[r][q]);
-                            d = ms_f32x2{__uint_as_float(w[2] << 16), __uint_as_float(w[2] & 0xffff0000u)} - ms_f32x2{q1[0], q1[1]};
-                            acc[r][q] = __builtin_elementwise_fma(d, d, acc[r][q]);
-                            d = ms_f32x2{__uint_as_float(w[3] << 16), __uint_as_float(w[3] & 0xffff0000u)} - ms_f32x2{q1[2], q1[3]};
-                            acc[r][q] = __builtin_elementwise_fma(d, d, acc[r][q]);
-                        }
-                    }
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        unsigned long long kmin = ~0ull;
-#pragma unroll
-        for (int r = 0; r < MS_ROWS_PER_WAVE; ++r) {
-            const long long row = row0 + r;
-            float v = acc[r][q][0] + acc[r][q][1];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-            if (row < seg_n) {
-                const unsigned long long k = pack_key(v, (unsigned)row);      // local row: ties to the lowest
-                kmin = k < kmin ? k : kmin;
-            }
-        }
-        if (lane == 0) wbest[wave][q] = kmin;
-    }
-    __syncthreads();
-    if (tid < nq) {                                  // tid < nq <= Q
-        unsigned long long k = wbest[0][tid];
-#pragma unroll
-        for (int w = 1; w < MS_WAVES; ++w) k = wbest[w][tid] < k ? wbest[w][tid] : k;
-        partial[(size_t)qidx[tid] * pstride + blockIdx.x] = k;
-    }
-}
-
 // partial: [Q][gridDim.x] (query-major, the query's chunks of its segment)
 template <bool BF16>
 __global__ __launch_bounds__(256) void mocha_match_seg_scan(const void* __restrict__ bank, const float* __restrict__ query, const int* __restrict__ plan,
                                                             const int* __restrict__ seg_start, int D, unsigned long long* __restrict__ partial) {
-    constexpr int MS_CHUNK = BF16 ? MS_CHUNK_BF16 : MS_CHUNK_F32;
-    __shared__ __attribute__((aligned(16))) float qs[8 * MS_CHUNK];
-    __shared__ unsigned long long wbest[MS_WAVES][8];
-    __shared__ int qidx[8];
-    const int b = blockIdx.y;
-    if (b >= plan[0]) return;
-    const int* e = plan + 1 + (size_t)b * PLAN_STRIDE;
-    const int s = e[0], nq = e[1];
-    const long long lo = seg_start[s], n = (long long)seg_start[s + 1] - lo;
-    const long long x0 = (long long)blockIdx.x * SEG_ROWS;
-    if (x0 >= n) return;
-    if (threadIdx.x < 8) qidx[threadIdx.x] = threadIdx.x < nq ? e[2 + threadIdx.x] : 0;
-    // (the body's first barrier orders qidx before its use)
-    const long long row0 = x0 + (long long)(threadIdx.x >> 6) * MS_ROWS_PER_WAVE;
-    const int ps = gridDim.x;
-    if (nq == 1) seg_scan_body<1, BF16>(bank, query, qidx, nq, lo, n, row0, D, qs, wbest, partial, ps);
-    else if (nq == 2) seg_scan_body<2, BF16>(bank, query, qidx, nq, lo, n, row0, D, qs, wbest, partial, ps);
-    else if (nq <= 4) seg_scan_body<4, BF16>(bank, query, qidx, nq, lo, n, row0, D, qs, wbest, partial, ps);
-    else seg_scan_body<8, BF16>(bank, query, qidx, nq, lo, n, row0, D, qs, wbest, partial, ps);
+    seg_scan_workgroup<BF16, false>(bank, query, plan, seg_start, D, partial, (int)gridDim.x);
 }
 
 template <bool BF16>
@@ -252,23 +115,18 @@ __global__ __launch_bounds__(256) void mocha_match_seg_finish(const unsigned lon
         if (gidx) gidx[q] = (int32_t)row;
     }
     if (!dist) return;
-    float a = 0.f;
-    for (int i = tid; i < D; i += 256) {
-        float b;
-        if (BF16) b = __uint_as_float((unsigned)reinterpret_cast<const unsigned short*>(bank)[row * D + i] << 16);
-        else b = reinterpret_cast<const float*>(bank)[row * D + i];
-        const float d = query[(size_t)q * D + i] - b;
-        a = fmaf(d, d, a);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
-    if ((tid & 63) == 0) red[tid >> 6] = a;
-    __syncthreads();
-    if (tid == 0) dist[q] = sqrtf((red[0] + red[1]) + (red[2] + red[3]));
+    const float d2 = seg_direct_dist2<BF16>(bank, query + (size_t)q * D, row, D, red);
+    if (tid == 0) dist[q] = sqrtf(d2);
 }
 
 size_t match_seg_scratch_words(int Q, int64_t max_rows) {       // partial minima of Q queries against segments of up to max_rows rows
     return (size_t)Q * (size_t)((max_rows + SEG_ROWS - 1) / SEG_ROWS);
+}
+
+hipError_t launch_seg_plan(const int32_t* seg, int Q, int S, int* plan, hipStream_t s) {
+    if (Q < 1 || Q > SEG_MAX_Q || S < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mocha_seg_plan, dim3(1), dim3(SEG_PLAN_T), 0, s, seg, Q, S, plan);
+    return hipGetLastError();
 }
 
 hipError_t launch_match_segmented(const void* bank, int bank_bf16, const float* query, const int32_t* seg, int Q, const int* seg_start, int S,

@@ -110,6 +110,10 @@ struct SetScratch {
     // segmented calls never allocate)
     DeviceBuffer<unsigned long long> seg_partial{BUF_MOVES_GENERATION};
     DeviceBuffer<int> seg_plan{BUF_MOVES_GENERATION};
+    // the soft matcher's keys: every row's key of SEG_TOPK_Q queries against the largest segment (match_seg_topk.hip).  Reserved with the two
+    // above and nowhere else, i.e. only by mocha_bank_set_segments, which moves the generation for the new bank anyway: BUF_PLAIN, so
+    // that the generation counts what it counted before this buffer existed
+    DeviceBuffer<unsigned long long> seg_keys;
     const float* amax_enc_of = nullptr; float* amax_enc = nullptr;     // encoder output pointer -> its slot
     const float* amax_dec_of = nullptr; float* amax_dec = nullptr;     // decoder output pointer -> its slot
     const float* amax_tok_of = nullptr; float* amax_tok = nullptr;     // embedding output pointer -> its slot
@@ -271,12 +275,15 @@ struct mocha_ctx {
         // mocha_live_step_ours only: the state buffer, the four statistics, the caller's noise and the seeded output; the noise mode and seed
         const void* ours[7] = {};
         int noise = 0; unsigned long long seed = 0;
+        // the soft steps only: neighbours, temperature, and the (windows, k) outputs idx_k / w_k
+        int soft_k = 0; float soft_t = 0.f; const void* soft[2] = {};
         bool operator==(const StepKey& o) const {
             if (!(x == o.x && mean == o.mean && sd == o.sd && y == o.y && idx == o.idx && seg == o.seg && windows == o.windows && raw == o.raw))
                 return false;
             for (int i = 0; i < 17; ++i) if (live[i] != o.live[i]) return false;
             for (int i = 0; i < 7; ++i) if (ours[i] != o.ours[i]) return false;
             if (noise != o.noise || seed != o.seed) return false;
+            if (soft_k != o.soft_k || soft_t != o.soft_t || soft[0] != o.soft[0] || soft[1] != o.soft[1]) return false;
             const mocha_post_cfg &a = post, &b = o.post;
             for (int i = 0; i < 4; ++i) if (a.contact_bones[i] != b.contact_bones[i]) return false;
             return a.dt == b.dt && a.ik_max_length_buffer == b.ik_max_length_buffer && a.ik_foot_height == b.ik_foot_height &&
@@ -287,7 +294,8 @@ struct mocha_ctx {
     struct StepGraph {
         hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr;
         StepKey key; int64_t generation = -1;
-    } step[MAX_SETS], seg_step, live_step, ours_step; // seg_step: mocha_step_graph_segmented, live_step: mocha_live_step, ours_step: mocha_live_step_ours (workspace set 0)
+    } step[MAX_SETS], seg_step, live_step, ours_step, // seg_step: mocha_step_graph_segmented, live_step: mocha_live_step, ours_step: mocha_live_step_ours (workspace set 0)
+      soft_step, live_soft_step;                      // mocha_step_graph_soft_segmented, mocha_live_step_soft (workspace set 0)
     hipStream_t cap_stream = nullptr;                 // capture happens on this internal stream (the caller's may be the null stream)
     ncclComm_t comm = nullptr; int comm_rank = 0, comm_size = 1;      // mocha_comm_init
     DeviceBuffer<long long> bcast_hdr;                                  // device: {entries, bf16?} header of mocha_bank_broadcast
@@ -1247,6 +1255,7 @@ int ensure_seg_scratch(mocha_ctx* c, int set) {
     const int S = (int)c->bank.seg_start.size() - 1;
     int rc = reserve(c, c->sets[set].seg_partial, match_seg_scratch_words(c->seg_q, c->bank.seg_max_rows));
     if (!rc) rc = reserve(c, c->sets[set].seg_plan, seg_plan_ints(c->seg_q, S));
+    if (!rc) rc = reserve(c, c->sets[set].seg_keys, match_seg_keys_words(c->bank.seg_max_rows));
     return rc;
 }
 
@@ -1267,6 +1276,26 @@ int seg_match(mocha_ctx* c, const float* q, int Q, const int32_t* seg, int32_t* 
                                       c->sets[set].seg_partial.p, c->sets[set].seg_plan.p, idx ? idx + q0 : nullptr, gidx ? gidx + q0 : nullptr,
                                       dist ? dist + q0 : nullptr, s));
     }
+    return 0;
+}
+
+// The k nearest rows of every query within its own segment, their softmax weights and the blend of their encoded rows (match_seg_topk.hip):
+// q as for seg_match; idx0 (Q) / idx_k, dist_k, w_k (Q,k) / out (Q,90,256), each may be null.  One pass over the queries' segments per 16
+// queries, through the key buffer of the current workspace set.
+int seg_topk(mocha_ctx* c, const float* q, int Q, const int32_t* seg, int k, float temperature, int32_t* idx0, int32_t* idx_k, float* dist_k,
+             float* w_k, float* out, hipStream_t s) {
+    if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    const int set = c->cur, S = (int)c->bank.seg_start.size() - 1;
+    const int D = 90 * 256;
+    if (!c->sets[set].seg_keys.p || !c->sets[set].seg_plan.p)
+        return fail(c, MOCHA_ERR_STATE, "workspace set %d has no segmented-match scratch: call mocha_bank_set_segments after changing the workspaces", set);
+    const bool b16 = c->bank.is_bf16;
+    const void* bank = b16 ? (const void*)c->bank.bf16.p : (const void*)c->bank.cnt;
+    const double passes = (Q + SEG_TOPK_Q - 1) / SEG_TOPK_Q;
+    LAUNCH(c, s, b16 ? "mocha_match_seg_keys<bf16>" : "mocha_match_seg_keys<f32>", "match.soft", 3.0 * Q * c->bank.seg_max_rows * D + 2.0 * Q * k * D,
+           passes * c->bank.seg_max_rows * D * (b16 ? 2.0 : 4.0) + 16.0 * Q * c->bank.seg_max_rows + Q * (k * (b16 ? 6.0 : 8.0) + 8.0) * D,
+           launch_match_seg_topk(bank, b16 ? 1 : 0, q, seg, Q, c->bank.seg_dev.p, S, c->bank.seg_max_rows, D, c->sets[set].seg_keys.p,
+                                 c->sets[set].seg_plan.p, c->bank.enc, k, temperature, idx0, idx_k, dist_k, w_k, out, s));
     return 0;
 }
 
@@ -1337,7 +1366,7 @@ void mocha_destroy(mocha_ctx* c) {
     if (c->aux) (void)hipStreamDestroy(c->aux);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    for (auto* g : {&c->step[0], &c->step[1], &c->step[2], &c->seg_step, &c->live_step, &c->ours_step}) {
+    for (auto* g : {&c->step[0], &c->step[1], &c->step[2], &c->seg_step, &c->live_step, &c->ours_step, &c->soft_step, &c->live_soft_step}) {
         if (g->exec) (void)hipGraphExecDestroy(g->exec);
         if (g->graph) (void)hipGraphDestroy(g->graph);
     }
@@ -2155,6 +2184,100 @@ int mocha_step_graph_segmented(mocha_ctx* c, const float* X, int S_w, const int3
     });
 }
 
+// ------------------------------------------------------------------------------------------- soft matching, multi-character bank
+// The decoder's character feature as the softmax-weighted blend of the k nearest entries of the window's own segment instead of the one
+// nearest entry: nothing trained, and no pop when two entries are nearly equidistant.  The matcher is match_seg_topk.hip; the decoder runs
+// on the blended feature itself (the literal flow: instance norm and style MLP of the feature per call, as mocha_live_step_ours - the
+// bank's per-entry decoder constants do not apply to a blend).
+static_assert(MOCHA_SOFT_MAX_K == SEG_TOPK_MAX_K, "the header's k limit is the kernel's");
+static int soft_args(mocha_ctx* c, const char* what, int k, float temperature) {
+    if (k < 1 || k > MOCHA_SOFT_MAX_K) return fail(c, MOCHA_ERR_ARG, "%s: 1 <= k <= %d neighbours", what, MOCHA_SOFT_MAX_K);
+    if (!(temperature > 0.f)) return fail(c, MOCHA_ERR_ARG, "%s: temperature must be positive", what);
+    return 0;
+}
+
+// embed -> encoder -> cnt, z-score (bf16 bank: centred queries) -> k nearest + weights + blend into the "sel" workspace -> literal decoder on
+// the blend -> to_mot.  idx0 (B) / idx_k, w_k (B,k): each may be null.  The caller checked k and temperature.
+static int characterize_soft_impl(mocha_ctx* c, const float* src_X, int B, const int32_t* seg, int k, float temperature, const float* cnt_mean,
+                                  const float* cnt_std, float* Y, int32_t* idx0, int32_t* idx_k, float* w_k, bool raw, void* stream) {
+    int rc = ready(c, B); if (rc) return rc;
+    if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
+    if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (B == 0) return 0;
+    if (!cnt_mean || !cnt_std || !src_X || !Y || !seg) return fail(c, MOCHA_ERR_ARG, "null argument");
+    const size_t ys = (size_t)60 * c->cfg.V * c->cfg.C_in;
+    const size_t xs = raw ? (size_t)60 * (c->cfg.V + 1) * c->cfg.C_in : ys;
+    return for_chunks(c, B, (hipStream_t)stream, [&](int b0, int b, hipStream_t s) -> int {
+        int r;
+        if ((r = run_embed(c, src_X + b0 * xs, b, WS(c, "x5"), true, s, raw))) return r;
+        if ((r = run_encoder(c, WS(c, "x5"), b, WS(c, "enc_s"), s))) return r;
+        InormExtra ex = IEX(c);
+        if (c->bank.is_bf16) { ex.centre = c->bank.center.p; ex.zc = WS(c, "qc"); }
+        LAUNCH(c, s, "mocha_instnorm", "mvn", 0.0, b * 90.0 * 256 * 4 * (c->bank.is_bf16 ? 3.0 : 2.0), launch_instnorm(WS(c, "enc_s"), nullptr, nullptr, cnt_mean, cnt_std, WS(c, "qnm"), b, 90, s, &ex));
+        if ((r = seg_topk(c, WS(c, c->bank.is_bf16 ? "qc" : "qnm"), b, seg + b0, k, temperature, idx0 ? idx0 + b0 : nullptr,
+                          idx_k ? idx_k + (size_t)b0 * k : nullptr, nullptr, w_k ? w_k + (size_t)b0 * k : nullptr, WS(c, "sel"), s))) return r;
+        if ((r = run_decoder(c, WS(c, "enc_s"), WS(c, "sel"), b, WS(c, "dec"), s))) return r;
+        return run_to_mot(c, WS(c, "dec"), b, Y + b0 * ys, s, raw);
+    });
+}
+
+int mocha_match_topk_segmented(mocha_ctx* c, const float* query_nm, int Q, const int32_t* seg, int k, int32_t* idx, float* dist, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    int rc = soft_args(c, "match_topk_segmented", k, 1.f); if (rc) return rc;
+    if ((rc = ready(c, 0))) return rc;
+    if (!query_nm || !seg || !idx || Q < 0) return fail(c, MOCHA_ERR_ARG, "bad match_topk_segmented arguments");
+    if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (Q == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int D = 90 * 256;
+    c->cur = 0;
+    if (!c->bank.is_bf16) return seg_topk(c, query_nm, Q, seg, k, 1.f, nullptr, idx, dist, nullptr, nullptr, s);
+    // the bf16 copy holds bf16(b - centroid of the union): centred queries, as many at a time as the centred-query buffer holds
+    const int per = (int)std::min<size_t>((size_t)c->seg_q, c->sets[0].match_qc.n / D);
+    for (int q0 = 0; q0 < Q; q0 += per) {
+        const int n = std::min(per, Q - q0);
+        LAUNCH(c, s, "mocha_sub_rows", "match.center", 0.0, 8.0 * n * D, launch_sub_rows(query_nm + (size_t)q0 * D, c->bank.center.p, c->sets[0].match_qc.p, n, D, s));
+        if ((rc = seg_topk(c, c->sets[0].match_qc.p, n, seg + q0, k, 1.f, nullptr, idx + (size_t)q0 * k, dist ? dist + (size_t)q0 * k : nullptr, nullptr,
+                           nullptr, s))) return rc;
+    }
+    return 0;
+}
+
+int mocha_characterize_soft_segmented(mocha_ctx* c, const float* src_X, int B, const int32_t* seg, int k, float temperature, const float* cnt_mean,
+                                      const float* cnt_std, float* Y, int32_t* idx_k, float* w_k, int raw, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    int rc = soft_args(c, "characterize_soft_segmented", k, temperature); if (rc) return rc;
+    if (B > 0 && !seg) return fail(c, MOCHA_ERR_ARG, "characterize_soft_segmented: null argument");
+    return characterize_soft_impl(c, src_X, B, seg, k, temperature, cnt_mean, cnt_std, Y, nullptr, idx_k, w_k, raw != 0, stream);
+}
+
+int mocha_step_graph_soft_segmented(mocha_ctx* c, const float* X, int S_w, const int32_t* seg, int k, float temperature, const float* cnt_mean,
+                                    const float* cnt_std, float* Y, int32_t* idx_k, float* w_k, int raw, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    int rc = soft_args(c, "step_graph_soft_segmented", k, temperature); if (rc) return rc;
+    if (S_w < 1 || S_w > 16) return fail(c, MOCHA_ERR_ARG, "step_graph_soft_segmented: 1 <= S_w <= 16 windows");
+    if ((rc = ready(c, S_w))) return rc;
+    if (!X || !seg || !cnt_mean || !cnt_std || !Y || !idx_k || !w_k) return fail(c, MOCHA_ERR_ARG, "null argument");
+    if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
+    if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    mocha_ctx::StepKey key; key.x = X; key.mean = cnt_mean; key.sd = cnt_std; key.y = Y; key.seg = seg; key.windows = S_w; key.raw = raw != 0;
+    key.soft_k = k; key.soft_t = temperature; key.soft[0] = idx_k; key.soft[1] = w_k;
+    auto body = [&](hipStream_t cs) -> int {
+        c->lane = 0;
+        const int r = characterize_soft_impl(c, X, S_w, seg, k, temperature, cnt_mean, cnt_std, Y, nullptr, idx_k, w_k, raw != 0, cs);
+        c->cur = 0;
+        return r;
+    };
+    const auto& g = c->soft_step;
+    if (!(g.exec && g.key == key && g.generation == c->generation)) {
+        // Before a capture: the step once, eagerly, so that whatever its kernels make on first use - the plane GEMMs' weight images, the
+        // float64 weights of the literal decoder's style MLP - exists; it writes what the replay then writes again.
+        if ((rc = body((hipStream_t)stream))) return rc;
+    }
+    // the ids are read by the captured kernels on every replay: new ids in `seg` are not part of the key; k and the temperature are
+    return step_replay(c, c->soft_step, key, (hipStream_t)stream, body);
+}
+
 // ------------------------------------------------------------------------------------------- RCCL (multi-GPU set-up)
 // One process per GPU; the only exchange on the path is the one-time broadcast of the character bank.
 // RCCL is resolved at run time (dlopen of librccl.so.1) so that single-GPU users never load it.
@@ -2770,11 +2893,12 @@ int mocha_live_reset(mocha_ctx* c, void* live, int streams, const int32_t* which
     return 0;
 }
 
-int mocha_live_step(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos, const float* Yvel,
-                    const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed, const unsigned char* contact,
-                    const int32_t* seg, const float* cnt_mean, const float* cnt_std, double* pos, double* rot, double* ik_rot, double* bvh_pos,
-                    double* bvh_euler, int32_t* idx, int32_t* valid, void* stream) {
-    if (!c) return MOCHA_ERR_ARG;
+// mocha_live_step (k = 0: the hard 1-NN characterize, idx_k / w_k unused) and mocha_live_step_soft (k >= 1: the soft characterize in its place;
+// the caller checked k, the temperature and idx_k / w_k): one body, each with its own captured graph
+static int live_step_impl(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos, const float* Yvel,
+                          const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed, const unsigned char* contact,
+                          const int32_t* seg, const float* cnt_mean, const float* cnt_std, double* pos, double* rot, double* ik_rot, double* bvh_pos,
+                          double* bvh_euler, int32_t* idx, int32_t* valid, int k, float temperature, int32_t* idx_k, float* w_k, void* stream) {
     if (streams < 1 || streams > 16) return fail(c, MOCHA_ERR_ARG, "live_step: 1 <= streams <= 16");
     if (!live || !Yrot || !Ypos || !Yvel || !Yang || !src_rvel || !src_rang || !src_speed || !contact || !seg || !cnt_mean || !cnt_std || !pos ||
         !rot || !ik_rot || !idx || !valid || (!bvh_pos) != (!bvh_euler))
@@ -2809,13 +2933,19 @@ int mocha_live_step(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, int str
     p.n_clips = streams; p.n_frames = 1; p.state = pstate; p.valid = valid;
     const int J = c->cfg.V + 1, V = c->cfg.V;
 
+    // the segmented characterize of the S staging windows with the ids in eff: hard, or soft with column 0 of idx_k in idx
+    auto characterize = [&](int32_t* ix, int32_t* ixk, float* wk, hipStream_t cs) -> int {
+        c->lane = 0;
+        const int r = k > 0 ? characterize_soft_impl(c, xraw, streams, eff, k, temperature, cnt_mean, cnt_std, ystage, ix, ixk, wk, true, cs)
+                            : characterize_impl(c, xraw, streams, cnt_mean, cnt_std, ystage, ix, cs, true, eff);
+        c->cur = 0;
+        return r;
+    };
     // ring push + featurize -> segmented characterize of the S windows with the effective ids -> pose heads -> one post-processing frame
     auto body = [&](hipStream_t cs) -> int {
         LAUNCH(c, cs, "mocha_live_push", "live.push", streams * 60.0 * J * 150, streams * (60.0 * J * (13 + 15) + J * 26.0) * 4,
                launch_live_push(ring, Yrot, Ypos, Yvel, Yang, seg, c->bone_parents.p, xraw, eff, valid, streams, J, cs));
-        c->lane = 0;
-        const int r = characterize_impl(c, xraw, streams, cnt_mean, cnt_std, ystage, idx, cs, true, eff);
-        c->cur = 0;
+        const int r = characterize(idx, idx_k, w_k, cs);
         if (r) return r;
         LAUNCH(c, cs, "mocha_pose_heads", "live.heads", 0.0, streams * (60.0 * 12 + V * 28.0 * 4), launch_pose_heads(ystage, heads, speed, streams, c->cfg.T, V, cs));
         LAUNCH(c, cs, "mocha_post_clip", "live.post", 0.0, (double)streams * (V * 13.0 * 4 + J * 11.0 * 8 + 2.0 * POST_STATE_DOUBLES * 8),
@@ -2831,19 +2961,37 @@ int mocha_live_step(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, int str
     const void* ptrs[17] = {Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, pos, rot, ik_rot, bvh_pos, bvh_euler, valid, nullptr, nullptr, nullptr};
     for (int i = 0; i < 17; ++i) key.live[i] = ptrs[i];
     key.post = *cfg;
-    const auto& g = c->live_step;
+    key.soft_k = k; key.soft_t = k > 0 ? temperature : 0.f; key.soft[0] = k > 0 ? idx_k : nullptr; key.soft[1] = k > 0 ? w_k : nullptr;
+    mocha_ctx::StepGraph& g = k > 0 ? c->live_soft_step : c->live_step;
     if (!(g.exec && g.key == key && g.generation == c->generation)) {
         // Before a capture: one eager characterize of the staging windows with every id -1 (no bank row is matched, no state of the
-        // session moves), so that whatever the kernels of the step make on first use - the plane GEMMs' weight images - exists and the
-        // captured step takes the kernels every later step takes.
+        // session moves), so that whatever the kernels of the step make on first use - the plane GEMMs' weight images, for the soft step
+        // the float64 weights of the literal decoder's style MLP - exists and the captured step takes the kernels every later step takes.
         HIPCHK(c, hipMemsetAsync(xraw, 0, (size_t)streams * 60 * J * c->cfg.C_in * sizeof(float), s));
         HIPCHK(c, hipMemsetAsync(eff, 0xFF, (size_t)streams * sizeof(int32_t), s));
-        c->lane = 0;
-        rc = characterize_impl(c, xraw, streams, cnt_mean, cnt_std, ystage, nullptr, s, true, eff);
-        c->cur = 0;
-        if (rc) return rc;
+        if ((rc = characterize(nullptr, nullptr, nullptr, s))) return rc;
     }
-    return step_replay(c, c->live_step, key, s, body);
+    return step_replay(c, g, key, s, body);
+}
+
+int mocha_live_step(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos, const float* Yvel,
+                    const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed, const unsigned char* contact,
+                    const int32_t* seg, const float* cnt_mean, const float* cnt_std, double* pos, double* rot, double* ik_rot, double* bvh_pos,
+                    double* bvh_euler, int32_t* idx, int32_t* valid, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    return live_step_impl(c, cfg, live, streams, Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, seg, cnt_mean, cnt_std, pos, rot,
+                          ik_rot, bvh_pos, bvh_euler, idx, valid, 0, 0.f, nullptr, nullptr, stream);
+}
+
+int mocha_live_step_soft(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos, const float* Yvel,
+                         const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed, const unsigned char* contact,
+                         const int32_t* seg, const float* cnt_mean, const float* cnt_std, int k, float temperature, double* pos, double* rot,
+                         double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx, int32_t* valid, int32_t* idx_k, float* w_k, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    int rc = soft_args(c, "live_step_soft", k, temperature); if (rc) return rc;
+    if (!idx_k || !w_k) return fail(c, MOCHA_ERR_ARG, "live_step_soft: null argument");
+    return live_step_impl(c, cfg, live, streams, Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, seg, cnt_mean, cnt_std, pos, rot,
+                          ik_rot, bvh_pos, bvh_euler, idx, valid, k, temperature, idx_k, w_k, stream);
 }
 
 }  // extern "C"

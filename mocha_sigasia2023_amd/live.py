@@ -19,15 +19,18 @@ import torch
 
 from . import _C
 from .generator import DIM, NTOK, _dev_f32, _ptr, _stream
-from .multi_character import MultiCharacterBank
+from .multi_character import MultiCharacterBank, soft_params
 from .postprocess import PostProcessor
 
 
 class LiveSession:
     """``streams`` live streams (1..16) on ``bank``'s context.  ``post``: the post-processing constants (default: the demo's);
-    ``bvh``: also produce the BVH writer's channels.  Needs ``Generator.set_pose_norm``."""
+    ``bvh``: also produce the BVH writer's channels.  Needs ``Generator.set_pose_norm``.  ``soft=(k, temperature)``: every stream's decoder
+    reads the softmax(-dist / temperature)-weighted blend of its k nearest entries instead of the nearest one (``mocha_live_step_soft``):
+    no pop when two entries are nearly equidistant; the outputs gain ``idx_k`` (S,k) and ``weight`` (S,k), ``idx`` is column 0."""
 
-    def __init__(self, bank: MultiCharacterBank, cnt_mean, cnt_std, streams: int = 1, post: Optional[PostProcessor] = None, bvh: bool = True):
+    def __init__(self, bank: MultiCharacterBank, cnt_mean, cnt_std, streams: int = 1, post: Optional[PostProcessor] = None, bvh: bool = True,
+                 soft=None):
         if not 1 <= int(streams) <= 16:
             raise ValueError("streams must be 1..16")
         self.bank, self.model = bank, bank.model
@@ -37,6 +40,7 @@ class LiveSession:
         self.post = post or PostProcessor(m)
         self.streams = S = int(streams)
         self.bvh = bool(bvh)
+        self.soft = soft_params(soft, "LiveSession")
         self.mean = _dev_f32(cnt_mean, dev, (NTOK, DIM), "cnt_mean")
         self.std = _dev_f32(cnt_std, dev, (NTOK, DIM), "cnt_std")
         J, V = m.V + 1, m.V
@@ -60,6 +64,9 @@ class LiveSession:
             self.out["bvh_pos"], self.out["bvh_euler"] = f64(S, V, 3), f64(S, V, 3)
         self.out["idx"] = torch.full((S,), -1, dtype=torch.int32, device=dev)
         self.out["valid"] = torch.zeros((S,), dtype=torch.int32, device=dev)
+        if self.soft is not None:
+            self.out["idx_k"] = torch.full((S, self.soft[0]), -1, dtype=torch.int32, device=dev)
+            self.out["weight"] = torch.zeros((S, self.soft[0]), dtype=torch.float32, device=dev)
         bank._ensure()
 
     @property
@@ -95,6 +102,13 @@ class LiveSession:
         """The step on what the fixed buffers hold (a producer on the device may have written them in place)."""
         self.bank._ensure()
         o = self.out
+        if self.soft is not None:
+            self.model._ctx.call("mocha_live_step_soft", C.byref(self.post.cfg), _ptr(self.live), self.streams, _ptr(self.rot), _ptr(self.pos),
+                                 _ptr(self.vel), _ptr(self.ang), _ptr(self.rvel), _ptr(self.rang), _ptr(self.speed), _ptr(self.contact),
+                                 _ptr(self.ids), _ptr(self.mean), _ptr(self.std), self.soft[0], self.soft[1], _ptr(o["pos"]), _ptr(o["rot"]),
+                                 _ptr(o["ik_rot"]), _ptr(o["bvh_pos"]) if self.bvh else None, _ptr(o["bvh_euler"]) if self.bvh else None,
+                                 _ptr(o["idx"]), _ptr(o["valid"]), _ptr(o["idx_k"]), _ptr(o["weight"]), _stream())
+            return o
         self.model._ctx.call("mocha_live_step", C.byref(self.post.cfg), _ptr(self.live), self.streams, _ptr(self.rot), _ptr(self.pos), _ptr(self.vel),
                              _ptr(self.ang), _ptr(self.rvel), _ptr(self.rang), _ptr(self.speed), _ptr(self.contact), _ptr(self.ids),
                              _ptr(self.mean), _ptr(self.std), _ptr(o["pos"]), _ptr(o["rot"]), _ptr(o["ik_rot"]),
@@ -154,7 +168,9 @@ class LiveOursSession(LiveSession):
 
     def __init__(self, bank: MultiCharacterBank, cnt_mean, cnt_std, cvae_state_dict, src_cnt_mean, src_cnt_std, cha_encoded_mean,
                  cha_encoded_std, streams: int = 1, post: Optional[PostProcessor] = None, bvh: bool = True, noise: str = "device",
-                 seed: int = 0):
+                 seed: int = 0, soft=None):
+        if soft is not None:
+            raise ValueError("LiveOursSession: soft matching does not apply - the decoder already reads a sampled character feature")
         if noise not in self.NOISE:
             raise ValueError(f"noise must be one of {sorted(self.NOISE)}")
         super().__init__(bank, cnt_mean, cnt_std, streams=streams, post=post, bvh=bvh)

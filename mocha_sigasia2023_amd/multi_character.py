@@ -17,6 +17,22 @@ import torch
 from .generator import DIM, NTOK, Generator, _dev_f32, _ptr, _stream
 
 _BORROW, _BF16, _NO_DEC_CACHE = 1, 2, 4          # mocha_bank_set flags (include/mocha_hip.h)
+SOFT_MAX_K = 8                                   # MOCHA_SOFT_MAX_K
+
+
+def soft_params(soft, who: str):
+    """``soft=(k, temperature)`` checked on the host -> (int k, float temperature), or None for the hard 1-NN."""
+    if soft is None:
+        return None
+    try:
+        k, t = soft
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: soft must be None or a (k, temperature) pair") from None
+    if int(k) != k or not 1 <= int(k) <= SOFT_MAX_K:
+        raise ValueError(f"{who}: soft k must be an integer in 1 .. {SOFT_MAX_K}")
+    if not float(t) > 0.0:
+        raise ValueError(f"{who}: soft temperature must be positive")
+    return int(k), float(t)
 
 
 class MultiCharacterBank:
@@ -86,19 +102,31 @@ class MultiCharacterBank:
             raise ValueError(f"characters: {ids.shape[0]} ids for {n} queries")
         return ids
 
-    def query(self, query_nm, characters):
-        """Exact 1-NN of each query within its character's rows -> (dist (Q,1), idx (Q,1)), idx local to that character's bank."""
+    def query(self, query_nm, characters, k: int = 1):
+        """Exact 1-NN of each query within its character's rows -> (dist (Q,1), idx (Q,1)), idx local to that character's bank.
+        ``k > 1`` (up to 8): the k nearest rows of that character, nearest first, ties to the lower row -> (dist (Q,k), idx (Q,k)); a
+        character with fewer than k rows gives idx -1 / dist +inf in the columns it cannot fill (``mocha_match_topk_segmented``)."""
         self._ensure()
         q = _dev_f32(query_nm, self.model.device, None, "query").reshape(-1, NTOK * DIM)
         Q = q.shape[0]
         ids = self._ids(characters, Q)
+        if int(k) != k or not 1 <= int(k) <= SOFT_MAX_K:
+            raise ValueError(f"query: k must be an integer in 1 .. {SOFT_MAX_K}")
+        if k > 1:
+            k = int(k)
+            idx = torch.empty((Q, k), dtype=torch.int32, device=q.device)
+            dist = torch.empty((Q, k), dtype=torch.float32, device=q.device)
+            self.model._ctx.call("mocha_match_topk_segmented", _ptr(q), Q, _ptr(ids), k, _ptr(idx), _ptr(dist), _stream())
+            return dist, idx
         idx = torch.empty((Q,), dtype=torch.int32, device=q.device)
         dist = torch.empty((Q,), dtype=torch.float32, device=q.device)
         self.model._ctx.call("mocha_match_segmented", _ptr(q), Q, _ptr(ids), _ptr(idx), _ptr(dist), _stream())
         return dist[:, None], idx[:, None]
 
-    def characterize(self, src_X, characters, cnt_mean, cnt_std, return_index: bool = False, raw: bool = False):
-        """``ContextBank.characterize`` with every window matched against its own character: Y (B,T,V,C) [, idx (B,) local rows]."""
+    def characterize(self, src_X, characters, cnt_mean, cnt_std, return_index: bool = False, raw: bool = False, soft=None):
+        """``ContextBank.characterize`` with every window matched against its own character: Y (B,T,V,C) [, idx (B,) local rows].
+        ``soft=(k, temperature)``: the decoder reads the softmax(-dist / temperature)-weighted blend of the window's k nearest entries
+        instead of the nearest one (``mocha_characterize_soft_segmented``); with ``return_index`` -> (Y, idx_k (B,k), weight (B,k))."""
         self._ensure()
         m = self.model
         X = m._xraw(src_X, "src_X_raw") if raw else m._x(src_X, "src_X")
@@ -107,6 +135,14 @@ class MultiCharacterBank:
         mean = _dev_f32(cnt_mean, m.device, (NTOK, DIM), "cnt_mean")
         std = _dev_f32(cnt_std, m.device, (NTOK, DIM), "cnt_std")
         Y = torch.empty((B, m.cfg["nframes"], m.V, m.cfg["mot_in_dim"]), dtype=torch.float32, device=m.device)
+        sp = soft_params(soft, "characterize")
+        if sp is not None:
+            k, t = sp
+            idx_k = torch.empty((B, k), dtype=torch.int32, device=m.device)
+            w_k = torch.empty((B, k), dtype=torch.float32, device=m.device)
+            m._ctx.call("mocha_characterize_soft_segmented", _ptr(X), B, _ptr(ids), k, t, _ptr(mean), _ptr(std), _ptr(Y), _ptr(idx_k), _ptr(w_k),
+                        1 if raw else 0, _stream())
+            return (Y, idx_k, w_k) if return_index else Y
         idx = torch.empty((B,), dtype=torch.int32, device=m.device)
         m._ctx.call("mocha_characterize_segmented", _ptr(X), B, _ptr(ids), _ptr(mean), _ptr(std), _ptr(Y), _ptr(idx), 1 if raw else 0, _stream())
         return (Y, idx) if return_index else Y
@@ -115,9 +151,11 @@ class MultiCharacterBank:
 class MultiStreamCharacterizer:
     """One window of each of ``streams`` streams per step, every stream matched against its own character: the segmented characterize of
     the ``streams`` windows captured once into a HIP graph (``mocha_step_graph_segmented``) and replayed.  The character of each stream
-    may change from step to step: the ids live in a device buffer the graph reads, so a change does not re-capture."""
+    may change from step to step: the ids live in a device buffer the graph reads, so a change does not re-capture.
+    ``soft=(k, temperature)``: the soft characterize (``mocha_step_graph_soft_segmented``); ``step`` then returns
+    (Y, idx_k (streams,k), weight (streams,k))."""
 
-    def __init__(self, bank: MultiCharacterBank, cnt_mean, cnt_std, streams: int, raw: bool = False):
+    def __init__(self, bank: MultiCharacterBank, cnt_mean, cnt_std, streams: int, raw: bool = False, soft=None):
         if not 1 <= streams <= 16:
             raise ValueError("streams must be 1..16")
         self.bank, self.model = bank, bank.model
@@ -132,6 +170,10 @@ class MultiStreamCharacterizer:
         self.y = torch.empty(shape, dtype=torch.float32, device=m.device)
         self.idx = torch.zeros((self.streams,), dtype=torch.int32, device=m.device)
         self.ids = torch.zeros((self.streams,), dtype=torch.int32, device=m.device)
+        self.soft = soft_params(soft, "MultiStreamCharacterizer")
+        if self.soft is not None:
+            self.idx_k = torch.full((self.streams, self.soft[0]), -1, dtype=torch.int32, device=m.device)
+            self.weight = torch.zeros((self.streams, self.soft[0]), dtype=torch.float32, device=m.device)
         bank._ensure()
 
     @property
@@ -152,6 +194,11 @@ class MultiStreamCharacterizer:
         if windows is not None:
             self.x.copy_(windows.reshape(self.x.shape), non_blocking=True)
         self.bank._ensure()
+        if self.soft is not None:
+            self.model._ctx.call("mocha_step_graph_soft_segmented", _ptr(self.x), self.streams, _ptr(self.ids), self.soft[0], self.soft[1],
+                                 _ptr(self.mean), _ptr(self.std), _ptr(self.y), _ptr(self.idx_k), _ptr(self.weight), 1 if self.raw else 0,
+                                 _stream())
+            return self.y, self.idx_k, self.weight
         self.model._ctx.call("mocha_step_graph_segmented", _ptr(self.x), self.streams, _ptr(self.ids), _ptr(self.mean), _ptr(self.std),
                              _ptr(self.y), _ptr(self.idx), 1 if self.raw else 0, _stream())
         return self.y, self.idx

@@ -107,6 +107,45 @@ def ours(a, dev, model, mb, mean, std, clip, per, J):
     return res
 
 
+def soft(a, dev, model, mb, mean, std, clip, per, J):
+    """--soft K: the hard live step and the soft live step (K neighbours, temperature 2), alternating in one process."""
+    from mocha_sigasia2023_amd import LiveSession
+    res = {"bank": "8 characters x 2048 rows, fp32, segmented", "layout": "mocha (24 joints)", "soft": [a.soft, 2.0],
+           "timing": "HIP events around single graph replays; (a) live step, (b) soft live step, alternating", "streams": {}}
+    for S in (1, 8):
+        ids = torch.tensor([(k * 3) % 8 for k in range(S)], dtype=torch.int32)
+        hard, sft = LiveSession(mb, mean, std, streams=S), LiveSession(mb, mean, std, streams=S, soft=(a.soft, 2.0))
+        frame = [0]
+
+        def push():
+            f = frame[0] % 644; frame[0] += 1
+            for sess in (hard, sft):
+                sess.rot.copy_(clip[0][f]); sess.pos.copy_(clip[1][f]); sess.vel.copy_(clip[2][f]); sess.ang.copy_(clip[3][f])
+                sess.rvel.copy_(per[0][f]); sess.rang.copy_(per[1][f]); sess.speed.copy_(per[2][f]); sess.contact.copy_(per[3][f])
+        for sess in (hard, sft):
+            sess.characters.copy_(ids)
+        for _ in range(max(a.warmup, 70)):
+            push(); hard.replay(); sft.replay()
+        torch.cuda.synchronize()
+        assert bool((sft.out["valid"] == 1).all()) and bool((sft.out["idx_k"] >= 0).all())
+        ta, tb = [], []
+        for _ in range(a.reps):
+            push(); torch.cuda.synchronize()
+            ta.append(event_ms(hard.replay, 1)[0]); tb.append(event_ms(sft.replay, 1)[0])
+        e = {"a_live_step": pct(np.asarray(ta)), "b_live_step_soft": pct(np.asarray(tb))}
+        e["b_minus_a_p50_ms"] = e["b_live_step_soft"]["p50_ms"] - e["a_live_step"]["p50_ms"]
+        n = 100                                         # the soft step's kernels, one launch at a time (eager while profiling)
+        model.profile_start()
+        for _ in range(n):
+            sft.replay()
+        prof = model.profile_stop()
+        e["soft_sites_us"] = {k: 1e3 * v["ms"] / n for k, v in prof["sites"].items() if k.split("|")[0] in ("match.soft", "dec.in_cha", "dec.style")}
+        assert bool(torch.isfinite(sft.out["pos"]).all())
+        res["streams"][str(S)] = e
+        del hard, sft
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=1000)
@@ -114,7 +153,10 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08", "live_step.json"))
     ap.add_argument("--baseline-only", action="store_true")
     ap.add_argument("--ours", action="store_true", help="the CVAE branch: live step / live step with the branch / the route without the live step")
+    ap.add_argument("--soft", type=int, default=0, metavar="K", help="soft matching: live step / soft live step with K neighbours, temperature 2")
     a = ap.parse_args()
+    if a.soft and a.out == ap.get_default("out"):
+        a.out = os.path.join(ROOT, "profiles", "r10", "live_soft_step.json")
     if a.ours and a.out == ap.get_default("out"):
         a.out = os.path.join(ROOT, "profiles", "r09", "live_ours_step.json")
     if not torch.cuda.is_available():
@@ -136,6 +178,8 @@ def main():
     per = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (rvel, rang, np.linalg.norm(hipvel, axis=-1).mean(-1).astype(np.float32), contact)]
     res = {"bank": "8 characters x 2048 rows, fp32, segmented", "layout": "mocha (24 joints)", "timing": "HIP events around single graph replays, live and baseline alternating",
            "streams": {}}
+    if a.soft:
+        return write_out(a, soft(a, dev, model, mb, mean, std, clip, per, J))
     if a.ours:
         return write_out(a, ours(a, dev, model, mb, mean, std, clip, per, J))
     for S in (1, 8):

@@ -5,7 +5,10 @@
     rows(segment) x 90*256 x bytes per value) and the fraction of 8 TB/s, for
       - 8 windows on 8 characters of 2 048 rows each (fp32 and bf16 banks),
       - 8 windows on one 2 048-row character, next to mocha_match_stream<f32> on the same rows,
-      - 1 window on a 16 384-row single segment, next to mocha_match_stream<f32> on the same rows (option scan16 = 0).
+      - 1 window on a 16 384-row single segment, next to mocha_match_stream<f32> on the same rows (option scan16 = 0),
+    and, from the same trace, the soft matcher on the first case (k = 4): its all-keys scan (mocha_match_seg_keys, the same bytes as the
+    hard scan plus 8 B written per row and query) and its selection (mocha_seg_topk_blend: one read of the keys and k bank rows per query;
+    this tool asks for indices and distances only, so no blend is written).
 (b) p50 / p99 of the 8-stream captured step (MultiStreamCharacterizer, 8 characters of 2 048 rows) next to what exists without it:
     8 contexts, each with its own current bank and StreamingCharacterizer, stepped one after another.
 
@@ -38,6 +41,10 @@ CASES = [
     ("  same rows, mocha_match_stream<f32> (8 queries)", "mocha_match_stream<8, false>", 2048 * D * 4),
     ("1 window x 16384-row segment, fp32", "mocha_match_seg_scan<false>", 16384 * D * 4),
     ("  same rows, mocha_match_stream<f32> (1 query, scan16 = 0)", "mocha_match_stream<1, false>", 16384 * D * 4),
+    ("soft k = 4: all-keys scan, 8 x 8 x 2048, fp32", "mocha_match_seg_keys<false>", 8 * 2048 * (D * 4 + 8)),
+    ("  its selection (keys + 4 bank rows per query)", "mocha_seg_topk_blend<false>", 8 * (2048 * 8 + 4 * D * 4)),
+    ("soft k = 4: all-keys scan, 8 x 8 x 2048, bf16", "mocha_match_seg_keys<true>", 8 * 2048 * (D * 2 + 8)),
+    ("  its selection (keys + 4 bank rows per query)", "mocha_seg_topk_blend<true>", 8 * (2048 * 8 + 4 * D * 2)),
 ]
 
 
@@ -59,6 +66,8 @@ def scan_cases():
         mb = MultiCharacterBank(model, banks, bf16=bf16, dec_cache=False)
         for _ in range(REPS):
             mb.query(q, list(range(8)))
+        for _ in range(REPS):
+            mb.query(q, list(range(8)), k=4)
     torch.cuda.synchronize()
     mb = MultiCharacterBank(model, banks, dec_cache=False)
     for _ in range(REPS):
