@@ -569,6 +569,12 @@ int mocha_column_stats(mocha_ctx* ctx, const float* x, int64_t N, float* mean, f
  * than five decades below their window's largest magnitude keep fewer digits than fp32 would.  Launches without a bound (the raw-pose
  * embedding, calls of up to four windows) stay on the bf16 planes; the attention and the matcher always do.  The current bank's per-entry
  * bounds are taken at the next mocha_bank_set.
+ * "walk" (default 1; changes results: no): the order in which the row-walking kernels of the batch path (plane GEMM, full-batch
+ * attention, instance norm / AdaIN, the embedding's and to_mot's pointwise kernels, the matcher's centring, row norms and plane image)
+ * touch their row blocks.  0 = every launch walks upwards; 1 = the tensor-producing steps of a call alternate - a consumer starts at the
+ * rows its producer wrote last, the ones most likely still in the 256 MiB last-level cache; 2 = every eligible launch walks downwards
+ * (tests).  Same tiles, same arithmetic per tile: bit-identical.  The direction is a function of the call's launch sequence alone (the
+ * count starts over at every entry point and chunk), so a captured step bakes in what an eager call does.
  * Every option that changes which kernels a step launches bumps mocha_generation(ctx). */
 int mocha_set_option(mocha_ctx* ctx, const char* name, int value);
 

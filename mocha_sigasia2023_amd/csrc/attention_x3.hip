@@ -52,8 +52,9 @@ __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(PF2 ? 2 : 3
     const int id = blockIdx.x;                           // XCD-aware order as in attention.hip: the heads of a window share an XCD
     const int slot = id >> 3;
     const int head = slot % p.heads;
-    const int b = (slot / p.heads) * 8 + (id & 7);
+    int b = (slot / p.heads) * 8 + (id & 7);
     if (b >= p.B) return;                                // whole workgroup: EXEC stays all ones for the transposed reads below
+    if (!PF2 && p.reverse) b = p.B - 1 - b;              // AttnParams::reverse (full batches): the mirrored window, its heads still on one XCD
     const int nq = p.nq, nk = p.nk;
 
     const float* qg = p.q + (size_t)b * nq * p.ldq + head * DH;

@@ -65,9 +65,10 @@ __device__ __forceinline__ float x3_gelu(float x) { return mocha_gelu(x); }
 // W [N][K] fp32 -> packed planes.  One workgroup per (n tile, k step) block: thread = (row, k half) reads 32 bytes and writes one
 // 16-byte piece per plane, so every wave writes 512-byte runs of the 12 KB block (the image is written once per weight, but once per
 // call for the matcher's transient bank).  wsub (K values, may be null) is subtracted from every row first (centred bank).
-__global__ __launch_bounds__(256) void mocha_pack_x3(const float* __restrict__ W, const float* __restrict__ wsub, int N, int K, unsigned short* __restrict__ out) {
+__global__ __launch_bounds__(256) void mocha_pack_x3(const float* __restrict__ W, const float* __restrict__ wsub, int N, int K, unsigned short* __restrict__ out, int reverse) {
     const int ksteps = K / XK;
-    const int nt = blockIdx.x / ksteps, ks = blockIdx.x - nt * ksteps;
+    const int bx = reverse ? gridDim.x - 1 - blockIdx.x : blockIdx.x;          // reverse: the blocks, and with them the rows, from the last to the first
+    const int nt = bx / ksteps, ks = bx - nt * ksteps;
     const int r = threadIdx.x >> 1, h = threadIdx.x & 1;
     const int n = nt * XN + r;
     const int k = ks * XK + 8 * h;
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(256) void mocha_pack_x3(const float* __restrict__ W
     }
     u32x2 a[3], b[3];
     plane_split4(lo, a); plane_split4(hi, b);
-    unsigned short* blk = out + (size_t)blockIdx.x * XW_BLOCK;
+    unsigned short* blk = out + (size_t)bx * XW_BLOCK;
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
         const u32x4 v = {a[q][0], a[q][1], b[q][0], b[q][1]};
@@ -92,11 +93,11 @@ __global__ __launch_bounds__(256) void mocha_pack_x3(const float* __restrict__ W
 
 size_t gemm_x3_packed_elems(int N, int K) { return (size_t)((N + XN - 1) / XN) * (K / XK) * XW_BLOCK; }
 
-hipError_t launch_pack_x3(const float* W, int N, int K, unsigned short* out, hipStream_t s, const float* wsub) {
+hipError_t launch_pack_x3(const float* W, int N, int K, unsigned short* out, hipStream_t s, const float* wsub, int reverse) {
     if (K % XK != 0) return hipErrorInvalidValue;
     const long long blocks = (long long)((N + XN - 1) / XN) * (K / XK);
     if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(mocha_pack_x3, dim3((unsigned)blocks), dim3(256), 0, s, W, wsub, N, K, out);
+    hipLaunchKernelGGL(mocha_pack_x3, dim3((unsigned)blocks), dim3(256), 0, s, W, wsub, N, K, out, reverse);
     return hipGetLastError();
 }
 
@@ -131,6 +132,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         nt = bid - mt * n_tiles;
     }
     if (mt >= m_tiles) return;
+    if (p.reverse) mt = m_tiles - 1 - mt;         // GemmParams::reverse: the same workgroup slot, the mirrored row block
     const int m0 = mt * TILE_M, n0 = nt * TILE_N;
     // K split over gridDim.z (the matcher's 23 040-long contraction): this workgroup takes steps s0 .. s0 + nsteps - 1 and writes raw
     // partial sums to slab blockIdx.z; the host guarantees at least two steps per slab
@@ -492,6 +494,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
             nt = t - mt * n_tiles;
         }
         T.valid = mt < m_tiles;
+        if (p.reverse) mt = m_tiles - 1 - mt;     // GemmParams::reverse: walk step t takes the mirrored row block, so does the successor the last two steps prefetch (padded m-tiles: negative, not valid)
         T.m0 = (T.valid ? mt : 0) * TILE_M; T.n0 = nt * TILE_N;
 #pragma unroll
         for (int i = 0; i < TM; ++i) {

@@ -51,6 +51,9 @@ struct GemmParams {
     const float* a_amax = nullptr;
     float* c_amax = nullptr;
     int rows_per_win = 0;
+    // gemm_x3.hip (one-shot and persistent instances, ksplit = 1): the m-tiles are walked from the last row block to the first - the same
+    // tiles, the same code per tile, the n-tiles of an m-tile on the same XCD; nothing but the order in which the rows are touched changes
+    int reverse = 0;
 };
 hipError_t launch_gemm(const GemmParams& p, hipStream_t s);
 bool gemm_is_narrow(const GemmParams& p);
@@ -63,7 +66,7 @@ hipError_t gemm_init();           // one-time function attributes (dynamic LDS s
 hipError_t gemm_x3_init();
 bool gemm_x3_supports(const GemmParams& p);
 size_t gemm_x3_packed_elems(int N, int K);
-hipError_t launch_pack_x3(const float* W, int N, int K, unsigned short* out, hipStream_t s, const float* wsub = nullptr);   // wsub: K values subtracted from every row
+hipError_t launch_pack_x3(const float* W, int N, int K, unsigned short* out, hipStream_t s, const float* wsub = nullptr, int reverse = 0);   // wsub: K values subtracted from every row
 hipError_t launch_gemm_x3(const GemmParams& p, hipStream_t s);
 // the same engine with the activations resident in registers (gemm_x3r.hip, round 6): K = 256, N a multiple of 128 (>= 256), plain rows, bias / activation epilogue;
 // bit-identical to launch_gemm_x3.  grid: workgroups (one per CU; 0 = 256)
@@ -95,6 +98,8 @@ struct AttnParams {
     // launch_attention_x3 only: window b's keys / values are rows [kv_idx[b] * nk, +nk) of k / v (index clamped to [0, kv_rows)) - the decoder
     // reading IN(cha) and cha of the matched bank entries in place (test_fullframework.py:465), no gathered copy
     const int32_t* kv_idx = nullptr; long long kv_rows = 0;
+    // launch_attention_x3, full-batch instances only: the windows are walked from the last to the first (GemmParams::reverse)
+    int reverse = 0;
 };
 hipError_t launch_attention(const AttnParams& p, hipStream_t s);
 // the same on the bf16 matrix pipe with exact three-plane operands (attention_x3.hip): nq, nk <= 96, dh = 128 / 256
@@ -123,15 +128,15 @@ hipError_t launch_embed_front(const float* X, const float* W1, const float* b1, 
                               float* out, int nframes, int V, int Cin, const float* xmean, const float* xstd, int raw_root,
                               hipStream_t s, bool planes = false, int max_wgs = 512);
 hipError_t launch_embed_sums(const float* X, const float* W1, const float* b1, const float* AP, float* u, int nwin, int V, int Cin,
-                             const float* xmean, const float* xstd, int raw_root, hipStream_t s, int max_wgs = 512);      // max_wgs: option "embed_front_max_wgs" (per context)
+                             const float* xmean, const float* xstd, int raw_root, hipStream_t s, int max_wgs = 512, int reverse = 0);      // reverse: row blocks from the last to the first (GemmParams::reverse), here and below; max_wgs: option "embed_front_max_wgs" (per context)
 // rows (b,t,p) x 256 -> LeakyReLU -> body-part adjacency (2 hops) -> rows (b,t,w) x (k*256+c)
-hipError_t launch_body_front(const float* x, const float* A_b /*2*6*6*/, float* out, int rows6 /*B*15*/, hipStream_t s);
+hipError_t launch_body_front(const float* x, const float* A_b /*2*6*6*/, float* out, int rows6 /*B*15*/, hipStream_t s, int reverse = 0);
 // g rows (b,t',p) x (k*64+c) -> y2c rows (b,t',w) x 64 : sum_k sum_p AU[k][p][w] g[...]
-hipError_t launch_joint_expand(const float* g, const float* AU /*3*6*V*/, float* out, int nframes15, int V, hipStream_t s);
+hipError_t launch_joint_expand(const float* g, const float* AU /*3*6*V*/, float* out, int nframes15, int V, hipStream_t s, int reverse = 0);
 // z rows x 64 -> LeakyReLU -> 1x1 conv 64->Cout + bias -> Y rows x Cout   [model.py:77-79]
 // ymean/ystd ((V+1)*Cout, root row first) non-null: Y is de-normalised in the epilogue
 hipError_t launch_final_proj(const float* z, const float* W6, const float* b6, float* Y, int rows, int Cout, int V,
-                             const float* ymean, const float* ystd, hipStream_t s, int phased = 0);
+                             const float* ymean, const float* ystd, hipStream_t s, int phased = 0, int reverse = 0);
 // per (b, channel) instance norm over n tokens (net/transformer.py:13-20).
 //   out = (x-mean)/(std+eps); mean_out (B,256) optional; zn = (out - gm)/gs optional
 // optional extras of the instance norm: zc = zn - centre (the matcher's centred queries, bit-identical to mocha_sub_rows on zn);
@@ -150,6 +155,7 @@ struct InormExtra {
     unsigned short* kvimg = nullptr;
     int split_max = 1 << 30;             // windows up to which a window's channels go over four workgroups (per context: option "inorm_split_max")
     double* mean64 = nullptr;            // (B, 256) token mean summed in float64: the input of the float64 style MLP (launch_linear_f64)
+    int reverse = 0;                     // windows from the last to the first (GemmParams::reverse)
 };
 hipError_t launch_instnorm(const float* x, float* out, float* mean_out, const float* gm, const float* gs, float* zn,
                            int B, int n, hipStream_t s, const InormExtra* ex = nullptr);
@@ -158,7 +164,7 @@ hipError_t launch_instnorm(const float* x, float* out, float* mean_out, const fl
 // closed != 0: qin from the first statistics in closed form (no cancellation against beta; pointwise.hip)
 // gb_idx non-null: window b reads its gamma / beta at gb + clamp(gb_idx[b], gb_rows) * gb_stride (the bank's cached style constants)
 hipError_t launch_adain(const float* x, const float* gb, int gb_stride /*floats between windows*/, float* xad, float* qin, int B, int n, hipStream_t s,
-                        int closed = 1, const int32_t* gb_idx = nullptr, long long gb_rows = 0, int split_max = 1 << 30);
+                        int closed = 1, const int32_t* gb_idx = nullptr, long long gb_rows = 0, int split_max = 1 << 30, int reverse = 0);
 // Y = act(X W^T + bias) in float64, L independent column blocks (pointwise.hip: the decoder's style MLP)
 hipError_t launch_linear_f64(const double* X, int ldx, int xcol, const double* W, const double* bias, double* y64, float* y32, int ldy,
                              int M, int N, int K, int L, int act, hipStream_t s);
@@ -232,7 +238,7 @@ size_t column_mean_scratch_doubles(int cols);
 hipError_t launch_column_mean(const float* x, int64_t N, int cols, float* mean, double* scratch, hipStream_t s);
 hipError_t launch_column_stats(const float* x, int64_t N, int cols, float* mean, float* sd, hipStream_t s);
 // bank row squared norms
-hipError_t launch_rownorm2(const float* x, const float* sub /*or null*/, float* out, int64_t rows, int cols, hipStream_t s);
+hipError_t launch_rownorm2(const float* x, const float* sub /*or null*/, float* out, int64_t rows, int cols, hipStream_t s, int reverse = 0);
 hipError_t launch_sub_rows(const float* x, const float* sub, float* out, int64_t rows, int cols, hipStream_t s);
 // many-query matcher (match_mfma.hip): centred bf16 queries, one-plane bf16 coarse scores S[z][q][n] (K split z), and the
 // select kernel: per query, EVERY row whose coarse score ||b-c||^2 - 2 S lies within margin_rel * (2||q-c||^2 + ||b-c||^2 +
@@ -245,7 +251,7 @@ hipError_t launch_center_bf16(const float* x, const float* centre, void* out, in
 // row by row: planes[0] = bf16(x - centre) and, with nplanes = 2, planes[1] = bf16(x - centre - planes[0]) (stacked: plane 1 starts rows * cols
 // elements after plane 0), or out32 = x - centre in fp32; qstat[row] = QSTAT_PARTS pairs whose sums are {||x - centre||^2, ||x - centre - planes||^2 (0 for fp32)} (all of it in part 0).  One
 // workgroup per row, fixed summation order.  Exactly one of planes / out32 is non-null.
-hipError_t launch_center_rows(const float* x, const float* centre, void* planes, int nplanes, float* out32, float* qstat, int64_t rows, int cols, hipStream_t s);
+hipError_t launch_center_rows(const float* x, const float* centre, void* planes, int nplanes, float* out32, float* qstat, int64_t rows, int cols, hipStream_t s, int reverse = 0);
 // planes = 2: qc16 holds two stacked bf16 planes of the queries (plane 1 starts Q * D elements after plane 0), S = (a0 + a1) b^T
 // tiled: the bank as launch_tile_bf16 wrote it (match_tiled_elems(N, D) bf16), or null to read the row-major bank16
 // nt_bank != 0: the bank's LDS-DMA loads carry the non-temporal hint

@@ -206,6 +206,11 @@ struct mocha_ctx {
     int inorm_split_max = 1 << 30, embed_max_wgs = 512, gemm_persistent = 768, gemm_persistent_max_n = 512; bool embed_sums = true;
     int gemm_x3r_min_n = 0;            // plane GEMM with the activations resident in registers (gemm_x3r.hip) for K = 256 launches at least this wide (0 = never); option "gemm_x3r_min_n"
     int gemm_tile64_below = 0;         // plane GEMM: 64 x 64 tiles for mid-size 128-multiple launches with fewer 64 x 128 tiles than this (measured: no gain; gemm_x3.hip)
+    // Walk direction of the row-walking kernels of the batch path (option "walk"): 0 every launch walks its row blocks
+    // upwards, 1 (default) the tensor-producing steps of a call alternate, so that a consumer meets its producer's newest rows first, 2 every
+    // eligible launch walks downwards (tests).  walk_ord: eligible steps issued so far in this call (reset by every entry point and chunk):
+    // a launch's direction is a pure function of the call's launch sequence, so a captured graph bakes in what an eager call does.
+    int walk = 1, walk_ord = 0;
     bool pair_overlap = true;          // characterize_pair: the transient bank's decoder constants on the internal stream, beside the matching
     bool adain_closed = true;          // mocha_adain: qin from the first statistics in closed form (pointwise.hip); 0 = the literal two-pass order
     bool style_f64 = true;             // the style MLP in float64 (mocha_linear_f64); 0 = the fp32 GEMM engines
@@ -498,6 +503,21 @@ int prof_begin(mocha_ctx* c, hipStream_t s, const char* kernel, const char* site
         if ((c)->prof_on) HIPCHK((c), hipEventRecord((c)->prof.back().e1, (s)));                             \
     } while (0)
 
+// Direction of the next eligible step on stream s (mocha_ctx::walk): 1 = its row blocks from the last to the first.  Launches on the
+// internal stream walk upwards and do not count.  same_step: a second launch that produces the same tensor as the one before it
+// (emb.front_sums' two clips, mot.tcn_joint's column halves) takes that launch's direction.
+int walk_peek(const mocha_ctx* c, hipStream_t s, bool same_step = false) {
+    if (c->walk == 0 || (c->aux && s == c->aux)) return 0;
+    if (c->walk == 2) return 1;
+    return (same_step ? c->walk_ord - 1 : c->walk_ord) & 1;
+}
+int walk_next(mocha_ctx* c, hipStream_t s, bool same_step = false) {
+    const int r = walk_peek(c, s, same_step);
+    if (!same_step && !(c->aux && s == c->aux)) c->walk_ord++;
+    return r;
+}
+InormExtra IEXW(mocha_ctx* c, hipStream_t s) { InormExtra e = IEX(c); e.reverse = walk_next(c, s); return e; }     // IEX for a launch that is this call's next step
+
 const char* gemm_kernel_name(const GemmParams& p) {
     if (gemm_is_skinny16(p)) return "mocha_gemm_skinny16";
     if (gemm_is_skinny(p)) return "mocha_gemm_skinny";
@@ -600,7 +620,7 @@ int amax_measure(mocha_ctx* c, hipStream_t s, const float* x, int nwin, long lon
     return 0;
 }
 
-int gemm(mocha_ctx* c, hipStream_t s, const char* site, const GemmParams& p0) {
+int gemm(mocha_ctx* c, hipStream_t s, const char* site, const GemmParams& p0, bool same_step = false) {
     GemmParams p = p0; p.tile64_below = c->gemm_tile64_below; p.persistent = c->gemm_persistent; p.persistent_max_n = c->gemm_persistent_max_n;
     if (p.rows_per_win <= 0) p.rows_per_win = 90;      // rows of a launch per window: 90 tokens unless the site says otherwise (to_mot's joint rows)
     if (c->gemm_h2 && p.a_amax && gemm_h2_supports(p)) {
@@ -630,6 +650,7 @@ int gemm(mocha_ctx* c, hipStream_t s, const char* site, const GemmParams& p0) {
                 LAUNCH(c, s, "mocha_gemm_x3r", site, flops, bytes, launch_gemm_x3r(q, s));
                 return 0;
             }
+            q.reverse = walk_next(c, s, same_step);
             LAUNCH(c, s, "mocha_gemm_x3", site, flops, bytes, launch_gemm_x3(q, s));
             return 0;
         }
@@ -644,11 +665,16 @@ const char* attn_kernel_name(const mocha_ctx* c, int DH, long long pairs = 1 << 
     return x3 ? (DH == 128 ? "mocha_attention_x3<128>" : "mocha_attention_x3<256>")
               : (DH == 64 ? "mocha_attention_f32<64>" : DH == 128 ? "mocha_attention_f32<128>" : "mocha_attention_f32<256>");
 }
-hipError_t attention(const mocha_ctx* c, const AttnParams& a0, hipStream_t s) {
+hipError_t attention(mocha_ctx* c, const AttnParams& a0, hipStream_t s) {
     AttnParams a = a0; a.split_max = c->attn_split_max;
-    return (c->attn_x3 && (a.dh == 128 || a.dh == 256) && a.nq <= 96 && a.nk <= 96) ? launch_attention_x3(a, s) : launch_attention(a, s);
+    if (!(c->attn_x3 && (a.dh == 128 || a.dh == 256) && a.nq <= 96 && a.nk <= 96)) return launch_attention(a, s);
+    // the full-batch instance (more (window, head) pairs than CUs, not the twelve-wave variant) takes the walk direction
+    const long long pairs = (long long)a.B * a.heads;
+    if (pairs > 256 && !(a.dh == 256 && pairs <= a.split_max)) a.reverse = walk_next(c, s);
+    return launch_attention_x3(a, s);
 }
 #define GEMM(c, s, site, p) do { int rc__ = gemm((c), (s), (site), (p)); if (rc__) return rc__; } while (0)
+#define GEMM_SAME(c, s, site, p) do { int rc__ = gemm((c), (s), (site), (p), true); if (rc__) return rc__; } while (0)      // same step as the launch before
 
 GemmParams plain(const float* A, int lda, const float* Wt, float* C, int ldc, int M, int N, int K) {
     GemmParams p;
@@ -680,17 +706,19 @@ int run_embed(mocha_ctx* c, const float* X, int b, float* tokens, bool add_pos, 
     float* x5_amax = nullptr;
     if (c->fold_joint && c->gemm_x3 && c->embed_sums) {
         // conv1 + lrelu + adjacency + joint->part pool, and the 4-frame sums of the five taps, in one kernel: the frame rows stay in LDS
-        LAUNCH(c, s, "mocha_embed_sums_x3", "emb.front_sums", b * 60.0 * V * 64 * (2.0 * 15 + 2.0 * 18) + b * 90.0 * 960 * 4,
-               b * 4.0 * (60.0 * V * 15 + 90.0 * 960),
-               launch_embed_sums(X, DW(c, "emb.W1"), DW(c, "emb.b1"), DW(c, "AP"), WS(c, "u"), b, V, c->cfg.C_in,
-                                 raw ? c->pose_norm.p : nullptr, raw ? c->pose_norm.p + nn : nullptr, raw ? 1 : 0, s, c->embed_max_wgs));
-        if (X2 && b2 > 0) {
-            LAUNCH(c, s, "mocha_embed_sums_x3", "emb.front_sums", b2 * 60.0 * V * 64 * (2.0 * 15 + 2.0 * 18) + b2 * 90.0 * 960 * 4,
-                   b2 * 4.0 * (60.0 * V * 15 + 90.0 * 960),
-                   launch_embed_sums(X2, DW(c, "emb.W1"), DW(c, "emb.b1"), DW(c, "AP"), WS(c, "u") + (size_t)b * 90 * 960, b2, V, c->cfg.C_in,
-                                     raw ? c->pose_norm.p : nullptr, raw ? c->pose_norm.p + nn : nullptr, raw ? 1 : 0, s, c->embed_max_wgs));
-            b += b2;
+        // the two clips' launches produce one tensor: one step of the walk; downwards, the second clip (the upper rows) is issued first
+        const int rev = walk_next(c, s);
+        const bool two = X2 && b2 > 0;
+        for (int k = 0; k < (two ? 2 : 1); ++k) {
+            const bool second = two && (k == 1) != (rev != 0);
+            const float* Xk = second ? X2 : X;
+            const int bk = second ? b2 : b;
+            LAUNCH(c, s, "mocha_embed_sums_x3", "emb.front_sums", bk * 60.0 * V * 64 * (2.0 * 15 + 2.0 * 18) + bk * 90.0 * 960 * 4,
+                   bk * 4.0 * (60.0 * V * 15 + 90.0 * 960),
+                   launch_embed_sums(Xk, DW(c, "emb.W1"), DW(c, "emb.b1"), DW(c, "AP"), WS(c, "u") + (second ? (size_t)b * 90 * 960 : 0), bk, V, c->cfg.C_in,
+                                     raw ? c->pose_norm.p : nullptr, raw ? c->pose_norm.p + nn : nullptr, raw ? 1 : 0, s, c->embed_max_wgs, rev));
         }
+        if (two) b += b2;
         GemmParams gf = plain(WS(c, "u"), 960, DW(c, "emb.Wc"), WS(c, "x5"), 256, b * 90, 256, 960);
         gf.rowbias = DW(c, "emb.rbc"); gf.rb_mod = 6;
         gf.a_amax = amax_use(c, u_amax); gf.c_amax = x5_amax = amax_slot(c);
@@ -731,7 +759,7 @@ int run_embed(mocha_ctx* c, const float* X, int b, float* tokens, bool add_pos, 
     }
     }
     // body block                                                               model.py:48,137-162
-    LAUNCH(c, s, "mocha_body_front", "emb.body_front", b * 90.0 * 512 * 12, b * 90.0 * (256 + 512) * 4, launch_body_front(WS(c, "x5"), DW(c, "A_b"), WS(c, "xA"), b * 15, s));
+    LAUNCH(c, s, "mocha_body_front", "emb.body_front", b * 90.0 * 512 * 12, b * 90.0 * (256 + 512) * 4, launch_body_front(WS(c, "x5"), DW(c, "A_b"), WS(c, "xA"), b * 15, s, walk_next(c, s)));
     GemmParams g3 = plain(WS(c, "xA"), 512, DW(c, "emb.Wgb"), WS(c, "t1"), 256, b * 90, 256, 512);
     g3.rowbias = DW(c, "emb.rbb"); g3.rb_mod = 6;
     g3.a_amax = amax_use(c, x5_amax); g3.c_amax = amax_slot(c);        // body_front: LeakyReLU + a column-normalised mix of x5
@@ -846,7 +874,7 @@ int build_dec_consts(mocha_ctx* c, const float* enc, int64_t N, float* kin, floa
     const int L = c->cfg.dec_depth;
     for (int64_t r0 = 0; r0 < N; r0 += cap) {
         const int rows = (int)std::min<int64_t>(cap, N - r0);
-        InormExtra ex = IEX(c); ex.mean64 = mean64;
+        InormExtra ex = IEXW(c, s); ex.mean64 = mean64;
         LAUNCH(c, s, "mocha_instnorm", "bank.in_cha", 0.0, rows * 90.0 * 256 * 4 * 2,
                launch_instnorm(enc + (size_t)r0 * D, kin + (size_t)r0 * D, nullptr, nullptr, nullptr, nullptr, rows, 90, s, &ex));
         int rc = run_style_f64(c, mean64, hidden, gb + (size_t)r0 * 512 * L, rows, s);
@@ -897,7 +925,7 @@ int run_decoder(mocha_ctx* c, const float* src, const float* cha, int b, float* 
     float* x_amax = nullptr;
     SET(c).amax_dec_of = nullptr;
     if (!cached) {
-        InormExtra ex = IEX(c);
+        InormExtra ex = IEXW(c, s);
         if (gather_table) { ex.table = gather_table; ex.row_idx = gather_idx; ex.table_rows = gather_rows; ex.copy_out = use_kv ? nullptr : WS(c, "sel"); }
         if (use_kv) ex.kvimg = reinterpret_cast<unsigned short*>(WS(c, "kvimg"));
         if (c->style_f64) ex.mean64 = reinterpret_cast<double*>(WS(c, "smean64"));
@@ -917,7 +945,7 @@ int run_decoder(mocha_ctx* c, const float* src, const float* cha, int b, float* 
         const std::string p = "dec" + std::to_string(l);
         LAUNCH(c, s, "mocha_adain", "dec.adain", 0.0, b * 90.0 * 256 * 4 * 3,
                launch_adain(x, gbp + (size_t)l * 512, 512 * L, WS(c, "xad"), WS(c, "qin"), b, 90, s, c->adain_closed ? 1 : 0,
-                            cached ? gather_idx : nullptr, gather_rows, c->inorm_split_max));
+                            cached ? gather_idx : nullptr, gather_rows, c->inorm_split_max, walk_next(c, s)));
         if (c->fold_decoder && DH == 256) {
             // S_h = IN(x) (Wq_h^T Wk_h) IN(cha)^T and out = sum_h (P_h cha) (Wv_h^T Wo_h^T): with dim_head == dim the key and
             // value projections fold into the query and output weights (exact algebra, net/transformer.py:62-76), so the
@@ -972,7 +1000,7 @@ int run_to_mot(mocha_ctx* c, const float* tokens, int b, float* Y, hipStream_t s
         if (tokens == SET(c).amax_dec_of && amax_use(c, SET(c).amax_dec)) t_amax = SET(c).amax_dec;
         else { int rc = amax_measure(c, s, tokens, b, 90ll * 256, &t_amax); if (rc) return rc; }
     }
-    LAUNCH(c, s, "mocha_body_front", "mot.body_front", b * 90.0 * 512 * 12, b * 90.0 * (256 + 512) * 4, launch_body_front(tokens, DW(c, "A_b"), WS(c, "xA"), b * 15, s));
+    LAUNCH(c, s, "mocha_body_front", "mot.body_front", b * 90.0 * 512 * 12, b * 90.0 * (256 + 512) * 4, launch_body_front(tokens, DW(c, "A_b"), WS(c, "xA"), b * 15, s, walk_next(c, s)));
     GemmParams g1 = plain(WS(c, "xA"), 512, DW(c, "mot.Wgb"), WS(c, "t1"), 256, M, 256, 512);
     g1.rowbias = DW(c, "mot.rbb"); g1.rb_mod = 6;
     g1.a_amax = amax_use(c, t_amax); g1.c_amax = amax_slot(c);
@@ -987,7 +1015,7 @@ int run_to_mot(mocha_ctx* c, const float* tokens, int b, float* Y, hipStream_t s
     g3.a_lrelu = 1; g3.bias = DW(c, "mot.bg2");
     g3.a_amax = amax_use(c, g2.c_amax); g3.c_amax = amax_slot(c);
     GEMM(c, s, "mot.gcn_joint", g3);
-    LAUNCH(c, s, "mocha_joint_expand", "mot.joint_expand", b * 15.0 * V * 64 * 36, b * 15.0 * (6 * 192 + V * 64) * 4, launch_joint_expand(WS(c, "g"), DW(c, "AU"), WS(c, "y2c"), b * 15, V, s));
+    LAUNCH(c, s, "mocha_joint_expand", "mot.joint_expand", b * 15.0 * V * 64 * 36, b * 15.0 * (6 * 192 + V * 64) * 4, launch_joint_expand(WS(c, "g"), DW(c, "AU"), WS(c, "y2c"), b * 15, V, s, walk_next(c, s)));
     // temporal conv k=5 over the x4-upsampled frames, read through the gather (t >> 2)
     if (c->fold_upsample) {
         // rows (window, source frame s, joint), columns (phase, channel): z[(b, s, v)][phase*64 + c] is the conv's output at frame 4 s + phase
@@ -998,9 +1026,11 @@ int run_to_mot(mocha_ctx* c, const float* tokens, int b, float* Y, hipStream_t s
         if (b >= c->upsample_split_min) {
             // large batches: two launches of two taps each instead of one with a third of its weight blocks zero
             GemmParams ga = g4; ga.W = DW(c, "mot.Wt2a"); ga.N = 128; ga.K = 128; ga.ntaps = 2;
-            GEMM(c, s, "mot.tcn_joint", ga);
             GemmParams gb = ga; gb.W = DW(c, "mot.Wt2b"); gb.C = WS(c, "z") + 128; gb.pad = -2; gb.bias = DW(c, "mot.bt2p") + 128;
-            GEMM(c, s, "mot.tcn_joint", gb);
+            // the column halves produce one tensor: one step of the walk, issued in the opposite order when it runs downwards
+            const bool rev = walk_peek(c, s) != 0;
+            GEMM(c, s, "mot.tcn_joint", rev ? gb : ga);
+            GEMM_SAME(c, s, "mot.tcn_joint", rev ? ga : gb);
         } else
         GEMM(c, s, "mot.tcn_joint", g4);
     } else {
@@ -1010,7 +1040,7 @@ int run_to_mot(mocha_ctx* c, const float* tokens, int b, float* Y, hipStream_t s
     GEMM(c, s, "mot.tcn_joint", g4);
     }
     LAUNCH(c, s, "mocha_final_proj", "mot.final_proj", b * 60.0 * V * 64 * 15 * 2, b * 60.0 * V * (64 + 15) * 4, launch_final_proj(WS(c, "z"), DW(c, "mot.W6"), DW(c, "mot.b6"), Y, b * 60 * V, c->cfg.C_in, V,
-                             denorm ? c->pose_norm.p + 2 * nn : nullptr, denorm ? c->pose_norm.p + 3 * nn : nullptr, s, c->fold_upsample ? 1 : 0));
+                             denorm ? c->pose_norm.p + 2 * nn : nullptr, denorm ? c->pose_norm.p + 3 * nn : nullptr, s, c->fold_upsample ? 1 : 0, walk_next(c, s)));
     return 0;
 }
 
@@ -1023,7 +1053,7 @@ int for_chunks(mocha_ctx* c, int B, hipStream_t s, F&& fn) {
     const bool dual = c->dual_stream && B >= c->dual_min && c->dual_ready && !c->sets[1].ws.empty();
     if (!dual) {
         c->cur = c->lane;
-        for (int b0 = 0; b0 < B; b0 += c->chunk) { int rc = fn(b0, std::min(c->chunk, B - b0), s); if (rc) return rc; }
+        for (int b0 = 0; b0 < B; b0 += c->chunk) { c->walk_ord = 0; int rc = fn(b0, std::min(c->chunk, B - b0), s); if (rc) return rc; }      // (the walk order starts over with every chunk)
         return 0;
     }
     HIPCHK(c, hipEventRecord(c->ev_fork, s));
@@ -1031,7 +1061,7 @@ int for_chunks(mocha_ctx* c, int B, hipStream_t s, F&& fn) {
     const int h = (B + 1) / 2;
     int rc = 0;
     c->cur = 0;
-    for (int b0 = 0; b0 < h && !rc; b0 += c->chunk) rc = fn(b0, std::min(c->chunk, h - b0), s);
+    for (int b0 = 0; b0 < h && !rc; b0 += c->chunk) { c->walk_ord = 0; rc = fn(b0, std::min(c->chunk, h - b0), s); }
     c->cur = 1;
     for (int b0 = h; b0 < B && !rc; b0 += c->chunk) rc = fn(b0, std::min(c->chunk, B - b0), c->aux);
     c->cur = 0;
@@ -1043,8 +1073,9 @@ int for_chunks(mocha_ctx* c, int B, hipStream_t s, F&& fn) {
     return 0;
 }
 
-int ready(mocha_ctx* c, int B) {
+int ready(mocha_ctx* c, int B, bool entry = true) {
     if (!c) return MOCHA_ERR_ARG;
+    if (entry) c->walk_ord = 0;                      // an entry point: the walk order starts over (mocha_ctx::walk)
     if (!c->finalized) return fail(c, MOCHA_ERR_STATE, "weights not finalised: call mocha_finalize_weights first");
     if (B < 0) return fail(c, MOCHA_ERR_ARG, "negative batch");
     HIPCHK(c, hipSetDevice(c->device));
@@ -1126,9 +1157,9 @@ int do_match(mocha_ctx* c, Bank& b, const float* qnm, int Q, int32_t* idx, float
     const float* qc_pre = (qc_pre_any && qc_pre_bf16 == (b.is_bf16 && Q > 8) && (!sel2 || qstat_pre)) ? static_cast<const float*>(qc_pre_any) : nullptr;
     if (need_qc && !qc_pre) {
         if (sel2 && b.is_bf16)
-            LAUNCH(c, s, "mocha_center_rows", "match.center", 0.0, 8.0 * Q * D, launch_center_rows(qnm, b.center.p, st.match_qc.p, c->match_planes, nullptr, st.match_qstat.p, Q, D, s));
+            LAUNCH(c, s, "mocha_center_rows", "match.center", 0.0, 8.0 * Q * D, launch_center_rows(qnm, b.center.p, st.match_qc.p, c->match_planes, nullptr, st.match_qstat.p, Q, D, s, walk_next(c, s)));
         else if (sel2)
-            LAUNCH(c, s, "mocha_center_rows", "match.center", 0.0, 8.0 * Q * D, launch_center_rows(qnm, b.center.p, nullptr, 0, st.match_qc.p, st.match_qstat.p, Q, D, s));
+            LAUNCH(c, s, "mocha_center_rows", "match.center", 0.0, 8.0 * Q * D, launch_center_rows(qnm, b.center.p, nullptr, 0, st.match_qc.p, st.match_qstat.p, Q, D, s, walk_next(c, s)));
         else if (b.is_bf16 && Q > 8)
             LAUNCH(c, s, "mocha_center_bf16", "match.center", 0.0, 6.0 * Q * D, launch_center_bf16(qnm, b.center.p, st.match_qc.p, Q, D, s));
         else
@@ -1684,7 +1715,7 @@ int mocha_encode(mocha_ctx* c, const float* X, int B, float* encoded, float* cnt
         if (r) return r;
         if ((r = run_encoder(c, WS(c, "x5"), b, encoded + b0 * ts, s))) return r;
         if (cnt || zn) {
-            const InormExtra iex0 = IEX(c);
+            const InormExtra iex0 = IEXW(c, s);
             LAUNCH(c, s, "mocha_instnorm", "mvn", 0.0, b * 90.0 * 256 * 4 * (1 + (cnt ? 1 : 0) + (zn ? 1 : 0)),
                    launch_instnorm(encoded + b0 * ts, cnt ? cnt + b0 * ts : nullptr, nullptr, zn ? cnt_mean : nullptr, zn ? cnt_std : nullptr,
                                    zn ? cnt_nm + b0 * ts : nullptr, b, 90, s, &iex0));
@@ -1708,7 +1739,7 @@ int mocha_style_constants(mocha_ctx* c, const float* cha_enc, int B, float* gb, 
     NEED_PTRS(c, B, "mocha_style_constants", cha_enc, gb);
     const size_t T = 90 * 256, G = (size_t)512 * c->cfg.dec_depth;
     return for_chunks(c, B, (hipStream_t)stream, [&](int b0, int b, hipStream_t s) -> int {
-        InormExtra ex = IEX(c);
+        InormExtra ex = IEXW(c, s);
         if (c->style_f64) ex.mean64 = reinterpret_cast<double*>(WS(c, "smean64"));
         LAUNCH(c, s, "mocha_instnorm", "dec.in_cha", 0.0, b * 90.0 * 256 * 4 * 2,
                launch_instnorm(cha_enc + b0 * T, WS(c, "kin"), WS(c, "smean"), nullptr, nullptr, nullptr, b, 90, s, &ex));
@@ -1765,7 +1796,7 @@ static int bank_own_rows(mocha_ctx* c, Bank& b, int64_t N) {
 // derived image and cache.  b = c->pair, the transient bank of mocha_characterize_pair: centroid, row norms and the plane image only, and
 // captured graphs stay valid (no generation bump, the current bank's segment table, bounds, copies and decoder cache are not its business)
 static int bank_set_impl(mocha_ctx* c, Bank& b, const float* cnt_nm, const float* encoded, int64_t N, int flags, void* stream) {
-    int rc = ready(c, 0); if (rc) return rc;
+    int rc = ready(c, 0, &b != &c->pair); if (rc) return rc;      // (the transient bank is set in the middle of a call: its walk order goes on)
     if (!cnt_nm || !encoded || N < 1 || N > (int64_t)1 << 30) return fail(c, MOCHA_ERR_ARG, "bad bank arguments");
     const bool current = &b == &c->bank;
     hipStream_t s = (hipStream_t)stream;
@@ -1796,7 +1827,7 @@ static int bank_set_impl(mocha_ctx* c, Bank& b, const float* cnt_nm, const float
         LAUNCH(c, s, "mocha_to_bf16", "bank.to_bf16", 0.0, 6.0 * N * D, launch_to_bf16(b.cnt, b.center.p, (int)D, b.bf16.p, (int64_t)N * D, s));
         LAUNCH(c, s, "mocha_rownorm2_bf16", "bank.norms", 2.0 * N * D, 2.0 * N * D, launch_rownorm2_bf16(b.bf16.p, b.norm.p, N, (int)D, s));
     } else {
-        LAUNCH(c, s, "mocha_rownorm2", "bank.norms", 2.0 * N * D, 4.0 * N * D, launch_rownorm2(b.cnt, b.center.p, b.norm.p, N, (int)D, s));
+        LAUNCH(c, s, "mocha_rownorm2", "bank.norms", 2.0 * N * D, 4.0 * N * D, launch_rownorm2(b.cnt, b.center.p, b.norm.p, N, (int)D, s, walk_next(c, s)));
     }
     b.amax_ok = false; b.b16f_valid = false; b.b8_valid = false; b.dec_valid = false;
     // two-plane fp16 engine: the decoder's attention rows are bounded by the matched entries' largest magnitude, taken once here
@@ -1845,7 +1876,7 @@ static int bank_set_impl(mocha_ctx* c, Bank& b, const float* cnt_nm, const float
     b.x3_valid = false;
     if (!b.is_bf16 && c->gemm_x3 && N <= X3_BANK_MAX) {
         if ((rc = reserve(c, b.x3, gemm_x3_packed_elems((int)N, (int)D)))) return rc;
-        LAUNCH(c, s, "mocha_pack_x3", "bank.pack_x3", 0.0, 10.0 * N * D, launch_pack_x3(b.cnt, (int)N, (int)D, b.x3.p, s, b.center.p));
+        LAUNCH(c, s, "mocha_pack_x3", "bank.pack_x3", 0.0, 10.0 * N * D, launch_pack_x3(b.cnt, (int)N, (int)D, b.x3.p, s, b.center.p, walk_next(c, s)));
         b.x3_valid = true;
     }
     return 0;
@@ -1924,7 +1955,7 @@ static int characterize_impl(mocha_ctx* c, const float* src_X, int B, const floa
         if ((r = run_encoder(c, WS(c, "x5"), b, WS(c, "enc_s"), s))) return r;
         if (seg) {
             // cnt and its z-score (and, bf16 bank, the queries centred on the union's centroid), the segmented matcher, the decoder on the global rows
-            InormExtra ex = IEX(c);
+            InormExtra ex = IEXW(c, s);
             if (c->bank.is_bf16) { ex.centre = c->bank.center.p; ex.zc = WS(c, "qc"); }
             LAUNCH(c, s, "mocha_instnorm", "mvn", 0.0, b * 90.0 * 256 * 4 * (c->bank.is_bf16 ? 3.0 : 2.0), launch_instnorm(WS(c, "enc_s"), nullptr, nullptr, cnt_mean, cnt_std, WS(c, "qnm"), b, 90, s, &ex));
             int32_t* gx = SET(c).idx_ws.p;
@@ -1938,7 +1969,7 @@ static int characterize_impl(mocha_ctx* c, const float* src_X, int B, const floa
         const bool q16 = c->bank.is_bf16 && b > 8;
         const bool sel2 = use_select2(c, c->bank, b);                   // the selection's row statistics (and the second bf16 plane) come from this pass too
         if (sel2 && (r = ensure_match_scratch(c, c->cur, b, c->bank, false))) return r;
-        InormExtra ex = IEX(c); ex.centre = c->bank.center.p;
+        InormExtra ex = IEXW(c, s); ex.centre = c->bank.center.p;
         if (q16) ex.zc16 = reinterpret_cast<unsigned short*>(WS(c, "qc")); else ex.zc = WS(c, "qc");
         if (sel2) { ex.qstat = SET(c).match_qstat.p; if (q16 && c->match_planes == 2) ex.plane_stride = (long long)b * 90 * 256; }
         LAUNCH(c, s, "mocha_instnorm", "mvn", 0.0, b * 90.0 * 256 * 4 * (q16 ? (sel2 ? 3.0 : 2.5) : 3.0), launch_instnorm(WS(c, "enc_s"), nullptr, nullptr, cnt_mean, cnt_std, WS(c, "qnm"), b, 90, s, &ex));
@@ -2006,7 +2037,7 @@ static int characterize_pair_impl(mocha_ctx* c, const float* src_X, int B_src, c
     auto join = [&]() -> int { if (forked) { forked = false; HIPCHK(c, hipStreamWaitEvent(s, c->ev_join, 0)); } return 0; };
     // everything between the fork and the join runs in a lambda: an early error return must not skip the join
     rc = [&]() -> int {
-        const InormExtra iex0 = IEX(c);
+        const InormExtra iex0 = IEXW(c, s);
         LAUNCH(c, s, "mocha_instnorm", "mvn", 0.0, B * 90.0 * 256 * 4 * 2,
                launch_instnorm(WS(c, "enc_s"), nullptr, nullptr, cnt_mean, cnt_std, WS(c, "qnm"), B, 90, s, &iex0));
         if (cha_encoded) HIPCHK(c, hipMemcpyAsync(cha_encoded, WS(c, "enc_s"), (size_t)B_cha * T * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -2211,7 +2242,7 @@ static int characterize_soft_impl(mocha_ctx* c, const float* src_X, int B, const
         int r;
         if ((r = run_embed(c, src_X + b0 * xs, b, WS(c, "x5"), true, s, raw))) return r;
         if ((r = run_encoder(c, WS(c, "x5"), b, WS(c, "enc_s"), s))) return r;
-        InormExtra ex = IEX(c);
+        InormExtra ex = IEXW(c, s);
         if (c->bank.is_bf16) { ex.centre = c->bank.center.p; ex.zc = WS(c, "qc"); }
         LAUNCH(c, s, "mocha_instnorm", "mvn", 0.0, b * 90.0 * 256 * 4 * (c->bank.is_bf16 ? 3.0 : 2.0), launch_instnorm(WS(c, "enc_s"), nullptr, nullptr, cnt_mean, cnt_std, WS(c, "qnm"), b, 90, s, &ex));
         if ((r = seg_topk(c, WS(c, c->bank.is_bf16 ? "qc" : "qnm"), b, seg + b0, k, temperature, idx0 ? idx0 + b0 : nullptr,
@@ -2509,7 +2540,7 @@ int mocha_encode_raw(mocha_ctx* c, const float* X_raw, int B, float* encoded, fl
         if ((r = run_embed(c, X_raw + b0 * xs, b, WS(c, "x5"), true, s, true))) return r;
         if ((r = run_encoder(c, WS(c, "x5"), b, encoded + b0 * ts, s))) return r;
         if (cnt || zn) {
-            const InormExtra iex0 = IEX(c);
+            const InormExtra iex0 = IEXW(c, s);
             LAUNCH(c, s, "mocha_instnorm", "mvn", 0.0, b * 90.0 * 256 * 4 * (1 + (cnt ? 1 : 0) + (zn ? 1 : 0)),
                    launch_instnorm(encoded + b0 * ts, cnt ? cnt + b0 * ts : nullptr, nullptr, zn ? cnt_mean : nullptr, zn ? cnt_std : nullptr,
                                    zn ? cnt_nm + b0 * ts : nullptr, b, 90, s, &iex0));
@@ -3213,6 +3244,7 @@ int mocha_set_option(mocha_ctx* c, const char* name, int value) {
     if (n == "embed_front_max_wgs") { c->embed_max_wgs = value; c->generation++; return 0; }
     if (n == "inorm_split_max") { c->inorm_split_max = value < 0 ? 0 : value; c->generation++; return 0; }
     if (n == "pair_overlap") { c->pair_overlap = value != 0; c->generation++; return 0; }
+    if (n == "walk") { if (value < 0 || value > 2) return fail(c, MOCHA_ERR_ARG, "walk must be 0, 1 or 2"); c->walk = value; c->generation++; return 0; }
     if (n == "adain_closed_form") { c->adain_closed = value != 0; c->generation++; return 0; }
     if (n == "style_f64") { c->style_f64 = value != 0; c->bank.dec_valid = false; c->generation++; return 0; }     // cached bank constants: rebuilt at the next mocha_bank_set
     if (n == "bank_dec_cache") { c->bank_dec_cache = value != 0; if (!value) c->bank.dec_valid = false; c->generation++; return 0; }     // takes effect at the next mocha_bank_set

@@ -288,7 +288,7 @@ __global__ __launch_bounds__(256) void mocha_embed_front_x3(const float* __restr
 __global__ __launch_bounds__(256) void mocha_embed_sums_x3(const float* __restrict__ X, const float* __restrict__ W1,
                                                            const float* __restrict__ b1, const float* __restrict__ AP,
                                                            float* __restrict__ u, int nwin, int V, int Cin,
-                                                           const float* __restrict__ xmean, const float* __restrict__ xstd, int raw_root) {
+                                                           const float* __restrict__ xmean, const float* __restrict__ xstd, int raw_root, int reverse) {
     __shared__ __attribute__((aligned(16))) float xs_all[4][32 * 20];
     __shared__ __attribute__((aligned(16))) float ring[12][18 * 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -301,7 +301,8 @@ __global__ __launch_bounds__(256) void mocha_embed_sums_x3(const float* __restri
     __builtin_amdgcn_wave_barrier();
 
     const long long T = (long long)nwin * 15;
-    const int tp_begin = (int)(T * blockIdx.x / gridDim.x), tp_end = (int)(T * (blockIdx.x + 1) / gridDim.x);
+    const long long bx = reverse ? gridDim.x - 1 - blockIdx.x : blockIdx.x;      // reverse: the ranges from the last window's to the first's
+    const int tp_begin = (int)(T * bx / gridDim.x), tp_end = (int)(T * (bx + 1) / gridDim.x);
     if (tp_begin >= tp_end) return;
     float xr[8];
     auto fetch = [&](int w, int a, int s) __attribute__((always_inline)) {
@@ -385,12 +386,12 @@ hipError_t launch_embed_front(const float* X, const float* W1, const float* b1, 
 }
 
 hipError_t launch_embed_sums(const float* X, const float* W1, const float* b1, const float* AP, float* u, int nwin, int V, int Cin,
-                             const float* xmean, const float* xstd, int raw_root, hipStream_t s, int max_wgs) {
+                             const float* xmean, const float* xstd, int raw_root, hipStream_t s, int max_wgs, int reverse) {
     if (nwin <= 0) return hipSuccess;
     if (V > 32 || Cin > 16 || V * Cin > 512) return hipErrorInvalidValue;
     const long long T = (long long)nwin * 15;
     const int cap = max_wgs > 0 ? max_wgs : 512;
-    hipLaunchKernelGGL(mocha_embed_sums_x3, dim3((unsigned)(T < cap ? T : cap)), dim3(256), 0, s, X, W1, b1, AP, u, nwin, V, Cin, xmean, xstd, raw_root);
+    hipLaunchKernelGGL(mocha_embed_sums_x3, dim3((unsigned)(T < cap ? T : cap)), dim3(256), 0, s, X, W1, b1, AP, u, nwin, V, Cin, xmean, xstd, raw_root, reverse);
     return hipGetLastError();
 }
 
@@ -404,8 +405,8 @@ hipError_t launch_embed_sums(const float* X, const float* W1, const float* b1, c
 // tools/experiments/README.md, "two streams").  The coefficients come from scalar loads, so no LDS and no barrier either.
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) MOCHA_NO_PACKED_F32
-void mocha_body_front(const float* __restrict__ x, const float* __restrict__ Ab, float* __restrict__ out, int frames) {
-    const int gid = blockIdx.x * 256 + threadIdx.x;
+void mocha_body_front(const float* __restrict__ x, const float* __restrict__ Ab, float* __restrict__ out, int frames, int reverse) {
+    const int gid = (reverse ? gridDim.x - 1 - blockIdx.x : blockIdx.x) * 256 + threadIdx.x;      // reverse: the frame blocks from the last to the first
     const int f = gid >> 6, c4 = (gid & 63) * 4;
     if (f >= frames) return;
     f32x4 xv[6];
@@ -426,10 +427,10 @@ void mocha_body_front(const float* __restrict__ x, const float* __restrict__ Ab,
         }
 }
 
-hipError_t launch_body_front(const float* x, const float* A_b, float* out, int rows6, hipStream_t s) {
+hipError_t launch_body_front(const float* x, const float* A_b, float* out, int rows6, hipStream_t s, int reverse) {
     if (rows6 <= 0) return hipSuccess;
     const long long threads = (long long)rows6 * 64;
-    hipLaunchKernelGGL(mocha_body_front, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, x, A_b, out, rows6);
+    hipLaunchKernelGGL(mocha_body_front, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, x, A_b, out, rows6, reverse);
     return hipGetLastError();
 }
 
@@ -445,9 +446,9 @@ hipError_t launch_body_front(const float* x, const float* A_b, float* out, int r
 // the HBM peak.  Same products in the same order per output.  VT = joints at compile time (22, 24) or 0: any V <= 32, a loop over joints.
 template <int VT>
 __global__ __launch_bounds__(256) void mocha_joint_expand(const float* __restrict__ g, const float* __restrict__ AU,
-                                                          float* __restrict__ out, int frames, int V) {
+                                                          float* __restrict__ out, int frames, int V, int reverse) {
     const int c = threadIdx.x & 63;
-    const int f = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int f = (reverse ? gridDim.x - 1 - blockIdx.x : blockIdx.x) * 4 + (threadIdx.x >> 6);
     if (f >= frames) return;
     const float* gf = g + (size_t)f * 6 * 192 + c;
     float gv[3][6];
@@ -481,13 +482,13 @@ __global__ __launch_bounds__(256) void mocha_joint_expand(const float* __restric
     }
 }
 
-hipError_t launch_joint_expand(const float* g, const float* AU, float* out, int nframes15, int V, hipStream_t s) {
+hipError_t launch_joint_expand(const float* g, const float* AU, float* out, int nframes15, int V, hipStream_t s, int reverse) {
     if (nframes15 <= 0) return hipSuccess;
     if (V > 32) return hipErrorInvalidValue;
     const dim3 grid((nframes15 + 3) / 4);
-    if (V == 22) hipLaunchKernelGGL(mocha_joint_expand<22>, grid, dim3(256), 0, s, g, AU, out, nframes15, V);
-    else if (V == 24) hipLaunchKernelGGL(mocha_joint_expand<24>, grid, dim3(256), 0, s, g, AU, out, nframes15, V);
-    else hipLaunchKernelGGL(mocha_joint_expand<0>, grid, dim3(256), 0, s, g, AU, out, nframes15, V);
+    if (V == 22) hipLaunchKernelGGL(mocha_joint_expand<22>, grid, dim3(256), 0, s, g, AU, out, nframes15, V, reverse);
+    else if (V == 24) hipLaunchKernelGGL(mocha_joint_expand<24>, grid, dim3(256), 0, s, g, AU, out, nframes15, V, reverse);
+    else hipLaunchKernelGGL(mocha_joint_expand<0>, grid, dim3(256), 0, s, g, AU, out, nframes15, V, reverse);
     return hipGetLastError();
 }
 
@@ -500,11 +501,11 @@ hipError_t launch_joint_expand(const float* g, const float* AU, float* out, int 
 __global__ __launch_bounds__(256) void mocha_final_proj(const float* __restrict__ z, const float* __restrict__ W6,
                                                         const float* __restrict__ b6, float* __restrict__ Y, int rows,
                                                         int Cout, int V, const float* __restrict__ ymean,
-                                                        const float* __restrict__ ystd, int phased) {
+                                                        const float* __restrict__ ystd, int phased, int reverse) {
     __shared__ float ys[128 * 16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hh = lane >> 5;
-    const int r0 = blockIdx.x * 128;
+    const int r0 = (reverse ? gridDim.x - 1 - blockIdx.x : blockIdx.x) * 128;
     const int row = r0 + wave * 32 + l31;
     // phased (mocha_api.cpp, fold_upsample): z holds rows (window, source frame s, joint) x (phase, channel); output row (window, t, joint)
     // reads the 64 channels of phase t & 3 in row (window, t >> 2, joint)
@@ -547,10 +548,10 @@ __global__ __launch_bounds__(256) void mocha_final_proj(const float* __restrict_
 }
 
 hipError_t launch_final_proj(const float* z, const float* W6, const float* b6, float* Y, int rows, int Cout, int V,
-                             const float* ymean, const float* ystd, hipStream_t s, int phased) {
+                             const float* ymean, const float* ystd, hipStream_t s, int phased, int reverse) {
     if (rows <= 0) return hipSuccess;
     if (Cout > 16) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(mocha_final_proj, dim3((rows + 127) / 128), dim3(256), 0, s, z, W6, b6, Y, rows, Cout, V, ymean, ystd, phased);
+    hipLaunchKernelGGL(mocha_final_proj, dim3((rows + 127) / 128), dim3(256), 0, s, z, W6, b6, Y, rows, Cout, V, ymean, ystd, phased, reverse);
     return hipGetLastError();
 }
 
@@ -602,7 +603,7 @@ __global__ __launch_bounds__(QW * IN_NG) void mocha_instnorm(const float* __rest
                                                              float* __restrict__ mean_out, const float* __restrict__ gm,
                                                              const float* __restrict__ gs, float* __restrict__ zn, int n, InormExtra ex) {
     __shared__ f32x4 red[QW * IN_NG];
-    const int b = blockIdx.x, ql = threadIdx.x % QW, g = threadIdx.x / QW;
+    const int b = ex.reverse ? gridDim.x - 1 - blockIdx.x : blockIdx.x, ql = threadIdx.x % QW, g = threadIdx.x / QW;      // reverse: the windows from the last to the first
     const int q = blockIdx.y * QW + ql;                     // channel quad 0..63
     const int cnt = (n - g + IN_NG - 1) / IN_NG;           // tokens g, g + NG, ...
     const float* xrow = x + (size_t)b * n * 256;
@@ -761,9 +762,9 @@ hipError_t launch_instnorm(const float* x, float* out, float* mean_out, const fl
 template <int QW>
 __global__ __launch_bounds__(QW * IN_NG) void mocha_adain(const float* __restrict__ x, const float* __restrict__ gb, int gb_stride,
                                                           float* __restrict__ xad, float* __restrict__ qin, int n, int closed,
-                                                          const int32_t* __restrict__ gb_idx, long long gb_rows) {
+                                                          const int32_t* __restrict__ gb_idx, long long gb_rows, int reverse) {
     __shared__ f32x4 red[QW * IN_NG];
-    const int b = blockIdx.x, ql = threadIdx.x % QW, g = threadIdx.x / QW;
+    const int b = reverse ? gridDim.x - 1 - blockIdx.x : blockIdx.x, ql = threadIdx.x % QW, g = threadIdx.x / QW;
     const int q = blockIdx.y * QW + ql;
     const int cnt = (n - g + IN_NG - 1) / IN_NG;
     const f32x4* xb = reinterpret_cast<const f32x4*>(x + (size_t)b * n * 256) + q;
@@ -809,11 +810,11 @@ __global__ __launch_bounds__(QW * IN_NG) void mocha_adain(const float* __restric
 }
 
 hipError_t launch_adain(const float* x, const float* gb, int gb_stride, float* xad, float* qin, int B, int n, hipStream_t s, int closed,
-                        const int32_t* gb_idx, long long gb_rows, int split_max) {
+                        const int32_t* gb_idx, long long gb_rows, int split_max, int reverse) {
     if (B <= 0) return hipSuccess;
     if (n > IN_NG * IN_MAXT || n < 2 || gb_stride < 512 || (gb_stride & 3) || (gb_idx && gb_rows < 1)) return hipErrorInvalidValue;
-    if (B <= split_max) hipLaunchKernelGGL(mocha_adain<16>, dim3(B, 4), dim3(16 * IN_NG), 0, s, x, gb, gb_stride, xad, qin, n, closed, gb_idx, gb_rows);
-    else hipLaunchKernelGGL(mocha_adain<64>, dim3(B, 1), dim3(64 * IN_NG), 0, s, x, gb, gb_stride, xad, qin, n, closed, gb_idx, gb_rows);
+    if (B <= split_max) hipLaunchKernelGGL(mocha_adain<16>, dim3(B, 4), dim3(16 * IN_NG), 0, s, x, gb, gb_stride, xad, qin, n, closed, gb_idx, gb_rows, reverse);
+    else hipLaunchKernelGGL(mocha_adain<64>, dim3(B, 1), dim3(64 * IN_NG), 0, s, x, gb, gb_stride, xad, qin, n, closed, gb_idx, gb_rows, reverse);
     return hipGetLastError();
 }
 
@@ -991,9 +992,9 @@ hipError_t launch_window_sums(const float* y, float* u, int rows, int channels, 
 // ---------------------------------------------------------------------------------------
 // out[row] = ||x[row] - sub||^2 (sub may be null)
 __global__ __launch_bounds__(256) void mocha_rownorm2(const float* __restrict__ x, const float* __restrict__ sub, float* __restrict__ out,
-                                                      int cols) {
+                                                      int cols, int reverse) {
     __shared__ float red[4];
-    const size_t row = blockIdx.x;
+    const size_t row = reverse ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
     const f32x4* xr = reinterpret_cast<const f32x4*>(x + row * cols);
     float a = 0.f;
     for (int i = threadIdx.x; i < cols / 4; i += 256) {
@@ -1007,10 +1008,10 @@ __global__ __launch_bounds__(256) void mocha_rownorm2(const float* __restrict__ 
     if (threadIdx.x == 0) out[row] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-hipError_t launch_rownorm2(const float* x, const float* sub, float* out, int64_t rows, int cols, hipStream_t s) {
+hipError_t launch_rownorm2(const float* x, const float* sub, float* out, int64_t rows, int cols, hipStream_t s, int reverse) {
     if (rows <= 0) return hipSuccess;
     if (cols % 4) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(mocha_rownorm2, dim3((unsigned)rows), dim3(256), 0, s, x, sub, out, cols);
+    hipLaunchKernelGGL(mocha_rownorm2, dim3((unsigned)rows), dim3(256), 0, s, x, sub, out, cols, reverse);
     return hipGetLastError();
 }
 
@@ -1034,9 +1035,9 @@ hipError_t launch_sub_rows(const float* x, const float* sub, float* out, int64_t
 // (match_select2.hip): ||x - c||^2 and the squared norm of what the planes leave out.  Thread t takes the 4-element pieces t, t + 512, ...;
 // wave sums, then the eight waves in order: the statistics are reproducible.
 __global__ __launch_bounds__(512) void mocha_center_rows(const float* __restrict__ x, const float* __restrict__ c, unsigned short* __restrict__ planes,
-                                                         float* __restrict__ out32, float* __restrict__ qstat, long long plane_stride, int cols4) {
+                                                         float* __restrict__ out32, float* __restrict__ qstat, long long plane_stride, int cols4, int reverse) {
     __shared__ float red[2][8];
-    const size_t row = blockIdx.x;
+    const size_t row = reverse ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
     const f32x4* xr = reinterpret_cast<const f32x4*>(x) + row * cols4;
     const f32x4* cr = reinterpret_cast<const f32x4*>(c);
     float qn = 0.f, dn = 0.f;
@@ -1069,11 +1070,11 @@ __global__ __launch_bounds__(512) void mocha_center_rows(const float* __restrict
     }
 }
 
-hipError_t launch_center_rows(const float* x, const float* centre, void* planes, int nplanes, float* out32, float* qstat, int64_t rows, int cols, hipStream_t s) {
+hipError_t launch_center_rows(const float* x, const float* centre, void* planes, int nplanes, float* out32, float* qstat, int64_t rows, int cols, hipStream_t s, int reverse) {
     if (rows <= 0) return hipSuccess;
     if (cols % 4 || !qstat || (planes == nullptr) == (out32 == nullptr) || (planes && nplanes != 1 && nplanes != 2)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(mocha_center_rows, dim3((unsigned)rows), dim3(512), 0, s, x, centre, (unsigned short*)planes, out32, qstat,
-                       nplanes == 2 ? (long long)rows * cols : 0ll, cols / 4);
+                       nplanes == 2 ? (long long)rows * cols : 0ll, cols / 4, reverse);
     return hipGetLastError();
 }
 
