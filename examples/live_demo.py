@@ -3,11 +3,15 @@
 mocap frame at a time through ``LiveSession`` - ring push + featurize, segmented characterize, pose heads and one post-processing
 frame per push, one captured graph - and written as two BVH files.
 
-    python examples/live_demo.py [--frames 180] [--out bench_outputs/live_demo] [--ours [--seed 7]]
+    python examples/live_demo.py [--frames 180] [--out bench_outputs/live_demo] [--ours [--seed 7]] [--switch 120 [--inertial 0.1]]
 
 ``--ours`` runs the CVAE ("Ours") branch inside the same graph (``LiveOursSession``): each stream's character feature is seeded with
 its matched bank row on the first pose and sampled from the previous one afterwards, the noise drawn on the device; the files are then
 named ``Ours_stream<s>.bvh`` as the reference names its result ``Ours.bvh``.
+
+``--switch FRAME``: stream 0 names character 1 from that frame on - the new id is device data, the graph is not captured again.
+``--inertial HALFLIFE`` (seconds): the switch does not pop; the jump of the pose heads decays as an offset (``LiveSession(inertial=...)``,
+the reference's per-bone inertializers on the device).  The size of the largest bone-position step at the switch frame is printed.
 
 Weights, norms and motions are synthetic (see demo_pair.py for what to replace with real assets).
 """
@@ -31,7 +35,11 @@ ap.add_argument("--ours", action="store_true", help="the CVAE branch inside the 
 ap.add_argument("--seed", type=int, default=7, help="--ours: seed of the device's noise")
 ap.add_argument("--soft", nargs=2, metavar=("K", "T"), help="soft matching: the decoder reads the softmax(-dist / T) blend of each stream's K nearest "
                 "entries (1..8) instead of the nearest one")
+ap.add_argument("--switch", type=int, default=None, metavar="FRAME", help="stream 0 takes character 1 from that frame on")
+ap.add_argument("--inertial", type=float, default=None, metavar="HALFLIFE", help="inertialize character switches with that half-life in seconds")
 a = ap.parse_args()
+if a.ours and a.inertial is not None:
+    raise SystemExit("--inertial does not apply to --ours: that branch seeds again on a switch and keeps its own chain state")
 if a.ours and a.soft:
     raise SystemExit("--soft does not apply to --ours: its decoder already reads a sampled character feature")
 soft = (int(a.soft[0]), float(a.soft[1])) if a.soft else None
@@ -72,7 +80,7 @@ if a.ours:                                                            # test_ful
     sess = LiveOursSession(bank, cnt_mean, cnt_std, synthetic_cvae_state_dict(99, 1.0), *stats, streams=S, post=PostProcessor(model),
                            noise="device", seed=a.seed)
 else:
-    sess = LiveSession(bank, cnt_mean, cnt_std, streams=S, post=PostProcessor(model), soft=soft)
+    sess = LiveSession(bank, cnt_mean, cnt_std, streams=S, post=PostProcessor(model), soft=soft, inertial=a.inertial)
 sess.push(*[torch.stack([src[s][k][0] for s in range(S)]) for k in range(4)], *[torch.stack([per[s][k][0] for s in range(S)]) for k in range(4)],
           characters=[0, 1])                                          # the first push captures the step
 sess.reset()
@@ -80,7 +88,7 @@ torch.cuda.synchronize(); t0 = time.perf_counter()
 pos, eul = [], []
 for f in range(F):
     o = sess.push(*[torch.stack([src[s][k][f] for s in range(S)]) for k in range(4)],
-                  *[torch.stack([per[s][k][f] for s in range(S)]) for k in range(4)])
+                  *[torch.stack([per[s][k][f] for s in range(S)]) for k in range(4)], characters=[1, 1] if f == a.switch else None)
     if f >= 59:                                                       # both streams started together: both are valid from here on
         pos.append(o["bvh_pos"].clone()); eul.append(o["bvh_euler"].clone())
 torch.cuda.synchronize(); dt = time.perf_counter() - t0
@@ -91,5 +99,9 @@ for s in range(S):
     p = os.path.join(a.out, f"{'Ours' if a.ours else 'soft' if soft else 'live'}_stream{s}.bvh")
     write_bvh(p, names, LAYOUTS["mocha"]["parents"], pos[s], eul[s])
     print(f"  {p}: {os.path.getsize(p)} bytes, {pos.shape[1]} frames")
+if a.switch is not None and 60 <= a.switch < F:
+    step = (pos[0, 1:, 1:] - pos[0, :-1, 1:]).abs().amax(dim=(1, 2))     # per frame, the non-root bones of stream 0
+    print(f"  stream 0 switches character at frame {a.switch}: largest bone-position step there {float(step[a.switch - 60]):.4f}, "
+          f"median over the clip {float(step.median()):.4f}" + (f" (inertialized, half-life {a.inertial} s)" if a.inertial is not None else ""))
 print(f"{F} pushes of {S} streams in {dt * 1e3:.1f} ms ({dt / F * 1e3:.3f} ms per push, host loop included)")
 assert bool(torch.isfinite(pos).all()) and bool(torch.isfinite(eul).all())

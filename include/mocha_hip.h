@@ -424,6 +424,63 @@ int mocha_live_step_soft(mocha_ctx* ctx, const mocha_post_cfg* cfg, void* live, 
                          double* pos, double* rot, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx, int32_t* valid,
                          int32_t* idx_k, float* w_k, void* stream);
 
+/* Inertialized character switches.  A live stream may name another character on any frame; the decoder then reads a row of another
+ * segment and mocha_pose_heads hands the post-processing frame a pose that has nothing to do with the previous one.  The reference holds
+ * the remedy and never calls it: the per-bone inertializers of motion/Inertialization.py:71-91 (springs :10-37).  Here they run on the
+ * pose heads, per stream and per non-root bone j = 0..V-1, on all 13 channels of a head row [pos 3 | quat wxyz 4 | vel 3 | ang 3] (fp32, as
+ * mocha_pose_heads writes it).  The ROOT bone is not inertialized: the frame loop integrates it from its own previous output
+ * (test_fullframework.py:500-503), so it is continuous by construction.
+ *   mocha_inert_cfg        : halflife (seconds) and dt (seconds per frame).  NULL = {0.1, 1/60}.  halflife < 0, dt <= 0 or a non-finite
+ *                            value is MOCHA_ERR_ARG; halflife == 0 is legal (the reference adds 1e-5).
+ *   mocha_inert_state_bytes: bytes of state per stream (private layout, float64).  Host-side, no synchronisation.  The state holds the
+ *                            flags `seen` and `active`, `last_id`, `prev_in` (the stream's previous valid input heads, before offsets)
+ *                            and the offsets off_pos, off_vel, off_ang (3 each) and off_rot (a quaternion).  ALL-ZERO BYTES ARE A RESET
+ *                            STREAM: a reset is a hipMemsetAsync, a snapshot / rollback a device copy, as for mocha_post_state_bytes.
+ *   mocha_inertialize_step : ONE frame of n independent streams, heads_in (n,V,13) -> heads_out (n,V,13), which may be the same buffer;
+ *                            state: n * mocha_inert_state_bytes device bytes; ids / trigger / valid (n) int32 device, each may be NULL
+ *                            (valid NULL: every stream is valid).  Per stream, from device data alone:
+ *                              not valid  - valid[s] == 0 (the stream is warming): its heads are untouched, its state is cleared
+ *                                           (seen = active = 0, offsets at rest).  A stream reset with mocha_live_reset warms for 59
+ *                                           frames, so it needs no reset call of its own.
+ *                              first      - seen == 0: prev_in = in, last_id = id, seen = 1; the output is the input, bit for bit.
+ *                              transition - seen, and ids given with ids[s] != last_id, or trigger given with trigger[s] != 0:
+ *                                           off_pos, off_vel = inertialize_transition_pos(off_pos, off_vel, prev_in.pos, prev_in.vel,
+ *                                           in.pos, in.vel) (:71-74); off_rot, off_ang = inertialize_transition_rot(off_rot, off_ang,
+ *                                           prev_in.rot, prev_in.ang, in.rot, in.ang) (:82-85, with quat.abs: w > 0.0, negated
+ *                                           otherwise); active = 1; then the update below IN THE SAME FRAME (pose_transition followed
+ *                                           by pose_update).  "src" is the stream's previous valid frame, not an extrapolation of it
+ *                                           to the switch frame: the function as the reference wrote it.
+ *                              update     - active: out.pos, out.vel, off_pos, off_vel = inertialize_update_pos(off_pos, off_vel,
+ *                                           in.pos, in.vel, halflife, dt) (:76-80, :18-26, :10-14: fast_negexpf is the rational
+ *                                           function as written, halflife_to_damping uses eps = 1e-5); out.rot, out.ang, off_rot,
+ *                                           off_ang = inertialize_update_rot(...) (:87-91, :28-37; quat.log and quat.exp keep their
+ *                                           eps = 1e-5 branches; out.rot = off_rot (x) in.rot is not renormalised, as in the reference).
+ *                              not active - seen and no transition since the reset: the output is the input bit for bit (the words
+ *                                           are copied, no arithmetic: in + 0.0 would turn -0.0 into +0.0).
+ *                              always, for a valid frame: prev_in = in (the input, not the output), last_id = id.
+ *                            float64 arithmetic on the fp32 inputs, outputs rounded to fp32 once, offsets float64 across frames.
+ *                            n == 0 is a no-op; a NULL required pointer or a bad cfg is MOCHA_ERR_ARG, never a launch.  One launch
+ *                            (mocha_inertialize, one 64-lane workgroup per stream), no allocation, no synchronisation: capture-safe.
+ *   mocha_live_step_inert  : the arguments of mocha_live_step_soft, then `inert` (streams * mocha_inert_state_bytes device bytes, the
+ *                            caller's, zeroed = reset) and icfg.  k == 0 is the hard route of mocha_live_step (idx_k / w_k may be NULL),
+ *                            k >= 1 the soft route.  The step is mocha_live_step's with ONE launch between mocha_pose_heads and the
+ *                            post-processing frame: mocha_inertialize in place on the session's staged heads, ids = the step's
+ *                            effective ids, valid = the step's valid.  A stream that never switches gets the bits of mocha_live_step /
+ *                            _soft; mocha_live_state_bytes and the layout of `live` are unchanged.  Captured into its own HIP graph,
+ *                            keyed as the live step's plus `inert` and the two doubles of icfg: a new id is device data and does not
+ *                            capture again.  While mocha_profile_start is active the step runs eagerly, the launch named
+ *                            mocha_inertialize, site live.inert.  Refusals as mocha_live_step / _soft; a NULL `inert` or a bad icfg is
+ *                            MOCHA_ERR_ARG.  Nothing is launched on a refusal. */
+typedef struct mocha_inert_cfg { double halflife, dt; } mocha_inert_cfg;
+int64_t mocha_inert_state_bytes(const mocha_ctx* ctx);
+int mocha_inertialize_step(mocha_ctx* ctx, const mocha_inert_cfg* cfg, void* state, const float* heads_in, float* heads_out,
+                           const int32_t* ids, const int32_t* trigger, const int32_t* valid, int n, void* stream);
+int mocha_live_step_inert(mocha_ctx* ctx, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos,
+                          const float* Yvel, const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed,
+                          const unsigned char* contact, const int32_t* seg, const float* cnt_mean, const float* cnt_std, int k,
+                          float temperature, double* pos, double* rot, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx,
+                          int32_t* valid, int32_t* idx_k, float* w_k, void* stream, void* inert, const mocha_inert_cfg* icfg);
+
 /* The CVAE ("Ours") branch inside the live step (test_fullframework.py:446-457; a stream's first frame is :290-298): mocha_live_step
  * with the decoder's character feature sampled from the previous one instead of taken from the matched bank row.  The autoregressive
  * state of every stream lives in a second caller-owned device buffer `ours`, every decision of a frame is device data, and the noise can

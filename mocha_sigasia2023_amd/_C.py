@@ -31,6 +31,10 @@ class mocha_ours_cfg(C.Structure):
                 ("noise", C.c_int), ("eps", C.c_void_p), ("seed", C.c_uint64)]
 
 
+class mocha_inert_cfg(C.Structure):
+    _fields_ = [("halflife", C.c_double), ("dt", C.c_double)]
+
+
 _vp, _i, _i64 = C.c_void_p, C.c_int, C.c_int64
 
 # name -> (restype, argtypes); every symbol include/mocha_hip.h declares
@@ -95,6 +99,9 @@ SIGNATURES = {
     "mocha_characterize_soft_segmented": (_i, [_vp, _vp, _i, _vp, _i, C.c_float, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "mocha_step_graph_soft_segmented": (_i, [_vp, _vp, _i, _vp, _i, C.c_float, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "mocha_live_step_soft": (_i, [_vp, _vp, _vp, _i] + [_vp] * 11 + [_i, C.c_float] + [_vp] * 10),
+    "mocha_inert_state_bytes": (_i64, [_vp]),
+    "mocha_inertialize_step": (_i, [_vp] * 8 + [_i, _vp]),
+    "mocha_live_step_inert": (_i, [_vp, _vp, _vp, _i] + [_vp] * 11 + [_i, C.c_float] + [_vp] * 12),
     "mocha_set_rccl_library": (_i, [C.c_char_p]),
     "mocha_comm_unique_id": (_i, [_vp, _vp]),
     "mocha_comm_init": (_i, [_vp, _vp, _i, _i]),

@@ -233,6 +233,13 @@ hipError_t launch_post_clip(const PostParams& p, hipStream_t s);
 // one frame per clip with the clip's state (p.state: POST_STATE_DOUBLES float64 words per clip, all-zero = no frame seen yet) in device
 // memory: p as for launch_post_clip with n_frames = 1, the same kernels
 hipError_t launch_post_step(const PostParams& p, hipStream_t s);
+// Inertialization of the pose heads across a character switch (motion/Inertialization.py:71-91 per non-root bone), ONE frame of n
+// independent streams: heads_in / heads_out (n, V, 13) fp32 (they may alias), state (n, INERT_STATE_DOUBLES) float64 words, all-zero =
+// a reset stream; ids / trigger / valid (n) or null.  One launch, no allocation, no synchronisation.
+static constexpr int INERT_BONE_DOUBLES = 13 + 3 + 3 + 3 + 4;      // prev_in | off_pos | off_vel | off_ang | off_rot
+static constexpr int INERT_STATE_DOUBLES = 2 + MOCHA_MAX_BONES * INERT_BONE_DOUBLES;
+hipError_t launch_inertialize(double* state, const float* heads_in, float* heads_out, const int32_t* ids, const int32_t* trigger,
+                              const int32_t* valid, int n, int V, double halflife, double dt, hipStream_t s);
 // per-column mean and population std over N rows (bank build: cnt_norm)
 size_t column_mean_scratch_doubles(int cols);
 hipError_t launch_column_mean(const float* x, int64_t N, int cols, float* mean, double* scratch, hipStream_t s);

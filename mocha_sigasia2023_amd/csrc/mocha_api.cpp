@@ -282,6 +282,8 @@ struct mocha_ctx {
         int noise = 0; unsigned long long seed = 0;
         // the soft steps only: neighbours, temperature, and the (windows, k) outputs idx_k / w_k
         int soft_k = 0; float soft_t = 0.f; const void* soft[2] = {};
+        // mocha_live_step_inert only: the inertializer's state buffer and its two constants
+        const void* inert = nullptr; double inert_halflife = 0.0, inert_dt = 0.0;
         bool operator==(const StepKey& o) const {
             if (!(x == o.x && mean == o.mean && sd == o.sd && y == o.y && idx == o.idx && seg == o.seg && windows == o.windows && raw == o.raw))
                 return false;
@@ -289,6 +291,7 @@ struct mocha_ctx {
             for (int i = 0; i < 7; ++i) if (ours[i] != o.ours[i]) return false;
             if (noise != o.noise || seed != o.seed) return false;
             if (soft_k != o.soft_k || soft_t != o.soft_t || soft[0] != o.soft[0] || soft[1] != o.soft[1]) return false;
+            if (inert != o.inert || inert_halflife != o.inert_halflife || inert_dt != o.inert_dt) return false;
             const mocha_post_cfg &a = post, &b = o.post;
             for (int i = 0; i < 4; ++i) if (a.contact_bones[i] != b.contact_bones[i]) return false;
             return a.dt == b.dt && a.ik_max_length_buffer == b.ik_max_length_buffer && a.ik_foot_height == b.ik_foot_height &&
@@ -300,7 +303,8 @@ struct mocha_ctx {
         hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr;
         StepKey key; int64_t generation = -1;
     } step[MAX_SETS], seg_step, live_step, ours_step, // seg_step: mocha_step_graph_segmented, live_step: mocha_live_step, ours_step: mocha_live_step_ours (workspace set 0)
-      soft_step, live_soft_step;                      // mocha_step_graph_soft_segmented, mocha_live_step_soft (workspace set 0)
+      soft_step, live_soft_step,                      // mocha_step_graph_soft_segmented, mocha_live_step_soft (workspace set 0)
+      live_inert_step;                                // mocha_live_step_inert, hard or soft (workspace set 0)
     hipStream_t cap_stream = nullptr;                 // capture happens on this internal stream (the caller's may be the null stream)
     ncclComm_t comm = nullptr; int comm_rank = 0, comm_size = 1;      // mocha_comm_init
     DeviceBuffer<long long> bcast_hdr;                                  // device: {entries, bf16?} header of mocha_bank_broadcast
@@ -1397,7 +1401,8 @@ void mocha_destroy(mocha_ctx* c) {
     if (c->aux) (void)hipStreamDestroy(c->aux);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    for (auto* g : {&c->step[0], &c->step[1], &c->step[2], &c->seg_step, &c->live_step, &c->ours_step, &c->soft_step, &c->live_soft_step}) {
+    for (auto* g : {&c->step[0], &c->step[1], &c->step[2], &c->seg_step, &c->live_step, &c->ours_step, &c->soft_step, &c->live_soft_step,
+                    &c->live_inert_step}) {
         if (g->exec) (void)hipGraphExecDestroy(g->exec);
         if (g->graph) (void)hipGraphDestroy(g->graph);
     }
@@ -2929,7 +2934,8 @@ int mocha_live_reset(mocha_ctx* c, void* live, int streams, const int32_t* which
 static int live_step_impl(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos, const float* Yvel,
                           const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed, const unsigned char* contact,
                           const int32_t* seg, const float* cnt_mean, const float* cnt_std, double* pos, double* rot, double* ik_rot, double* bvh_pos,
-                          double* bvh_euler, int32_t* idx, int32_t* valid, int k, float temperature, int32_t* idx_k, float* w_k, void* stream) {
+                          double* bvh_euler, int32_t* idx, int32_t* valid, int k, float temperature, int32_t* idx_k, float* w_k, void* stream,
+                          void* inert = nullptr, const mocha_inert_cfg* icfg = nullptr) {
     if (streams < 1 || streams > 16) return fail(c, MOCHA_ERR_ARG, "live_step: 1 <= streams <= 16");
     if (!live || !Yrot || !Ypos || !Yvel || !Yang || !src_rvel || !src_rang || !src_speed || !contact || !seg || !cnt_mean || !cnt_std || !pos ||
         !rot || !ik_rot || !idx || !valid || (!bvh_pos) != (!bvh_euler))
@@ -2979,6 +2985,10 @@ static int live_step_impl(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, i
         const int r = characterize(idx, idx_k, w_k, cs);
         if (r) return r;
         LAUNCH(c, cs, "mocha_pose_heads", "live.heads", 0.0, streams * (60.0 * 12 + V * 28.0 * 4), launch_pose_heads(ystage, heads, speed, streams, c->cfg.T, V, cs));
+        // mocha_live_step_inert: the staged heads inertialized in place, on the step's effective ids and its valid flags
+        if (inert)
+            LAUNCH(c, cs, "mocha_inertialize", "live.inert", 0.0, (double)streams * (V * 26.0 * 4 + 2.0 * INERT_STATE_DOUBLES * 8),
+                   launch_inertialize(static_cast<double*>(inert), heads, heads, eff, nullptr, valid, streams, V, icfg->halflife, icfg->dt, cs));
         LAUNCH(c, cs, "mocha_post_clip", "live.post", 0.0, (double)streams * (V * 13.0 * 4 + J * 11.0 * 8 + 2.0 * POST_STATE_DOUBLES * 8),
                launch_post_step(p, cs));
         return 0;
@@ -2993,7 +3003,8 @@ static int live_step_impl(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, i
     for (int i = 0; i < 17; ++i) key.live[i] = ptrs[i];
     key.post = *cfg;
     key.soft_k = k; key.soft_t = k > 0 ? temperature : 0.f; key.soft[0] = k > 0 ? idx_k : nullptr; key.soft[1] = k > 0 ? w_k : nullptr;
-    mocha_ctx::StepGraph& g = k > 0 ? c->live_soft_step : c->live_step;
+    if (inert) { key.inert = inert; key.inert_halflife = icfg->halflife; key.inert_dt = icfg->dt; }
+    mocha_ctx::StepGraph& g = inert ? c->live_inert_step : k > 0 ? c->live_soft_step : c->live_step;
     if (!(g.exec && g.key == key && g.generation == c->generation)) {
         // Before a capture: one eager characterize of the staging windows with every id -1 (no bank row is matched, no state of the
         // session moves), so that whatever the kernels of the step make on first use - the plane GEMMs' weight images, for the soft step
@@ -3023,6 +3034,53 @@ int mocha_live_step_soft(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, in
     if (!idx_k || !w_k) return fail(c, MOCHA_ERR_ARG, "live_step_soft: null argument");
     return live_step_impl(c, cfg, live, streams, Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, seg, cnt_mean, cnt_std, pos, rot,
                           ik_rot, bvh_pos, bvh_euler, idx, valid, k, temperature, idx_k, w_k, stream);
+}
+
+// cfg (NULL = half-life 0.1 s at 60 frames per second) checked and copied into `out`
+static int inert_cfg(mocha_ctx* c, const char* who, const mocha_inert_cfg* cfg, mocha_inert_cfg& out) {
+    out = cfg ? *cfg : mocha_inert_cfg{0.1, 1.0 / 60.0};
+    if (!std::isfinite(out.halflife) || !std::isfinite(out.dt) || out.halflife < 0.0 || !(out.dt > 0.0))
+        return fail(c, MOCHA_ERR_ARG, "%s: halflife must be finite and >= 0, dt finite and > 0", who);
+    return 0;
+}
+
+int64_t mocha_inert_state_bytes(const mocha_ctx* c) {
+    if (!c) return MOCHA_ERR_ARG;
+    return (int64_t)INERT_STATE_DOUBLES * (int64_t)sizeof(double);
+}
+
+int mocha_inertialize_step(mocha_ctx* c, const mocha_inert_cfg* cfg, void* state, const float* heads_in, float* heads_out, const int32_t* ids,
+                           const int32_t* trigger, const int32_t* valid, int n, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    mocha_inert_cfg ic;
+    int rc = inert_cfg(c, "inertialize_step", cfg, ic); if (rc) return rc;
+    if (n < 0) return fail(c, MOCHA_ERR_ARG, "inertialize_step: n must not be negative");
+    if (n == 0) return 0;
+    if (!state || !heads_in || !heads_out) return fail(c, MOCHA_ERR_ARG, "inertialize_step: null argument");
+    if (c->cfg.V + 1 > MOCHA_MAX_BONES) return fail(c, MOCHA_ERR_ARG, "inertialize_step: too many bones");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    LAUNCH(c, s, "mocha_inertialize", "post.inert", 0.0, (double)n * (c->cfg.V * 26.0 * 4 + 2.0 * INERT_STATE_DOUBLES * 8),
+           launch_inertialize(static_cast<double*>(state), heads_in, heads_out, ids, trigger, valid, n, c->cfg.V, ic.halflife, ic.dt, s));
+    return 0;
+}
+
+int mocha_live_step_inert(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos, const float* Yvel,
+                          const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed, const unsigned char* contact,
+                          const int32_t* seg, const float* cnt_mean, const float* cnt_std, int k, float temperature, double* pos, double* rot,
+                          double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx, int32_t* valid, int32_t* idx_k, float* w_k, void* stream,
+                          void* inert, const mocha_inert_cfg* icfg) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (k != 0) {
+        int rc = soft_args(c, "live_step_inert", k, temperature); if (rc) return rc;
+        if (!idx_k || !w_k) return fail(c, MOCHA_ERR_ARG, "live_step_inert: null argument");
+    }
+    if (!inert) return fail(c, MOCHA_ERR_ARG, "live_step_inert: null inertializer state");
+    mocha_inert_cfg ic;
+    int rc = inert_cfg(c, "live_step_inert", icfg, ic); if (rc) return rc;
+    return live_step_impl(c, cfg, live, streams, Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, seg, cnt_mean, cnt_std, pos, rot,
+                          ik_rot, bvh_pos, bvh_euler, idx, valid, k, k > 0 ? temperature : 0.f, k > 0 ? idx_k : nullptr, k > 0 ? w_k : nullptr,
+                          stream, inert, &ic);
 }
 
 }  // extern "C"

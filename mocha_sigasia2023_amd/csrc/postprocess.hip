@@ -7,6 +7,8 @@
 //                      integration, position blending, the foot-lock state machine (motion/Inertialization.py:300-377)
 //                      and the two-bone IK (motion/quat.py:295-343), then the root merge + Euler channels the BVH
 //                      writer consumes.  float64, because the reference's state arrays are NumPy float64.
+//  mocha_inertialize   one 64-lane workgroup per stream, between the two above in a live step: the per-bone inertializers of
+//                      motion/Inertialization.py:71-91 on the pose heads, so that a character switch decays instead of popping.
 //
 // Both kernels also serve the resumable form (launch_post_step, live sessions): ONE frame per clip and launch, the per-lane state (root
 // transform, the bone's previous position, the contact record) loaded from and stored to device memory around it.
@@ -412,6 +414,122 @@ hipError_t launch_post_clip(const PostParams& p, hipStream_t s) {
 hipError_t launch_post_step(const PostParams& p, hipStream_t s) {
     if (p.n_frames != 1 || !p.state) return hipErrorInvalidValue;
     return launch_post_clip(p, s);
+}
+
+// ----------------------------------------------------------------------------------------------- inertialized character switches
+// The reference's per-bone inertializers (motion/Inertialization.py:71-91, springs :10-37), which its demo never calls, applied to the
+// pose heads between mocha_pose_heads and the post-processing frame: when a stream names another character, the decoder's pose has
+// nothing to do with the previous one, and the difference is kept as an offset that decays with a critically damped spring.
+//
+// One 64-lane workgroup per stream, lane j owns non-root bone j (V + 1 <= MOCHA_MAX_BONES) and all 13 channels of its head row
+// [pos 3 | quat wxyz 4 | vel 3 | ang 3].  The ROOT bone is not inertialized: the frame loop integrates it from its own previous output
+// (test_fullframework.py:500-503), so it is continuous by construction.
+//
+// State of one stream, INERT_STATE_DOUBLES 8-byte words: [0] flags (int64: bit 0 seen, bit 1 active), [1] last id (int64), then
+// INERT_BONE_DOUBLES planes of MOCHA_MAX_BONES words, word k of bone j at 2 + k * MOCHA_MAX_BONES + j: prev_in (13: the stream's previous
+// valid INPUT heads, before offsets), off_pos, off_vel, off_ang (3 each), off_rot (4).  All-zero bytes are a reset stream: with seen == 0
+// no offset is read, and the first valid frame writes them at rest (off_rot = identity).
+//
+// Per frame and stream, from device data alone:
+//   not valid   valid given and valid[s] == 0 (the stream is warming): heads untouched, seen = active = 0.
+//   first       seen == 0: prev_in = in, last_id = id, offsets at rest, seen = 1; out = in bit for bit.
+//   transition  seen, and ids given with ids[s] != last_id, or trigger given with trigger[s] != 0: inertialize_transition_pos / _rot
+//               (:71-74, :82-85, with quat.abs: w > 0.0 or negated) with src = prev_in and dst = in, then active = 1 and the update below in
+//               the same frame (pose_transition followed by pose_update).  "src" is the stream's previous valid frame, NOT an extrapolation
+//               of it to the switch frame: the function as the reference wrote it.
+//   update      active: inertialize_update_pos / _rot (:76-80, :87-91): the offsets decay (fast_negexpf as the rational function written
+//               there, halflife_to_damping with eps = 1e-5, quat.log / quat.exp with their eps = 1e-5 branches), out = in (+) offset;
+//               out.rot = off_rot * in.rot is not renormalised, as in the reference.
+//   not active  seen, no transition since the reset: out = in bit for bit (the words are copied: in + 0.0 would lose a -0.0).
+//   always, for a valid frame: prev_in = in (the input, not the output), last_id = id.
+// float64 arithmetic on the fp32 inputs, outputs rounded to fp32 once, offsets float64 across frames.
+__device__ inline d3 to_scaled_angle_axis(dq q) {                                              // quat.py:149-152, 160-161
+    const d3 v = {q.x, q.y, q.z};
+    const double l = len(v);
+    const double h = l < 1e-5 ? 1.0 : atan2(l, q.w) / l;
+    return 2.0 * (v * h);
+}
+
+__global__ __launch_bounds__(64) void mocha_inertialize(double* __restrict__ state, const float* heads_in, float* heads_out,
+                                                        const int32_t* __restrict__ ids, const int32_t* __restrict__ trigger,
+                                                        const int32_t* __restrict__ valid, int V, double halflife, double dt) {
+    const int s = blockIdx.x, lane = threadIdx.x;
+    double* S = state + (size_t)s * INERT_STATE_DOUBLES;
+    long long* F = reinterpret_cast<long long*>(S);
+    if (valid && valid[s] == 0) {                               // uniform over the workgroup
+        if (lane == 0) F[0] = 0;
+        return;
+    }
+    const long long flags = F[0], last_id = F[1];
+    const bool seen = (flags & 1) != 0;
+    const long long id = ids ? (long long)ids[s] : (seen ? last_id : 0);
+    const bool trans = seen && ((ids && id != last_id) || (trigger && trigger[s] != 0));
+    const bool active = seen && (trans || (flags & 2) != 0);
+    __syncthreads();                                            // every lane has read the flags before lane 0 rewrites them
+    if (lane == 0) { F[0] = 1 | (active ? 2 : 0); F[1] = id; }
+    if (lane >= V) return;
+    double* B = S + 2 + lane;                                   // word k of this bone: B[k * MOCHA_MAX_BONES]
+    const float* hin = heads_in + ((size_t)s * V + lane) * 13;
+    float* hout = heads_out + ((size_t)s * V + lane) * 13;
+    float h[13];
+#pragma unroll
+    for (int k = 0; k < 13; ++k) h[k] = hin[k];
+    auto W = [&](int k) -> double& { return B[k * MOCHA_MAX_BONES]; };
+    if (!active) {
+        if (!seen) {
+#pragma unroll
+            for (int k = 13; k < INERT_BONE_DOUBLES; ++k) W(k) = k == 22 ? 1.0 : 0.0;         // offsets at rest, off_rot = (1, 0, 0, 0)
+        }
+#pragma unroll
+        for (int k = 0; k < 13; ++k) { W(k) = (double)h[k]; hout[k] = h[k]; }
+        return;
+    }
+    const d3 in_p = {(double)h[0], (double)h[1], (double)h[2]}, in_v = {(double)h[7], (double)h[8], (double)h[9]},
+             in_a = {(double)h[10], (double)h[11], (double)h[12]};
+    const dq in_r = {(double)h[3], (double)h[4], (double)h[5], (double)h[6]};
+    d3 off_p = {W(13), W(14), W(15)}, off_v = {W(16), W(17), W(18)}, off_a = {W(19), W(20), W(21)};
+    dq off_r = {W(22), W(23), W(24), W(25)};
+    if (trans) {
+        const d3 src_p = {W(0), W(1), W(2)}, src_v = {W(7), W(8), W(9)}, src_a = {W(10), W(11), W(12)};
+        const dq src_r = {W(3), W(4), W(5), W(6)};
+        off_p = (src_p + off_p) - in_p;                                                        // Inertialization.py:72-73
+        off_v = (src_v + off_v) - in_v;
+        off_r = qmul(qmul(off_r, src_r), qinv(in_r));                                          // :83
+        if (!(off_r.w > 0.0)) off_r = {-off_r.w, -off_r.x, -off_r.y, -off_r.z};                // quat.py:18-19
+        off_a = (off_a + src_a) - in_a;                                                        // :84
+    }
+    const double y = (4.0 * 0.6931471805599453) / (halflife + 1e-5) / 2.0;                     // :13-14, 19
+    const double ydt = y * dt;
+    const double eydt = 1.0 / (1.0 + ydt + 0.48 * ydt * ydt + 0.235 * ydt * ydt * ydt);        // :10-11
+    {
+        const d3 j1 = off_v + off_p * y;                                                       // :18-26
+        off_p = eydt * (off_p + j1 * dt);
+        off_v = eydt * (off_v - (j1 * y) * dt);
+    }
+    {
+        const d3 j0 = to_scaled_angle_axis(off_r);                                             // :28-37
+        const d3 j1 = off_a + j0 * y;
+        off_r = from_scaled_angle_axis(eydt * (j0 + j1 * dt));
+        off_a = eydt * (off_a - (j1 * y) * dt);
+    }
+    const d3 out_p = in_p + off_p, out_v = in_v + off_v, out_a = off_a + in_a;                 // :78-79, 90
+    const dq out_r = qmul(off_r, in_r);                                                        // :89
+#pragma unroll
+    for (int k = 0; k < 13; ++k) W(k) = (double)h[k];
+    W(13) = off_p.x; W(14) = off_p.y; W(15) = off_p.z; W(16) = off_v.x; W(17) = off_v.y; W(18) = off_v.z;
+    W(19) = off_a.x; W(20) = off_a.y; W(21) = off_a.z; W(22) = off_r.w; W(23) = off_r.x; W(24) = off_r.y; W(25) = off_r.z;
+    hout[0] = (float)out_p.x; hout[1] = (float)out_p.y; hout[2] = (float)out_p.z;
+    hout[3] = (float)out_r.w; hout[4] = (float)out_r.x; hout[5] = (float)out_r.y; hout[6] = (float)out_r.z;
+    hout[7] = (float)out_v.x; hout[8] = (float)out_v.y; hout[9] = (float)out_v.z;
+    hout[10] = (float)out_a.x; hout[11] = (float)out_a.y; hout[12] = (float)out_a.z;
+}
+
+hipError_t launch_inertialize(double* state, const float* heads_in, float* heads_out, const int32_t* ids, const int32_t* trigger,
+                              const int32_t* valid, int n, int V, double halflife, double dt, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (V < 1 || V + 1 > MOCHA_MAX_BONES) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mocha_inertialize, dim3(n), dim3(64), 0, s, state, heads_in, heads_out, ids, trigger, valid, V, halflife, dt);
+    return hipGetLastError();
 }
 
 }  // namespace mocha

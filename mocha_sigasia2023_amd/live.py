@@ -27,10 +27,13 @@ class LiveSession:
     """``streams`` live streams (1..16) on ``bank``'s context.  ``post``: the post-processing constants (default: the demo's);
     ``bvh``: also produce the BVH writer's channels.  Needs ``Generator.set_pose_norm``.  ``soft=(k, temperature)``: every stream's decoder
     reads the softmax(-dist / temperature)-weighted blend of its k nearest entries instead of the nearest one (``mocha_live_step_soft``):
-    no pop when two entries are nearly equidistant; the outputs gain ``idx_k`` (S,k) and ``weight`` (S,k), ``idx`` is column 0."""
+    no pop when two entries are nearly equidistant; the outputs gain ``idx_k`` (S,k) and ``weight`` (S,k), ``idx`` is column 0.
+    ``inertial=halflife`` (seconds): a stream that names another character does not pop - the jump of its pose heads becomes an offset
+    that decays with that half-life (``mocha_live_step_inert``: the reference's inertializers, state and decision on the device, the frame
+    time taken from ``post``); a stream that never switches gets the bits of ``inertial=None``."""
 
     def __init__(self, bank: MultiCharacterBank, cnt_mean, cnt_std, streams: int = 1, post: Optional[PostProcessor] = None, bvh: bool = True,
-                 soft=None):
+                 soft=None, inertial: Optional[float] = None):
         if not 1 <= int(streams) <= 16:
             raise ValueError("streams must be 1..16")
         self.bank, self.model = bank, bank.model
@@ -49,6 +52,15 @@ class LiveSession:
         if nbytes <= 0:
             raise RuntimeError("mocha_live_state_bytes failed")
         self.live = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)          # zeroed = a reset session
+        self.inert = self.icfg = None
+        if inertial is not None:
+            if not (float(inertial) >= 0.0 and float(inertial) != float("inf")):
+                raise ValueError("LiveSession: inertial is a half-life in seconds, finite and >= 0")
+            ibytes = int(m._ctx.lib.mocha_inert_state_bytes(m._ctx.h))
+            if ibytes <= 0:
+                raise RuntimeError("mocha_inert_state_bytes failed")
+            self.inert = torch.zeros((S, ibytes), dtype=torch.uint8, device=dev)   # zeroed = no stream has seen a frame
+            self.icfg = _C.mocha_inert_cfg(float(inertial), float(self.post.cfg.dt))
 
         def f32(*shape):
             return torch.zeros(shape, dtype=torch.float32, device=dev)
@@ -102,6 +114,15 @@ class LiveSession:
         """The step on what the fixed buffers hold (a producer on the device may have written them in place)."""
         self.bank._ensure()
         o = self.out
+        if self.inert is not None:
+            k, t = self.soft if self.soft is not None else (0, 0.0)
+            self.model._ctx.call("mocha_live_step_inert", C.byref(self.post.cfg), _ptr(self.live), self.streams, _ptr(self.rot), _ptr(self.pos),
+                                 _ptr(self.vel), _ptr(self.ang), _ptr(self.rvel), _ptr(self.rang), _ptr(self.speed), _ptr(self.contact),
+                                 _ptr(self.ids), _ptr(self.mean), _ptr(self.std), k, t, _ptr(o["pos"]), _ptr(o["rot"]),
+                                 _ptr(o["ik_rot"]), _ptr(o["bvh_pos"]) if self.bvh else None, _ptr(o["bvh_euler"]) if self.bvh else None,
+                                 _ptr(o["idx"]), _ptr(o["valid"]), _ptr(o.get("idx_k")), _ptr(o.get("weight")), _stream(), _ptr(self.inert),
+                                 C.byref(self.icfg))
+            return o
         if self.soft is not None:
             self.model._ctx.call("mocha_live_step_soft", C.byref(self.post.cfg), _ptr(self.live), self.streams, _ptr(self.rot), _ptr(self.pos),
                                  _ptr(self.vel), _ptr(self.ang), _ptr(self.rvel), _ptr(self.rang), _ptr(self.speed), _ptr(self.contact),
@@ -168,7 +189,9 @@ class LiveOursSession(LiveSession):
 
     def __init__(self, bank: MultiCharacterBank, cnt_mean, cnt_std, cvae_state_dict, src_cnt_mean, src_cnt_std, cha_encoded_mean,
                  cha_encoded_std, streams: int = 1, post: Optional[PostProcessor] = None, bvh: bool = True, noise: str = "device",
-                 seed: int = 0, soft=None):
+                 seed: int = 0, soft=None, inertial=None):
+        if inertial is not None:
+            raise ValueError("LiveOursSession: inertial does not apply - the branch seeds again on a character switch and keeps its own chain state")
         if soft is not None:
             raise ValueError("LiveOursSession: soft matching does not apply - the decoder already reads a sampled character feature")
         if noise not in self.NOISE:

@@ -11,6 +11,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
+from . import _C
 from .generator import Generator, _dev_f32, _ptr, _stream
 
 
@@ -132,6 +133,56 @@ class PostProcessor:
         m._ctx.call("mocha_postprocess_step", C.byref(self.cfg), _ptr(state), _ptr(h), _ptr(sp), _ptr(rv), _ptr(ra), _ptr(ssp), _ptr(ct), nclip,
                     _ptr(out["pos"]), _ptr(out["rot"]), _ptr(out["ik_rot"]),
                     _ptr(out["bvh_pos"]) if bvh else None, _ptr(out["bvh_euler"]) if bvh else None, _stream())
+        return out
+
+
+class Inertializer:
+    """The reference's per-bone inertializers (motion/Inertialization.py:71-91) on the pose heads, on the device
+    (``mocha_inertialize_step``): when a stream names another character, or is told so by ``trigger``, the jump between its previous
+    heads and the new ones becomes an offset that decays with half-life ``halflife`` (seconds; ``dt`` seconds per frame) instead of
+    popping.  The root bone is not part of the heads and is not inertialized: the frame loop integrates it from its own output."""
+
+    def __init__(self, model: Generator, halflife: float = 0.1, dt: float = 1.0 / 60.0):
+        self.model = model
+        self.cfg = _C.mocha_inert_cfg(float(halflife), float(dt))
+
+    def state(self, n: int = 1) -> torch.Tensor:
+        """A zeroed state for ``step``: (n, mocha_inert_state_bytes) uint8 on the device.  All-zero bytes are a reset stream, so
+        ``state.zero_()`` (or zeroing one row) is a reset and ``state.clone()`` / ``state.copy_`` a snapshot / rollback."""
+        ctx = self.model._ctx
+        nbytes = int(ctx.lib.mocha_inert_state_bytes(ctx.h))
+        if nbytes <= 0:
+            raise RuntimeError("mocha_inert_state_bytes failed")
+        return torch.zeros((int(n), nbytes), dtype=torch.uint8, device=self.model.device)
+
+    def step(self, state, heads, ids=None, trigger=None, valid=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """ONE frame of the n streams of ``state``: heads (n,V,13) fp32 as ``pose_heads`` gives them -> the inertialized heads (n,V,13),
+        written to ``out`` (which may be ``heads`` itself).  ids / trigger / valid: (n,) int32, each optional - a stream transitions when
+        its id differs from the one of its previous valid frame or its trigger is non-zero; a stream with valid == 0 is left untouched
+        and its state cleared.  A stream that never transitions gets its input back bit for bit."""
+        m, dev, V = self.model, self.model.device, self.model.V
+        if not (isinstance(state, torch.Tensor) and state.dtype == torch.uint8 and state.dim() == 2 and state.is_contiguous()
+                and state.device == dev):
+            raise ValueError("inertializer step: state must come from Inertializer.state()")
+        n = state.shape[0]
+        h = _dev_f32(torch.as_tensor(heads), dev, (V, 13), "heads")
+        if h.numel() != n * V * 13:
+            raise ValueError(f"inertializer step: heads {tuple(h.shape)} for a state of {n} streams")
+        if out is None:
+            out = torch.empty((n, V, 13), dtype=torch.float32, device=dev)
+        elif not (out.dtype == torch.float32 and out.device == dev and out.is_contiguous() and out.numel() == n * V * 13):
+            raise ValueError("inertializer step: out must be a contiguous float32 (n,V,13) tensor on the model's device")
+
+        def i32(a, name):
+            if a is None:
+                return None
+            t = torch.as_tensor(a).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+            if t.numel() != n:
+                raise ValueError(f"inertializer step: {name} has {t.numel()} entries, expected {n}")
+            return t
+        ids, trigger, valid = i32(ids, "ids"), i32(trigger, "trigger"), i32(valid, "valid")
+        m._ctx.call("mocha_inertialize_step", C.byref(self.cfg), _ptr(state), _ptr(h), _ptr(out), _ptr(ids), _ptr(trigger), _ptr(valid), n,
+                    _stream())
         return out
 
 

@@ -15,6 +15,10 @@ mocha_profile_start / stop, during which the step runs eagerly.
         the CVAE ("Ours") branch: (a) LiveSession.replay, (b) LiveOursSession.replay with device noise, (c) the same frame without the
         live step - featurize + encode + segmented match + OursSession.step + pose heads + PostProcessor.step on a window the caller
         keeps (its upkeep is not timed) - alternating replay by replay in one process, S = 1 and S = 8
+    python tools/live_latency.py --inertial 0.1 [--out profiles/r12/live_inert_step.json]
+        the plain live step and the inertialized one (LiveSession(inertial=H) = mocha_live_step_inert: one more launch, mocha_inertialize,
+        between the pose heads and the post frame), alternating replay by replay in one process, S = 1 and S = 8; stream 0 switches
+        character half-way through the warm-up, so the timed inertialized steps take the kernel's arithmetic path
 """
 import argparse
 import json
@@ -146,6 +150,50 @@ def soft(a, dev, model, mb, mean, std, clip, per, J):
     return res
 
 
+def inertial(a, dev, model, mb, mean, std, clip, per, J):
+    """--inertial H: the plain live step and the inertialized one (half-life H seconds), alternating in one process."""
+    from mocha_sigasia2023_amd import LiveSession
+    res = {"bank": "8 characters x 2048 rows, fp32, segmented", "layout": "mocha (24 joints)", "inertial_halflife_s": a.inertial,
+           "timing": "HIP events around single graph replays; (a) live step, (b) inertialized live step, alternating; every stream of (b) has "
+                     "switched character once and is decaying its offsets", "streams": {}}
+    for S in (1, 8):
+        ids = torch.tensor([(k * 3) % 8 for k in range(S)], dtype=torch.int32)
+        plain, inert = LiveSession(mb, mean, std, streams=S), LiveSession(mb, mean, std, streams=S, inertial=a.inertial)
+        frame = [0]
+
+        def push():
+            f = frame[0] % 644; frame[0] += 1
+            for sess in (plain, inert):
+                sess.rot.copy_(clip[0][f]); sess.pos.copy_(clip[1][f]); sess.vel.copy_(clip[2][f]); sess.ang.copy_(clip[3][f])
+                sess.rvel.copy_(per[0][f]); sess.rang.copy_(per[1][f]); sess.speed.copy_(per[2][f]); sess.contact.copy_(per[3][f])
+        for sess in (plain, inert):
+            sess.characters.copy_((ids + 1) % 8)
+        warm = max(a.warmup, 70)
+        for i in range(warm):
+            if i == 65:                                  # every stream is running: all of them switch, the offsets start to decay
+                for sess in (plain, inert):
+                    sess.characters.copy_(ids)
+            push(); plain.replay(); inert.replay()
+        torch.cuda.synchronize()
+        assert bool((inert.out["valid"] == 1).all()) and torch.equal(inert.out["idx"], plain.out["idx"])
+        ta, tb = [], []
+        for _ in range(a.reps):
+            push(); torch.cuda.synchronize()
+            ta.append(event_ms(plain.replay, 1)[0]); tb.append(event_ms(inert.replay, 1)[0])
+        e = {"a_live_step": pct(np.asarray(ta)), "b_live_step_inert": pct(np.asarray(tb))}
+        e["b_minus_a_p50_ms"] = e["b_live_step_inert"]["p50_ms"] - e["a_live_step"]["p50_ms"]
+        n = 200                                          # the step's own launches, one at a time (eager while profiling)
+        model.profile_start()
+        for _ in range(n):
+            inert.replay()
+        prof = model.profile_stop()
+        e["sites_us"] = {k: 1e3 * v["ms"] / v["launches"] for k, v in prof["sites"].items() if k.split("|")[0] in ADDED + ("live.inert",)}
+        assert bool(torch.isfinite(inert.out["pos"]).all())
+        res["streams"][str(S)] = e
+        del plain, inert
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=1000)
@@ -154,7 +202,10 @@ def main():
     ap.add_argument("--baseline-only", action="store_true")
     ap.add_argument("--ours", action="store_true", help="the CVAE branch: live step / live step with the branch / the route without the live step")
     ap.add_argument("--soft", type=int, default=0, metavar="K", help="soft matching: live step / soft live step with K neighbours, temperature 2")
+    ap.add_argument("--inertial", type=float, default=None, metavar="H", help="inertialized switches: live step / live step with half-life H seconds")
     a = ap.parse_args()
+    if a.inertial is not None and a.out == ap.get_default("out"):
+        a.out = os.path.join(ROOT, "profiles", "r12", "live_inert_step.json")
     if a.soft and a.out == ap.get_default("out"):
         a.out = os.path.join(ROOT, "profiles", "r10", "live_soft_step.json")
     if a.ours and a.out == ap.get_default("out"):
@@ -178,6 +229,8 @@ def main():
     per = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (rvel, rang, np.linalg.norm(hipvel, axis=-1).mean(-1).astype(np.float32), contact)]
     res = {"bank": "8 characters x 2048 rows, fp32, segmented", "layout": "mocha (24 joints)", "timing": "HIP events around single graph replays, live and baseline alternating",
            "streams": {}}
+    if a.inertial is not None:
+        return write_out(a, inertial(a, dev, model, mb, mean, std, clip, per, J))
     if a.soft:
         return write_out(a, soft(a, dev, model, mb, mean, std, clip, per, J))
     if a.ours:
