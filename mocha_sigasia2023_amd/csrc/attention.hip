@@ -211,6 +211,7 @@ __global__ __launch_bounds__(NQW * 64) __attribute__((amdgpu_waves_per_eu(NKT !=
 hipError_t launch_attention(const AttnParams& p, hipStream_t s) {
     if (p.B <= 0) return hipSuccess;
     if (p.nq < 1 || p.nk < 1 || p.nq > 192 || p.nk > 192) return hipErrorInvalidValue;
+    if (p.kv_idx) return hipErrorInvalidValue;           // only launch_attention_x3 gathers keys / values: ignoring the index would be a wrong result
     dim3 grid((unsigned)(((p.B + 7) / 8) * 8 * p.heads));
     const bool small = p.nq <= 96 && p.nk <= 96;
     if (p.dh == 128 && small) hipLaunchKernelGGL((mocha_attention_f32<128, 3, 3>), grid, dim3(192), 0, s, p);

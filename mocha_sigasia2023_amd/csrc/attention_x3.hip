@@ -204,8 +204,8 @@ __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(PF2 ? 2 : 3
     for (int t = 0; t < NKT; ++t)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const f32x4 lo = {st[t][8 * j] * inv, st[t][8 * j + 1] * inv, st[t][8 * j + 2] * inv, st[t][8 * j + 3] * inv};
-            const f32x4 hi = {st[t][8 * j + 4] * inv, st[t][8 * j + 5] * inv, st[t][8 * j + 6] * inv, st[t][8 * j + 7] * inv};
+            const f32x4 lo = {mul_rn(st[t][8 * j], inv), mul_rn(st[t][8 * j + 1], inv), mul_rn(st[t][8 * j + 2], inv), mul_rn(st[t][8 * j + 3], inv)};
+            const f32x4 hi = {mul_rn(st[t][8 * j + 4], inv), mul_rn(st[t][8 * j + 5], inv), mul_rn(st[t][8 * j + 6], inv), mul_rn(st[t][8 * j + 7], inv)};
             u32x2 a[3], b2[3];
             plane_split4(lo, a); plane_split4(hi, b2);
 #pragma unroll
@@ -431,8 +431,8 @@ __global__ __launch_bounds__(768) void mocha_attention_x3_split(AttnParams p) {
     for (int t = 0; t < NKT; ++t)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const f32x4 lo = {st[t][8 * j] * inv, st[t][8 * j + 1] * inv, st[t][8 * j + 2] * inv, st[t][8 * j + 3] * inv};
-            const f32x4 hi = {st[t][8 * j + 4] * inv, st[t][8 * j + 5] * inv, st[t][8 * j + 6] * inv, st[t][8 * j + 7] * inv};
+            const f32x4 lo = {mul_rn(st[t][8 * j], inv), mul_rn(st[t][8 * j + 1], inv), mul_rn(st[t][8 * j + 2], inv), mul_rn(st[t][8 * j + 3], inv)};
+            const f32x4 hi = {mul_rn(st[t][8 * j + 4], inv), mul_rn(st[t][8 * j + 5], inv), mul_rn(st[t][8 * j + 6], inv), mul_rn(st[t][8 * j + 7], inv)};
             u32x2 a[3], b2[3];
             plane_split4(lo, a); plane_split4(hi, b2);
 #pragma unroll

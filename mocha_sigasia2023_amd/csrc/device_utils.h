@@ -138,6 +138,13 @@ __device__ __forceinline__ void plane_split4(const f32x4_t v, u32x2_t (&out)[3])
         }
     }
 }
+// a * b rounded to fp32 whatever follows: a product that is split into planes must be the fp32 number the comments call it.  Left to the
+// compiler, the product is contracted into the split's first subtraction (fma(a, b, -plane 0)), the planes then carry the UNROUNDED product
+// and a softmax weight that is exactly 1 (one key) stops being 1 (attention_x3.hip, attention_kv.hip; tests/test_attention_kernels.py).
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
 // eight floats -> three planes of eight bf16: one MFMA operand (K = 16, this lane's k half) per plane
 __device__ __forceinline__ void plane_split8(const float (&x)[8], s16x8_t (&out)[3]) {
     const f32x4_t lo = {x[0], x[1], x[2], x[3]}, hi = {x[4], x[5], x[6], x[7]};

@@ -87,6 +87,14 @@ hipError_t launch_gather_f32(const float* table, const int32_t* idx, long long r
 // Multi-head attention, nq queries x nk keys (<= 192), one workgroup per (window, head)
 // (net/transformer.py:65-76; nn.MultiheadAttention in model_CVAE.py):
 //   out[b, i, h*DH + d] = softmax_j(q_i·k_j * scale) v_j ;  batch b starts at row b*nq (q, out) / b*nk (k, v)
+// What the kernels rely on and no launcher checks (tests/gemm_probe/attention_probe.cpp refuses it before a launch):
+//   scale > 0 and finite (the row maximum is taken over the unscaled scores);
+//   q, k, v, out (and the kv image) 16-byte aligned, ldq / ldk / ldv / ldo and an explicit hsk / hsv multiples of 4 floats: every operand
+//   fetch and every store is 16 bytes at row * ld + 4c floats;
+//   heads >= 1, ldq / ldo >= heads * dh, ldk / ldv >= (heads - 1) * hs + dh; a window's rows are all that is read (padded rows are
+//   zero-filled or clamped to the window's last row), so the buffers may end with the last window's last row;
+//   reverse is honoured only by the full-batch instances of launch_attention_x3 (B * heads > 256) and ignored elsewhere: the same windows
+//   in another order, results identical to the bit either way.
 // ---------------------------------------------------------------------------------------
 struct AttnParams {
     const float* q; const float* k; const float* v; float* out;
@@ -95,8 +103,8 @@ struct AttnParams {
     float scale;
     int hsk = -1, hsv = -1;       // column offset per head of k / v (default dh; 0 = all heads share the same rows)
     int split_max = 192;          // (window, head) pairs up to which the twelve-wave head-dim-256 variant is launched (0 = never)
-    // launch_attention_x3 only: window b's keys / values are rows [kv_idx[b] * nk, +nk) of k / v (index clamped to [0, kv_rows)) - the decoder
-    // reading IN(cha) and cha of the matched bank entries in place (test_fullframework.py:465), no gathered copy
+    // launch_attention_x3 only (launch_attention refuses it): window b's keys / values are rows [kv_idx[b] * nk, +nk) of k / v (index clamped
+    // to [0, kv_rows)) - the decoder reading IN(cha) and cha of the matched bank entries in place (test_fullframework.py:465), no gathered copy
     const int32_t* kv_idx = nullptr; long long kv_rows = 0;
     // launch_attention_x3, full-batch instances only: the windows are walked from the last to the first (GemmParams::reverse)
     int reverse = 0;
