@@ -3,7 +3,7 @@
 mocap frame at a time through ``LiveSession`` - ring push + featurize, segmented characterize, pose heads and one post-processing
 frame per push, one captured graph - and written as two BVH files.
 
-    python examples/live_demo.py [--frames 180] [--out bench_outputs/live_demo] [--ours [--seed 7]] [--switch 120 [--inertial 0.1]]
+    python examples/live_demo.py [--frames 180] [--out bench_outputs/live_demo] [--ours [--seed 7]] [--switch 120 [--inertial 0.1]] [--raw L]
 
 ``--ours`` runs the CVAE ("Ours") branch inside the same graph (``LiveOursSession``): each stream's character feature is seeded with
 its matched bank row on the first pose and sampled from the previous one afterwards, the noise drawn on the device; the files are then
@@ -12,6 +12,10 @@ named ``Ours_stream<s>.bvh`` as the reference names its result ``Ours.bvh``.
 ``--switch FRAME``: stream 0 names character 1 from that frame on - the new id is device data, the graph is not captured again.
 ``--inertial HALFLIFE`` (seconds): the switch does not pop; the jump of the pose heads decays as an offset (``LiveSession(inertial=...)``,
 the reference's per-bone inertializers on the device).  The size of the largest bone-position step at the switch frame is printed.
+
+``--raw L``: the streams push RAW mocap frames - local Euler rotations in degrees and local positions in centimetres of the 24 joints, as
+a BVH file holds them (a synthetic walk) - and the mocap front end inside the same graph makes the root bone, the velocities and the foot
+contacts (``LiveSession(raw=L)``, ``push_raw``), L = 0..18 frames of lookahead.  The first pose then comes with push 90.
 
 Weights, norms and motions are synthetic (see demo_pair.py for what to replace with real assets).
 """
@@ -37,14 +41,18 @@ ap.add_argument("--soft", nargs=2, metavar=("K", "T"), help="soft matching: the 
                 "entries (1..8) instead of the nearest one")
 ap.add_argument("--switch", type=int, default=None, metavar="FRAME", help="stream 0 takes character 1 from that frame on")
 ap.add_argument("--inertial", type=float, default=None, metavar="HALFLIFE", help="inertialize character switches with that half-life in seconds")
+ap.add_argument("--raw", type=int, default=None, metavar="L", help="push raw mocap frames; the front end runs in the graph with L frames of lookahead")
 a = ap.parse_args()
+if a.ours and a.raw is not None:
+    raise SystemExit("--raw does not apply to --ours: the CVAE session has no mocap front end")
 if a.ours and a.inertial is not None:
     raise SystemExit("--inertial does not apply to --ours: that branch seeds again on a switch and keeps its own chain state")
 if a.ours and a.soft:
     raise SystemExit("--soft does not apply to --ours: its decoder already reads a sampled character feature")
 soft = (int(a.soft[0]), float(a.soft[1])) if a.soft else None
-if a.frames < 60:
-    raise SystemExit("--frames must be at least 60: a stream's first pose comes with its 60th frame")
+first = 59 if a.raw is None else 89                                   # index of the push that brings the first pose
+if a.frames <= first:
+    raise SystemExit(f"--frames must be at least {first + 1}: a stream's first pose comes with that push")
 os.makedirs(a.out, exist_ok=True)
 dev = torch.device("cuda:0")
 F, J, C, S = a.frames, 25, 15, 2
@@ -80,28 +88,39 @@ if a.ours:                                                            # test_ful
     sess = LiveOursSession(bank, cnt_mean, cnt_std, synthetic_cvae_state_dict(99, 1.0), *stats, streams=S, post=PostProcessor(model),
                            noise="device", seed=a.seed)
 else:
-    sess = LiveSession(bank, cnt_mean, cnt_std, streams=S, post=PostProcessor(model), soft=soft, inertial=a.inertial)
-sess.push(*[torch.stack([src[s][k][0] for s in range(S)]) for k in range(4)], *[torch.stack([per[s][k][0] for s in range(S)]) for k in range(4)],
-          characters=[0, 1])                                          # the first push captures the step
+    sess = LiveSession(bank, cnt_mean, cnt_std, streams=S, post=PostProcessor(model), soft=soft, inertial=a.inertial, raw=a.raw)
+if a.raw is not None:
+    raw = [synthetic.raw_walk_clip(LAYOUTS["mocha"]["parents"], F, seed=40 + s) for s in range(S)]
+    raw_rot = torch.from_numpy(np.stack([r[0] for r in raw])).to(dev)  # (S, F, 24, 3) degrees, 'zyx'
+    raw_pos = torch.from_numpy(np.stack([r[1] for r in raw])).to(dev)  # (S, F, 24, 3) centimetres
+
+
+def push(f, characters=None):
+    if a.raw is not None:
+        return sess.push_raw(raw_rot[:, f], raw_pos[:, f], characters=characters)
+    return sess.push(*[torch.stack([src[s][k][f] for s in range(S)]) for k in range(4)],
+                     *[torch.stack([per[s][k][f] for s in range(S)]) for k in range(4)], characters=characters)
+
+
+push(0, characters=[0, 1])                                            # the first push captures the step
 sess.reset()
 torch.cuda.synchronize(); t0 = time.perf_counter()
 pos, eul = [], []
 for f in range(F):
-    o = sess.push(*[torch.stack([src[s][k][f] for s in range(S)]) for k in range(4)],
-                  *[torch.stack([per[s][k][f] for s in range(S)]) for k in range(4)], characters=[1, 1] if f == a.switch else None)
-    if f >= 59:                                                       # both streams started together: both are valid from here on
+    o = push(f, characters=[1, 1] if f == a.switch else None)
+    if f >= first:                                                    # both streams started together: both are valid from here on
         pos.append(o["bvh_pos"].clone()); eul.append(o["bvh_euler"].clone())
 torch.cuda.synchronize(); dt = time.perf_counter() - t0
-pos, eul = torch.stack(pos, 1), torch.stack(eul, 1)                   # (S, F - 59, V, 3)
+pos, eul = torch.stack(pos, 1), torch.stack(eul, 1)                   # (S, F - first, V, 3)
 
 names = ["Joint%02d" % i for i in range(24)]
 for s in range(S):
-    p = os.path.join(a.out, f"{'Ours' if a.ours else 'soft' if soft else 'live'}_stream{s}.bvh")
+    p = os.path.join(a.out, f"{'Ours' if a.ours else 'soft' if soft else 'raw' if a.raw is not None else 'live'}_stream{s}.bvh")
     write_bvh(p, names, LAYOUTS["mocha"]["parents"], pos[s], eul[s])
     print(f"  {p}: {os.path.getsize(p)} bytes, {pos.shape[1]} frames")
-if a.switch is not None and 60 <= a.switch < F:
+if a.switch is not None and first + 1 <= a.switch < F:
     step = (pos[0, 1:, 1:] - pos[0, :-1, 1:]).abs().amax(dim=(1, 2))     # per frame, the non-root bones of stream 0
-    print(f"  stream 0 switches character at frame {a.switch}: largest bone-position step there {float(step[a.switch - 60]):.4f}, "
+    print(f"  stream 0 switches character at frame {a.switch}: largest bone-position step there {float(step[a.switch - first - 1]):.4f}, "
           f"median over the clip {float(step.median()):.4f}" + (f" (inertialized, half-life {a.inertial} s)" if a.inertial is not None else ""))
 print(f"{F} pushes of {S} streams in {dt * 1e3:.1f} ms ({dt / F * 1e3:.3f} ms per push, host loop included)")
 assert bool(torch.isfinite(pos).all()) and bool(torch.isfinite(eul).all())

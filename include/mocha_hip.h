@@ -538,6 +538,66 @@ int mocha_live_step_ours(mocha_ctx* ctx, const mocha_post_cfg* cfg, void* live, 
                          const mocha_ours_cfg* ocfg, double* pos, double* rot, double* ik_rot, double* bvh_pos, double* bvh_euler,
                          int32_t* idx, int32_t* valid, int32_t* seeded, void* stream);
 
+/* The mocap front end of a live session: RAW frames in.  What mocha_live_step takes per frame - Yrot / Ypos / Yvel / Yang with a synthetic
+ * root bone, src_rvel / src_rang / src_speed, the foot contacts - is what the reference's process_data (preprocess/generate_database.py:
+ * 86-177) makes of a whole clip with filters that read frames after the one they produce.  These calls are its streaming form, on the
+ * device: a stream pushes ONE raw frame per call - the local rotations and local positions of its V joints, joint 0 the hips, as a mocap
+ * device or one line of a BVH file holds them - and, once it has pushed 31 frames (the 31-tap filter refuses a shorter clip), every push
+ * emits frame t = n-1-lookahead of process_data applied to the n frames pushed since the stream's reset.
+ *   lookahead = 18 (0.3 s): the emitted frame is the whole clip's frame, contacts included (pos / vel / rot / ang already from 16 on).
+ *   lookahead = 0: no added latency; the reference's clip-end rules are applied at every frame - the polynomial edge fit of
+ *     savgol_filter(mode='interp'), v[-1] = v[-2] + (v[-2] - v[-3]), the 'nearest' padding of the median filter.
+ * Per emitted frame: root position = 15-tap cubic fit of the spine joint on xz, root direction = 31-tap cubic fit of the projected
+ * across-direction (shoulders + upper legs), renormalised before and after; root rotation = normalize(between(z, direction)); the hips
+ * made root-local; velocities and angular velocities by central differences at `fps`; contacts = fk_vel down each toe chain, speed <
+ * contact_velocity_threshold, then the 6-frame majority vote ("at least 3 of t-3 .. t+2").  src_rvel / src_rang = inv_mul_vec(Yrot[0],
+ * Yvel[0] / Yang[0]) and src_speed = the mean speed of bone 1 over the last 60 emitted frames (test_fullframework.py:142-143, :164-169,
+ * :493; 0 until 60 were emitted) are evaluated in float64 on the emitted fp32 values and rounded once: the demo evaluates them in fp32
+ * NumPy, so they may sit one fp32 ulp away from its values.  Everything else is float64 on the fp32 inputs, rounded to fp32 once.
+ * Inherited from the reference, not fixed: between([0,0,1], d) is singular for a character facing exactly -z; contacts flip at a hard
+ * threshold.  Not provided: the last `lookahead` frames of a clip are never emitted (no flush), no mirroring, no BVH text parsing.
+ *   mocha_ingest_cfg_default : the reference's constants (lookahead 0, Euler degrees in 'zyx' channel order, unit scale 0.01: cm -> m,
+ *                            60 frames per second, threshold 0.5 m/s) and the role joints of `layout`: 0 ('mocha': Spine2 = 7, shoulders
+ *                            9 / 16, upper legs 1 / 20), 1 ('mixamo' of this library's 22-joint table: 3, 6 / 10, 18 / 14).
+ *   mocha_ingest_state_bytes : bytes of the front end's buffer for `streams` streams (caller-owned device memory, private layout: per
+ *                            stream the frame counts, the sign state of quat.unroll, a ring of the last 40 raw frames and the last 60
+ *                            emitted hips positions; then the staging mocha_live_step_raw hands to the live step).  ALL-ZERO BYTES = no
+ *                            frame seen; a snapshot is a copy.
+ *   mocha_ingest_reset     : zeroes the rows of the named streams (which NULL: all).  Enqueued on `stream`, graph-safe.
+ *   mocha_live_ingest_step : the front end alone.  rot (S,V,4) quaternions w,x,y,z or (S,V,3) Euler degrees in the order of
+ *                            cfg->euler_order (rot_format), pos (S,V,3); the toes are post->contact_bones (post NULL: the demo's).
+ *                            Outputs Yrot (S,V+1,4), Ypos / Yvel / Yang (S,V+1,3), src_rvel / src_rang (S,3), src_speed (S), contact
+ *                            (S,n_contact) uint8, have (S) int32: 1 where the stream emitted a frame.  Rows of a stream with have == 0 are
+ *                            left untouched.  One launch (mocha_live_ingest, one 64-lane workgroup per stream), no allocation, no
+ *                            synchronisation: capture-safe.
+ *   mocha_live_step_raw    : mocha_live_ingest_step into the buffer's staging, then the live step on it, in ONE captured graph.  k == 0:
+ *                            the hard step (idx_k / w_k may be NULL), k >= 1: the soft step; inert non-NULL: the inertialized step (icfg
+ *                            NULL: its default).  A stream with have == 0 pushes nothing into its window ring: valid[s] = 0, its
+ *                            outputs and its post state stay, exactly as for a warming stream - so valid first becomes 1 on push 90.
+ *                            Keyed as the step it wraps plus `ingest`, the raw pointers and the CONTENTS of icfg_in; while profiling
+ *                            the launch is named mocha_live_ingest, site live.ingest.
+ * Refusals (MOCHA_ERR_ARG, nothing launched): a NULL required pointer, lookahead outside 0..18, rot_format outside 0..1, an Euler order
+ * that is no permutation of 0..2, a role joint outside 0..V-1, unit_scale / fps / threshold not finite or fps <= 0, a skeleton whose
+ * joints do not follow their parents, and what the post cfg refuses. */
+typedef struct mocha_ingest_cfg {
+    int lookahead;                       /* 0..18 frames */
+    int rot_format;                      /* 0: quaternions (w,x,y,z), 1: Euler angles in degrees */
+    int euler_order[3];                  /* axis index (0 x, 1 y, 2 z) of channel 0, 1, 2: quat.from_euler's `order` */
+    double unit_scale, fps, contact_velocity_threshold;
+    int spine, shoulder_l, shoulder_r, upleg_l, upleg_r;      /* raw joint indices */
+} mocha_ingest_cfg;
+void mocha_ingest_cfg_default(mocha_ingest_cfg* cfg, int layout);
+int64_t mocha_ingest_state_bytes(const mocha_ctx* ctx, int streams);
+int mocha_ingest_reset(mocha_ctx* ctx, void* ingest, int streams, const int32_t* which, int n, void* stream);
+int mocha_live_ingest_step(mocha_ctx* ctx, const mocha_ingest_cfg* cfg, const mocha_post_cfg* post, void* ingest, int streams,
+                           const float* rot, const float* pos, float* Yrot, float* Ypos, float* Yvel, float* Yang, float* src_rvel,
+                           float* src_rang, float* src_speed, unsigned char* contact, int32_t* have, void* stream);
+int mocha_live_step_raw(mocha_ctx* ctx, const mocha_post_cfg* cfg, const mocha_ingest_cfg* icfg_in, void* live, void* ingest, int streams,
+                        const float* rot, const float* pos, const int32_t* seg, const float* cnt_mean, const float* cnt_std, int k,
+                        float temperature, double* pos_out, double* rot_out, double* ik_rot, double* bvh_pos, double* bvh_euler,
+                        int32_t* idx, int32_t* valid, int32_t* idx_k, float* w_k, void* stream, void* inert,
+                        const mocha_inert_cfg* icfg);
+
 /* Bank build statistics: cnt_mean, cnt_std = np.mean(cnt, 0), np.std(cnt, 0) over the N bank entries
  * (compute_cnt_norm.py:174-175; population std), x (N, 90*256) -> mean, std (90*256). */
 int mocha_column_stats(mocha_ctx* ctx, const float* x, int64_t N, float* mean, float* std_, void* stream);

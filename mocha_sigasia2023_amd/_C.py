@@ -35,6 +35,12 @@ class mocha_inert_cfg(C.Structure):
     _fields_ = [("halflife", C.c_double), ("dt", C.c_double)]
 
 
+class mocha_ingest_cfg(C.Structure):
+    _fields_ = [("lookahead", C.c_int), ("rot_format", C.c_int), ("euler_order", C.c_int * 3), ("unit_scale", C.c_double), ("fps", C.c_double),
+                ("contact_velocity_threshold", C.c_double), ("spine", C.c_int), ("shoulder_l", C.c_int), ("shoulder_r", C.c_int),
+                ("upleg_l", C.c_int), ("upleg_r", C.c_int)]
+
+
 _vp, _i, _i64 = C.c_void_p, C.c_int, C.c_int64
 
 # name -> (restype, argtypes); every symbol include/mocha_hip.h declares
@@ -102,6 +108,11 @@ SIGNATURES = {
     "mocha_inert_state_bytes": (_i64, [_vp]),
     "mocha_inertialize_step": (_i, [_vp] * 8 + [_i, _vp]),
     "mocha_live_step_inert": (_i, [_vp, _vp, _vp, _i] + [_vp] * 11 + [_i, C.c_float] + [_vp] * 12),
+    "mocha_ingest_cfg_default": (None, [_vp, _i]),
+    "mocha_ingest_state_bytes": (_i64, [_vp, _i]),
+    "mocha_ingest_reset": (_i, [_vp, _vp, _i, C.POINTER(C.c_int32), _i, _vp]),
+    "mocha_live_ingest_step": (_i, [_vp, _vp, _vp, _vp, _i] + [_vp] * 12),
+    "mocha_live_step_raw": (_i, [_vp, _vp, _vp, _vp, _vp, _i] + [_vp] * 5 + [_i, C.c_float] + [_vp] * 12),
     "mocha_set_rccl_library": (_i, [C.c_char_p]),
     "mocha_comm_unique_id": (_i, [_vp, _vp]),
     "mocha_comm_init": (_i, [_vp, _vp, _i, _i]),

@@ -201,8 +201,11 @@ hipError_t launch_featurize(const float* Yrot, const float* Ypos, const float* Y
 static constexpr int LIVE_WINDOW = 60;
 struct LiveRing { int32_t* counters; float *rot, *pos, *vel, *ang; };
 hipError_t live_init();
+// have (S) or null: a stream with have[s] == 0 brought no frame - nothing is pushed, its counters stay, eff[s] = -1, valid[s] = 0 and its
+// window is featurised as an empty ring's
 hipError_t launch_live_push(const LiveRing& r, const float* Yrot, const float* Ypos, const float* Yvel, const float* Yang, const int32_t* seg,
-                            const int* parents /*J, device*/, float* X, int32_t* eff, int32_t* valid, int S, int J, hipStream_t s);
+                            const int* parents /*J, device*/, float* X, int32_t* eff, int32_t* valid, int S, int J, hipStream_t s,
+                            const int32_t* have = nullptr);
 // the CVAE branch of a live step (live_ours.hip).  counters (S,3) = {chain: steps since the stream's seed frame, last: the character id of
 // its last step, mode}; cnt / prev / vae (S,90,256), cond (S,180,256), eps (S,256); sm / ss / cm / cs (90,256) the CVAE's statistics.
 // condition: mode[s] = 0 (eff[s] outside 0..nseg-1: warming) / 1 (chain == 0 or eff[s] != last: seed) / 2 (chain) into the counters;
@@ -219,6 +222,27 @@ hipError_t launch_live_ours_update(int32_t* counters, const int32_t* eff, const 
 #define MOCHA_MAX_CONTACT 4
 #define MOCHA_MAX_CHAIN 8
 #define MOCHA_MAX_BONES 32
+// The mocap front end of a live session (ingest.hip): ONE raw frame of S independent streams in - local rotations (V,4) wxyz or (V,3)
+// Euler degrees, local positions (V,3), joint 0 the hips - and, once a stream has seen INGEST_FIRST frames, frame n-1-lookahead of the
+// reference's process_data on the stream's prefix out: Yrot (S,V+1,4), Ypos / Yvel / Yang (S,V+1,3) root bone first, src_rvel / src_rang
+// (S,3), src_speed (S), contact (S,n_contact), have (S) = 1 / 0.  state: (S, INGEST_STATE_DOUBLES) float64 words, all-zero = no frame seen.
+// rows15 / rows31: the (15,15) and (31,31) cubic fit rows on the device.  One launch, no allocation, no synchronisation.
+static constexpr int INGEST_FIRST = 31, INGEST_RING = 40, INGEST_MAX_LOOKAHEAD = 18;
+static constexpr int INGEST_FRAME_DOUBLES = MOCHA_MAX_BONES * 7 + 4;      // quaternions | positions | spine xz | direction xz
+static constexpr int INGEST_STATE_DOUBLES = 2 + MOCHA_MAX_BONES * 4 + INGEST_RING * INGEST_FRAME_DOUBLES + 60 * 3;
+struct IngestParams {
+    double* state;
+    const double *rows15, *rows31;
+    const float *rot, *pos;         // the raw frame: (S,V,4|3), (S,V,3)
+    float *Yrot, *Ypos, *Yvel, *Yang, *src_rvel, *src_rang, *src_speed;
+    unsigned char* contact;
+    int32_t* have;
+    int V, lookahead, euler, order[3], roles[5], n_contact;
+    int parents[MOCHA_MAX_BONES];   // of the V raw joints
+    int contact_bones[MOCHA_MAX_CONTACT];
+    double scale, fps, threshold;
+};
+hipError_t launch_live_ingest(const IngestParams& p, int S, hipStream_t s);
 static constexpr int POST_STATE_DOUBLES = 8 + MOCHA_MAX_BONES * 3 + MOCHA_MAX_CONTACT * 19;
 struct PostParams {
     const float* heads;             // (clips, frames, V, 13)

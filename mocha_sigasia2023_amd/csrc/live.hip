@@ -7,6 +7,8 @@
 //                      featurises window frame t through featurize_frame (featurize_body.h), the body of mocha_featurize, so the bits
 //                      are those of mocha_featurize on the materialised window - plus the stream's effective character id (seg[s]
 //                      once the ring holds 60 frames, -1 before: the segmented matcher reads no bank row for -1) and valid[s].
+//                      With `have` (mocha_live_step_raw), a stream whose have[s] == 0 pushes nothing: counters and ring stay, eff = -1,
+//                      valid = 0, its window is featurised as an empty ring's.
 //
 // Frames of a ring that is still filling are featurised as identity rotations and zeros: finite features, because the streams of a
 // step share every later launch.
@@ -19,7 +21,8 @@ namespace mocha {
 __global__ __launch_bounds__(FT) MOCHA_NO_PACKED_F32 void mocha_live_push(LiveRing r, const float* __restrict__ Yrot, const float* __restrict__ Ypos,
                                                       const float* __restrict__ Yvel, const float* __restrict__ Yang,
                                                       const int32_t* __restrict__ seg, const int* __restrict__ parents,
-                                                      float* __restrict__ X, int32_t* __restrict__ eff, int32_t* __restrict__ valid, int J) {
+                                                      float* __restrict__ X, int32_t* __restrict__ eff, int32_t* __restrict__ valid, int J,
+                                                      const int32_t* __restrict__ have) {
     extern __shared__ float g[];                                  // [J][FC][FT]
     const int s = blockIdx.x, tid = threadIdx.x;
     const int T = LIVE_WINDOW;
@@ -31,18 +34,19 @@ __global__ __launch_bounds__(FT) MOCHA_NO_PACKED_F32 void mocha_live_push(LiveRi
     float* vel = r.vel + (size_t)s * T * J * 3;
     float* ang = r.ang + (size_t)s * T * J * 3;
     __syncthreads();                                              // every thread has read the counters
+    const bool none = have && have[s] == 0;                       // uniform: no frame for this stream (mocha_live_step_raw's front end is warming)
     // the new frame into slot `head`
-    for (int k = tid; k < J * 4; k += FT) rot[(size_t)head * J * 4 + k] = Yrot[(size_t)s * J * 4 + k];
-    for (int k = tid; k < J * 3; k += FT) {
+    for (int k = tid; !none && k < J * 4; k += FT) rot[(size_t)head * J * 4 + k] = Yrot[(size_t)s * J * 4 + k];
+    for (int k = tid; !none && k < J * 3; k += FT) {
         pos[(size_t)head * J * 3 + k] = Ypos[(size_t)s * J * 3 + k];
         vel[(size_t)head * J * 3 + k] = Yvel[(size_t)s * J * 3 + k];
         ang[(size_t)head * J * 3 + k] = Yang[(size_t)s * J * 3 + k];
     }
-    const int nhead = head + 1 == T ? 0 : head + 1;
-    const int nfill = fill < T ? fill + 1 : T;
+    const int nhead = none ? head : head + 1 == T ? 0 : head + 1;
+    const int nfill = none ? fill : fill < T ? fill + 1 : T;
     if (tid == 0) {
-        cnt[0] = nhead; cnt[1] = nfill;
-        const bool full = nfill == T;
+        if (!none) { cnt[0] = nhead; cnt[1] = nfill; }
+        const bool full = !none && nfill == T;
         eff[s] = full ? seg[s] : -1;
         valid[s] = full ? 1 : 0;
     }
@@ -50,15 +54,16 @@ __global__ __launch_bounds__(FT) MOCHA_NO_PACKED_F32 void mocha_live_push(LiveRi
     if (tid >= T) return;
     // window frame tid (0 oldest .. 59 newest) has age 59 - tid; the frame of age a sits a + 1 slots behind the new head
     const int age = T - 1 - tid;
-    const bool held = age < nfill;
+    const bool held = !none && age < nfill;
     int slot = nhead - 1 - age;
     if (slot < 0) slot += T;
     // bone 0 of the window's last frame: the frame just pushed
     const size_t last = (size_t)s * J;
-    const Q Rr = {Yrot[last * 4], Yrot[last * 4 + 1], Yrot[last * 4 + 2], Yrot[last * 4 + 3]};
-    const V3 Rp = {Ypos[last * 3], Ypos[last * 3 + 1], Ypos[last * 3 + 2]};
-    const V3 Rv = {Yvel[last * 3], Yvel[last * 3 + 1], Yvel[last * 3 + 2]};
-    const V3 Ra = {Yang[last * 3], Yang[last * 3 + 1], Yang[last * 3 + 2]};
+    auto in = [&](const float* a, size_t i, float d) { return none ? d : a[i]; };       // no frame: the identity root, whatever the staging row holds
+    const Q Rr = {in(Yrot, last * 4, 1.f), in(Yrot, last * 4 + 1, 0.f), in(Yrot, last * 4 + 2, 0.f), in(Yrot, last * 4 + 3, 0.f)};
+    const V3 Rp = {in(Ypos, last * 3, 0.f), in(Ypos, last * 3 + 1, 0.f), in(Ypos, last * 3 + 2, 0.f)};
+    const V3 Rv = {in(Yvel, last * 3, 0.f), in(Yvel, last * 3 + 1, 0.f), in(Yvel, last * 3 + 2, 0.f)};
+    const V3 Ra = {in(Yang, last * 3, 0.f), in(Yang, last * 3 + 1, 0.f), in(Yang, last * 3 + 2, 0.f)};
     featurize_frame([&](int i, Q& lr, V3& lp, V3& lv, V3& la) {
         if (held) {
             const size_t e = (size_t)slot * J + i;
@@ -78,11 +83,11 @@ hipError_t live_init() {
 }
 
 hipError_t launch_live_push(const LiveRing& r, const float* Yrot, const float* Ypos, const float* Yvel, const float* Yang, const int32_t* seg,
-                            const int* parents, float* X, int32_t* eff, int32_t* valid, int S, int J, hipStream_t s) {
+                            const int* parents, float* X, int32_t* eff, int32_t* valid, int S, int J, hipStream_t s, const int32_t* have) {
     if (S <= 0) return hipSuccess;
     if (J > FEAT_MAX_BONES || J < 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(mocha_live_push, dim3(S), dim3(FT), (size_t)J * FC * FT * sizeof(float), s, r, Yrot, Ypos, Yvel, Yang, seg, parents, X,
-                       eff, valid, J);
+                       eff, valid, J, have);
     return hipGetLastError();
 }
 

@@ -247,6 +247,7 @@ struct mocha_ctx {
     bool fold_upsample = true;         // to_mot: the k=5 temporal conv over the x4-upsampled frames as a 3-tap conv over the SOURCE frames with per-phase summed weights
     bool fold_joint = true;            // embedding joint block: gcn 1x1 conv folded into the k=5 temporal conv (one K = 960 GEMM)
     DeviceBuffer<int> bone_parents;    // device: parents of the (V+1)-bone skeleton with the root bone in front
+    DeviceBuffer<double> ingest_rows;  // device: the cubic fit rows of the mocap front end, (15,15) then (31,31) (ensure_ingest_rows)
     DeviceBuffer<float> pose_norm;     // [x_mean | x_std | y_mean | y_std], (V+1)*C_in each (norm.npz of the reference)
     bool use_tiled = false;            // option "bank_tiled": -4 % on the cold pass for 2 x the bf16 copy's memory (profiles/r04/c_tiled_loader_ab.txt): off
     DeviceBuffer<unsigned long long> topk_keys{BUF_MOVES_GENERATION};      // every row's key of up to 8 queries (mocha_match_topk)
@@ -284,6 +285,8 @@ struct mocha_ctx {
         int soft_k = 0; float soft_t = 0.f; const void* soft[2] = {};
         // mocha_live_step_inert only: the inertializer's state buffer and its two constants
         const void* inert = nullptr; double inert_halflife = 0.0, inert_dt = 0.0;
+        // mocha_live_step_raw only: the front end's buffer and the raw frame's arrays; its configuration, which the captured launch carries by value
+        const void* ingest[3] = {}; mocha_ingest_cfg icfg{};
         bool operator==(const StepKey& o) const {
             if (!(x == o.x && mean == o.mean && sd == o.sd && y == o.y && idx == o.idx && seg == o.seg && windows == o.windows && raw == o.raw))
                 return false;
@@ -292,6 +295,12 @@ struct mocha_ctx {
             if (noise != o.noise || seed != o.seed) return false;
             if (soft_k != o.soft_k || soft_t != o.soft_t || soft[0] != o.soft[0] || soft[1] != o.soft[1]) return false;
             if (inert != o.inert || inert_halflife != o.inert_halflife || inert_dt != o.inert_dt) return false;
+            for (int i = 0; i < 3; ++i) if (ingest[i] != o.ingest[i] || icfg.euler_order[i] != o.icfg.euler_order[i]) return false;
+            if (icfg.lookahead != o.icfg.lookahead || icfg.rot_format != o.icfg.rot_format || icfg.unit_scale != o.icfg.unit_scale ||
+                icfg.fps != o.icfg.fps || icfg.contact_velocity_threshold != o.icfg.contact_velocity_threshold || icfg.spine != o.icfg.spine ||
+                icfg.shoulder_l != o.icfg.shoulder_l || icfg.shoulder_r != o.icfg.shoulder_r || icfg.upleg_l != o.icfg.upleg_l ||
+                icfg.upleg_r != o.icfg.upleg_r)
+                return false;
             const mocha_post_cfg &a = post, &b = o.post;
             for (int i = 0; i < 4; ++i) if (a.contact_bones[i] != b.contact_bones[i]) return false;
             return a.dt == b.dt && a.ik_max_length_buffer == b.ik_max_length_buffer && a.ik_foot_height == b.ik_foot_height &&
@@ -304,7 +313,8 @@ struct mocha_ctx {
         StepKey key; int64_t generation = -1;
     } step[MAX_SETS], seg_step, live_step, ours_step, // seg_step: mocha_step_graph_segmented, live_step: mocha_live_step, ours_step: mocha_live_step_ours (workspace set 0)
       soft_step, live_soft_step,                      // mocha_step_graph_soft_segmented, mocha_live_step_soft (workspace set 0)
-      live_inert_step;                                // mocha_live_step_inert, hard or soft (workspace set 0)
+      live_inert_step,                                // mocha_live_step_inert, hard or soft (workspace set 0)
+      live_raw_step[3];                               // mocha_live_step_raw: hard, soft, inertialized (workspace set 0)
     hipStream_t cap_stream = nullptr;                 // capture happens on this internal stream (the caller's may be the null stream)
     ncclComm_t comm = nullptr; int comm_rank = 0, comm_size = 1;      // mocha_comm_init
     DeviceBuffer<long long> bcast_hdr;                                  // device: {entries, bf16?} header of mocha_bank_broadcast
@@ -1402,7 +1412,7 @@ void mocha_destroy(mocha_ctx* c) {
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     for (auto* g : {&c->step[0], &c->step[1], &c->step[2], &c->seg_step, &c->live_step, &c->ours_step, &c->soft_step, &c->live_soft_step,
-                    &c->live_inert_step}) {
+                    &c->live_inert_step, &c->live_raw_step[0], &c->live_raw_step[1], &c->live_raw_step[2]}) {
         if (g->exec) (void)hipGraphExecDestroy(g->exec);
         if (g->graph) (void)hipGraphDestroy(g->graph);
     }
@@ -2935,7 +2945,8 @@ static int live_step_impl(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, i
                           const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed, const unsigned char* contact,
                           const int32_t* seg, const float* cnt_mean, const float* cnt_std, double* pos, double* rot, double* ik_rot, double* bvh_pos,
                           double* bvh_euler, int32_t* idx, int32_t* valid, int k, float temperature, int32_t* idx_k, float* w_k, void* stream,
-                          void* inert = nullptr, const mocha_inert_cfg* icfg = nullptr) {
+                          void* inert = nullptr, const mocha_inert_cfg* icfg = nullptr, const IngestParams* ing = nullptr,
+                          const mocha_ingest_cfg* ing_cfg = nullptr) {
     if (streams < 1 || streams > 16) return fail(c, MOCHA_ERR_ARG, "live_step: 1 <= streams <= 16");
     if (!live || !Yrot || !Ypos || !Yvel || !Yang || !src_rvel || !src_rang || !src_speed || !contact || !seg || !cnt_mean || !cnt_std || !pos ||
         !rot || !ik_rot || !idx || !valid || (!bvh_pos) != (!bvh_euler))
@@ -2980,8 +2991,12 @@ static int live_step_impl(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, i
     };
     // ring push + featurize -> segmented characterize of the S windows with the effective ids -> pose heads -> one post-processing frame
     auto body = [&](hipStream_t cs) -> int {
+        // mocha_live_step_raw: the front end writes the frame the push reads (Yrot .. contact are its staging) and says which streams have one
+        if (ing)
+            LAUNCH(c, cs, "mocha_live_ingest", "live.ingest", 0.0, (double)streams * (V * 7.0 * 4 + J * 13.0 * 4 + 40.0 * 4 * 8 + J * 16.0 * 13 * 8),
+                   launch_live_ingest(*ing, streams, cs));
         LAUNCH(c, cs, "mocha_live_push", "live.push", streams * 60.0 * J * 150, streams * (60.0 * J * (13 + 15) + J * 26.0) * 4,
-               launch_live_push(ring, Yrot, Ypos, Yvel, Yang, seg, c->bone_parents.p, xraw, eff, valid, streams, J, cs));
+               launch_live_push(ring, Yrot, Ypos, Yvel, Yang, seg, c->bone_parents.p, xraw, eff, valid, streams, J, cs, ing ? ing->have : nullptr));
         const int r = characterize(idx, idx_k, w_k, cs);
         if (r) return r;
         LAUNCH(c, cs, "mocha_pose_heads", "live.heads", 0.0, streams * (60.0 * 12 + V * 28.0 * 4), launch_pose_heads(ystage, heads, speed, streams, c->cfg.T, V, cs));
@@ -3004,7 +3019,8 @@ static int live_step_impl(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, i
     key.post = *cfg;
     key.soft_k = k; key.soft_t = k > 0 ? temperature : 0.f; key.soft[0] = k > 0 ? idx_k : nullptr; key.soft[1] = k > 0 ? w_k : nullptr;
     if (inert) { key.inert = inert; key.inert_halflife = icfg->halflife; key.inert_dt = icfg->dt; }
-    mocha_ctx::StepGraph& g = inert ? c->live_inert_step : k > 0 ? c->live_soft_step : c->live_step;
+    if (ing) { key.ingest[0] = ing->state; key.ingest[1] = ing->rot; key.ingest[2] = ing->pos; key.icfg = *ing_cfg; }
+    mocha_ctx::StepGraph& g = ing ? c->live_raw_step[inert ? 2 : k > 0 ? 1 : 0] : inert ? c->live_inert_step : k > 0 ? c->live_soft_step : c->live_step;
     if (!(g.exec && g.key == key && g.generation == c->generation)) {
         // Before a capture: one eager characterize of the staging windows with every id -1 (no bank row is matched, no state of the
         // session moves), so that whatever the kernels of the step make on first use - the plane GEMMs' weight images, for the soft step
@@ -3081,6 +3097,204 @@ int mocha_live_step_inert(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, i
     return live_step_impl(c, cfg, live, streams, Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, seg, cnt_mean, cnt_std, pos, rot,
                           ik_rot, bvh_pos, bvh_euler, idx, valid, k, k > 0 ? temperature : 0.f, k > 0 ? idx_k : nullptr, k > 0 ? w_k : nullptr,
                           stream, inert, &ic);
+}
+
+}  // extern "C"
+
+namespace {
+// The mocap front end's buffer (caller-owned device memory, private layout): per stream the kernel's state row, then the staging
+// mocha_live_step_raw hands to the live step.  Every section starts on a 256-byte boundary.
+struct IngestLayout {
+    size_t state, rot, pos, vel, ang, rvel, rang, speed, contact, have, bytes;
+};
+IngestLayout ingest_layout(const mocha_ctx* c, int S) {
+    const size_t J = (size_t)c->cfg.V + 1, n = (size_t)S;
+    IngestLayout l{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) / 256 * 256; return at; };
+    l.state = take(n * INGEST_STATE_DOUBLES * sizeof(double));
+    l.rot = take(n * J * 4 * sizeof(float));
+    l.pos = take(n * J * 3 * sizeof(float));
+    l.vel = take(n * J * 3 * sizeof(float));
+    l.ang = take(n * J * 3 * sizeof(float));
+    l.rvel = take(n * 3 * sizeof(float));
+    l.rang = take(n * 3 * sizeof(float));
+    l.speed = take(n * sizeof(float));
+    l.contact = take(n * MOCHA_MAX_CONTACT);
+    l.have = take(n * sizeof(int32_t));
+    l.bytes = off;
+    return l;
+}
+
+// rows of A (A^T A)^-1 A^T for the cubic Vandermonde matrix on the centred abscissae of a W-sample window, in long double
+void fit_rows(int W, double* out) {
+    std::vector<long double> A((size_t)W * 4);
+    for (int r = 0; r < W; ++r) {
+        const long double x = (long double)r - (long double)(W - 1) / 2;
+        A[r * 4] = 1; A[r * 4 + 1] = x; A[r * 4 + 2] = x * x; A[r * 4 + 3] = x * x * x;
+    }
+    long double M[4][8] = {};
+    for (int i = 0; i < 4; ++i) {
+        for (int j = 0; j < 4; ++j)
+            for (int r = 0; r < W; ++r) M[i][j] += A[r * 4 + i] * A[r * 4 + j];
+        M[i][4 + i] = 1;
+    }
+    for (int col = 0; col < 4; ++col) {                      // Gauss-Jordan with partial pivoting
+        int piv = col;
+        for (int r = col + 1; r < 4; ++r) if (std::fabs(M[r][col]) > std::fabs(M[piv][col])) piv = r;
+        for (int j = 0; j < 8; ++j) std::swap(M[col][j], M[piv][j]);
+        const long double d = M[col][col];
+        for (int j = 0; j < 8; ++j) M[col][j] /= d;
+        for (int r = 0; r < 4; ++r) {
+            if (r == col) continue;
+            const long double f = M[r][col];
+            for (int j = 0; j < 8; ++j) M[r][j] -= f * M[col][j];
+        }
+    }
+    for (int r = 0; r < W; ++r)
+        for (int q = 0; q < W; ++q) {
+            long double acc = 0;
+            for (int i = 0; i < 4; ++i) {
+                long double t = 0;
+                for (int j = 0; j < 4; ++j) t += M[i][4 + j] * A[q * 4 + j];
+                acc += A[r * 4 + i] * t;
+            }
+            out[(size_t)r * W + q] = (double)acc;
+        }
+}
+
+// the fit rows on the device, uploaded once: before any capture
+int ensure_ingest_rows(mocha_ctx* c) {
+    if (c->ingest_rows.p) return 0;
+    std::vector<double> rows(15 * 15 + 31 * 31);
+    fit_rows(15, rows.data());
+    fit_rows(31, rows.data() + 15 * 15);
+    int rc = reserve(c, c->ingest_rows, rows.size()); if (rc) return rc;
+    HIPCHK(c, hipMemcpy(c->ingest_rows.p, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// cfg and the toes of `post` (NULL = the demo's) checked and copied into the kernel's parameters; the caller adds the pointers
+int ingest_params(mocha_ctx* c, const char* who, const mocha_ingest_cfg* cfg, const mocha_post_cfg* post, IngestParams& p) {
+    if (!cfg) return fail(c, MOCHA_ERR_ARG, "%s: null ingest configuration", who);
+    mocha_post_cfg d;
+    if (!post) { mocha_post_cfg_default(&d); post = &d; }
+    PostParams pp{};
+    int rc = post_params(c, post, pp); if (rc) return rc;      // bone count, n_contact, the toes and their chains
+    const int V = c->cfg.V;
+    if (cfg->lookahead < 0 || cfg->lookahead > INGEST_MAX_LOOKAHEAD) return fail(c, MOCHA_ERR_ARG, "%s: lookahead must be 0..%d", who, INGEST_MAX_LOOKAHEAD);
+    if (cfg->rot_format < 0 || cfg->rot_format > 1) return fail(c, MOCHA_ERR_ARG, "%s: rot_format must be 0 (quaternions) or 1 (Euler degrees)", who);
+    int seen = 0;
+    for (int i = 0; i < 3; ++i) {
+        if (cfg->euler_order[i] < 0 || cfg->euler_order[i] > 2) return fail(c, MOCHA_ERR_ARG, "%s: euler_order must name the axes 0..2", who);
+        seen |= 1 << cfg->euler_order[i];
+    }
+    if (seen != 7) return fail(c, MOCHA_ERR_ARG, "%s: euler_order must be a permutation of 0..2", who);
+    if (!std::isfinite(cfg->unit_scale) || !std::isfinite(cfg->fps) || !std::isfinite(cfg->contact_velocity_threshold) || !(cfg->fps > 0.0))
+        return fail(c, MOCHA_ERR_ARG, "%s: unit_scale, fps and contact_velocity_threshold must be finite, fps positive", who);
+    const int roles[5] = {cfg->spine, cfg->shoulder_l, cfg->shoulder_r, cfg->upleg_l, cfg->upleg_r};
+    for (int i = 0; i < 5; ++i)
+        if (roles[i] < 0 || roles[i] >= V) return fail(c, MOCHA_ERR_ARG, "%s: role joint %d out of range 0..%d", who, roles[i], V - 1);
+    if (c->sk.parents[0] != -1) return fail(c, MOCHA_ERR_ARG, "%s: joint 0 must be the hips (no parent)", who);
+    for (int v = 1; v < V; ++v)
+        if (c->sk.parents[v] < 0 || c->sk.parents[v] >= v) return fail(c, MOCHA_ERR_ARG, "%s: joint %d does not follow its parent", who, v);
+    p.V = V; p.lookahead = cfg->lookahead; p.euler = cfg->rot_format;
+    for (int i = 0; i < 3; ++i) p.order[i] = cfg->euler_order[i];
+    for (int i = 0; i < 5; ++i) p.roles[i] = roles[i];
+    p.n_contact = pp.n_contact;
+    for (int i = 0; i < pp.n_contact; ++i) p.contact_bones[i] = pp.contact_bones[i];
+    for (int v = 0; v < V; ++v) p.parents[v] = c->sk.parents[v];
+    p.scale = cfg->unit_scale; p.fps = cfg->fps; p.threshold = cfg->contact_velocity_threshold;
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+void mocha_ingest_cfg_default(mocha_ingest_cfg* cfg, int layout) {
+    if (!cfg) return;
+    *cfg = mocha_ingest_cfg{};
+    cfg->lookahead = 0;
+    cfg->rot_format = 1;                                       // a BVH file's channels: Euler degrees, 'zyx'
+    cfg->euler_order[0] = 2; cfg->euler_order[1] = 1; cfg->euler_order[2] = 0;
+    cfg->unit_scale = 0.01;                                    // generate_database.py:91
+    cfg->fps = 60.0;                                           // :140
+    cfg->contact_velocity_threshold = 0.5;                     // :162
+    if (layout == 1) { cfg->spine = 3; cfg->shoulder_l = 6; cfg->shoulder_r = 10; cfg->upleg_l = 18; cfg->upleg_r = 14; }
+    else { cfg->spine = 7; cfg->shoulder_l = 9; cfg->shoulder_r = 16; cfg->upleg_l = 1; cfg->upleg_r = 20; }   // :102, :109-111
+}
+
+int64_t mocha_ingest_state_bytes(const mocha_ctx* c, int streams) {
+    if (!c || streams < 1 || streams > 16) return MOCHA_ERR_ARG;
+    return (int64_t)ingest_layout(c, streams).bytes;
+}
+
+int mocha_ingest_reset(mocha_ctx* c, void* ingest, int streams, const int32_t* which, int n, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (streams < 1 || streams > 16) return fail(c, MOCHA_ERR_ARG, "ingest_reset: 1 <= streams <= 16");
+    if (!ingest) return fail(c, MOCHA_ERR_ARG, "ingest_reset: null argument");
+    if (which && (n < 0 || n > streams)) return fail(c, MOCHA_ERR_ARG, "ingest_reset: n must be 0..streams");
+    for (int i = 0; which && i < n; ++i)
+        if (which[i] < 0 || which[i] >= streams) return fail(c, MOCHA_ERR_ARG, "ingest_reset: stream %d out of range 0..%d", (int)which[i], streams - 1);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    char* base = static_cast<char*>(ingest) + ingest_layout(c, streams).state;
+    const size_t row = INGEST_STATE_DOUBLES * sizeof(double);
+    if (!which) { HIPCHK(c, hipMemsetAsync(base, 0, row * streams, s)); return 0; }
+    for (int i = 0; i < n; ++i) HIPCHK(c, hipMemsetAsync(base + row * which[i], 0, row, s));
+    return 0;
+}
+
+int mocha_live_ingest_step(mocha_ctx* c, const mocha_ingest_cfg* cfg, const mocha_post_cfg* post, void* ingest, int streams, const float* rot,
+                           const float* pos, float* Yrot, float* Ypos, float* Yvel, float* Yang, float* src_rvel, float* src_rang,
+                           float* src_speed, unsigned char* contact, int32_t* have, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (streams < 1 || streams > 16) return fail(c, MOCHA_ERR_ARG, "live_ingest_step: 1 <= streams <= 16");
+    if (!ingest || !rot || !pos || !Yrot || !Ypos || !Yvel || !Yang || !src_rvel || !src_rang || !src_speed || !contact || !have)
+        return fail(c, MOCHA_ERR_ARG, "live_ingest_step: null argument");
+    IngestParams p{};
+    int rc = ingest_params(c, "live_ingest_step", cfg, post, p); if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = ensure_ingest_rows(c))) return rc;
+    p.state = reinterpret_cast<double*>(static_cast<char*>(ingest) + ingest_layout(c, streams).state);
+    p.rows15 = c->ingest_rows.p; p.rows31 = c->ingest_rows.p + 15 * 15;
+    p.rot = rot; p.pos = pos; p.Yrot = Yrot; p.Ypos = Ypos; p.Yvel = Yvel; p.Yang = Yang; p.src_rvel = src_rvel; p.src_rang = src_rang;
+    p.src_speed = src_speed; p.contact = contact; p.have = have;
+    hipStream_t s = (hipStream_t)stream;
+    const int V = c->cfg.V, J = V + 1;
+    LAUNCH(c, s, "mocha_live_ingest", "ingest.step", 0.0, (double)streams * (V * 7.0 * 4 + J * 13.0 * 4 + 40.0 * 4 * 8 + J * 16.0 * 13 * 8),
+           launch_live_ingest(p, streams, s));
+    return 0;
+}
+
+int mocha_live_step_raw(mocha_ctx* c, const mocha_post_cfg* cfg, const mocha_ingest_cfg* icfg_in, void* live, void* ingest, int streams,
+                        const float* rot, const float* pos, const int32_t* seg, const float* cnt_mean, const float* cnt_std, int k,
+                        float temperature, double* pos_out, double* rot_out, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx,
+                        int32_t* valid, int32_t* idx_k, float* w_k, void* stream, void* inert, const mocha_inert_cfg* icfg) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (streams < 1 || streams > 16) return fail(c, MOCHA_ERR_ARG, "live_step_raw: 1 <= streams <= 16");
+    if (!ingest || !rot || !pos) return fail(c, MOCHA_ERR_ARG, "live_step_raw: null argument");
+    if (k != 0) {
+        int rc = soft_args(c, "live_step_raw", k, temperature); if (rc) return rc;
+        if (!idx_k || !w_k) return fail(c, MOCHA_ERR_ARG, "live_step_raw: null argument");
+    }
+    mocha_inert_cfg ic{};
+    if (inert) { int rc = inert_cfg(c, "live_step_raw", icfg, ic); if (rc) return rc; }
+    IngestParams p{};
+    int rc = ingest_params(c, "live_step_raw", icfg_in, cfg, p); if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = ensure_ingest_rows(c))) return rc;
+    const IngestLayout l = ingest_layout(c, streams);
+    char* base = static_cast<char*>(ingest);
+    auto f32 = [&](size_t at) { return reinterpret_cast<float*>(base + at); };
+    p.state = reinterpret_cast<double*>(base + l.state);
+    p.rows15 = c->ingest_rows.p; p.rows31 = c->ingest_rows.p + 15 * 15;
+    p.rot = rot; p.pos = pos; p.Yrot = f32(l.rot); p.Ypos = f32(l.pos); p.Yvel = f32(l.vel); p.Yang = f32(l.ang);
+    p.src_rvel = f32(l.rvel); p.src_rang = f32(l.rang); p.src_speed = f32(l.speed);
+    p.contact = reinterpret_cast<unsigned char*>(base + l.contact); p.have = reinterpret_cast<int32_t*>(base + l.have);
+    return live_step_impl(c, cfg, live, streams, p.Yrot, p.Ypos, p.Yvel, p.Yang, p.src_rvel, p.src_rang, p.src_speed, p.contact, seg, cnt_mean,
+                          cnt_std, pos_out, rot_out, ik_rot, bvh_pos, bvh_euler, idx, valid, k, k > 0 ? temperature : 0.f, k > 0 ? idx_k : nullptr,
+                          k > 0 ? w_k : nullptr, stream, inert, inert ? &ic : nullptr, &p, icfg_in);
 }
 
 }  // extern "C"

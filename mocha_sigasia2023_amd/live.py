@@ -20,6 +20,7 @@ import torch
 from . import _C
 from .generator import DIM, NTOK, _dev_f32, _ptr, _stream
 from .multi_character import MultiCharacterBank, soft_params
+from .ingest import IngestConfig, reset_ingest
 from .postprocess import PostProcessor
 
 
@@ -30,10 +31,13 @@ class LiveSession:
     no pop when two entries are nearly equidistant; the outputs gain ``idx_k`` (S,k) and ``weight`` (S,k), ``idx`` is column 0.
     ``inertial=halflife`` (seconds): a stream that names another character does not pop - the jump of its pose heads becomes an offset
     that decays with that half-life (``mocha_live_step_inert``: the reference's inertializers, state and decision on the device, the frame
-    time taken from ``post``); a stream that never switches gets the bits of ``inertial=None``."""
+    time taken from ``post``); a stream that never switches gets the bits of ``inertial=None``.
+    ``raw=IngestConfig(...)`` or ``raw=lookahead``: the session also takes RAW mocap frames (``push_raw``: local rotations and positions of
+    the V joints) - the mocap front end (``ingest.py``, ``mocha_live_step_raw``) runs inside the same captured graph and produces what
+    ``push`` takes; a stream emits its first frame on its 31st raw push, so ``valid`` first becomes 1 on push 90."""
 
     def __init__(self, bank: MultiCharacterBank, cnt_mean, cnt_std, streams: int = 1, post: Optional[PostProcessor] = None, bvh: bool = True,
-                 soft=None, inertial: Optional[float] = None):
+                 soft=None, inertial: Optional[float] = None, raw=None):
         if not 1 <= int(streams) <= 16:
             raise ValueError("streams must be 1..16")
         self.bank, self.model = bank, bank.model
@@ -61,6 +65,16 @@ class LiveSession:
                 raise RuntimeError("mocha_inert_state_bytes failed")
             self.inert = torch.zeros((S, ibytes), dtype=torch.uint8, device=dev)   # zeroed = no stream has seen a frame
             self.icfg = _C.mocha_inert_cfg(float(inertial), float(self.post.cfg.dt))
+        self.raw = self.rcfg = self.ingest = None
+        if raw is not None:
+            self.raw = IngestConfig.of(raw)
+            self.rcfg = self.raw.struct(m)
+            rbytes = int(m._ctx.lib.mocha_ingest_state_bytes(m._ctx.h, S))
+            if rbytes <= 0:
+                raise RuntimeError("mocha_ingest_state_bytes failed")
+            self.ingest = torch.zeros((rbytes,), dtype=torch.uint8, device=dev)        # zeroed = no raw frame seen
+            self.raw_rot = torch.zeros((S, V, 3 if self.rcfg.rot_format == 1 else 4), dtype=torch.float32, device=dev)
+            self.raw_pos = torch.zeros((S, V, 3), dtype=torch.float32, device=dev)
 
         def f32(*shape):
             return torch.zeros(shape, dtype=torch.float32, device=dev)
@@ -110,6 +124,33 @@ class LiveSession:
         self.contact.copy_(ct.reshape(self.contact.shape), non_blocking=True)
         return self.replay()
 
+    def push_raw(self, rot, pos, characters=None):
+        """The new RAW frame of every stream (``raw=`` sessions): rot (S,V,3) Euler degrees in the configured order or (S,V,4) quaternions
+        (w,x,y,z), pos (S,V,3) in the configured unit, joint 0 the hips [, characters].  Returns what ``push`` returns; the frame behind
+        it is frame ``n-1-lookahead`` of the stream.  No host synchronisation."""
+        if self.raw is None:
+            raise RuntimeError("LiveSession.push_raw: the session was not created with raw=")
+        if characters is not None:
+            self.ids.copy_(self.bank._ids(characters, self.streams), non_blocking=True)
+        self._frame(rot, self.raw_rot, "rot")
+        self._frame(pos, self.raw_pos, "pos")
+        return self.replay_raw()
+
+    def replay_raw(self):
+        """The raw step on what ``raw_rot`` / ``raw_pos`` hold (a producer on the device may have written them in place)."""
+        if self.raw is None:
+            raise RuntimeError("LiveSession.replay_raw: the session was not created with raw=")
+        self.bank._ensure()
+        o = self.out
+        k, t = self.soft if self.soft is not None else (0, 0.0)
+        self.model._ctx.call("mocha_live_step_raw", C.byref(self.post.cfg), C.byref(self.rcfg), _ptr(self.live), _ptr(self.ingest), self.streams,
+                             _ptr(self.raw_rot), _ptr(self.raw_pos), _ptr(self.ids), _ptr(self.mean), _ptr(self.std), k, t, _ptr(o["pos"]),
+                             _ptr(o["rot"]), _ptr(o["ik_rot"]), _ptr(o["bvh_pos"]) if self.bvh else None,
+                             _ptr(o["bvh_euler"]) if self.bvh else None, _ptr(o["idx"]), _ptr(o["valid"]), _ptr(o.get("idx_k")),
+                             _ptr(o.get("weight")), _stream(), _ptr(self.inert) if self.inert is not None else None,
+                             C.byref(self.icfg) if self.icfg is not None else None)
+        return o
+
     def replay(self):
         """The step on what the fixed buffers hold (a producer on the device may have written them in place)."""
         self.bank._ensure()
@@ -146,7 +187,28 @@ class LiveSession:
             ids = [int(s) for s in streams]
             arr = (C.c_int32 * max(len(ids), 1))(*ids)
             ctx.call("mocha_live_reset", _ptr(self.live), self.streams, arr, len(ids), _stream())
+        if self.ingest is not None:
+            reset_ingest(self.model, self.ingest, self.streams, streams)
         return self
+
+    def run_clip_raw(self, rot, pos, characters=None):
+        """Convenience: pushes the F raw frames of every stream's clip - rot (S,F,V,3|4), pos (S,F,V,3) - into a RESET session and returns
+        the stacked valid frames: a dict of (S, F - 89, ...) tensors.  The last ``lookahead`` frames of the clip are not produced."""
+        dev = self.model.device
+        rot = torch.as_tensor(rot).to(device=dev, dtype=torch.float32)
+        pos = torch.as_tensor(pos).to(device=dev, dtype=torch.float32)
+        F = rot.shape[1]
+        if F < 90:
+            raise ValueError("run_clip_raw: a clip needs at least 90 frames")
+        self.reset()
+        keep = [k for k in self.out if k != "valid"]
+        frames = {k: [] for k in keep}
+        for f in range(F):
+            o = self.push_raw(rot[:, f], pos[:, f], characters if f == 0 else None)
+            if f >= 89:
+                for k in keep:
+                    frames[k].append(o[k].clone())
+        return {k: torch.stack(v, dim=1) for k, v in frames.items()}
 
     def run_clip(self, Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, characters=None):
         """Convenience: pushes the F frames of every stream's clip - Yrot (S,F,V+1,4), Ypos / Yvel / Yang (S,F,V+1,3); src_rvel /
@@ -189,7 +251,10 @@ class LiveOursSession(LiveSession):
 
     def __init__(self, bank: MultiCharacterBank, cnt_mean, cnt_std, cvae_state_dict, src_cnt_mean, src_cnt_std, cha_encoded_mean,
                  cha_encoded_std, streams: int = 1, post: Optional[PostProcessor] = None, bvh: bool = True, noise: str = "device",
-                 seed: int = 0, soft=None, inertial=None):
+                 seed: int = 0, soft=None, inertial=None, raw=None):
+        if raw is not None:
+            raise ValueError("LiveOursSession: raw= is not supported - the CVAE branch's step has no mocap front end; run an Ingestor and "
+                             "push its emitted frames")
         if inertial is not None:
             raise ValueError("LiveOursSession: inertial does not apply - the branch seeds again on a character switch and keeps its own chain state")
         if soft is not None:

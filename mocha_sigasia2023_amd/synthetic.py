@@ -117,3 +117,50 @@ def slide_windows(a: np.ndarray, window: int = 60, step: int = 1) -> np.ndarray:
     test_fullframework.py:128; preprocess/generate_database.py:65-84), as a contiguous copy."""
     v = np.lib.stride_tricks.sliding_window_view(a, window, axis=0)          # (F - w + 1, ..., w)
     return np.ascontiguousarray(np.moveaxis(v, -1, 1)[::step])
+
+
+def raw_walk_clip(parents, frames=100, seed=20231213, legs=((1, 2, 3, 4), (20, 21, 22, 23)), shoulders=(9, 16), spine=(5, 6, 7, 8), flip_bone=12, lean=9.0):
+    """A smooth walk as a BVH file would hold it: Euler degrees (frames, V, 3) in 'zyx' channel order and positions in centimetres
+    (frames, V, 3), both fp32.  ``legs``: the left and the right leg's joints, hip to toe; ``shoulders``: left, right.  The hips advance
+    at 0.7 m/s along a heading that turns from +15 to +110 degrees about y (never within 30 degrees of -z, which is 180); each leg
+    sweeps backwards at the hips' speed for 60 % of a 1.1 Hz cycle (its toe stands still on the ground) and swings forward in the rest;
+    ``flip_bone`` spins through more than a full turn about y, its angle wrapped into [-180, 180): the wrap is a sign flip for unroll to undo."""
+    V = len(parents)
+    rng = _rng(seed)
+    tt = np.arange(frames) / 60.0
+    off = rng.uniform(-1.0, 1.0, (V, 3)) * 4.0 + np.array([0.0, 8.0, 0.0])
+    for side, leg in zip((1.0, -1.0), legs):
+        off[leg[0]] = np.array([9.0 * side, -6.0, 0.0])
+        off[leg[1]] = np.array([0.0, -36.0, 0.0])
+        off[leg[2]] = np.array([0.0, -36.0, 0.0])
+        off[leg[3]] = np.array([0.0, -3.0, 10.0])
+    off[shoulders[0]] = np.array([7.0, 10.0, 0.0])
+    off[shoulders[1]] = np.array([-7.0, 10.0, 0.0])
+    pos = np.tile(off, (frames, 1, 1))
+    heading = 15.0 + 95.0 * (0.4 * (tt / tt[-1]) + 0.6 * (tt / tt[-1]) ** 1.5)
+    hr = np.radians(heading)
+    speed, cadence, stance, reach = 70.0, 1.1, 0.6, 0.75          # cm/s, Hz, fraction of the cycle on the ground, leg length (m)
+    x = np.cumsum(np.sin(hr) * speed / 60.0)
+    z = np.cumsum(np.cos(hr) * speed / 60.0)
+    pos[:, 0] = np.stack([x, 84.0 + 0.3 * np.cos(4.0 * np.pi * cadence * tt), z], axis=1)
+    rot = np.zeros((frames, V, 3))
+    for b in range(1, V):                                          # every free joint keeps turning: no angular velocity near zero
+        w = rng.uniform(0.4, 1.0, 3)
+        ph = rng.uniform(0, 2 * np.pi, 3)
+        rot[:, b] = 3.0 * np.sin(2 * np.pi * w[None] * tt[:, None] + ph[None]) + rng.uniform(25.0, 40.0, 3)[None] * tt[:, None]
+    rot[:, 0, 1] = heading + 2.0 * np.sin(2.0 * np.pi * cadence * tt)     # 'zyx' order: channel 1 is y; the pelvis swings about it
+    rot[:, 0, 0] = 1.0 * np.cos(2.0 * np.pi * cadence * tt)               # rolls a quarter cycle later
+    rot[:, 0, 2] = lean * tt                                              # and leans forward steadily: its angular velocity never vanishes
+    half = 0.5 * (speed / 100.0) * (stance / cadence) / reach      # sine of half the sweep that keeps the foot still during stance
+    for li, leg in enumerate(legs):
+        u = (cadence * tt + 0.5 * li) % 1.0
+        sweep = np.degrees(np.arcsin(half * np.where(u < stance, 2.0 * u / stance - 1.0, np.cos(np.pi * (u - stance) / (1.0 - stance)))))
+        for b in leg:
+            rot[:, b] = 0.0
+        rot[:, leg[0], 2] = sweep                                  # channel 2 is x: + puts the foot behind the hips
+        rot[:, leg[0], 1] = (20.0 - 40.0 * li) * tt                # a slow twist about the leg's own axis: the toe barely moves
+    for b in spine:                                                # the trunk twists the way the heading turns: the root keeps turning
+        rot[:, b] = 0.0
+        rot[:, b, 1] = 10.0 * tt
+    rot[:, flip_bone, 1] = (400.0 * tt / tt[-1] - 20.0 + 180.0) % 360.0 - 180.0   # wrapped as a file holds it: +179 -> -179 flips q
+    return rot.astype(np.float32), pos.astype(np.float32)

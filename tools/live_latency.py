@@ -19,6 +19,9 @@ mocha_profile_start / stop, during which the step runs eagerly.
         the plain live step and the inertialized one (LiveSession(inertial=H) = mocha_live_step_inert: one more launch, mocha_inertialize,
         between the pose heads and the post frame), alternating replay by replay in one process, S = 1 and S = 8; stream 0 switches
         character half-way through the warm-up, so the timed inertialized steps take the kernel's arithmetic path
+    python tools/live_latency.py --raw 2 [--out profiles/r13/live_raw_step.json]
+        the plain live step and the raw step (LiveSession(raw=L) = mocha_live_step_raw: one more launch, mocha_live_ingest, in front of
+        the ring push), alternating replay by replay in one process, S = 1 and S = 8, both past their warm-up
 """
 import argparse
 import json
@@ -194,6 +197,49 @@ def inertial(a, dev, model, mb, mean, std, clip, per, J):
     return res
 
 
+def raw(a, dev, model, mb, mean, std, clip, per, J):
+    """--raw L: the plain live step and the raw step (the mocap front end in the graph, L frames of lookahead), alternating in one process."""
+    from mocha_sigasia2023_amd import LiveSession
+    from mocha_sigasia2023_amd.skeleton import LAYOUTS
+    res = {"bank": "8 characters x 2048 rows, fp32, segmented", "layout": "mocha (24 joints)", "lookahead": a.raw,
+           "timing": "HIP events around single graph replays; (a) live step, (b) raw live step (mocap front end + live step), alternating",
+           "streams": {}}
+    walk = synthetic.raw_walk_clip(LAYOUTS["mocha"]["parents"], 644, seed=9)
+    wrot, wpos = torch.from_numpy(walk[0]).to(dev), torch.from_numpy(walk[1]).to(dev)
+    for S in (1, 8):
+        ids = torch.tensor([(k * 3) % 8 for k in range(S)], dtype=torch.int32)
+        plain, rs = LiveSession(mb, mean, std, streams=S), LiveSession(mb, mean, std, streams=S, raw=a.raw)
+        frame = [0]
+
+        def push():
+            f = frame[0] % 644; frame[0] += 1
+            plain.rot.copy_(clip[0][f]); plain.pos.copy_(clip[1][f]); plain.vel.copy_(clip[2][f]); plain.ang.copy_(clip[3][f])
+            plain.rvel.copy_(per[0][f]); plain.rang.copy_(per[1][f]); plain.speed.copy_(per[2][f]); plain.contact.copy_(per[3][f])
+            rs.raw_rot.copy_(wrot[f]); rs.raw_pos.copy_(wpos[f])
+        for sess in (plain, rs):
+            sess.characters.copy_(ids)
+        for _ in range(max(a.warmup, 100)):                                        # past both warm-ups: 60 and 90 pushes
+            push(); plain.replay(); rs.replay_raw()
+        torch.cuda.synchronize()
+        assert bool((rs.out["valid"] == 1).all()) and bool((plain.out["valid"] == 1).all())
+        ta, tb = [], []
+        for _ in range(a.reps):
+            push(); torch.cuda.synchronize()
+            ta.append(event_ms(plain.replay, 1)[0]); tb.append(event_ms(rs.replay_raw, 1)[0])
+        e = {"a_live_step": pct(np.asarray(ta)), "b_live_step_raw": pct(np.asarray(tb))}
+        e["b_minus_a_p50_ms"] = e["b_live_step_raw"]["p50_ms"] - e["a_live_step"]["p50_ms"]
+        n = 200                                          # the step's own launches, one at a time (eager while profiling)
+        model.profile_start()
+        for _ in range(n):
+            rs.replay_raw()
+        prof = model.profile_stop()
+        e["sites_us"] = {k: 1e3 * v["ms"] / v["launches"] for k, v in prof["sites"].items() if k.split("|")[0] in ADDED + ("live.ingest",)}
+        assert bool(torch.isfinite(rs.out["pos"]).all())
+        res["streams"][str(S)] = e
+        del plain, rs
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=1000)
@@ -203,7 +249,10 @@ def main():
     ap.add_argument("--ours", action="store_true", help="the CVAE branch: live step / live step with the branch / the route without the live step")
     ap.add_argument("--soft", type=int, default=0, metavar="K", help="soft matching: live step / soft live step with K neighbours, temperature 2")
     ap.add_argument("--inertial", type=float, default=None, metavar="H", help="inertialized switches: live step / live step with half-life H seconds")
+    ap.add_argument("--raw", type=int, default=None, metavar="L", help="raw mocap input: live step / raw live step with L frames of lookahead")
     a = ap.parse_args()
+    if a.raw is not None and a.out == ap.get_default("out"):
+        a.out = os.path.join(ROOT, "profiles", "r13", "live_raw_step.json")
     if a.inertial is not None and a.out == ap.get_default("out"):
         a.out = os.path.join(ROOT, "profiles", "r12", "live_inert_step.json")
     if a.soft and a.out == ap.get_default("out"):
@@ -229,6 +278,8 @@ def main():
     per = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (rvel, rang, np.linalg.norm(hipvel, axis=-1).mean(-1).astype(np.float32), contact)]
     res = {"bank": "8 characters x 2048 rows, fp32, segmented", "layout": "mocha (24 joints)", "timing": "HIP events around single graph replays, live and baseline alternating",
            "streams": {}}
+    if a.raw is not None:
+        return write_out(a, raw(a, dev, model, mb, mean, std, clip, per, J))
     if a.inertial is not None:
         return write_out(a, inertial(a, dev, model, mb, mean, std, clip, per, J))
     if a.soft:
