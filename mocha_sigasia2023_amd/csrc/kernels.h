@@ -279,6 +279,25 @@ hipError_t launch_column_stats(const float* x, int64_t N, int cols, float* mean,
 // bank row squared norms
 hipError_t launch_rownorm2(const float* x, const float* sub /*or null*/, float* out, int64_t rows, int cols, hipStream_t s, int reverse = 0);
 hipError_t launch_sub_rows(const float* x, const float* sub, float* out, int64_t rows, int cols, hipStream_t s);
+// ---------------------------------------------------------------------------------------
+// Context matching.  Every path is a cheap coarse stage, a pruning rule and an exact re-rank; the result is exact as long as the coarse
+// stage's error stays inside the bound the rule assumes (stated with each kernel; held stage by stage by tests/test_match_kernels.py).
+// What the kernels rely on and no launcher checks (tests/gemm_probe/match_probe.cpp refuses it before a launch):
+//   pointers: every operand non-null and sized as stated; launch_to_bf16: x, sub 16-byte and y 8-byte aligned; launch_center_bf16: x,
+//   centre, out 16-byte aligned; inputs finite (the bf16 conversions do not look for NaN);
+//   coarse passes (launch_match_gemm_bf16, launch_match_pass256): qc16, bank16 and an image 16-byte aligned; S 16-byte aligned when
+//   N % 4 == 0 (its stores are then 16 bytes); with planes = 2 the second plane EXACTLY Q * D elements after the first; the image of the full
+//   match_tiled_elems / match_tile32_elems size (rows past N are part of it); tickets all zero at first use (they are left at zero);
+//   K slice z covers the 64-k steps [z * per, (z + 1) * per) cut at D / 64, per = ceil(D / 64 / ksplit): a slice past the end is empty and its slab
+//   is written as zeros; S is ksplit slabs of Q * N floats, every element of every slab written, nothing else;
+//   selections (launch_match_select, launch_match_select2): exactly one of bank / bank16; query, centre and the bank 16-byte aligned (centre
+//   is read in both bank modes by launch_match_select); lds >= N and slab_stride >= (Q - 1) * lds + N (ksplit > 1); S and bnorm 16-byte aligned
+//   where lds, N and slab_stride are all multiples of 4 (the 16-byte score path; otherwise scalar loads); D >= 256 (D = 0 passes D % 256
+//   and would read in front of the centre); NaN scores never qualify; a query without any finite score gets row 0, dist NaN from
+//   launch_match_select2 and row 0's direct-form distance from launch_match_select;
+//   few-query scans: rho / rho8 must be UPPER bounds of the copies' residual norms (an underestimate silently drops true winners); the
+//   first match_scan16_scratch_head_words() words of the scratch zero at first use.
+// ---------------------------------------------------------------------------------------
 // many-query matcher (match_mfma.hip): centred bf16 queries, one-plane bf16 coarse scores S[z][q][n] (K split z), and the
 // select kernel: per query, EVERY row whose coarse score ||b-c||^2 - 2 S lies within margin_rel * (2||q-c||^2 + ||b-c||^2 +
 // ||b0-c||^2) of the best one (margin_rel >= 0 bounds the coarse pass's error; a negative value is rejected) is re-evaluated
@@ -313,7 +332,8 @@ hipError_t launch_match_select(const float* S, int ksplit, long long slab_stride
 // the same selection without the usually unnecessary work (match_select2.hip): the row statistics of the error bound come from the
 // producer of the centred queries (qstat: 2 x QSTAT_PARTS floats per query - launch_center_rows, InormExtra::qstat), nothing is staged in LDS, and a
 // query whose coarse minimum stands alone is answered without touching a bank row when dist == nullptr.  Otherwise the same arguments,
-// bounds and result semantics as launch_match_select.
+// bounds and result semantics as launch_match_select, but for a query without any finite score: row 0 from both, dist NaN here, row 0's
+// direct-form distance there.
 hipError_t launch_match_select2(const float* S, int ksplit, long long slab_stride, int lds, const float* bnorm, const float* query,
                                 const float* centre, const float* bank, const void* bank16, const float* qstat, float margin_rel, int Q,
                                 int64_t N, int D, int32_t* idx, float* dist, hipStream_t s);

@@ -499,7 +499,7 @@ __global__ __launch_bounds__(SEL_T) void mocha_match_select(const float* __restr
     const unsigned nmin = (unsigned)(r_key & 0xffffffffull);
     const unsigned umin = (unsigned)(r_key >> 32);
     const float vmin = __uint_as_float((umin & 0x80000000u) ? (umin & 0x7fffffffu) : ~umin);
-    const bool none = !(vmin < INFINITY);                        // no finite score at all (NaN / inf inputs): row 0, distance NaN / inf
+    const bool none = !(vmin < INFINITY);                        // no finite score at all: row 0, which is evaluated like a candidate - its direct-form distance (NaN / inf if the inputs are)
     const float bmin = none ? 0.f : bnorm[nmin];
     const float base = 2.f * r_qn + bmin;
     // bf16 bank: the coarse score of row n differs from the exact one by 2 |sum dq_i b_ni| <= 2 ||dq|| ||b_n - c|| (Cauchy-Schwarz with the

@@ -24,7 +24,7 @@ static constexpr int MS_CHUNK_I8 = 2560;        // elements of every query stage
 // rows (x - centre) -> biased bytes + scale + residual bound; one workgroup per row
 __global__ __launch_bounds__(256) void mocha_to_i8(const float* __restrict__ x, const float* __restrict__ centre, unsigned char* __restrict__ y,
                                                    float* __restrict__ scale, float* __restrict__ rho, int cols) {
-    __shared__ float red[3][4];
+    __shared__ float red[5][4];
     __shared__ float s_inv, s_s;
     const size_t row = blockIdx.x;
     const int tid = threadIdx.x;
@@ -41,7 +41,11 @@ __global__ __launch_bounds__(256) void mocha_to_i8(const float* __restrict__ x, 
     }
     __syncthreads();
     const float s = s_s, inv = s_inv;
-    float a = 0.f, nn = 0.f;
+    // small rows are summed a second time scaled by 2^64, in the same pass, and those sums are used when ||x - c||^2 < 2^-40 (mocha_rowresid,
+    // match_stream.hip, says why): at 1e-30 the squares flush to zero and rho came out as 0, an underestimate; from 1e-15 down they are
+    // denormal (tests/test_match_kernels.py, family 1, "tiny" and "small")
+    constexpr float UP = 0x1p64f, DOWN = 0x1p-64f, SMALL2 = 0x1p-40f;
+    float a = 0.f, nn = 0.f, as = 0.f, ns = 0.f;
     for (int i = tid; i < cols; i += 256) {
         const float t = x[row * cols + i] - centre[i];
         float q = rintf(t * inv);
@@ -49,15 +53,21 @@ __global__ __launch_bounds__(256) void mocha_to_i8(const float* __restrict__ x, 
         y[row * cols + i] = (unsigned char)(int)(q + 128.f);
         const float d = t - s * q;              // s * q: ONE rounding - the value the scan rebuilds as fma(u8, s, -128 s)
         a = fmaf(d, d, a); nn = fmaf(t, t, nn);
+        const float du = d * UP, tu = t * UP;
+        as = fmaf(du, du, as); ns = fmaf(tu, tu, ns);
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o); nn += __shfl_xor(nn, o); }
-    if ((tid & 63) == 0) { red[1][tid >> 6] = a; red[2][tid >> 6] = nn; }
+    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o); nn += __shfl_xor(nn, o); as += __shfl_xor(as, o); ns += __shfl_xor(ns, o); }
+    if ((tid & 63) == 0) { red[1][tid >> 6] = a; red[2][tid >> 6] = nn; red[3][tid >> 6] = as; red[4][tid >> 6] = ns; }
     __syncthreads();
     if (tid == 0) {
         const float r2 = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]), n2 = (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]);
         scale[row] = s;
-        rho[row] = sqrtf(r2) * 1.000001f + 1e-6f * sqrtf(n2);
+        if (n2 >= SMALL2) rho[row] = sqrtf(r2) * 1.000001f + 1e-6f * sqrtf(n2);
+        else {
+            const float r2s = (red[3][0] + red[3][1]) + (red[3][2] + red[3][3]), n2s = (red[4][0] + red[4][1]) + (red[4][2] + red[4][3]);
+            rho[row] = (sqrtf(r2s) * DOWN) * 1.000001f + 1e-6f * (sqrtf(n2s) * DOWN);
+        }
     }
 }
 

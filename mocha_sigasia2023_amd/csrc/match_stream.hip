@@ -179,23 +179,41 @@ hipError_t launch_match_topk(const void* bank, int bank_bf16, const float* query
 static constexpr int RF_T = 1024, RF_W = RF_T / 64, RF_CAP = 4096, RF_SPLIT = 64;
 static constexpr int S8_DEGENERATE = 12;           // candidates in one slice (1 / RF_SPLIT of the rows) beyond which the byte image is not worth scanning (~770 in all)
 
+// rho[row] >= ||(x - c) - b16|| in exact arithmetic (the refine's pruning rests on it), and no looser than the formula says:
+//   * the residual is taken from the EXACT x - c: t = fl(x - c) carries up to 2^-24 |t| of rounding, which a row with one large entry (1e4
+//     among unit ones) shows as 3e-5 of its residual norm; e = (x - c) - t is recovered with the two-sum and added to t - b16, which is exact
+//     (tests/test_match_kernels.py, family 1, "outlier");
+//   * small rows are summed a second time scaled by 2^64, in the same pass, and those sums are used when ||x - c||^2 < 2^-40 (they stay
+//     below 2^88).  At 1e-30 d^2 and t^2 flush to zero and rho came out as 0, an underestimate ("tiny"); from 1e-15 down the d^2 are
+//     denormal ("small").  Above the switch a d^2 below the normal range means |d| < 1.1e-19: all such terms together are worth less than
+//     1e-19 sqrt(cols) of residual norm against a slack of 1e-6 ||x - c|| >= 1e-12, so nothing rests on denormals being kept.
 __global__ __launch_bounds__(256) void mocha_rowresid(const float* __restrict__ x, const float* __restrict__ centre,
                                                       const unsigned short* __restrict__ x16, float* __restrict__ rho, int cols) {
-    __shared__ float red[2][4];
+    __shared__ float red[4][4];
     const size_t row = blockIdx.x;
-    float a = 0.f, nn = 0.f;
+    constexpr float UP = 0x1p64f, DOWN = 0x1p-64f, SMALL2 = 0x1p-40f;
+    float a = 0.f, nn = 0.f, as = 0.f, ns = 0.f;
     for (int i = threadIdx.x; i < cols; i += 256) {
-        const float t = x[row * cols + i] - centre[i];
-        const float d = t - __uint_as_float((unsigned)x16[row * cols + i] << 16);
+        const float xv = x[row * cols + i], nc = -centre[i];
+        const float t = xv + nc;
+        const float bp = t - xv;
+        const float e = (xv - (t - bp)) + (nc - bp);                  // (x - c) - t, exactly
+        const float d = (t - __uint_as_float((unsigned)x16[row * cols + i] << 16)) + e;
         a = fmaf(d, d, a); nn = fmaf(t, t, nn);
+        const float du = d * UP, tu = t * UP;
+        as = fmaf(du, du, as); ns = fmaf(tu, tu, ns);
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o); nn += __shfl_xor(nn, o); }
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = nn; }
+    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o); nn += __shfl_xor(nn, o); as += __shfl_xor(as, o); ns += __shfl_xor(ns, o); }
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = nn; red[2][threadIdx.x >> 6] = as; red[3][threadIdx.x >> 6] = ns; }
     __syncthreads();
     if (threadIdx.x == 0) {
         const float r2 = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]), n2 = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-        rho[row] = sqrtf(r2) * 1.000001f + 1e-6f * sqrtf(n2);
+        if (n2 >= SMALL2) rho[row] = sqrtf(r2) * 1.000001f + 1e-6f * sqrtf(n2);
+        else {
+            const float r2s = (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]), n2s = (red[3][0] + red[3][1]) + (red[3][2] + red[3][3]);
+            rho[row] = (sqrtf(r2s) * DOWN) * 1.000001f + 1e-6f * (sqrtf(n2s) * DOWN);
+        }
     }
 }
 
