@@ -73,6 +73,12 @@ hipError_t launch_pose_heads(const float* Y, float* heads, float* speed, int B, 
 }
 
 // ----------------------------------------------------------------------------------------------- clip loop (float64)
+// cross product of two vectors that may be the SAME vector, without fused multiply-adds: fma(a.y, b.z, -(a.z * b.y)) leaves the rounding
+// error of one product where a x a is exactly 0, and normalize() divides that 1e-17 by its eps of 1e-8
+__device__ inline d3 cross_unfused(d3 a, d3 b) {
+#pragma clang fp contract(off)
+    return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+}
 struct ContactRec {
     bool state, lock;
     d3 position, velocity, point, target, off_x, off_v;
@@ -301,7 +307,9 @@ __global__ __launch_bounds__(64) void mocha_post_clip(PostParams p) {
                 const dq r0 = from_angle_axis(ac_ab_1 - ac_ab_0, axis_rot);
                 const dq r1 = from_angle_axis(ba_bc_1 - ba_bc_0, axis_rot);
                 const d3 c_a = normalize(e - a), t_a = normalize(t - a);
-                const dq r2 = from_angle_axis(acos(clamp1(dot(c_a, t_a))), normalize(cross(c_a, t_a)));
+                // a contact that has not locked yet has its target ON the heel: c_a and t_a may be the same bits (whenever toe + (heel - toe)
+                // rounds to the heel), and their cross product then has to be the exact 0 the reference gets - r2 turns nothing
+                const dq r2 = from_angle_axis(acos(clamp1(dot(c_a, t_a))), normalize(cross_unfused(c_a, t_a)));
                 stq(&sh_ikq[ci][0][0], qmul(qinv(gr[4]), qmul(r2, qmul(r0, gr[3]))));          // the hip's (chain[3])
                 stq(&sh_ikq[ci][1][0], qmul(qinv(gr[3]), qmul(r1, gr[2])));                    // the knee's (chain[2])
                 sh_ikv[ci] = 1;
