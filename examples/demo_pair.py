@@ -8,6 +8,15 @@
 The reference's data (BVH clips, norm.npz, checkpoints) is not redistributable, so weights, norms and motions are synthetic;
 with real assets replace `synthetic_state_dict` by torch.load(ckpt)['gen_ema'], the norms by norm.npz / cnt_norm.npz /
 cvae_norm.npz and the bone features by the output of the reference's process_data (motion/bvh.py + preprocess).
+
+With --from-raw both clips start as RAW mocap (synthetic.raw_walk_clip: Euler degrees and centimetres per joint, as a BVH file holds them)
+and the reference's clip preparation runs on the device as well:
+
+    raw clip  --ingest_clips-->  root bone, velocities, contacts  --clip_windows-->  60-frame windows  --featurize-->  X_raw  --> as above
+
+The source's per-window inputs of the post-processing are then its own: root-local velocities of each window's last frame, the mean hip
+speed of the window, the contacts of its last frame (test_fullframework.py:142-143, :493).  The pair call's output and the windows are
+also written to <out>/from_raw.npz.
 """
 import argparse
 import os
@@ -26,6 +35,7 @@ from mocha_sigasia2023_amd.skeleton import LAYOUTS  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--frames", type=int, default=120, help="windows per clip (the demo clips have 585)")
 ap.add_argument("--out", default="gpurun_out/demo")
+ap.add_argument("--from-raw", action="store_true", help="start from raw mocap clips: ingest_clips -> clip_windows -> featurize")
 a = ap.parse_args()
 os.makedirs(a.out, exist_ok=True)
 dev = torch.device("cuda:0")
@@ -44,10 +54,29 @@ stats = [(0.1 * rng.standard_normal((90, 256))).astype(np.float32), rng.uniform(
          (0.1 * rng.standard_normal((90, 256))).astype(np.float32), rng.uniform(0.5, 1.5, (90, 256)).astype(np.float32)]
 
 # ---- the two clips as local bone features of N sixty-frame windows each                      :120-140, 203-222
-src_bones = synthetic.bone_windows(11, N)
-cha_bones = synthetic.bone_windows(12, N)
-_, rvel, rang, hipvel, contact = synthetic.postprocess_inputs(5, N)           # root-local velocities / contacts of the source
-src_speed = np.linalg.norm(hipvel, axis=-1).mean(-1).astype(np.float32)
+if a.from_raw:
+    from mocha_sigasia2023_amd import clip_windows, ingest_clips  # noqa: E402
+    if N < 16:
+        ap.error("--from-raw needs at least 16 windows per clip: a clip of N + 15 frames gives N windows, and 31 frames are the least")
+    raw = [synthetic.raw_walk_clip(LAYOUTS["mocha"]["parents"], N + 15, seed=s) for s in (11, 12)]        # source, character
+    clips = ingest_clips(model, np.concatenate([r for r, _ in raw]), np.concatenate([p for _, p in raw]), [N + 15, N + 15])
+    win = clip_windows(clips, [N + 15, N + 15], window=60, step=1)      # N windows per clip, the last 44 padded
+    src_bones = tuple(win[k][:N] for k in ("Yrot", "Ypos", "Yvel", "Yang"))
+    cha_bones = tuple(win[k][N:] for k in ("Yrot", "Ypos", "Yvel", "Yang"))
+    rot0, vel0, ang0 = (win[k][:N, -1, 0].double().cpu().numpy() for k in ("Yrot", "Yvel", "Yang"))
+
+    def inv_mul_vec(q, v):                                                     # quat.inv_mul_vec
+        u = -q[:, 1:]
+        t = 2.0 * np.cross(u, v)
+        return v + q[:, :1] * t + np.cross(u, t)
+    rvel, rang = inv_mul_vec(rot0, vel0).astype(np.float32), inv_mul_vec(rot0, ang0).astype(np.float32)
+    src_speed = win["Yvel"][:N, :, 1].norm(dim=-1).mean(-1).cpu().numpy()
+    contact = win["contact"][:N, -1].cpu().numpy()
+else:
+    src_bones = synthetic.bone_windows(11, N)
+    cha_bones = synthetic.bone_windows(12, N)
+    _, rvel, rang, hipvel, contact = synthetic.postprocess_inputs(5, N)       # root-local velocities / contacts of the source
+    src_speed = np.linalg.norm(hipvel, axis=-1).mean(-1).astype(np.float32)
 
 torch.cuda.synchronize(); t0 = time.perf_counter()
 src_X = model.featurize(*src_bones)                                            # :141-185 on the device
@@ -67,6 +96,9 @@ ours = retarget_clip_ours(sess, src_enc[1:], src_cnt[1:], rvel[1:], rang[1:], sr
                           denorm=(Y_mean[1:], Y_std[1:]))
 torch.cuda.synchronize(); dt = time.perf_counter() - t0
 
+if a.from_raw:
+    np.savez(os.path.join(a.out, "from_raw.npz"), Y=Y.cpu().numpy(), idx=idx.cpu().numpy(), contact=contact, src_speed=src_speed,
+             **{"src_" + k: v.cpu().numpy() for k, v in zip(("Yrot", "Ypos", "Yvel", "Yang"), src_bones)})
 names = ["Joint%02d" % i for i in range(24)]
 parents = LAYOUTS["mocha"]["parents"]
 write_bvh(os.path.join(a.out, "cm_trans.bvh"), names, parents, nn["bvh_pos"], nn["bvh_euler"])          # :690-713

@@ -555,7 +555,8 @@ int mocha_live_step_ours(mocha_ctx* ctx, const mocha_post_cfg* cfg, void* live, 
  * :493; 0 until 60 were emitted) are evaluated in float64 on the emitted fp32 values and rounded once: the demo evaluates them in fp32
  * NumPy, so they may sit one fp32 ulp away from its values.  Everything else is float64 on the fp32 inputs, rounded to fp32 once.
  * Inherited from the reference, not fixed: between([0,0,1], d) is singular for a character facing exactly -z; contacts flip at a hard
- * threshold.  Not provided: the last `lookahead` frames of a clip are never emitted (no flush), no mirroring, no BVH text parsing.
+ * threshold.  A stream never emits the last `lookahead` frames of a clip and does not mirror: whole clips, mirrored or not, go through
+ * mocha_ingest_clips below, which emits every frame.  Not provided: BVH text parsing.
  *   mocha_ingest_cfg_default : the reference's constants (lookahead 0, Euler degrees in 'zyx' channel order, unit scale 0.01: cm -> m,
  *                            60 frames per second, threshold 0.5 m/s) and the role joints of `layout`: 0 ('mocha': Spine2 = 7, shoulders
  *                            9 / 16, upper legs 1 / 20), 1 ('mixamo' of this library's 22-joint table: 3, 6 / 10, 18 / 14).
@@ -597,6 +598,47 @@ int mocha_live_step_raw(mocha_ctx* ctx, const mocha_post_cfg* cfg, const mocha_i
                         float temperature, double* pos_out, double* rot_out, double* ik_rot, double* bvh_pos, double* bvh_euler,
                         int32_t* idx, int32_t* valid, int32_t* idx_k, float* w_k, void* stream, void* inert,
                         const mocha_inert_cfg* icfg);
+
+/* WHOLE clips through the same preparation, parallel over frames: process_data (preprocess/generate_database.py:86-177) with mirror =
+ * False / True and divide_clip(divide=True) (:57-84), the first link of raw clip -> database.bin -> bank (generate_database_bin.py:96-208)
+ * and of raw clip pair -> windows -> mocha_characterize_pair.  Every frame of a clip is emitted, frame 0 and the last included: the fits'
+ * first / last window rows (savgol_filter mode='interp'), v[0] = v[1] - (v[3] - v[2]), v[-1] = v[-2] + (v[-2] - v[-3]), the median
+ * filter's 'nearest' padding.  Float64 on the fp32 inputs, rounded to fp32 once at the output, as mocha_live_ingest_step.
+ *   mocha_ingest_clips     : n_clips clips concatenated along the frame axis, clip c = frames clip_offsets[c] .. clip_offsets[c+1]-1 (host
+ *                            array of n_clips + 1 values, clip_offsets[0] = 0); nothing crosses a clip boundary.  rot (F,V,4) quaternions
+ *                            w,x,y,z or (F,V,3) Euler degrees (cfg->rot_format, cfg->euler_order), pos (F,V,3); cfg->lookahead is ignored.
+ *                            mirror_flags (n_clips, host, or NULL): a clip with a non-zero flag goes through animation_mirror
+ *                            (generate_database.py:40-55: forward kinematics, mirror_pos * gpos[map], from_xform(mirror_rot *
+ *                            to_xform(grot[map])) with the four branches of quat.py:69-94, quat.ik) and a second quat.unroll (:95) first;
+ *                            mirror_map (V, host): the joint exchange, map[map[v]] == v.  Outputs, root bone first: out_pos / out_vel /
+ *                            out_ang (F,V+1,3), out_rot (F,V+1,4) fp32, out_contact (F,n_contact) uint8.  quat.unroll (quat.py:135-141)
+ *                            runs as a parity scan per (clip, joint); six launches, eight with a mirrored clip.
+ *                            NOT capture-safe: the call copies its tables to the device and waits for `stream` once before its launches,
+ *                            and it may (re)allocate the context's float64 clip workspace (about 90 (V+1) bytes per frame, grow-only, does
+ *                            not move mocha_generation()).
+ *   mocha_clip_window_count: counts[c] = the windows divide_clip cuts from clip c: j = 0, step, 2 step, ... < n - window / 4 (:67).  Host
+ *                            only; MOCHA_ERR_ARG for a NULL pointer, window < 4, step < 1 or offsets that do not increase.
+ *   mocha_clip_windows     : the gather, ONE launch: window b of a clip starts at frame j = b * step of it; a slice of m < window frames
+ *                            is padded on the left with (window-m)/2 + (window-m)%2 copies of its first frame and on the right with
+ *                            (window-m)/2 copies of its last (:69-77), padding frames of vel / ang zero.  Inputs as mocha_ingest_clips
+ *                            writes them; outputs Yrot (B,window,V+1,4), Ypos / Yvel / Yang (B,window,V+1,3) as mocha_featurize takes
+ *                            them and Ycontact (B,window,n_contact), B = the sum of mocha_clip_window_count, clip after clip.
+ *                            divide=False is not provided.  Not capture-safe, as above.
+ *   mocha_mirror_map_default: the left / right exchange of `layout`: 0 ('mocha': Left* / Right* of the 24 joint names, legs 1-4 / 20-23,
+ *                            arms 9-12 / 16-19), 1 ('mixamo' of this library's 22-joint table: arms 6-9 / 10-13, legs 14-17 / 18-21).
+ * Refusals (MOCHA_ERR_ARG, nothing launched): everything mocha_live_ingest_step refuses (the lookahead apart); a clip shorter than 31 frames
+ * (savgol_filter(window_length=31) raises there); clip_offsets that do not start at 0 or do not increase; a mirror flag set while
+ * mirror_map is NULL; a mirror_map that is no involution or does not commute with the parents; window < 4 or step < 1.
+ * Inherited from the reference: the singular -z heading; contacts flip at a hard threshold (generate_database_bin.py uses 0.2 m/s,
+ * process_data 0.5: cfg->contact_velocity_threshold).  Not provided: BVH text parsing. */
+int mocha_ingest_clips(mocha_ctx* ctx, const mocha_ingest_cfg* cfg, const mocha_post_cfg* post, const float* rot, const float* pos,
+                       const int32_t* clip_offsets, int n_clips, const int32_t* mirror_map, const unsigned char* mirror_flags,
+                       float* out_pos, float* out_vel, float* out_rot, float* out_ang, unsigned char* out_contact, void* stream);
+int mocha_clip_window_count(const int32_t* clip_offsets, int n_clips, int window, int step, int64_t* counts);
+int mocha_clip_windows(mocha_ctx* ctx, const float* pos, const float* vel, const float* rot, const float* ang,
+                       const unsigned char* contact, int n_contact, const int32_t* clip_offsets, int n_clips, int window, int step,
+                       float* Yrot, float* Ypos, float* Yvel, float* Yang, unsigned char* Ycontact, void* stream);
+int mocha_mirror_map_default(int layout, int32_t* map);
 
 /* Bank build statistics: cnt_mean, cnt_std = np.mean(cnt, 0), np.std(cnt, 0) over the N bank entries
  * (compute_cnt_norm.py:174-175; population std), x (N, 90*256) -> mean, std (90*256). */

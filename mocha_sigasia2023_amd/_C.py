@@ -113,7 +113,11 @@ SIGNATURES = {
     "mocha_ingest_reset": (_i, [_vp, _vp, _i, C.POINTER(C.c_int32), _i, _vp]),
     "mocha_live_ingest_step": (_i, [_vp, _vp, _vp, _vp, _i] + [_vp] * 12),
     "mocha_live_step_raw": (_i, [_vp, _vp, _vp, _vp, _vp, _i] + [_vp] * 5 + [_i, C.c_float] + [_vp] * 12),
-    "mocha_set_rccl_library": (_i, [C.c_char_p]),
+    "mocha_ingest_clips": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), C.POINTER(C.c_ubyte)] + [_vp] * 6),
+    "mocha_clip_window_count": (_i, [C.POINTER(C.c_int32), _i, _i, _i, C.POINTER(_i64)]),
+    "mocha_clip_windows": (_i, [_vp] * 6 + [_i, C.POINTER(C.c_int32), _i, _i, _i] + [_vp] * 6),
+    "mocha_mirror_map_default": (_i, [_i, C.POINTER(C.c_int32)]),
+    "mocha_set_rccl_library":(_i, [C.c_char_p]),
     "mocha_comm_unique_id": (_i, [_vp, _vp]),
     "mocha_comm_init": (_i, [_vp, _vp, _i, _i]),
     "mocha_comm_destroy": (_i, [_vp]),

@@ -8,7 +8,7 @@ from .multi_character import MultiCharacterBank, MultiStreamCharacterizer  # noq
 from .bank import BatchPipeline, ShardedContextBank, build_bank, load_bank, save_bank  # noqa: F401
 from .postprocess import Inertializer, PostProcessor, pose_heads, retarget_clip, retarget_clip_ours, retarget_frame_ours, write_bvh  # noqa: F401
 from .live import LiveOursSession, LiveSession  # noqa: F401
-from .ingest import IngestConfig, Ingestor  # noqa: F401
+from .ingest import IngestConfig, Ingestor, clip_windows, ingest_clips  # noqa: F401
 from .skeleton import skeleton_constants  # noqa: F401
 from . import synthetic  # noqa: F401
 from .weights import DEFAULT_CFG, param_shapes, synthetic_state_dict  # noqa: F401
@@ -16,4 +16,4 @@ from .weights import DEFAULT_CFG, param_shapes, synthetic_state_dict  # noqa: F4
 __all__ = ["Generator", "CVAE", "OursSession", "ContextBank", "StreamingCharacterizer", "mean_variance_norm", "skeleton_constants",
            "synthetic_state_dict", "param_shapes", "DEFAULT_CFG", "build_bank", "save_bank", "load_bank", "ShardedContextBank", "BatchPipeline",
            "PostProcessor", "pose_heads", "MultiCharacterBank", "MultiStreamCharacterizer", "retarget_clip", "retarget_clip_ours", "retarget_frame_ours", "write_bvh",
-           "LiveSession", "LiveOursSession", "Inertializer", "Ingestor", "IngestConfig"]
+           "LiveSession", "LiveOursSession", "Inertializer", "Ingestor", "IngestConfig", "ingest_clips", "clip_windows"]

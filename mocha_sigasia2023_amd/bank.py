@@ -10,6 +10,8 @@
   preprocess/generate_database_bin.py:228-246); ``collect_windows`` — the bank scripts' step-1 windowing over the
   clips of one character (collect_CVAE_feature_action.py:104-133); ``build_bank_from_database`` chains them with the
   device featurisation and ``build_bank``: database.bin -> windows -> X -> encoded / cnt -> the reference's ``.npz`` files.
+* ``build_database_from_clips`` — raw mocap clips -> that database on the device, every clip plain and mirrored
+  (preprocess/generate_database_bin.py:83-222; ``ingest.ingest_clips``).
 * ``BatchPipeline`` — consecutive batches overlapped: a few contexts of one process, each with its own stream, characterize
   alternate batches against the same bank.  A mid-size batch (the per-GPU share of BASELINE configs[3]: 128 windows) is a latency
   chain of ~37 launches that leaves most of the chip idle; independent batches fill each other's gaps (128 windows: 121 -> 160 k
@@ -28,6 +30,7 @@ import torch
 
 from . import distributed as D
 from .generator import DIM, NTOK, ContextBank, Generator, _dev_f32, _ptr, _stream
+from .skeleton import LAYOUTS
 
 
 def build_bank(model: Generator, X, batch: int = 1024, raw: bool = False):
@@ -100,6 +103,32 @@ def write_database(filename: str, db: dict) -> None:
         for k in ("range_starts", "range_stops", "style_labels", labels):
             f.write(struct.pack("<I", len(db["range_starts"])) + i32(k).tobytes())
         f.write(struct.pack("<II", nframes, contacts.shape[1]) + contacts.tobytes())
+
+
+def build_database_from_clips(model: Generator, clips, style_labels, action_labels, mirror: bool = True, raw=None, post=None) -> dict:
+    """Raw clips -> the motion database of preprocess/generate_database_bin.py:83-222 as ``load_database`` returns it, prepared on the
+    device (``ingest.ingest_clips``).  ``clips``: a list of (rot, pos) pairs, rot (n,V,3) Euler degrees or (n,V,4) quaternions and pos
+    (n,V,3) as ``raw`` (an ``IngestConfig``) says; ``style_labels`` / ``action_labels``: one int per clip.  With ``mirror`` every clip
+    goes in twice, plain and then mirrored (:96-111), each with its own range, ranges laid end to end (:201-208).  The contact threshold
+    is ``raw``'s: generate_database_bin.py uses 0.2 m/s (:178), process_data and ``IngestConfig`` default to 0.5.  The result goes
+    unchanged into ``write_database`` and ``build_bank_from_database``."""
+    from .ingest import IngestConfig, ingest_clips
+    if not clips or len(style_labels) != len(clips) or len(action_labels) != len(clips):
+        raise ValueError("build_database_from_clips: one style and one action label per clip, at least one clip")
+    reps = 2 if mirror else 1
+    rot = np.concatenate([np.asarray(r, dtype=np.float32) for r, _ in clips for _ in range(reps)])
+    pos = np.concatenate([np.asarray(p, dtype=np.float32) for _, p in clips for _ in range(reps)])
+    lengths = [len(r) for r, _ in clips for _ in range(reps)]
+    flags = [k == 1 for _ in clips for k in range(reps)]
+    out = ingest_clips(model, rot, pos, lengths, raw=IngestConfig() if raw is None else raw, mirror=flags if mirror else None, post=post)
+    stops = np.cumsum(lengths)
+    parents = np.concatenate([[-1], np.asarray(LAYOUTS[model.layout]["parents"], dtype=np.int64) + 1])
+    labels = np.repeat(np.asarray(action_labels, dtype=np.int32), reps)
+    return {"bone_positions": out["pos"].cpu().numpy(), "bone_velocities": out["vel"].cpu().numpy(),
+            "bone_rotations": out["rot"].cpu().numpy(), "bone_angular_velocities": out["ang"].cpu().numpy(),
+            "bone_parents": parents.astype(np.int32), "range_starts": (stops - lengths).astype(np.int32),
+            "range_stops": stops.astype(np.int32), "style_labels": np.repeat(np.asarray(style_labels, dtype=np.int32), reps),
+            "content_labels": labels, "action_labels": labels, "contact_states": out["contact"].cpu().numpy().astype(np.int8)}
 
 
 def collect_windows(db: dict, style_labels, action_labels, window: int = 60) -> dict:

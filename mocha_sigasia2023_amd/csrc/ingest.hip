@@ -31,9 +31,11 @@
 // quaternion per joint (MOCHA_MAX_BONES x 4), the ring (slot = frame % INGEST_RING: quaternions MOCHA_MAX_BONES x 4 | positions x 3 |
 // spine xz | direction xz), then the last 60 emitted fp32 hips positions (slot = emitted % 60).  All-zero bytes = no frame seen.
 //
+// The frame-level arithmetic - the fit's row, the root from the fitted series, the central differences, the toe chain - is ingest_body.h,
+// shared with the whole-clip form (ingest_clip.hip), which emits every frame of a clip and mirrors.
+//
 // Inherited from the reference: between([0,0,1], d) is singular for a character facing exactly -z; contacts flip at a hard threshold.
-#include "kernels.h"
-#include "quat64.h"
+#include "ingest_body.h"
 
 namespace mocha {
 
@@ -46,11 +48,8 @@ constexpr int NROOT = 8, NVEL = 6;               // frames t-4 .. t+3 with a roo
 
 // the fit of one series (word `off` of every ring frame) at frame j of a prefix of n frames: rows (W,W)
 __device__ inline double fit(const double* __restrict__ rows, int W, const double* ring, int off, int j, int n) {
-    const int h = W / 2;
     int start, row;
-    if (j < h) { start = 0; row = j; }
-    else if (j > n - 1 - h) { start = n - W; row = j - (n - W); }
-    else { start = j - h; row = h; }
+    ingest_fit_row(W, j, n, start, row);
     double acc = 0.0;
     for (int k = 0; k < W; ++k) acc += rows[row * W + k] * ring[(size_t)((start + k) % RING) * INGEST_FRAME_DOUBLES + off];
     return acc;
@@ -128,13 +127,9 @@ __global__ __launch_bounds__(64) void mocha_live_ingest(IngestParams p) {
     }
     __syncthreads();
     if (tid < nroot) {
-        double dx = s_fit[tid][2], dz = s_fit[tid][3];
-        const double l = sqrt(dx * dx + dz * dz);
-        dx /= l; dz /= l;
-        const double w = sqrt(1.0 * (dx * dx + dz * dz)) + dz;   // between([0,0,1], d) = [sqrt(|z|^2 |d|^2) + z.d, cross(z, d)]
-        const double m = sqrt(w * w + dx * dx) + 1e-8;           // normalize: x / (|x| + 1e-8)
-        const dq R = {w / m, 0.0, dx / m, 0.0};
-        const d3 rp = {s_fit[tid][0], 0.0, s_fit[tid][1]};
+        d3 rp;
+        dq R;
+        ingest_root(s_fit[tid][0], s_fit[tid][1], s_fit[tid][2], s_fit[tid][3], rp, R);
         const double* f = ring + (size_t)((lo + tid) % RING) * INGEST_FRAME_DOUBLES;
         const dq Ri = qinv(R);
         s_rootp[tid] = rp; s_rootq[tid] = R;
@@ -153,13 +148,8 @@ __global__ __launch_bounds__(64) void mocha_live_ingest(IngestParams p) {
     const double f60 = p.fps;
     for (int i = tid; i < (vcen - vlo + 1) * J; i += 64) {
         const int j = vlo + i / J, b = i % J;
-        const d3 p0 = P(j - 1, b), p1 = P(j, b), p2 = P(j + 1, b);
-        s_vel[j - vlo][b] = 0.5 * (p2 - p1) * f60 + 0.5 * (p1 - p0) * f60;
-        const dq q0 = Q(j - 1, b), q1 = Q(j, b), q2 = Q(j + 1, b);
-        dq a = qmul(q2, qinv(q1)), c = qmul(q1, qinv(q0));
-        if (!(a.w > 0.0)) a = {-a.w, -a.x, -a.y, -a.z};          // quat.abs
-        if (!(c.w > 0.0)) c = {-c.w, -c.x, -c.y, -c.z};
-        s_ang[j - vlo][b] = 0.5 * to_scaled_angle_axis(a) * f60 + 0.5 * to_scaled_angle_axis(c) * f60;
+        s_vel[j - vlo][b] = ingest_central_vel(P, j, b, f60);
+        s_ang[j - vlo][b] = ingest_central_ang(Q, j, b, f60);
     }
     __syncthreads();
     if (vhi == n - 1) {                                          // lookahead <= 2: frames n-3, n-2 are in the window
@@ -173,18 +163,9 @@ __global__ __launch_bounds__(64) void mocha_live_ingest(IngestParams p) {
     // ---- contacts: lane (toe, frame of the vote)
     if (tid < p.n_contact * NVEL) {
         const int ci = tid / NVEL, j = min(t - 3 + tid % NVEL, n - 1);
-        int chain[MOCHA_MAX_CHAIN], depth = 0;
-        for (int b = p.contact_bones[ci]; b > 0 && depth < MOCHA_MAX_CHAIN; b = p.parents[b - 1] + 1) chain[depth++] = b;
-        d3 gv = s_vel[j - vlo][0], ga = s_ang[j - vlo][0];
-        dq gr = Q(j, 0);
-        for (int d = depth - 1; d >= 0; --d) {
-            const int b = chain[d];
-            const d3 lp = qrot(gr, P(j, b));
-            const d3 ngv = qrot(gr, s_vel[j - vlo][b]) + cross(ga, lp) + gv;
-            const d3 nga = qrot(gr, s_ang[j - vlo][b]) + ga;
-            gr = qmul(gr, Q(j, b)); gv = ngv; ga = nga;
-        }
-        s_vote[ci][tid % NVEL] = sqrt(gv.x * gv.x + gv.y * gv.y + gv.z * gv.z) < p.threshold ? 1 : 0;
+        auto Vel = [&](int f, int b) -> d3 { return s_vel[f - vlo][b]; };
+        auto Ang = [&](int f, int b) -> d3 { return s_ang[f - vlo][b]; };
+        s_vote[ci][tid % NVEL] = ingest_toe_speed(p.parents, p.contact_bones[ci], j, P, Q, Vel, Ang) < p.threshold ? 1 : 0;
     }
     __syncthreads();
     // ---- emit frame t

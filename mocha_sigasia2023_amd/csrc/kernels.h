@@ -243,6 +243,44 @@ struct IngestParams {
     double scale, fps, threshold;
 };
 hipError_t launch_live_ingest(const IngestParams& p, int S, hipStream_t s);
+// The same preparation for WHOLE clips (ingest_clip.hip): C clips concatenated along the frame axis, clip c = frames offsets[c] ..
+// offsets[c+1]-1, every clip at least INGEST_FIRST frames; nothing crosses a clip boundary.  Parallel over frames; float64 on the fp32
+// inputs, rounded to fp32 once at the output.  flags[c] != 0: the clip is mirrored (animation_mirror, generate_database.py:40-55) with the
+// joint exchange `map` before the root bone is extracted.  The float64 workspace, per frame: raw quaternions | unrolled quaternions (V,4
+// each) | positions (V,3) | spine xz, direction xz | root position xz, root rotation, root-local hips position and rotation
+// (CLIP_ROOT_DOUBLES); `below`: the per-frame toe speed flags the vote reads.
+static constexpr int CLIP_ROOT_DOUBLES = 13;
+static constexpr int CLIP_SCAN_CHUNK = 32, CLIP_SCAN_THREADS = 128;       // unroll scan: frames per lane, lanes per workgroup
+struct ClipParams {
+    const float *rot, *pos;         // (F,V,4|3), (F,V,3)
+    const int *offsets, *flags;     // device: (C+1), (C) or NULL
+    const double *rows15, *rows31;
+    double *qraw, *q, *p, *series, *root;
+    unsigned char* below;           // (F, MOCHA_MAX_CONTACT)
+    float *out_pos, *out_vel, *out_rot, *out_ang;
+    unsigned char* out_contact;     // (F, n_contact)
+    int F, C, V, euler, order[3], roles[5], n_contact, max_depth;
+    int parents[MOCHA_MAX_BONES];   // of the V raw joints
+    int depth[MOCHA_MAX_BONES];     // ancestors of a raw joint
+    int map[MOCHA_MAX_BONES];       // the mirror exchange
+    int contact_bones[MOCHA_MAX_CONTACT];
+    double scale, fps, threshold;
+};
+// launch = 0 quaternions, 1 unroll (all clips), 2 mirror, 3 unroll (mirrored clips), 4 series, 5 root, 6 velocities + toe speed flags,
+// 7 contact vote: one kernel each, so that the host layer can time every launch
+hipError_t launch_clip_ingest(const ClipParams& p, int launch, hipStream_t s);
+// divide_clip(divide=True) (generate_database.py:57-84) as one gather: window b of clip c (wcum[c] <= b < wcum[c+1]) starts at frame
+// (b - wcum[c]) * step of the clip; a short slice is padded by its first / last frame, vel and ang padding zero
+struct ClipWindowParams {
+    const float *pos, *vel, *rot, *ang;   // (F,J,3|3|4|3)
+    const unsigned char* contact;          // (F,nc)
+    const int *offsets, *wcum;             // device: (C+1) each
+    float *Yrot, *Ypos, *Yvel, *Yang;      // (B,window,J,.)
+    unsigned char* Ycontact;               // (B,window,nc)
+    int C, J, nc, window, step;
+    long long B;
+};
+hipError_t launch_clip_windows(const ClipWindowParams& p, hipStream_t s);
 static constexpr int POST_STATE_DOUBLES = 8 + MOCHA_MAX_BONES * 3 + MOCHA_MAX_CONTACT * 19;
 struct PostParams {
     const float* heads;             // (clips, frames, V, 13)

@@ -248,6 +248,9 @@ struct mocha_ctx {
     bool fold_joint = true;            // embedding joint block: gcn 1x1 conv folded into the k=5 temporal conv (one K = 960 GEMM)
     DeviceBuffer<int> bone_parents;    // device: parents of the (V+1)-bone skeleton with the root bone in front
     DeviceBuffer<double> ingest_rows;  // device: the cubic fit rows of the mocap front end, (15,15) then (31,31) (ensure_ingest_rows)
+    // device: the clip ingester's tables (offsets, mirror flags / window counts) and its float64 workspace (mocha_ingest_clips,
+    // mocha_clip_windows).  Grow-only; only those two calls read it and neither is captured, so a new allocation does not move the generation.
+    DeviceBuffer<double> clip_ws;
     DeviceBuffer<float> pose_norm;     // [x_mean | x_std | y_mean | y_std], (V+1)*C_in each (norm.npz of the reference)
     bool use_tiled = false;            // option "bank_tiled": -4 % on the cold pass for 2 x the bf16 copy's memory (profiles/r04/c_tiled_loader_ab.txt): off
     DeviceBuffer<unsigned long long> topk_keys{BUF_MOVES_GENERATION};      // every row's key of up to 8 queries (mocha_match_topk)
@@ -3295,6 +3298,161 @@ int mocha_live_step_raw(mocha_ctx* c, const mocha_post_cfg* cfg, const mocha_ing
     return live_step_impl(c, cfg, live, streams, p.Yrot, p.Ypos, p.Yvel, p.Yang, p.src_rvel, p.src_rang, p.src_speed, p.contact, seg, cnt_mean,
                           cnt_std, pos_out, rot_out, ik_rot, bvh_pos, bvh_euler, idx, valid, k, k > 0 ? temperature : 0.f, k > 0 ? idx_k : nullptr,
                           k > 0 ? w_k : nullptr, stream, inert, inert ? &ic : nullptr, &p, icfg_in);
+}
+
+}  // extern "C"
+
+namespace {
+// clip_offsets of the clip calls: offsets[0] = 0, strictly increasing, every clip at least min_len frames
+int clip_offsets_check(mocha_ctx* c, const char* who, const int32_t* off, int n_clips, int min_len) {
+    if (!off) return fail(c, MOCHA_ERR_ARG, "%s: null argument", who);
+    if (n_clips < 1) return fail(c, MOCHA_ERR_ARG, "%s: n_clips must be at least 1", who);
+    if (off[0] != 0) return fail(c, MOCHA_ERR_ARG, "%s: clip_offsets[0] must be 0", who);
+    for (int i = 0; i < n_clips; ++i) {
+        if (off[i + 1] <= off[i]) return fail(c, MOCHA_ERR_ARG, "%s: clip_offsets must increase (clip %d)", who, i);
+        if (off[i + 1] - off[i] < min_len)
+            return fail(c, MOCHA_ERR_ARG, "%s: clip %d has %d frames, fewer than %d", who, i, (int)(off[i + 1] - off[i]), min_len);
+    }
+    return 0;
+}
+
+// windows divide_clip(divide=True) cuts from a clip of n frames: j = 0, step, 2 step, ... < n - window / 4 (generate_database.py:67)
+int64_t clip_window_count(int64_t n, int window, int step) {
+    const int64_t span = n - window / 4;
+    return span <= 0 ? 0 : (span + step - 1) / step;
+}
+
+// the tables of a clip call at the head of the context's clip buffer, then `doubles` float64 words; the tables are on the device when
+// this returns (the stream is waited for once: the host arrays are the caller's)
+int clip_tables(mocha_ctx* c, hipStream_t s, const std::vector<int>& tab, size_t doubles, int** tab_dev, double** ws) {
+    const size_t head = (tab.size() * sizeof(int) + 255) / 256 * 32;        // doubles, a multiple of 256 bytes
+    int rc = reserve(c, c->clip_ws, head + doubles); if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->clip_ws.p, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    *tab_dev = reinterpret_cast<int*>(c->clip_ws.p);
+    *ws = c->clip_ws.p + head;
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int mocha_mirror_map_default(int layout, int32_t* map) {
+    if (!map || layout < 0 || layout > 1) return MOCHA_ERR_ARG;
+    // 'mocha': Left* / Right* of the 24 joint names (legs 1-4 / 20-23, arms 9-12 / 16-19); 'mixamo': arms 6-9 / 10-13, legs 14-17 / 18-21
+    const int V = layout == 1 ? 22 : 24;
+    for (int v = 0; v < V; ++v) map[v] = v;
+    auto swap_run = [&](int a, int b, int n) { for (int k = 0; k < n; ++k) { map[a + k] = b + k; map[b + k] = a + k; } };
+    if (layout == 1) { swap_run(6, 10, 4); swap_run(14, 18, 4); }
+    else { swap_run(1, 20, 4); swap_run(9, 16, 4); }
+    return 0;
+}
+
+int mocha_clip_window_count(const int32_t* offsets, int n_clips, int window, int step, int64_t* counts) {
+    if (!offsets || !counts || n_clips < 1 || window < 4 || step < 1) return MOCHA_ERR_ARG;
+    for (int i = 0; i < n_clips; ++i) {
+        if (offsets[i + 1] <= offsets[i]) return MOCHA_ERR_ARG;
+        counts[i] = clip_window_count((int64_t)offsets[i + 1] - offsets[i], window, step);
+    }
+    return 0;
+}
+
+int mocha_ingest_clips(mocha_ctx* c, const mocha_ingest_cfg* cfg, const mocha_post_cfg* post, const float* rot, const float* pos,
+                       const int32_t* clip_offsets, int n_clips, const int32_t* mirror_map, const unsigned char* mirror_flags,
+                       float* out_pos, float* out_vel, float* out_rot, float* out_ang, unsigned char* out_contact, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (!cfg) return fail(c, MOCHA_ERR_ARG, "ingest_clips: null ingest configuration");
+    if (!rot || !pos || !out_pos || !out_vel || !out_rot || !out_ang || !out_contact) return fail(c, MOCHA_ERR_ARG, "ingest_clips: null argument");
+    mocha_ingest_cfg whole = *cfg;
+    whole.lookahead = 0;                                       // a whole clip has no lookahead: the field is ignored
+    IngestParams ip{};
+    int rc = ingest_params(c, "ingest_clips", &whole, post, ip); if (rc) return rc;
+    if ((rc = clip_offsets_check(c, "ingest_clips", clip_offsets, n_clips, INGEST_FIRST))) return rc;
+    const int V = c->cfg.V, J = V + 1, F = clip_offsets[n_clips];
+    bool mirrored = false;
+    double mirrored_share = 0.0;                               // of the frames: what the two launches for mirrored clips touch
+    for (int i = 0; mirror_flags && i < n_clips; ++i)
+        if (mirror_flags[i]) { mirrored = true; mirrored_share += (double)(clip_offsets[i + 1] - clip_offsets[i]) / F; }
+    if (mirrored && !mirror_map) return fail(c, MOCHA_ERR_ARG, "ingest_clips: mirror_flags set without a mirror_map");
+    ClipParams p{};
+    if (mirror_map) {
+        for (int v = 0; v < V; ++v)
+            if (mirror_map[v] < 0 || mirror_map[v] >= V || mirror_map[mirror_map[v]] != v)
+                return fail(c, MOCHA_ERR_ARG, "ingest_clips: mirror_map is no involution at joint %d", v);
+        if (mirror_map[0] != 0) return fail(c, MOCHA_ERR_ARG, "ingest_clips: mirror_map must keep the hips");
+        for (int v = 1; v < V; ++v)
+            if (c->sk.parents[mirror_map[v]] != mirror_map[c->sk.parents[v]])
+                return fail(c, MOCHA_ERR_ARG, "ingest_clips: mirror_map does not commute with the parents at joint %d", v);
+        for (int v = 0; v < V; ++v) p.map[v] = mirror_map[v];
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = ensure_ingest_rows(c))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> tab(clip_offsets, clip_offsets + n_clips + 1);
+    for (int i = 0; i < n_clips; ++i) tab.push_back(mirror_flags && mirror_flags[i] ? 1 : 0);
+    const size_t nF = (size_t)F, nq = nF * V * 4, np_ = nF * V * 3;
+    const size_t doubles = 2 * nq + np_ + nF * 4 + nF * CLIP_ROOT_DOUBLES + (nF * MOCHA_MAX_CONTACT + 7) / 8;
+    int* tab_dev = nullptr; double* ws = nullptr;
+    if ((rc = clip_tables(c, s, tab, doubles, &tab_dev, &ws))) return rc;
+    p.rot = rot; p.pos = pos; p.offsets = tab_dev; p.flags = tab_dev + n_clips + 1;
+    p.rows15 = c->ingest_rows.p; p.rows31 = c->ingest_rows.p + 15 * 15;
+    p.qraw = ws; p.q = p.qraw + nq; p.p = p.q + nq; p.series = p.p + np_; p.root = p.series + nF * 4;
+    p.below = reinterpret_cast<unsigned char*>(p.root + nF * CLIP_ROOT_DOUBLES);
+    p.out_pos = out_pos; p.out_vel = out_vel; p.out_rot = out_rot; p.out_ang = out_ang; p.out_contact = out_contact;
+    p.F = F; p.C = n_clips; p.V = V; p.euler = ip.euler; p.n_contact = ip.n_contact;
+    for (int i = 0; i < 3; ++i) p.order[i] = ip.order[i];
+    for (int i = 0; i < 5; ++i) p.roles[i] = ip.roles[i];
+    for (int i = 0; i < ip.n_contact; ++i) p.contact_bones[i] = ip.contact_bones[i];
+    for (int v = 0; v < V; ++v) {
+        p.parents[v] = ip.parents[v];
+        p.depth[v] = v == 0 ? 0 : p.depth[ip.parents[v]] + 1;
+        p.max_depth = std::max(p.max_depth, p.depth[v]);
+    }
+    p.scale = ip.scale; p.fps = ip.fps; p.threshold = ip.threshold;
+    // bytes per launch: what it reads and writes once (the fit windows and the neighbours of a difference come from cache)
+    const double fq = (double)nq * 8, fp = (double)np_ * 8, fr = (double)nF * CLIP_ROOT_DOUBLES * 8, fin = (double)nF * V * (ip.euler ? 6 : 7) * 4;
+    LAUNCH(c, s, "mocha_clip_quat", "clip.quat", 0.0, fin + fq + fp, launch_clip_ingest(p, 0, s));
+    LAUNCH(c, s, "mocha_clip_unroll", "clip.unroll", 0.0, 2 * fq, launch_clip_ingest(p, 1, s));
+    if (mirrored) {
+        LAUNCH(c, s, "mocha_clip_mirror", "clip.mirror", 0.0, mirrored_share * 2 * (fq + fp), launch_clip_ingest(p, 2, s));
+        LAUNCH(c, s, "mocha_clip_unroll", "clip.unroll_mirrored", 0.0, mirrored_share * 2 * fq, launch_clip_ingest(p, 3, s));
+    }
+    LAUNCH(c, s, "mocha_clip_series", "clip.series", 0.0, fq + fp + (double)nF * 32, launch_clip_ingest(p, 4, s));
+    LAUNCH(c, s, "mocha_clip_root", "clip.root", 0.0, (double)nF * 32 + fr + (double)nF * 56, launch_clip_ingest(p, 5, s));
+    LAUNCH(c, s, "mocha_clip_vel", "clip.vel", 0.0, fq + fp + fr + (double)nF * J * 13 * 4 + (double)nF * 4, launch_clip_ingest(p, 6, s));
+    LAUNCH(c, s, "mocha_clip_vote", "clip.vote", 0.0, (double)nF * (4 + ip.n_contact), launch_clip_ingest(p, 7, s));
+    return 0;
+}
+
+int mocha_clip_windows(mocha_ctx* c, const float* pos, const float* vel, const float* rot, const float* ang, const unsigned char* contact,
+                       int n_contact, const int32_t* clip_offsets, int n_clips, int window, int step, float* Yrot, float* Ypos, float* Yvel,
+                       float* Yang, unsigned char* Ycontact, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (window < 4 || step < 1) return fail(c, MOCHA_ERR_ARG, "clip_windows: window must be at least 4 and step at least 1");
+    if (n_contact < 0 || n_contact > MOCHA_MAX_CONTACT) return fail(c, MOCHA_ERR_ARG, "clip_windows: n_contact must be 0..4");
+    int rc = clip_offsets_check(c, "clip_windows", clip_offsets, n_clips, 1); if (rc) return rc;
+    std::vector<int> tab(clip_offsets, clip_offsets + n_clips + 1);
+    int64_t B = 0;
+    tab.push_back(0);
+    for (int i = 0; i < n_clips; ++i) {
+        B += clip_window_count((int64_t)clip_offsets[i + 1] - clip_offsets[i], window, step);
+        if (B > 0x7fffffff) return fail(c, MOCHA_ERR_ARG, "clip_windows: more than 2^31 - 1 windows");
+        tab.push_back((int)B);
+    }
+    if (B == 0) return 0;
+    if (!pos || !vel || !rot || !ang || !Yrot || !Ypos || !Yvel || !Yang || (n_contact > 0 && (!contact || !Ycontact)))
+        return fail(c, MOCHA_ERR_ARG, "clip_windows: null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    int* tab_dev = nullptr; double* ws = nullptr;
+    if ((rc = clip_tables(c, s, tab, 0, &tab_dev, &ws))) return rc;
+    ClipWindowParams p{};
+    p.pos = pos; p.vel = vel; p.rot = rot; p.ang = ang; p.contact = contact; p.offsets = tab_dev; p.wcum = tab_dev + n_clips + 1;
+    p.Yrot = Yrot; p.Ypos = Ypos; p.Yvel = Yvel; p.Yang = Yang; p.Ycontact = Ycontact;
+    p.C = n_clips; p.J = c->cfg.V + 1; p.nc = n_contact; p.window = window; p.step = step; p.B = B;
+    LAUNCH(c, s, "mocha_clip_windows_k", "clip.windows", 0.0, 2.0 * (double)B * window * (p.J * 13.0 * 4 + n_contact),
+           launch_clip_windows(p, s));
+    return 0;
 }
 
 }  // extern "C"

@@ -5,14 +5,18 @@ reference's ``process_data`` makes of a whole clip - a synthetic root bone, velo
 after the one they produce.  ``Ingestor`` is that preparation in streaming form: one raw frame per call and stream, and from the 31st
 push on every call emits frame ``n-1-lookahead`` of ``process_data`` applied to the frames pushed so far.  ``lookahead=18`` gives the
 whole clip's frame 0.3 s late; ``lookahead=0`` the newest frame under the reference's clip-end rules.  ``LiveSession(raw=...)`` runs it
-inside the session's captured graph.  Not provided: a flush of the last ``lookahead`` frames at the end of a clip, mirroring, BVH text
-parsing.  Inherited from the reference: a character facing exactly -z is singular; contacts flip at a hard speed threshold.
+inside the session's captured graph.  A stream never emits the last ``lookahead`` frames of a clip and does not mirror: whole clips go
+through ``ingest_clips`` (``mocha_ingest_clips``: every frame of every clip, plain or mirrored as ``animation_mirror`` does, parallel over
+frames) and ``clip_windows`` (``divide_clip``), the first link of raw clip -> ``bank.build_database_from_clips`` -> bank and of raw clip
+pair -> windows -> ``featurize`` -> ``characterize_pair``.  Not provided: BVH text parsing.  Inherited from the reference: a character
+facing exactly -z is singular; contacts flip at a hard speed threshold.
 """
 from __future__ import annotations
 
 import ctypes as C
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _C
@@ -25,11 +29,14 @@ AXES = {"x": 0, "y": 1, "z": 2}
 class IngestConfig:
     """``mocha_ingest_cfg``: ``lookahead`` 0..18 frames; ``order``: the Euler channel order as a BVH file holds it ('zyx', ...), degrees,
     or None for quaternion input (w,x,y,z); ``unit_scale`` (0.01: cm -> m), ``fps``, ``contact_velocity_threshold`` (m/s); the role joints
-    ``spine``, ``shoulder_l``, ``shoulder_r``, ``upleg_l``, ``upleg_r`` as raw joint indices (default: the layout's)."""
+    ``spine``, ``shoulder_l``, ``shoulder_r``, ``upleg_l``, ``upleg_r`` as raw joint indices (default: the layout's).  ``mirror_map``
+    (``ingest_clips`` only): the joint exchange of a mirrored clip, V ints with map[map[v]] == v; None = the layout's left / right
+    exchange (``mocha_mirror_map_default``)."""
 
     def __init__(self, lookahead: int = 0, order: Optional[str] = "zyx", unit_scale: float = 0.01, fps: float = 60.0,
-                 contact_velocity_threshold: float = 0.5, **roles):
+                 contact_velocity_threshold: float = 0.5, mirror_map=None, **roles):
         self.lookahead, self.order = int(lookahead), order
+        self.mirror_map = None if mirror_map is None else [int(v) for v in mirror_map]
         self.unit_scale, self.fps, self.threshold = float(unit_scale), float(fps), float(contact_velocity_threshold)
         for k in roles:
             if k not in ("spine", "shoulder_l", "shoulder_r", "upleg_l", "upleg_r"):
@@ -115,3 +122,97 @@ def reset_ingest(model: Generator, state: torch.Tensor, n_streams: int, streams:
         ids = [int(s) for s in streams]
         arr = (C.c_int32 * max(len(ids), 1))(*ids)
         model._ctx.call("mocha_ingest_reset", _ptr(state), n_streams, arr, len(ids), _stream())
+
+
+class ProcessedClips(dict):
+    """``ingest_clips``'s result: the dict of device tensors, plus the model whose context made them (``clip_windows`` runs there)."""
+    model: Optional[Generator] = None
+
+
+def default_mirror_map(layout: str):
+    """The left / right joint exchange of a layout (``mocha_mirror_map_default``)."""
+    m = (C.c_int32 * 32)()
+    if _C.load_library().mocha_mirror_map_default(LAYOUT_ID[layout], m) != 0:
+        raise ValueError(f"no mirror map for layout {layout!r}")
+    return [int(m[v]) for v in range(22 if LAYOUT_ID[layout] == 1 else 24)]
+
+
+def _offsets(lengths):
+    off = np.concatenate([[0], np.cumsum(np.asarray(lengths, dtype=np.int64))])
+    if len(off) < 2 or off[-1] >= 2 ** 31:
+        raise ValueError("lengths: at least one clip and fewer than 2^31 frames in all")
+    return (C.c_int32 * len(off))(*[int(v) for v in off]), int(off[-1])
+
+
+def ingest_clips(model: Generator, rot, pos, lengths, raw=IngestConfig(), mirror=None, post=None):
+    """Whole clips through the reference's ``process_data`` on the device (``mocha_ingest_clips``).  ``rot`` (F,V,3) Euler degrees in
+    ``raw.order`` or (F,V,4) quaternions, ``pos`` (F,V,3): the clips concatenated along the frame axis, ``lengths`` their frame counts
+    (each at least 31).  ``mirror``: per clip, truthy = mirrored first (``animation_mirror`` with ``raw.mirror_map``); None = no clip.
+    ``post``: the post-processing constants whose ``contact_bones`` are the toes (default: the demo's).  Returns device tensors, root
+    bone first: ``pos`` / ``vel`` / ``ang`` (F,V+1,3), ``rot`` (F,V+1,4) fp32, ``contact`` (F,n_contact) uint8.  Every frame of every
+    clip is there; nothing crosses a clip boundary.  Waits for the current stream once (the tables' upload); not for graph capture.
+    The dict is a ``ProcessedClips``: it remembers ``model`` for ``clip_windows``."""
+    from .postprocess import PostProcessor
+    post = post or PostProcessor(model)
+    cfg = IngestConfig.of(raw)
+    st = cfg.struct(model)
+    width = 3 if st.rot_format == 1 else 4
+    V, J, dev = model.V, model.V + 1, model.device
+    off, F = _offsets(lengths)
+    r = _dev_f32(rot, dev, (V, width), "rot")
+    p = _dev_f32(pos, dev, (V, 3), "pos")
+    if r.numel() != F * V * width or p.numel() != F * V * 3:
+        raise ValueError(f"ingest_clips: rot / pos do not hold the {F} frames of lengths")
+    n = len(lengths)
+    flags = None
+    if mirror is not None:
+        if len(mirror) != n:
+            raise ValueError("ingest_clips: one mirror flag per clip")
+        flags = (C.c_ubyte * n)(*[1 if m else 0 for m in mirror])
+    mp = cfg.mirror_map if cfg.mirror_map is not None else (default_mirror_map(model.layout) if flags is not None else None)
+    if mp is not None and len(mp) != V:
+        raise ValueError(f"ingest_clips: mirror_map needs {V} entries")
+    mp_arr = None if mp is None else (C.c_int32 * V)(*mp)
+    nc = max(int(post.cfg.n_contact), 1)
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)    # noqa: E731
+    out = ProcessedClips({"pos": f32(F, J, 3), "vel": f32(F, J, 3), "rot": f32(F, J, 4), "ang": f32(F, J, 3),
+                          "contact": torch.zeros((F, nc), dtype=torch.uint8, device=dev)})
+    out.model = model
+    model._ctx.call("mocha_ingest_clips", C.byref(st), C.byref(post.cfg), _ptr(r), _ptr(p), off, n, mp_arr, flags, _ptr(out["pos"]),
+                    _ptr(out["vel"]), _ptr(out["rot"]), _ptr(out["ang"]), _ptr(out["contact"]), _stream())
+    return out
+
+
+def clip_window_counts(lengths, window: int = 60, step: int = 1):
+    """Windows per clip as ``divide_clip(divide=True)`` cuts them (``mocha_clip_window_count``)."""
+    off, _ = _offsets(lengths)
+    counts = (C.c_int64 * len(lengths))()
+    if _C.load_library().mocha_clip_window_count(off, len(lengths), int(window), int(step), counts) != 0:
+        raise ValueError("clip_window_counts: window must be at least 4, step at least 1, every length positive")
+    return [int(v) for v in counts]
+
+
+def clip_windows(processed, lengths, window: int = 60, step: int = 1, model: Optional[Generator] = None):
+    """``divide_clip(divide=True)`` of processed clips in one launch (``mocha_clip_windows``).  ``processed``: ``ingest_clips``'s dict, or
+    any dict of pos / vel / ang (F,V+1,3), rot (F,V+1,4) fp32 and contact (F,n_contact) uint8 together with ``model``.
+    Returns ``Yrot`` (B,window,V+1,4), ``Ypos`` / ``Yvel`` / ``Yang`` (B,window,V+1,3) as ``featurize`` takes them and ``contact``
+    (B,window,n_contact), clip after clip; short slices padded with their first / last frame, ``Yvel`` / ``Yang`` padding zero."""
+    model = model or getattr(processed, "model", None)
+    if model is None:
+        raise ValueError("clip_windows: processed is not ingest_clips's result; pass model=")
+    off, F = _offsets(lengths)
+    J, dev = model.V + 1, model.device
+    B = sum(clip_window_counts(lengths, window, step))
+    src = {k: _dev_f32(processed[k], dev, (J, w), k) for k, w in (("pos", 3), ("vel", 3), ("rot", 4), ("ang", 3))}
+    con = processed["contact"]
+    if con.dtype != torch.uint8 or any(t.shape[0] != F for t in src.values()) or con.shape[0] != F:
+        raise ValueError(f"clip_windows: processed does not hold the {F} frames of lengths (contact uint8)")
+    con = con.to(dev).contiguous()
+    nc = int(con.shape[1])
+    f32 = lambda w: torch.empty((B, window, J, w), dtype=torch.float32, device=dev)    # noqa: E731
+    out = {"Yrot": f32(4), "Ypos": f32(3), "Yvel": f32(3), "Yang": f32(3),
+           "contact": torch.zeros((B, window, nc), dtype=torch.uint8, device=dev)}
+    model._ctx.call("mocha_clip_windows", _ptr(src["pos"]), _ptr(src["vel"]), _ptr(src["rot"]), _ptr(src["ang"]), _ptr(con), nc, off,
+                    len(lengths), int(window), int(step), _ptr(out["Yrot"]), _ptr(out["Ypos"]), _ptr(out["Yvel"]), _ptr(out["Yang"]),
+                    _ptr(out["contact"]), _stream())
+    return out
