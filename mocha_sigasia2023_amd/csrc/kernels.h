@@ -375,6 +375,32 @@ hipError_t launch_match_select(const float* S, int ksplit, long long slab_stride
 hipError_t launch_match_select2(const float* S, int ksplit, long long slab_stride, int lds, const float* bnorm, const float* query,
                                 const float* centre, const float* bank, const void* bank16, const float* qstat, float margin_rel, int Q,
                                 int64_t N, int D, int32_t* idx, float* dist, hipStream_t s);
+// ---------------------------------------------------------------------------------------
+// Few-query scans and segmented matchers (match_stream.hip, match_scan8.hip, match_segmented.hip, match_seg_topk.hip, the two gathers of
+// pointwise.hip; held at the kernel boundary by tests/test_scan_kernels.py).  What the kernels rely on and no launcher checks
+// (tests/gemm_probe/scan_probe.cpp refuses it before a launch):
+//   pointers: every operand non-null unless stated optional, sized as stated; the bank (fp32, bf16 or byte rows), the queries (qc and
+//   query), enc, src and the gathers' out 16-byte aligned (16-byte loads and stores, the refine's LDS-DMA of the query row); scratch,
+//   partial and keys 8-byte aligned;
+//   1 <= N <= 0x7ffffff0 (the row is the low word of a key; row N - 1 stands in for the rows past the end of the last workgroup) and
+//   D > 0: D = 0 passes every D % chunk test.  D a multiple of the chunk - 1280 fp32, 1536 bf16, 2560 AND 1536 for the byte stage (so
+//   7680 | D there) - is checked by the launchers; launch_match_scan16 / _scan8 also check D % 256 == 0 and D <= 23040 (the refine holds a
+//   query row in LDS, match_refine_init), launch_match_refine checks NOTHING: 256 <= D <= 23040, D % 256 == 0, 1 <= nq <= 8, nwg >= 1 are
+//   its caller's, and wgmin[q] must hold, per query, keys of that query whose minimum is the minimum of keys[q] (the scan's per-16-row minima);
+//   scratch sizes: partial >= match_stream_scratch(Q, N) (whole groups of 8 queries), keys >= 8 * N for launch_match_topk, scratch >=
+//   match_scan16_scratch_words(N) (the refine alone: the head), partial >= match_seg_scratch_words(Q, max_rows), plan >= seg_plan_ints(Q, S)
+//   (the soft matcher: of SEG_TOPK_Q), keys >= match_seg_keys_words(max_rows); the scratch HEAD - match_scan16_scratch_head_words() words -
+//   zero at first use: the arrival tickets must be zero when a launch starts (every completed launch leaves them so) and the byte stage's
+//   two mode words start at {0, 0};
+//   rho / rho8 UPPER bounds of the copies' residual norms (an underestimate silently drops true winners); a coarse key that is NaN never
+//   qualifies for the re-rank; a query without any finite coarse key has every row re-ranked;
+//   segment table: S + 1 device ints, seg_start[0] = 0, non-decreasing, seg_start[S] <= the bank's rows, and NO EMPTY SEGMENT
+//   (mocha_bank_set_segments refuses one: the finish kernels would read row seg_start[s] of it, which for the last segment is past the
+//   bank); max_rows >= the largest segment (rows beyond max_rows would never be scanned); Q <= SEG_MAX_Q for launch_seg_plan and
+//   launch_match_segmented (checked); the ids seg[q] may be ANY int - outside [0, S): no block, -1 / row 0 / +inf / weights 0 / enc[0];
+//   launch_gather_blend: k <= 64, cols % 4 == 0, temperature > 0 (checked); neighbours with idx outside [0, nrows) are left out;
+//   launch_gather_rows: idx clamped into [0, nrows).
+// ---------------------------------------------------------------------------------------
 // streaming matcher for few queries against a large bank (HBM-bound): bank fp32 or bf16;
 // partial = match_stream_scratch(Q, N) u64 words of scratch
 size_t match_stream_scratch(int Q, int64_t N);

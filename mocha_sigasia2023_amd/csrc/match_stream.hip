@@ -285,13 +285,18 @@ __global__ __launch_bounds__(RF_T) void mocha_match_refine(const unsigned long l
     }
     __syncthreads();
     const unsigned nmin = (unsigned)(r_key & 0xffffffffull);
-    const float d16min = sqrtf(fmaxf(key_value(r_key), 0.f));
-    // (no finite coarse key at all - every key NaN or ~0 - leaves nmin out of range: nothing is excluded then)
-    const float hi = (long long)nmin < N ? d16min + rho[nmin] + 2e-5f * d16min : __builtin_inff();      // upper bound of the coarse minimum's exact distance
+    const float v16min = key_value(r_key);
+    // no finite coarse key at all: the smallest key is NaN or +inf (they sort behind every number) or the ~0 of an empty list - nothing is
+    // excluded then.  (fmaxf(NaN, 0) is 0: without this test a NaN key read as distance 0, and EVERY row with a NaN key was a candidate.)
+    const bool none = !((long long)nmin < N) || !(v16min < __builtin_inff());
+    const float d16min = sqrtf(fmaxf(v16min, 0.f));
+    const float hi = none ? __builtin_inff() : d16min + rho[nmin] + 2e-5f * d16min;      // upper bound of the coarse minimum's exact distance
     auto qualifies = [&](long long n, unsigned long long k, float r) -> bool {
-        if ((unsigned)n == nmin) return true;
-        const float d = sqrtf(fmaxf(key_value(k), 0.f));
-        return d - r - 2e-5f * d <= hi;                                // NaN distances never qualify
+        if (none || (unsigned)n == nmin) return true;
+        const float v = key_value(k);
+        if (v != v) return false;                                      // a NaN key never qualifies
+        const float d = sqrtf(fmaxf(v, 0.f));
+        return d - r - 2e-5f * d <= hi;
     };
     // ---- 2. index windows of RF_CAP rows of the slice: list, then exact distances.  EVERY wave takes part in EVERY row: the row's
     // D / 4 pieces are cut into RF_W fixed segments, wave w sums segment w (lanes stride it, then a wave reduction) and the RF_W segment

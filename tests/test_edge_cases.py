@@ -447,10 +447,12 @@ def test_null_pointers_come_back_as_error_codes(model):
 
 @pytest.mark.parametrize("N", [4096, 4097, 20011, 40000, 70001])
 def test_bf16_copy_scan_at_odd_bank_sizes(model, N):
-    """The re-rank's branches by bank size: a slice's keys held in registers (up to 2 048 rows per slice: N <= 32 768) or re-read
-    (beyond), one index window per slice or several (more than 4 096 rows per slice: N > 65 536), row counts that are not a
-    multiple of the scan's 16 rows per workgroup or of the 16 slices, the winner in the first / last row and in the last slice's
-    ragged end, and near-duplicates of the winner spread over the slices.  Against the fp32 scan and a float64 search."""
+    """Bank sizes that are no multiple of the scan's 16 rows per workgroup or of the re-rank's slices, the winner in the first / last
+    row and in the last slice's ragged end, and near-duplicates of the winner spread over the slices.  Against the fp32 scan and a float64
+    search.  The re-rank has 64 slices (per_slice = ceil(N / 64)): a slice's keys are held in registers up to 2 048 rows per slice
+    (N <= 131 072) and re-read beyond, and a slice has one index window up to 4 096 rows (N <= 262 144) and several beyond; at D = 23040
+    such a bank is 12 - 24 GB, so every N here stays on the register / one-window side.  The branches beyond those bounds are held at
+    D = 256 by tests/test_scan_kernels.py::test_refine_on_authored_keys (N = 131 072, 131 073, 262 145)."""
     from mocha_sigasia2023_amd import ContextBank
     D = 90 * 256
     g = torch.Generator(device="cuda:0"); g.manual_seed(N)

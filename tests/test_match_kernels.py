@@ -50,7 +50,8 @@ or >= 1e-4, the realised error between 0.8 and 1.0 of the bound, the candidate c
 (test_select_cases_are_valid_and_cover).  Asserted: the index is the float64 argmin, ties to the lowest row; dist against the float64
 direct form, pooled per kernel and bank type; NaN rows never win; a query without a finite score gets row 0 (select2: dist NaN; select
 evaluates row 0 and reports its distance); NaN in other queries' scores leaves a query's bits alone.
-Family 4 (launch_match_stream / _topk / _scan16 / _scan8 with authored rho) is NOT here: left out whole, as the issue allows.
+Family 4 (launch_match_stream / _topk / _scan16 / _scan8, mocha_match_refine on authored keys and rho) and family 5 (the segmented and soft
+matchers, the plan, the gathers) are held in tests/test_scan_kernels.py through tests/gemm_probe/scan_probe.cpp.
 
 Kernel fixes (family 1 found both; rowresid and to_i8 are bank-set kernels, not on the step's path):
   1. rho underestimated on tiny rows.  Rows of size 1e-30: d^2 and t^2 leave the fp32 range, both sums came out 0 and rho = 0 against a
