@@ -4,6 +4,7 @@ mocap frame at a time through ``LiveSession`` - ring push + featurize, segmented
 frame per push, one captured graph - and written as two BVH files.
 
     python examples/live_demo.py [--frames 180] [--out bench_outputs/live_demo] [--ours [--seed 7]] [--switch 120 [--inertial 0.1]] [--raw L]
+                                 [--actions A,B[:F]]
 
 ``--ours`` runs the CVAE ("Ours") branch inside the same graph (``LiveOursSession``): each stream's character feature is seeded with
 its matched bank row on the first pose and sampled from the previous one afterwards, the noise drawn on the device; the files are then
@@ -16,6 +17,11 @@ the reference's per-bone inertializers on the device).  The size of the largest 
 ``--raw L``: the streams push RAW mocap frames - local Euler rotations in degrees and local positions in centimetres of the 24 joints, as
 a BVH file holds them (a synthetic walk) - and the mocap front end inside the same graph makes the root bone, the velocities and the foot
 contacts (``LiveSession(raw=L)``, ``push_raw``), L = 0..18 frames of lookahead.  The first pose then comes with push 90.
+
+``--actions A,B[:F]``: the bank's entries carry action labels in runs of 25 (a synthetic stand-in for ``load_bank(path)["action_label"]``:
+200 entries, actions 0 .. 7) and, from frame F on (default: from the start), every stream is matched among its character's entries of the
+listed actions only (``LiveSession(constrained=True)``, ``push(..., allow=)``).  The new masks are device data: nothing is captured again.
+How many posed frames were constrained is printed.
 
 Weights, norms and motions are synthetic (see demo_pair.py for what to replace with real assets).
 """
@@ -42,7 +48,15 @@ ap.add_argument("--soft", nargs=2, metavar=("K", "T"), help="soft matching: the 
 ap.add_argument("--switch", type=int, default=None, metavar="FRAME", help="stream 0 takes character 1 from that frame on")
 ap.add_argument("--inertial", type=float, default=None, metavar="HALFLIFE", help="inertialize character switches with that half-life in seconds")
 ap.add_argument("--raw", type=int, default=None, metavar="L", help="push raw mocap frames; the front end runs in the graph with L frames of lookahead")
+ap.add_argument("--actions", default=None, metavar="A,B[:F]", help="allow only these action labels (0..7 here), from frame F on")
 a = ap.parse_args()
+if a.ours and a.actions:
+    raise SystemExit("--actions does not apply to --ours: the branch's seed match searches the whole character")
+allow_from, allow_mask = 0, None
+if a.actions:
+    from mocha_sigasia2023_amd import action_mask
+    spec, _, at = a.actions.partition(":")
+    allow_mask, allow_from = action_mask([int(v) for v in spec.split(",")]), int(at) if at else 0
 if a.ours and a.raw is not None:
     raise SystemExit("--raw does not apply to --ours: the CVAE session has no mocap front end")
 if a.ours and a.inertial is not None:
@@ -71,7 +85,8 @@ for seed in (12, 13):
     clip = synthetic.smooth_bone_clip(seed, 60 + 200 - 1)
     b = build_bank(model, model.featurize(*[synthetic.slide_windows(x) for x in clip]), raw=True)
     banks.append((((b["cnt"] - cnt_mean) / cnt_std).reshape(-1, 90 * 256), b["encoded"]))
-bank = MultiCharacterBank(model, banks)
+labels = [(np.arange(b[0].shape[0]) // 25).astype(np.int32) for b in banks] if a.actions else None      # actions in runs, one per clip range
+bank = MultiCharacterBank(model, banks, labels=labels)
 
 # ---- two source clips arriving frame by frame, stream s retargeted to character s
 src = [[torch.from_numpy(x).to(dev) for x in synthetic.smooth_bone_clip(30 + s, F, phase=0.4 * s)] for s in range(S)]
@@ -88,7 +103,8 @@ if a.ours:                                                            # test_ful
     sess = LiveOursSession(bank, cnt_mean, cnt_std, synthetic_cvae_state_dict(99, 1.0), *stats, streams=S, post=PostProcessor(model),
                            noise="device", seed=a.seed)
 else:
-    sess = LiveSession(bank, cnt_mean, cnt_std, streams=S, post=PostProcessor(model), soft=soft, inertial=a.inertial, raw=a.raw)
+    sess = LiveSession(bank, cnt_mean, cnt_std, streams=S, post=PostProcessor(model), soft=soft, inertial=a.inertial, raw=a.raw,
+                       constrained=bool(a.actions))
 if a.raw is not None:
     raw = [synthetic.raw_walk_clip(LAYOUTS["mocha"]["parents"], F, seed=40 + s) for s in range(S)]
     raw_rot = torch.from_numpy(np.stack([r[0] for r in raw])).to(dev)  # (S, F, 24, 3) degrees, 'zyx'
@@ -96,20 +112,27 @@ if a.raw is not None:
 
 
 def push(f, characters=None):
+    kw = dict(allow=[allow_mask] * S) if a.actions and f == allow_from else {}
     if a.raw is not None:
+        if kw:
+            sess.set_allow(kw["allow"])
         return sess.push_raw(raw_rot[:, f], raw_pos[:, f], characters=characters)
     return sess.push(*[torch.stack([src[s][k][f] for s in range(S)]) for k in range(4)],
-                     *[torch.stack([per[s][k][f] for s in range(S)]) for k in range(4)], characters=characters)
+                     *[torch.stack([per[s][k][f] for s in range(S)]) for k in range(4)], characters=characters, **kw)
 
 
 push(0, characters=[0, 1])                                            # the first push captures the step
 sess.reset()
 torch.cuda.synchronize(); t0 = time.perf_counter()
-pos, eul = [], []
+pos, eul, applied = [], [], []
+if a.actions:
+    sess.allow.zero_()
 for f in range(F):
     o = push(f, characters=[1, 1] if f == a.switch else None)
     if f >= first:                                                    # both streams started together: both are valid from here on
         pos.append(o["bvh_pos"].clone()); eul.append(o["bvh_euler"].clone())
+        if a.actions:
+            applied.append(o["applied"].clone())
 torch.cuda.synchronize(); dt = time.perf_counter() - t0
 pos, eul = torch.stack(pos, 1), torch.stack(eul, 1)                   # (S, F - first, V, 3)
 
@@ -122,5 +145,10 @@ if a.switch is not None and first + 1 <= a.switch < F:
     step = (pos[0, 1:, 1:] - pos[0, :-1, 1:]).abs().amax(dim=(1, 2))     # per frame, the non-root bones of stream 0
     print(f"  stream 0 switches character at frame {a.switch}: largest bone-position step there {float(step[a.switch - first - 1]):.4f}, "
           f"median over the clip {float(step.median()):.4f}" + (f" (inertialized, half-life {a.inertial} s)" if a.inertial is not None else ""))
+if a.actions:
+    ap_ = torch.stack(applied, 1)
+    print(f"  actions {a.actions.partition(':')[0]} allowed from frame {allow_from}: " + ", ".join(
+        f"stream {s}: {int((ap_[s] == 1).sum())} constrained, {int((ap_[s] == -1).sum())} fell back, {int((ap_[s] == 0).sum())} unconstrained"
+        for s in range(S)))
 print(f"{F} pushes of {S} streams in {dt * 1e3:.1f} ms ({dt / F * 1e3:.3f} ms per push, host loop included)")
 assert bool(torch.isfinite(pos).all()) and bool(torch.isfinite(eul).all())

@@ -250,6 +250,50 @@ int mocha_step_graph_soft_segmented(mocha_ctx* ctx, const float* X, int S_w, con
                                     const float* cnt_std, float* Y, int32_t* idx_k, float* w_k, int raw, void* stream);
 /* (mocha_live_step_soft is declared below, after mocha_live_step.) */
 
+/* Action-constrained context matching on a multi-character bank: "this character is crawling now".  The reference picks an action, keeps
+ * the character's windows of that action and builds its BallTree over that subset (train_CVAE.py:181-211; one bank per action list in
+ * collect_CVAE_feature_action.py:50-63,104-108).  Here every ROW carries an action label 0..63 and every QUERY a 64-bit allow mask (bit a
+ * set: rows of action a are admissible), both device-side data of ONE bank:
+ *   any[s] = OR of (1 << label) over the rows of segment s.  A query of character s with mask m is CONSTRAINED iff (m & any[s]) != 0: its
+ *   answer is the exact nearest neighbour (or the k nearest) among the rows of segment s whose label bit is in m - ties to the lowest row,
+ *   the index LOCAL to the segment and counting ALL its rows (not the subset's), the distance in the bank's arithmetic, missing neighbours
+ *   -1 / +inf / weight 0, exactly as mocha_match_segmented / mocha_match_topk_segmented.  m == 0 (nothing asked) and (m & any[s]) == 0
+ *   (the character has no entry of those actions: the match FALLS BACK to the whole segment) take the unconstrained answer to the bit.
+ *   applied (int32 per query, or NULL): 1 constrained, 0 nothing asked, -1 fell back; an id outside [0, S): idx -1, dist +inf, applied 0.
+ * A row's squared distance does not depend on the other rows, so on an fp32 bank a constrained answer has the bits the plain call gives on
+ * a bank made of the admissible rows alone.  The scan skips every 16-row workgroup none of whose queries admits a label it holds, before
+ * its first bank row: with labels in runs (one per clip range) a constrained match reads about the admissible share of the segment.  The
+ * launch count is the plain match's.  The plain calls and their results are unchanged.
+ *   mocha_bank_set_labels : labels (HOST, N int32) of the rows of the current segmented bank; MOCHA_ERR_STATE without a segment table,
+ *                             MOCHA_ERR_ARG for a label outside 0..63 (the previous labels stay).  Builds the device tables (1 byte per
+ *                             row, 8 bytes per segment and per 16 rows) and synchronises the stream; the constrained calls never allocate.
+ *                             Moves the generation.  labels == NULL removes the labels.  mocha_bank_set, mocha_bank_set_segments and
+ *                             mocha_bank_broadcast clear them, as they clear the segment table; a constrained call on a bank without
+ *                             labels is MOCHA_ERR_STATE.
+ *   mocha_match_segmented_allow : allow (DEVICE, Q uint64).  k == 1: mocha_match_segmented's idx (Q) / dist (Q) or NULL; 2 <= k <=
+ *                             MOCHA_SOFT_MAX_K: mocha_match_topk_segmented's (Q,k) outputs (whose column 0 is the k == 1 answer to the
+ *                             bit).  applied (Q) or NULL.
+ *   mocha_characterize_segmented_allow : k == 0: mocha_characterize_segmented (idx_k holds B entries or is NULL, w_k may be NULL);
+ *                             k >= 1: mocha_characterize_soft_segmented.  applied (B) or NULL.
+ *   mocha_step_graph_segmented_allow : that call for 1 <= S_w <= 16 windows captured and replayed (idx_k required; w_k for k >= 1).  The
+ *                             graph key gains the allow and applied pointers: new masks written into allow are read by the replay and do
+ *                             not re-capture.
+ *   mocha_live_step_allow / mocha_live_step_raw_allow (declared with the live calls below): the argument lists of mocha_live_step_inert /
+ *                             mocha_live_step_raw (k == 0: hard; inert may be NULL), then allow (S uint64, DEVICE) and applied (S) or
+ *                             NULL.  Each has its own captured graph; a warming stream gets applied 0.
+ * NOT covered: the calls that search the union of all rows (mocha_match, mocha_characterize, mocha_step_graph), the seed match of
+ * mocha_live_step_ours, and inertializing a CHANGE of the allowed actions (the inertializer triggers on a change of character only; soft
+ * matching already softens a change of mask). */
+int mocha_bank_set_labels(mocha_ctx* ctx, const int32_t* labels, void* stream);
+int mocha_match_segmented_allow(mocha_ctx* ctx, const float* query_nm, int Q, const int32_t* seg, const uint64_t* allow, int k, int32_t* idx,
+                                float* dist, int32_t* applied, void* stream);
+int mocha_characterize_segmented_allow(mocha_ctx* ctx, const float* src_X, int B, const int32_t* seg, const uint64_t* allow, int k,
+                                       float temperature, const float* cnt_mean, const float* cnt_std, float* Y, int32_t* idx_k, float* w_k,
+                                       int32_t* applied, int raw, void* stream);
+int mocha_step_graph_segmented_allow(mocha_ctx* ctx, const float* X, int S_w, const int32_t* seg, const uint64_t* allow, int k,
+                                     float temperature, const float* cnt_mean, const float* cnt_std, float* Y, int32_t* idx_k, float* w_k,
+                                     int32_t* applied, int raw, void* stream);
+
 /* Multi-GPU set-up: one process per GPU, windows sharded across ranks, the character bank replicated.
  * The reference has no counterpart (trainer.py:45-47 is nn.DataParallel); the only exchange on the path is this one-time
  * bank broadcast over RCCL / xGMI.  RCCL is loaded lazily (dlopen "librccl.so.1"); single-GPU callers never touch it.
@@ -598,6 +642,20 @@ int mocha_live_step_raw(mocha_ctx* ctx, const mocha_post_cfg* cfg, const mocha_i
                         float temperature, double* pos_out, double* rot_out, double* ik_rot, double* bvh_pos, double* bvh_euler,
                         int32_t* idx, int32_t* valid, int32_t* idx_k, float* w_k, void* stream, void* inert,
                         const mocha_inert_cfg* icfg);
+/* The action-constrained live steps (see mocha_bank_set_labels): mocha_live_step_inert's / mocha_live_step_raw's arguments - k == 0 the hard
+ * matcher, inert may be NULL - then allow (streams uint64, DEVICE: read by every replay, a producer may write it in place) and applied
+ * (streams int32, or NULL). */
+int mocha_live_step_allow(mocha_ctx* ctx, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos,
+                          const float* Yvel, const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed,
+                          const unsigned char* contact, const int32_t* seg, const float* cnt_mean, const float* cnt_std, int k,
+                          float temperature, double* pos, double* rot, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx,
+                          int32_t* valid, int32_t* idx_k, float* w_k, void* stream, void* inert, const mocha_inert_cfg* icfg,
+                          const uint64_t* allow, int32_t* applied);
+int mocha_live_step_raw_allow(mocha_ctx* ctx, const mocha_post_cfg* cfg, const mocha_ingest_cfg* icfg_in, void* live, void* ingest, int streams,
+                              const float* rot, const float* pos, const int32_t* seg, const float* cnt_mean, const float* cnt_std, int k,
+                              float temperature, double* pos_out, double* rot_out, double* ik_rot, double* bvh_pos, double* bvh_euler,
+                              int32_t* idx, int32_t* valid, int32_t* idx_k, float* w_k, void* stream, void* inert,
+                              const mocha_inert_cfg* icfg, const uint64_t* allow, int32_t* applied);
 
 /* WHOLE clips through the same preparation, parallel over frames: process_data (preprocess/generate_database.py:86-177) with mirror =
  * False / True and divide_clip(divide=True) (:57-84), the first link of raw clip -> database.bin -> bank (generate_database_bin.py:96-208)

@@ -113,6 +113,12 @@ SIGNATURES = {
     "mocha_ingest_reset": (_i, [_vp, _vp, _i, C.POINTER(C.c_int32), _i, _vp]),
     "mocha_live_ingest_step": (_i, [_vp, _vp, _vp, _vp, _i] + [_vp] * 12),
     "mocha_live_step_raw": (_i, [_vp, _vp, _vp, _vp, _vp, _i] + [_vp] * 5 + [_i, C.c_float] + [_vp] * 12),
+    "mocha_bank_set_labels": (_i, [_vp, C.POINTER(C.c_int32), _vp]),
+    "mocha_match_segmented_allow": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "mocha_characterize_segmented_allow": (_i, [_vp, _vp, _i, _vp, _vp, _i, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "mocha_step_graph_segmented_allow": (_i, [_vp, _vp, _i, _vp, _vp, _i, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "mocha_live_step_allow": (_i, [_vp, _vp, _vp, _i] + [_vp] * 11 + [_i, C.c_float] + [_vp] * 14),
+    "mocha_live_step_raw_allow": (_i, [_vp, _vp, _vp, _vp, _vp, _i] + [_vp] * 5 + [_i, C.c_float] + [_vp] * 14),
     "mocha_ingest_clips": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), C.POINTER(C.c_ubyte)] + [_vp] * 6),
     "mocha_clip_window_count": (_i, [C.POINTER(C.c_int32), _i, _i, _i, C.POINTER(_i64)]),
     "mocha_clip_windows": (_i, [_vp] * 6 + [_i, C.POINTER(C.c_int32), _i, _i, _i] + [_vp] * 6),

@@ -436,9 +436,25 @@ hipError_t launch_rownorm2_bf16(const void* x, float* out, int64_t rows, int col
 static constexpr int SEG_MAX_Q = 4096;
 size_t match_seg_scratch_words(int Q, int64_t max_rows);
 size_t seg_plan_ints(int Q, int S);
+// Action-constrained matching (the ALLOW instances of the two scans): every bank row carries a label 0..63, every query a 64-bit allow
+// mask.  any[s] = OR of 1 << label over segment s.  Query q of segment s is CONSTRAINED iff (allow[q] & any[s]) != 0: its candidates are
+// the rows of s whose label bit is in allow[q]; otherwise (zero mask: nothing asked; no row of those labels: fall back) it takes the plain
+// answer.  gran[gran_start[s] + x] = OR of the label bits of the segment's rows [16 x, 16 x + 16): a scan workgroup none of whose queries
+// admits any of its rows writes ~0 keys and returns without reading a bank row.  applied[q] (or null) = 1 constrained / 0 nothing asked
+// (or an id outside [0, S)) / -1 fell back, written by the finish / blend kernel.  All pointers but `applied` are required; label: one
+// byte per GLOBAL row, any: S words, gran_start: S + 1 ints, gran: gran_start[S] words; allow / applied: Q entries, as idx.
+static constexpr int SEG_GRANULE_ROWS = 16;      // rows per granule word = rows per scan workgroup (match_seg_body.h)
+struct SegAllow {
+    const unsigned long long* allow;
+    const unsigned char* label;
+    const unsigned long long* any;
+    const unsigned long long* gran;
+    const int* gran_start;
+    int32_t* applied;
+};
 hipError_t launch_match_segmented(const void* bank, int bank_bf16, const float* query, const int32_t* seg, int Q, const int* seg_start, int S,
                                   int64_t max_rows, int D, unsigned long long* partial, int* plan, int32_t* idx, int32_t* gidx, float* dist,
-                                  hipStream_t s);
+                                  hipStream_t s, const SegAllow* al = nullptr);
 hipError_t launch_seg_plan(const int32_t* seg, int Q, int S, int* plan, hipStream_t s);      // the matcher's first kernel alone (plan = seg_plan_ints(Q, S) ints)
 // soft matching on a multi-character bank (match_seg_topk.hip): per query the k <= SEG_TOPK_MAX_K nearest rows of its own segment - idx_k
 // (Q,k) local rows ascending by distance, ties to the lower row, -1 where the segment has fewer than k rows; dist_k (Q,k) the distance
@@ -451,7 +467,8 @@ static constexpr int SEG_TOPK_Q = 16;
 size_t match_seg_keys_words(int64_t max_rows);
 hipError_t launch_match_seg_topk(const void* bank, int bank_bf16, const float* query, const int32_t* seg, int Q, const int* seg_start, int S,
                                  int64_t max_rows, int D, unsigned long long* keys, int* plan, const float* enc, int k, float temperature,
-                                 int32_t* idx0, int32_t* idx_k, float* dist_k, float* w_k, float* out, hipStream_t s);
+                                 int32_t* idx0, int32_t* idx_k, float* dist_k, float* w_k, float* out, hipStream_t s,
+                                 const SegAllow* al = nullptr);        // al: rows outside a constrained query's mask count as missing
 // out[q] = src[idx[q]] rows of `cols` floats
 hipError_t launch_gather_rows(const float* src, const int32_t* idx, float* out, int Q, int cols, int64_t nrows, hipStream_t s);
 

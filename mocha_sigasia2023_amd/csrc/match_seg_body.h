@@ -7,6 +7,7 @@
 namespace mocha {
 
 static constexpr int SEG_ROWS = MS_WAVES * MS_ROWS_PER_WAVE;     // rows per scan workgroup
+static_assert(SEG_ROWS == SEG_GRANULE_ROWS, "the host builds one granule word per scan workgroup");
 
 __host__ __device__ inline int seg_blocks_bound(int Q, int S) {      // sum_s ceil(c_s / 8) <= (Q + 7 min(S, Q)) / 8, and <= Q
     const int k = S < Q ? S : Q;
@@ -20,10 +21,14 @@ static constexpr int PLAN_STRIDE = 10;
 // rows [row0, row0 + 4) of this wave, clamped to the segment's last row; qidx: the block's query indices (LDS)
 // ALLKEYS (soft matching): every row's key goes to partial[query][local row] (pstride words per query; ~0 for the workgroup's rows past
 // the segment's end) instead of one minimum per (query, workgroup) to partial[query][blockIdx.x]
-template <int Q, bool BF16, bool ALLKEYS>
+// ALLOW (action-constrained matching): the distance loop is the plain one; at key time row r is a candidate of query q only if its label's
+// bit is in eff[q] (LDS: the query's effective mask, all ones for an unconstrained query), else its key is ~0.  label: one byte per global
+// row.  ALLOW = false reads neither.
+template <int Q, bool BF16, bool ALLKEYS, bool ALLOW = false>
 __device__ __forceinline__ void seg_scan_body(const void* __restrict__ bank, const float* __restrict__ query, const int* qidx, int nq,
                                               long long seg_lo, long long seg_n, long long row0, int D, float* __restrict__ qs,
-                                              unsigned long long (*wbest)[8], unsigned long long* __restrict__ partial, int pstride) {
+                                              unsigned long long (*wbest)[8], unsigned long long* __restrict__ partial, int pstride,
+                                              const unsigned long long* eff = nullptr, const unsigned char* __restrict__ label = nullptr) {
     constexpr int MS_CHUNK = BF16 ? MS_CHUNK_BF16 : MS_CHUNK_F32;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     ms_f32x2 acc[MS_ROWS_PER_WAVE][Q];
@@ -104,16 +109,26 @@ __device__ __forceinline__ void seg_scan_body(const void* __restrict__ bank, con
             }
         }
     }
+    unsigned long long rbit[MS_ROWS_PER_WAVE];         // ALLOW: the label bit of each of this wave's rows (uniform per wave; 0 past the end)
+    if (ALLOW) {
+#pragma unroll
+        for (int r = 0; r < MS_ROWS_PER_WAVE; ++r) {
+            const long long row = row0 + r;
+            rbit[r] = row < seg_n ? 1ull << (label[seg_lo + row] & 63) : 0ull;
+        }
+    }
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
         unsigned long long kmin = ~0ull;
+        const unsigned long long em = ALLOW ? eff[q] : 0ull;
 #pragma unroll
         for (int r = 0; r < MS_ROWS_PER_WAVE; ++r) {
             const long long row = row0 + r;
             float v = acc[r][q][0] + acc[r][q][1];
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-            const unsigned long long k = row < seg_n ? pack_key(v, (unsigned)row) : ~0ull;      // local row: ties to the lowest
+            unsigned long long k = row < seg_n ? pack_key(v, (unsigned)row) : ~0ull;      // local row: ties to the lowest
+            if (ALLOW) k = (rbit[r] & em) ? k : ~0ull;
             if (ALLKEYS) {
                 // row < 16 (blockIdx.x + 1) <= the segment's rows rounded up to 16 <= pstride
                 if (lane == 0 && q < nq) partial[(size_t)qidx[q] * pstride + row] = k;
@@ -135,13 +150,18 @@ __device__ __forceinline__ void seg_scan_body(const void* __restrict__ bank, con
 
 // One scan workgroup: (x, y) scans rows [16 x, 16 x + 16) of block y's segment for the block's queries; a workgroup beyond the block count or
 // past the end of its segment returns at once.  pstride: words per query of `partial` (gridDim.x minima, or the key stride).
-template <bool BF16, bool ALLKEYS>
+// ALLOW: al's masks and tables (kernels.h, SegAllow).  The workgroup forms its queries' effective masks in LDS, and when no query admits
+// any label of its 16 rows (the granule word) it writes ~0 for each query - one minimum, or the 16 row keys, which the finish / top-k
+// kernels read - and returns before the first bank row.
+template <bool BF16, bool ALLKEYS, bool ALLOW = false>
 __device__ __forceinline__ void seg_scan_workgroup(const void* __restrict__ bank, const float* __restrict__ query, const int* __restrict__ plan,
-                                                   const int* __restrict__ seg_start, int D, unsigned long long* __restrict__ partial, int pstride) {
+                                                   const int* __restrict__ seg_start, int D, unsigned long long* __restrict__ partial, int pstride,
+                                                   SegAllow al = SegAllow{}) {
     constexpr int MS_CHUNK = BF16 ? MS_CHUNK_BF16 : MS_CHUNK_F32;
     __shared__ __attribute__((aligned(16))) float qs[8 * MS_CHUNK];
     __shared__ unsigned long long wbest[MS_WAVES][8];
     __shared__ int qidx[8];
+    __shared__ unsigned long long eff[ALLOW ? 8 : 1];
     const int b = blockIdx.y;
     if (b >= plan[0]) return;
     const int* e = plan + 1 + (size_t)b * PLAN_STRIDE;
@@ -152,10 +172,39 @@ __device__ __forceinline__ void seg_scan_workgroup(const void* __restrict__ bank
     if (threadIdx.x < 8) qidx[threadIdx.x] = threadIdx.x < nq ? e[2 + threadIdx.x] : 0;
     // (the body's first barrier orders qidx before its use)
     const long long row0 = x0 + (long long)(threadIdx.x >> 6) * MS_ROWS_PER_WAVE;
-    if (nq == 1) seg_scan_body<1, BF16, ALLKEYS>(bank, query, qidx, nq, lo, n, row0, D, qs, wbest, partial, pstride);
-    else if (nq == 2) seg_scan_body<2, BF16, ALLKEYS>(bank, query, qidx, nq, lo, n, row0, D, qs, wbest, partial, pstride);
-    else if (nq <= 4) seg_scan_body<4, BF16, ALLKEYS>(bank, query, qidx, nq, lo, n, row0, D, qs, wbest, partial, pstride);
-    else seg_scan_body<8, BF16, ALLKEYS>(bank, query, qidx, nq, lo, n, row0, D, qs, wbest, partial, pstride);
+    if (ALLOW) {
+        if (threadIdx.x < 8) {                       // (the thread that wrote qidx[t]) a slot beyond nq admits nothing
+            unsigned long long m = 0ull;
+            if (threadIdx.x < nq) {
+                m = al.allow[e[2 + threadIdx.x]];
+                m = (m & al.any[s]) ? m : ~0ull;     // nothing asked, or no row of those labels: the whole segment
+            }
+            eff[threadIdx.x] = m;
+        }
+        __syncthreads();
+        unsigned long long u = 0ull;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) u |= eff[i];
+        if (!(al.gran[al.gran_start[s] + blockIdx.x] & u)) {       // uniform: no row here is anybody's candidate
+            if (ALLKEYS) {
+                // row < 16 (blockIdx.x + 1) <= the segment's rows rounded up to 16 <= pstride
+                if (threadIdx.x < SEG_ROWS * nq) partial[(size_t)qidx[threadIdx.x / SEG_ROWS] * pstride + x0 + threadIdx.x % SEG_ROWS] = ~0ull;
+            } else if (threadIdx.x < nq) {
+                partial[(size_t)qidx[threadIdx.x] * pstride + blockIdx.x] = ~0ull;
+            }
+            return;
+        }
+    }
+    const unsigned char* lab = ALLOW ? al.label : nullptr;
+    if (nq == 1) seg_scan_body<1, BF16, ALLKEYS, ALLOW>(bank, query, qidx, nq, lo, n, row0, D, qs, wbest, partial, pstride, eff, lab);
+    else if (nq == 2) seg_scan_body<2, BF16, ALLKEYS, ALLOW>(bank, query, qidx, nq, lo, n, row0, D, qs, wbest, partial, pstride, eff, lab);
+    else if (nq <= 4) seg_scan_body<4, BF16, ALLKEYS, ALLOW>(bank, query, qidx, nq, lo, n, row0, D, qs, wbest, partial, pstride, eff, lab);
+    else seg_scan_body<8, BF16, ALLKEYS, ALLOW>(bank, query, qidx, nq, lo, n, row0, D, qs, wbest, partial, pstride, eff, lab);
+}
+
+// applied[q] of the finish / blend kernels: 1 constrained, 0 nothing asked, -1 the segment has no row of the asked labels (fell back)
+__device__ __forceinline__ int seg_allow_applied(unsigned long long mask, unsigned long long any) {
+    return mask == 0ull ? 0 : ((mask & any) ? 1 : -1);
 }
 
 // The squared distance the segmented calls REPORT for a matched row: the direct form summed by the whole workgroup (256 threads) in one

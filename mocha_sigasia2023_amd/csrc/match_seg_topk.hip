@@ -17,6 +17,9 @@
 //    switched off: a staged blend of separate multiplies and adds in the same order has the same bits; w = {1} gives the row itself).
 //    An id outside [0, S): idx -1, dist +inf, w 0, out = encoded[0] (an in-bank row for the decoder, as mocha_match_seg_finish's global
 //    row 0).  No kernel indexes the bank with an id: only with rows inside [0, N).
+// Action-constrained (a SegAllow, kernels.h): step 2 is mocha_match_seg_keys_allow - a row outside a constrained query's mask gets the key
+// ~0, which step 3 already reads as "no row", and a workgroup of inadmissible rows writes its 16 x queries ~0 keys without reading the bank;
+// step 3 also writes applied.  Fewer admissible rows than k: the missing neighbours are -1 / +inf / weight 0.
 #include "kernels.h"
 #include "match_seg_body.h"
 
@@ -30,13 +33,24 @@ __global__ __launch_bounds__(256) void mocha_match_seg_keys(const void* __restri
     seg_scan_workgroup<BF16, true>(bank, query, plan, seg_start, D, keys, kstride);
 }
 
+// the all-keys scan of the action-constrained soft matcher: a row outside a constrained query's mask gets the key ~0 - to the selection
+// below a missing row - and workgroups of inadmissible rows write their 16 x queries ~0 keys without reading the bank
+template <bool BF16>
+__global__ __launch_bounds__(256) void mocha_match_seg_keys_allow(const void* __restrict__ bank, const float* __restrict__ query, const int* __restrict__ plan,
+                                                                  const int* __restrict__ seg_start, int D, unsigned long long* __restrict__ keys, int kstride,
+                                                                  SegAllow al) {
+    seg_scan_workgroup<BF16, true, true>(bank, query, plan, seg_start, D, keys, kstride, al);
+}
+
 // keys: [group's queries][kstride]; idx0 (Q) / idx_k, dist_k, w_k (Q, k) / out (Q, cols4 x 4): each may be null
 template <bool BF16>
 __global__ __launch_bounds__(256) void mocha_seg_topk_blend(const unsigned long long* __restrict__ keys, int kstride, const int32_t* __restrict__ seg, int S,
                                                             const int* __restrict__ seg_start, const void* __restrict__ bank,
                                                             const float* __restrict__ query, int D, const float* __restrict__ enc, int cols4, int k,
                                                             float inv_temp, int32_t* __restrict__ idx0, int32_t* __restrict__ idx_k,
-                                                            float* __restrict__ dist_k, float* __restrict__ w_k, float* __restrict__ out) {
+                                                            float* __restrict__ dist_k, float* __restrict__ w_k, float* __restrict__ out,
+                                                            const unsigned long long* __restrict__ allow, const unsigned long long* __restrict__ any,
+                                                            int32_t* __restrict__ applied) {
     __shared__ unsigned long long wmin[MS_WAVES];
     __shared__ unsigned long long sel[SEG_TOPK_MAX_K];
     __shared__ float red[4];
@@ -52,6 +66,7 @@ __global__ __launch_bounds__(256) void mocha_seg_topk_blend(const unsigned long 
             if (w_k) w_k[(size_t)q * k + tid] = 0.f;
         }
         if (tid == 0 && idx0) idx0[q] = -1;
+        if (tid == 0 && applied) applied[q] = 0;
         if (o) for (int i = tid; i < cols4; i += 256) o[i] = reinterpret_cast<const st_f32x4*>(enc)[i];
         return;
     }
@@ -113,6 +128,7 @@ __global__ __launch_bounds__(256) void mocha_seg_topk_blend(const unsigned long 
             if (w_k) w_k[(size_t)q * k + j] = wj[j];
         }
         if (idx0) idx0[q] = rowj[0] >= 0 ? (int32_t)(rowj[0] - lo) : -1;
+        if (applied) applied[q] = seg_allow_applied(allow[q], any[s]);
     }
     if (!o) return;
     __syncthreads();
@@ -137,8 +153,9 @@ size_t match_seg_keys_words(int64_t max_rows) { return (size_t)SEG_TOPK_Q * (siz
 
 hipError_t launch_match_seg_topk(const void* bank, int bank_bf16, const float* query, const int32_t* seg, int Q, const int* seg_start, int S,
                                  int64_t max_rows, int D, unsigned long long* keys, int* plan, const float* enc, int k, float temperature,
-                                 int32_t* idx0, int32_t* idx_k, float* dist_k, float* w_k, float* out, hipStream_t s) {
+                                 int32_t* idx0, int32_t* idx_k, float* dist_k, float* w_k, float* out, hipStream_t s, const SegAllow* al) {
     if (Q <= 0) return hipSuccess;
+    if (al && (!al->allow || !al->label || !al->any || !al->gran || !al->gran_start)) return hipErrorInvalidValue;
     if (S < 1 || max_rows < 1 || max_rows > 0x7fffffff - SEG_ROWS || D % (bank_bf16 ? MS_CHUNK_BF16 : MS_CHUNK_F32) != 0 || D % 4 != 0 || k < 1 ||
         k > SEG_TOPK_MAX_K || !(temperature > 0.f) || (out && !enc))
         return hipErrorInvalidValue;
@@ -157,14 +174,18 @@ hipError_t launch_match_seg_topk(const void* bank, int bank_bf16, const float* q
         float* dk = dist_k ? dist_k + (size_t)q0 * k : nullptr;
         float* wk = w_k ? w_k + (size_t)q0 * k : nullptr;
         float* op = out ? out + (size_t)q0 * D : nullptr;
+        SegAllow g{};                                   // this group's masks and report
+        if (al) { g = *al; g.allow += q0; if (g.applied) g.applied += q0; }
         if (bank_bf16) {
-            hipLaunchKernelGGL(mocha_match_seg_keys<true>, dim3(gx, gy), dim3(256), 0, s, bank, qp, plan, seg_start, D, keys, kstride);
+            if (al) hipLaunchKernelGGL(mocha_match_seg_keys_allow<true>, dim3(gx, gy), dim3(256), 0, s, bank, qp, plan, seg_start, D, keys, kstride, g);
+            else hipLaunchKernelGGL(mocha_match_seg_keys<true>, dim3(gx, gy), dim3(256), 0, s, bank, qp, plan, seg_start, D, keys, kstride);
             hipLaunchKernelGGL(mocha_seg_topk_blend<true>, dim3(n), dim3(256), 0, s, keys, kstride, sp, S, seg_start, bank, qp, D, enc, D / 4, k, inv_temp,
-                               i0, ik, dk, wk, op);
+                               i0, ik, dk, wk, op, g.allow, g.any, g.applied);
         } else {
-            hipLaunchKernelGGL(mocha_match_seg_keys<false>, dim3(gx, gy), dim3(256), 0, s, bank, qp, plan, seg_start, D, keys, kstride);
+            if (al) hipLaunchKernelGGL(mocha_match_seg_keys_allow<false>, dim3(gx, gy), dim3(256), 0, s, bank, qp, plan, seg_start, D, keys, kstride, g);
+            else hipLaunchKernelGGL(mocha_match_seg_keys<false>, dim3(gx, gy), dim3(256), 0, s, bank, qp, plan, seg_start, D, keys, kstride);
             hipLaunchKernelGGL(mocha_seg_topk_blend<false>, dim3(n), dim3(256), 0, s, keys, kstride, sp, S, seg_start, bank, qp, D, enc, D / 4, k, inv_temp,
-                               i0, ik, dk, wk, op);
+                               i0, ik, dk, wk, op, g.allow, g.any, g.applied);
         }
     }
     return hipGetLastError();

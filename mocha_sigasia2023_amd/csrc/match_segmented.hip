@@ -22,6 +22,12 @@
 //    local row), and the Euclidean distance in the direct form.  An invalid id: local row -1, distance +inf, global row 0 (an
 //    in-bank row for the decoder's gather).  No kernel ever indexes the bank with an id: only with rows inside [0, N).
 // The bank may be fp32 rows or the centred bf16 copy (then with centred queries), as mocha_match_stream<f32|bf16>.
+//
+// Action-constrained matching (launch_match_segmented with a SegAllow, kernels.h): the scan is mocha_match_seg_scan_allow - the same
+// grid, plan and partial minima; a workgroup first forms its queries' effective allow masks and reads ONE granule word (the label bits of
+// its 16 rows): when no query admits any of them it writes ~0 minima and returns before its first bank row, otherwise it runs the plain
+// distance loop and masks at key time.  With labels in runs a constrained pass reads about the admissible rows.  The finish kernel is the
+// plain one and also writes applied (1 constrained / 0 nothing asked / -1 fell back).  The same three launches.
 #include "kernels.h"
 #include "match_seg_body.h"
 
@@ -80,10 +86,22 @@ __global__ __launch_bounds__(256) void mocha_match_seg_scan(const void* __restri
     seg_scan_workgroup<BF16, false>(bank, query, plan, seg_start, D, partial, (int)gridDim.x);
 }
 
+// the action-constrained scan (match_seg_body.h, ALLOW): the same grid, the same partial minima; whole workgroups of inadmissible rows return
+// before their first bank row
+template <bool BF16>
+__global__ __launch_bounds__(256) void mocha_match_seg_scan_allow(const void* __restrict__ bank, const float* __restrict__ query, const int* __restrict__ plan,
+                                                                  const int* __restrict__ seg_start, int D, unsigned long long* __restrict__ partial,
+                                                                  SegAllow al) {
+    seg_scan_workgroup<BF16, false, true>(bank, query, plan, seg_start, D, partial, (int)gridDim.x, al);
+}
+
+// allow / any / applied: the constrained match's masks and its per-query report (all null for the plain match)
 template <bool BF16>
 __global__ __launch_bounds__(256) void mocha_match_seg_finish(const unsigned long long* __restrict__ partial, int pstride, const int32_t* __restrict__ seg, int S,
                                                               const int* __restrict__ seg_start, const void* __restrict__ bank, const float* __restrict__ query, int D,
-                                                              int32_t* __restrict__ idx, int32_t* __restrict__ gidx, float* __restrict__ dist) {
+                                                              int32_t* __restrict__ idx, int32_t* __restrict__ gidx, float* __restrict__ dist,
+                                                              const unsigned long long* __restrict__ allow, const unsigned long long* __restrict__ any,
+                                                              int32_t* __restrict__ applied) {
     __shared__ unsigned long long kred[256];
     __shared__ float red[4];
     const int q = blockIdx.x, tid = threadIdx.x;
@@ -93,6 +111,7 @@ __global__ __launch_bounds__(256) void mocha_match_seg_finish(const unsigned lon
             if (idx) idx[q] = -1;
             if (gidx) gidx[q] = 0;
             if (dist) dist[q] = __builtin_inff();
+            if (applied) applied[q] = 0;
         }
         return;
     }
@@ -113,6 +132,7 @@ __global__ __launch_bounds__(256) void mocha_match_seg_finish(const unsigned lon
     if (tid == 0) {
         if (idx) idx[q] = (int32_t)local;
         if (gidx) gidx[q] = (int32_t)row;
+        if (applied) applied[q] = seg_allow_applied(allow[q], any[s]);
     }
     if (!dist) return;
     const float d2 = seg_direct_dist2<BF16>(bank, query + (size_t)q * D, row, D, red);
@@ -131,18 +151,26 @@ hipError_t launch_seg_plan(const int32_t* seg, int Q, int S, int* plan, hipStrea
 
 hipError_t launch_match_segmented(const void* bank, int bank_bf16, const float* query, const int32_t* seg, int Q, const int* seg_start, int S,
                                   int64_t max_rows, int D, unsigned long long* partial, int* plan, int32_t* idx, int32_t* gidx, float* dist,
-                                  hipStream_t s) {
+                                  hipStream_t s, const SegAllow* al) {
     if (Q <= 0) return hipSuccess;
+    if (al && (!al->allow || !al->label || !al->any || !al->gran || !al->gran_start)) return hipErrorInvalidValue;
     if (Q > SEG_MAX_Q || S < 1 || max_rows < 1 || D % (bank_bf16 ? MS_CHUNK_BF16 : MS_CHUNK_F32) != 0) return hipErrorInvalidValue;
     const unsigned gx = (unsigned)((max_rows + SEG_ROWS - 1) / SEG_ROWS);
     const unsigned gy = (unsigned)seg_blocks_bound(Q, S);
     hipLaunchKernelGGL(mocha_seg_plan, dim3(1), dim3(SEG_PLAN_T), 0, s, seg, Q, S, plan);
+    const unsigned long long* am = al ? al->allow : nullptr;
+    const unsigned long long* an = al ? al->any : nullptr;
+    int32_t* ap = al ? al->applied : nullptr;
     if (bank_bf16) {
-        hipLaunchKernelGGL(mocha_match_seg_scan<true>, dim3(gx, gy), dim3(256), 0, s, bank, query, plan, seg_start, D, partial);
-        hipLaunchKernelGGL(mocha_match_seg_finish<true>, dim3(Q), dim3(256), 0, s, partial, (int)gx, seg, S, seg_start, bank, query, D, idx, gidx, dist);
+        if (al) hipLaunchKernelGGL(mocha_match_seg_scan_allow<true>, dim3(gx, gy), dim3(256), 0, s, bank, query, plan, seg_start, D, partial, *al);
+        else hipLaunchKernelGGL(mocha_match_seg_scan<true>, dim3(gx, gy), dim3(256), 0, s, bank, query, plan, seg_start, D, partial);
+        hipLaunchKernelGGL(mocha_match_seg_finish<true>, dim3(Q), dim3(256), 0, s, partial, (int)gx, seg, S, seg_start, bank, query, D, idx, gidx, dist,
+                           am, an, ap);
     } else {
-        hipLaunchKernelGGL(mocha_match_seg_scan<false>, dim3(gx, gy), dim3(256), 0, s, bank, query, plan, seg_start, D, partial);
-        hipLaunchKernelGGL(mocha_match_seg_finish<false>, dim3(Q), dim3(256), 0, s, partial, (int)gx, seg, S, seg_start, bank, query, D, idx, gidx, dist);
+        if (al) hipLaunchKernelGGL(mocha_match_seg_scan_allow<false>, dim3(gx, gy), dim3(256), 0, s, bank, query, plan, seg_start, D, partial, *al);
+        else hipLaunchKernelGGL(mocha_match_seg_scan<false>, dim3(gx, gy), dim3(256), 0, s, bank, query, plan, seg_start, D, partial);
+        hipLaunchKernelGGL(mocha_match_seg_finish<false>, dim3(Q), dim3(256), 0, s, partial, (int)gx, seg, S, seg_start, bank, query, D, idx, gidx, dist,
+                           am, an, ap);
     }
     return hipGetLastError();
 }

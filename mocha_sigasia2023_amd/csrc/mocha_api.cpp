@@ -155,6 +155,21 @@ struct Bank {
     std::vector<int64_t> seg_start;                    // S + 1 entries; empty = no table
     int64_t seg_max_rows = 0;
     DeviceBuffer<int> seg_dev;
+    // action labels of a multi-character bank's rows (mocha_bank_set_labels), cleared with the segment table: one byte per global row, the
+    // OR of the label bits per segment (lab_any) and per 16 rows of a segment (lab_gran, segment s from word lab_gran_start[s]) - what the
+    // action-constrained scans read (kernels.h, SegAllow)
+    bool labelled = false;
+    DeviceBuffer<unsigned char> lab_dev;
+    DeviceBuffer<unsigned long long> lab_any, lab_gran;
+    DeviceBuffer<int> lab_gran_start;
+};
+
+// The action constraint of a segmented call: per query a 64-bit allow mask (device) and, optionally, where the `applied` report goes.  A null
+// AllowArg* is the plain call.
+struct AllowArg {
+    const unsigned long long* allow = nullptr;
+    int32_t* applied = nullptr;
+    AllowArg at(size_t q0) const { return AllowArg{allow + q0, applied ? applied + q0 : nullptr}; }
 };
 
 }  // namespace
@@ -290,6 +305,8 @@ struct mocha_ctx {
         const void* inert = nullptr; double inert_halflife = 0.0, inert_dt = 0.0;
         // mocha_live_step_raw only: the front end's buffer and the raw frame's arrays; its configuration, which the captured launch carries by value
         const void* ingest[3] = {}; mocha_ingest_cfg icfg{};
+        // the action-constrained steps only: the masks (read by every replay) and the applied report
+        const void* allow[2] = {};
         bool operator==(const StepKey& o) const {
             if (!(x == o.x && mean == o.mean && sd == o.sd && y == o.y && idx == o.idx && seg == o.seg && windows == o.windows && raw == o.raw))
                 return false;
@@ -297,6 +314,7 @@ struct mocha_ctx {
             for (int i = 0; i < 7; ++i) if (ours[i] != o.ours[i]) return false;
             if (noise != o.noise || seed != o.seed) return false;
             if (soft_k != o.soft_k || soft_t != o.soft_t || soft[0] != o.soft[0] || soft[1] != o.soft[1]) return false;
+            if (allow[0] != o.allow[0] || allow[1] != o.allow[1]) return false;
             if (inert != o.inert || inert_halflife != o.inert_halflife || inert_dt != o.inert_dt) return false;
             for (int i = 0; i < 3; ++i) if (ingest[i] != o.ingest[i] || icfg.euler_order[i] != o.icfg.euler_order[i]) return false;
             if (icfg.lookahead != o.icfg.lookahead || icfg.rot_format != o.icfg.rot_format || icfg.unit_scale != o.icfg.unit_scale ||
@@ -317,7 +335,8 @@ struct mocha_ctx {
     } step[MAX_SETS], seg_step, live_step, ours_step, // seg_step: mocha_step_graph_segmented, live_step: mocha_live_step, ours_step: mocha_live_step_ours (workspace set 0)
       soft_step, live_soft_step,                      // mocha_step_graph_soft_segmented, mocha_live_step_soft (workspace set 0)
       live_inert_step,                                // mocha_live_step_inert, hard or soft (workspace set 0)
-      live_raw_step[3];                               // mocha_live_step_raw: hard, soft, inertialized (workspace set 0)
+      live_raw_step[3],                               // mocha_live_step_raw: hard, soft, inertialized (workspace set 0)
+      seg_allow_step, live_allow_step, live_raw_allow_step;      // mocha_step_graph_segmented_allow, mocha_live_step_allow, mocha_live_step_raw_allow
     hipStream_t cap_stream = nullptr;                 // capture happens on this internal stream (the caller's may be the null stream)
     ncclComm_t comm = nullptr; int comm_rank = 0, comm_size = 1;      // mocha_comm_init
     DeviceBuffer<long long> bcast_hdr;                                  // device: {entries, bf16?} header of mocha_bank_broadcast
@@ -1307,10 +1326,18 @@ int ensure_seg_scratch(mocha_ctx* c, int set) {
     return rc;
 }
 
+// the kernels' view of a constraint: the caller's masks and report with the current bank's label tables
+SegAllow seg_allow_of(mocha_ctx* c, const AllowArg& a) {
+    return SegAllow{a.allow, c->bank.lab_dev.p, c->bank.lab_any.p, c->bank.lab_gran.p, c->bank.lab_gran_start.p, a.applied};
+}
+
 // Exact 1-NN of every query within its own segment (match_segmented.hip), in launches of up to c->seg_q queries.  q: the z-scored queries
 // (fp32 bank) or the queries minus the union's centroid (bf16 bank).  idx: local rows (or null), gidx: global rows (or null).
-int seg_match(mocha_ctx* c, const float* q, int Q, const int32_t* seg, int32_t* idx, int32_t* gidx, float* dist, hipStream_t s) {
+// al: the action constraint (the ALLOW scan), or null
+int seg_match(mocha_ctx* c, const float* q, int Q, const int32_t* seg, int32_t* idx, int32_t* gidx, float* dist, hipStream_t s,
+              const AllowArg* al = nullptr) {
     if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (al && !c->bank.labelled) return fail(c, MOCHA_ERR_STATE, "no action labels: call mocha_bank_set_labels first");
     const int set = c->cur, S = (int)c->bank.seg_start.size() - 1;
     const int D = 90 * 256;
     if (!c->sets[set].seg_partial.p || !c->sets[set].seg_plan.p)
@@ -1318,11 +1345,13 @@ int seg_match(mocha_ctx* c, const float* q, int Q, const int32_t* seg, int32_t* 
     const void* bank = c->bank.is_bf16 ? (const void*)c->bank.bf16.p : (const void*)c->bank.cnt;
     for (int q0 = 0; q0 < Q; q0 += c->seg_q) {
         const int n = std::min(c->seg_q, Q - q0);
+        SegAllow sa{};
+        if (al) sa = seg_allow_of(c, al->at(q0));
         LAUNCH(c, s, c->bank.is_bf16 ? "mocha_match_seg_scan<bf16>" : "mocha_match_seg_scan<f32>", "match.segmented", 3.0 * n * c->bank.seg_max_rows * D,
                (double)n * c->bank.seg_max_rows * D * (c->bank.is_bf16 ? 2.0 : 4.0) + 4.0 * n * D,
                launch_match_segmented(bank, c->bank.is_bf16 ? 1 : 0, q + (size_t)q0 * D, seg + q0, n, c->bank.seg_dev.p, S, c->bank.seg_max_rows, D,
                                       c->sets[set].seg_partial.p, c->sets[set].seg_plan.p, idx ? idx + q0 : nullptr, gidx ? gidx + q0 : nullptr,
-                                      dist ? dist + q0 : nullptr, s));
+                                      dist ? dist + q0 : nullptr, s, al ? &sa : nullptr));
     }
     return 0;
 }
@@ -1331,8 +1360,11 @@ int seg_match(mocha_ctx* c, const float* q, int Q, const int32_t* seg, int32_t* 
 // q as for seg_match; idx0 (Q) / idx_k, dist_k, w_k (Q,k) / out (Q,90,256), each may be null.  One pass over the queries' segments per 16
 // queries, through the key buffer of the current workspace set.
 int seg_topk(mocha_ctx* c, const float* q, int Q, const int32_t* seg, int k, float temperature, int32_t* idx0, int32_t* idx_k, float* dist_k,
-             float* w_k, float* out, hipStream_t s) {
+             float* w_k, float* out, hipStream_t s, const AllowArg* al = nullptr) {
     if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (al && !c->bank.labelled) return fail(c, MOCHA_ERR_STATE, "no action labels: call mocha_bank_set_labels first");
+    SegAllow sa{};
+    if (al) sa = seg_allow_of(c, *al);
     const int set = c->cur, S = (int)c->bank.seg_start.size() - 1;
     const int D = 90 * 256;
     if (!c->sets[set].seg_keys.p || !c->sets[set].seg_plan.p)
@@ -1343,7 +1375,7 @@ int seg_topk(mocha_ctx* c, const float* q, int Q, const int32_t* seg, int k, flo
     LAUNCH(c, s, b16 ? "mocha_match_seg_keys<bf16>" : "mocha_match_seg_keys<f32>", "match.soft", 3.0 * Q * c->bank.seg_max_rows * D + 2.0 * Q * k * D,
            passes * c->bank.seg_max_rows * D * (b16 ? 2.0 : 4.0) + 16.0 * Q * c->bank.seg_max_rows + Q * (k * (b16 ? 6.0 : 8.0) + 8.0) * D,
            launch_match_seg_topk(bank, b16 ? 1 : 0, q, seg, Q, c->bank.seg_dev.p, S, c->bank.seg_max_rows, D, c->sets[set].seg_keys.p,
-                                 c->sets[set].seg_plan.p, c->bank.enc, k, temperature, idx0, idx_k, dist_k, w_k, out, s));
+                                 c->sets[set].seg_plan.p, c->bank.enc, k, temperature, idx0, idx_k, dist_k, w_k, out, s, al ? &sa : nullptr));
     return 0;
 }
 
@@ -1415,7 +1447,8 @@ void mocha_destroy(mocha_ctx* c) {
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     for (auto* g : {&c->step[0], &c->step[1], &c->step[2], &c->seg_step, &c->live_step, &c->ours_step, &c->soft_step, &c->live_soft_step,
-                    &c->live_inert_step, &c->live_raw_step[0], &c->live_raw_step[1], &c->live_raw_step[2]}) {
+                    &c->live_inert_step, &c->live_raw_step[0], &c->live_raw_step[1], &c->live_raw_step[2], &c->seg_allow_step,
+                    &c->live_allow_step, &c->live_raw_allow_step}) {
         if (g->exec) (void)hipGraphExecDestroy(g->exec);
         if (g->graph) (void)hipGraphDestroy(g->graph);
     }
@@ -1831,6 +1864,7 @@ static int bank_set_impl(mocha_ctx* c, Bank& b, const float* cnt_nm, const float
     b.N = N;
     b.is_bf16 = (flags & MOCHA_BANK_BF16) != 0;
     b.seg_start.clear(); b.seg_max_rows = 0;              // a plain bank has no segment table (mocha_bank_set_segments sets it after)
+    b.labelled = false;                                   // ... and no action labels (mocha_bank_set_labels)
     b.tiled_valid = false; b.tile32_valid = false;
     if (current) c->generation++;                         // a captured step has the previous bank's pointers and row count baked in
     // match scratch for every query count the workspace admits: a later match never allocates (capture-safe)
@@ -1958,7 +1992,7 @@ int mocha_bank_gather(mocha_ctx* c, const int32_t* idx, int Q, float* out, void*
 // seg != null (mocha_characterize_segmented): every window is matched within its own segment of a multi-character bank; idx then receives
 // the local rows and the decoder gathers through the global rows the matcher leaves in the workspace's index buffer
 static int characterize_impl(mocha_ctx* c, const float* src_X, int B, const float* cnt_mean, const float* cnt_std, float* Y,
-                             int32_t* idx, void* stream, bool raw, const int32_t* seg = nullptr) {
+                             int32_t* idx, void* stream, bool raw, const int32_t* seg = nullptr, const AllowArg* al = nullptr) {
     int rc = ready(c, B); if (rc) return rc;
     if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
     if (seg && c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
@@ -1977,7 +2011,9 @@ static int characterize_impl(mocha_ctx* c, const float* src_X, int B, const floa
             if (c->bank.is_bf16) { ex.centre = c->bank.center.p; ex.zc = WS(c, "qc"); }
             LAUNCH(c, s, "mocha_instnorm", "mvn", 0.0, b * 90.0 * 256 * 4 * (c->bank.is_bf16 ? 3.0 : 2.0), launch_instnorm(WS(c, "enc_s"), nullptr, nullptr, cnt_mean, cnt_std, WS(c, "qnm"), b, 90, s, &ex));
             int32_t* gx = SET(c).idx_ws.p;
-            if ((r = seg_match(c, WS(c, c->bank.is_bf16 ? "qc" : "qnm"), b, seg + b0, idx ? idx + b0 : nullptr, gx, nullptr, s))) return r;
+            AllowArg ab;
+            if (al) ab = al->at(b0);
+            if ((r = seg_match(c, WS(c, c->bank.is_bf16 ? "qc" : "qnm"), b, seg + b0, idx ? idx + b0 : nullptr, gx, nullptr, s, al ? &ab : nullptr))) return r;
             if ((r = run_decoder(c, WS(c, "enc_s"), nullptr, b, WS(c, "dec"), s, c->bank.enc, gx, c->bank.N,
                                  c->bank.dec_valid ? c->bank.kin.p : nullptr, c->bank.dec_valid ? c->bank.gb.p : nullptr))) return r;
             return run_to_mot(c, WS(c, "dec"), b, Y + b0 * ys, s, raw);
@@ -2248,7 +2284,8 @@ static int soft_args(mocha_ctx* c, const char* what, int k, float temperature) {
 // embed -> encoder -> cnt, z-score (bf16 bank: centred queries) -> k nearest + weights + blend into the "sel" workspace -> literal decoder on
 // the blend -> to_mot.  idx0 (B) / idx_k, w_k (B,k): each may be null.  The caller checked k and temperature.
 static int characterize_soft_impl(mocha_ctx* c, const float* src_X, int B, const int32_t* seg, int k, float temperature, const float* cnt_mean,
-                                  const float* cnt_std, float* Y, int32_t* idx0, int32_t* idx_k, float* w_k, bool raw, void* stream) {
+                                  const float* cnt_std, float* Y, int32_t* idx0, int32_t* idx_k, float* w_k, bool raw, void* stream,
+                                  const AllowArg* al = nullptr) {
     int rc = ready(c, B); if (rc) return rc;
     if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
     if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
@@ -2263,8 +2300,11 @@ static int characterize_soft_impl(mocha_ctx* c, const float* src_X, int B, const
         InormExtra ex = IEXW(c, s);
         if (c->bank.is_bf16) { ex.centre = c->bank.center.p; ex.zc = WS(c, "qc"); }
         LAUNCH(c, s, "mocha_instnorm", "mvn", 0.0, b * 90.0 * 256 * 4 * (c->bank.is_bf16 ? 3.0 : 2.0), launch_instnorm(WS(c, "enc_s"), nullptr, nullptr, cnt_mean, cnt_std, WS(c, "qnm"), b, 90, s, &ex));
+        AllowArg ab;
+        if (al) ab = al->at(b0);
         if ((r = seg_topk(c, WS(c, c->bank.is_bf16 ? "qc" : "qnm"), b, seg + b0, k, temperature, idx0 ? idx0 + b0 : nullptr,
-                          idx_k ? idx_k + (size_t)b0 * k : nullptr, nullptr, w_k ? w_k + (size_t)b0 * k : nullptr, WS(c, "sel"), s))) return r;
+                          idx_k ? idx_k + (size_t)b0 * k : nullptr, nullptr, w_k ? w_k + (size_t)b0 * k : nullptr, WS(c, "sel"), s,
+                          al ? &ab : nullptr))) return r;
         if ((r = run_decoder(c, WS(c, "enc_s"), WS(c, "sel"), b, WS(c, "dec"), s))) return r;
         return run_to_mot(c, WS(c, "dec"), b, Y + b0 * ys, s, raw);
     });
@@ -2325,6 +2365,129 @@ int mocha_step_graph_soft_segmented(mocha_ctx* c, const float* X, int S_w, const
     }
     // the ids are read by the captured kernels on every replay: new ids in `seg` are not part of the key; k and the temperature are
     return step_replay(c, c->soft_step, key, (hipStream_t)stream, body);
+}
+
+// ------------------------------------------------------------------------------------------- action-constrained matching
+// Every row of a multi-character bank carries an action label 0..63 (mocha_bank_set_labels), every query a 64-bit allow mask: the match is
+// the exact nearest neighbour(s) among the rows of the query's segment whose label is allowed; a zero mask, or one that names no label the
+// segment holds, takes the plain answer (match_seg_body.h, the ALLOW scans).  The calls below are the segmented ones with an AllowArg.
+int mocha_bank_set_labels(mocha_ctx* c, const int32_t* labels, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!labels) { c->bank.labelled = false; c->generation++; return 0; }
+    const int S = (int)c->bank.seg_start.size() - 1;
+    const int64_t N = c->bank.N;
+    for (int64_t i = 0; i < N; ++i)
+        if (labels[i] < 0 || labels[i] > 63) return fail(c, MOCHA_ERR_ARG, "bank_set_labels: label %d of row %lld is outside 0..63", (int)labels[i], (long long)i);
+    std::vector<unsigned char> lab((size_t)N);
+    std::vector<unsigned long long> any((size_t)S, 0ull), gran;
+    std::vector<int> gstart((size_t)S + 1, 0);
+    for (int s = 0; s < S; ++s) {
+        const int64_t lo = c->bank.seg_start[s], n = c->bank.seg_start[s + 1] - lo;
+        gstart[s + 1] = gstart[s] + (int)((n + SEG_GRANULE_ROWS - 1) / SEG_GRANULE_ROWS);
+        gran.resize((size_t)gstart[s + 1], 0ull);
+        for (int64_t r = 0; r < n; ++r) {
+            const unsigned long long bit = 1ull << labels[lo + r];
+            lab[(size_t)(lo + r)] = (unsigned char)labels[lo + r];
+            any[s] |= bit;
+            gran[(size_t)gstart[s] + (size_t)(r / SEG_GRANULE_ROWS)] |= bit;
+        }
+    }
+    // everything a constrained call reads exists from here on: none of them allocates (their scratch is the segmented matcher's)
+    c->bank.labelled = false;
+    int rc = reserve(c, c->bank.lab_dev, lab.size());
+    if (!rc) rc = reserve(c, c->bank.lab_any, any.size());
+    if (!rc) rc = reserve(c, c->bank.lab_gran, gran.size());
+    if (!rc) rc = reserve(c, c->bank.lab_gran_start, gstart.size());
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(c, hipMemcpyAsync(c->bank.lab_dev.p, lab.data(), lab.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->bank.lab_any.p, any.data(), any.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->bank.lab_gran.p, gran.data(), gran.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->bank.lab_gran_start.p, gstart.data(), gstart.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipStreamSynchronize(s));                  // (the host vectors go out of scope)
+    c->bank.labelled = true;
+    c->generation++;                                     // a captured constrained step has the previous tables baked in
+    return 0;
+}
+
+int mocha_match_segmented_allow(mocha_ctx* c, const float* query_nm, int Q, const int32_t* seg, const uint64_t* allow, int k, int32_t* idx,
+                                float* dist, int32_t* applied, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (k < 1 || k > MOCHA_SOFT_MAX_K) return fail(c, MOCHA_ERR_ARG, "match_segmented_allow: 1 <= k <= %d neighbours", MOCHA_SOFT_MAX_K);
+    int rc = ready(c, 0); if (rc) return rc;
+    if (!query_nm || !seg || !allow || !idx || Q < 0) return fail(c, MOCHA_ERR_ARG, "bad match_segmented_allow arguments");
+    if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (!c->bank.labelled) return fail(c, MOCHA_ERR_STATE, "no action labels: call mocha_bank_set_labels first");
+    if (Q == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int D = 90 * 256;
+    c->cur = 0;
+    const AllowArg al{reinterpret_cast<const unsigned long long*>(allow), applied};
+    // k = 1: the hard matcher; k >= 2: the top-k matcher.  q: z-scored (fp32 bank) or centred (bf16 bank) queries
+    auto match = [&](const float* q, int q0, int n) -> int {
+        const AllowArg a = al.at(q0);
+        if (k == 1) return seg_match(c, q, n, seg + q0, idx + q0, nullptr, dist ? dist + q0 : nullptr, s, &a);
+        return seg_topk(c, q, n, seg + q0, k, 1.f, nullptr, idx + (size_t)q0 * k, dist ? dist + (size_t)q0 * k : nullptr, nullptr, nullptr, s, &a);
+    };
+    if (!c->bank.is_bf16) return match(query_nm, 0, Q);
+    // the bf16 copy holds bf16(b - centroid of the union): centred queries, as many at a time as the centred-query buffer holds
+    const int per = (int)std::min<size_t>((size_t)c->seg_q, c->sets[0].match_qc.n / D);
+    for (int q0 = 0; q0 < Q; q0 += per) {
+        const int n = std::min(per, Q - q0);
+        LAUNCH(c, s, "mocha_sub_rows", "match.center", 0.0, 8.0 * n * D, launch_sub_rows(query_nm + (size_t)q0 * D, c->bank.center.p, c->sets[0].match_qc.p, n, D, s));
+        if ((rc = match(c->sets[0].match_qc.p, q0, n))) return rc;
+    }
+    return 0;
+}
+
+// k = 0: the hard characterize (idx_k holds B entries, w_k unused); k >= 1: the soft one
+static int characterize_allow_impl(mocha_ctx* c, const float* X, int B, const int32_t* seg, const AllowArg& al, int k, float temperature,
+                                   const float* cnt_mean, const float* cnt_std, float* Y, int32_t* idx_k, float* w_k, bool raw, void* stream) {
+    if (k == 0) return characterize_impl(c, X, B, cnt_mean, cnt_std, Y, idx_k, stream, raw, seg, &al);
+    return characterize_soft_impl(c, X, B, seg, k, temperature, cnt_mean, cnt_std, Y, nullptr, idx_k, w_k, raw, stream, &al);
+}
+
+int mocha_characterize_segmented_allow(mocha_ctx* c, const float* src_X, int B, const int32_t* seg, const uint64_t* allow, int k, float temperature,
+                                       const float* cnt_mean, const float* cnt_std, float* Y, int32_t* idx_k, float* w_k, int32_t* applied,
+                                       int raw, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (k != 0) { int rc = soft_args(c, "characterize_segmented_allow", k, temperature); if (rc) return rc; }
+    if (B > 0 && (!seg || !allow)) return fail(c, MOCHA_ERR_ARG, "characterize_segmented_allow: null argument");
+    if (!c->bank.seg_start.empty() && !c->bank.labelled) return fail(c, MOCHA_ERR_STATE, "no action labels: call mocha_bank_set_labels first");
+    const AllowArg al{reinterpret_cast<const unsigned long long*>(allow), applied};
+    return characterize_allow_impl(c, src_X, B, seg, al, k, temperature, cnt_mean, cnt_std, Y, idx_k, w_k, raw != 0, stream);
+}
+
+int mocha_step_graph_segmented_allow(mocha_ctx* c, const float* X, int S_w, const int32_t* seg, const uint64_t* allow, int k, float temperature,
+                                     const float* cnt_mean, const float* cnt_std, float* Y, int32_t* idx_k, float* w_k, int32_t* applied, int raw,
+                                     void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (k != 0) { int rc = soft_args(c, "step_graph_segmented_allow", k, temperature); if (rc) return rc; }
+    if (S_w < 1 || S_w > 16) return fail(c, MOCHA_ERR_ARG, "step_graph_segmented_allow: 1 <= S_w <= 16 windows");
+    int rc = ready(c, S_w); if (rc) return rc;
+    if (!X || !seg || !allow || !cnt_mean || !cnt_std || !Y || !idx_k || (k > 0 && !w_k)) return fail(c, MOCHA_ERR_ARG, "null argument");
+    if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
+    if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (!c->bank.labelled) return fail(c, MOCHA_ERR_STATE, "no action labels: call mocha_bank_set_labels first");
+    const AllowArg al{reinterpret_cast<const unsigned long long*>(allow), applied};
+    mocha_ctx::StepKey key; key.x = X; key.mean = cnt_mean; key.sd = cnt_std; key.y = Y; key.seg = seg; key.windows = S_w; key.raw = raw != 0;
+    key.soft_k = k; key.soft_t = k > 0 ? temperature : 0.f; key.soft[0] = idx_k; key.soft[1] = k > 0 ? w_k : nullptr;
+    key.allow[0] = allow; key.allow[1] = applied;
+    auto body = [&](hipStream_t cs) -> int {
+        c->lane = 0;
+        const int r = characterize_allow_impl(c, X, S_w, seg, al, k, temperature, cnt_mean, cnt_std, Y, idx_k, w_k, raw != 0, cs);
+        c->cur = 0;
+        return r;
+    };
+    const auto& g = c->seg_allow_step;
+    if (k > 0 && !(g.exec && g.key == key && g.generation == c->generation)) {
+        // as mocha_step_graph_soft_segmented: the soft step once, eagerly, before a capture (first-use images of its kernels)
+        if ((rc = body((hipStream_t)stream))) return rc;
+    }
+    // the ids and the masks are read by the captured kernels on every replay: new values in `seg` / `allow` are not part of the key
+    return step_replay(c, c->seg_allow_step, key, (hipStream_t)stream, body);
 }
 
 // ------------------------------------------------------------------------------------------- RCCL (multi-GPU set-up)
@@ -2949,7 +3112,7 @@ static int live_step_impl(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, i
                           const int32_t* seg, const float* cnt_mean, const float* cnt_std, double* pos, double* rot, double* ik_rot, double* bvh_pos,
                           double* bvh_euler, int32_t* idx, int32_t* valid, int k, float temperature, int32_t* idx_k, float* w_k, void* stream,
                           void* inert = nullptr, const mocha_inert_cfg* icfg = nullptr, const IngestParams* ing = nullptr,
-                          const mocha_ingest_cfg* ing_cfg = nullptr) {
+                          const mocha_ingest_cfg* ing_cfg = nullptr, const AllowArg* al = nullptr) {
     if (streams < 1 || streams > 16) return fail(c, MOCHA_ERR_ARG, "live_step: 1 <= streams <= 16");
     if (!live || !Yrot || !Ypos || !Yvel || !Yang || !src_rvel || !src_rang || !src_speed || !contact || !seg || !cnt_mean || !cnt_std || !pos ||
         !rot || !ik_rot || !idx || !valid || (!bvh_pos) != (!bvh_euler))
@@ -2958,6 +3121,7 @@ static int live_step_impl(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, i
     if (!c->pose_norm.p) return fail(c, MOCHA_ERR_STATE, "live_step: no pose norm: call mocha_set_pose_norm first");
     if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set_segments first");
     if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (al && !c->bank.labelled) return fail(c, MOCHA_ERR_STATE, "no action labels: call mocha_bank_set_labels first");
     mocha_post_cfg d;
     if (!cfg) { mocha_post_cfg_default(&d); cfg = &d; }
     PostParams p{};
@@ -2987,8 +3151,8 @@ static int live_step_impl(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, i
     // the segmented characterize of the S staging windows with the ids in eff: hard, or soft with column 0 of idx_k in idx
     auto characterize = [&](int32_t* ix, int32_t* ixk, float* wk, hipStream_t cs) -> int {
         c->lane = 0;
-        const int r = k > 0 ? characterize_soft_impl(c, xraw, streams, eff, k, temperature, cnt_mean, cnt_std, ystage, ix, ixk, wk, true, cs)
-                            : characterize_impl(c, xraw, streams, cnt_mean, cnt_std, ystage, ix, cs, true, eff);
+        const int r = k > 0 ? characterize_soft_impl(c, xraw, streams, eff, k, temperature, cnt_mean, cnt_std, ystage, ix, ixk, wk, true, cs, al)
+                            : characterize_impl(c, xraw, streams, cnt_mean, cnt_std, ystage, ix, cs, true, eff, al);
         c->cur = 0;
         return r;
     };
@@ -3023,7 +3187,9 @@ static int live_step_impl(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, i
     key.soft_k = k; key.soft_t = k > 0 ? temperature : 0.f; key.soft[0] = k > 0 ? idx_k : nullptr; key.soft[1] = k > 0 ? w_k : nullptr;
     if (inert) { key.inert = inert; key.inert_halflife = icfg->halflife; key.inert_dt = icfg->dt; }
     if (ing) { key.ingest[0] = ing->state; key.ingest[1] = ing->rot; key.ingest[2] = ing->pos; key.icfg = *ing_cfg; }
-    mocha_ctx::StepGraph& g = ing ? c->live_raw_step[inert ? 2 : k > 0 ? 1 : 0] : inert ? c->live_inert_step : k > 0 ? c->live_soft_step : c->live_step;
+    if (al) { key.allow[0] = al->allow; key.allow[1] = al->applied; }
+    mocha_ctx::StepGraph& g = al ? (ing ? c->live_raw_allow_step : c->live_allow_step)
+                                 : ing ? c->live_raw_step[inert ? 2 : k > 0 ? 1 : 0] : inert ? c->live_inert_step : k > 0 ? c->live_soft_step : c->live_step;
     if (!(g.exec && g.key == key && g.generation == c->generation)) {
         // Before a capture: one eager characterize of the staging windows with every id -1 (no bank row is matched, no state of the
         // session moves), so that whatever the kernels of the step make on first use - the plane GEMMs' weight images, for the soft step
@@ -3100,6 +3266,27 @@ int mocha_live_step_inert(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, i
     return live_step_impl(c, cfg, live, streams, Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, seg, cnt_mean, cnt_std, pos, rot,
                           ik_rot, bvh_pos, bvh_euler, idx, valid, k, k > 0 ? temperature : 0.f, k > 0 ? idx_k : nullptr, k > 0 ? w_k : nullptr,
                           stream, inert, &ic);
+}
+
+// mocha_live_step_inert's arguments (inert may be NULL: no inertializer; k = 0: the hard matcher) with the streams' allow masks: the
+// characterize of the step is the action-constrained one.  A warming stream has the id -1 and so applied 0.
+int mocha_live_step_allow(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos, const float* Yvel,
+                          const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed, const unsigned char* contact,
+                          const int32_t* seg, const float* cnt_mean, const float* cnt_std, int k, float temperature, double* pos, double* rot,
+                          double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx, int32_t* valid, int32_t* idx_k, float* w_k, void* stream,
+                          void* inert, const mocha_inert_cfg* icfg, const uint64_t* allow, int32_t* applied) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (k != 0) {
+        int rc = soft_args(c, "live_step_allow", k, temperature); if (rc) return rc;
+        if (!idx_k || !w_k) return fail(c, MOCHA_ERR_ARG, "live_step_allow: null argument");
+    }
+    if (!allow) return fail(c, MOCHA_ERR_ARG, "live_step_allow: null allow masks");
+    mocha_inert_cfg ic{};
+    if (inert) { int rc = inert_cfg(c, "live_step_allow", icfg, ic); if (rc) return rc; }
+    const AllowArg al{reinterpret_cast<const unsigned long long*>(allow), applied};
+    return live_step_impl(c, cfg, live, streams, Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, seg, cnt_mean, cnt_std, pos, rot,
+                          ik_rot, bvh_pos, bvh_euler, idx, valid, k, k > 0 ? temperature : 0.f, k > 0 ? idx_k : nullptr, k > 0 ? w_k : nullptr,
+                          stream, inert, inert ? &ic : nullptr, nullptr, nullptr, &al);
 }
 
 }  // extern "C"
@@ -3270,21 +3457,23 @@ int mocha_live_ingest_step(mocha_ctx* c, const mocha_ingest_cfg* cfg, const moch
     return 0;
 }
 
-int mocha_live_step_raw(mocha_ctx* c, const mocha_post_cfg* cfg, const mocha_ingest_cfg* icfg_in, void* live, void* ingest, int streams,
-                        const float* rot, const float* pos, const int32_t* seg, const float* cnt_mean, const float* cnt_std, int k,
-                        float temperature, double* pos_out, double* rot_out, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx,
-                        int32_t* valid, int32_t* idx_k, float* w_k, void* stream, void* inert, const mocha_inert_cfg* icfg) {
+// mocha_live_step_raw (al = null) and mocha_live_step_raw_allow: one body
+static int live_step_raw_impl(mocha_ctx* c, const char* who, const mocha_post_cfg* cfg, const mocha_ingest_cfg* icfg_in, void* live, void* ingest,
+                              int streams, const float* rot, const float* pos, const int32_t* seg, const float* cnt_mean, const float* cnt_std, int k,
+                              float temperature, double* pos_out, double* rot_out, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx,
+                              int32_t* valid, int32_t* idx_k, float* w_k, void* stream, void* inert, const mocha_inert_cfg* icfg,
+                              const AllowArg* al) {
     if (!c) return MOCHA_ERR_ARG;
-    if (streams < 1 || streams > 16) return fail(c, MOCHA_ERR_ARG, "live_step_raw: 1 <= streams <= 16");
-    if (!ingest || !rot || !pos) return fail(c, MOCHA_ERR_ARG, "live_step_raw: null argument");
+    if (streams < 1 || streams > 16) return fail(c, MOCHA_ERR_ARG, "%s: 1 <= streams <= 16", who);
+    if (!ingest || !rot || !pos) return fail(c, MOCHA_ERR_ARG, "%s: null argument", who);
     if (k != 0) {
-        int rc = soft_args(c, "live_step_raw", k, temperature); if (rc) return rc;
-        if (!idx_k || !w_k) return fail(c, MOCHA_ERR_ARG, "live_step_raw: null argument");
+        int rc = soft_args(c, who, k, temperature); if (rc) return rc;
+        if (!idx_k || !w_k) return fail(c, MOCHA_ERR_ARG, "%s: null argument", who);
     }
     mocha_inert_cfg ic{};
-    if (inert) { int rc = inert_cfg(c, "live_step_raw", icfg, ic); if (rc) return rc; }
+    if (inert) { int rc = inert_cfg(c, who, icfg, ic); if (rc) return rc; }
     IngestParams p{};
-    int rc = ingest_params(c, "live_step_raw", icfg_in, cfg, p); if (rc) return rc;
+    int rc = ingest_params(c, who, icfg_in, cfg, p); if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     if ((rc = ensure_ingest_rows(c))) return rc;
     const IngestLayout l = ingest_layout(c, streams);
@@ -3297,7 +3486,27 @@ int mocha_live_step_raw(mocha_ctx* c, const mocha_post_cfg* cfg, const mocha_ing
     p.contact = reinterpret_cast<unsigned char*>(base + l.contact); p.have = reinterpret_cast<int32_t*>(base + l.have);
     return live_step_impl(c, cfg, live, streams, p.Yrot, p.Ypos, p.Yvel, p.Yang, p.src_rvel, p.src_rang, p.src_speed, p.contact, seg, cnt_mean,
                           cnt_std, pos_out, rot_out, ik_rot, bvh_pos, bvh_euler, idx, valid, k, k > 0 ? temperature : 0.f, k > 0 ? idx_k : nullptr,
-                          k > 0 ? w_k : nullptr, stream, inert, inert ? &ic : nullptr, &p, icfg_in);
+                          k > 0 ? w_k : nullptr, stream, inert, inert ? &ic : nullptr, &p, icfg_in, al);
+}
+
+int mocha_live_step_raw(mocha_ctx* c, const mocha_post_cfg* cfg, const mocha_ingest_cfg* icfg_in, void* live, void* ingest, int streams,
+                        const float* rot, const float* pos, const int32_t* seg, const float* cnt_mean, const float* cnt_std, int k,
+                        float temperature, double* pos_out, double* rot_out, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx,
+                        int32_t* valid, int32_t* idx_k, float* w_k, void* stream, void* inert, const mocha_inert_cfg* icfg) {
+    return live_step_raw_impl(c, "live_step_raw", cfg, icfg_in, live, ingest, streams, rot, pos, seg, cnt_mean, cnt_std, k, temperature, pos_out,
+                              rot_out, ik_rot, bvh_pos, bvh_euler, idx, valid, idx_k, w_k, stream, inert, icfg, nullptr);
+}
+
+int mocha_live_step_raw_allow(mocha_ctx* c, const mocha_post_cfg* cfg, const mocha_ingest_cfg* icfg_in, void* live, void* ingest, int streams,
+                              const float* rot, const float* pos, const int32_t* seg, const float* cnt_mean, const float* cnt_std, int k,
+                              float temperature, double* pos_out, double* rot_out, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx,
+                              int32_t* valid, int32_t* idx_k, float* w_k, void* stream, void* inert, const mocha_inert_cfg* icfg,
+                              const uint64_t* allow, int32_t* applied) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (!allow) return fail(c, MOCHA_ERR_ARG, "live_step_raw_allow: null allow masks");
+    const AllowArg al{reinterpret_cast<const unsigned long long*>(allow), applied};
+    return live_step_raw_impl(c, "live_step_raw_allow", cfg, icfg_in, live, ingest, streams, rot, pos, seg, cnt_mean, cnt_std, k, temperature, pos_out,
+                              rot_out, ik_rot, bvh_pos, bvh_euler, idx, valid, idx_k, w_k, stream, inert, icfg, &al);
 }
 
 }  // extern "C"

@@ -34,10 +34,15 @@ class LiveSession:
     time taken from ``post``); a stream that never switches gets the bits of ``inertial=None``.
     ``raw=IngestConfig(...)`` or ``raw=lookahead``: the session also takes RAW mocap frames (``push_raw``: local rotations and positions of
     the V joints) - the mocap front end (``ingest.py``, ``mocha_live_step_raw``) runs inside the same captured graph and produces what
-    ``push`` takes; a stream emits its first frame on its 31st raw push, so ``valid`` first becomes 1 on push 90."""
+    ``push`` takes; a stream emits its first frame on its 31st raw push, so ``valid`` first becomes 1 on push 90.
+    ``constrained=True`` (a bank with action labels): every stream carries a 64-bit allow mask of admissible actions in ``self.allow``
+    ((S,) int64 on the device; ``push(..., allow=)``, ``set_allow`` or written in place) and is matched among its character's entries of those actions
+    (``mocha_live_step_allow`` / ``mocha_live_step_raw_allow``); the outputs gain ``applied`` (S,): 1 constrained, 0 nothing asked or
+    warming, -1 the character has no such entry and the whole character was searched.  With zero masks the session gives the plain
+    session's bits.  A change of the allowed actions is not inertialized (``soft=`` softens it)."""
 
     def __init__(self, bank: MultiCharacterBank, cnt_mean, cnt_std, streams: int = 1, post: Optional[PostProcessor] = None, bvh: bool = True,
-                 soft=None, inertial: Optional[float] = None, raw=None):
+                 soft=None, inertial: Optional[float] = None, raw=None, constrained: bool = False):
         if not 1 <= int(streams) <= 16:
             raise ValueError("streams must be 1..16")
         self.bank, self.model = bank, bank.model
@@ -93,6 +98,12 @@ class LiveSession:
         if self.soft is not None:
             self.out["idx_k"] = torch.full((S, self.soft[0]), -1, dtype=torch.int32, device=dev)
             self.out["weight"] = torch.zeros((S, self.soft[0]), dtype=torch.float32, device=dev)
+        self.constrained = bool(constrained)
+        if self.constrained:
+            if bank.labels is None:
+                raise RuntimeError("LiveSession: constrained=True needs a bank with action labels (MultiCharacterBank(labels=))")
+            self.allow = torch.zeros((S,), dtype=torch.int64, device=dev)
+            self.out["applied"] = torch.zeros((S,), dtype=torch.int32, device=dev)
         bank._ensure()
 
     @property
@@ -106,12 +117,23 @@ class LiveSession:
             raise ValueError(f"LiveSession.push: {name} has {t.numel()} values, expected {tuple(buf.shape)}")
         buf.copy_(t.reshape(buf.shape), non_blocking=True)
 
-    def push(self, Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, characters=None):
+    def set_allow(self, allow):
+        """New allow masks for the next step (constrained sessions), one per stream - an int mask, an iterable of labels or None each, or
+        one int for all; checked on the host, copied into ``self.allow``.  ``push(..., allow=)`` calls this; before ``push_raw`` call it
+        yourself (or write ``self.allow`` in place)."""
+        if not self.constrained:
+            raise RuntimeError("LiveSession: allow= needs a session created with constrained=True")
+        self.allow.copy_(self.bank._allow(allow, self.streams, "LiveSession"), non_blocking=True)
+
+    def push(self, Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, characters=None, allow=None):
         """The new frame of every stream: Yrot (S,V+1,4) (w,x,y,z), Ypos / Yvel / Yang (S,V+1,3), root bone first; src_rvel / src_rang
         (S,3), src_speed (S,), contact (S,n_contact) of that frame [, characters: one id per stream; default: the ids already set].
         Returns the session's own device tensors - pos (S,V+1,3), rot / ik_rot (S,V+1,4), (bvh_pos / bvh_euler (S,V,3)), idx (S,) the
         matched row local to the stream's character (-1 while warming up), valid (S,) - overwritten by the next push.  Rows of a stream
-        with valid == 0 are not written.  No host synchronisation."""
+        with valid == 0 are not written.  No host synchronisation.  ``allow`` (constrained sessions): new allow masks, one per stream -
+        an int mask, an iterable of labels or None each, or one int for all; default: the masks already set."""
+        if allow is not None:
+            self.set_allow(allow)
         if characters is not None:
             self.ids.copy_(self.bank._ids(characters, self.streams), non_blocking=True)
         for a, buf, name in ((Yrot, self.rot, "Yrot"), (Ypos, self.pos, "Ypos"), (Yvel, self.vel, "Yvel"), (Yang, self.ang, "Yang"),
@@ -143,6 +165,14 @@ class LiveSession:
         self.bank._ensure()
         o = self.out
         k, t = self.soft if self.soft is not None else (0, 0.0)
+        if self.constrained:
+            self.model._ctx.call("mocha_live_step_raw_allow", C.byref(self.post.cfg), C.byref(self.rcfg), _ptr(self.live), _ptr(self.ingest),
+                                 self.streams, _ptr(self.raw_rot), _ptr(self.raw_pos), _ptr(self.ids), _ptr(self.mean), _ptr(self.std), k, t,
+                                 _ptr(o["pos"]), _ptr(o["rot"]), _ptr(o["ik_rot"]), _ptr(o["bvh_pos"]) if self.bvh else None,
+                                 _ptr(o["bvh_euler"]) if self.bvh else None, _ptr(o["idx"]), _ptr(o["valid"]), _ptr(o.get("idx_k")),
+                                 _ptr(o.get("weight")), _stream(), _ptr(self.inert) if self.inert is not None else None,
+                                 C.byref(self.icfg) if self.icfg is not None else None, _ptr(self.allow), _ptr(o["applied"]))
+            return o
         self.model._ctx.call("mocha_live_step_raw", C.byref(self.post.cfg), C.byref(self.rcfg), _ptr(self.live), _ptr(self.ingest), self.streams,
                              _ptr(self.raw_rot), _ptr(self.raw_pos), _ptr(self.ids), _ptr(self.mean), _ptr(self.std), k, t, _ptr(o["pos"]),
                              _ptr(o["rot"]), _ptr(o["ik_rot"]), _ptr(o["bvh_pos"]) if self.bvh else None,
@@ -155,6 +185,16 @@ class LiveSession:
         """The step on what the fixed buffers hold (a producer on the device may have written them in place)."""
         self.bank._ensure()
         o = self.out
+        if self.constrained:
+            k, t = self.soft if self.soft is not None else (0, 0.0)
+            self.model._ctx.call("mocha_live_step_allow", C.byref(self.post.cfg), _ptr(self.live), self.streams, _ptr(self.rot), _ptr(self.pos),
+                                 _ptr(self.vel), _ptr(self.ang), _ptr(self.rvel), _ptr(self.rang), _ptr(self.speed), _ptr(self.contact),
+                                 _ptr(self.ids), _ptr(self.mean), _ptr(self.std), k, t, _ptr(o["pos"]), _ptr(o["rot"]),
+                                 _ptr(o["ik_rot"]), _ptr(o["bvh_pos"]) if self.bvh else None, _ptr(o["bvh_euler"]) if self.bvh else None,
+                                 _ptr(o["idx"]), _ptr(o["valid"]), _ptr(o.get("idx_k")), _ptr(o.get("weight")), _stream(),
+                                 _ptr(self.inert) if self.inert is not None else None, C.byref(self.icfg) if self.icfg is not None else None,
+                                 _ptr(self.allow), _ptr(o["applied"]))
+            return o
         if self.inert is not None:
             k, t = self.soft if self.soft is not None else (0, 0.0)
             self.model._ctx.call("mocha_live_step_inert", C.byref(self.post.cfg), _ptr(self.live), self.streams, _ptr(self.rot), _ptr(self.pos),
@@ -251,7 +291,9 @@ class LiveOursSession(LiveSession):
 
     def __init__(self, bank: MultiCharacterBank, cnt_mean, cnt_std, cvae_state_dict, src_cnt_mean, src_cnt_std, cha_encoded_mean,
                  cha_encoded_std, streams: int = 1, post: Optional[PostProcessor] = None, bvh: bool = True, noise: str = "device",
-                 seed: int = 0, soft=None, inertial=None, raw=None):
+                 seed: int = 0, soft=None, inertial=None, raw=None, constrained: bool = False):
+        if constrained:
+            raise ValueError("LiveOursSession: constrained=True is not supported - the branch's seed match searches the whole character")
         if raw is not None:
             raise ValueError("LiveOursSession: raw= is not supported - the CVAE branch's step has no mocap front end; run an Ingestor and "
                              "push its emitted frames")

@@ -5,6 +5,11 @@ every character's bank as one row segment of a single bank on one context.  Each
 (``characters``: one id per window); the match is the exact 1-NN within that character's rows only, and the returned index is the row
 LOCAL to that character's bank, as ``BallTree(that character's cnt_nm).query(k=1)`` and ``ContextBank(that character).query`` return it.
 Encoding, z-score, gather, decoder and to_mot are the batched kernels of ``ContextBank.characterize``.
+
+Action-constrained matching: a bank built with ``labels`` (one action label 0 .. 63 per entry, e.g. ``load_bank(path)["action_label"]``)
+accepts ``allow=`` in ``query`` / ``characterize`` / ``step``: per query a 64-bit mask of admissible actions (``action_mask``).  The match is
+then the exact nearest entry among that character's entries of those actions; a zero mask asks for nothing, and a mask naming no action
+the character has falls back to the whole character (``applied``: 1 / 0 / -1).
 """
 from __future__ import annotations
 
@@ -18,6 +23,56 @@ from .generator import DIM, NTOK, Generator, _dev_f32, _ptr, _stream
 
 _BORROW, _BF16, _NO_DEC_CACHE = 1, 2, 4          # mocha_bank_set flags (include/mocha_hip.h)
 SOFT_MAX_K = 8                                   # MOCHA_SOFT_MAX_K
+
+
+def action_mask(actions) -> int:
+    """The 64-bit allow mask of a set of action labels: bit ``a`` set for every label ``a`` in ``actions`` (an iterable of integers, or one
+    integer).  ``ValueError`` for a label outside 0 .. 63.  An empty set gives 0: nothing asked."""
+    if isinstance(actions, (int, np.integer)):
+        actions = [actions]
+    m = 0
+    for a in actions:
+        if isinstance(a, (bool, np.bool_)) or not isinstance(a, (int, np.integer)):
+            raise ValueError(f"action_mask: integer labels expected, got {a!r}")
+        if not 0 <= int(a) <= 63:
+            raise ValueError(f"action_mask: label {int(a)} is outside 0 .. 63")
+        m |= 1 << int(a)
+    return m
+
+
+def _mask_of(entry, who: str) -> int:
+    """One query's ``allow`` entry -> its mask: None (0), an int bit pattern 0 .. 2**64 - 1, or an iterable of labels."""
+    if entry is None:
+        return 0
+    if isinstance(entry, (int, np.integer)) and not isinstance(entry, (bool, np.bool_)):
+        if not 0 <= int(entry) < 1 << 64:
+            raise ValueError(f"{who}: an allow mask must lie in 0 .. 2**64 - 1")
+        return int(entry)
+    return action_mask(entry)
+
+
+def allow_masks(allow, n: int, device, who: str) -> torch.Tensor:
+    """``allow`` -> the (n,) int64 device tensor of bit patterns the constrained calls read.  A device int64 tensor is taken as it is (the
+    caller's to keep meaningful); an int is one mask for all n queries; any other sequence holds one entry per query, each an int mask,
+    an iterable of labels, or None.  Host data is checked here, before anything is launched."""
+    if isinstance(allow, torch.Tensor) and allow.device.type != "cpu":
+        if allow.dtype != torch.int64:
+            raise ValueError(f"{who}: a device allow tensor must be int64 (the masks' bit patterns)")
+        t = allow.reshape(-1).to(device).contiguous()
+        if t.shape[0] != n:
+            raise ValueError(f"{who}: {t.shape[0]} allow masks for {n} queries")
+        return t
+    if isinstance(allow, torch.Tensor):
+        allow = allow.tolist()
+    if isinstance(allow, (int, np.integer)) and not isinstance(allow, (bool, np.bool_)):
+        masks = [_mask_of(allow, who)] * n
+    else:
+        entries = list(allow)
+        if len(entries) != n:
+            raise ValueError(f"{who}: {len(entries)} allow entries for {n} queries")
+        masks = [_mask_of(e, who) for e in entries]
+    signed = [m - (1 << 64) if m >= 1 << 63 else m for m in masks]          # the bit pattern as int64
+    return torch.tensor(signed, dtype=torch.int64).to(device)
 
 
 def soft_params(soft, who: str):
@@ -38,9 +93,11 @@ def soft_params(soft, who: str):
 class MultiCharacterBank:
     """``banks``: a sequence of ``(cnt_nm, encoded)`` pairs, one per character (cnt_nm (N_c, 90*256) z-scored with the SAME global
     cnt_mean / cnt_std as every other character, encoded (N_c, 90, 256)).  They are concatenated once into device tensors this object
-    owns and lends to the context.  ``bf16`` / ``dec_cache`` mean what they mean for ``ContextBank``."""
+    owns and lends to the context.  ``bf16`` / ``dec_cache`` mean what they mean for ``ContextBank``.  ``labels``: one integer array
+    (N_c,) of action labels 0 .. 63 per character (``set_labels``)."""
 
-    def __init__(self, model: Generator, banks: Sequence[Tuple[torch.Tensor, torch.Tensor]], bf16: bool = False, dec_cache: bool = True):
+    def __init__(self, model: Generator, banks: Sequence[Tuple[torch.Tensor, torch.Tensor]], bf16: bool = False, dec_cache: bool = True,
+                 labels=None):
         model._need()
         self.model = model
         if len(banks) < 1:
@@ -62,6 +119,7 @@ class MultiCharacterBank:
         self.seg_start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         self._bf16 = bool(bf16)
         self._dec_cache = bool(dec_cache)
+        self.labels = None if labels is None else self._check_labels(labels)
         self.activate()
 
     def rows(self, c: int) -> Tuple[int, int]:
@@ -76,7 +134,47 @@ class MultiCharacterBank:
         seg = (C.c_int64 * (self.S + 1))(*self.seg_start.tolist())
         self.model._ctx.call("mocha_bank_set_segments", _ptr(self.cnt_nm), _ptr(self.encoded), self.N, seg, self.S, flags, _stream())
         self.model._bank = self
+        self._send_labels()
         return self
+
+    def _check_labels(self, labels) -> np.ndarray:
+        if len(labels) != self.S:
+            raise ValueError(f"labels: {len(labels)} arrays for {self.S} characters")
+        out = []
+        for c, lab in enumerate(labels):
+            a = lab.cpu().numpy() if isinstance(lab, torch.Tensor) else np.asarray(lab)
+            a = a.reshape(-1)
+            n = int(self.seg_start[c + 1] - self.seg_start[c])
+            if a.shape[0] != n:
+                raise ValueError(f"labels[{c}]: {a.shape[0]} labels for {n} entries")
+            if not np.issubdtype(a.dtype, np.integer):
+                raise ValueError(f"labels[{c}]: integer labels expected, got {a.dtype}")
+            if a.min() < 0 or a.max() > 63:
+                raise ValueError(f"labels[{c}]: labels must lie in 0 .. 63")
+            out.append(a.astype(np.int32))
+        return np.ascontiguousarray(np.concatenate(out))
+
+    def _send_labels(self):
+        if self.labels is None:
+            return
+        self.model._ctx.call("mocha_bank_set_labels", self.labels.ctypes.data_as(C.POINTER(C.c_int32)), _stream())
+
+    def set_labels(self, labels):
+        """Action labels of every character's entries (one integer array (N_c,) per character, 0 .. 63), or None to remove them.
+        ``allow=`` needs them."""
+        self._ensure()
+        if labels is None:
+            self.labels = None
+            self.model._ctx.call("mocha_bank_set_labels", None, _stream())
+            return self
+        self.labels = self._check_labels(labels)
+        self._send_labels()
+        return self
+
+    def _allow(self, allow, n: int, who: str) -> torch.Tensor:
+        if self.labels is None:
+            raise RuntimeError(f"{who}: allow= needs a bank with action labels (MultiCharacterBank(labels=) or set_labels)")
+        return allow_masks(allow, n, self.model.device, who)
 
     def _ensure(self):
         if getattr(self.model, "_bank", None) is not self:
@@ -102,16 +200,29 @@ class MultiCharacterBank:
             raise ValueError(f"characters: {ids.shape[0]} ids for {n} queries")
         return ids
 
-    def query(self, query_nm, characters, k: int = 1):
+    def query(self, query_nm, characters, k: int = 1, allow=None, return_applied: bool = False):
         """Exact 1-NN of each query within its character's rows -> (dist (Q,1), idx (Q,1)), idx local to that character's bank.
         ``k > 1`` (up to 8): the k nearest rows of that character, nearest first, ties to the lower row -> (dist (Q,k), idx (Q,k)); a
-        character with fewer than k rows gives idx -1 / dist +inf in the columns it cannot fill (``mocha_match_topk_segmented``)."""
+        character with fewer than k rows gives idx -1 / dist +inf in the columns it cannot fill (``mocha_match_topk_segmented``).
+        ``allow`` (see ``allow_masks``): the match among the rows of each query's admissible actions (``mocha_match_segmented_allow``);
+        fewer than k such rows leave -1 / +inf; ``return_applied`` adds applied (Q,) int32: 1 constrained, 0 nothing asked, -1 fell back."""
         self._ensure()
         q = _dev_f32(query_nm, self.model.device, None, "query").reshape(-1, NTOK * DIM)
         Q = q.shape[0]
         ids = self._ids(characters, Q)
         if int(k) != k or not 1 <= int(k) <= SOFT_MAX_K:
             raise ValueError(f"query: k must be an integer in 1 .. {SOFT_MAX_K}")
+        if allow is not None:
+            k = int(k)
+            masks = self._allow(allow, Q, "query")
+            idx = torch.empty((Q, k), dtype=torch.int32, device=q.device)
+            dist = torch.empty((Q, k), dtype=torch.float32, device=q.device)
+            applied = torch.empty((Q,), dtype=torch.int32, device=q.device)
+            self.model._ctx.call("mocha_match_segmented_allow", _ptr(q), Q, _ptr(ids), _ptr(masks), k, _ptr(idx), _ptr(dist), _ptr(applied),
+                                 _stream())
+            return (dist, idx, applied) if return_applied else (dist, idx)
+        if return_applied:
+            raise ValueError("query: return_applied needs allow=")
         if k > 1:
             k = int(k)
             idx = torch.empty((Q, k), dtype=torch.int32, device=q.device)
@@ -123,8 +234,10 @@ class MultiCharacterBank:
         self.model._ctx.call("mocha_match_segmented", _ptr(q), Q, _ptr(ids), _ptr(idx), _ptr(dist), _stream())
         return dist[:, None], idx[:, None]
 
-    def characterize(self, src_X, characters, cnt_mean, cnt_std, return_index: bool = False, raw: bool = False, soft=None):
-        """``ContextBank.characterize`` with every window matched against its own character: Y (B,T,V,C) [, idx (B,) local rows].
+    def characterize(self, src_X, characters, cnt_mean, cnt_std, return_index: bool = False, raw: bool = False, soft=None, allow=None):
+        """``allow`` (see ``allow_masks``): every window matched among its character's entries of the admissible actions
+        (``mocha_characterize_segmented_allow``); with ``return_index`` the outputs gain applied (B,) int32 at the end.
+        ``ContextBank.characterize`` with every window matched against its own character: Y (B,T,V,C) [, idx (B,) local rows].
         ``soft=(k, temperature)``: the decoder reads the softmax(-dist / temperature)-weighted blend of the window's k nearest entries
         instead of the nearest one (``mocha_characterize_soft_segmented``); with ``return_index`` -> (Y, idx_k (B,k), weight (B,k))."""
         self._ensure()
@@ -136,6 +249,17 @@ class MultiCharacterBank:
         std = _dev_f32(cnt_std, m.device, (NTOK, DIM), "cnt_std")
         Y = torch.empty((B, m.cfg["nframes"], m.V, m.cfg["mot_in_dim"]), dtype=torch.float32, device=m.device)
         sp = soft_params(soft, "characterize")
+        if allow is not None:
+            masks = self._allow(allow, B, "characterize")
+            k, t = sp if sp is not None else (0, 0.0)
+            idx_k = torch.empty((B, k) if k else (B,), dtype=torch.int32, device=m.device)
+            w_k = torch.empty((B, k), dtype=torch.float32, device=m.device) if k else None
+            applied = torch.empty((B,), dtype=torch.int32, device=m.device)
+            m._ctx.call("mocha_characterize_segmented_allow", _ptr(X), B, _ptr(ids), _ptr(masks), k, t, _ptr(mean), _ptr(std), _ptr(Y),
+                        _ptr(idx_k), _ptr(w_k) if k else None, _ptr(applied), 1 if raw else 0, _stream())
+            if not return_index:
+                return Y
+            return (Y, idx_k, w_k, applied) if k else (Y, idx_k, applied)
         if sp is not None:
             k, t = sp
             idx_k = torch.empty((B, k), dtype=torch.int32, device=m.device)
@@ -153,9 +277,12 @@ class MultiStreamCharacterizer:
     the ``streams`` windows captured once into a HIP graph (``mocha_step_graph_segmented``) and replayed.  The character of each stream
     may change from step to step: the ids live in a device buffer the graph reads, so a change does not re-capture.
     ``soft=(k, temperature)``: the soft characterize (``mocha_step_graph_soft_segmented``); ``step`` then returns
-    (Y, idx_k (streams,k), weight (streams,k))."""
+    (Y, idx_k (streams,k), weight (streams,k)).
+    ``constrained=True``: the action-constrained step (``mocha_step_graph_segmented_allow``); ``allow`` is then a (streams,) int64 device
+    tensor of allow masks the graph reads - a producer may write it in place, new masks do not re-capture - and ``step`` returns
+    ``applied`` (streams,) int32 as its last output."""
 
-    def __init__(self, bank: MultiCharacterBank, cnt_mean, cnt_std, streams: int, raw: bool = False, soft=None):
+    def __init__(self, bank: MultiCharacterBank, cnt_mean, cnt_std, streams: int, raw: bool = False, soft=None, constrained: bool = False):
         if not 1 <= streams <= 16:
             raise ValueError("streams must be 1..16")
         self.bank, self.model = bank, bank.model
@@ -174,6 +301,12 @@ class MultiStreamCharacterizer:
         if self.soft is not None:
             self.idx_k = torch.full((self.streams, self.soft[0]), -1, dtype=torch.int32, device=m.device)
             self.weight = torch.zeros((self.streams, self.soft[0]), dtype=torch.float32, device=m.device)
+        self.constrained = bool(constrained)
+        if self.constrained:
+            if bank.labels is None:
+                raise RuntimeError("MultiStreamCharacterizer: constrained=True needs a bank with action labels")
+            self.allow = torch.zeros((self.streams,), dtype=torch.int64, device=m.device)
+            self.applied = torch.zeros((self.streams,), dtype=torch.int32, device=m.device)
         bank._ensure()
 
     @property
@@ -186,14 +319,25 @@ class MultiStreamCharacterizer:
         """The captured step's own character ids (streams,) int32 on the device: a producer may write them in place and call ``step()``."""
         return self.ids
 
-    def step(self, windows: Optional[torch.Tensor] = None, characters=None):
+    def step(self, windows: Optional[torch.Tensor] = None, characters=None, allow=None):
         """windows (streams, 60, V, 15) [, characters: one id per stream] -> (Y (streams, 60, V, 15) view, idx (streams,) view); both are
-        overwritten by the next step.  Without arguments the windows and ids already in ``input`` / ``characters`` are used."""
+        overwritten by the next step.  Without arguments the windows and ids already in ``input`` / ``characters`` are used.
+        ``allow`` (constrained only): new allow masks, one per stream (see ``allow_masks``), copied into ``self.allow``."""
+        if allow is not None:
+            if not self.constrained:
+                raise RuntimeError("step: allow= needs MultiStreamCharacterizer(constrained=True)")
+            self.allow.copy_(self.bank._allow(allow, self.streams, "step"), non_blocking=True)
         if characters is not None:
             self.ids.copy_(self.bank._ids(characters, self.streams), non_blocking=True)
         if windows is not None:
             self.x.copy_(windows.reshape(self.x.shape), non_blocking=True)
         self.bank._ensure()
+        if self.constrained:
+            k, t = self.soft if self.soft is not None else (0, 0.0)
+            self.model._ctx.call("mocha_step_graph_segmented_allow", _ptr(self.x), self.streams, _ptr(self.ids), _ptr(self.allow), k, t,
+                                 _ptr(self.mean), _ptr(self.std), _ptr(self.y), _ptr(self.idx_k if k else self.idx),
+                                 _ptr(self.weight) if k else None, _ptr(self.applied), 1 if self.raw else 0, _stream())
+            return (self.y, self.idx_k, self.weight, self.applied) if k else (self.y, self.idx, self.applied)
         if self.soft is not None:
             self.model._ctx.call("mocha_step_graph_soft_segmented", _ptr(self.x), self.streams, _ptr(self.ids), self.soft[0], self.soft[1],
                                  _ptr(self.mean), _ptr(self.std), _ptr(self.y), _ptr(self.idx_k), _ptr(self.weight), 1 if self.raw else 0,

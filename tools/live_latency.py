@@ -153,6 +153,51 @@ def soft(a, dev, model, mb, mean, std, clip, per, J):
     return res
 
 
+def constrained(a, dev, model, mb, mean, std, clip, per, J):
+    """--constrained: the plain live step and the action-constrained one with zero masks (LiveSession(constrained=True) =
+    mocha_live_step_allow: the same launches, the scan reads the masks and one granule word), alternating in one process; then the same
+    with every stream allowing one action of 16 (labels in runs of 128 rows)."""
+    from mocha_sigasia2023_amd import LiveSession
+    mb.set_labels([(np.arange(2048) // 128).astype(np.int32)] * 8)
+    res = {"bank": "8 characters x 2048 rows, fp32, segmented, labels in runs of 128 rows (16 actions)", "layout": "mocha (24 joints)",
+           "timing": "HIP events around single graph replays; (a) live step, (b) constrained live step with zero masks, (c) constrained live "
+                     "step with one action of 16 allowed per stream, alternating", "streams": {}}
+    for S in (1, 8):
+        ids = torch.tensor([(k * 3) % 8 for k in range(S)], dtype=torch.int32)
+        plain = LiveSession(mb, mean, std, streams=S)
+        zero = LiveSession(mb, mean, std, streams=S, constrained=True)
+        one = LiveSession(mb, mean, std, streams=S, constrained=True)
+        one.allow.copy_(torch.tensor([1 << (k % 16) for k in range(S)], dtype=torch.int64))
+        frame = [0]
+
+        def push():
+            f = frame[0] % 644; frame[0] += 1
+            for sess in (plain, zero, one):
+                sess.rot.copy_(clip[0][f]); sess.pos.copy_(clip[1][f]); sess.vel.copy_(clip[2][f]); sess.ang.copy_(clip[3][f])
+                sess.rvel.copy_(per[0][f]); sess.rang.copy_(per[1][f]); sess.speed.copy_(per[2][f]); sess.contact.copy_(per[3][f])
+        for sess in (plain, zero, one):
+            sess.characters.copy_(ids)
+        for _ in range(max(a.warmup, 70)):
+            push(); plain.replay(); zero.replay(); one.replay()
+        torch.cuda.synchronize()
+        assert bool((zero.out["valid"] == 1).all()) and torch.equal(zero.out["idx"], plain.out["idx"]) and bool((one.out["applied"] == 1).all())
+        # the two constrained sessions share ONE captured graph slot of the context (keyed on the session's buffers): alternating them
+        # would capture again at every replay, so each is measured in its own pass, alternating with the plain step
+        ta, tb, tc = [], [], []
+        for sess, t in ((zero, tb), (one, tc)):
+            for _ in range(10):
+                push(); sess.replay()
+            for _ in range(a.reps):
+                push(); torch.cuda.synchronize()
+                ta.append(event_ms(plain.replay, 1)[0]); t.append(event_ms(sess.replay, 1)[0])
+        e = {"a_live_step": pct(np.asarray(ta)), "b_live_step_allow_zero_masks": pct(np.asarray(tb)), "c_live_step_allow_one_of_16": pct(np.asarray(tc))}
+        e["b_minus_a_p50_ms"] = e["b_live_step_allow_zero_masks"]["p50_ms"] - e["a_live_step"]["p50_ms"]
+        e["c_minus_a_p50_ms"] = e["c_live_step_allow_one_of_16"]["p50_ms"] - e["a_live_step"]["p50_ms"]
+        res["streams"][str(S)] = e
+        del plain, zero, one
+    return res
+
+
 def inertial(a, dev, model, mb, mean, std, clip, per, J):
     """--inertial H: the plain live step and the inertialized one (half-life H seconds), alternating in one process."""
     from mocha_sigasia2023_amd import LiveSession
@@ -250,7 +295,10 @@ def main():
     ap.add_argument("--soft", type=int, default=0, metavar="K", help="soft matching: live step / soft live step with K neighbours, temperature 2")
     ap.add_argument("--inertial", type=float, default=None, metavar="H", help="inertialized switches: live step / live step with half-life H seconds")
     ap.add_argument("--raw", type=int, default=None, metavar="L", help="raw mocap input: live step / raw live step with L frames of lookahead")
+    ap.add_argument("--constrained", action="store_true", help="action-constrained matching: live step / constrained live step with zero masks / one action of 16")
     a = ap.parse_args()
+    if a.constrained and a.out == ap.get_default("out"):
+        a.out = os.path.join(ROOT, "profiles", "r15", "live_allow_step.json")
     if a.raw is not None and a.out == ap.get_default("out"):
         a.out = os.path.join(ROOT, "profiles", "r13", "live_raw_step.json")
     if a.inertial is not None and a.out == ap.get_default("out"):
@@ -278,6 +326,8 @@ def main():
     per = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (rvel, rang, np.linalg.norm(hipvel, axis=-1).mean(-1).astype(np.float32), contact)]
     res = {"bank": "8 characters x 2048 rows, fp32, segmented", "layout": "mocha (24 joints)", "timing": "HIP events around single graph replays, live and baseline alternating",
            "streams": {}}
+    if a.constrained:
+        return write_out(a, constrained(a, dev, model, mb, mean, std, clip, per, J))
     if a.raw is not None:
         return write_out(a, raw(a, dev, model, mb, mean, std, clip, per, J))
     if a.inertial is not None:
