@@ -17,6 +17,12 @@ and the reference's clip preparation runs on the device as well:
 The source's per-window inputs of the post-processing are then its own: root-local velocities of each window's last frame, the mean hip
 speed of the window, the contacts of its last frame (test_fullframework.py:142-143, :493).  The pair call's output and the windows are
 also written to <out>/from_raw.npz.
+
+With --src-bvh A --cha-bvh B the same route starts from two BVH FILES (source, character; the 24-joint 'mocha' skeleton in file order,
+at least 31 frames each): load_bvh reads the hierarchy on the host and parses the MOTION text on the device, and its two arrays go into
+ingest_clips with the files' rotation order and frame rate.  A clip of n frames gives n - 15 windows; --frames is ignored.
+
+    file  --load_bvh-->  raw clip  --ingest_clips-->  ...  as --from-raw, <out>/from_raw.npz included
 """
 import argparse
 import os
@@ -36,7 +42,13 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--frames", type=int, default=120, help="windows per clip (the demo clips have 585)")
 ap.add_argument("--out", default="gpurun_out/demo")
 ap.add_argument("--from-raw", action="store_true", help="start from raw mocap clips: ingest_clips -> clip_windows -> featurize")
+ap.add_argument("--src-bvh", help="the source clip as a BVH file (with --cha-bvh): the --from-raw route on files")
+ap.add_argument("--cha-bvh", help="the character clip as a BVH file")
 a = ap.parse_args()
+if bool(a.src_bvh) != bool(a.cha_bvh):
+    ap.error("--src-bvh and --cha-bvh go together")
+if a.src_bvh:
+    a.from_raw = True
 os.makedirs(a.out, exist_ok=True)
 dev = torch.device("cuda:0")
 N = a.frames
@@ -56,11 +68,20 @@ stats = [(0.1 * rng.standard_normal((90, 256))).astype(np.float32), rng.uniform(
 # ---- the two clips as local bone features of N sixty-frame windows each                      :120-140, 203-222
 if a.from_raw:
     from mocha_sigasia2023_amd import clip_windows, ingest_clips  # noqa: E402
-    if N < 16:
-        ap.error("--from-raw needs at least 16 windows per clip: a clip of N + 15 frames gives N windows, and 31 frames are the least")
-    raw = [synthetic.raw_walk_clip(LAYOUTS["mocha"]["parents"], N + 15, seed=s) for s in (11, 12)]        # source, character
-    clips = ingest_clips(model, np.concatenate([r for r, _ in raw]), np.concatenate([p for _, p in raw]), [N + 15, N + 15])
-    win = clip_windows(clips, [N + 15, N + 15], window=60, step=1)      # N windows per clip, the last 44 padded
+    if a.src_bvh:
+        from mocha_sigasia2023_amd import IngestConfig, load_bvh  # noqa: E402
+        files = load_bvh(model, [a.src_bvh, a.cha_bvh])
+        if len(files.names) != model.V or min(files.lengths) < 31:
+            ap.error(f"the files must hold the {model.V} joints of the model's skeleton and at least 31 frames each")
+        lengths, N = files.lengths, files.lengths[0] - 15
+        clips = ingest_clips(model, files.rot, files.pos, lengths, raw=IngestConfig(order=files.order, fps=round(1.0 / files.frametime)))
+    else:
+        if N < 16:
+            ap.error("--from-raw needs at least 16 windows per clip: a clip of N + 15 frames gives N windows, and 31 frames are the least")
+        raw = [synthetic.raw_walk_clip(LAYOUTS["mocha"]["parents"], N + 15, seed=s) for s in (11, 12)]        # source, character
+        lengths = [N + 15, N + 15]
+        clips = ingest_clips(model, np.concatenate([r for r, _ in raw]), np.concatenate([p for _, p in raw]), lengths)
+    win = clip_windows(clips, lengths, window=60, step=1)      # n - 15 windows per clip, the last 44 padded
     src_bones = tuple(win[k][:N] for k in ("Yrot", "Ypos", "Yvel", "Yang"))
     cha_bones = tuple(win[k][N:] for k in ("Yrot", "Ypos", "Yvel", "Yang"))
     rot0, vel0, ang0 = (win[k][:N, -1, 0].double().cpu().numpy() for k in ("Yrot", "Yvel", "Yang"))

@@ -600,7 +600,7 @@ int mocha_live_step_ours(mocha_ctx* ctx, const mocha_post_cfg* cfg, void* live, 
  * NumPy, so they may sit one fp32 ulp away from its values.  Everything else is float64 on the fp32 inputs, rounded to fp32 once.
  * Inherited from the reference, not fixed: between([0,0,1], d) is singular for a character facing exactly -z; contacts flip at a hard
  * threshold.  A stream never emits the last `lookahead` frames of a clip and does not mirror: whole clips, mirrored or not, go through
- * mocha_ingest_clips below, which emits every frame.  Not provided: BVH text parsing.
+ * mocha_ingest_clips below, which emits every frame.  BVH text is read by mocha_bvh_header / mocha_bvh_motion further down.
  *   mocha_ingest_cfg_default : the reference's constants (lookahead 0, Euler degrees in 'zyx' channel order, unit scale 0.01: cm -> m,
  *                            60 frames per second, threshold 0.5 m/s) and the role joints of `layout`: 0 ('mocha': Spine2 = 7, shoulders
  *                            9 / 16, upper legs 1 / 20), 1 ('mixamo' of this library's 22-joint table: 3, 6 / 10, 18 / 14).
@@ -688,7 +688,7 @@ int mocha_live_step_raw_allow(mocha_ctx* ctx, const mocha_post_cfg* cfg, const m
  * (savgol_filter(window_length=31) raises there); clip_offsets that do not start at 0 or do not increase; a mirror flag set while
  * mirror_map is NULL; a mirror_map that is no involution or does not commute with the parents; window < 4 or step < 1.
  * Inherited from the reference: the singular -z heading; contacts flip at a hard threshold (generate_database_bin.py uses 0.2 m/s,
- * process_data 0.5: cfg->contact_velocity_threshold).  Not provided: BVH text parsing. */
+ * process_data 0.5: cfg->contact_velocity_threshold).  BVH text: mocha_bvh_header / mocha_bvh_motion below. */
 int mocha_ingest_clips(mocha_ctx* ctx, const mocha_ingest_cfg* cfg, const mocha_post_cfg* post, const float* rot, const float* pos,
                        const int32_t* clip_offsets, int n_clips, const int32_t* mirror_map, const unsigned char* mirror_flags,
                        float* out_pos, float* out_vel, float* out_rot, float* out_ang, unsigned char* out_contact, void* stream);
@@ -697,6 +697,77 @@ int mocha_clip_windows(mocha_ctx* ctx, const float* pos, const float* vel, const
                        const unsigned char* contact, int n_contact, const int32_t* clip_offsets, int n_clips, int window, int step,
                        float* Yrot, float* Ypos, float* Yvel, float* Yang, unsigned char* Ycontact, void* stream);
 int mocha_mirror_map_default(int layout, int32_t* map);
+
+/* BVH TEXT in front of mocha_ingest_clips: what the reference's loader (motion/bvh.py:22-138) returns - Euler degrees in file channel
+ * order and positions in file units per joint - as the two fp32 device arrays mocha_ingest_clips reads.  The hierarchy is read on the
+ * host, the numbers of the MOTION block (over 99.9 % of a file) are parsed on the device.
+ *   mocha_bvh_header       : HOST only, no context, no GPU.  Reads the HIERARCHY block and the Frames: / Frame Time: lines of `text`
+ *                            (nbytes bytes, NOT NUL-terminated; nothing outside [text, text + nbytes) is read).  Joints are numbered in
+ *                            file order as bvh.load numbers them (:43-49, :81-87); End Site offsets are ignored (:61-65); names are (byte
+ *                            offset, length) into the text and may hold ':' (:43, :81).  channels = 3: the root has 6 channels, every
+ *                            other joint 3 rotations; 6: every joint has 3 positions and 3 rotations (a root alone counts as 6).
+ *                            order[i] = the axis (0 x, 1 y, 2 z) of rotation channel i.  [motion_begin, motion_end) = the numeric block:
+ *                            from the first byte after the Frame Time: line to nbytes.  Line ends \n or \r\n, tabs and spaces.
+ *                            Refused (MOCHA_ERR_ARG; error_offset = the first byte of the offending line, error = what is wrong, where
+ *                            the reference reads silently and wrongly, :67-77, :112-118): 9-channel joints, position channels not in
+ *                            X Y Z order, joints that disagree on the rotation order or on the channel count beyond the root / non-root
+ *                            split, more than MOCHA_BVH_MAX_JOINTS joints, a missing MOTION, Frames: or Frame Time:, unbalanced braces,
+ *                            text that ends inside the hierarchy, any other line in the hierarchy.
+ *   mocha_bvh_motion       : the numeric blocks of n_clips files -> rot / pos (F,v_out,3) fp32, F = clip_offsets[n_clips], in exactly the
+ *                            layout mocha_ingest_clips reads.
+ *                            text_dev (DEVICE, 16-byte aligned, nbytes a multiple of MOCHA_BVH_ALIGN) holds ONLY the numeric blocks.
+ *                            Packing rule: clip c occupies [clip_text_begin[c], clip_text_end[c]); clip_text_begin[0] = 0 and every begin
+ *                            is a multiple of MOCHA_BVH_ALIGN; every byte between a clip's end and the next begin, and from the last end
+ *                            to nbytes, is '\n'.  text_host (or NULL) is a host copy of the same bytes.  clip_text_begin / clip_text_end
+ *                            (n_clips) and clip_offsets (n_clips + 1, as mocha_ingest_clips takes them) are HOST arrays; n_joints and
+ *                            channels come from the header and hold for every clip of the call.  joint_map (HOST, n_joints, or NULL =
+ *                            identity with v_out = n_joints): file joint j is written to output joint joint_map[j], -1 drops it; the
+ *                            kept joints must cover 0..v_out-1 once each.  offsets_out (HOST, (v_out,3) fp32; required for channels ==
+ *                            3): the positions of the joints that have no position channels (:97, :113).
+ *                            A token is a maximal run of bytes other than space, \t, \r, \n; a frame is a non-empty line and holds
+ *                            exactly C = 3 + 3 n_joints (channels 3) or 6 n_joints (channels 6) tokens; clip c holds exactly
+ *                            (clip_offsets[c+1] - clip_offsets[c]) C tokens.  Grammar of a token, at most 64 bytes:
+ *                            [+-]? (digits [. digits?]? | . digits) ([eE] [+-]? digits)?  - no nan, inf, hex or underscores.  Its value
+ *                            is float(token) as Python reads it (:109, correctly rounded decimal -> float64), rounded once to fp32: bit
+ *                            for bit, -0.000000 keeps its sign.  At most 15 significant digits and a net decimal exponent within +-22
+ *                            (everything a %f writer emits) convert on the device: double(m) * 10^e or double(m) / 10^-e, one IEEE
+ *                            operation on exact operands.  Any other token is a SLOW token: the device lists it (at most
+ *                            MOCHA_BVH_MAX_SLOW per call), the call converts it with strtod from text_host and patches the outputs.
+ *                            Four launches (mocha_bvh_count, mocha_bvh_scan, mocha_bvh_parse, mocha_bvh_finish), a fifth
+ *                            (mocha_bvh_patch) only with slow tokens.  report (HOST, may be NULL): tokens found, slow tokens, first_bad =
+ *                            the byte offset into text_dev of the first violation or -1.
+ *                            MOCHA_ERR_STATE (first_bad set, outputs unspecified): a malformed or overlong token (its first byte), a
+ *                            line whose first token is not a multiple of C into its clip or a token C into a line that does not start
+ *                            one (that token), a token beyond the clip's frames or in a gap (that token), a clip with too few tokens
+ *                            (its clip_text_end); also a slow token without text_host and more than MOCHA_BVH_MAX_SLOW slow tokens.
+ *                            MOCHA_ERR_ARG, nothing launched: a NULL required pointer, a misaligned text_dev / nbytes / clip begin,
+ *                            clip ranges that overlap or leave the buffer, nbytes >= 2^31, n_joints outside 1..MOCHA_BVH_MAX_JOINTS,
+ *                            channels other than 3 or 6, a joint_map that is no such map, clip_offsets that do not increase from 0.
+ *                            NOT capture-safe: the call uploads its tables, may (re)allocate the context's parse buffer (8 bytes per
+ *                            4096 bytes of text plus 64 KiB, grow-only, does not move mocha_generation()) and waits for `stream` once
+ *                            after its launches to read the report (a second time only to patch slow tokens). */
+#define MOCHA_BVH_MAX_JOINTS 256
+#define MOCHA_BVH_ALIGN 4096
+#define MOCHA_BVH_MAX_SLOW 4096
+typedef struct mocha_bvh_hdr {
+    int32_t n_joints, channels;          /* channels: 3 or 6, see above */
+    int32_t order[3], reserved;
+    int64_t frames;
+    double frame_time;
+    int64_t motion_begin, motion_end;    /* byte range of the numeric block */
+    int64_t error_offset;                /* -1, or the first byte of the refused line */
+    char error[128];
+    int32_t parents[MOCHA_BVH_MAX_JOINTS];
+    int32_t name_length[MOCHA_BVH_MAX_JOINTS];
+    int64_t name_offset[MOCHA_BVH_MAX_JOINTS];
+    double offsets[MOCHA_BVH_MAX_JOINTS][3];
+} mocha_bvh_hdr;
+typedef struct mocha_bvh_report { int64_t tokens, slow, first_bad; } mocha_bvh_report;
+int mocha_bvh_header(const char* text, int64_t nbytes, mocha_bvh_hdr* hdr);
+int mocha_bvh_motion(mocha_ctx* ctx, const char* text_dev, int64_t nbytes, const char* text_host, const int64_t* clip_text_begin,
+                     const int64_t* clip_text_end, const int32_t* clip_offsets, int n_clips, int n_joints, int channels,
+                     const int32_t* joint_map, int v_out, const float* offsets_out, float* rot, float* pos, mocha_bvh_report* report,
+                     void* stream);
 
 /* Bank build statistics: cnt_mean, cnt_std = np.mean(cnt, 0), np.std(cnt, 0) over the N bank entries
  * (compute_cnt_norm.py:174-175; population std), x (N, 90*256) -> mean, std (90*256). */

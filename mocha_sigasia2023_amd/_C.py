@@ -41,6 +41,20 @@ class mocha_ingest_cfg(C.Structure):
                 ("upleg_l", C.c_int), ("upleg_r", C.c_int)]
 
 
+BVH_MAX_JOINTS, BVH_ALIGN, BVH_MAX_SLOW = 256, 4096, 4096
+
+
+class mocha_bvh_hdr(C.Structure):
+    _fields_ = [("n_joints", C.c_int32), ("channels", C.c_int32), ("order", C.c_int32 * 3), ("reserved", C.c_int32), ("frames", C.c_int64),
+                ("frame_time", C.c_double), ("motion_begin", C.c_int64), ("motion_end", C.c_int64), ("error_offset", C.c_int64),
+                ("error", C.c_char * 128), ("parents", C.c_int32 * BVH_MAX_JOINTS), ("name_length", C.c_int32 * BVH_MAX_JOINTS),
+                ("name_offset", C.c_int64 * BVH_MAX_JOINTS), ("offsets", C.c_double * 3 * BVH_MAX_JOINTS)]
+
+
+class mocha_bvh_report(C.Structure):
+    _fields_ = [("tokens", C.c_int64), ("slow", C.c_int64), ("first_bad", C.c_int64)]
+
+
 _vp, _i, _i64 = C.c_void_p, C.c_int, C.c_int64
 
 # name -> (restype, argtypes); every symbol include/mocha_hip.h declares
@@ -123,6 +137,9 @@ SIGNATURES = {
     "mocha_clip_window_count": (_i, [C.POINTER(C.c_int32), _i, _i, _i, C.POINTER(_i64)]),
     "mocha_clip_windows": (_i, [_vp] * 6 + [_i, C.POINTER(C.c_int32), _i, _i, _i] + [_vp] * 6),
     "mocha_mirror_map_default": (_i, [_i, C.POINTER(C.c_int32)]),
+    "mocha_bvh_header": (_i, [_vp, _i64, C.POINTER(mocha_bvh_hdr)]),
+    "mocha_bvh_motion": (_i, [_vp, _vp, _i64, _vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_int32), _i, _i, _i, C.POINTER(C.c_int32), _i,
+                              C.POINTER(C.c_float), _vp, _vp, C.POINTER(mocha_bvh_report), _vp]),
     "mocha_set_rccl_library":(_i, [C.c_char_p]),
     "mocha_comm_unique_id": (_i, [_vp, _vp]),
     "mocha_comm_init": (_i, [_vp, _vp, _i, _i]),

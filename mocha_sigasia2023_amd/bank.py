@@ -116,8 +116,12 @@ def build_database_from_clips(model: Generator, clips, style_labels, action_labe
     if not clips or len(style_labels) != len(clips) or len(action_labels) != len(clips):
         raise ValueError("build_database_from_clips: one style and one action label per clip, at least one clip")
     reps = 2 if mirror else 1
-    rot = np.concatenate([np.asarray(r, dtype=np.float32) for r, _ in clips for _ in range(reps)])
-    pos = np.concatenate([np.asarray(p, dtype=np.float32) for _, p in clips for _ in range(reps)])
+    if any(torch.is_tensor(x) for clip in clips for x in clip):         # device arrays (load_bvh's) stay on the device
+        cat = lambda xs: torch.cat([torch.as_tensor(x, dtype=torch.float32, device=model.device) for x in xs])    # noqa: E731
+    else:
+        cat = lambda xs: np.concatenate([np.asarray(x, dtype=np.float32) for x in xs])    # noqa: E731
+    rot = cat([r for r, _ in clips for _ in range(reps)])
+    pos = cat([p for _, p in clips for _ in range(reps)])
     lengths = [len(r) for r, _ in clips for _ in range(reps)]
     flags = [k == 1 for _ in clips for k in range(reps)]
     out = ingest_clips(model, rot, pos, lengths, raw=IngestConfig() if raw is None else raw, mirror=flags if mirror else None, post=post)
@@ -129,6 +133,21 @@ def build_database_from_clips(model: Generator, clips, style_labels, action_labe
             "bone_parents": parents.astype(np.int32), "range_starts": (stops - lengths).astype(np.int32),
             "range_stops": stops.astype(np.int32), "style_labels": np.repeat(np.asarray(style_labels, dtype=np.int32), reps),
             "content_labels": labels, "action_labels": labels, "contact_states": out["contact"].cpu().numpy().astype(np.int8)}
+
+
+def build_database_from_bvh(model: Generator, paths, style_labels, action_labels, mirror: bool = True, raw=None, post=None, joints=None) -> dict:
+    """BVH files -> the motion database: ``bvh.load_bvh`` (the MOTION text parsed on the device) followed by
+    ``build_database_from_clips``; the files' numbers reach the database without a host copy.  ``joints``: the file's joints in the model
+    layout's order (names or indices; None = all, in file order).  ``raw`` defaults to ``IngestConfig(order=<the files' rotation order>,
+    fps=round(1 / <the first file's frame time>))``."""
+    from .bvh import load_bvh
+    from .ingest import IngestConfig
+    clips = load_bvh(model, paths, joints=joints)
+    if len(clips.names) != model.V:
+        raise ValueError(f"build_database_from_bvh: the files give {len(clips.names)} joints, the model's layout has {model.V}: select with joints=")
+    if raw is None:
+        raw = IngestConfig(order=clips.order, fps=float(round(1.0 / clips.frametime)) if clips.frametime > 0 else 60.0)
+    return build_database_from_clips(model, clips.clips(), style_labels, action_labels, mirror=mirror, raw=raw, post=post)
 
 
 def collect_windows(db: dict, style_labels, action_labels, window: int = 60) -> dict:

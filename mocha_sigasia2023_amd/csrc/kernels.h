@@ -281,6 +281,27 @@ struct ClipWindowParams {
     long long B;
 };
 hipError_t launch_clip_windows(const ClipWindowParams& p, hipStream_t s);
+// The MOTION blocks of BVH files as text -> rot / pos (F,v_out,3) fp32 (mocha_bvh_motion, bvh_parse.hip).  The text is walked in blocks
+// of BVH_BLOCK bytes; clips start on block boundaries, so a clip's first token ordinal is the token prefix at its first block.
+static constexpr int BVH_BLOCK = 4096, BVH_MAX_TOKEN = 64, BVH_MAX_SLOW = 4096;
+struct BvhSlow { unsigned long long dest, at; };      // dest: element index, bit 63 set for rot; at: byte offset (the fp32 bits once patched)
+struct BvhReport { unsigned long long first_bad; unsigned slow, tokens; };      // first_bad: ~0 = none
+struct BvhParams {
+    const unsigned char* text;          // nbytes = nblocks * BVH_BLOCK, 16-byte aligned
+    long long nbytes;
+    unsigned nblocks;
+    const long long *begin, *end;       // device: (C) byte ranges of the clips
+    const int *offsets, *map;           // device: (C+1) frame offsets, (n_joints) output joint or -1
+    const float* off_out;               // device: (v_out,3) or NULL
+    unsigned *counts, *prefix;          // device: (nblocks) token starts per block, (nblocks+1) their exclusive scan
+    BvhReport* report;
+    BvhSlow* slow;                      // device: BVH_MAX_SLOW entries
+    float *rot, *pos;
+    int C, n_joints, channels, v_out, per_frame, root_out, n_patch;
+    long long F;
+};
+// launch = 0 count, 1 scan, 2 parse, 3 finish + fill, 4 patch (n_patch slow tokens converted on the host): one kernel each
+hipError_t launch_bvh_parse(const BvhParams& p, int launch, hipStream_t s);
 static constexpr int POST_STATE_DOUBLES = 8 + MOCHA_MAX_BONES * 3 + MOCHA_MAX_CONTACT * 19;
 struct PostParams {
     const float* heads;             // (clips, frames, V, 13)

@@ -266,6 +266,9 @@ struct mocha_ctx {
     // device: the clip ingester's tables (offsets, mirror flags / window counts) and its float64 workspace (mocha_ingest_clips,
     // mocha_clip_windows).  Grow-only; only those two calls read it and neither is captured, so a new allocation does not move the generation.
     DeviceBuffer<double> clip_ws;
+    // device: the BVH text parser's tables, report, slow-token list and per-block token counts (mocha_bvh_motion).  Grow-only; only that
+    // call reads it and it is never captured, so a new allocation does not move the generation.
+    DeviceBuffer<unsigned long long> bvh_ws;
     DeviceBuffer<float> pose_norm;     // [x_mean | x_std | y_mean | y_std], (V+1)*C_in each (norm.npz of the reference)
     bool use_tiled = false;            // option "bank_tiled": -4 % on the cold pass for 2 x the bf16 copy's memory (profiles/r04/c_tiled_loader_ab.txt): off
     DeviceBuffer<unsigned long long> topk_keys{BUF_MOVES_GENERATION};      // every row's key of up to 8 queries (mocha_match_topk)
@@ -3661,6 +3664,114 @@ int mocha_clip_windows(mocha_ctx* c, const float* pos, const float* vel, const f
     p.C = n_clips; p.J = c->cfg.V + 1; p.nc = n_contact; p.window = window; p.step = step; p.B = B;
     LAUNCH(c, s, "mocha_clip_windows_k", "clip.windows", 0.0, 2.0 * (double)B * window * (p.J * 13.0 * 4 + n_contact),
            launch_clip_windows(p, s));
+    return 0;
+}
+
+int mocha_bvh_motion(mocha_ctx* c, const char* text_dev, int64_t nbytes, const char* text_host, const int64_t* clip_text_begin,
+                     const int64_t* clip_text_end, const int32_t* clip_offsets, int n_clips, int n_joints, int channels,
+                     const int32_t* joint_map, int v_out, const float* offsets_out, float* rot, float* pos, mocha_bvh_report* report,
+                     void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (report) *report = mocha_bvh_report{0, 0, -1};
+    if (!text_dev || !clip_text_begin || !clip_text_end || !rot || !pos) return fail(c, MOCHA_ERR_ARG, "bvh_motion: null argument");
+    if (n_joints < 1 || n_joints > MOCHA_BVH_MAX_JOINTS) return fail(c, MOCHA_ERR_ARG, "bvh_motion: n_joints must be 1..%d", MOCHA_BVH_MAX_JOINTS);
+    if (channels != 3 && channels != 6) return fail(c, MOCHA_ERR_ARG, "bvh_motion: channels must be 3 or 6");
+    int rc = clip_offsets_check(c, "bvh_motion", clip_offsets, n_clips, 1); if (rc) return rc;
+    if (reinterpret_cast<uintptr_t>(text_dev) % 16) return fail(c, MOCHA_ERR_ARG, "bvh_motion: text_dev must be 16-byte aligned");
+    if (nbytes <= 0 || nbytes % MOCHA_BVH_ALIGN || nbytes >= (int64_t)1 << 31)
+        return fail(c, MOCHA_ERR_ARG, "bvh_motion: nbytes must be a positive multiple of %d below 2^31", MOCHA_BVH_ALIGN);
+    for (int i = 0; i < n_clips; ++i) {
+        if (clip_text_begin[i] % MOCHA_BVH_ALIGN || (i == 0 && clip_text_begin[0] != 0))
+            return fail(c, MOCHA_ERR_ARG, "bvh_motion: clip %d begins at byte %lld: clip 0 at 0, every clip at a multiple of %d", i,
+                        (long long)clip_text_begin[i], MOCHA_BVH_ALIGN);
+        const int64_t limit = i + 1 < n_clips ? clip_text_begin[i + 1] : nbytes;
+        if (clip_text_end[i] <= clip_text_begin[i] || clip_text_end[i] > limit)
+            return fail(c, MOCHA_ERR_ARG, "bvh_motion: the text of clip %d is empty or runs into the next clip", i);
+    }
+    if (!joint_map) {
+        if (v_out != n_joints) return fail(c, MOCHA_ERR_ARG, "bvh_motion: without a joint_map v_out must be n_joints");
+    } else {
+        if (v_out < 1 || v_out > n_joints) return fail(c, MOCHA_ERR_ARG, "bvh_motion: v_out must be 1..n_joints");
+        std::vector<char> seen(v_out, 0);
+        int kept = 0;
+        for (int j = 0; j < n_joints; ++j) {
+            if (joint_map[j] < -1 || joint_map[j] >= v_out || (joint_map[j] >= 0 && seen[joint_map[j]]++))
+                return fail(c, MOCHA_ERR_ARG, "bvh_motion: joint_map[%d] = %d: -1 or an output joint, each once", j, joint_map[j]);
+            kept += joint_map[j] >= 0;
+        }
+        if (kept != v_out) return fail(c, MOCHA_ERR_ARG, "bvh_motion: joint_map leaves an output joint unwritten");
+    }
+    if (channels == 3 && !offsets_out) return fail(c, MOCHA_ERR_ARG, "bvh_motion: channels == 3 needs offsets_out");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+
+    // the buffer, in 8-byte words: report | clip begins | clip ends | frame offsets | joint map | offsets_out  (uploaded)  | slow list |
+    // block counts | prefix
+    typedef unsigned long long W;
+    const size_t nC = (size_t)n_clips, nblocks = (size_t)(nbytes / BVH_BLOCK);
+    const size_t w_begin = 2, w_end = w_begin + nC, w_off = w_end + nC, w_map = w_off + (nC + 2) / 2, w_out = w_map + ((size_t)n_joints + 1) / 2,
+                 w_slow = w_out + ((size_t)v_out * 3 + 1) / 2, w_counts = w_slow + (size_t)BVH_MAX_SLOW * 2, w_prefix = w_counts + (nblocks + 1) / 2,
+                 words = w_prefix + (nblocks + 2) / 2;
+    std::vector<W> tab(w_slow, 0);
+    BvhReport fresh{~0ull, 0u, 0u};
+    memcpy(&tab[0], &fresh, sizeof fresh);
+    for (size_t i = 0; i < nC; ++i) { tab[w_begin + i] = (W)clip_text_begin[i]; tab[w_end + i] = (W)clip_text_end[i]; }
+    memcpy(&tab[w_off], clip_offsets, (nC + 1) * sizeof(int32_t));
+    int32_t* map_host = reinterpret_cast<int32_t*>(&tab[w_map]);
+    for (int j = 0; j < n_joints; ++j) map_host[j] = joint_map ? joint_map[j] : j;
+    if (offsets_out) memcpy(&tab[w_out], offsets_out, (size_t)v_out * 3 * sizeof(float));
+    if ((rc = reserve(c, c->bvh_ws, words))) return rc;
+    W* ws = c->bvh_ws.p;
+    HIPCHK(c, hipMemcpyAsync(ws, tab.data(), tab.size() * sizeof(W), hipMemcpyHostToDevice, s));
+
+    BvhParams p{};
+    p.text = reinterpret_cast<const unsigned char*>(text_dev); p.nbytes = nbytes; p.nblocks = (unsigned)nblocks;
+    p.report = reinterpret_cast<BvhReport*>(ws);
+    p.begin = reinterpret_cast<const long long*>(ws + w_begin); p.end = reinterpret_cast<const long long*>(ws + w_end);
+    p.offsets = reinterpret_cast<const int*>(ws + w_off); p.map = reinterpret_cast<const int*>(ws + w_map);
+    p.off_out = offsets_out ? reinterpret_cast<const float*>(ws + w_out) : nullptr;
+    p.slow = reinterpret_cast<BvhSlow*>(ws + w_slow);
+    p.counts = reinterpret_cast<unsigned*>(ws + w_counts); p.prefix = reinterpret_cast<unsigned*>(ws + w_prefix);
+    p.rot = rot; p.pos = pos;
+    p.C = n_clips; p.n_joints = n_joints; p.channels = channels; p.v_out = v_out;
+    p.per_frame = channels == 3 ? 3 + 3 * n_joints : 6 * n_joints;
+    p.root_out = map_host[0];
+    p.F = clip_offsets[n_clips];
+    const double out_bytes = (double)p.F * v_out * 6 * sizeof(float);
+    LAUNCH(c, s, "mocha_bvh_count", "bvh.count", 0.0, (double)nbytes + nblocks * 4.0, launch_bvh_parse(p, 0, s));
+    LAUNCH(c, s, "mocha_bvh_scan", "bvh.scan", 0.0, nblocks * 12.0, launch_bvh_parse(p, 1, s));
+    LAUNCH(c, s, "mocha_bvh_parse", "bvh.parse", 0.0, (double)nbytes + nblocks * 4.0 + out_bytes, launch_bvh_parse(p, 2, s));
+    LAUNCH(c, s, "mocha_bvh_finish", "bvh.finish", 0.0, channels == 3 ? out_bytes / 2 : nC * 24.0, launch_bvh_parse(p, 3, s));
+    BvhReport got{};
+    HIPCHK(c, hipMemcpyAsync(&got, p.report, sizeof got, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));               // the one wait: the report decides what the call returns (and `tab` may go)
+    const int64_t bad = got.first_bad == ~0ull ? -1 : (int64_t)got.first_bad;
+    if (report) *report = mocha_bvh_report{(int64_t)got.tokens, (int64_t)got.slow, bad};
+    if (bad >= 0) return fail(c, MOCHA_ERR_STATE, "bvh_motion: the text breaks the frame layout or the number grammar at byte %lld", (long long)bad);
+    if (got.slow == 0) return 0;
+    if (got.slow > (unsigned)BVH_MAX_SLOW)
+        return fail(c, MOCHA_ERR_STATE, "bvh_motion: %u tokens need the host's conversion, more than %d", got.slow, BVH_MAX_SLOW);
+    if (!text_host) return fail(c, MOCHA_ERR_STATE, "bvh_motion: %u tokens need the host's conversion and there is no text_host", got.slow);
+    std::vector<BvhSlow> slow(got.slow);
+    HIPCHK(c, hipMemcpyAsync(slow.data(), p.slow, slow.size() * sizeof(BvhSlow), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    for (BvhSlow& e : slow) {
+        char buf[BVH_MAX_TOKEN + 1];
+        int len = 0;
+        for (int64_t at = (int64_t)e.at; len < BVH_MAX_TOKEN && at + len < nbytes; ++len) {
+            const char ch = text_host[at + len];
+            if (ch == ' ' || ch == '\t' || ch == '\r' || ch == '\n') break;
+            buf[len] = ch;
+        }
+        buf[len] = 0;
+        const float v = (float)strtod(buf, nullptr);      // the device has checked the grammar: strtod reads the whole token
+        unsigned bits; memcpy(&bits, &v, sizeof bits);
+        e.at = bits;
+    }
+    HIPCHK(c, hipMemcpyAsync(p.slow, slow.data(), slow.size() * sizeof(BvhSlow), hipMemcpyHostToDevice, s));
+    p.n_patch = (int)slow.size();
+    LAUNCH(c, s, "mocha_bvh_patch", "bvh.patch", 0.0, slow.size() * 20.0, launch_bvh_parse(p, 4, s));
+    HIPCHK(c, hipStreamSynchronize(s));               // `slow` is the copy's source
     return 0;
 }
 

@@ -8,7 +8,7 @@ whole clip's frame 0.3 s late; ``lookahead=0`` the newest frame under the refere
 inside the session's captured graph.  A stream never emits the last ``lookahead`` frames of a clip and does not mirror: whole clips go
 through ``ingest_clips`` (``mocha_ingest_clips``: every frame of every clip, plain or mirrored as ``animation_mirror`` does, parallel over
 frames) and ``clip_windows`` (``divide_clip``), the first link of raw clip -> ``bank.build_database_from_clips`` -> bank and of raw clip
-pair -> windows -> ``featurize`` -> ``characterize_pair``.  Not provided: BVH text parsing.  Inherited from the reference: a character
+pair -> windows -> ``featurize`` -> ``characterize_pair``.  BVH files are read by ``bvh.load_bvh``.  Inherited from the reference: a character
 facing exactly -z is singular; contacts flip at a hard speed threshold.
 """
 from __future__ import annotations
