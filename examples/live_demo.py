@@ -4,7 +4,7 @@ mocap frame at a time through ``LiveSession`` - ring push + featurize, segmented
 frame per push, one captured graph - and written as two BVH files.
 
     python examples/live_demo.py [--frames 180] [--out bench_outputs/live_demo] [--ours [--seed 7]] [--switch 120 [--inertial 0.1]] [--raw L]
-                                 [--actions A,B[:F]]
+                                 [--actions A,B[:F]] [--load-at F]
 
 ``--ours`` runs the CVAE ("Ours") branch inside the same graph (``LiveOursSession``): each stream's character feature is seeded with
 its matched bank row on the first pose and sampled from the previous one afterwards, the noise drawn on the device; the files are then
@@ -23,6 +23,10 @@ contacts (``LiveSession(raw=L)``, ``push_raw``), L = 0..18 frames of lookahead. 
 listed actions only (``LiveSession(constrained=True)``, ``push(..., allow=)``).  The new masks are device data: nothing is captured again.
 How many posed frames were constrained is printed.
 
+``--load-at F``: the run starts on a ``ResidentCharacterBank`` that holds the two characters; at frame F a third character is added to it
+in place - its own rows and decoder constants, enqueued on the stream - and stream 1 switches to it.  The captured step keeps replaying:
+the model's generation before and after is printed.
+
 Weights, norms and motions are synthetic (see demo_pair.py for what to replace with real assets).
 """
 import argparse
@@ -34,8 +38,8 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mocha_sigasia2023_amd import (Generator, LiveOursSession, LiveSession, MultiCharacterBank, PostProcessor, build_bank, synthetic,  # noqa: E402
-                                   synthetic_state_dict, write_bvh)
+from mocha_sigasia2023_amd import (Generator, LiveOursSession, LiveSession, MultiCharacterBank, PostProcessor, ResidentCharacterBank,  # noqa: E402
+                                   build_bank, synthetic, synthetic_state_dict, write_bvh)
 from mocha_sigasia2023_amd.skeleton import LAYOUTS  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -49,6 +53,8 @@ ap.add_argument("--switch", type=int, default=None, metavar="FRAME", help="strea
 ap.add_argument("--inertial", type=float, default=None, metavar="HALFLIFE", help="inertialize character switches with that half-life in seconds")
 ap.add_argument("--raw", type=int, default=None, metavar="L", help="push raw mocap frames; the front end runs in the graph with L frames of lookahead")
 ap.add_argument("--actions", default=None, metavar="A,B[:F]", help="allow only these action labels (0..7 here), from frame F on")
+ap.add_argument("--load-at", type=int, default=None, metavar="FRAME", help="start on a resident bank; at that frame a third character is added in "
+                "place and stream 1 switches to it")
 a = ap.parse_args()
 if a.ours and a.actions:
     raise SystemExit("--actions does not apply to --ours: the branch's seed match searches the whole character")
@@ -81,12 +87,17 @@ cnt_mean, cnt_std = (torch.from_numpy(x).to(dev) for x in synthetic.cnt_norm(7))
 
 # ---- two characters' banks from two clips, one multi-character bank                          :203-222, 271-277
 banks = []
-for seed in (12, 13):
+for seed in (12, 13) + ((14,) if a.load_at is not None else ()):
     clip = synthetic.smooth_bone_clip(seed, 60 + 200 - 1)
     b = build_bank(model, model.featurize(*[synthetic.slide_windows(x) for x in clip]), raw=True)
     banks.append((((b["cnt"] - cnt_mean) / cnt_std).reshape(-1, 90 * 256), b["encoded"]))
 labels = [(np.arange(b[0].shape[0]) // 25).astype(np.int32) for b in banks] if a.actions else None      # actions in runs, one per clip range
-bank = MultiCharacterBank(model, banks, labels=labels)
+if a.load_at is not None:                                             # storage for three characters reserved once; two loaded now
+    bank = ResidentCharacterBank(model, capacity_rows=3 * 208, max_characters=3, max_rows_per_character=208)
+    for c in range(2):
+        bank.add(*banks[c], labels=labels[c] if labels else None)
+else:
+    bank = MultiCharacterBank(model, banks, labels=labels)
 
 # ---- two source clips arriving frame by frame, stream s retargeted to character s
 src = [[torch.from_numpy(x).to(dev) for x in synthetic.smooth_bone_clip(30 + s, F, phase=0.4 * s)] for s in range(S)]
@@ -127,8 +138,13 @@ torch.cuda.synchronize(); t0 = time.perf_counter()
 pos, eul, applied = [], [], []
 if a.actions:
     sess.allow.zero_()
+gen0 = model._ctx.generation()
 for f in range(F):
-    o = push(f, characters=[1, 1] if f == a.switch else None)
+    chars = [1, 1] if f == a.switch else None
+    if f == a.load_at:                                                # one more character while the session runs: no new bank, no new capture
+        new = bank.add(*banks[2], labels=labels[2] if labels else None)
+        chars = [1 if a.switch is not None and f >= a.switch else 0, new]
+    o = push(f, characters=chars)
     if f >= first:                                                    # both streams started together: both are valid from here on
         pos.append(o["bvh_pos"].clone()); eul.append(o["bvh_euler"].clone())
         if a.actions:
@@ -145,6 +161,9 @@ if a.switch is not None and first + 1 <= a.switch < F:
     step = (pos[0, 1:, 1:] - pos[0, :-1, 1:]).abs().amax(dim=(1, 2))     # per frame, the non-root bones of stream 0
     print(f"  stream 0 switches character at frame {a.switch}: largest bone-position step there {float(step[a.switch - first - 1]):.4f}, "
           f"median over the clip {float(step.median()):.4f}" + (f" (inertialized, half-life {a.inertial} s)" if a.inertial is not None else ""))
+if a.load_at is not None and 0 <= a.load_at < F:
+    print(f"  character 2 ({banks[2][0].shape[0]} entries) added to the resident bank at frame {a.load_at}, rows {bank.rows(2)}; stream 1 took it; "
+          f"generation {gen0} -> {model._ctx.generation()}; {bank.free_rows} rows free")
 if a.actions:
     ap_ = torch.stack(applied, 1)
     print(f"  actions {a.actions.partition(':')[0]} allowed from frame {allow_from}: " + ", ".join(

@@ -294,6 +294,49 @@ int mocha_step_graph_segmented_allow(mocha_ctx* ctx, const float* X, int S_w, co
                                      float temperature, const float* cnt_mean, const float* cnt_std, float* Y, int32_t* idx_k, float* w_k,
                                      int32_t* applied, int raw, void* stream);
 
+/* Resident multi-character bank: characters added and retired in place, while the captured steps keep replaying.
+ * mocha_bank_set_segments fixes the set of characters: one more character means a concatenation of every character's rows, the whole
+ * union's derived data over again, and a new generation - every captured segmented and live step is thrown away, and for the duration
+ * the bank exists twice.  A resident bank reserves its storage, tables and scratch ONCE; a character then costs its own bytes and its own
+ * style MLP, enqueued on the caller's stream, and mocha_generation() does not move.  Each character occupies a SLOT (its id in the
+ * segmented and live calls, 0 .. max_characters - 1) and an extent of whole 16-row granules, first fit, never moved (no compaction).
+ *   mocha_bank_resident_create : the context's current bank becomes an EMPTY resident bank for up to capacity_rows rows (rounded up to
+ *                             16) in up to max_characters slots of up to max_rows_per_character rows each.  fp32 only and owned:
+ *                             MOCHA_BANK_BF16 or MOCHA_BANK_BORROW is MOCHA_ERR_ARG; MOCHA_BANK_NO_DEC_CACHE is honoured.  Allocates,
+ *                             zero-filled, the rows, the per-entry decoder constants (if the memory is not there the decoder computes them
+ *                             per call, as for any bank), the label and slot tables and the segmented matcher's scratch of every workspace
+ *                             set, sized by the two maxima.  Moves the generation once, as any new bank.  After it, add, retire and every
+ *                             segmented or live call neither allocate, nor synchronise, nor move the generation; mocha_reserve re-sizes
+ *                             the matcher's scratch itself (and moves the generation, as workspace growth does).  The scan grid of every
+ *                             segmented call is sized by max_rows_per_character, not by the largest character loaded.
+ *   mocha_bank_resident_add : the n rows cnt_nm / encoded (DEVICE, as mocha_bank_set_segments takes them) with labels (DEVICE, n int32, read
+ *                             as label & 63; NULL: every row label 0) become the character of `slot` (-1: the lowest empty slot); the slot
+ *                             taken goes to slot_out (HOST, or NULL).  Enqueues two row copies, the rows' decoder constants - the bits
+ *                             of the style MLP's tiled float64 kernel, however few the rows are (what mocha_bank_set_segments computes for every
+ *                             chunk of more than 16 rows; it walks a bank 4096 rows at a time, and a chunk of at most 16 rows - a bank
+ *                             that small, or such a remainder - takes a wave-reduction kernel with another summation order) - their label
+ *                             tables and, last, the slot's table entry.  Refused before anything is enqueued: a slot out of range, n < 1
+ *                             or n > max_rows_per_character (MOCHA_ERR_ARG); an occupied slot, no empty slot, no free extent of n rows
+ *                             (MOCHA_ERR_STATE; the message names the largest free extent).
+ *   mocha_bank_resident_retire : the slot becomes empty (row count 0 in the table) and its extent free.  Its rows are not cleared: an empty
+ *                             slot is never read.  Replacing a character is retire + add of the same slot on the same stream.  Ordering
+ *                             is the stream's: a context is driven from one stream at a time, as for the graph steps.
+ *   mocha_bank_resident_info : host-side.  slot >= 0: its first row and row count (0: empty); always: the free rows and the largest
+ *                             free extent, in rows.  Any output may be NULL.  slot -1: the bank's figures only.
+ * An id that names an EMPTY slot is treated as an id outside [0, S): idx -1, dist +inf, weights 0, applied 0, no bank row read for the
+ * match.  In the live steps - on a resident bank only - a stream that names an empty slot is treated as WARMING: its frame goes into its
+ * ring, valid[s] = 0, idx[s] = -1, its post state is not advanced and its output rows are left untouched; it resumes with the first frame
+ * after the slot holds a character again.  The calls that search or read the union of all rows - mocha_match, mocha_match_topk,
+ * mocha_characterize, mocha_step_graph[_lane], mocha_bank_gather[_blend], mocha_bank_export, mocha_bank_view, mocha_bank_broadcast - and
+ * mocha_bank_set_labels are MOCHA_ERR_STATE on a resident bank (no centroid, norms or images are built; it is always labelled, through
+ * add); mocha_bank_set* replaces it as it replaces any bank. */
+int mocha_bank_resident_create(mocha_ctx* ctx, int64_t capacity_rows, int max_characters, int64_t max_rows_per_character, int flags,
+                               void* stream);
+int mocha_bank_resident_add(mocha_ctx* ctx, int slot, const float* cnt_nm, const float* encoded, int64_t n, const int32_t* labels,
+                            int32_t* slot_out, void* stream);
+int mocha_bank_resident_retire(mocha_ctx* ctx, int slot, void* stream);
+int mocha_bank_resident_info(const mocha_ctx* ctx, int slot, int64_t* first_row, int64_t* rows, int64_t* free_rows, int64_t* largest_free);
+
 /* Multi-GPU set-up: one process per GPU, windows sharded across ranks, the character bank replicated.
  * The reference has no counterpart (trainer.py:45-47 is nn.DataParallel); the only exchange on the path is this one-time
  * bank broadcast over RCCL / xGMI.  RCCL is loaded lazily (dlopen "librccl.so.1"); single-GPU callers never touch it.

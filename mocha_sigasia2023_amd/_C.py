@@ -133,6 +133,10 @@ SIGNATURES = {
     "mocha_step_graph_segmented_allow": (_i, [_vp, _vp, _i, _vp, _vp, _i, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "mocha_live_step_allow": (_i, [_vp, _vp, _vp, _i] + [_vp] * 11 + [_i, C.c_float] + [_vp] * 14),
     "mocha_live_step_raw_allow": (_i, [_vp, _vp, _vp, _vp, _vp, _i] + [_vp] * 5 + [_i, C.c_float] + [_vp] * 14),
+    "mocha_bank_resident_create": (_i, [_vp, _i64, _i, _i64, _i, _vp]),
+    "mocha_bank_resident_add": (_i, [_vp, _i, _vp, _vp, _i64, _vp, C.POINTER(C.c_int32), _vp]),
+    "mocha_bank_resident_retire": (_i, [_vp, _i, _vp]),
+    "mocha_bank_resident_info": (_i, [_vp, _i] + [C.POINTER(_i64)] * 4),
     "mocha_ingest_clips": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), C.POINTER(C.c_ubyte)] + [_vp] * 6),
     "mocha_clip_window_count": (_i, [C.POINTER(C.c_int32), _i, _i, _i, C.POINTER(_i64)]),
     "mocha_clip_windows": (_i, [_vp] * 6 + [_i, C.POINTER(C.c_int32), _i, _i, _i] + [_vp] * 6),

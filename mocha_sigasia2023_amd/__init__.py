@@ -4,7 +4,7 @@ own call surface.  The arithmetic lives in ``libmocha_hip.so`` (``csrc/``, C ABI
 ``include/mocha_hip.h``); this package is the thin host-side mirror of the reference interface.
 """
 from .generator import CVAE, ContextBank, Generator, OursSession, StreamingCharacterizer, mean_variance_norm  # noqa: F401
-from .multi_character import MultiCharacterBank, MultiStreamCharacterizer, action_mask  # noqa: F401
+from .multi_character import MultiCharacterBank, MultiStreamCharacterizer, ResidentCharacterBank, action_mask  # noqa: F401
 from .bank import BatchPipeline, ShardedContextBank, build_bank, build_database_from_bvh, load_bank, save_bank  # noqa: F401
 from .postprocess import Inertializer, PostProcessor, pose_heads, retarget_clip, retarget_clip_ours, retarget_frame_ours, write_bvh  # noqa: F401
 from .live import LiveOursSession, LiveSession  # noqa: F401
@@ -16,6 +16,6 @@ from .weights import DEFAULT_CFG, param_shapes, synthetic_state_dict  # noqa: F4
 
 __all__ = ["Generator", "CVAE", "OursSession", "ContextBank", "StreamingCharacterizer", "mean_variance_norm", "skeleton_constants",
            "synthetic_state_dict", "param_shapes", "DEFAULT_CFG", "build_bank", "save_bank", "load_bank", "ShardedContextBank", "BatchPipeline",
-           "PostProcessor", "pose_heads", "MultiCharacterBank", "MultiStreamCharacterizer", "action_mask", "retarget_clip", "retarget_clip_ours", "retarget_frame_ours", "write_bvh",
+           "PostProcessor", "pose_heads", "MultiCharacterBank", "MultiStreamCharacterizer", "ResidentCharacterBank", "action_mask", "retarget_clip", "retarget_clip_ours", "retarget_frame_ours", "write_bvh",
            "LiveSession", "LiveOursSession", "Inertializer", "Ingestor", "IngestConfig", "ingest_clips", "clip_windows",
            "read_bvh_header", "load_bvh", "BvhHeader", "BvhClips", "build_database_from_bvh"]

@@ -174,8 +174,10 @@ hipError_t launch_instnorm(const float* x, float* out, float* mean_out, const fl
 hipError_t launch_adain(const float* x, const float* gb, int gb_stride /*floats between windows*/, float* xad, float* qin, int B, int n, hipStream_t s,
                         int closed = 1, const int32_t* gb_idx = nullptr, long long gb_rows = 0, int split_max = 1 << 30, int reverse = 0);
 // Y = act(X W^T + bias) in float64, L independent column blocks (pointwise.hip: the decoder's style MLP)
+// tiled != 0: the tiled kernel also for M <= 16 rows, which by default take a wave-reduction kernel whose summation order is another one
+// (both tile sizes sum one fma chain over ascending k): a row's result then does not depend on how many rows the launch has
 hipError_t launch_linear_f64(const double* X, int ldx, int xcol, const double* W, const double* bias, double* y64, float* y32, int ldy,
-                             int M, int N, int K, int L, int act, hipStream_t s);
+                             int M, int N, int K, int L, int act, hipStream_t s, int tiled = 0);
 // u rows (b,t',p) x (dt*256+c) = 1/4 sum of the 4 reflect-indexed frames of tap dt (conv k=5 fused with AvgPool(4))
 hipError_t launch_window_sums(const float* y, float* u, int rows, int channels /*256 or 192*/, hipStream_t s);
 // ---- CVAE sampler pieces (cvae.hip; model_CVAE.py)
@@ -203,9 +205,11 @@ struct LiveRing { int32_t* counters; float *rot, *pos, *vel, *ang; };
 hipError_t live_init();
 // have (S) or null: a stream with have[s] == 0 brought no frame - nothing is pushed, its counters stay, eff[s] = -1, valid[s] = 0 and its
 // window is featurised as an empty ring's
+// slot_table (n_slots pairs) or null: a resident bank's slot table (below); a stream that names an EMPTY slot pushes its frame as usual but
+// gets eff[s] = -1, valid[s] = 0 - the step treats it as warming until the slot holds a character again
 hipError_t launch_live_push(const LiveRing& r, const float* Yrot, const float* Ypos, const float* Yvel, const float* Yang, const int32_t* seg,
                             const int* parents /*J, device*/, float* X, int32_t* eff, int32_t* valid, int S, int J, hipStream_t s,
-                            const int32_t* have = nullptr);
+                            const int32_t* have = nullptr, const int* slot_table = nullptr, int n_slots = 0);
 // the CVAE branch of a live step (live_ours.hip).  counters (S,3) = {chain: steps since the stream's seed frame, last: the character id of
 // its last step, mode}; cnt / prev / vae (S,90,256), cond (S,180,256), eps (S,256); sm / ss / cm / cs (90,256) the CVAE's statistics.
 // condition: mode[s] = 0 (eff[s] outside 0..nseg-1: warming) / 1 (chain == 0 or eff[s] != last: seed) / 2 (chain) into the counters;
@@ -473,9 +477,20 @@ struct SegAllow {
     const int* gran_start;
     int32_t* applied;
 };
+// slot_table != 0 (here and in launch_match_seg_topk; fp32 bank only): seg_start is not S + 1 starts but a RESIDENT bank's slot table - 2 S
+// device ints, {first row, rows} per slot, first row a multiple of SEG_GRANULE_ROWS, the extents disjoint and inside the bank, rows <=
+// max_rows; rows = 0 is an EMPTY slot, whose id is treated as an id outside [0, S) (and no row of it is read).  gran_start[s] is then
+// first row / SEG_GRANULE_ROWS.  The table is device data a replayed graph reads: launch_resident_publish rewrites an entry in stream order.
 hipError_t launch_match_segmented(const void* bank, int bank_bf16, const float* query, const int32_t* seg, int Q, const int* seg_start, int S,
                                   int64_t max_rows, int D, unsigned long long* partial, int* plan, int32_t* idx, int32_t* gidx, float* dist,
-                                  hipStream_t s, const SegAllow* al = nullptr);
+                                  hipStream_t s, const SegAllow* al = nullptr, int slot_table = 0);
+// resident bank (bank_resident.hip): the label tables of the rows [first_row, first_row + n) of a new character - label bytes (labels[r] &
+// 63, or 0 for null labels), the granule words from first_row / 16 on, and *any_slot - and the slot table entry {first_row, rows} with
+// gran_start[slot], written last; rows = 0 empties the slot.  One workgroup each; first_row a multiple of 16 and first_row + n <= capacity_rows (checked).
+hipError_t launch_resident_labels(const int32_t* labels, int64_t n, int64_t first_row, int64_t capacity_rows, unsigned char* label,
+                                  unsigned long long* gran, unsigned long long* any_slot, hipStream_t s);
+hipError_t launch_resident_publish(int* slots, int* gran_start, int slot, int n_slots, int64_t first_row, int64_t rows, int64_t capacity_rows,
+                                   hipStream_t s);
 hipError_t launch_seg_plan(const int32_t* seg, int Q, int S, int* plan, hipStream_t s);      // the matcher's first kernel alone (plan = seg_plan_ints(Q, S) ints)
 // soft matching on a multi-character bank (match_seg_topk.hip): per query the k <= SEG_TOPK_MAX_K nearest rows of its own segment - idx_k
 // (Q,k) local rows ascending by distance, ties to the lower row, -1 where the segment has fewer than k rows; dist_k (Q,k) the distance
@@ -489,7 +504,8 @@ size_t match_seg_keys_words(int64_t max_rows);
 hipError_t launch_match_seg_topk(const void* bank, int bank_bf16, const float* query, const int32_t* seg, int Q, const int* seg_start, int S,
                                  int64_t max_rows, int D, unsigned long long* keys, int* plan, const float* enc, int k, float temperature,
                                  int32_t* idx0, int32_t* idx_k, float* dist_k, float* w_k, float* out, hipStream_t s,
-                                 const SegAllow* al = nullptr);        // al: rows outside a constrained query's mask count as missing
+                                 const SegAllow* al = nullptr,         // al: rows outside a constrained query's mask count as missing
+                                 int slot_table = 0);
 // out[q] = src[idx[q]] rows of `cols` floats
 hipError_t launch_gather_rows(const float* src, const int32_t* idx, float* out, int Q, int cols, int64_t nrows, hipStream_t s);
 

@@ -18,11 +18,14 @@
 
 namespace mocha {
 
+// SLOTS: the step runs on a resident bank, whose slot table ({first row, rows} per slot, n_slots of them) says which ids name a character
+// right now; SLOTS = false reads neither argument
+template <bool SLOTS>
 __global__ __launch_bounds__(FT) MOCHA_NO_PACKED_F32 void mocha_live_push(LiveRing r, const float* __restrict__ Yrot, const float* __restrict__ Ypos,
                                                       const float* __restrict__ Yvel, const float* __restrict__ Yang,
                                                       const int32_t* __restrict__ seg, const int* __restrict__ parents,
                                                       float* __restrict__ X, int32_t* __restrict__ eff, int32_t* __restrict__ valid, int J,
-                                                      const int32_t* __restrict__ have) {
+                                                      const int32_t* __restrict__ have, const int* __restrict__ slot_table, int n_slots) {
     extern __shared__ float g[];                                  // [J][FC][FT]
     const int s = blockIdx.x, tid = threadIdx.x;
     const int T = LIVE_WINDOW;
@@ -46,7 +49,11 @@ __global__ __launch_bounds__(FT) MOCHA_NO_PACKED_F32 void mocha_live_push(LiveRi
     const int nfill = none ? fill : fill < T ? fill + 1 : T;
     if (tid == 0) {
         if (!none) { cnt[0] = nhead; cnt[1] = nfill; }
-        const bool full = !none && nfill == T;
+        bool full = !none && nfill == T;
+        if (SLOTS) {                                              // an empty slot: the frame is in the ring, the stream sits this step out
+            const int id = seg[s];
+            if (id >= 0 && id < n_slots && slot_table[2 * id + 1] == 0) full = false;
+        }
         eff[s] = full ? seg[s] : -1;
         valid[s] = full ? 1 : 0;
     }
@@ -78,16 +85,23 @@ __global__ __launch_bounds__(FT) MOCHA_NO_PACKED_F32 void mocha_live_push(LiveRi
 }
 
 hipError_t live_init() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&mocha_live_push), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(FEAT_MAX_BONES * FC * FT * sizeof(float)));
+    const int lds = (int)(FEAT_MAX_BONES * FC * FT * sizeof(float));
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mocha_live_push<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&mocha_live_push<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 }
 
 hipError_t launch_live_push(const LiveRing& r, const float* Yrot, const float* Ypos, const float* Yvel, const float* Yang, const int32_t* seg,
-                            const int* parents, float* X, int32_t* eff, int32_t* valid, int S, int J, hipStream_t s, const int32_t* have) {
+                            const int* parents, float* X, int32_t* eff, int32_t* valid, int S, int J, hipStream_t s, const int32_t* have,
+                            const int* slot_table, int n_slots) {
     if (S <= 0) return hipSuccess;
-    if (J > FEAT_MAX_BONES || J < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(mocha_live_push, dim3(S), dim3(FT), (size_t)J * FC * FT * sizeof(float), s, r, Yrot, Ypos, Yvel, Yang, seg, parents, X,
-                       eff, valid, J, have);
+    if (J > FEAT_MAX_BONES || J < 1 || (slot_table && n_slots < 1)) return hipErrorInvalidValue;
+    const size_t lds = (size_t)J * FC * FT * sizeof(float);
+    if (slot_table)
+        hipLaunchKernelGGL(mocha_live_push<true>, dim3(S), dim3(FT), lds, s, r, Yrot, Ypos, Yvel, Yang, seg, parents, X, eff, valid, J, have, slot_table,
+                           n_slots);
+    else
+        hipLaunchKernelGGL(mocha_live_push<false>, dim3(S), dim3(FT), lds, s, r, Yrot, Ypos, Yvel, Yang, seg, parents, X, eff, valid, J, have, nullptr, 0);
     return hipGetLastError();
 }
 

@@ -148,12 +148,26 @@ __device__ __forceinline__ void seg_scan_body(const void* __restrict__ bank, con
     }
 }
 
+// The segment table's two forms (kernels.h): PAIRS = false, seg_start[S + 1] of contiguous segments; PAIRS = true, the slot table of a
+// resident bank - {first row, rows} per slot, rows = 0 for an empty slot.  -> the segment's first global row and its row count
+template <bool PAIRS>
+__device__ __forceinline__ void seg_extent(const int* __restrict__ table, int s, long long& lo, long long& n) {
+    if (PAIRS) {
+        lo = table[2 * s];
+        n = table[2 * s + 1];
+    } else {
+        lo = table[s];
+        n = (long long)table[s + 1] - lo;
+    }
+}
+
 // One scan workgroup: (x, y) scans rows [16 x, 16 x + 16) of block y's segment for the block's queries; a workgroup beyond the block count or
-// past the end of its segment returns at once.  pstride: words per query of `partial` (gridDim.x minima, or the key stride).
+// past the end of its segment (every workgroup of an empty slot) returns at once.  pstride: words per query of `partial` (gridDim.x
+// minima, or the key stride).
 // ALLOW: al's masks and tables (kernels.h, SegAllow).  The workgroup forms its queries' effective masks in LDS, and when no query admits
 // any label of its 16 rows (the granule word) it writes ~0 for each query - one minimum, or the 16 row keys, which the finish / top-k
 // kernels read - and returns before the first bank row.
-template <bool BF16, bool ALLKEYS, bool ALLOW = false>
+template <bool BF16, bool ALLKEYS, bool ALLOW = false, bool PAIRS = false>
 __device__ __forceinline__ void seg_scan_workgroup(const void* __restrict__ bank, const float* __restrict__ query, const int* __restrict__ plan,
                                                    const int* __restrict__ seg_start, int D, unsigned long long* __restrict__ partial, int pstride,
                                                    SegAllow al = SegAllow{}) {
@@ -166,7 +180,8 @@ __device__ __forceinline__ void seg_scan_workgroup(const void* __restrict__ bank
     if (b >= plan[0]) return;
     const int* e = plan + 1 + (size_t)b * PLAN_STRIDE;
     const int s = e[0], nq = e[1];
-    const long long lo = seg_start[s], n = (long long)seg_start[s + 1] - lo;
+    long long lo, n;
+    seg_extent<PAIRS>(seg_start, s, lo, n);
     const long long x0 = (long long)blockIdx.x * SEG_ROWS;
     if (x0 >= n) return;
     if (threadIdx.x < 8) qidx[threadIdx.x] = threadIdx.x < nq ? e[2 + threadIdx.x] : 0;

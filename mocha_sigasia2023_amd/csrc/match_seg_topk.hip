@@ -27,23 +27,24 @@ namespace mocha {
 
 typedef float st_f32x4 __attribute__((ext_vector_type(4)));
 
-template <bool BF16>
+// PAIRS (here and below): seg_start is a resident bank's slot table (match_seg_body.h, seg_extent); an empty slot is an invalid id
+template <bool BF16, bool PAIRS = false>
 __global__ __launch_bounds__(256) void mocha_match_seg_keys(const void* __restrict__ bank, const float* __restrict__ query, const int* __restrict__ plan,
                                                             const int* __restrict__ seg_start, int D, unsigned long long* __restrict__ keys, int kstride) {
-    seg_scan_workgroup<BF16, true>(bank, query, plan, seg_start, D, keys, kstride);
+    seg_scan_workgroup<BF16, true, false, PAIRS>(bank, query, plan, seg_start, D, keys, kstride);
 }
 
 // the all-keys scan of the action-constrained soft matcher: a row outside a constrained query's mask gets the key ~0 - to the selection
 // below a missing row - and workgroups of inadmissible rows write their 16 x queries ~0 keys without reading the bank
-template <bool BF16>
+template <bool BF16, bool PAIRS = false>
 __global__ __launch_bounds__(256) void mocha_match_seg_keys_allow(const void* __restrict__ bank, const float* __restrict__ query, const int* __restrict__ plan,
                                                                   const int* __restrict__ seg_start, int D, unsigned long long* __restrict__ keys, int kstride,
                                                                   SegAllow al) {
-    seg_scan_workgroup<BF16, true, true>(bank, query, plan, seg_start, D, keys, kstride, al);
+    seg_scan_workgroup<BF16, true, true, PAIRS>(bank, query, plan, seg_start, D, keys, kstride, al);
 }
 
 // keys: [group's queries][kstride]; idx0 (Q) / idx_k, dist_k, w_k (Q, k) / out (Q, cols4 x 4): each may be null
-template <bool BF16>
+template <bool BF16, bool PAIRS = false>
 __global__ __launch_bounds__(256) void mocha_seg_topk_blend(const unsigned long long* __restrict__ keys, int kstride, const int32_t* __restrict__ seg, int S,
                                                             const int* __restrict__ seg_start, const void* __restrict__ bank,
                                                             const float* __restrict__ query, int D, const float* __restrict__ enc, int cols4, int k,
@@ -59,7 +60,13 @@ __global__ __launch_bounds__(256) void mocha_seg_topk_blend(const unsigned long 
     const int q = blockIdx.x, tid = threadIdx.x;
     const int s = seg[q];
     st_f32x4* o = out ? reinterpret_cast<st_f32x4*>(out) + (size_t)q * cols4 : nullptr;
-    if (s < 0 || s >= S) {                        // an id outside the table: no neighbour; the decoder reads row 0
+    bool none = s < 0 || s >= S;
+    long long lo = 0, n = 0;
+    if (!none) {
+        seg_extent<PAIRS>(seg_start, s, lo, n);
+        if (PAIRS) none = n == 0;
+    }
+    if (none) {                                   // an id outside the table (or an empty slot): no neighbour; the decoder reads row 0
         if (tid < k) {
             if (idx_k) idx_k[(size_t)q * k + tid] = -1;
             if (dist_k) dist_k[(size_t)q * k + tid] = __builtin_inff();
@@ -70,7 +77,6 @@ __global__ __launch_bounds__(256) void mocha_seg_topk_blend(const unsigned long 
         if (o) for (int i = tid; i < cols4; i += 256) o[i] = reinterpret_cast<const st_f32x4*>(enc)[i];
         return;
     }
-    const long long lo = seg_start[s], n = (long long)seg_start[s + 1] - lo;
     const long long n16 = (n + SEG_ROWS - 1) / SEG_ROWS * SEG_ROWS;          // what the scan wrote of this query's keys (<= kstride)
     const unsigned long long* kq = keys + (size_t)q * kstride;
 
@@ -153,8 +159,10 @@ size_t match_seg_keys_words(int64_t max_rows) { return (size_t)SEG_TOPK_Q * (siz
 
 hipError_t launch_match_seg_topk(const void* bank, int bank_bf16, const float* query, const int32_t* seg, int Q, const int* seg_start, int S,
                                  int64_t max_rows, int D, unsigned long long* keys, int* plan, const float* enc, int k, float temperature,
-                                 int32_t* idx0, int32_t* idx_k, float* dist_k, float* w_k, float* out, hipStream_t s, const SegAllow* al) {
+                                 int32_t* idx0, int32_t* idx_k, float* dist_k, float* w_k, float* out, hipStream_t s, const SegAllow* al,
+                                 int slot_table) {
     if (Q <= 0) return hipSuccess;
+    if (slot_table && bank_bf16) return hipErrorInvalidValue;          // a resident bank is fp32
     if (al && (!al->allow || !al->label || !al->any || !al->gran || !al->gran_start)) return hipErrorInvalidValue;
     if (S < 1 || max_rows < 1 || max_rows > 0x7fffffff - SEG_ROWS || D % (bank_bf16 ? MS_CHUNK_BF16 : MS_CHUNK_F32) != 0 || D % 4 != 0 || k < 1 ||
         k > SEG_TOPK_MAX_K || !(temperature > 0.f) || (out && !enc))
@@ -176,7 +184,12 @@ hipError_t launch_match_seg_topk(const void* bank, int bank_bf16, const float* q
         float* op = out ? out + (size_t)q0 * D : nullptr;
         SegAllow g{};                                   // this group's masks and report
         if (al) { g = *al; g.allow += q0; if (g.applied) g.applied += q0; }
-        if (bank_bf16) {
+        if (slot_table) {
+            if (al) hipLaunchKernelGGL((mocha_match_seg_keys_allow<false, true>), dim3(gx, gy), dim3(256), 0, s, bank, qp, plan, seg_start, D, keys, kstride, g);
+            else hipLaunchKernelGGL((mocha_match_seg_keys<false, true>), dim3(gx, gy), dim3(256), 0, s, bank, qp, plan, seg_start, D, keys, kstride);
+            hipLaunchKernelGGL((mocha_seg_topk_blend<false, true>), dim3(n), dim3(256), 0, s, keys, kstride, sp, S, seg_start, bank, qp, D, enc, D / 4, k,
+                               inv_temp, i0, ik, dk, wk, op, g.allow, g.any, g.applied);
+        } else if (bank_bf16) {
             if (al) hipLaunchKernelGGL(mocha_match_seg_keys_allow<true>, dim3(gx, gy), dim3(256), 0, s, bank, qp, plan, seg_start, D, keys, kstride, g);
             else hipLaunchKernelGGL(mocha_match_seg_keys<true>, dim3(gx, gy), dim3(256), 0, s, bank, qp, plan, seg_start, D, keys, kstride);
             hipLaunchKernelGGL(mocha_seg_topk_blend<true>, dim3(n), dim3(256), 0, s, keys, kstride, sp, S, seg_start, bank, qp, D, enc, D / 4, k, inv_temp,

@@ -28,6 +28,10 @@
 // its 16 rows): when no query admits any of them it writes ~0 minima and returns before its first bank row, otherwise it runs the plain
 // distance loop and masks at key time.  With labels in runs a constrained pass reads about the admissible rows.  The finish kernel is the
 // plain one and also writes applied (1 constrained / 0 nothing asked / -1 fell back).  The same three launches.
+//
+// A resident bank (launch_match_segmented with slot_table, kernels.h): the PAIRS = true instances of the scan and finish kernels read the
+// segment as a {first row, rows} pair of a slot table instead of seg_start[s], seg_start[s + 1]; rows = 0 (an empty slot) is an invalid id.
+// The plan kernel is the same (it only needs S).  The PAIRS = false instances are the kernels as they were.
 #include "kernels.h"
 #include "match_seg_body.h"
 
@@ -80,23 +84,25 @@ __global__ __launch_bounds__(SEG_PLAN_T) void mocha_seg_plan(const int32_t* __re
 }
 
 // partial: [Q][gridDim.x] (query-major, the query's chunks of its segment)
-template <bool BF16>
+// PAIRS: seg_start is a resident bank's slot table (match_seg_body.h, seg_extent)
+template <bool BF16, bool PAIRS = false>
 __global__ __launch_bounds__(256) void mocha_match_seg_scan(const void* __restrict__ bank, const float* __restrict__ query, const int* __restrict__ plan,
                                                             const int* __restrict__ seg_start, int D, unsigned long long* __restrict__ partial) {
-    seg_scan_workgroup<BF16, false>(bank, query, plan, seg_start, D, partial, (int)gridDim.x);
+    seg_scan_workgroup<BF16, false, false, PAIRS>(bank, query, plan, seg_start, D, partial, (int)gridDim.x);
 }
 
 // the action-constrained scan (match_seg_body.h, ALLOW): the same grid, the same partial minima; whole workgroups of inadmissible rows return
 // before their first bank row
-template <bool BF16>
+template <bool BF16, bool PAIRS = false>
 __global__ __launch_bounds__(256) void mocha_match_seg_scan_allow(const void* __restrict__ bank, const float* __restrict__ query, const int* __restrict__ plan,
                                                                   const int* __restrict__ seg_start, int D, unsigned long long* __restrict__ partial,
                                                                   SegAllow al) {
-    seg_scan_workgroup<BF16, false, true>(bank, query, plan, seg_start, D, partial, (int)gridDim.x, al);
+    seg_scan_workgroup<BF16, false, true, PAIRS>(bank, query, plan, seg_start, D, partial, (int)gridDim.x, al);
 }
 
 // allow / any / applied: the constrained match's masks and its per-query report (all null for the plain match)
-template <bool BF16>
+// PAIRS (a resident bank's slot table): an empty slot is an invalid id
+template <bool BF16, bool PAIRS = false>
 __global__ __launch_bounds__(256) void mocha_match_seg_finish(const unsigned long long* __restrict__ partial, int pstride, const int32_t* __restrict__ seg, int S,
                                                               const int* __restrict__ seg_start, const void* __restrict__ bank, const float* __restrict__ query, int D,
                                                               int32_t* __restrict__ idx, int32_t* __restrict__ gidx, float* __restrict__ dist,
@@ -106,7 +112,13 @@ __global__ __launch_bounds__(256) void mocha_match_seg_finish(const unsigned lon
     __shared__ float red[4];
     const int q = blockIdx.x, tid = threadIdx.x;
     const int s = seg[q];
-    if (s < 0 || s >= S) {                        // an id outside the table: no match; the decoder reads row 0
+    bool none = s < 0 || s >= S;
+    long long lo = 0, n = 0;
+    if (!none) {
+        seg_extent<PAIRS>(seg_start, s, lo, n);
+        if (PAIRS) none = n == 0;
+    }
+    if (none) {                                   // an id outside the table (or an empty slot): no match; the decoder reads row 0
         if (tid == 0) {
             if (idx) idx[q] = -1;
             if (gidx) gidx[q] = 0;
@@ -115,7 +127,6 @@ __global__ __launch_bounds__(256) void mocha_match_seg_finish(const unsigned lon
         }
         return;
     }
-    const long long lo = seg_start[s], n = (long long)seg_start[s + 1] - lo;
     const int nch = (int)((n + SEG_ROWS - 1) / SEG_ROWS);
     const unsigned long long* pq = partial + (size_t)q * pstride;
     unsigned long long k = ~0ull;
@@ -151,17 +162,23 @@ hipError_t launch_seg_plan(const int32_t* seg, int Q, int S, int* plan, hipStrea
 
 hipError_t launch_match_segmented(const void* bank, int bank_bf16, const float* query, const int32_t* seg, int Q, const int* seg_start, int S,
                                   int64_t max_rows, int D, unsigned long long* partial, int* plan, int32_t* idx, int32_t* gidx, float* dist,
-                                  hipStream_t s, const SegAllow* al) {
+                                  hipStream_t s, const SegAllow* al, int slot_table) {
     if (Q <= 0) return hipSuccess;
     if (al && (!al->allow || !al->label || !al->any || !al->gran || !al->gran_start)) return hipErrorInvalidValue;
     if (Q > SEG_MAX_Q || S < 1 || max_rows < 1 || D % (bank_bf16 ? MS_CHUNK_BF16 : MS_CHUNK_F32) != 0) return hipErrorInvalidValue;
+    if (slot_table && bank_bf16) return hipErrorInvalidValue;          // a resident bank is fp32
     const unsigned gx = (unsigned)((max_rows + SEG_ROWS - 1) / SEG_ROWS);
     const unsigned gy = (unsigned)seg_blocks_bound(Q, S);
     hipLaunchKernelGGL(mocha_seg_plan, dim3(1), dim3(SEG_PLAN_T), 0, s, seg, Q, S, plan);
     const unsigned long long* am = al ? al->allow : nullptr;
     const unsigned long long* an = al ? al->any : nullptr;
     int32_t* ap = al ? al->applied : nullptr;
-    if (bank_bf16) {
+    if (slot_table) {
+        if (al) hipLaunchKernelGGL((mocha_match_seg_scan_allow<false, true>), dim3(gx, gy), dim3(256), 0, s, bank, query, plan, seg_start, D, partial, *al);
+        else hipLaunchKernelGGL((mocha_match_seg_scan<false, true>), dim3(gx, gy), dim3(256), 0, s, bank, query, plan, seg_start, D, partial);
+        hipLaunchKernelGGL((mocha_match_seg_finish<false, true>), dim3(Q), dim3(256), 0, s, partial, (int)gx, seg, S, seg_start, bank, query, D, idx, gidx,
+                           dist, am, an, ap);
+    } else if (bank_bf16) {
         if (al) hipLaunchKernelGGL(mocha_match_seg_scan_allow<true>, dim3(gx, gy), dim3(256), 0, s, bank, query, plan, seg_start, D, partial, *al);
         else hipLaunchKernelGGL(mocha_match_seg_scan<true>, dim3(gx, gy), dim3(256), 0, s, bank, query, plan, seg_start, D, partial);
         hipLaunchKernelGGL(mocha_match_seg_finish<true>, dim3(Q), dim3(256), 0, s, partial, (int)gx, seg, S, seg_start, bank, query, D, idx, gidx, dist,

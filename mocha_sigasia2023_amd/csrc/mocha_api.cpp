@@ -4,6 +4,7 @@
 #include "../../include/mocha_hip.h"
 #include "kernels.h"
 #include "host_buffer.h"
+#include "extent_alloc.h"
 
 #include <rccl/rccl.h>      // types only: the RCCL entry points are resolved at run time (see Rccl below)
 #include <dlfcn.h>
@@ -162,6 +163,17 @@ struct Bank {
     DeviceBuffer<unsigned char> lab_dev;
     DeviceBuffer<unsigned long long> lab_any, lab_gran;
     DeviceBuffer<int> lab_gran_start;
+    // resident bank (mocha_bank_resident_create): N = the reserved capacity, owned rows, always labelled.  Characters live in `slot`s,
+    // each an extent of whole granules handed out by `extents`; seg_dev then holds the slot table ({first row, rows} per slot, the
+    // kernels' pair form), seg_start stays empty and seg_max_rows is the reserved maximum of rows per character.  add / retire rewrite
+    // table entries in stream order; no pointer or launch shape a captured step bakes in changes while the bank is current.
+    bool resident = false;
+    struct Slot { int64_t first = 0, rows = 0; };      // rows = 0: empty
+    std::vector<Slot> slot;                            // host mirror of the slot table
+    ExtentAlloc extents;                               // units of SEG_GRANULE_ROWS rows
+
+    bool segmented() const { return resident || !seg_start.empty(); }                 // the segmented calls serve this bank
+    int segments() const { return resident ? (int)slot.size() : (int)seg_start.size() - 1; }
 };
 
 // The action constraint of a segmented call: per query a 64-bit allow mask (device) and, optionally, where the `applied` report goes.  A null
@@ -866,12 +878,15 @@ int run_encoder(mocha_ctx* c, const float* tokens, int b, float* encoded, hipStr
 
 // the style MLPs of every decoder layer in float64 (net/transformer.py:102-107): gb (rows, 512 L) = [gamma | beta] per layer, from the
 // float64 token means; hidden = rows x 512 L doubles of scratch
-int run_style_f64(mocha_ctx* c, const double* mean64, double* hidden, float* gb, int rows, hipStream_t s) {
+// tiled: the tiled kernel whatever the row count (launch_linear_f64): a row's constants then do not depend on how many rows come with it
+int run_style_f64(mocha_ctx* c, const double* mean64, double* hidden, float* gb, int rows, hipStream_t s, bool tiled = false) {
     const int L = c->cfg.dec_depth;
     LAUNCH(c, s, "mocha_linear_f64", "dec.style1", 2.0 * rows * 512.0 * L * 256, rows * 8.0 * (256 + 512 * L) + 8.0 * 512 * L * 256,
-           launch_linear_f64(mean64, 256, 0, c->w64.at("dec.Ws1_all").p, c->w64.at("dec.bs1_all").p, hidden, nullptr, 512 * L, rows, 512 * L, 256, 1, 2, s));
+           launch_linear_f64(mean64, 256, 0, c->w64.at("dec.Ws1_all").p, c->w64.at("dec.bs1_all").p, hidden, nullptr, 512 * L, rows, 512 * L, 256, 1, 2, s,
+                             tiled ? 1 : 0));
     LAUNCH(c, s, "mocha_linear_f64", "dec.style2", 2.0 * rows * 512.0 * L * 512, rows * (8.0 + 4.0) * 512 * L + 8.0 * L * 512 * 512,
-           launch_linear_f64(hidden, 512 * L, 512, c->w64.at("dec.Ws2_all").p, c->w64.at("dec.bs2_all").p, nullptr, gb, 512 * L, rows, 512, 512, L, 0, s));
+           launch_linear_f64(hidden, 512 * L, 512, c->w64.at("dec.Ws2_all").p, c->w64.at("dec.bs2_all").p, nullptr, gb, 512 * L, rows, 512, 512, L, 0, s,
+                             tiled ? 1 : 0));
     return 0;
 }
 
@@ -908,7 +923,9 @@ bool dec_cache_ok(const mocha_ctx* c) {
 
 // What the decoder derives from bank entries alone, for rows [0, N) of `enc`: kin = IN(entry) (the folded decoder's keys) and gb = every
 // layer's AdaIN gamma / beta (float64 style MLP of the entry's float64 token mean).  mean64 / hidden: scratch for `cap` rows.
-int build_dec_consts(mocha_ctx* c, const float* enc, int64_t N, float* kin, float* gb, double* mean64, double* hidden, int64_t cap, hipStream_t s) {
+// tiled (a resident bank's add): the style MLP's tiled kernel however few rows these are - what a chunk of more than 16 rows gets here
+int build_dec_consts(mocha_ctx* c, const float* enc, int64_t N, float* kin, float* gb, double* mean64, double* hidden, int64_t cap, hipStream_t s,
+                     bool tiled = false) {
     const size_t D = 90 * 256;
     const int L = c->cfg.dec_depth;
     for (int64_t r0 = 0; r0 < N; r0 += cap) {
@@ -916,7 +933,7 @@ int build_dec_consts(mocha_ctx* c, const float* enc, int64_t N, float* kin, floa
         InormExtra ex = IEXW(c, s); ex.mean64 = mean64;
         LAUNCH(c, s, "mocha_instnorm", "bank.in_cha", 0.0, rows * 90.0 * 256 * 4 * 2,
                launch_instnorm(enc + (size_t)r0 * D, kin + (size_t)r0 * D, nullptr, nullptr, nullptr, nullptr, rows, 90, s, &ex));
-        int rc = run_style_f64(c, mean64, hidden, gb + (size_t)r0 * 512 * L, rows, s);
+        int rc = run_style_f64(c, mean64, hidden, gb + (size_t)r0 * 512 * L, rows, s, tiled);
         if (rc) return rc;
     }
     return 0;
@@ -1320,13 +1337,21 @@ int do_match(mocha_ctx* c, Bank& b, const float* qnm, int Q, int32_t* idx, float
 }
 
 // Scratch of the segmented matcher in workspace set `set` for launches of up to c->seg_q queries against the current table (mocha_bank_set_segments
-// sizes it for every set that exists, so that no segmented call allocates)
+// sizes it for every set that exists, so that no segmented call allocates).  A resident bank: its two reserved maxima - rows per
+// character, slots - stand where the largest segment and the segment count stand
 int ensure_seg_scratch(mocha_ctx* c, int set) {
-    const int S = (int)c->bank.seg_start.size() - 1;
+    const int S = c->bank.segments();
     int rc = reserve(c, c->sets[set].seg_partial, match_seg_scratch_words(c->seg_q, c->bank.seg_max_rows));
     if (!rc) rc = reserve(c, c->sets[set].seg_plan, seg_plan_ints(c->seg_q, S));
     if (!rc) rc = reserve(c, c->sets[set].seg_keys, match_seg_keys_words(c->bank.seg_max_rows));
     return rc;
+}
+
+// A call that searches or reads the bank's rows as ONE set: a resident bank has free extents and retired rows among them, and none of the
+// union's derived data (centroid, norms, images) - it serves the segmented and live calls only
+int refuse_resident(mocha_ctx* c, const char* who) {
+    if (!c->bank.resident) return 0;
+    return fail(c, MOCHA_ERR_STATE, "%s: the current bank is a resident bank (mocha_bank_resident_create), which is searched and read per character only", who);
 }
 
 // the kernels' view of a constraint: the caller's masks and report with the current bank's label tables
@@ -1339,12 +1364,13 @@ SegAllow seg_allow_of(mocha_ctx* c, const AllowArg& a) {
 // al: the action constraint (the ALLOW scan), or null
 int seg_match(mocha_ctx* c, const float* q, int Q, const int32_t* seg, int32_t* idx, int32_t* gidx, float* dist, hipStream_t s,
               const AllowArg* al = nullptr) {
-    if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
     if (al && !c->bank.labelled) return fail(c, MOCHA_ERR_STATE, "no action labels: call mocha_bank_set_labels first");
-    const int set = c->cur, S = (int)c->bank.seg_start.size() - 1;
+    const int set = c->cur, S = c->bank.segments();
     const int D = 90 * 256;
     if (!c->sets[set].seg_partial.p || !c->sets[set].seg_plan.p)
-        return fail(c, MOCHA_ERR_STATE, "workspace set %d has no segmented-match scratch: call mocha_bank_set_segments after changing the workspaces", set);
+        return fail(c, MOCHA_ERR_STATE, "workspace set %d has no segmented-match scratch: call %s after changing the workspaces", set,
+                    c->bank.resident ? "mocha_reserve" : "mocha_bank_set_segments");
     const void* bank = c->bank.is_bf16 ? (const void*)c->bank.bf16.p : (const void*)c->bank.cnt;
     for (int q0 = 0; q0 < Q; q0 += c->seg_q) {
         const int n = std::min(c->seg_q, Q - q0);
@@ -1354,7 +1380,7 @@ int seg_match(mocha_ctx* c, const float* q, int Q, const int32_t* seg, int32_t* 
                (double)n * c->bank.seg_max_rows * D * (c->bank.is_bf16 ? 2.0 : 4.0) + 4.0 * n * D,
                launch_match_segmented(bank, c->bank.is_bf16 ? 1 : 0, q + (size_t)q0 * D, seg + q0, n, c->bank.seg_dev.p, S, c->bank.seg_max_rows, D,
                                       c->sets[set].seg_partial.p, c->sets[set].seg_plan.p, idx ? idx + q0 : nullptr, gidx ? gidx + q0 : nullptr,
-                                      dist ? dist + q0 : nullptr, s, al ? &sa : nullptr));
+                                      dist ? dist + q0 : nullptr, s, al ? &sa : nullptr, c->bank.resident ? 1 : 0));
     }
     return 0;
 }
@@ -1364,21 +1390,23 @@ int seg_match(mocha_ctx* c, const float* q, int Q, const int32_t* seg, int32_t* 
 // queries, through the key buffer of the current workspace set.
 int seg_topk(mocha_ctx* c, const float* q, int Q, const int32_t* seg, int k, float temperature, int32_t* idx0, int32_t* idx_k, float* dist_k,
              float* w_k, float* out, hipStream_t s, const AllowArg* al = nullptr) {
-    if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
     if (al && !c->bank.labelled) return fail(c, MOCHA_ERR_STATE, "no action labels: call mocha_bank_set_labels first");
     SegAllow sa{};
     if (al) sa = seg_allow_of(c, *al);
-    const int set = c->cur, S = (int)c->bank.seg_start.size() - 1;
+    const int set = c->cur, S = c->bank.segments();
     const int D = 90 * 256;
     if (!c->sets[set].seg_keys.p || !c->sets[set].seg_plan.p)
-        return fail(c, MOCHA_ERR_STATE, "workspace set %d has no segmented-match scratch: call mocha_bank_set_segments after changing the workspaces", set);
+        return fail(c, MOCHA_ERR_STATE, "workspace set %d has no segmented-match scratch: call %s after changing the workspaces", set,
+                    c->bank.resident ? "mocha_reserve" : "mocha_bank_set_segments");
     const bool b16 = c->bank.is_bf16;
     const void* bank = b16 ? (const void*)c->bank.bf16.p : (const void*)c->bank.cnt;
     const double passes = (Q + SEG_TOPK_Q - 1) / SEG_TOPK_Q;
     LAUNCH(c, s, b16 ? "mocha_match_seg_keys<bf16>" : "mocha_match_seg_keys<f32>", "match.soft", 3.0 * Q * c->bank.seg_max_rows * D + 2.0 * Q * k * D,
            passes * c->bank.seg_max_rows * D * (b16 ? 2.0 : 4.0) + 16.0 * Q * c->bank.seg_max_rows + Q * (k * (b16 ? 6.0 : 8.0) + 8.0) * D,
            launch_match_seg_topk(bank, b16 ? 1 : 0, q, seg, Q, c->bank.seg_dev.p, S, c->bank.seg_max_rows, D, c->sets[set].seg_keys.p,
-                                 c->sets[set].seg_plan.p, c->bank.enc, k, temperature, idx0, idx_k, dist_k, w_k, out, s, al ? &sa : nullptr));
+                                 c->sets[set].seg_plan.p, c->bank.enc, k, temperature, idx0, idx_k, dist_k, w_k, out, s, al ? &sa : nullptr,
+                                 c->bank.resident ? 1 : 0));
     return 0;
 }
 
@@ -1701,6 +1729,14 @@ int mocha_reserve(mocha_ctx* c, int max_batch) {
     }
     int rc = ensure_ws(c, max_batch);
     if (rc) return rc;
+    if (c->bank.resident) {
+        // a resident bank is searched per character only: its scratch is the segmented matcher's, which depends on nothing but the
+        // workspace and the bank's two reserved maxima - re-sized here, so that the calls after it still never allocate
+        c->seg_q = std::min(SEG_MAX_Q, std::max(set_windows(c, 0), 16));
+        for (int set = 0; set < mocha_ctx::MAX_SETS; ++set)
+            if ((set == 0 || !c->sets[set].ws.empty()) && (rc = ensure_seg_scratch(c, set))) return rc;
+        return 0;
+    }
     if (c->bank.N > 0)                                    // ... and the match scratch of the current bank for that many queries
         for (int set = 0; set < mocha_ctx::MAX_SETS; ++set)
             if (!c->sets[set].ws.empty() && (rc = ensure_match_scratch(c, set, set_windows(c, set), c->bank, true))) return rc;
@@ -1841,7 +1877,7 @@ static int bank_own_rows(mocha_ctx* c, Bank& b, int64_t N) {
     const size_t need = (size_t)N * 90 * 256;
     if (b.cnt_own.n >= need && b.enc_own.n >= need) return 0;
     // the current bank may be the copy that is about to be freed: no dangling pointers if an allocation below fails
-    if (b.cnt == b.cnt_own.p || b.enc == b.enc_own.p) { b.cnt = nullptr; b.enc = nullptr; b.N = 0; c->generation++; }
+    if (b.cnt == b.cnt_own.p || b.enc == b.enc_own.p) { b.cnt = nullptr; b.enc = nullptr; b.N = 0; b.resident = false; b.slot.clear(); c->generation++; }
     int rc = reserve(c, b.cnt_own, need);
     return rc ? rc : reserve(c, b.enc_own, need);
 }
@@ -1867,6 +1903,7 @@ static int bank_set_impl(mocha_ctx* c, Bank& b, const float* cnt_nm, const float
     b.N = N;
     b.is_bf16 = (flags & MOCHA_BANK_BF16) != 0;
     b.seg_start.clear(); b.seg_max_rows = 0;              // a plain bank has no segment table (mocha_bank_set_segments sets it after)
+    b.resident = false; b.slot.clear();                   // ... and replaces a resident bank like any other
     b.labelled = false;                                   // ... and no action labels (mocha_bank_set_labels)
     b.tiled_valid = false; b.tile32_valid = false;
     if (current) c->generation++;                         // a captured step has the previous bank's pointers and row count baked in
@@ -1944,6 +1981,7 @@ int mocha_bank_set(mocha_ctx* c, const float* cnt_nm, const float* encoded, int6
 
 int mocha_match(mocha_ctx* c, const float* query_nm, int Q, int32_t* idx, float* dist, void* stream) {
     int rc = ready(c, 0); if (rc) return rc;
+    if ((rc = refuse_resident(c, "mocha_match"))) return rc;
     if (Q == 0) return 0;
     if (!query_nm || !idx || Q < 0) return fail(c, MOCHA_ERR_ARG, "bad match arguments");
     if (Q == 0) return 0;
@@ -1952,6 +1990,7 @@ int mocha_match(mocha_ctx* c, const float* query_nm, int Q, int32_t* idx, float*
 
 int mocha_match_topk(mocha_ctx* c, const float* query_nm, int Q, int k, int32_t* idx, float* dist, void* stream) {
     int rc = ready(c, 0); if (rc) return rc;
+    if ((rc = refuse_resident(c, "mocha_match_topk"))) return rc;
     if (Q == 0) return 0;
     if (!query_nm || !idx || Q < 0 || k < 1 || k > 64) return fail(c, MOCHA_ERR_ARG, "bad top-k arguments (1 <= k <= 64)");
     if (!c->bank.cnt || c->bank.N <= 0) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
@@ -1973,6 +2012,7 @@ int mocha_match_topk(mocha_ctx* c, const float* query_nm, int Q, int k, int32_t*
 
 int mocha_bank_gather_blend(mocha_ctx* c, const int32_t* idx, const float* dist, float temperature, int Q, int k, float* out, void* stream) {
     int rc = ready(c, 0); if (rc) return rc;
+    if ((rc = refuse_resident(c, "mocha_bank_gather_blend"))) return rc;
     if (!c->bank.enc) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
     if (Q == 0) return 0;
     if (!idx || !dist || !out || Q < 0 || k < 1 || k > 64 || !(temperature > 0.f)) return fail(c, MOCHA_ERR_ARG, "bad gather_blend arguments");
@@ -1984,6 +2024,7 @@ int mocha_bank_gather_blend(mocha_ctx* c, const int32_t* idx, const float* dist,
 
 int mocha_bank_gather(mocha_ctx* c, const int32_t* idx, int Q, float* out, void* stream) {
     int rc = ready(c, 0); if (rc) return rc;
+    if ((rc = refuse_resident(c, "mocha_bank_gather"))) return rc;
     if (!c->bank.enc) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
     if (Q == 0) return 0;
     if (!idx || !out || Q < 0) return fail(c, MOCHA_ERR_ARG, "bad gather arguments");
@@ -1997,8 +2038,9 @@ int mocha_bank_gather(mocha_ctx* c, const int32_t* idx, int Q, float* out, void*
 static int characterize_impl(mocha_ctx* c, const float* src_X, int B, const float* cnt_mean, const float* cnt_std, float* Y,
                              int32_t* idx, void* stream, bool raw, const int32_t* seg = nullptr, const AllowArg* al = nullptr) {
     int rc = ready(c, B); if (rc) return rc;
+    if (!seg && (rc = refuse_resident(c, "mocha_characterize / mocha_step_graph"))) return rc;
     if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
-    if (seg && c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (seg && !c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
     if (B == 0) return 0;
     if (!cnt_mean || !cnt_std || !src_X || !Y) return fail(c, MOCHA_ERR_ARG, "null argument");
     const size_t ys = (size_t)60 * c->cfg.V * c->cfg.C_in;
@@ -2170,6 +2212,7 @@ int mocha_step_graph_lane(mocha_ctx* c, int lane, const float* X1, const float* 
     if (lane < 0 || lane >= c->lanes) return fail(c, MOCHA_ERR_ARG, "lane %d: the context has %d lane(s) (mocha_set_option \"lanes\")", lane, c->lanes);
     int rc = ready(c, 1); if (rc) return rc;
     if (!X1 || !cnt_mean || !cnt_std || !Y1 || !idx) return fail(c, MOCHA_ERR_ARG, "null argument");
+    if ((rc = refuse_resident(c, "mocha_step_graph"))) return rc;
     if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
     if (c->sets[lane].ws.empty()) return fail(c, MOCHA_ERR_STATE, "lane %d has no workspace", lane);
     mocha_ctx::StepKey key; key.x = X1; key.mean = cnt_mean; key.sd = cnt_std; key.y = Y1; key.idx = idx; key.raw = raw != 0;
@@ -2230,7 +2273,7 @@ int mocha_bank_set_segments(mocha_ctx* c, const float* cnt_nm, const float* enco
 int mocha_match_segmented(mocha_ctx* c, const float* query_nm, int Q, const int32_t* seg, int32_t* idx, float* dist, void* stream) {
     int rc = ready(c, 0); if (rc) return rc;
     if (!query_nm || !seg || !idx || Q < 0) return fail(c, MOCHA_ERR_ARG, "bad match_segmented arguments");
-    if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
     if (Q == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const int D = 90 * 256;
@@ -2260,7 +2303,7 @@ int mocha_step_graph_segmented(mocha_ctx* c, const float* X, int S_w, const int3
     int rc = ready(c, S_w); if (rc) return rc;
     if (!X || !seg || !cnt_mean || !cnt_std || !Y || !idx) return fail(c, MOCHA_ERR_ARG, "null argument");
     if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
-    if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
     mocha_ctx::StepKey key; key.x = X; key.mean = cnt_mean; key.sd = cnt_std; key.y = Y; key.idx = idx; key.seg = seg; key.windows = S_w;
     key.raw = raw != 0;
     // the ids are read by the captured kernels on every replay: new ids in `seg` are not part of the key
@@ -2291,7 +2334,7 @@ static int characterize_soft_impl(mocha_ctx* c, const float* src_X, int B, const
                                   const AllowArg* al = nullptr) {
     int rc = ready(c, B); if (rc) return rc;
     if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
-    if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
     if (B == 0) return 0;
     if (!cnt_mean || !cnt_std || !src_X || !Y || !seg) return fail(c, MOCHA_ERR_ARG, "null argument");
     const size_t ys = (size_t)60 * c->cfg.V * c->cfg.C_in;
@@ -2318,7 +2361,7 @@ int mocha_match_topk_segmented(mocha_ctx* c, const float* query_nm, int Q, const
     int rc = soft_args(c, "match_topk_segmented", k, 1.f); if (rc) return rc;
     if ((rc = ready(c, 0))) return rc;
     if (!query_nm || !seg || !idx || Q < 0) return fail(c, MOCHA_ERR_ARG, "bad match_topk_segmented arguments");
-    if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
     if (Q == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const int D = 90 * 256;
@@ -2351,7 +2394,7 @@ int mocha_step_graph_soft_segmented(mocha_ctx* c, const float* X, int S_w, const
     if ((rc = ready(c, S_w))) return rc;
     if (!X || !seg || !cnt_mean || !cnt_std || !Y || !idx_k || !w_k) return fail(c, MOCHA_ERR_ARG, "null argument");
     if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
-    if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
     mocha_ctx::StepKey key; key.x = X; key.mean = cnt_mean; key.sd = cnt_std; key.y = Y; key.seg = seg; key.windows = S_w; key.raw = raw != 0;
     key.soft_k = k; key.soft_t = temperature; key.soft[0] = idx_k; key.soft[1] = w_k;
     auto body = [&](hipStream_t cs) -> int {
@@ -2376,10 +2419,11 @@ int mocha_step_graph_soft_segmented(mocha_ctx* c, const float* X, int S_w, const
 // segment holds, takes the plain answer (match_seg_body.h, the ALLOW scans).  The calls below are the segmented ones with an AllowArg.
 int mocha_bank_set_labels(mocha_ctx* c, const int32_t* labels, void* stream) {
     if (!c) return MOCHA_ERR_ARG;
-    if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (c->bank.resident) return fail(c, MOCHA_ERR_STATE, "bank_set_labels: a resident bank takes its labels with mocha_bank_resident_add");
+    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
     HIPCHK(c, hipSetDevice(c->device));
     if (!labels) { c->bank.labelled = false; c->generation++; return 0; }
-    const int S = (int)c->bank.seg_start.size() - 1;
+    const int S = c->bank.segments();
     const int64_t N = c->bank.N;
     for (int64_t i = 0; i < N; ++i)
         if (labels[i] < 0 || labels[i] > 63) return fail(c, MOCHA_ERR_ARG, "bank_set_labels: label %d of row %lld is outside 0..63", (int)labels[i], (long long)i);
@@ -2421,7 +2465,7 @@ int mocha_match_segmented_allow(mocha_ctx* c, const float* query_nm, int Q, cons
     if (k < 1 || k > MOCHA_SOFT_MAX_K) return fail(c, MOCHA_ERR_ARG, "match_segmented_allow: 1 <= k <= %d neighbours", MOCHA_SOFT_MAX_K);
     int rc = ready(c, 0); if (rc) return rc;
     if (!query_nm || !seg || !allow || !idx || Q < 0) return fail(c, MOCHA_ERR_ARG, "bad match_segmented_allow arguments");
-    if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
     if (!c->bank.labelled) return fail(c, MOCHA_ERR_STATE, "no action labels: call mocha_bank_set_labels first");
     if (Q == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
@@ -2458,7 +2502,7 @@ int mocha_characterize_segmented_allow(mocha_ctx* c, const float* src_X, int B, 
     if (!c) return MOCHA_ERR_ARG;
     if (k != 0) { int rc = soft_args(c, "characterize_segmented_allow", k, temperature); if (rc) return rc; }
     if (B > 0 && (!seg || !allow)) return fail(c, MOCHA_ERR_ARG, "characterize_segmented_allow: null argument");
-    if (!c->bank.seg_start.empty() && !c->bank.labelled) return fail(c, MOCHA_ERR_STATE, "no action labels: call mocha_bank_set_labels first");
+    if (c->bank.segmented() && !c->bank.labelled) return fail(c, MOCHA_ERR_STATE, "no action labels: call mocha_bank_set_labels first");
     const AllowArg al{reinterpret_cast<const unsigned long long*>(allow), applied};
     return characterize_allow_impl(c, src_X, B, seg, al, k, temperature, cnt_mean, cnt_std, Y, idx_k, w_k, raw != 0, stream);
 }
@@ -2472,7 +2516,7 @@ int mocha_step_graph_segmented_allow(mocha_ctx* c, const float* X, int S_w, cons
     int rc = ready(c, S_w); if (rc) return rc;
     if (!X || !seg || !allow || !cnt_mean || !cnt_std || !Y || !idx_k || (k > 0 && !w_k)) return fail(c, MOCHA_ERR_ARG, "null argument");
     if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
-    if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
     if (!c->bank.labelled) return fail(c, MOCHA_ERR_STATE, "no action labels: call mocha_bank_set_labels first");
     const AllowArg al{reinterpret_cast<const unsigned long long*>(allow), applied};
     mocha_ctx::StepKey key; key.x = X; key.mean = cnt_mean; key.sd = cnt_std; key.y = Y; key.seg = seg; key.windows = S_w; key.raw = raw != 0;
@@ -2491,6 +2535,158 @@ int mocha_step_graph_segmented_allow(mocha_ctx* c, const float* X, int S_w, cons
     }
     // the ids and the masks are read by the captured kernels on every replay: new values in `seg` / `allow` are not part of the key
     return step_replay(c, c->seg_allow_step, key, (hipStream_t)stream, body);
+}
+
+// ------------------------------------------------------------------------------------------- resident multi-character bank
+// A multi-character bank whose storage, tables and scratch are reserved ONCE: characters are added to and retired from it by calls that
+// only enqueue work on the caller's stream.  On an fp32 bank a row's distance depends on no other row, the decoder constants are per
+// entry and the label tables per row / 16 rows / character: what ties the characters of mocha_bank_set_segments together is only its
+// contiguous seg_start table and the host values baked into launches.  Here the kernels read a slot table ({first row, rows} per slot,
+// device data; match_seg_body.h, PAIRS) and the launches are shaped by the two reserved maxima, so the captured graphs of the segmented
+// and live steps keep replaying across add / retire: the generation does not move.
+static int64_t granule_units(int64_t rows) { return (rows + SEG_GRANULE_ROWS - 1) / SEG_GRANULE_ROWS; }
+
+int mocha_bank_resident_create(mocha_ctx* c, int64_t capacity_rows, int max_characters, int64_t max_rows_per_character, int flags, void* stream) {
+    int rc = ready(c, 0); if (rc) return rc;
+    if (flags & (MOCHA_BANK_BF16 | MOCHA_BANK_BORROW))
+        return fail(c, MOCHA_ERR_ARG, "bank_resident_create: a resident bank is fp32 and owns its rows (no MOCHA_BANK_BF16, no MOCHA_BANK_BORROW)");
+    if (capacity_rows < 1 || capacity_rows > (int64_t)1 << 30 || max_characters < 1 || max_characters > 1 << 20 || max_rows_per_character < 1 ||
+        max_rows_per_character > capacity_rows)
+        return fail(c, MOCHA_ERR_ARG, "bank_resident_create: needs 1 <= max_rows_per_character <= capacity_rows <= 2^30 and 1 <= max_characters <= 2^20");
+    const int64_t cap = granule_units(capacity_rows) * SEG_GRANULE_ROWS;
+    const size_t D = 90 * 256;
+    const int L = c->cfg.dec_depth;
+    hipStream_t s = (hipStream_t)stream;
+    Bank& b = c->bank;
+    // from here on the previous bank is gone; a failure below leaves the context without a current bank
+    b.cnt = nullptr; b.enc = nullptr; b.N = 0;
+    b.seg_start.clear(); b.seg_max_rows = 0; b.labelled = false; b.resident = false; b.slot.clear();
+    b.is_bf16 = false;
+    b.tiled_valid = false; b.tile32_valid = false; b.x3_valid = false; b.b16f_valid = false; b.b8_valid = false; b.dec_valid = false; b.amax_ok = false;
+    c->generation++;                                      // a captured step has the previous bank's pointers and shapes baked in
+    if ((rc = bank_own_rows(c, b, cap))) return rc;
+    HIPCHK(c, hipMemsetAsync(b.cnt_own.p, 0, (size_t)cap * D * sizeof(float), s));
+    HIPCHK(c, hipMemsetAsync(b.enc_own.p, 0, (size_t)cap * D * sizeof(float), s));
+    // the decoder constants of every row the bank can hold; without the memory the decoder computes them per call, as for any bank
+    if (dec_cache_ok(c) && !(flags & MOCHA_BANK_NO_DEC_CACHE)) {
+        if (b.kin.reserve((size_t)cap * D) != hipSuccess || b.gb.reserve((size_t)cap * 512 * L) != hipSuccess) {
+            (void)hipGetLastError();                      // the failed allocation's sticky error
+            b.kin.release(); b.gb.release();
+        } else {
+            const size_t rows = (size_t)std::min<int64_t>(max_rows_per_character, 4096);
+            if ((rc = reserve(c, c->style_scratch, rows * (256 + (size_t)512 * L)))) return rc;
+            HIPCHK(c, hipMemsetAsync(b.kin.p, 0, (size_t)cap * D * sizeof(float), s));
+            HIPCHK(c, hipMemsetAsync(b.gb.p, 0, (size_t)cap * 512 * L * sizeof(float), s));
+            b.dec_valid = true;
+        }
+    }
+    if (c->gemm_h2) {
+        if ((rc = reserve(c, b.amax, (size_t)cap))) return rc;
+        HIPCHK(c, hipMemsetAsync(b.amax.p, 0, (size_t)cap * sizeof(float), s));
+        b.amax_ok = true;
+    }
+    // label bytes, granule words (one per 16 rows of the BANK: a character's words start at first row / 16), per-slot any and gran_start,
+    // and the slot table - all zero: every slot empty
+    const size_t S = (size_t)max_characters, G = (size_t)(cap / SEG_GRANULE_ROWS);
+    if ((rc = reserve(c, b.lab_dev, (size_t)cap))) return rc;
+    if ((rc = reserve(c, b.lab_any, S))) return rc;
+    if ((rc = reserve(c, b.lab_gran, G))) return rc;
+    if ((rc = reserve(c, b.lab_gran_start, S + 1))) return rc;
+    if ((rc = reserve(c, b.seg_dev, 2 * S))) return rc;
+    HIPCHK(c, hipMemsetAsync(b.lab_dev.p, 0, (size_t)cap, s));
+    HIPCHK(c, hipMemsetAsync(b.lab_any.p, 0, S * sizeof(unsigned long long), s));
+    HIPCHK(c, hipMemsetAsync(b.lab_gran.p, 0, G * sizeof(unsigned long long), s));
+    HIPCHK(c, hipMemsetAsync(b.lab_gran_start.p, 0, (S + 1) * sizeof(int), s));
+    HIPCHK(c, hipMemsetAsync(b.seg_dev.p, 0, 2 * S * sizeof(int), s));
+    b.slot.assign(S, Bank::Slot{});
+    b.extents.reset(cap / SEG_GRANULE_ROWS);
+    b.seg_max_rows = max_rows_per_character;
+    b.resident = true;
+    // the segmented matcher's scratch of every workspace set, for the two reserved maxima
+    c->seg_q = std::min(SEG_MAX_Q, std::max(set_windows(c, 0), 16));
+    for (int set = 0; set < mocha_ctx::MAX_SETS; ++set)
+        if ((set == 0 || !c->sets[set].ws.empty()) && (rc = ensure_seg_scratch(c, set))) { b.resident = false; b.slot.clear(); b.seg_max_rows = 0; return rc; }
+    b.cnt = b.cnt_own.p; b.enc = b.enc_own.p; b.N = cap;
+    b.labelled = true;
+    return 0;
+}
+
+int mocha_bank_resident_add(mocha_ctx* c, int slot, const float* cnt_nm, const float* encoded, int64_t n, const int32_t* labels, int32_t* slot_out,
+                            void* stream) {
+    int rc = ready(c, 0); if (rc) return rc;
+    Bank& b = c->bank;
+    if (!b.resident) return fail(c, MOCHA_ERR_STATE, "bank_resident_add: no resident bank: call mocha_bank_resident_create first");
+    if (!cnt_nm || !encoded) return fail(c, MOCHA_ERR_ARG, "bank_resident_add: null argument");
+    const int S = b.segments();
+    if (slot < -1 || slot >= S) return fail(c, MOCHA_ERR_ARG, "bank_resident_add: slot %d out of range 0 .. %d (-1: the lowest empty one)", slot, S - 1);
+    if (n < 1 || n > b.seg_max_rows)
+        return fail(c, MOCHA_ERR_ARG, "bank_resident_add: %lld rows: a character of this bank has 1 .. %lld", (long long)n, (long long)b.seg_max_rows);
+    if (slot >= 0 && b.slot[slot].rows) return fail(c, MOCHA_ERR_STATE, "bank_resident_add: slot %d is occupied: retire it first", slot);
+    for (int i = 0; slot < 0 && i < S; ++i)
+        if (!b.slot[i].rows) slot = i;
+    if (slot < 0) return fail(c, MOCHA_ERR_STATE, "bank_resident_add: all %d slots are occupied", S);
+    const int64_t units = granule_units(n);
+    const int64_t unit0 = b.extents.take(units);
+    if (unit0 < 0)
+        return fail(c, MOCHA_ERR_STATE, "bank_resident_add: no free extent of %lld rows: the largest is %lld rows (%lld rows free in all; extents do not move)",
+                    (long long)n, (long long)(b.extents.largest() * SEG_GRANULE_ROWS), (long long)(b.extents.free_units() * SEG_GRANULE_ROWS));
+    const int64_t first = unit0 * SEG_GRANULE_ROWS;
+    const size_t D = 90 * 256;
+    const int L = c->cfg.dec_depth;
+    hipStream_t s = (hipStream_t)stream;
+    // rows -> their decoder constants (and bounds) -> their label tables -> the slot, published last
+    rc = [&]() -> int {
+        HIPCHK(c, hipMemcpyAsync(b.cnt_own.p + (size_t)first * D, cnt_nm, (size_t)n * D * sizeof(float), hipMemcpyDeviceToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(b.enc_own.p + (size_t)first * D, encoded, (size_t)n * D * sizeof(float), hipMemcpyDeviceToDevice, s));
+        if (b.dec_valid) {
+            const size_t rows = (size_t)std::min<int64_t>(b.seg_max_rows, 4096);        // what mocha_bank_resident_create reserved
+            int r = build_dec_consts(c, b.enc_own.p + (size_t)first * D, n, b.kin.p + (size_t)first * D, b.gb.p + (size_t)first * 512 * L, c->style_scratch.p,
+                                     c->style_scratch.p + rows * 256, (int64_t)rows, s, true);
+            if (r) return r;
+        }
+        if (b.amax_ok) {
+            HIPCHK(c, hipMemsetAsync(b.amax.p + first, 0, (size_t)n * sizeof(float), s));
+            for (int64_t n0 = 0; n0 < n; n0 += 65535)     // (the kernel's grid.y)
+                LAUNCH(c, s, "mocha_absmax", "bank.absmax", 0.0, 4.0 * std::min<int64_t>(65535, n - n0) * D,
+                       launch_absmax(b.enc_own.p + (size_t)(first + n0) * D, std::min<int64_t>(65535, n - n0), (long long)D, b.amax.p + first + n0, s));
+        }
+        LAUNCH(c, s, "mocha_resident_labels", "bank.labels", 0.0, 5.0 * n,
+               launch_resident_labels(labels, n, first, b.N, b.lab_dev.p, b.lab_gran.p, b.lab_any.p + slot, s));
+        LAUNCH(c, s, "mocha_resident_publish", "bank.publish", 0.0, 12.0,
+               launch_resident_publish(b.seg_dev.p, b.lab_gran_start.p, slot, S, first, n, b.N, s));
+        return 0;
+    }();
+    if (rc) { (void)b.extents.release(unit0, units); return rc; }      // (the slot was not published: its rows are nobody's)
+    b.slot[slot].first = first; b.slot[slot].rows = n;
+    if (slot_out) *slot_out = slot;
+    return 0;
+}
+
+int mocha_bank_resident_retire(mocha_ctx* c, int slot, void* stream) {
+    int rc = ready(c, 0); if (rc) return rc;
+    Bank& b = c->bank;
+    if (!b.resident) return fail(c, MOCHA_ERR_STATE, "bank_resident_retire: no resident bank: call mocha_bank_resident_create first");
+    const int S = b.segments();
+    if (slot < 0 || slot >= S) return fail(c, MOCHA_ERR_ARG, "bank_resident_retire: slot %d out of range 0 .. %d", slot, S - 1);
+    if (!b.slot[slot].rows) return fail(c, MOCHA_ERR_STATE, "bank_resident_retire: slot %d is empty", slot);
+    hipStream_t s = (hipStream_t)stream;
+    // row count 0: the slot's id is now an id outside the table; its rows stay as they are and are never read
+    LAUNCH(c, s, "mocha_resident_publish", "bank.publish", 0.0, 12.0, launch_resident_publish(b.seg_dev.p, b.lab_gran_start.p, slot, S, 0, 0, b.N, s));
+    (void)b.extents.release(b.slot[slot].first / SEG_GRANULE_ROWS, granule_units(b.slot[slot].rows));
+    b.slot[slot] = Bank::Slot{};
+    return 0;
+}
+
+int mocha_bank_resident_info(const mocha_ctx* c, int slot, int64_t* first_row, int64_t* rows, int64_t* free_rows, int64_t* largest_free) {
+    if (!c) return MOCHA_ERR_ARG;
+    const Bank& b = c->bank;
+    if (!b.resident) return MOCHA_ERR_STATE;
+    if (slot < -1 || slot >= b.segments()) return MOCHA_ERR_ARG;
+    if (first_row) *first_row = slot >= 0 ? b.slot[slot].first : 0;
+    if (rows) *rows = slot >= 0 ? b.slot[slot].rows : 0;
+    if (free_rows) *free_rows = b.extents.free_units() * SEG_GRANULE_ROWS;
+    if (largest_free) *largest_free = b.extents.largest() * SEG_GRANULE_ROWS;
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------- RCCL (multi-GPU set-up)
@@ -2659,6 +2855,10 @@ int mocha_bank_broadcast(mocha_ctx* c, void* comm_, int root, int64_t N, int fla
     NCCLCHK(c, g_rccl.CommCount(comm, &world));
     NCCLCHK(c, g_rccl.CommUserRank(comm, &rank));
     if (root < 0 || root >= world || N < 1 || N > (int64_t)1 << 30) return fail(c, MOCHA_ERR_ARG, "bad bank_broadcast arguments");
+    // A resident bank has no union to send.  A root that is alone refuses at once, as the other union calls do; among several ranks it
+    // must not leave the others inside the header exchange, so it announces "no such bank" below - every rank then fails - and names the
+    // reason in its own message
+    if (rank == root && world == 1 && (rc = refuse_resident(c, "mocha_bank_broadcast"))) return rc;
     hipStream_t s = (hipStream_t)stream;
     const size_t D = 90 * 256;
     const bool want_bf16 = (flags & MOCHA_BANK_BF16) != 0;
@@ -2670,12 +2870,13 @@ int mocha_bank_broadcast(mocha_ctx* c, void* comm_, int root, int64_t N, int fla
     if ((rc = reserve(c, c->bcast_hdr, 2 * 4096))) return rc;
     std::vector<long long> hdr((size_t)2 * world, 0);
     long long mine[2] = {(long long)N, want_bf16 ? 1 : 0};
-    if (rank == root) { mine[0] = (c->bank.cnt && c->bank.N == N) ? (long long)N : -1; mine[1] = c->bank.is_bf16 ? 1 : 0; }
+    if (rank == root) { mine[0] = (c->bank.cnt && c->bank.N == N && !c->bank.resident) ? (long long)N : -1; mine[1] = c->bank.is_bf16 ? 1 : 0; }
     HIPCHK(c, hipMemcpyAsync(c->bcast_hdr.p + 2 * rank, mine, sizeof mine, hipMemcpyHostToDevice, s));
     if (world > 1) NCCLCHK(c, g_rccl.AllGather(c->bcast_hdr.p + 2 * rank, c->bcast_hdr.p, 2, ncclInt64, comm, s));
     HIPCHK(c, hipMemcpyAsync(hdr.data(), c->bcast_hdr.p, hdr.size() * sizeof(long long), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     if (hdr[2 * root] != (long long)N || hdr[2 * root] < 0) {
+        if (rank == root && (rc = refuse_resident(c, "mocha_bank_broadcast"))) return rc;
         if (hdr[2 * root] < 0)
             return fail(c, MOCHA_ERR_STATE, "bank_broadcast: the root (rank %d) has no current bank of the number of entries it was called with", root);
         return fail(c, MOCHA_ERR_STATE, "bank_broadcast: the root (rank %d) has no current bank of %lld entries (it announced %lld)", root,
@@ -3123,7 +3324,7 @@ static int live_step_impl(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, i
     if (!c->finalized) return fail(c, MOCHA_ERR_STATE, "weights not finalised: call mocha_finalize_weights first");
     if (!c->pose_norm.p) return fail(c, MOCHA_ERR_STATE, "live_step: no pose norm: call mocha_set_pose_norm first");
     if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set_segments first");
-    if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
     if (al && !c->bank.labelled) return fail(c, MOCHA_ERR_STATE, "no action labels: call mocha_bank_set_labels first");
     mocha_post_cfg d;
     if (!cfg) { mocha_post_cfg_default(&d); cfg = &d; }
@@ -3166,7 +3367,8 @@ static int live_step_impl(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, i
             LAUNCH(c, cs, "mocha_live_ingest", "live.ingest", 0.0, (double)streams * (V * 7.0 * 4 + J * 13.0 * 4 + 40.0 * 4 * 8 + J * 16.0 * 13 * 8),
                    launch_live_ingest(*ing, streams, cs));
         LAUNCH(c, cs, "mocha_live_push", "live.push", streams * 60.0 * J * 150, streams * (60.0 * J * (13 + 15) + J * 26.0) * 4,
-               launch_live_push(ring, Yrot, Ypos, Yvel, Yang, seg, c->bone_parents.p, xraw, eff, valid, streams, J, cs, ing ? ing->have : nullptr));
+               launch_live_push(ring, Yrot, Ypos, Yvel, Yang, seg, c->bone_parents.p, xraw, eff, valid, streams, J, cs, ing ? ing->have : nullptr,
+                                c->bank.resident ? c->bank.seg_dev.p : nullptr, c->bank.resident ? c->bank.segments() : 0));
         const int r = characterize(idx, idx_k, w_k, cs);
         if (r) return r;
         LAUNCH(c, cs, "mocha_pose_heads", "live.heads", 0.0, streams * (60.0 * 12 + V * 28.0 * 4), launch_pose_heads(ystage, heads, speed, streams, c->cfg.T, V, cs));
@@ -3843,7 +4045,7 @@ int mocha_live_step_ours(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, in
     if (!c->cvae_ready) return fail(c, MOCHA_ERR_STATE, "live_step_ours: no CVAE on this context: call mocha_cvae_load_weight and mocha_cvae_finalize first");
     if (!c->pose_norm.p) return fail(c, MOCHA_ERR_STATE, "live_step_ours: no pose norm: call mocha_set_pose_norm first");
     if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set_segments first");
-    if (c->bank.seg_start.empty()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
     mocha_post_cfg d;
     if (!cfg) { mocha_post_cfg_default(&d); cfg = &d; }
     PostParams p{};
@@ -3879,7 +4081,7 @@ int mocha_live_step_ours(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, in
     float* logvar = reinterpret_cast<float*>(ob + ol.logvar);
     const mocha_ours_cfg oc = *ocfg;
     const int J = c->cfg.V + 1, V = c->cfg.V, S = streams;
-    const int nseg = (int)c->bank.seg_start.size() - 1;
+    const int nseg = c->bank.segments();
 
     // sampler -> literal decoder on `cha` -> to_mot (de-normalised) into the staging: the tail of the step, and of the warm pass
     auto tail = [&](const float* cha, hipStream_t cs) -> int {
@@ -3891,7 +4093,8 @@ int mocha_live_step_ours(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, in
     // sampler -> state update -> decoder on the streams' character features -> to_mot -> pose heads -> one post-processing frame
     auto body = [&](hipStream_t cs) -> int {
         LAUNCH(c, cs, "mocha_live_push", "live.push", S * 60.0 * J * 150, S * (60.0 * J * (13 + 15) + J * 26.0) * 4,
-               launch_live_push(ring, Yrot, Ypos, Yvel, Yang, seg, c->bone_parents.p, xraw, eff, valid, S, J, cs));
+               launch_live_push(ring, Yrot, Ypos, Yvel, Yang, seg, c->bone_parents.p, xraw, eff, valid, S, J, cs, nullptr,
+                                c->bank.resident ? c->bank.seg_dev.p : nullptr, c->bank.resident ? c->bank.segments() : 0));
         c->lane = 0; c->cur = 0;
         int r;
         if ((r = run_embed(c, xraw, S, WS(c, "x5"), true, cs, true))) return r;
@@ -4094,6 +4297,7 @@ int mocha_scan_byte_state(mocha_ctx* c, int set, int32_t* state, void* stream) {
 int mocha_bank_view(mocha_ctx* c, const float** cnt_nm, const float** encoded, const float** centroid, const float** row_norm2,
                     const void** cnt_bf16, int64_t* N) {
     if (!c) return MOCHA_ERR_ARG;
+    if (int rc = refuse_resident(c, "mocha_bank_view")) return rc;
     if (!c->bank.cnt || c->bank.N <= 0) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
     if (cnt_nm) *cnt_nm = c->bank.cnt;
     if (encoded) *encoded = c->bank.enc;
@@ -4106,6 +4310,7 @@ int mocha_bank_view(mocha_ctx* c, const float** cnt_nm, const float** encoded, c
 
 int mocha_bank_export(mocha_ctx* c, float* cnt_nm, float* encoded, void* stream) {
     int rc = ready(c, 0); if (rc) return rc;
+    if ((rc = refuse_resident(c, "mocha_bank_export"))) return rc;
     if (!c->bank.cnt || !c->bank.enc || c->bank.N <= 0) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set or mocha_bank_broadcast first");
     const size_t bytes = (size_t)c->bank.N * 90 * 256 * sizeof(float);
     hipStream_t s = (hipStream_t)stream;

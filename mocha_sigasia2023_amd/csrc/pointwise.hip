@@ -918,10 +918,10 @@ __global__ __launch_bounds__(256) void mocha_linear_f64_rows(const double* __res
 }
 
 hipError_t launch_linear_f64(const double* X, int ldx, int xcol, const double* W, const double* bias, double* y64, float* y32, int ldy,
-                             int M, int N, int K, int L, int act, hipStream_t s) {
+                             int M, int N, int K, int L, int act, hipStream_t s, int tiled) {
     if (M <= 0) return hipSuccess;
     if (N < 1 || K < 32 || (K & 31) || L < 1 || (act != 0 && act != 2) || (!y64 && !y32) || (ldx & 1) || (xcol & 1)) return hipErrorInvalidValue;      // 16-byte row loads
-    if (M <= 16) {
+    if (M <= 16 && !tiled) {
         const dim3 grid((N + 7) / 8, M, L);
         if (act == 2) hipLaunchKernelGGL(mocha_linear_f64_rows<2>, grid, dim3(256), 0, s, X, ldx, xcol, W, bias, y64, y32, ldy, N, K);
         else hipLaunchKernelGGL(mocha_linear_f64_rows<0>, grid, dim3(256), 0, s, X, ldx, xcol, W, bias, y64, y32, ldy, N, K);

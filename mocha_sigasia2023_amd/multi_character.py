@@ -90,95 +90,14 @@ def soft_params(soft, who: str):
     return int(k), float(t)
 
 
-class MultiCharacterBank:
-    """``banks``: a sequence of ``(cnt_nm, encoded)`` pairs, one per character (cnt_nm (N_c, 90*256) z-scored with the SAME global
-    cnt_mean / cnt_std as every other character, encoded (N_c, 90, 256)).  They are concatenated once into device tensors this object
-    owns and lends to the context.  ``bf16`` / ``dec_cache`` mean what they mean for ``ContextBank``.  ``labels``: one integer array
-    (N_c,) of action labels 0 .. 63 per character (``set_labels``)."""
-
-    def __init__(self, model: Generator, banks: Sequence[Tuple[torch.Tensor, torch.Tensor]], bf16: bool = False, dec_cache: bool = True,
-                 labels=None):
-        model._need()
-        self.model = model
-        if len(banks) < 1:
-            raise ValueError("MultiCharacterBank: needs at least one character")
-        dev = model.device
-        nms, encs, sizes = [], [], []
-        for c, (nm, enc) in enumerate(banks):
-            nm = _dev_f32(nm, dev, None, f"banks[{c}].cnt_nm").reshape(-1, NTOK * DIM)
-            enc = _dev_f32(enc, dev, (NTOK, DIM), f"banks[{c}].encoded").reshape(-1, NTOK, DIM)
-            if nm.shape[0] != enc.shape[0]:
-                raise ValueError(f"banks[{c}]: cnt_nm and encoded have different entry counts")
-            if nm.shape[0] < 1:
-                raise ValueError(f"banks[{c}]: a character needs at least one entry")
-            nms.append(nm); encs.append(enc); sizes.append(int(nm.shape[0]))
-        self.cnt_nm = torch.cat(nms).contiguous()
-        self.encoded = torch.cat(encs).contiguous()
-        self.N = int(self.cnt_nm.shape[0])
-        self.S = len(sizes)
-        self.seg_start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        self._bf16 = bool(bf16)
-        self._dec_cache = bool(dec_cache)
-        self.labels = None if labels is None else self._check_labels(labels)
-        self.activate()
-
-    def rows(self, c: int) -> Tuple[int, int]:
-        """(start, stop) of character ``c``'s rows in the concatenated bank."""
-        if not 0 <= c < self.S:
-            raise IndexError(f"character {c} out of range 0 .. {self.S - 1}")
-        return int(self.seg_start[c]), int(self.seg_start[c + 1])
-
-    def activate(self):
-        """Make this bank (with its segment table) the context's current bank; the no-cache intent travels as a flag of this one call."""
-        flags = _BORROW | (_BF16 if self._bf16 else 0) | (0 if self._dec_cache else _NO_DEC_CACHE)
-        seg = (C.c_int64 * (self.S + 1))(*self.seg_start.tolist())
-        self.model._ctx.call("mocha_bank_set_segments", _ptr(self.cnt_nm), _ptr(self.encoded), self.N, seg, self.S, flags, _stream())
-        self.model._bank = self
-        self._send_labels()
-        return self
-
-    def _check_labels(self, labels) -> np.ndarray:
-        if len(labels) != self.S:
-            raise ValueError(f"labels: {len(labels)} arrays for {self.S} characters")
-        out = []
-        for c, lab in enumerate(labels):
-            a = lab.cpu().numpy() if isinstance(lab, torch.Tensor) else np.asarray(lab)
-            a = a.reshape(-1)
-            n = int(self.seg_start[c + 1] - self.seg_start[c])
-            if a.shape[0] != n:
-                raise ValueError(f"labels[{c}]: {a.shape[0]} labels for {n} entries")
-            if not np.issubdtype(a.dtype, np.integer):
-                raise ValueError(f"labels[{c}]: integer labels expected, got {a.dtype}")
-            if a.min() < 0 or a.max() > 63:
-                raise ValueError(f"labels[{c}]: labels must lie in 0 .. 63")
-            out.append(a.astype(np.int32))
-        return np.ascontiguousarray(np.concatenate(out))
-
-    def _send_labels(self):
-        if self.labels is None:
-            return
-        self.model._ctx.call("mocha_bank_set_labels", self.labels.ctypes.data_as(C.POINTER(C.c_int32)), _stream())
-
-    def set_labels(self, labels):
-        """Action labels of every character's entries (one integer array (N_c,) per character, 0 .. 63), or None to remove them.
-        ``allow=`` needs them."""
-        self._ensure()
-        if labels is None:
-            self.labels = None
-            self.model._ctx.call("mocha_bank_set_labels", None, _stream())
-            return self
-        self.labels = self._check_labels(labels)
-        self._send_labels()
-        return self
+class _SegmentedBank:
+    """What ``MultiCharacterBank`` and ``ResidentCharacterBank`` share: the segmented calls on the model's current bank.  A subclass
+    provides ``model``, ``S`` (ids are 0 .. S - 1), ``labels`` (None: no action labels) and ``_ensure()``."""
 
     def _allow(self, allow, n: int, who: str) -> torch.Tensor:
         if self.labels is None:
             raise RuntimeError(f"{who}: allow= needs a bank with action labels (MultiCharacterBank(labels=) or set_labels)")
         return allow_masks(allow, n, self.model.device, who)
-
-    def _ensure(self):
-        if getattr(self.model, "_bank", None) is not self:
-            self.activate()
 
     def _ids(self, characters, n: int) -> torch.Tensor:
         """Character ids as a device int32 vector of n entries.  Host data (list, numpy, CPU tensor) is checked here, before anything is
@@ -270,6 +189,202 @@ class MultiCharacterBank:
         idx = torch.empty((B,), dtype=torch.int32, device=m.device)
         m._ctx.call("mocha_characterize_segmented", _ptr(X), B, _ptr(ids), _ptr(mean), _ptr(std), _ptr(Y), _ptr(idx), 1 if raw else 0, _stream())
         return (Y, idx) if return_index else Y
+
+
+class MultiCharacterBank(_SegmentedBank):
+    """``banks``: a sequence of ``(cnt_nm, encoded)`` pairs, one per character (cnt_nm (N_c, 90*256) z-scored with the SAME global
+    cnt_mean / cnt_std as every other character, encoded (N_c, 90, 256)).  They are concatenated once into device tensors this object
+    owns and lends to the context.  ``bf16`` / ``dec_cache`` mean what they mean for ``ContextBank``.  ``labels``: one integer array
+    (N_c,) of action labels 0 .. 63 per character (``set_labels``)."""
+
+    def __init__(self, model: Generator, banks: Sequence[Tuple[torch.Tensor, torch.Tensor]], bf16: bool = False, dec_cache: bool = True,
+                 labels=None):
+        model._need()
+        self.model = model
+        if len(banks) < 1:
+            raise ValueError("MultiCharacterBank: needs at least one character")
+        dev = model.device
+        nms, encs, sizes = [], [], []
+        for c, (nm, enc) in enumerate(banks):
+            nm = _dev_f32(nm, dev, None, f"banks[{c}].cnt_nm").reshape(-1, NTOK * DIM)
+            enc = _dev_f32(enc, dev, (NTOK, DIM), f"banks[{c}].encoded").reshape(-1, NTOK, DIM)
+            if nm.shape[0] != enc.shape[0]:
+                raise ValueError(f"banks[{c}]: cnt_nm and encoded have different entry counts")
+            if nm.shape[0] < 1:
+                raise ValueError(f"banks[{c}]: a character needs at least one entry")
+            nms.append(nm); encs.append(enc); sizes.append(int(nm.shape[0]))
+        self.cnt_nm = torch.cat(nms).contiguous()
+        self.encoded = torch.cat(encs).contiguous()
+        self.N = int(self.cnt_nm.shape[0])
+        self.S = len(sizes)
+        self.seg_start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        self._bf16 = bool(bf16)
+        self._dec_cache = bool(dec_cache)
+        self.labels = None if labels is None else self._check_labels(labels)
+        self.activate()
+
+    def rows(self, c: int) -> Tuple[int, int]:
+        """(start, stop) of character ``c``'s rows in the concatenated bank."""
+        if not 0 <= c < self.S:
+            raise IndexError(f"character {c} out of range 0 .. {self.S - 1}")
+        return int(self.seg_start[c]), int(self.seg_start[c + 1])
+
+    def activate(self):
+        """Make this bank (with its segment table) the context's current bank; the no-cache intent travels as a flag of this one call."""
+        flags = _BORROW | (_BF16 if self._bf16 else 0) | (0 if self._dec_cache else _NO_DEC_CACHE)
+        seg = (C.c_int64 * (self.S + 1))(*self.seg_start.tolist())
+        self.model._ctx.call("mocha_bank_set_segments", _ptr(self.cnt_nm), _ptr(self.encoded), self.N, seg, self.S, flags, _stream())
+        self.model._bank = self
+        self._send_labels()
+        return self
+
+    def _check_labels(self, labels) -> np.ndarray:
+        if len(labels) != self.S:
+            raise ValueError(f"labels: {len(labels)} arrays for {self.S} characters")
+        out = []
+        for c, lab in enumerate(labels):
+            a = lab.cpu().numpy() if isinstance(lab, torch.Tensor) else np.asarray(lab)
+            a = a.reshape(-1)
+            n = int(self.seg_start[c + 1] - self.seg_start[c])
+            if a.shape[0] != n:
+                raise ValueError(f"labels[{c}]: {a.shape[0]} labels for {n} entries")
+            if not np.issubdtype(a.dtype, np.integer):
+                raise ValueError(f"labels[{c}]: integer labels expected, got {a.dtype}")
+            if a.min() < 0 or a.max() > 63:
+                raise ValueError(f"labels[{c}]: labels must lie in 0 .. 63")
+            out.append(a.astype(np.int32))
+        return np.ascontiguousarray(np.concatenate(out))
+
+    def _send_labels(self):
+        if self.labels is None:
+            return
+        self.model._ctx.call("mocha_bank_set_labels", self.labels.ctypes.data_as(C.POINTER(C.c_int32)), _stream())
+
+    def set_labels(self, labels):
+        """Action labels of every character's entries (one integer array (N_c,) per character, 0 .. 63), or None to remove them.
+        ``allow=`` needs them."""
+        self._ensure()
+        if labels is None:
+            self.labels = None
+            self.model._ctx.call("mocha_bank_set_labels", None, _stream())
+            return self
+        self.labels = self._check_labels(labels)
+        self._send_labels()
+        return self
+
+    def _ensure(self):
+        if getattr(self.model, "_bank", None) is not self:
+            self.activate()
+
+
+class ResidentCharacterBank(_SegmentedBank):
+    """A multi-character bank whose characters are added and retired IN PLACE (``mocha_bank_resident_create``): storage for
+    ``capacity_rows`` rows (rounded up to 16), ``max_characters`` slots and up to ``max_rows_per_character`` rows per character are
+    reserved once, on the model's context; ``add`` / ``retire`` / ``replace`` then only enqueue work on the current stream - the
+    character's own bytes and its own decoder constants - and the captured steps of ``MultiStreamCharacterizer``, ``LiveSession`` and
+    ``LiveOursSession`` keep replaying: the model's generation does not move.  fp32 only.  A character's id is its slot, 0 ..
+    ``max_characters - 1``, whether or not the slot holds a character: a query that names an empty slot gets idx -1 / dist +inf, a
+    live stream that names one sits the step out as a warming stream does (``valid == 0``).  Every character is labelled (``add``
+    without labels gives every entry action 0), so ``allow=`` always applies.  A resident bank cannot be rebuilt from the host: once
+    another bank has been activated on the model, this object's calls raise."""
+
+    def __init__(self, model: Generator, capacity_rows: int, max_characters: int, max_rows_per_character: int, dec_cache: bool = True):
+        model._need()
+        self.model = model
+        self.S = int(max_characters)
+        self.max_rows_per_character = int(max_rows_per_character)
+        model._ctx.call("mocha_bank_resident_create", int(capacity_rows), self.S, self.max_rows_per_character, 0 if dec_cache else _NO_DEC_CACHE,
+                        _stream())
+        model._bank = self
+        self.labels = [None] * self.S                  # per slot: the character's labels as given (None: empty, or added without)
+
+    def _ensure(self):
+        if getattr(self.model, "_bank", None) is not self:
+            raise RuntimeError("ResidentCharacterBank: another bank has been activated on this model; a resident bank cannot be rebuilt "
+                               "from the host - create a new one and add its characters again")
+
+    def _info(self, slot: int):
+        self._ensure()
+        out = [C.c_int64(0) for _ in range(4)]
+        ctx = self.model._ctx
+        rc = ctx.lib.mocha_bank_resident_info(ctx.h, int(slot), *[C.byref(v) for v in out])
+        if rc == -1:                                   # MOCHA_ERR_ARG: the only argument that can be wrong is the slot
+            raise IndexError(f"ResidentCharacterBank: slot {slot} out of range 0 .. {self.S - 1}")
+        if rc != 0:                                    # MOCHA_ERR_STATE: the context's current bank is no longer this one
+            raise RuntimeError(f"mocha_bank_resident_info failed (status {rc}): the context's current bank is not a resident bank "
+                               "(it was replaced through the C ABI)")
+        return [int(v.value) for v in out]
+
+    def rows(self, slot: int) -> Tuple[int, int]:
+        """(start, stop) of the rows the character in ``slot`` occupies in the bank; start == stop for an empty slot."""
+        if not 0 <= int(slot) < self.S:
+            raise IndexError(f"slot {slot} out of range 0 .. {self.S - 1}")
+        first, n, _, _ = self._info(slot)
+        return first, first + n
+
+    @property
+    def free_rows(self) -> int:
+        """Rows not occupied by any character (whole 16-row granules)."""
+        return self._info(-1)[2]
+
+    @property
+    def largest_free(self) -> int:
+        """Rows of the largest free extent: the largest character ``add`` can still take (extents never move)."""
+        return self._info(-1)[3]
+
+    def add(self, cnt_nm, encoded, labels=None, slot: Optional[int] = None) -> int:
+        """One more character: cnt_nm (n, 90*256) z-scored as every other character's, encoded (n, 90, 256), ``labels`` (n,) integer
+        action labels 0 .. 63 (host data is range-checked here; a device int32 tensor is taken as it is and read as label & 63) or None:
+        action 0 for every entry.  ``slot``: the slot to fill, or None for the lowest empty one.  Returns the slot - the character's id.
+        Enqueued on the current stream, no synchronisation; ``RuntimeError`` when the slot is occupied, no slot is empty or no free
+        extent holds n rows (the message names the largest one)."""
+        self._ensure()
+        dev = self.model.device
+        nm = _dev_f32(cnt_nm, dev, None, "cnt_nm").reshape(-1, NTOK * DIM)
+        enc = _dev_f32(encoded, dev, (NTOK, DIM), "encoded").reshape(-1, NTOK, DIM)
+        n = int(nm.shape[0])
+        if enc.shape[0] != n:
+            raise ValueError("add: cnt_nm and encoded have different entry counts")
+        if slot is not None and not 0 <= int(slot) < self.S:
+            raise IndexError(f"add: slot {slot} out of range 0 .. {self.S - 1}")
+        lab = kept = None
+        if labels is not None:
+            if isinstance(labels, torch.Tensor) and labels.device.type != "cpu":
+                if labels.dtype != torch.int32:
+                    raise ValueError("add: device labels must be int32")
+                lab = labels.reshape(-1).to(dev).contiguous()
+                kept = lab
+            else:
+                a = (labels.numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)).reshape(-1)
+                if a.size and not np.issubdtype(a.dtype, np.integer):
+                    raise ValueError(f"add: integer labels expected, got {a.dtype}")
+                if a.size and (a.min() < 0 or a.max() > 63):
+                    raise ValueError("add: labels must lie in 0 .. 63")
+                kept = np.ascontiguousarray(a.astype(np.int32))
+                lab = torch.from_numpy(kept).to(dev)
+            if lab.shape[0] != n:
+                raise ValueError(f"add: {lab.shape[0]} labels for {n} entries")
+        got = C.c_int32(-1)
+        self.model._ctx.call("mocha_bank_resident_add", -1 if slot is None else int(slot), _ptr(nm), _ptr(enc), n, _ptr(lab) if lab is not None else None,
+                             C.byref(got), _stream())
+        self.labels[got.value] = kept if kept is not None else np.zeros(n, np.int32)
+        return int(got.value)
+
+    def retire(self, slot: int):
+        """The character in ``slot`` leaves: the slot is empty and its rows are free from the next call on the current stream on."""
+        self._ensure()
+        if not 0 <= int(slot) < self.S:
+            raise IndexError(f"retire: slot {slot} out of range 0 .. {self.S - 1}")
+        self.model._ctx.call("mocha_bank_resident_retire", int(slot), _stream())
+        self.labels[int(slot)] = None
+        return self
+
+    def replace(self, slot: int, cnt_nm, encoded, labels=None) -> int:
+        """Another character under the same id: ``retire(slot)`` (if it holds one) then ``add(..., slot=slot)``, on the current stream."""
+        first, stop = self.rows(slot)
+        if first != stop:
+            self.retire(slot)
+        return self.add(cnt_nm, encoded, labels=labels, slot=slot)
 
 
 class MultiStreamCharacterizer:
