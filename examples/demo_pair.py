@@ -122,8 +122,8 @@ if a.from_raw:
              **{"src_" + k: v.cpu().numpy() for k, v in zip(("Yrot", "Ypos", "Yvel", "Yang"), src_bones)})
 names = ["Joint%02d" % i for i in range(24)]
 parents = LAYOUTS["mocha"]["parents"]
-write_bvh(os.path.join(a.out, "cm_trans.bvh"), names, parents, nn["bvh_pos"], nn["bvh_euler"])          # :690-713
-write_bvh(os.path.join(a.out, "ours.bvh"), names, parents, ours["bvh_pos"], ours["bvh_euler"])
+write_bvh(os.path.join(a.out, "cm_trans.bvh"), names, parents, nn["bvh_pos"], nn["bvh_euler"], model=model)          # :690-713; the numbers are formatted on the device
+write_bvh(os.path.join(a.out, "ours.bvh"), names, parents, ours["bvh_pos"], ours["bvh_euler"], model=model)
 print(f"{N} windows per clip: featurize + NN branch + Ours branch + post-processing in {dt * 1e3:.1f} ms "
       f"({(N - 1) / dt:.0f} frames/s including the sequential CVAE loop); matched entries {idx[:8].tolist()} ...")
 for k in ("cm_trans.bvh", "ours.bvh"):

@@ -812,6 +812,43 @@ int mocha_bvh_motion(mocha_ctx* ctx, const char* text_dev, int64_t nbytes, const
                      const int32_t* joint_map, int v_out, const float* offsets_out, float* rot, float* pos, mocha_bvh_report* report,
                      void* stream);
 
+/* BVH TEXT behind mocha_postprocess: the MOTION block the reference's writer emits (motion/bvh.py:210-224) for the float64 channels
+ * mocha_postprocess leaves on the device, produced on the device.  The hierarchy lines stay with the host (a few hundred bytes).
+ *   mocha_bvh_text_bound   : HOST only, no context, no GPU.  frames * (C * MOCHA_BVHW_MAX_TOKEN + 1): the most bytes frames frames can
+ *                            take, C = 3 + 3 n_joints (save_positions 0) or 6 n_joints (1).  -1 for frames < 0 or n_joints < 1.
+ *   mocha_bvh_format       : bvh_pos / bvh_euler (F,n_joints,3) float64 (DEVICE; F = clip_offsets[n_clips]; degrees) -> text_dev (DEVICE,
+ *                            any alignment, capacity bytes).  A token is element (frame, column) of a virtual (F, C) matrix.
+ *                            save_positions 0: columns 0..2 are pos[f, 0, :], column 3 + 3i + k is euler[f, visit[i], axes[k]].
+ *                            save_positions 1: column 6i + k is pos[f, visit[i], k] for k < 3, else euler[f, visit[i], axes[k - 3]].
+ *                            visit (HOST, n_joints): the joint of column group i - the writer's depth-first order; axes (HOST, 3): the
+ *                            axis (0 x, 1 y, 2 z) of rotation channel k.  Every token is followed by one space, every frame ends with
+ *                            '\n' behind its last space.  Clips are concatenated along the frames (clip_offsets: HOST, n_clips + 1,
+ *                            increasing from 0, as mocha_ingest_clips takes them) and their text blocks lie back to back:
+ *                            clip_text_begin (HOST, n_clips + 1, written by the call) holds the first byte of every clip's block and,
+ *                            last, the total.
+ *                            A token is Python's "%f" of the float64 (:215-222): the correctly rounded six-decimal expansion, ties to
+ *                            even, in exact integer arithmetic (csrc/fmt_f6.h); the sign is the sign BIT (-0.0 and -1e-9 give
+ *                            "-0.000000").  Admitted values are finite with |x| < 1e12 - a token then has at most 20 bytes,
+ *                            MOCHA_BVHW_MAX_TOKEN with its space.  NaN, +-inf and |x| >= 1e12 are refused.
+ *                            The call launches mocha_bvhw_count and mocha_bvhw_scan, then waits for `stream` ONCE to read the totals.
+ *                            report (HOST, may be NULL): tokens = F C, bytes = the exact length of the text, first_bad = the SMALLEST
+ *                            refused token ordinal (frame * C + column) or -1.
+ *                            MOCHA_ERR_STATE: a value was refused; report.first_bad says which, text_dev is untouched.
+ *                            MOCHA_ERR_ARG after the wait: capacity is below the exact total; report.bytes and clip_text_begin are set,
+ *                            text_dev is untouched.  Otherwise the call enqueues mocha_bvhw_write and returns without a second wait;
+ *                            no byte outside [text_dev, text_dev + report.bytes) is written.
+ *                            MOCHA_ERR_ARG, nothing launched (judged before the context is looked at): a NULL required pointer,
+ *                            n_joints outside 1..MOCHA_BVH_MAX_JOINTS, a visit or axes that is no permutation, clip_offsets that do
+ *                            not increase from 0, a negative capacity, mocha_bvh_text_bound at or above 2^31 bytes, a NULL context.
+ *                            NOT capture-safe: the call uploads its tables, may (re)allocate the context's format buffer (8 bytes per
+ *                            256 tokens plus the tables, grow-only, does not move mocha_generation()) and waits for `stream`. */
+#define MOCHA_BVHW_MAX_TOKEN 21   /* bytes, with the space */
+typedef struct mocha_bvhw_report { int64_t tokens, bytes, first_bad; } mocha_bvhw_report;  /* first_bad: token ordinal or -1 */
+int64_t mocha_bvh_text_bound(int64_t frames, int n_joints, int save_positions);
+int mocha_bvh_format(mocha_ctx* ctx, const double* bvh_pos, const double* bvh_euler, const int32_t* clip_offsets, int n_clips,
+                     int n_joints, const int32_t* visit, const int32_t axes[3], int save_positions, char* text_dev, int64_t capacity,
+                     int64_t* clip_text_begin, mocha_bvhw_report* report, void* stream);
+
 /* Bank build statistics: cnt_mean, cnt_std = np.mean(cnt, 0), np.std(cnt, 0) over the N bank entries
  * (compute_cnt_norm.py:174-175; population std), x (N, 90*256) -> mean, std (90*256). */
 int mocha_column_stats(mocha_ctx* ctx, const float* x, int64_t N, float* mean, float* std_, void* stream);

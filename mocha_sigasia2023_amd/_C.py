@@ -55,6 +55,13 @@ class mocha_bvh_report(C.Structure):
     _fields_ = [("tokens", C.c_int64), ("slow", C.c_int64), ("first_bad", C.c_int64)]
 
 
+BVHW_MAX_TOKEN = 21
+
+
+class mocha_bvhw_report(C.Structure):
+    _fields_ = [("tokens", C.c_int64), ("bytes", C.c_int64), ("first_bad", C.c_int64)]
+
+
 _vp, _i, _i64 = C.c_void_p, C.c_int, C.c_int64
 
 # name -> (restype, argtypes); every symbol include/mocha_hip.h declares
@@ -144,6 +151,9 @@ SIGNATURES = {
     "mocha_bvh_header": (_i, [_vp, _i64, C.POINTER(mocha_bvh_hdr)]),
     "mocha_bvh_motion": (_i, [_vp, _vp, _i64, _vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_int32), _i, _i, _i, C.POINTER(C.c_int32), _i,
                               C.POINTER(C.c_float), _vp, _vp, C.POINTER(mocha_bvh_report), _vp]),
+    "mocha_bvh_text_bound": (_i64, [_i64, _i, _i]),
+    "mocha_bvh_format": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _vp, _i64,
+                              C.POINTER(_i64), C.POINTER(mocha_bvhw_report), _vp]),
     "mocha_set_rccl_library":(_i, [C.c_char_p]),
     "mocha_comm_unique_id": (_i, [_vp, _vp]),
     "mocha_comm_init": (_i, [_vp, _vp, _i, _i]),

@@ -7,6 +7,7 @@ from .generator import CVAE, ContextBank, Generator, OursSession, StreamingChara
 from .multi_character import MultiCharacterBank, MultiStreamCharacterizer, ResidentCharacterBank, action_mask  # noqa: F401
 from .bank import BatchPipeline, ShardedContextBank, build_bank, build_database_from_bvh, load_bank, save_bank  # noqa: F401
 from .postprocess import Inertializer, PostProcessor, pose_heads, retarget_clip, retarget_clip_ours, retarget_frame_ours, write_bvh  # noqa: F401
+from .postprocess import BvhValueRefused, format_bvh_motion, write_bvh_clips  # noqa: F401
 from .live import LiveOursSession, LiveSession  # noqa: F401
 from .ingest import IngestConfig, Ingestor, clip_windows, ingest_clips  # noqa: F401
 from .bvh import BvhClips, BvhHeader, load_bvh, read_bvh_header  # noqa: F401
@@ -16,6 +17,6 @@ from .weights import DEFAULT_CFG, param_shapes, synthetic_state_dict  # noqa: F4
 
 __all__ = ["Generator", "CVAE", "OursSession", "ContextBank", "StreamingCharacterizer", "mean_variance_norm", "skeleton_constants",
            "synthetic_state_dict", "param_shapes", "DEFAULT_CFG", "build_bank", "save_bank", "load_bank", "ShardedContextBank", "BatchPipeline",
-           "PostProcessor", "pose_heads", "MultiCharacterBank", "MultiStreamCharacterizer", "ResidentCharacterBank", "action_mask", "retarget_clip", "retarget_clip_ours", "retarget_frame_ours", "write_bvh",
+           "PostProcessor", "pose_heads", "MultiCharacterBank", "MultiStreamCharacterizer", "ResidentCharacterBank", "action_mask", "retarget_clip", "retarget_clip_ours", "retarget_frame_ours", "write_bvh", "write_bvh_clips", "format_bvh_motion", "BvhValueRefused",
            "LiveSession", "LiveOursSession", "Inertializer", "Ingestor", "IngestConfig", "ingest_clips", "clip_windows",
            "read_bvh_header", "load_bvh", "BvhHeader", "BvhClips", "build_database_from_bvh"]

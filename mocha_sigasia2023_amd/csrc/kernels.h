@@ -306,6 +306,23 @@ struct BvhParams {
 };
 // launch = 0 count, 1 scan, 2 parse, 3 finish + fill, 4 patch (n_patch slow tokens converted on the host): one kernel each
 hipError_t launch_bvh_parse(const BvhParams& p, int launch, hipStream_t s);
+// The way back (mocha_bvh_format, bvh_format.hip): bvh_pos / bvh_euler (F,V,3) float64 -> the MOTION text of the reference's writer.
+// Token t = frame * C + column of a virtual (F, C) matrix; the text is produced in blocks of BVHW_BLOCK tokens, one per lane.
+static constexpr int BVHW_BLOCK = 256, BVHW_MAX_TOKEN = 21;
+struct BvhwReport { unsigned long long first_bad, bytes; };      // first_bad: the smallest refused token ordinal, ~0 = none
+struct BvhwParams {
+    const double *pos, *euler;          // (F,V,3)
+    const int *visit, *offsets;         // device: (V) joint of column group i, (n_clips+1) frame offsets
+    unsigned *counts, *prefix;          // device: (nblocks) bytes per block, (nblocks+1) their exclusive scan
+    long long* clip_begin;              // device: (n_clips+1) first byte of every clip's text, then the total
+    BvhwReport* report;
+    unsigned char* text;
+    int ax[3];
+    int V, C, save_positions, n_clips;
+    unsigned T, nblocks;                // tokens = F * C, blocks of BVHW_BLOCK tokens
+};
+// launch = 0 count, 1 scan, 2 write: one kernel each
+hipError_t launch_bvh_format(const BvhwParams& p, int launch, hipStream_t s);
 static constexpr int POST_STATE_DOUBLES = 8 + MOCHA_MAX_BONES * 3 + MOCHA_MAX_CONTACT * 19;
 struct PostParams {
     const float* heads;             // (clips, frames, V, 13)

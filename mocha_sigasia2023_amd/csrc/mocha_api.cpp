@@ -281,6 +281,9 @@ struct mocha_ctx {
     // device: the BVH text parser's tables, report, slow-token list and per-block token counts (mocha_bvh_motion).  Grow-only; only that
     // call reads it and it is never captured, so a new allocation does not move the generation.
     DeviceBuffer<unsigned long long> bvh_ws;
+    // device: the BVH text writer's report, clip byte offsets, uploaded tables and per-block byte counts (mocha_bvh_format).  Grow-only;
+    // only that call reads it and it is never captured, so a new allocation does not move the generation.
+    DeviceBuffer<unsigned long long> bvhw_ws;
     DeviceBuffer<float> pose_norm;     // [x_mean | x_std | y_mean | y_std], (V+1)*C_in each (norm.npz of the reference)
     bool use_tiled = false;            // option "bank_tiled": -4 % on the cold pass for 2 x the bf16 copy's memory (profiles/r04/c_tiled_loader_ab.txt): off
     DeviceBuffer<unsigned long long> topk_keys{BUF_MOVES_GENERATION};      // every row's key of up to 8 queries (mocha_match_topk)
@@ -3974,6 +3977,80 @@ int mocha_bvh_motion(mocha_ctx* c, const char* text_dev, int64_t nbytes, const c
     p.n_patch = (int)slow.size();
     LAUNCH(c, s, "mocha_bvh_patch", "bvh.patch", 0.0, slow.size() * 20.0, launch_bvh_parse(p, 4, s));
     HIPCHK(c, hipStreamSynchronize(s));               // `slow` is the copy's source
+    return 0;
+}
+
+int64_t mocha_bvh_text_bound(int64_t frames, int n_joints, int save_positions) {
+    if (frames < 0 || n_joints < 1) return -1;
+    const int64_t C = save_positions ? 6 * (int64_t)n_joints : 3 + 3 * (int64_t)n_joints;
+    return frames * (C * MOCHA_BVHW_MAX_TOKEN + 1);
+}
+
+int mocha_bvh_format(mocha_ctx* c, const double* bvh_pos, const double* bvh_euler, const int32_t* clip_offsets, int n_clips, int n_joints,
+                     const int32_t* visit, const int32_t axes[3], int save_positions, char* text_dev, int64_t capacity,
+                     int64_t* clip_text_begin, mocha_bvhw_report* report, void* stream) {
+    // the arguments are judged before the context is looked at: every refusal below needs neither a context nor a device
+    if (report) *report = mocha_bvhw_report{0, 0, -1};
+    if (!bvh_pos || !bvh_euler || !visit || !axes || !text_dev || !clip_text_begin) return fail(c, MOCHA_ERR_ARG, "bvh_format: null argument");
+    if (n_joints < 1 || n_joints > MOCHA_BVH_MAX_JOINTS) return fail(c, MOCHA_ERR_ARG, "bvh_format: n_joints must be 1..%d", MOCHA_BVH_MAX_JOINTS);
+    {
+        char seen[MOCHA_BVH_MAX_JOINTS] = {0};
+        for (int i = 0; i < n_joints; ++i)
+            if (visit[i] < 0 || visit[i] >= n_joints || seen[visit[i]]++)
+                return fail(c, MOCHA_ERR_ARG, "bvh_format: visit[%d] = %d: visit must be a permutation of the joints", i, visit[i]);
+        int axis_seen = 0;
+        for (int k = 0; k < 3; ++k) {
+            if (axes[k] < 0 || axes[k] > 2 || (axis_seen >> axes[k] & 1)) return fail(c, MOCHA_ERR_ARG, "bvh_format: axes must be a permutation of 0, 1, 2");
+            axis_seen |= 1 << axes[k];
+        }
+    }
+    int rc = clip_offsets_check(c, "bvh_format", clip_offsets, n_clips, 1); if (rc) return rc;
+    if (capacity < 0) return fail(c, MOCHA_ERR_ARG, "bvh_format: negative capacity");
+    const int64_t F = clip_offsets[n_clips], per_frame = save_positions ? 6 * (int64_t)n_joints : 3 + 3 * (int64_t)n_joints;
+    if (mocha_bvh_text_bound(F, n_joints, save_positions) >= (int64_t)1 << 31)
+        return fail(c, MOCHA_ERR_ARG, "bvh_format: %lld frames of %lld numbers may take 2^31 bytes or more: split the call", (long long)F,
+                    (long long)per_frame);
+    if (!c) return fail(nullptr, MOCHA_ERR_ARG, "bvh_format: null context");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+
+    // the buffer, in 8-byte words: report | clip byte offsets (read back together) | frame offsets | visit  (uploaded)  | block counts | prefix
+    typedef unsigned long long W;
+    const size_t nC = (size_t)n_clips, T = (size_t)(F * per_frame), nblocks = (T + BVHW_BLOCK - 1) / BVHW_BLOCK;
+    const size_t w_begin = 2, w_off = w_begin + nC + 1, w_visit = w_off + (nC + 2) / 2, w_counts = w_visit + ((size_t)n_joints + 1) / 2,
+                 w_prefix = w_counts + (nblocks + 1) / 2, words = w_prefix + (nblocks + 2) / 2;
+    std::vector<W> tab(w_counts, 0);
+    BvhwReport fresh{~0ull, 0ull};
+    memcpy(&tab[0], &fresh, sizeof fresh);
+    memcpy(&tab[w_off], clip_offsets, (nC + 1) * sizeof(int32_t));
+    memcpy(&tab[w_visit], visit, (size_t)n_joints * sizeof(int32_t));
+    if ((rc = reserve(c, c->bvhw_ws, words))) return rc;
+    W* ws = c->bvhw_ws.p;
+    HIPCHK(c, hipMemcpyAsync(ws, tab.data(), tab.size() * sizeof(W), hipMemcpyHostToDevice, s));
+
+    BvhwParams p{};
+    p.pos = bvh_pos; p.euler = bvh_euler;
+    p.report = reinterpret_cast<BvhwReport*>(ws);
+    p.clip_begin = reinterpret_cast<long long*>(ws + w_begin);
+    p.offsets = reinterpret_cast<const int*>(ws + w_off); p.visit = reinterpret_cast<const int*>(ws + w_visit);
+    p.counts = reinterpret_cast<unsigned*>(ws + w_counts); p.prefix = reinterpret_cast<unsigned*>(ws + w_prefix);
+    p.text = reinterpret_cast<unsigned char*>(text_dev);
+    for (int k = 0; k < 3; ++k) p.ax[k] = axes[k];
+    p.V = n_joints; p.C = (int)per_frame; p.save_positions = save_positions ? 1 : 0; p.n_clips = n_clips;
+    p.T = (unsigned)T; p.nblocks = (unsigned)nblocks;
+    LAUNCH(c, s, "mocha_bvhw_count", "bvhw.count", 0.0, T * 8.0 + nblocks * 4.0, launch_bvh_format(p, 0, s));
+    LAUNCH(c, s, "mocha_bvhw_scan", "bvhw.scan", 0.0, nblocks * 12.0, launch_bvh_format(p, 1, s));
+    std::vector<W> got(w_off);
+    HIPCHK(c, hipMemcpyAsync(got.data(), ws, got.size() * sizeof(W), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));               // the one wait: the totals decide what the call returns (and `tab` may go)
+    const int64_t bad = got[0] == ~0ull ? -1 : (int64_t)got[0], bytes = (int64_t)got[1];
+    if (report) *report = mocha_bvhw_report{(int64_t)T, bytes, bad};
+    if (bad >= 0)
+        return fail(c, MOCHA_ERR_STATE, "bvh_format: token %lld (frame %lld, column %lld) is NaN, infinite or at least 1e12 in magnitude", (long long)bad,
+                    (long long)(bad / per_frame), (long long)(bad % per_frame));
+    for (size_t i = 0; i <= nC; ++i) clip_text_begin[i] = (int64_t)got[w_begin + i];
+    if (capacity < bytes) return fail(c, MOCHA_ERR_ARG, "bvh_format: the text takes %lld bytes, capacity is %lld", (long long)bytes, (long long)capacity);
+    LAUNCH(c, s, "mocha_bvhw_write", "bvhw.write", 0.0, T * 8.0 + (double)bytes, launch_bvh_format(p, 2, s));
     return 0;
 }
 

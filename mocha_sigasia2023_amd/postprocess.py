@@ -1,7 +1,8 @@
 """Host mirror of the demo's post-processing: decoded windows -> animated skeleton -> BVH.
 
 ``pose_heads``, ``PostProcessor.run`` and ``PostProcessor.step`` call the HIP kernels of csrc/postprocess.hip through the C ABI; nothing here
-computes on the host except the final text formatting of ``write_bvh`` (the reference's motion/bvh.py:179-224 layout).
+computes on the host except the hierarchy lines of ``write_bvh`` (the reference's motion/bvh.py:179-224 layout): with ``model=`` the numbers
+of the MOTION block are formatted on the device too (``format_bvh_motion``, ``write_bvh_clips``; csrc/bvh_format.hip), without it on the host.
 """
 from __future__ import annotations
 
@@ -238,20 +239,60 @@ _CHANNEL = {"x": "Xrotation", "y": "Yrotation", "z": "Zrotation"}
 _AXIS = {"x": 0, "y": 1, "z": 2}
 
 
-def write_bvh(path: str, names: Sequence[str], parents: Sequence[int], positions, euler_deg, offsets=None,
-              order: str = "zyx", frametime: float = 1.0 / 60.0):
-    """BVH text in the reference writer's layout (motion/bvh.py:145-224, save_positions=False): the hierarchy is walked
-    depth-first in child-index order, every joint has three rotation channels named after ``order``, the root also three
-    position channels, leaves get a zero ``End Site``.  positions / euler_deg (N,V,3); offsets default to the first frame's
-    positions (test_fullframework.py:699)."""
-    pos = np.asarray(positions.cpu() if torch.is_tensor(positions) else positions, dtype=np.float64)
-    rot = np.asarray(euler_deg.cpu() if torch.is_tensor(euler_deg) else euler_deg, dtype=np.float64)
-    off = pos[0] if offsets is None else np.asarray(offsets, dtype=np.float64)
-    parents = [int(p) for p in parents]
-    if not (len(names) == len(parents) == pos.shape[1] == rot.shape[1]):
-        raise ValueError("write_bvh: names, parents, positions and rotations disagree on the joint count")
+class BvhValueRefused(ValueError):
+    """``format_bvh_motion``: a channel value is NaN, infinite or at least 1e12 in magnitude (``first_bad``: its token ordinal,
+    frame * columns + column) - the device writes no text for such input; ``write_bvh`` formats it on the host instead."""
+
+    def __init__(self, first_bad: int, message: str):
+        super().__init__(message)
+        self.first_bad = first_bad
+
+
+def _dev_f64(model: Generator, a) -> torch.Tensor:
+    """A contiguous float64 tensor on the model's device; anything else is cast THERE (fp32 -> float64 is exact)."""
+    if isinstance(a, np.ndarray):
+        a = torch.from_numpy(a)
+    return torch.as_tensor(a).to(model.device).to(torch.float64).contiguous()
+
+
+def format_bvh_motion(model: Generator, positions, euler_deg, visit: Sequence[int], order: str = "zyx", save_positions: bool = False,
+                      clip_offsets: Optional[Sequence[int]] = None):
+    """The MOTION block of the reference's writer (motion/bvh.py:210-224) as bytes ON THE DEVICE (``mocha_bvh_format``): positions /
+    euler_deg (F,V,3), float64 on the device as ``PostProcessor.run`` leaves ``bvh_pos`` / ``bvh_euler`` (anything else is cast on the
+    device), ``visit`` the joint order ``write_bvh`` returns, every number as Python's ``"%f "``, a newline behind every frame.
+    ``clip_offsets`` (n_clips + 1 frame offsets increasing from 0 to F; default one clip) cuts the frames into clips whose text blocks lie
+    back to back.  Returns (text, offsets): a uint8 device tensor of exactly the text's length and the n_clips + 1 byte offsets of the
+    clips' blocks in it (numpy int64).  Raises ``BvhValueRefused`` for NaN, infinities and |x| >= 1e12.  Waits for the current stream once
+    (the totals); the text itself is written behind that wait, in stream order.  Not for graph capture."""
+    pos, rot = _dev_f64(model, positions), _dev_f64(model, euler_deg)
+    if pos.dim() != 3 or pos.shape[2] != 3 or pos.shape != rot.shape:
+        raise ValueError(f"format_bvh_motion: positions {tuple(pos.shape)} and euler_deg {tuple(rot.shape)} must both be (F,V,3)")
+    F, V = int(pos.shape[0]), int(pos.shape[1])
+    offs = [0, F] if clip_offsets is None else [int(v) for v in clip_offsets]
+    if offs[-1] != F:
+        raise ValueError(f"format_bvh_motion: clip_offsets end at {offs[-1]}, the arrays hold {F} frames")
+    n = len(offs) - 1
+    ctx = model._ctx
+    bound = int(ctx.lib.mocha_bvh_text_bound(F, V, int(save_positions)))
+    if bound >= 2 ** 31:
+        raise ValueError(f"format_bvh_motion: {F} frames of {V} joints may take 2^31 bytes of text or more: format fewer frames per call")
+    text = torch.empty((max(bound, 1),), dtype=torch.uint8, device=model.device)
+    begin = (C.c_int64 * (n + 1))()
+    rep = _C.mocha_bvhw_report()
+    with torch.cuda.device(model.device):
+        rc = ctx.lib.mocha_bvh_format(ctx.h, _ptr(pos), _ptr(rot), (C.c_int32 * (n + 1))(*offs), n, V, (C.c_int32 * len(visit))(*[int(j) for j in visit]),
+                                      (C.c_int32 * 3)(*[_AXIS[c] for c in order]), int(save_positions), _ptr(text), bound, begin, C.byref(rep),
+                                      C.c_void_p(torch.cuda.current_stream(model.device).cuda_stream))
+    if rc != 0 and rep.first_bad >= 0:
+        raise BvhValueRefused(int(rep.first_bad), (ctx.lib.mocha_last_error(ctx.h) or b"?").decode())
+    _C.check(ctx.lib, ctx.h, rc, "mocha_bvh_format")
+    return text[: int(rep.bytes)], np.array(list(begin), dtype=np.int64)
+
+
+def _bvh_header_lines(names, parents, off, order: str, frames: int, frametime: float, save_positions: bool):
+    """The lines of a BVH file in front of its MOTION numbers, in the reference writer's layout (motion/bvh.py:145-208), and ``visit``:
+    the depth-first joint order, which is the column order of the motion block."""
     chan = " ".join(_CHANNEL[c] for c in order)
-    ax = [_AXIS[c] for c in order]
     lines, visit = [], [0]
 
     def joint(i, tabs):
@@ -259,7 +300,10 @@ def write_bvh(path: str, names: Sequence[str], parents: Sequence[int], positions
         lines.append(f"{tabs}JOINT {names[i]}"); lines.append(f"{tabs}{{")
         t = tabs + "\t"
         lines.append("%sOFFSET %f %f %f" % (t, off[i, 0], off[i, 1], off[i, 2]))
-        lines.append(f"{t}CHANNELS 3 {chan}")
+        if save_positions:
+            lines.append(f"{t}CHANNELS 6 Xposition Yposition Zposition {chan} ")      # (the reference's trailing space, bvh.py:152)
+        else:
+            lines.append(f"{t}CHANNELS 3 {chan}")
         kids = [j for j, p in enumerate(parents) if p == i]
         for j in kids:
             joint(j, t)
@@ -275,16 +319,119 @@ def write_bvh(path: str, names: Sequence[str], parents: Sequence[int], positions
     for j, p in enumerate(parents):
         if p == 0:
             joint(j, "\t")
-    lines += ["}", "MOTION", "Frames: %i" % len(rot), "Frame Time: %f" % frametime]
-    # the MOTION block: per frame the root's position, then every visited joint's three angles in channel order, each number as
-    # "%f " - one matrix in that column order and ONE format operation for the whole block (a Python loop over frames and joints
-    # took 20 ms for a 585-frame clip, several times the GPU's share of the demo)
+    lines += ["}", "MOTION", "Frames: %i" % frames, "Frame Time: %f" % frametime]
+    return lines, visit
+
+
+def _host_motion_block(pos, rot, visit, order: str, save_positions: bool) -> Optional[str]:
+    """The MOTION block on the host (no trailing newline; None without frames): per frame the root's position, then every visited
+    joint's three angles in channel order - with ``save_positions`` every visited joint's position and angles -, each number as
+    "%f " - one matrix in that column order and ONE format operation for the whole block (a Python loop over frames and joints
+    took 20 ms for a 585-frame clip, several times the GPU's share of the demo)."""
+    ax = [_AXIS[c] for c in order]
     n = rot.shape[0]
-    if n:
+    if not n:
+        return None
+    if save_positions:
+        cols = [a for j in visit for a in (pos[:, j, :], rot[:, j][:, ax])]
+    else:
         cols = [pos[:, 0, :]] + [rot[:, j][:, ax] for j in visit]
-        M = np.concatenate(cols, axis=1)                            # (n, 3 + 3 * len(visit))
-        row_fmt = "%f " * M.shape[1]
-        lines.append(("\n".join([row_fmt] * n)) % tuple(M.ravel().tolist()))
+    M = np.concatenate(cols, axis=1)                            # (n, 3 + 3 * len(visit)) or (n, 6 * len(visit))
+    row_fmt = "%f " * M.shape[1]
+    return ("\n".join([row_fmt] * n)) % tuple(M.ravel().tolist())
+
+
+def _write_with_text(path, lines, text: Optional[np.ndarray]):
+    """Header lines, then the motion block as the bytes the device produced (they end with the last frame's newline)."""
     with open(path, "w") as f:
         f.write("\n".join(lines) + "\n")
+        if text is not None and len(text):
+            f.flush()
+            f.buffer.write(text.data)
+
+
+def write_bvh(path: str, names: Sequence[str], parents: Sequence[int], positions, euler_deg, offsets=None,
+              order: str = "zyx", frametime: float = 1.0 / 60.0, save_positions: bool = False, model: Optional[Generator] = None):
+    """BVH text in the reference writer's layout (motion/bvh.py:145-224): the hierarchy is walked depth-first in child-index
+    order, every joint has three rotation channels named after ``order``, the root also three position channels - with
+    ``save_positions`` every joint has six -, leaves get a zero ``End Site``.  positions / euler_deg (N,V,3); offsets default to the
+    first frame's positions (test_fullframework.py:699).  Returns the joint order of the motion columns.
+    With ``model`` the numbers are formatted on the model's device (``format_bvh_motion``): the arrays stay there (float64 as
+    ``PostProcessor.run`` leaves them; anything else is cast there), one copy brings the text bytes back and they go to the file as they
+    are.  Input the device refuses (NaN, infinities, |x| >= 1e12) takes the host route below; the file is the same bytes on either route.
+    Without ``model`` every number goes through Python's "%f " on the host."""
+    parents = [int(p) for p in parents]
+    if model is not None and len(euler_deg):
+        pos_d, rot_d = _dev_f64(model, positions), _dev_f64(model, euler_deg)
+        if not (pos_d.dim() == rot_d.dim() == 3 and len(names) == len(parents) == pos_d.shape[1] == rot_d.shape[1]):
+            raise ValueError("write_bvh: names, parents, positions and rotations disagree on the joint count")
+        off = pos_d[0].cpu().numpy() if offsets is None else np.asarray(offsets, dtype=np.float64)
+        lines, visit = _bvh_header_lines(names, parents, off, order, int(rot_d.shape[0]), frametime, save_positions)
+        try:
+            text, _ = format_bvh_motion(model, pos_d, rot_d, visit, order, save_positions)
+        except BvhValueRefused:
+            text = None
+        if text is not None:
+            _write_with_text(path, lines, text.cpu().numpy())         # the one copy: the text's bytes
+            return visit
+    pos = np.asarray(positions.cpu() if torch.is_tensor(positions) else positions, dtype=np.float64)
+    rot = np.asarray(euler_deg.cpu() if torch.is_tensor(euler_deg) else euler_deg, dtype=np.float64)
+    off = pos[0] if offsets is None else np.asarray(offsets, dtype=np.float64)
+    if not (len(names) == len(parents) == pos.shape[1] == rot.shape[1]):
+        raise ValueError("write_bvh: names, parents, positions and rotations disagree on the joint count")
+    lines, visit = _bvh_header_lines(names, parents, off, order, len(rot), frametime, save_positions)
+    block = _host_motion_block(pos, rot, visit, order, save_positions)
+    if block is not None:
+        lines.append(block)
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return visit
+
+
+def write_bvh_clips(model: Generator, paths: Sequence[str], names: Sequence[str], parents: Sequence[int], positions, euler_deg,
+                    clip_offsets: Sequence[int], offsets=None, order: str = "zyx", frametime: float = 1.0 / 60.0,
+                    save_positions: bool = False):
+    """Many files of ONE skeleton: positions / euler_deg (F,V,3) hold the clips one after the other, ``clip_offsets`` (len(paths) + 1,
+    increasing from 0 to F) cuts them, file i gets clip i.  All numbers are formatted by one ``format_bvh_motion`` call and come back
+    in one copy (into pinned host memory where torch offers it); each file gets its own header - ``offsets`` (V,3), or by default the
+    first frame of ITS clip - and its slice of the text.  Calls whose text bound reaches 2 GiB are split at clip boundaries.  A clip
+    the device refuses (see ``write_bvh``) is written by the host route; every file equals what ``write_bvh`` writes for its clip.
+    Returns the joint order of the motion columns."""
+    offs = [int(v) for v in clip_offsets]
+    if len(offs) != len(paths) + 1 or offs[0] != 0 or any(b <= a for a, b in zip(offs, offs[1:])):
+        raise ValueError("write_bvh_clips: clip_offsets must hold len(paths) + 1 frame offsets increasing from 0")
+    parents = [int(p) for p in parents]
+    pos_d, rot_d = _dev_f64(model, positions), _dev_f64(model, euler_deg)
+    if not (pos_d.dim() == rot_d.dim() == 3 and len(names) == len(parents) == pos_d.shape[1] == rot_d.shape[1]) or pos_d.shape[0] != offs[-1]:
+        raise ValueError("write_bvh_clips: names, parents, positions, rotations and clip_offsets disagree on the joints or frames")
+    V = len(names)
+    firsts = None if offsets is not None else pos_d[torch.as_tensor(offs[:-1], device=pos_d.device)].cpu().numpy()      # (n_clips,V,3)
+    fixed = None if offsets is None else np.asarray(offsets, dtype=np.float64)
+    bound = lambda frames: int(model._ctx.lib.mocha_bvh_text_bound(frames, V, int(save_positions)))
+    visit, first = None, 0
+    while first < len(paths):
+        last = first + 1                                             # clips first .. last-1 share a call
+        while last < len(paths) and bound(offs[last + 1] - offs[first]) < 2 ** 31:
+            last += 1
+        lo, hi = offs[first], offs[last]
+        heads = [_bvh_header_lines(names, parents, fixed if fixed is not None else firsts[i], order, offs[i + 1] - offs[i], frametime,
+                                   save_positions) for i in range(first, last)]
+        visit = heads[0][1]
+        try:
+            text, begin = format_bvh_motion(model, pos_d[lo:hi], rot_d[lo:hi], visit, order, save_positions, [o - lo for o in offs[first: last + 1]])
+        except BvhValueRefused:
+            for i in range(first, last):
+                write_bvh(paths[i], names, parents, pos_d[offs[i]: offs[i + 1]], rot_d[offs[i]: offs[i + 1]],
+                          None if fixed is None else fixed, order, frametime, save_positions, model=model)
+            first = last
+            continue
+        try:
+            host = torch.empty(text.shape, dtype=torch.uint8, pin_memory=True)
+        except RuntimeError:
+            host = torch.empty(text.shape, dtype=torch.uint8)
+        host.copy_(text)                                             # the one copy
+        data = host.numpy()
+        for i in range(first, last):
+            _write_with_text(paths[i], heads[i - first][0], data[begin[i - first]: begin[i - first + 1]])
+        first = last
     return visit

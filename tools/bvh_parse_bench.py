@@ -3,7 +3,7 @@
 
     python tools/bvh_parse_bench.py [--clips 64 --frames 3600 --rounds 3 --out profiles/r16/bvh_parse.json]
 
-Workload: `clips` synthetic walks (synthetic.raw_walk_clip, 24 joints) of `frames` frames written by write_bvh, about 1.9 MB of text
+Workload: `clips` synthetic walks (synthetic.raw_walk_clip, 24 joints) of `frames` frames written by write_bvh_clips, about 1.9 MB of text
 each.  In the same process, alternating per round, HIP events and clocks untouched:
 
   (a) the host-to-device copy of the packed text, from pageable and from pinned memory (HIP events);
@@ -29,7 +29,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import bvh_ref  # noqa: E402
-from mocha_sigasia2023_amd import Generator, _C, load_bvh, read_bvh_header, synthetic, write_bvh  # noqa: E402
+from mocha_sigasia2023_amd import Generator, _C, load_bvh, read_bvh_header, synthetic, write_bvh_clips  # noqa: E402
 from mocha_sigasia2023_amd.skeleton import LAYOUTS  # noqa: E402
 
 HBM_PEAK = 8.0e12
@@ -50,11 +50,11 @@ def main():
     par = LAYOUTS["mocha"]["parents"]
     names = ["Joint%02d" % i for i in range(24)]
     tmp = tempfile.mkdtemp(prefix="bvh_parse_bench_")
-    paths = []
-    for i in range(a.clips):
-        rot, pos = synthetic.raw_walk_clip(par, a.frames, seed=1000 + i)
-        paths.append(os.path.join(tmp, f"clip{i:03d}.bvh"))
-        write_bvh(paths[-1], names, par, pos, rot)
+    paths = [os.path.join(tmp, f"clip{i:03d}.bvh") for i in range(a.clips)]
+    walks = [synthetic.raw_walk_clip(par, a.frames, seed=1000 + i) for i in range(a.clips)]
+    write_bvh_clips(model, paths, names, par, np.concatenate([w[1] for w in walks]), np.concatenate([w[0] for w in walks]),
+                    [i * a.frames for i in range(a.clips + 1)])       # the input files: one format call on the device, the same bytes as write_bvh's
+    del walks
     texts = [open(p, "rb").read() for p in paths]
     hdrs = [read_bvh_header(t) for t in texts]
     V, F = 24, a.clips * a.frames
