@@ -4,11 +4,16 @@ mocap frame at a time through ``LiveSession`` - ring push + featurize, segmented
 frame per push, one captured graph - and written as two BVH files.
 
     python examples/live_demo.py [--frames 180] [--out bench_outputs/live_demo] [--ours [--seed 7]] [--switch 120 [--inertial 0.1]] [--raw L]
-                                 [--actions A,B[:F]] [--load-at F]
+                                 [--actions A,B[:F]] [--load-at F] [--ours-per-character]
 
 ``--ours`` runs the CVAE ("Ours") branch inside the same graph (``LiveOursSession``): each stream's character feature is seeded with
 its matched bank row on the first pose and sampled from the previous one afterwards, the noise drawn on the device; the files are then
 named ``Ours_stream<s>.bvh`` as the reference names its result ``Ours.bvh``.
+
+``--ours-per-character`` (implies ``--ours``): ONE CVAE PER CHARACTER from a resident ``CVAEBank`` (synthetic CVAEs 99, 100 with their own
+statistics): stream s is sampled with the CVAE of its character, chosen inside the captured graph (``LiveOursSession(cvaes=, cvae_of=)``).
+With ``--load-at F`` the new character arrives without a CVAE - it falls back to plain context matching - until, ten frames later, its
+CVAE is stored and ``set_cvae`` names it: no new capture.
 
 ``--switch FRAME``: stream 0 names character 1 from that frame on - the new id is device data, the graph is not captured again.
 ``--inertial HALFLIFE`` (seconds): the switch does not pop; the jump of the pose heads decays as an offset (``LiveSession(inertial=...)``,
@@ -55,7 +60,9 @@ ap.add_argument("--raw", type=int, default=None, metavar="L", help="push raw moc
 ap.add_argument("--actions", default=None, metavar="A,B[:F]", help="allow only these action labels (0..7 here), from frame F on")
 ap.add_argument("--load-at", type=int, default=None, metavar="FRAME", help="start on a resident bank; at that frame a third character is added in "
                 "place and stream 1 switches to it")
+ap.add_argument("--ours-per-character", action="store_true", help="--ours with one CVAE per character from a CVAEBank (synthetic CVAEs)")
 a = ap.parse_args()
+a.ours = a.ours or a.ours_per_character
 if a.ours and a.actions:
     raise SystemExit("--actions does not apply to --ours: the branch's seed match searches the whole character")
 allow_from, allow_mask = 0, None
@@ -106,7 +113,21 @@ for s in range(S):
     _, rvel, rang, hipvel, contact = synthetic.postprocess_inputs(5 + s, F)
     per.append([torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in
                 (rvel, rang, np.linalg.norm(hipvel, axis=-1).mean(-1).astype(np.float32), contact)])
-if a.ours:                                                            # test_fullframework.py:52-58, 80-87: the CVAE and its statistics
+def cvae_stats(seed):
+    r = np.random.Generator(np.random.PCG64(seed))
+    return [(0.1 * r.standard_normal((90, 256))).astype(np.float32), r.uniform(0.5, 1.5, (90, 256)).astype(np.float32),
+            (0.1 * r.standard_normal((90, 256))).astype(np.float32), r.uniform(0.5, 1.5, (90, 256)).astype(np.float32)]
+
+
+if a.ours_per_character:                                              # train_CVAE.py: one CVAE and one cvae_norm.npz per target character
+    from mocha_sigasia2023_amd import CVAEBank
+    from mocha_sigasia2023_amd.weights import synthetic_cvae_state_dict
+    cvaes = CVAEBank(model, 3)
+    for c in range(2):
+        cvaes.store(c, synthetic_cvae_state_dict(99 + c, 1.0), *cvae_stats(3 + c))
+    sess = LiveOursSession(bank, cnt_mean, cnt_std, None, None, None, None, None, streams=S, post=PostProcessor(model), noise="device",
+                           seed=a.seed, cvaes=cvaes, cvae_of=[0, 1, -1][:bank.S])
+elif a.ours:                                                          # test_fullframework.py:52-58, 80-87: the CVAE and its statistics
     from mocha_sigasia2023_amd.weights import synthetic_cvae_state_dict
     r3 = np.random.Generator(np.random.PCG64(3))
     stats = [(0.1 * r3.standard_normal((90, 256))).astype(np.float32), r3.uniform(0.5, 1.5, (90, 256)).astype(np.float32),
@@ -135,7 +156,7 @@ def push(f, characters=None):
 push(0, characters=[0, 1])                                            # the first push captures the step
 sess.reset()
 torch.cuda.synchronize(); t0 = time.perf_counter()
-pos, eul, applied = [], [], []
+pos, eul, applied, seeded = [], [], [], []
 if a.actions:
     sess.allow.zero_()
 gen0 = model._ctx.generation()
@@ -144,7 +165,12 @@ for f in range(F):
     if f == a.load_at:                                                # one more character while the session runs: no new bank, no new capture
         new = bank.add(*banks[2], labels=labels[2] if labels else None)
         chars = [1 if a.switch is not None and f >= a.switch else 0, new]
+    if a.ours_per_character and a.load_at is not None and f == a.load_at + 10:      # the new character's CVAE arrives: stream order, no new capture
+        cvaes.store(2, synthetic_cvae_state_dict(101, 1.0), *cvae_stats(5))
+        sess.set_cvae(2, 2)
     o = push(f, characters=chars)
+    if a.ours:
+        seeded.append(o["seeded"].clone())
     if f >= first:                                                    # both streams started together: both are valid from here on
         pos.append(o["bvh_pos"].clone()); eul.append(o["bvh_euler"].clone())
         if a.actions:
@@ -157,6 +183,9 @@ for s in range(S):
     p = os.path.join(a.out, f"{'Ours' if a.ours else 'soft' if soft else 'raw' if a.raw is not None else 'live'}_stream{s}.bvh")
     write_bvh(p, names, LAYOUTS["mocha"]["parents"], pos[s], eul[s])
     print(f"  {p}: {os.path.getsize(p)} bytes, {pos.shape[1]} frames")
+if a.ours_per_character:
+    sd = torch.stack(seeded, 1).cpu()
+    print(f"  one CVAE per character: seed frames per stream {sd.sum(1).tolist()} of {F - first} posed frames; generation {gen0} -> {model._ctx.generation()}")
 if a.switch is not None and first + 1 <= a.switch < F:
     step = (pos[0, 1:, 1:] - pos[0, :-1, 1:]).abs().amax(dim=(1, 2))     # per frame, the non-root bones of stream 0
     print(f"  stream 0 switches character at frame {a.switch}: largest bone-position step there {float(step[a.switch - first - 1]):.4f}, "

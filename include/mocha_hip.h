@@ -607,6 +607,7 @@ int mocha_live_step_inert(mocha_ctx* ctx, const mocha_post_cfg* cfg, void* live,
  *                            ONE CVAE PER CONTEXT: its weights (mocha_cvae_load_weight / mocha_cvae_finalize ON THIS context, else
  *                            MOCHA_ERR_STATE) and the four statistics serve every stream - the reference trains one CVAE per target
  *                            character.  Streams may still name different segments; a seed row comes from the stream's own segment.
+ *                            (One CVAE per CHARACTER, from a resident weight bank: mocha_live_step_ours_grouped below.)
  *                            Captured into its own HIP graph, keyed as mocha_live_step's plus `ours`, the pointers in ocfg, noise, seed
  *                            and seeded.  Other refusals as mocha_live_step; a NULL `ours`, ocfg or statistic, noise outside 0..2, or
  *                            noise 1 without eps is MOCHA_ERR_ARG, as are more streams than the workspace limit (mocha_reserve): the
@@ -624,6 +625,60 @@ int mocha_live_step_ours(mocha_ctx* ctx, const mocha_post_cfg* cfg, void* live, 
                          const unsigned char* contact, const int32_t* seg, const float* cnt_mean, const float* cnt_std, void* ours,
                          const mocha_ours_cfg* ocfg, double* pos, double* rot, double* ik_rot, double* bvh_pos, double* bvh_euler,
                          int32_t* idx, int32_t* valid, int32_t* seeded, void* stream);
+
+/* One CVAE per character: a resident WEIGHT BANK of max_cvaes slots, each a whole CVAE (every tensor mocha_cvae_load_weight expects) with its
+ * four statistics, one positional table for the bank, and a device word per slot that says whether the slot holds weights.  Which slot a
+ * row of a sampler batch - or a stream of the live step - uses is DEVICE data, read by every launch: a captured step follows it.
+ *   mocha_cvae_bank_create : allocates the bank, zero-filled: (max_cvaes, ...) for every sampler tensor (about 10.5 MB per slot), the
+ *                            per-slot statistics (max_cvaes, 4, 90, 256) = src_cnt mean / std, cha_encoded mean / std, stored[max_cvaes] and
+ *                            the shared sin / cos positional table.  Moves the generation once.  1 <= max_cvaes <= 4096, else MOCHA_ERR_ARG.
+ *   mocha_cvae_bank_store  : writes the CVAE currently STAGED ON THE HOST by mocha_cvae_load_weight (mocha_cvae_finalize is not needed) into
+ *                            `slot`, with its statistics (host, (90,256) each).  (Staging un-finalises the context's OWN CVAE, as every
+ *                            mocha_cvae_load_weight does: mocha_cvae_finalize brings the staged one up as the context's.)  MOCHA_ERR_STATE without a bank or while a weight is missing
+ *                            (the message names it).  One positional table per bank: a staged pos_encoder.pe becomes the bank's table when no
+ *                            slot is stored; while one is, a staged table that differs from the bank's is MOCHA_ERR_ARG.  The copies
+ *                            are enqueued on `stream` from a context-owned pinned buffer; the slot's stored word is written LAST, by a one-lane
+ *                            kernel with an ordinary store.  NO generation move and no device-wide synchronisation: a captured grouped
+ *                            step replays before and after, and a replay enqueued on the same stream after the store samples with the new
+ *                            weights.  The call may wait for the PREVIOUS store's copies (they read the same pinned buffer), nothing else.
+ *   mocha_cvae_bank_clear  : enqueues stored[slot] = 0; the weights stay.  Rows and streams on the slot then count as having no CVAE.
+ *   mocha_cvae_bank_info   : host only: *capacity = max_cvaes; stored (capacity bytes, or NULL) = 1 / 0 per slot AS THE HOST ENQUEUED THEM.
+ *   mocha_cvae_sample_grouped : mocha_cvae_sample with row b on slot which[b] (device, (B) int32).  A row whose slot is outside
+ *                            [0, max_cvaes) or not stored reads no weight and gets zeros in out, mu and logvar; the other rows' bits do
+ *                            not depend on it, nor on B or on their place in the batch.  MOCHA_ERR_STATE without a weight bank.
+ *   mocha_linear_grouped   : the grouped GEMM alone on caller memory (all device), for tests and tooling, as mocha_linear is for the other
+ *                            engines: y[g] = act(x[g] w_bank[which[g]]^T + bias_bank[which[g]]) (+ residual[g]) for G groups of m
+ *                            consecutive rows; x (G*m, K), w_bank (Cw, N, K), bias_bank (Cw, N) or NULL, which (G) and stored (Cw) int32,
+ *                            y (G*m, ldc), residual (G*m, ldr) or NULL; act 0 none / 3 ReLU.  m >= 1, N % 16 == 0, K % 16 == 0, ldc >= N
+ *                            (and ldr >= N) multiples of 4, else MOCHA_ERR_ARG.  Exact fp32 (v_mfma_f32_16x16x4_f32); the order of an
+ *                            element's sum depends on K alone.  A group with which[g] outside [0, Cw) or stored[which[g]] == 0: zeros.
+ *   mocha_live_step_ours_grouped : mocha_live_step_ours's arguments plus cvae_of - device, one int32 per segment (or slot, on a resident
+ *                            bank) of the CURRENT character bank: the weight-bank slot of that character's CVAE.  Read by every replay; a
+ *                            producer may rewrite it in place.  The statistics pointers of ocfg are ignored and may be NULL: a stream's
+ *                            four statistics are those of slot cvae_of[eff[s]].  A stream whose character has NO CVAE - cvae_of negative
+ *                            or >= max_cvaes, or the slot not stored - is a SEED stream on every valid frame: its character feature is
+ *                            the matched bank row, seeded[s] = 1, the frame is mocha_live_step's frame, its cond rows are zeros.  A
+ *                            change of cvae_of[e] between frames does not reseed: `prev` is kept in de-normalised feature units and
+ *                            simply meets the new statistics.  Streams without a CVAE and warming streams cost no weight traffic (the
+ *                            sampler's stages still run for every stream of the batch).  No constrained seed match.  Its own captured
+ *                            graph, keyed as mocha_live_step_ours's plus cvae_of; works on a multi-character bank and on a resident bank
+ *                            alike.  Refusals as mocha_live_step_ours; in addition no weight bank is MOCHA_ERR_STATE and a NULL cvae_of
+ *                            MOCHA_ERR_ARG.  Nothing is launched on a refusal. */
+int mocha_cvae_bank_create(mocha_ctx* ctx, int max_cvaes);
+int mocha_cvae_bank_store(mocha_ctx* ctx, int slot, const float* src_cnt_mean, const float* src_cnt_std, const float* cha_encoded_mean,
+                          const float* cha_encoded_std /* host, (90,256) each */, void* stream);
+int mocha_cvae_bank_clear(mocha_ctx* ctx, int slot, void* stream);
+int mocha_cvae_bank_info(const mocha_ctx* ctx, int* capacity, unsigned char* stored);
+int mocha_cvae_sample_grouped(mocha_ctx* ctx, const float* cond, int B, const int32_t* which /* device (B) */, float* out, float* mu,
+                              float* logvar, const float* eps, void* stream);
+int mocha_linear_grouped(mocha_ctx* ctx, const float* x, const float* w_bank, const float* bias_bank, const int32_t* which,
+                         const int32_t* stored, float* y, int ldc, int G, int m, int N, int K, int Cw, int act, const float* residual, int ldr,
+                         void* stream);
+int mocha_live_step_ours_grouped(mocha_ctx* ctx, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos,
+                                 const float* Yvel, const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed,
+                                 const unsigned char* contact, const int32_t* seg, const float* cnt_mean, const float* cnt_std, void* ours,
+                                 const mocha_ours_cfg* ocfg, const int32_t* cvae_of, double* pos, double* rot, double* ik_rot, double* bvh_pos,
+                                 double* bvh_euler, int32_t* idx, int32_t* valid, int32_t* seeded, void* stream);
 
 /* The mocap front end of a live session: RAW frames in.  What mocha_live_step takes per frame - Yrot / Ypos / Yvel / Yang with a synthetic
  * root bone, src_rvel / src_rang / src_speed, the foot contacts - is what the reference's process_data (preprocess/generate_database.py:

@@ -98,6 +98,11 @@ SIGNATURES = {
     "mocha_cvae_finalize": (_i, [_vp]),
     "mocha_cvae_sample": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "mocha_cvae_condition": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "mocha_cvae_bank_create": (_i, [_vp, _i]),
+    "mocha_cvae_bank_store": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mocha_cvae_bank_clear": (_i, [_vp, _i, _vp]),
+    "mocha_cvae_bank_info": (_i, [_vp, C.POINTER(_i), _vp]),
+    "mocha_cvae_sample_grouped": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocha_scale_shift": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "mocha_featurize": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "mocha_post_cfg_default": (None, [_vp]),
@@ -111,9 +116,11 @@ SIGNATURES = {
     "mocha_live_ours_state_bytes": (_i64, [_vp, _i]),
     "mocha_live_ours_reset": (_i, [_vp, _vp, _vp, _i, C.POINTER(C.c_int32), _i, _vp]),
     "mocha_live_step_ours": (_i, [_vp, _vp, _vp, _i] + [_vp] * 11 + [_vp, _vp] + [_vp] * 8 + [_vp]),
+    "mocha_live_step_ours_grouped": (_i, [_vp, _vp, _vp, _i] + [_vp] * 11 + [_vp, _vp, _vp] + [_vp] * 8 + [_vp]),
     "mocha_column_stats": (_i, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "mocha_set_option": (_i, [_vp, C.c_char_p, _i]),
     "mocha_linear": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
+    "mocha_linear_grouped": (_i, [_vp] * 7 + [_i] * 7 + [_vp, _i, _vp]),
     "mocha_graph_constants": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mocha_generation": (_i64, [_vp]),
     "mocha_step_graph": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),

@@ -3,7 +3,7 @@ hot path (motion encoder -> context matching -> body-part decoder) behind the re
 own call surface.  The arithmetic lives in ``libmocha_hip.so`` (``csrc/``, C ABI in
 ``include/mocha_hip.h``); this package is the thin host-side mirror of the reference interface.
 """
-from .generator import CVAE, ContextBank, Generator, OursSession, StreamingCharacterizer, mean_variance_norm  # noqa: F401
+from .generator import CVAE, CVAEBank, ContextBank, Generator, OursSession, StreamingCharacterizer, mean_variance_norm  # noqa: F401
 from .multi_character import MultiCharacterBank, MultiStreamCharacterizer, ResidentCharacterBank, action_mask  # noqa: F401
 from .bank import BatchPipeline, ShardedContextBank, build_bank, build_database_from_bvh, load_bank, save_bank  # noqa: F401
 from .postprocess import Inertializer, PostProcessor, pose_heads, retarget_clip, retarget_clip_ours, retarget_frame_ours, write_bvh  # noqa: F401
@@ -15,7 +15,7 @@ from .skeleton import skeleton_constants  # noqa: F401
 from . import synthetic  # noqa: F401
 from .weights import DEFAULT_CFG, param_shapes, synthetic_state_dict  # noqa: F401
 
-__all__ = ["Generator", "CVAE", "OursSession", "ContextBank", "StreamingCharacterizer", "mean_variance_norm", "skeleton_constants",
+__all__ = ["Generator", "CVAE", "CVAEBank", "OursSession", "ContextBank", "StreamingCharacterizer", "mean_variance_norm", "skeleton_constants",
            "synthetic_state_dict", "param_shapes", "DEFAULT_CFG", "build_bank", "save_bank", "load_bank", "ShardedContextBank", "BatchPipeline",
            "PostProcessor", "pose_heads", "MultiCharacterBank", "MultiStreamCharacterizer", "ResidentCharacterBank", "action_mask", "retarget_clip", "retarget_clip_ours", "retarget_frame_ours", "write_bvh", "write_bvh_clips", "format_bvh_motion", "BvhValueRefused",
            "LiveSession", "LiveOursSession", "Inertializer", "Ingestor", "IngestConfig", "ingest_clips", "clip_windows",

@@ -192,6 +192,34 @@ hipError_t launch_cvae_latent(const float* x /*B,ntok,256*/, int ntok, const flo
 hipError_t launch_cvae_condition(const float* src_cnt, const float* sm, const float* ss, const float* prev, const float* cm,
                                  const float* cs, float* cond, int B, int n, hipStream_t s);
 hipError_t launch_scale_shift(const float* x, const float* mean, const float* sd, float* out, int B, int n, hipStream_t s);
+// ---- the sampler with one weight set per group of rows (cvae_grouped.hip): G groups of m consecutive rows, group g on slot which[g] of a
+// bank of Cw slots; stored[slot] != 0 says the slot holds weights.  which (G) and stored (Cw) are DEVICE int32 arrays read by every launch.
+// A group whose slot is outside [0, Cw) or not stored reads no weight, bias or residual and its output rows are zeros.
+// C[g] = act(A[g] W[slot]^T + bias[slot]) (+ R[g]), exact fp32 (v_mfma_f32_16x16x4_f32); W / bias of slot i start w_stride / b_stride
+// floats after those of slot i - 1.  Any m >= 1, N % 16 == 0, K % 16 == 0; act 0 or 3 (ReLU); lda / ldc / ldr / the strides multiples of 4
+// floats and every pointer 16-byte aligned (checked but for the alignment of the pointers).  The order of an output element's sum depends
+// on K alone: a group's rows are the same bits at any position of any batch.
+struct GroupedGemmParams {
+    const float* A = nullptr;         // (G * m, lda)
+    const float* W = nullptr;         // slot 0's [N][K], k contiguous
+    const float* bias = nullptr;      // slot 0's [N], or null
+    const int32_t* which = nullptr;   // device (G)
+    const int32_t* stored = nullptr;  // device (Cw)
+    float* C = nullptr;               // (G * m, ldc)
+    const float* residual = nullptr;  // (G * m, ldr) or null, added after the activation
+    int G = 0, m = 0, N = 0, K = 0, Cw = 0;
+    int lda = 0, ldc = 0, ldr = 0;
+    long long w_stride = 0, b_stride = 0;
+    int act = 0;
+};
+hipError_t launch_gemm_grouped(const GroupedGemmParams& p, hipStream_t s);
+// launch_layernorm256 / launch_cvae_prior_tokens with the affine pair / the two learned tokens of the group's slot (`stride` floats between slots)
+hipError_t launch_layernorm256_grouped(const float* x, const float* w, const float* b, long long stride, const int32_t* which,
+                                       const int32_t* stored, int Cw, float* y, int G, int m, hipStream_t s);
+hipError_t launch_cvae_prior_tokens_grouped(const float* c, const float* mu_tok, const float* lv_tok, long long stride, const int32_t* which,
+                                            const int32_t* stored, int Cw, const float* pe, float* out, int B, int nc, hipStream_t s);
+// stored[slot] = value by one lane with an ordinary store (mocha_cvae_bank_store's last launch, mocha_cvae_bank_clear)
+hipError_t launch_cvae_bank_publish(int32_t* stored, int slot, int Cw, int value, hipStream_t s);
 // demo featurisation (featurize.hip): local bone features of B windows -> X (B,T,J,15) un-normalised, root bone included
 hipError_t featurize_init();
 hipError_t launch_featurize(const float* Yrot, const float* Ypos, const float* Yvel, const float* Yang, const int* parents /*J, device*/,
@@ -216,12 +244,23 @@ hipError_t launch_live_push(const LiveRing& r, const float* Yrot, const float* Y
 //   cond[s] = 0 (mode 0), [(cnt - sm)/ss, 0] (mode 1), [(cnt - sm)/ss, (prev - cm)/cs] (mode 2); eps_out[s] = eps_in[s] (noise 1) or
 //   Philox4x32-10 (key = the seed's low / high word, counter (block 0..63, chain, s, 0)) + Box-Muller (noise 2); noise 0: not written.
 // update: mode 2: prev[s] = vae[s] * cs + cm; mode 1: prev[s] = bank_enc[gidx[s]]; modes 1, 2: chain + 1, last = eff[s]; seeded[s] = mode == 1.
+// grp non-null: the GROUPED instances - one CVAE per character from a weight bank of Cw slots.  Stream s takes slot cvae_of[eff[s]]
+// (cvae_of: one device int32 per segment / slot of the character bank) and that slot's statistics, stats (Cw, 4, 90, 256) = sm | ss | cm | cs;
+// sm / ss / cm / cs are then ignored.  No CVAE (cvae_of negative or >= Cw, or stored[slot] == 0): mode 1 on every valid frame, cond[s] = 0.
+// condition writes slot[s] (S) = the stream's slot, -1 for a warming stream or one without a CVAE; update reads it.
+struct OursGroup {
+    const int32_t* cvae_of = nullptr;
+    const int32_t* stored = nullptr;
+    const float* stats = nullptr;
+    int Cw = 0;
+    int32_t* slot = nullptr;
+};
 hipError_t launch_live_ours_condition(int32_t* counters, const int32_t* eff, int nseg, const float* cnt, const float* prev, const float* sm,
                                       const float* ss, const float* cm, const float* cs, float* cond, int noise, const float* eps_in,
-                                      unsigned long long seed, float* eps_out, int S, hipStream_t s);
+                                      unsigned long long seed, float* eps_out, int S, hipStream_t s, const OursGroup* grp = nullptr);
 hipError_t launch_live_ours_update(int32_t* counters, const int32_t* eff, const float* vae, const float* cm, const float* cs,
                                    const float* bank_enc, const int32_t* gidx, long long bank_rows, float* prev, int32_t* seeded, int S,
-                                   hipStream_t s);
+                                   hipStream_t s, const OursGroup* grp = nullptr);
 // post-processing of decoded windows (postprocess.hip)
 #define MOCHA_MAX_CONTACT 4
 #define MOCHA_MAX_CHAIN 8

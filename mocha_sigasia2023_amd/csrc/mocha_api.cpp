@@ -249,6 +249,21 @@ struct mocha_ctx {
     bool cvae_ready = false;
     int cvae_depth = 2, cvae_heads = 4, cvae_nc = 180, cvae_nq = 90;
     std::map<std::string, DeviceBuffer<float>> cws; int cvae_B = 0;
+    // CVAE weight bank (mocha_cvae_bank_create): Cw slots of `slot_floats` floats, every tensor of cvae_expect at off[name] inside its
+    // slot (so a grouped launch reads slot i's tensor `slot_floats` floats after slot i - 1's); the per-slot statistics (Cw,4,90,256),
+    // the stored words, the shared positional table, 16 words of -1 (the warm pass's `which`) and the live step's per-stream slots.
+    // None of these moves the generation on its own: creating the bank does, storing into it does not.
+    struct CvaeBank {
+        int Cw = 0;
+        size_t slot_floats = 0;
+        std::map<std::string, size_t> off;
+        DeviceBuffer<float> w, stats, pe;
+        DeviceBuffer<int32_t> stored, none, live_slot;
+        std::vector<unsigned char> host_stored;            // as the host enqueued them
+        std::vector<float> pe_host;
+        float* pin = nullptr;                              // pinned staging of one slot's weights and statistics
+        hipEvent_t ev = nullptr; bool ev_pending = false;  // the previous store's copies out of `pin`
+    } cvb;
     // fp32 GEMMs on the bf16 matrix pipe (gemm_x3.hip): packed three-plane images of the weights, made on first use
     bool gemm_x3 = true;
     bool attn_x3 = true;               // the Generator's attention as plane products on the bf16 pipe (attention_x3.hip)
@@ -325,6 +340,8 @@ struct mocha_ctx {
         const void* ingest[3] = {}; mocha_ingest_cfg icfg{};
         // the action-constrained steps only: the masks (read by every replay) and the applied report
         const void* allow[2] = {};
+        // mocha_live_step_ours_grouped only: the characters' weight-bank slots (read by every replay)
+        const void* cvae_of = nullptr;
         bool operator==(const StepKey& o) const {
             if (!(x == o.x && mean == o.mean && sd == o.sd && y == o.y && idx == o.idx && seg == o.seg && windows == o.windows && raw == o.raw))
                 return false;
@@ -333,6 +350,7 @@ struct mocha_ctx {
             if (noise != o.noise || seed != o.seed) return false;
             if (soft_k != o.soft_k || soft_t != o.soft_t || soft[0] != o.soft[0] || soft[1] != o.soft[1]) return false;
             if (allow[0] != o.allow[0] || allow[1] != o.allow[1]) return false;
+            if (cvae_of != o.cvae_of) return false;
             if (inert != o.inert || inert_halflife != o.inert_halflife || inert_dt != o.inert_dt) return false;
             for (int i = 0; i < 3; ++i) if (ingest[i] != o.ingest[i] || icfg.euler_order[i] != o.icfg.euler_order[i]) return false;
             if (icfg.lookahead != o.icfg.lookahead || icfg.rot_format != o.icfg.rot_format || icfg.unit_scale != o.icfg.unit_scale ||
@@ -354,7 +372,8 @@ struct mocha_ctx {
       soft_step, live_soft_step,                      // mocha_step_graph_soft_segmented, mocha_live_step_soft (workspace set 0)
       live_inert_step,                                // mocha_live_step_inert, hard or soft (workspace set 0)
       live_raw_step[3],                               // mocha_live_step_raw: hard, soft, inertialized (workspace set 0)
-      seg_allow_step, live_allow_step, live_raw_allow_step;      // mocha_step_graph_segmented_allow, mocha_live_step_allow, mocha_live_step_raw_allow
+      seg_allow_step, live_allow_step, live_raw_allow_step,      // mocha_step_graph_segmented_allow, mocha_live_step_allow, mocha_live_step_raw_allow
+      ours_grouped_step;                              // mocha_live_step_ours_grouped (workspace set 0)
     hipStream_t cap_stream = nullptr;                 // capture happens on this internal stream (the caller's may be the null stream)
     ncclComm_t comm = nullptr; int comm_rank = 0, comm_size = 1;      // mocha_comm_init
     DeviceBuffer<long long> bcast_hdr;                                  // device: {entries, bf16?} header of mocha_bank_broadcast
@@ -1482,11 +1501,13 @@ void mocha_destroy(mocha_ctx* c) {
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     for (auto* g : {&c->step[0], &c->step[1], &c->step[2], &c->seg_step, &c->live_step, &c->ours_step, &c->soft_step, &c->live_soft_step,
                     &c->live_inert_step, &c->live_raw_step[0], &c->live_raw_step[1], &c->live_raw_step[2], &c->seg_allow_step,
-                    &c->live_allow_step, &c->live_raw_allow_step}) {
+                    &c->live_allow_step, &c->live_raw_allow_step, &c->ours_grouped_step}) {
         if (g->exec) (void)hipGraphExecDestroy(g->exec);
         if (g->graph) (void)hipGraphDestroy(g->graph);
     }
     if (c->cap_stream) (void)hipStreamDestroy(c->cap_stream);
+    if (c->cvb.ev) { (void)hipEventSynchronize(c->cvb.ev); (void)hipEventDestroy(c->cvb.ev); }
+    if (c->cvb.pin) (void)hipHostFree(c->cvb.pin);
     (void)mocha_comm_destroy(c);
     delete c;                                             // every device buffer is a DeviceBuffer member: freed here
 }
@@ -3030,73 +3051,109 @@ static int cvae_ws(mocha_ctx* c, int B) {
     return 0;
 }
 
+// The sampler's weights come from the context's own CVAE (c->cw) or, for a GROUPED pass - `which` non-null: device, one weight-bank slot
+// per clip of the batch - from the weight bank: cvae_w then returns slot 0's tensor and the grouped launches step by the slot stride.
+static const float* cvae_w(mocha_ctx* c, const std::string& n, const int32_t* which) {
+    return which ? c->cvb.w.p + c->cvb.off.at(n) : c->cw.at(n).p;
+}
+// one GEMM of the sampler over B clips of m rows each: launch_gemm, or the grouped kernel with the clip's slot
+static int cvae_gemm(mocha_ctx* c, hipStream_t s, const char* site, const GemmParams& g, int m, const int32_t* which) {
+    if (!which) { GEMM(c, s, site, g); return 0; }
+    GroupedGemmParams q;
+    q.A = g.A; q.W = g.W; q.bias = g.bias; q.which = which; q.stored = c->cvb.stored.p; q.C = g.C; q.residual = g.residual;
+    q.G = g.M / m; q.m = m; q.N = g.N; q.K = g.K; q.Cw = c->cvb.Cw; q.lda = g.lda; q.ldc = g.ldc; q.ldr = g.ldr;
+    q.w_stride = q.b_stride = (long long)c->cvb.slot_floats; q.act = g.act;
+    // bytes: the activations and the output once, a group's weights once per 16 rows
+    LAUNCH(c, s, "mocha_gemm_grouped", site, 2.0 * g.M * (double)g.N * g.K,
+           4.0 * ((double)g.M * g.K + (double)q.G * ((m + 15) / 16) * (double)g.N * g.K + (double)g.M * g.N * (g.residual ? 2 : 1)),
+           launch_gemm_grouped(q, s));
+    return 0;
+}
+static int cvae_norm(mocha_ctx* c, hipStream_t s, const float* x, const std::string& norm, float* y, int B, int n, const int32_t* which) {
+    const float* w = cvae_w(c, norm + ".weight", which); const float* b = cvae_w(c, norm + ".bias", which);
+    if (which)
+        LAUNCH(c, s, "mocha_layernorm256_grouped", "cvae.norm", 0.0, B * n * 256.0 * 8,
+               launch_layernorm256_grouped(x, w, b, (long long)c->cvb.slot_floats, which, c->cvb.stored.p, c->cvb.Cw, y, B, n, s));
+    else
+        LAUNCH(c, s, "mocha_layernorm256", "cvae.norm", 0.0, B * n * 256.0 * 8, launch_layernorm256(x, w, b, y, B * n, s));
+    return 0;
+}
+
 // post-norm transformer sub-blocks shared by PriorNet and Decoder (nn.TransformerEncoderLayer / DecoderLayer defaults)
 static int cvae_attn_block(mocha_ctx* c, hipStream_t s, const std::string& p, const std::string& norm, float* x /*in/out*/, int nq,
-                           const float* kvsrc /*nullptr: self*/, int nk, int B) {
+                           const float* kvsrc /*nullptr: self*/, int nk, int B, const int32_t* which = nullptr) {
+    int rc;
     float* qkv = c->cws.at("qkv").p; float* t1 = c->cws.at("t1").p; float* t2 = c->cws.at("t2").p; float* kvb = c->cws.at("kv").p;
-    const float* Win = c->cw.at(p + ".in_proj_weight").p; const float* bin = c->cw.at(p + ".in_proj_bias").p;
+    const float* Win = cvae_w(c, p + ".in_proj_weight", which); const float* bin = cvae_w(c, p + ".in_proj_bias", which);
     const int H = c->cvae_heads, DH = 256 / H;
     AttnParams a{};
     if (!kvsrc) {
         GemmParams g = plain(x, 256, Win, qkv, 768, B * nq, 768, 256); g.bias = bin;
-        GEMM(c, s, "cvae.in_proj", g);
+        if ((rc = cvae_gemm(c, s, "cvae.in_proj", g, nq, which))) return rc;
         a = AttnParams{qkv, qkv + 256, qkv + 512, t1, 768, 768, 768, 256, B, H, DH, nq, nq, (float)std::pow((double)DH, -0.5)};
     } else {
         GemmParams gq = plain(x, 256, Win, qkv, 256, B * nq, 256, 256); gq.bias = bin;
-        GEMM(c, s, "cvae.q_proj", gq);
+        if ((rc = cvae_gemm(c, s, "cvae.q_proj", gq, nq, which))) return rc;
         GemmParams gk = plain(kvsrc, 256, Win + 256 * 256, kvb, 512, B * nk, 512, 256); gk.bias = bin + 256;
-        GEMM(c, s, "cvae.kv_proj", gk);
+        if ((rc = cvae_gemm(c, s, "cvae.kv_proj", gk, nk, which))) return rc;
         a = AttnParams{qkv, kvb, kvb + 256, t1, 256, 512, 512, 256, B, H, DH, nq, nk, (float)std::pow((double)DH, -0.5)};
     }
     LAUNCH(c, s, "mocha_attention_f32<64>", "cvae.attn", 4.0 * B * H * (double)a.nq * a.nk * DH, 4.0 * B * (a.nq + 2.0 * a.nk) * 256,
            launch_attention(a, s));
-    GemmParams o = plain(t1, 256, c->cw.at(p + ".out_proj.weight").p, t2, 256, B * nq, 256, 256);
-    o.bias = c->cw.at(p + ".out_proj.bias").p; o.residual = x; o.ldr = 256;
-    GEMM(c, s, "cvae.out_proj", o);
-    LAUNCH(c, s, "mocha_layernorm256", "cvae.norm", 0.0, B * nq * 256.0 * 8,
-           launch_layernorm256(t2, c->cw.at(norm + ".weight").p, c->cw.at(norm + ".bias").p, x, B * nq, s));
-    return 0;
+    GemmParams o = plain(t1, 256, cvae_w(c, p + ".out_proj.weight", which), t2, 256, B * nq, 256, 256);
+    o.bias = cvae_w(c, p + ".out_proj.bias", which); o.residual = x; o.ldr = 256;
+    if ((rc = cvae_gemm(c, s, "cvae.out_proj", o, nq, which))) return rc;
+    return cvae_norm(c, s, t2, norm, x, B, nq, which);
 }
 
-static int cvae_ff_block(mocha_ctx* c, hipStream_t s, const std::string& p, const std::string& norm, float* x, float* out, int n, int B) {
+static int cvae_ff_block(mocha_ctx* c, hipStream_t s, const std::string& p, const std::string& norm, float* x, float* out, int n, int B,
+                         const int32_t* which = nullptr) {
+    int rc;
     float* hff = c->cws.at("hff").p; float* t2 = c->cws.at("t2").p;
-    GemmParams f1 = plain(x, 256, c->cw.at(p + ".linear1.weight").p, hff, 512, B * n, 512, 256);
-    f1.bias = c->cw.at(p + ".linear1.bias").p; f1.act = 3;
-    GEMM(c, s, "cvae.ff1", f1);
-    GemmParams f2 = plain(hff, 512, c->cw.at(p + ".linear2.weight").p, t2, 256, B * n, 256, 512);
-    f2.bias = c->cw.at(p + ".linear2.bias").p; f2.residual = x; f2.ldr = 256;
-    GEMM(c, s, "cvae.ff2", f2);
-    LAUNCH(c, s, "mocha_layernorm256", "cvae.norm", 0.0, B * n * 256.0 * 8,
-           launch_layernorm256(t2, c->cw.at(norm + ".weight").p, c->cw.at(norm + ".bias").p, out, B * n, s));
-    return 0;
+    GemmParams f1 = plain(x, 256, cvae_w(c, p + ".linear1.weight", which), hff, 512, B * n, 512, 256);
+    f1.bias = cvae_w(c, p + ".linear1.bias", which); f1.act = 3;
+    if ((rc = cvae_gemm(c, s, "cvae.ff1", f1, n, which))) return rc;
+    GemmParams f2 = plain(hff, 512, cvae_w(c, p + ".linear2.weight", which), t2, 256, B * n, 256, 512);
+    f2.bias = cvae_w(c, p + ".linear2.bias", which); f2.residual = x; f2.ldr = 256;
+    if ((rc = cvae_gemm(c, s, "cvae.ff2", f2, n, which))) return rc;
+    return cvae_norm(c, s, t2, norm, out, B, n, which);
 }
 
 // CVAE.sample for B conditions on stream s: the body of mocha_cvae_sample and of the live step's CVAE branch.  The caller checked the
-// arguments, the weights (cvae_ready) and the workspace (cvae_ws(c, B)).
-static int cvae_sample_impl(mocha_ctx* c, const float* cond, int B, float* out, float* mu, float* logvar, const float* eps, hipStream_t s) {
+// arguments, the weights (cvae_ready, or the weight bank for a grouped pass) and the workspace (cvae_ws(c, B)).
+// which non-null: the GROUPED pass - clip b on slot which[b] (device) of the weight bank; a clip with an invalid slot reads no weight and
+// its out / mu / logvar are zeros (the attention and the latent kernel read no weights and run on the zero rows the grouped launches leave).
+static int cvae_sample_impl(mocha_ctx* c, const float* cond, int B, float* out, float* mu, float* logvar, const float* eps, hipStream_t s,
+                            const int32_t* which = nullptr) {
     int rc;
     const int nc = c->cvae_nc, nq = c->cvae_nq, ntok = nc + 2;
     float* t0 = c->cws.at("t0").p; float* mem = c->cws.at("mem").p;
+    const float* pe = which ? c->cvb.pe.p : c->cw.at("pe").p;
     // PriorNet.encode (model_CVAE.py:69-79)
-    LAUNCH(c, s, "mocha_cvae_prior_tokens", "cvae.tokens", 0.0, B * ntok * 256.0 * 8,
-           launch_cvae_prior_tokens(cond, c->cw.at("prior_net.mu_token").p, c->cw.at("prior_net.logvar_token").p, c->cw.at("pe").p, t0, B, nc, s));
+    if (which)
+        LAUNCH(c, s, "mocha_cvae_prior_tokens_grouped", "cvae.tokens", 0.0, B * ntok * 256.0 * 8,
+               launch_cvae_prior_tokens_grouped(cond, cvae_w(c, "prior_net.mu_token", which), cvae_w(c, "prior_net.logvar_token", which),
+                                                (long long)c->cvb.slot_floats, which, c->cvb.stored.p, c->cvb.Cw, pe, t0, B, nc, s));
+    else
+        LAUNCH(c, s, "mocha_cvae_prior_tokens", "cvae.tokens", 0.0, B * ntok * 256.0 * 8,
+               launch_cvae_prior_tokens(cond, c->cw.at("prior_net.mu_token").p, c->cw.at("prior_net.logvar_token").p, pe, t0, B, nc, s));
     for (int l = 0; l < c->cvae_depth; ++l) {
         const std::string p = "prior_net.encoder.layers." + std::to_string(l);
-        if ((rc = cvae_attn_block(c, s, p + ".self_attn", p + ".norm1", t0, ntok, nullptr, ntok, B))) return rc;
-        if ((rc = cvae_ff_block(c, s, p, p + ".norm2", t0, t0, ntok, B))) return rc;
+        if ((rc = cvae_attn_block(c, s, p + ".self_attn", p + ".norm1", t0, ntok, nullptr, ntok, B, which))) return rc;
+        if ((rc = cvae_ff_block(c, s, p, p + ".norm2", t0, t0, ntok, B, which))) return rc;
     }
     // reparameterize + Decoder inputs (model_CVAE.py:81-87, 158-163); the decoder state reuses t1's sibling t0 after this
     float* xq = c->cws.at("t1").p;     // free until the first attention writes it: use hff as query buffer instead
     xq = c->cws.at("hff").p;           // (B, nq, 256) fits in (B, 182, 512)
     LAUNCH(c, s, "mocha_cvae_latent", "cvae.latent", 0.0, B * (nc + nq + 2) * 256.0 * 4,
-           launch_cvae_latent(t0, ntok, eps, cond, nc, c->cw.at("pe").p, nq, mem, xq, mu, logvar, B, s));
+           launch_cvae_latent(t0, ntok, eps, cond, nc, pe, nq, mem, xq, mu, logvar, B, s));
     HIPCHK(c, hipMemcpyAsync(t0, xq, (size_t)B * nq * 256 * sizeof(float), hipMemcpyDeviceToDevice, s));
     for (int l = 0; l < c->cvae_depth; ++l) {
         const std::string p = "decoder.decoder.layers." + std::to_string(l);
-        if ((rc = cvae_attn_block(c, s, p + ".self_attn", p + ".norm1", t0, nq, nullptr, nq, B))) return rc;
-        if ((rc = cvae_attn_block(c, s, p + ".multihead_attn", p + ".norm2", t0, nq, mem, nc + 1, B))) return rc;
+        if ((rc = cvae_attn_block(c, s, p + ".self_attn", p + ".norm1", t0, nq, nullptr, nq, B, which))) return rc;
+        if ((rc = cvae_attn_block(c, s, p + ".multihead_attn", p + ".norm2", t0, nq, mem, nc + 1, B, which))) return rc;
         const bool last = l == c->cvae_depth - 1;
-        if ((rc = cvae_ff_block(c, s, p, p + ".norm3", t0, last ? out : t0, nq, B))) return rc;
+        if ((rc = cvae_ff_block(c, s, p, p + ".norm3", t0, last ? out : t0, nq, B, which))) return rc;
     }
     return 0;
 }
@@ -3109,6 +3166,136 @@ int mocha_cvae_sample(mocha_ctx* c, const float* cond, int B, float* out, float*
     HIPCHK(c, hipSetDevice(c->device));
     int rc = cvae_ws(c, B); if (rc) return rc;
     return cvae_sample_impl(c, cond, B, out, mu, logvar, eps, (hipStream_t)stream);
+}
+
+// ---- CVAE weight bank: one CVAE per slot, the slot of a row / stream chosen by device data (cvae_grouped.hip)
+int mocha_cvae_bank_create(mocha_ctx* c, int max_cvaes) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (max_cvaes < 1 || max_cvaes > 4096) return fail(c, MOCHA_ERR_ARG, "cvae_bank_create: 1 <= max_cvaes <= 4096 (got %d)", max_cvaes);
+    cvae_expectations(c);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());                    // a previous bank may still be read
+    auto& b = c->cvb;
+    b.Cw = 0; b.off.clear(); b.slot_floats = 0; b.host_stored.clear();
+    c->generation++;                                      // a captured grouped step has the previous bank's pointers baked in
+    size_t off = 0;
+    for (auto& kv : c->cvae_expect) {
+        size_t cnt = 1;
+        for (int64_t d : kv.second) cnt *= (size_t)d;
+        b.off[kv.first] = off;
+        off += (cnt + 3) / 4 * 4;                         // every tensor 16-byte aligned inside its slot
+    }
+    const size_t T = 90 * 256, Cw = (size_t)max_cvaes;
+    b.w.release(); b.stats.release(); b.stored.release();
+    int rc;
+    if ((rc = reserve(c, b.w, Cw * off))) return rc;
+    if ((rc = reserve(c, b.stats, Cw * 4 * T))) return rc;
+    if ((rc = reserve(c, b.stored, Cw))) return rc;
+    if ((rc = reserve(c, b.pe, (size_t)192 * 256))) return rc;
+    if ((rc = reserve(c, b.none, 16))) return rc;
+    if ((rc = reserve(c, b.live_slot, 16))) return rc;
+    HIPCHK(c, hipMemset(b.w.p, 0, Cw * off * sizeof(float)));
+    HIPCHK(c, hipMemset(b.stats.p, 0, Cw * 4 * T * sizeof(float)));
+    HIPCHK(c, hipMemset(b.stored.p, 0, Cw * sizeof(int32_t)));
+    HIPCHK(c, hipMemset(b.none.p, 0xFF, 16 * sizeof(int32_t)));
+    HIPCHK(c, hipMemset(b.live_slot.p, 0xFF, 16 * sizeof(int32_t)));
+    // the shared table: sin/cos positional encoding rows 0..191 (model_CVAE.py:168-178), float32 arithmetic like torch - mocha_cvae_finalize's
+    b.pe_host.assign((size_t)192 * 256, 0.f);
+    for (int i = 0; i < 128; ++i) {
+        const float div = expf((float)(2 * i) * (float)(-std::log(10000.0) / 256.0));
+        for (int t = 0; t < 192; ++t) {
+            const float a = (float)t * div;
+            b.pe_host[t * 256 + 2 * i] = sinf(a);
+            b.pe_host[t * 256 + 2 * i + 1] = cosf(a);
+        }
+    }
+    HIPCHK(c, hipMemcpy(b.pe.p, b.pe_host.data(), b.pe_host.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (b.pin) { (void)hipHostFree(b.pin); b.pin = nullptr; }
+    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&b.pin), (off + 4 * T + (size_t)192 * 256) * sizeof(float), hipHostMallocDefault));
+    if (!b.ev) HIPCHK(c, hipEventCreateWithFlags(&b.ev, hipEventDisableTiming));
+    b.ev_pending = false;
+    b.slot_floats = off;
+    b.host_stored.assign(Cw, 0);
+    b.Cw = max_cvaes;
+    return 0;
+}
+
+int mocha_cvae_bank_store(mocha_ctx* c, int slot, const float* src_cnt_mean, const float* src_cnt_std, const float* cha_encoded_mean,
+                          const float* cha_encoded_std, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    auto& b = c->cvb;
+    if (!b.Cw) return fail(c, MOCHA_ERR_STATE, "cvae_bank_store: no CVAE weight bank: call mocha_cvae_bank_create first");
+    if (slot < 0 || slot >= b.Cw) return fail(c, MOCHA_ERR_ARG, "cvae_bank_store: slot %d out of range 0 .. %d", slot, b.Cw - 1);
+    if (!src_cnt_mean || !src_cnt_std || !cha_encoded_mean || !cha_encoded_std) return fail(c, MOCHA_ERR_ARG, "cvae_bank_store: null statistic");
+    for (auto& kv : c->cvae_expect)
+        if (!c->cvae_host.count(kv.first)) return fail(c, MOCHA_ERR_STATE, "cvae_bank_store: missing CVAE weight '%s'", kv.first.c_str());
+    // One positional table per bank: the sin / cos table of mocha_cvae_bank_create until a store brings a pos_encoder.pe while NO slot is
+    // stored - that table becomes the bank's (a checkpoint's registered buffer, bit for bit); from then on a staged table must equal it.
+    auto pe = c->cvae_host.find("pe");
+    bool adopt_pe = false;
+    if (pe != c->cvae_host.end() && memcmp(pe->second.data.data(), b.pe_host.data(), b.pe_host.size() * sizeof(float)) != 0) {
+        if (std::find(b.host_stored.begin(), b.host_stored.end(), 1) != b.host_stored.end()) {
+            size_t i = 0;
+            while (pe->second.data[i] == b.pe_host[i]) ++i;
+            return fail(c, MOCHA_ERR_ARG, "cvae_bank_store: the staged pos_encoder.pe differs from the bank's table at %zu (%.9g vs %.9g): one table per bank",
+                        i, pe->second.data[i], b.pe_host[i]);
+        }
+        adopt_pe = true;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (b.ev_pending) HIPCHK(c, hipEventSynchronize(b.ev));      // the previous store's copies read the same pinned buffer
+    b.ev_pending = false;
+    const size_t T = 90 * 256;
+    for (auto& kv : b.off) {
+        const std::vector<float>& v = c->cvae_host.at(kv.first).data;
+        memcpy(b.pin + kv.second, v.data(), v.size() * sizeof(float));
+    }
+    const float* st[4] = {src_cnt_mean, src_cnt_std, cha_encoded_mean, cha_encoded_std};
+    for (int i = 0; i < 4; ++i) memcpy(b.pin + b.slot_floats + i * T, st[i], T * sizeof(float));
+    if (adopt_pe) {
+        b.pe_host = pe->second.data;
+        memcpy(b.pin + b.slot_floats + 4 * T, b.pe_host.data(), b.pe_host.size() * sizeof(float));
+        HIPCHK(c, hipMemcpyAsync(b.pe.p, b.pin + b.slot_floats + 4 * T, b.pe_host.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    }
+    // weights and statistics, then the slot's stored word, LAST: a launch that sees it set sees the whole slot
+    HIPCHK(c, hipMemcpyAsync(b.w.p + (size_t)slot * b.slot_floats, b.pin, b.slot_floats * sizeof(float), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(b.stats.p + (size_t)slot * 4 * T, b.pin + b.slot_floats, 4 * T * sizeof(float), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipEventRecord(b.ev, s));
+    b.ev_pending = true;
+    LAUNCH(c, s, "mocha_cvae_bank_publish", "cvae.publish", 0.0, 4.0, launch_cvae_bank_publish(b.stored.p, slot, b.Cw, 1, s));
+    b.host_stored[slot] = 1;
+    return 0;
+}
+
+int mocha_cvae_bank_clear(mocha_ctx* c, int slot, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    auto& b = c->cvb;
+    if (!b.Cw) return fail(c, MOCHA_ERR_STATE, "cvae_bank_clear: no CVAE weight bank: call mocha_cvae_bank_create first");
+    if (slot < 0 || slot >= b.Cw) return fail(c, MOCHA_ERR_ARG, "cvae_bank_clear: slot %d out of range 0 .. %d", slot, b.Cw - 1);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    LAUNCH(c, s, "mocha_cvae_bank_publish", "cvae.publish", 0.0, 4.0, launch_cvae_bank_publish(b.stored.p, slot, b.Cw, 0, s));
+    b.host_stored[slot] = 0;
+    return 0;
+}
+
+int mocha_cvae_bank_info(const mocha_ctx* c, int* capacity, unsigned char* stored) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (!c->cvb.Cw) return MOCHA_ERR_STATE;
+    if (capacity) *capacity = c->cvb.Cw;
+    if (stored) memcpy(stored, c->cvb.host_stored.data(), (size_t)c->cvb.Cw);
+    return 0;
+}
+
+int mocha_cvae_sample_grouped(mocha_ctx* c, const float* cond, int B, const int32_t* which, float* out, float* mu, float* logvar,
+                              const float* eps, void* stream) {
+    if (c && B == 0) return 0;
+    if (!c || !cond || !which || !out || B < 0) return fail(c, MOCHA_ERR_ARG, "bad grouped CVAE arguments");
+    if (!c->cvb.Cw) return fail(c, MOCHA_ERR_STATE, "cvae_sample_grouped: no CVAE weight bank: call mocha_cvae_bank_create first");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = cvae_ws(c, B); if (rc) return rc;
+    return cvae_sample_impl(c, cond, B, out, mu, logvar, eps, (hipStream_t)stream, which);
 }
 
 int mocha_cvae_condition(mocha_ctx* c, const float* src_cnt, const float* src_mean, const float* src_std, const float* prev_cha,
@@ -4099,18 +4286,21 @@ int mocha_live_ours_reset(mocha_ctx* c, void* live, void* ours, int streams, con
     return 0;
 }
 
-int mocha_live_step_ours(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos, const float* Yvel,
-                         const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed, const unsigned char* contact,
-                         const int32_t* seg, const float* cnt_mean, const float* cnt_std, void* ours, const mocha_ours_cfg* ocfg, double* pos,
-                         double* rot, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx, int32_t* valid, int32_t* seeded,
-                         void* stream) {
+// The body of mocha_live_step_ours and of mocha_live_step_ours_grouped (grouped: cvae_of is the device table of the characters' weight-bank
+// slots, the weights and statistics come from the weight bank, the step has its own captured graph).
+static int live_step_ours_impl(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos, const float* Yvel,
+                               const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed, const unsigned char* contact,
+                               const int32_t* seg, const float* cnt_mean, const float* cnt_std, void* ours, const mocha_ours_cfg* ocfg, double* pos,
+                               double* rot, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx, int32_t* valid, int32_t* seeded,
+                               void* stream, bool grouped, const int32_t* cvae_of) {
     if (!c) return MOCHA_ERR_ARG;
     if (streams < 1 || streams > 16) return fail(c, MOCHA_ERR_ARG, "live_step_ours: 1 <= streams <= 16");
     if (!live || !Yrot || !Ypos || !Yvel || !Yang || !src_rvel || !src_rang || !src_speed || !contact || !seg || !cnt_mean || !cnt_std || !pos ||
         !rot || !ik_rot || !idx || !valid || !seeded || (!bvh_pos) != (!bvh_euler))
         return fail(c, MOCHA_ERR_ARG, "live_step_ours: null argument");
     if (!ours || !ocfg) return fail(c, MOCHA_ERR_ARG, "live_step_ours: null state buffer or configuration");
-    if (!ocfg->src_cnt_mean || !ocfg->src_cnt_std || !ocfg->cha_encoded_mean || !ocfg->cha_encoded_std)
+    if (grouped && !cvae_of) return fail(c, MOCHA_ERR_ARG, "live_step_ours_grouped: null cvae_of");
+    if (!grouped && (!ocfg->src_cnt_mean || !ocfg->src_cnt_std || !ocfg->cha_encoded_mean || !ocfg->cha_encoded_std))
         return fail(c, MOCHA_ERR_ARG, "live_step_ours: null statistic");
     if (ocfg->noise < 0 || ocfg->noise > 2) return fail(c, MOCHA_ERR_ARG, "live_step_ours: noise must be 0 (none), 1 (given) or 2 (device)");
     if (ocfg->noise == 1 && !ocfg->eps) return fail(c, MOCHA_ERR_ARG, "live_step_ours: noise 1 needs eps");
@@ -4119,7 +4309,8 @@ int mocha_live_step_ours(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, in
     if (streams > c->max_chunk)
         return fail(c, MOCHA_ERR_ARG, "live_step_ours: %d streams exceed the workspace limit of %d windows (raise it with mocha_reserve)", streams, c->max_chunk);
     if (!c->finalized) return fail(c, MOCHA_ERR_STATE, "weights not finalised: call mocha_finalize_weights first");
-    if (!c->cvae_ready) return fail(c, MOCHA_ERR_STATE, "live_step_ours: no CVAE on this context: call mocha_cvae_load_weight and mocha_cvae_finalize first");
+    if (grouped && !c->cvb.Cw) return fail(c, MOCHA_ERR_STATE, "live_step_ours_grouped: no CVAE weight bank: call mocha_cvae_bank_create first");
+    if (!grouped && !c->cvae_ready) return fail(c, MOCHA_ERR_STATE, "live_step_ours: no CVAE on this context: call mocha_cvae_load_weight and mocha_cvae_finalize first");
     if (!c->pose_norm.p) return fail(c, MOCHA_ERR_STATE, "live_step_ours: no pose norm: call mocha_set_pose_norm first");
     if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set_segments first");
     if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
@@ -4156,9 +4347,13 @@ int mocha_live_step_ours(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, in
     float* eps_o = reinterpret_cast<float*>(ob + ol.eps);
     float* mu = reinterpret_cast<float*>(ob + ol.mu);
     float* logvar = reinterpret_cast<float*>(ob + ol.logvar);
-    const mocha_ours_cfg oc = *ocfg;
+    mocha_ours_cfg oc = *ocfg;
+    if (grouped) oc.src_cnt_mean = oc.src_cnt_std = oc.cha_encoded_mean = oc.cha_encoded_std = nullptr;      // ignored: the slot's statistics serve
     const int J = c->cfg.V + 1, V = c->cfg.V, S = streams;
     const int nseg = c->bank.segments();
+    // grouped: the condition kernel leaves every stream's slot in live_slot, the `which` of the sampler's grouped launches
+    const OursGroup grp{cvae_of, c->cvb.stored.p, c->cvb.stats.p, c->cvb.Cw, c->cvb.live_slot.p};
+    const OursGroup* gp = grouped ? &grp : nullptr;
 
     // sampler -> literal decoder on `cha` -> to_mot (de-normalised) into the staging: the tail of the step, and of the warm pass
     auto tail = [&](const float* cha, hipStream_t cs) -> int {
@@ -4184,10 +4379,10 @@ int mocha_live_step_ours(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, in
         if ((r = seg_match(c, WS(c, c->bank.is_bf16 ? "qc" : "qnm"), S, eff, idx, gx, nullptr, cs))) return r;
         LAUNCH(c, cs, "mocha_live_ours_condition", "ours.condition", 0.0, S * 180.0 * 256 * 8,
                launch_live_ours_condition(ocnt, eff, nseg, cnt_o, prev, oc.src_cnt_mean, oc.src_cnt_std, oc.cha_encoded_mean, oc.cha_encoded_std,
-                                          cond, oc.noise, oc.eps, oc.seed, eps_o, S, cs));
-        if ((r = cvae_sample_impl(c, cond, S, vae, mu, logvar, oc.noise ? eps_o : nullptr, cs))) return r;
+                                          cond, oc.noise, oc.eps, oc.seed, eps_o, S, cs, gp));
+        if ((r = cvae_sample_impl(c, cond, S, vae, mu, logvar, oc.noise ? eps_o : nullptr, cs, grouped ? grp.slot : nullptr))) return r;
         LAUNCH(c, cs, "mocha_live_ours_update", "ours.update", 0.0, S * 90.0 * 256 * 12,
-               launch_live_ours_update(ocnt, eff, vae, oc.cha_encoded_mean, oc.cha_encoded_std, c->bank.enc, gx, c->bank.N, prev, seeded, S, cs));
+               launch_live_ours_update(ocnt, eff, vae, oc.cha_encoded_mean, oc.cha_encoded_std, c->bank.enc, gx, c->bank.N, prev, seeded, S, cs, gp));
         if ((r = tail(prev, cs))) return r;
         LAUNCH(c, cs, "mocha_pose_heads", "live.heads", 0.0, S * (60.0 * 12 + V * 28.0 * 4), launch_pose_heads(ystage, heads, speed, S, c->cfg.T, V, cs));
         LAUNCH(c, cs, "mocha_post_clip", "live.post", 0.0, (double)S * (V * 13.0 * 4 + J * 11.0 * 8 + 2.0 * POST_STATE_DOUBLES * 8),
@@ -4205,11 +4400,13 @@ int mocha_live_step_ours(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, in
     for (int i = 0; i < 7; ++i) key.ours[i] = optrs[i];
     key.noise = oc.noise; key.seed = oc.noise == 2 ? oc.seed : 0;
     key.post = *cfg;
-    const auto& g = c->ours_step;
+    key.cvae_of = cvae_of;
+    auto& g = grouped ? c->ours_grouped_step : c->ours_step;
     if (!(g.exec && g.key == key && g.generation == c->generation)) {
         // Before a capture: one eager pass over staging alone - mocha_live_step's characterize of zeroed windows with every id -1, then the
         // sampler on a zeroed condition and the literal decoder on its sample - so that whatever the kernels of the step make on first
         // use (the plane GEMMs' weight images, the style MLP's float64 weights) exists.  No counter, ring, `prev` or post state moves.
+        // (grouped: the grouped sampler with every slot -1 - no weight is read, the sample is zeros.)
         HIPCHK(c, hipMemsetAsync(xraw, 0, (size_t)S * 60 * J * c->cfg.C_in * sizeof(float), s));
         HIPCHK(c, hipMemsetAsync(eff, 0xFF, (size_t)S * sizeof(int32_t), s));
         HIPCHK(c, hipMemsetAsync(cond, 0, (size_t)S * 180 * 256 * sizeof(float), s));
@@ -4217,10 +4414,28 @@ int mocha_live_step_ours(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, in
         rc = characterize_impl(c, xraw, S, cnt_mean, cnt_std, ystage, nullptr, s, true, eff);
         c->cur = 0;
         if (rc) return rc;
-        if ((rc = cvae_sample_impl(c, cond, S, vae, mu, logvar, nullptr, s))) return rc;
+        if ((rc = cvae_sample_impl(c, cond, S, vae, mu, logvar, nullptr, s, grouped ? c->cvb.none.p : nullptr))) return rc;
         if ((rc = tail(vae, s))) return rc;
     }
-    return step_replay(c, c->ours_step, key, s, body);
+    return step_replay(c, g, key, s, body);
+}
+
+int mocha_live_step_ours(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos, const float* Yvel,
+                         const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed, const unsigned char* contact,
+                         const int32_t* seg, const float* cnt_mean, const float* cnt_std, void* ours, const mocha_ours_cfg* ocfg, double* pos,
+                         double* rot, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx, int32_t* valid, int32_t* seeded,
+                         void* stream) {
+    return live_step_ours_impl(c, cfg, live, streams, Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, seg, cnt_mean, cnt_std, ours,
+                               ocfg, pos, rot, ik_rot, bvh_pos, bvh_euler, idx, valid, seeded, stream, false, nullptr);
+}
+
+int mocha_live_step_ours_grouped(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos,
+                                 const float* Yvel, const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed,
+                                 const unsigned char* contact, const int32_t* seg, const float* cnt_mean, const float* cnt_std, void* ours,
+                                 const mocha_ours_cfg* ocfg, const int32_t* cvae_of, double* pos, double* rot, double* ik_rot, double* bvh_pos,
+                                 double* bvh_euler, int32_t* idx, int32_t* valid, int32_t* seeded, void* stream) {
+    return live_step_ours_impl(c, cfg, live, streams, Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, seg, cnt_mean, cnt_std, ours,
+                               ocfg, pos, rot, ik_rot, bvh_pos, bvh_euler, idx, valid, seeded, stream, true, cvae_of);
 }
 
 int mocha_column_stats(mocha_ctx* c, const float* x, int64_t N, float* mean, float* std_, void* stream) {
@@ -4353,6 +4568,26 @@ int mocha_linear(mocha_ctx* c, const float* x, const float* w, const float* bias
     if (e == hipSuccess) e = (c->gemm_x3r_min_n > 0 && N >= c->gemm_x3r_min_n && gemm_x3r_supports(p)) ? launch_gemm_x3r(p, s) : launch_gemm_x3(p, s);      // option "gemm_x3r_min_n": same bits
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return fail(c, MOCHA_ERR_HIP, "mocha_linear: %s", hipGetErrorString(e));
+    return 0;
+}
+
+int mocha_linear_grouped(mocha_ctx* c, const float* x, const float* w_bank, const float* bias_bank, const int32_t* which, const int32_t* stored,
+                         float* y, int ldc, int G, int m, int N, int K, int Cw, int act, const float* residual, int ldr, void* stream) {
+    if (!c || !x || !w_bank || !which || !stored || !y) return fail(c, MOCHA_ERR_ARG, "mocha_linear_grouped: null argument");
+    if (G < 0 || m < 1 || N < 16 || K < 16 || N % 16 != 0 || K % 16 != 0 || Cw < 1 || (act != 0 && act != 3) || ldc < N || ldc % 4 != 0 ||
+        (residual && (ldr < N || ldr % 4 != 0)) || (long long)G * m > (1ll << 30))
+        return fail(c, MOCHA_ERR_ARG, "mocha_linear_grouped: G=%d m=%d N=%d K=%d Cw=%d act=%d ldc=%d ldr=%d (m >= 1, N %% 16 == 0, K %% 16 == 0, act 0 or 3, "
+                    "ldc / ldr >= N and multiples of 4)", G, m, N, K, Cw, act, ldc, ldr);
+    if (G == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    GroupedGemmParams p;
+    p.A = x; p.W = w_bank; p.bias = bias_bank; p.which = which; p.stored = stored; p.C = y; p.residual = residual;
+    p.G = G; p.m = m; p.N = N; p.K = K; p.Cw = Cw; p.lda = K; p.ldc = ldc; p.ldr = residual ? ldr : 0;
+    p.w_stride = (long long)N * K; p.b_stride = N; p.act = act;
+    const double M = (double)G * m;
+    LAUNCH(c, s, "mocha_gemm_grouped", "linear_grouped", 2.0 * M * N * K, 4.0 * (M * K + (double)G * ((m + 15) / 16) * N * K + M * N * (residual ? 2 : 1)),
+           launch_gemm_grouped(p, s));
     return 0;
 }
 

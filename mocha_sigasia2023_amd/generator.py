@@ -598,9 +598,9 @@ class StreamingCharacterizer:
         return Y, idx
 
 
-def _load_cvae_weights(ctx: "_Context", state_dict: Mapping, strict: bool = True):
+def _load_cvae_weights(ctx: "_Context", state_dict: Mapping, strict: bool = True, finalize: bool = True):
     """A CVAE ``state_dict`` into ``ctx`` (``mocha_cvae_load_weight`` per tensor, then ``mocha_cvae_finalize``): the loader of
-    ``CVAE.load_state_dict`` and ``Generator.load_cvae``."""
+    ``CVAE.load_state_dict`` and ``Generator.load_cvae``.  ``finalize=False`` only stages the tensors on the host (``CVAEBank.store``)."""
     from .weights import cvae_param_shapes
     want = cvae_param_shapes()
     seen = set()
@@ -626,7 +626,8 @@ def _load_cvae_weights(ctx: "_Context", state_dict: Mapping, strict: bool = True
         pe = np.ascontiguousarray(sincos_pe(192)[None], dtype=np.float32)
         ctx.call("mocha_cvae_load_weight", b"prior_net.pos_encoder.pe", pe.ctypes.data_as(C.c_void_p),
                  (C.c_int64 * 3)(*pe.shape), 3)
-    ctx.call("mocha_cvae_finalize")
+    if finalize:
+        ctx.call("mocha_cvae_finalize")
 
 
 class CVAE:
@@ -683,6 +684,69 @@ class CVAE:
         elif eps is None:
             eps = torch.randn((c.shape[0], DIM), dtype=torch.float32, device=self.device)
         return self._run(c, eps)[0]
+
+
+class CVAEBank:
+    """A resident bank of ``max_cvaes`` CVAEs on ``model``'s context (``mocha_cvae_bank_create``): one CVAE per target character, as the
+    reference trains them (``train_CVAE.py``), each with its four (90,256) statistics (``cvae_norm.npz``).  Which slot a row of
+    ``sample`` - or a stream of a ``LiveOursSession(cvaes=...)`` - uses is device data: ``store`` and ``clear`` are enqueued on the
+    current stream, move no generation and make no captured step capture again.  About 10.5 MB of device memory per slot; one
+    positional table serves the whole bank."""
+
+    def __init__(self, model: "Generator", max_cvaes: int):
+        self.model, self.device = model, model.device
+        self.max_cvaes = int(max_cvaes)
+        model._ctx.call("mocha_cvae_bank_create", self.max_cvaes)
+
+    def store(self, slot: int, state_dict: Mapping, src_cnt_mean, src_cnt_std, cha_encoded_mean, cha_encoded_std):
+        """``state_dict`` (as ``CVAE.load_state_dict`` takes it) and its statistics into ``slot``; a slot in use is overwritten in stream
+        order.  The tensors are staged through the context's host copy (``mocha_cvae_load_weight``), which un-finalises the model's
+        OWN CVAE (``Generator.load_cvae``; its device copy is not touched): a model that also runs single-CVAE sessions calls
+        ``load_cvae`` again after its stores."""
+        ctx = self.model._ctx
+        _load_cvae_weights(ctx, state_dict, True, finalize=False)
+        self.model._cvae_loaded = False
+        st = [np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a), dtype=np.float32)
+              for a in (src_cnt_mean, src_cnt_std, cha_encoded_mean, cha_encoded_std)]
+        for a, n in zip(st, ("src_cnt_mean", "src_cnt_std", "cha_encoded_mean", "cha_encoded_std")):
+            if a.shape != (NTOK, DIM):
+                raise ValueError(f"CVAEBank.store: {n} has shape {a.shape}, expected {(NTOK, DIM)}")
+        ctx.call("mocha_cvae_bank_store", int(slot), *[a.ctypes.data_as(C.c_void_p) for a in st], _stream())
+        return self
+
+    def clear(self, slot: int):
+        """``slot`` holds no CVAE from here on in stream order (its weights stay): rows and streams on it count as having none."""
+        self.model._ctx.call("mocha_cvae_bank_clear", int(slot), _stream())
+        return self
+
+    @property
+    def stored(self):
+        """Per slot, whether it holds a CVAE - as the host enqueued the stores and clears."""
+        cap = C.c_int(0)
+        buf = (C.c_ubyte * self.max_cvaes)()
+        self.model._ctx.call("mocha_cvae_bank_info", C.byref(cap), buf)
+        return [bool(x) for x in buf[: cap.value]]
+
+    def sample(self, cond, which, eps: Optional[torch.Tensor] = None, deterministic: bool = False):
+        """``CVAE.sample`` with row b of ``cond`` (B,180,256) on slot ``which[b]`` (``mocha_cvae_sample_grouped``): returns (out (B,90,256),
+        mu, logvar (B,256)).  A row whose slot is outside the bank or holds no CVAE gets zeros.  ``which``: a device int32 tensor is
+        read in place; anything else is copied.  Noise as in ``CVAE.sample``."""
+        c = _dev_f32(cond, self.device, (180, DIM), "condition")
+        B = c.shape[0]
+        w = which if isinstance(which, torch.Tensor) else torch.as_tensor(list(which))
+        w = w.to(device=self.device, dtype=torch.int32).contiguous()
+        if w.shape != (B,):
+            raise ValueError(f"CVAEBank.sample: which has shape {tuple(w.shape)}, expected {(B,)}")
+        if deterministic:
+            eps = None
+        elif eps is None:
+            eps = torch.randn((B, DIM), dtype=torch.float32, device=self.device)
+        e = None if eps is None else _dev_f32(eps, self.device, (DIM,), "eps")
+        out = torch.empty((B, NTOK, DIM), dtype=torch.float32, device=self.device)
+        mu = torch.empty((B, DIM), dtype=torch.float32, device=self.device)
+        logvar = torch.empty_like(mu)
+        self.model._ctx.call("mocha_cvae_sample_grouped", _ptr(c), B, _ptr(w), _ptr(out), _ptr(mu), _ptr(logvar), _ptr(e), _stream())
+        return out, mu, logvar
 
 
 class OursSession:

@@ -285,13 +285,28 @@ class LiveOursSession(LiveSession):
     so further sessions on a model should pass None.  ``noise``: ``"device"`` draws the
     sampler's noise on the device from ``seed`` (Philox4x32-10 counted by stream and frame: the same seed repeats the session),
     ``"given"`` reads ``sess.eps`` (S,256), which the caller writes before a push, ``"none"`` takes z = mu.  ``push`` / ``replay`` /
-    ``run_clip`` / ``reset`` as in ``LiveSession``; the outputs gain ``seeded`` (S,) int32: 1 where the frame was a seed frame."""
+    ``run_clip`` / ``reset`` as in ``LiveSession``; the outputs gain ``seeded`` (S,) int32: 1 where the frame was a seed frame.
+
+    ``cvaes=CVAEBank(...)``: ONE CVAE PER CHARACTER instead (``mocha_live_step_ours_grouped``).  The session owns ``self.cvae_of``, a
+    device int32 tensor with one entry per character of the bank - the character's slot of ``cvaes`` - initialised from ``cvae_of``
+    (default: all -1); ``set_cvae(character, slot)`` writes an entry in place, and so may a producer on the device: no new capture.  A
+    stream samples with its character's CVAE and statistics; a stream whose character has none (-1, a slot outside the bank, a cleared
+    or never stored slot) falls back to plain context matching - every valid frame is a seed frame.  ``cvae_state_dict`` and the four
+    statistics must then be None."""
 
     NOISE = {"none": 0, "given": 1, "device": 2}
 
     def __init__(self, bank: MultiCharacterBank, cnt_mean, cnt_std, cvae_state_dict, src_cnt_mean, src_cnt_std, cha_encoded_mean,
                  cha_encoded_std, streams: int = 1, post: Optional[PostProcessor] = None, bvh: bool = True, noise: str = "device",
-                 seed: int = 0, soft=None, inertial=None, raw=None, constrained: bool = False):
+                 seed: int = 0, soft=None, inertial=None, raw=None, constrained: bool = False, cvaes=None, cvae_of=None):
+        if cvaes is None and cvae_of is not None:
+            raise ValueError("LiveOursSession: cvae_of needs cvaes=CVAEBank(...)")
+        if cvaes is not None:
+            if cvaes.model is not bank.model:
+                raise ValueError("LiveOursSession: cvaes belongs to another model")
+            if any(a is not None for a in (cvae_state_dict, src_cnt_mean, src_cnt_std, cha_encoded_mean, cha_encoded_std)):
+                raise ValueError("LiveOursSession: with cvaes= the CVAEs and their statistics come from the bank - pass None for "
+                                 "cvae_state_dict and the four statistics")
         if constrained:
             raise ValueError("LiveOursSession: constrained=True is not supported - the branch's seed match searches the whole character")
         if raw is not None:
@@ -305,19 +320,27 @@ class LiveOursSession(LiveSession):
             raise ValueError(f"noise must be one of {sorted(self.NOISE)}")
         super().__init__(bank, cnt_mean, cnt_std, streams=streams, post=post, bvh=bvh)
         m, dev, S = self.model, self.model.device, self.streams
-        if cvae_state_dict is not None:
-            m.load_cvae(cvae_state_dict)
-        elif not getattr(m, "_cvae_loaded", False):
-            raise RuntimeError("LiveOursSession: cvae_state_dict=None needs a CVAE on the model (Generator.load_cvae)")
-        self.stats = [_dev_f32(a, dev, (NTOK, DIM), n) for a, n in ((src_cnt_mean, "src_cnt_mean"), (src_cnt_std, "src_cnt_std"),
-                                                                   (cha_encoded_mean, "cha_encoded_mean"), (cha_encoded_std, "cha_encoded_std"))]
+        self.cvaes, self.cvae_of = cvaes, None
+        if cvaes is not None:
+            of = torch.full((bank.S,), -1, dtype=torch.int32) if cvae_of is None else torch.as_tensor(cvae_of).to(torch.int32).reshape(-1).cpu()
+            if of.numel() != bank.S:
+                raise ValueError(f"LiveOursSession: cvae_of has {of.numel()} entries, the bank has {bank.S} characters")
+            self.cvae_of = of.to(dev)
+            self.stats = []
+        else:
+            if cvae_state_dict is not None:
+                m.load_cvae(cvae_state_dict)
+            elif not getattr(m, "_cvae_loaded", False):
+                raise RuntimeError("LiveOursSession: cvae_state_dict=None needs a CVAE on the model (Generator.load_cvae)")
+            self.stats = [_dev_f32(a, dev, (NTOK, DIM), n) for a, n in ((src_cnt_mean, "src_cnt_mean"), (src_cnt_std, "src_cnt_std"),
+                                                                       (cha_encoded_mean, "cha_encoded_mean"), (cha_encoded_std, "cha_encoded_std"))]
         nbytes = int(m._ctx.lib.mocha_live_ours_state_bytes(m._ctx.h, S))
         if nbytes <= 0:
             raise RuntimeError("mocha_live_ours_state_bytes failed")
         self.ours = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)          # zeroed = every stream seeds on its first valid frame
         self.eps = torch.zeros((S, DIM), dtype=torch.float32, device=dev)
         self.noise, self.seed = noise, int(seed) & 0xFFFFFFFFFFFFFFFF
-        self.ocfg = _C.mocha_ours_cfg(*[t.data_ptr() for t in self.stats], self.NOISE[noise], self.eps.data_ptr(), self.seed)
+        self.ocfg = _C.mocha_ours_cfg(*([t.data_ptr() for t in self.stats] or [None] * 4), self.NOISE[noise], self.eps.data_ptr(), self.seed)
         self.out["seeded"] = torch.zeros((S,), dtype=torch.int32, device=dev)
         at = ((S * 12 + 255) // 256) * 256                                          # `prev` follows the counters (include/mocha_hip.h)
         self._prev = self.ours[at: at + S * NTOK * DIM * 4].view(torch.float32).reshape(S, NTOK, DIM)
@@ -327,9 +350,26 @@ class LiveOursSession(LiveSession):
         """The streams' current character features (S,90,256): a view of the state the next step conditions on."""
         return self._prev
 
+    def set_cvae(self, character: int, slot: int):
+        """Character ``character`` samples with slot ``slot`` of the CVAE bank from the next step on (-1: no CVAE - plain context
+        matching).  An in-place device write on the current stream: no new capture, and a chaining stream does not seed again."""
+        if self.cvae_of is None:
+            raise RuntimeError("LiveOursSession.set_cvae: the session was not created with cvaes=")
+        if not 0 <= int(character) < self.cvae_of.numel():
+            raise ValueError(f"LiveOursSession.set_cvae: character {character} out of range 0 .. {self.cvae_of.numel() - 1}")
+        self.cvae_of[int(character)].fill_(int(slot))
+        return self
+
     def replay(self):
         self.bank._ensure()
         o = self.out
+        if self.cvae_of is not None:
+            self.model._ctx.call("mocha_live_step_ours_grouped", C.byref(self.post.cfg), _ptr(self.live), self.streams, _ptr(self.rot),
+                                 _ptr(self.pos), _ptr(self.vel), _ptr(self.ang), _ptr(self.rvel), _ptr(self.rang), _ptr(self.speed),
+                                 _ptr(self.contact), _ptr(self.ids), _ptr(self.mean), _ptr(self.std), _ptr(self.ours), C.byref(self.ocfg),
+                                 _ptr(self.cvae_of), _ptr(o["pos"]), _ptr(o["rot"]), _ptr(o["ik_rot"]), _ptr(o["bvh_pos"]) if self.bvh else None,
+                                 _ptr(o["bvh_euler"]) if self.bvh else None, _ptr(o["idx"]), _ptr(o["valid"]), _ptr(o["seeded"]), _stream())
+            return o
         self.model._ctx.call("mocha_live_step_ours", C.byref(self.post.cfg), _ptr(self.live), self.streams, _ptr(self.rot), _ptr(self.pos),
                              _ptr(self.vel), _ptr(self.ang), _ptr(self.rvel), _ptr(self.rang), _ptr(self.speed), _ptr(self.contact),
                              _ptr(self.ids), _ptr(self.mean), _ptr(self.std), _ptr(self.ours), C.byref(self.ocfg), _ptr(o["pos"]),

@@ -15,6 +15,11 @@ mocha_profile_start / stop, during which the step runs eagerly.
         the CVAE ("Ours") branch: (a) LiveSession.replay, (b) LiveOursSession.replay with device noise, (c) the same frame without the
         live step - featurize + encode + segmented match + OursSession.step + pose heads + PostProcessor.step on a window the caller
         keeps (its upkeep is not timed) - alternating replay by replay in one process, S = 1 and S = 8
+    python tools/live_latency.py --ours --grouped [--out profiles/r19/live_ours_grouped_step.json]
+        one CVAE per character: (a) LiveOursSession.replay (mocha_live_step_ours, one CVAE), (b) the grouped step
+        (LiveOursSession(cvaes=CVAEBank) = mocha_live_step_ours_grouped) with every character on ONE slot, (c) the grouped step with S
+        distinct slots - (b) and (c) are one session whose cvae_of is rewritten in place, so nothing captures again - alternating replay
+        by replay in one process, S = 1 and S = 8, p50 / p10 / p90; then the sampler's launches one at a time (profile hooks, eager)
     python tools/live_latency.py --inertial 0.1 [--out profiles/r12/live_inert_step.json]
         the plain live step and the inertialized one (LiveSession(inertial=H) = mocha_live_step_inert: one more launch, mocha_inertialize,
         between the pose heads and the post frame), alternating replay by replay in one process, S = 1 and S = 8; stream 0 switches
@@ -111,6 +116,73 @@ def ours(a, dev, model, mb, mean, std, clip, per, J):
         assert bool(torch.isfinite(lo.out["pos"]).all())
         res["streams"][str(S)] = e
         del live, lo, old
+    return res
+
+
+def ours_grouped(a, dev, model, mb, mean, std, clip, per, J):
+    """--ours --grouped: the single-CVAE live step against the grouped one (one slot for all / S distinct slots), alternating."""
+    from mocha_sigasia2023_amd import CVAEBank, LiveOursSession
+    from mocha_sigasia2023_amd.weights import synthetic_cvae_state_dict
+
+    def stats(slot):
+        rng = np.random.Generator(np.random.PCG64(3 + slot))
+        return [(0.1 * rng.standard_normal((90, 256))).astype(np.float32), rng.uniform(0.5, 1.5, (90, 256)).astype(np.float32),
+                (0.1 * rng.standard_normal((90, 256))).astype(np.float32), rng.uniform(0.5, 1.5, (90, 256)).astype(np.float32)]
+
+    def pct3(t):
+        t = np.asarray(t)
+        return {"p50_ms": float(np.percentile(t, 50)), "p10_ms": float(np.percentile(t, 10)), "p90_ms": float(np.percentile(t, 90)), "replays": int(len(t))}
+    cvaes = CVAEBank(model, 8)
+    for slot in range(8):
+        cvaes.store(slot, synthetic_cvae_state_dict(99 + slot, 1.0), *stats(slot))
+    model.load_cvae(synthetic_cvae_state_dict(99, 1.0))          # the model's own CVAE, after the stores (they stage through the same host copy)
+    res = {"bank": "8 characters x 2048 rows, fp32, segmented", "layout": "mocha (24 joints)", "cvae_bank": "8 slots, synthetic CVAEs 99 .. 106",
+           "timing": "HIP events around single graph replays; (a) mocha_live_step_ours, (b) mocha_live_step_ours_grouped with every character on "
+                     "slot 0, (c) the same session with character c on slot c, alternating; device noise; clocks untouched", "streams": {}}
+    one, distinct = torch.zeros(8, dtype=torch.int32, device=dev), torch.arange(8, dtype=torch.int32, device=dev)
+    for S in (1, 8):
+        ids = torch.tensor([(k * 3) % 8 for k in range(S)], dtype=torch.int32)
+        plain = LiveOursSession(mb, mean, std, None, *stats(0), streams=S, noise="device", seed=11)
+        grp = LiveOursSession(mb, mean, std, None, None, None, None, None, streams=S, noise="device", seed=11, cvaes=cvaes, cvae_of=distinct)
+        frame = [0]
+
+        def push():
+            f = frame[0] % 644; frame[0] += 1
+            for sess in (plain, grp):
+                sess.rot.copy_(clip[0][f]); sess.pos.copy_(clip[1][f]); sess.vel.copy_(clip[2][f]); sess.ang.copy_(clip[3][f])
+                sess.rvel.copy_(per[0][f]); sess.rang.copy_(per[1][f]); sess.speed.copy_(per[2][f]); sess.contact.copy_(per[3][f])
+        for sess in (plain, grp):
+            sess.characters.copy_(ids)
+        gen = None
+        for i in range(max(a.warmup, 70)):
+            push(); plain.replay(); grp.replay()
+            gen = model._ctx.generation() if i == 1 else gen
+        torch.cuda.synchronize()
+        assert bool((grp.out["valid"] == 1).all()) and not bool(grp.out["seeded"].any()) and not bool(plain.out["seeded"].any())
+        ta, tb, tc = [], [], []
+        for _ in range(a.reps):
+            push(); torch.cuda.synchronize()
+            ta.append(event_ms(plain.replay, 1)[0])
+            grp.cvae_of.copy_(one); torch.cuda.synchronize()
+            tb.append(event_ms(grp.replay, 1)[0])
+            grp.cvae_of.copy_(distinct); torch.cuda.synchronize()
+            tc.append(event_ms(grp.replay, 1)[0])
+        assert model._ctx.generation() == gen and not bool(grp.out["seeded"].any())      # nothing captured again, nothing reseeded
+        e = {"a_live_step_ours": pct3(ta), "b_grouped_one_slot": pct3(tb), "c_grouped_distinct_slots": pct3(tc)}
+        e["b_over_a_p50"] = e["b_grouped_one_slot"]["p50_ms"] / e["a_live_step_ours"]["p50_ms"]
+        e["c_over_a_p50"] = e["c_grouped_distinct_slots"]["p50_ms"] / e["a_live_step_ours"]["p50_ms"]
+        n = 50                                           # the sampler's launches, one at a time (the steps run eagerly while profiling)
+        for name, sess in (("a", plain), ("c", grp)):
+            model.profile_start()
+            for _ in range(n):
+                sess.replay()
+            prof = model.profile_stop()
+            e[name + "_cvae_sites_us_per_launch"] = {k: 1e3 * v["ms"] / v["launches"] for k, v in prof["sites"].items() if k.startswith("cvae.")}
+            e[name + "_cvae_launches_per_step"] = int(sum(v["launches"] for k, v in prof["sites"].items() if k.startswith("cvae.")) // n)
+            e[name + "_cvae_sum_us_per_step"] = float(sum(1e3 * v["ms"] for k, v in prof["sites"].items() if k.startswith("cvae.")) / n)
+        assert bool(torch.isfinite(grp.out["pos"]).all())
+        res["streams"][str(S)] = e
+        del plain, grp
     return res
 
 
@@ -292,6 +364,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08", "live_step.json"))
     ap.add_argument("--baseline-only", action="store_true")
     ap.add_argument("--ours", action="store_true", help="the CVAE branch: live step / live step with the branch / the route without the live step")
+    ap.add_argument("--grouped", action="store_true", help="with --ours: the single-CVAE step / the grouped step on one slot / on S distinct slots")
     ap.add_argument("--soft", type=int, default=0, metavar="K", help="soft matching: live step / soft live step with K neighbours, temperature 2")
     ap.add_argument("--inertial", type=float, default=None, metavar="H", help="inertialized switches: live step / live step with half-life H seconds")
     ap.add_argument("--raw", type=int, default=None, metavar="L", help="raw mocap input: live step / raw live step with L frames of lookahead")
@@ -305,6 +378,10 @@ def main():
         a.out = os.path.join(ROOT, "profiles", "r12", "live_inert_step.json")
     if a.soft and a.out == ap.get_default("out"):
         a.out = os.path.join(ROOT, "profiles", "r10", "live_soft_step.json")
+    if a.grouped and not a.ours:
+        raise SystemExit("--grouped goes with --ours")
+    if a.ours and a.grouped and a.out == ap.get_default("out"):
+        a.out = os.path.join(ROOT, "profiles", "r19", "live_ours_grouped_step.json")
     if a.ours and a.out == ap.get_default("out"):
         a.out = os.path.join(ROOT, "profiles", "r09", "live_ours_step.json")
     if not torch.cuda.is_available():
@@ -334,6 +411,8 @@ def main():
         return write_out(a, inertial(a, dev, model, mb, mean, std, clip, per, J))
     if a.soft:
         return write_out(a, soft(a, dev, model, mb, mean, std, clip, per, J))
+    if a.ours and a.grouped:
+        return write_out(a, ours_grouped(a, dev, model, mb, mean, std, clip, per, J))
     if a.ours:
         return write_out(a, ours(a, dev, model, mb, mean, std, clip, per, J))
     for S in (1, 8):
