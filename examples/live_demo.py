@@ -4,7 +4,7 @@ mocap frame at a time through ``LiveSession`` - ring push + featurize, segmented
 frame per push, one captured graph - and written as two BVH files.
 
     python examples/live_demo.py [--frames 180] [--out bench_outputs/live_demo] [--ours [--seed 7]] [--switch 120 [--inertial 0.1]] [--raw L]
-                                 [--actions A,B[:F]] [--load-at F] [--ours-per-character]
+                                 [--actions A,B[:F]] [--load-at F] [--ours-per-character] [--mix a:b:FRAMES | --mix-parts a:b:MASK]
 
 ``--ours`` runs the CVAE ("Ours") branch inside the same graph (``LiveOursSession``): each stream's character feature is seeded with
 its matched bank row on the first pose and sampled from the previous one afterwards, the noise drawn on the device; the files are then
@@ -31,6 +31,12 @@ How many posed frames were constrained is printed.
 ``--load-at F``: the run starts on a ``ResidentCharacterBank`` that holds the two characters; at frame F a third character is added to it
 in place - its own rows and decoder constants, enqueued on the stream - and stream 1 switches to it.  The captured step keeps replaying:
 the model's generation before and after is printed.
+
+``--mix a:b:FRAMES``: both streams are characterized by a MIX of characters a and b (``LiveSession(mix=2)``): a linear cross-fade from a
+to b over FRAMES frames, starting with the first posed frame - a weight ramp written into the session's device weights, in feature
+space; nothing is captured again.  ``--mix-parts a:b:MASK``: a splice by body part - MASK is six 0/1 characters, one per body part in the
+order of ``PART_NAMES`` (Spine, LeftLeg, LeftArm, Neck, RightArm, RightLeg for this layout): 1 takes the part from a, 0 from b.  Neither
+combines with ``--soft``, ``--inertial``, ``--actions``, ``--switch`` or ``--ours``.
 
 Weights, norms and motions are synthetic (see demo_pair.py for what to replace with real assets).
 """
@@ -61,8 +67,27 @@ ap.add_argument("--actions", default=None, metavar="A,B[:F]", help="allow only t
 ap.add_argument("--load-at", type=int, default=None, metavar="FRAME", help="start on a resident bank; at that frame a third character is added in "
                 "place and stream 1 switches to it")
 ap.add_argument("--ours-per-character", action="store_true", help="--ours with one CVAE per character from a CVAEBank (synthetic CVAEs)")
+ap.add_argument("--mix", default=None, metavar="a:b:FRAMES", help="cross-fade both streams from character a to b over FRAMES frames")
+ap.add_argument("--mix-parts", default=None, metavar="a:b:MASK", help="splice: body parts with 1 in the six-character MASK from a, the others from b")
 a = ap.parse_args()
 a.ours = a.ours or a.ours_per_character
+mix_ids = mix_ramp = mix_mask = None
+if a.mix or a.mix_parts:
+    if a.mix and a.mix_parts:
+        raise SystemExit("--mix and --mix-parts are two forms of one thing: give one")
+    if a.ours or a.soft or a.inertial is not None or a.actions or a.switch is not None:
+        raise SystemExit("--mix / --mix-parts do not combine with --ours, --soft, --inertial, --actions or --switch: mix is hard matching per "
+                         "component, and its weights are what changes a stream's character")
+    ca, cb, last = (a.mix or a.mix_parts).split(":")
+    mix_ids = [int(ca), int(cb)]
+    if a.mix:
+        mix_ramp = int(last)
+        if mix_ramp < 1:
+            raise SystemExit("--mix a:b:FRAMES: FRAMES must be at least 1")
+    else:
+        if len(last) != 6 or set(last) - {"0", "1"}:
+            raise SystemExit("--mix-parts a:b:MASK: MASK is six 0/1 characters, one per body part")
+        mix_mask = np.array([float(ch) for ch in last], np.float32)
 if a.ours and a.actions:
     raise SystemExit("--actions does not apply to --ours: the branch's seed match searches the whole character")
 allow_from, allow_mask = 0, None
@@ -136,7 +161,9 @@ elif a.ours:                                                          # test_ful
                            noise="device", seed=a.seed)
 else:
     sess = LiveSession(bank, cnt_mean, cnt_std, streams=S, post=PostProcessor(model), soft=soft, inertial=a.inertial, raw=a.raw,
-                       constrained=bool(a.actions))
+                       constrained=bool(a.actions), mix=2 if mix_ids else None)
+if mix_ids:
+    sess.set_mix((mix_ids, np.stack([mix_mask, 1 - mix_mask]) if mix_mask is not None else [1.0, 0.0]))
 if a.raw is not None:
     raw = [synthetic.raw_walk_clip(LAYOUTS["mocha"]["parents"], F, seed=40 + s) for s in range(S)]
     raw_rot = torch.from_numpy(np.stack([r[0] for r in raw])).to(dev)  # (S, F, 24, 3) degrees, 'zyx'
@@ -145,6 +172,11 @@ if a.raw is not None:
 
 def push(f, characters=None):
     kw = dict(allow=[allow_mask] * S) if a.actions and f == allow_from else {}
+    if mix_ids:
+        characters = None                                             # a mix session's characters are its mix
+        if mix_ramp:                                                  # the cross-fade: new weights in place, read by the replay
+            t = min(max((f - first + 1) / mix_ramp, 0.0), 1.0)
+            sess.mix_weights[:, 0].fill_(1.0 - t); sess.mix_weights[:, 1].fill_(t)
     if a.raw is not None:
         if kw:
             sess.set_allow(kw["allow"])
@@ -180,7 +212,7 @@ pos, eul = torch.stack(pos, 1), torch.stack(eul, 1)                   # (S, F - 
 
 names = ["Joint%02d" % i for i in range(24)]
 for s in range(S):
-    p = os.path.join(a.out, f"{'Ours' if a.ours else 'soft' if soft else 'raw' if a.raw is not None else 'live'}_stream{s}.bvh")
+    p = os.path.join(a.out, f"{'Ours' if a.ours else 'mix' if mix_ids else 'soft' if soft else 'raw' if a.raw is not None else 'live'}_stream{s}.bvh")
     write_bvh(p, names, LAYOUTS["mocha"]["parents"], pos[s], eul[s])
     print(f"  {p}: {os.path.getsize(p)} bytes, {pos.shape[1]} frames")
 if a.ours_per_character:
@@ -193,6 +225,11 @@ if a.switch is not None and first + 1 <= a.switch < F:
 if a.load_at is not None and 0 <= a.load_at < F:
     print(f"  character 2 ({banks[2][0].shape[0]} entries) added to the resident bank at frame {a.load_at}, rows {bank.rows(2)}; stream 1 took it; "
           f"generation {gen0} -> {model._ctx.generation()}; {bank.free_rows} rows free")
+if mix_ids:
+    wt = o["weight"][0].tolist()
+    what = f"cross-fade over {mix_ramp} frames from the first pose" if mix_ramp else f"splice {a.mix_parts.rpartition(':')[2]} by body part"
+    print(f"  mix of characters {mix_ids[0]} and {mix_ids[1]} ({what}): final normalised weights of stream 0 {wt}; "
+          f"generation {gen0} -> {model._ctx.generation()}")
 if a.actions:
     ap_ = torch.stack(applied, 1)
     print(f"  actions {a.actions.partition(':')[0]} allowed from frame {allow_from}: " + ", ".join(

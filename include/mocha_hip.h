@@ -755,6 +755,61 @@ int mocha_live_step_raw_allow(mocha_ctx* ctx, const mocha_post_cfg* cfg, const m
                               int32_t* idx, int32_t* valid, int32_t* idx_k, float* w_k, void* stream, void* inert,
                               const mocha_inert_cfg* icfg, const uint64_t* allow, int32_t* applied);
 
+/* Character mixing on a multi-character bank: a window characterized by up to MOCHA_MIX_MAX (character, six body-part weights) components
+ * instead of exactly one character - a strength dial ("70 % zombie, 30 % neutral"), a cross-fade (a weight ramp from a to b over n frames, in
+ * feature space) and a splice by body part ("arms of A, legs of B") are ONE operation.  The model's tokens are 15 time patches x 6 body
+ * parts, token = t * 6 + v (v in the column order of the layout's pool matrix, mocha_graph_constants); the decoder reads, part by part, the
+ * weighted blend of the components' matched entries.  Nothing is trained, as for the soft calls.
+ *   Window q carries ids[q][j] (int32) and weights[q][j][v] (fp32), j < J, 1 <= J <= MOCHA_MIX_MAX, v < MOCHA_MIX_PARTS; both DEVICE data.
+ *   PRESENT: component j is present iff ids[q][j] names a loaded character (inside the table; on a resident bank a non-empty slot) and at
+ *     least one of its six weights is usable.  A weight is usable iff 0 < w <= FLT_MAX: NaN, negatives, zero and infinities count as 0.
+ *     A component that is not present reads no bank row and reports idx -1, dist +inf, weights 0: a ramp that reached 0 costs no scan.
+ *   MATCH: a present component's row is the exact 1-NN of the window's query in that character - index, tie rule (lowest row), distance
+ *     and bank arithmetic are mocha_match_segmented's for (that query, that id), bit for bit (fp32 rows, or the centred bf16 copy).
+ *   NORMALISATION: per part v, s_v = the sum of the usable weights of present components (fp32, j ascending).  s_v > 0: wnorm[j][v] =
+ *     w[j][v] / s_v (one IEEE division); otherwise the lowest present j gets 1 for that part, the others 0.
+ *   FEATURE: F[t][v][c] = sum_j wnorm[j][v] * encoded[row_j][t][v][c] in the soft blend's arithmetic: from 0 in fp32, j ascending, every
+ *     product and every sum rounded on its own; terms with wnorm == 0 are skipped and their row not read, so a window with one effective
+ *     component gets that entry's bits.  The same id may appear in two components: both match the same row and their weights add.
+ *   NO COMPONENT PRESENT: as an invalid id in the hard calls - idx -1, dist +inf, weights 0, the decoder reads row 0 (an unspecified Y).
+ * NOT provided: mix together with soft (k > 1) or action-constrained matching per component, inertializing weight changes, the Ours
+ * sessions, more than MOCHA_MIX_MAX components, more than 16 streams per step.
+ * J outside 1..MOCHA_MIX_MAX and a NULL required pointer are MOCHA_ERR_ARG and a bank without a segment table MOCHA_ERR_STATE, before
+ * anything is launched.  Nothing here allocates or synchronises: mocha_bank_set_segments, mocha_bank_resident_create and mocha_reserve also
+ * reserve the scratch of 16 windows x 4 components per workspace set (64 x the largest segment's 16-row granules x 8 bytes, + 3 KB); a
+ * larger batch walks its windows 16 at a time.  Launches per 16 windows: mocha_mix_prep, the plan, the scan and the finish over the Q x J
+ * pseudo-queries (the J pseudo-queries of a window read its one query row), mocha_seg_mix_blend.  Scan cost: the sum over blocks (up to 8
+ * pseudo-queries sharing a character) of that character's rows x 23 040 x bytes per value.
+ *   mocha_match_mix_segmented : idx (Q,J) local rows; dist (Q,J), wnorm (Q,J,6), out (Q,90,256) or NULL.
+ *   mocha_characterize_mix_segmented : mocha_characterize_segmented with the decoder run on F (the literal flow of the soft calls: the
+ *                             bank's per-entry decoder constants do not apply to a blend).  idx (B,J) / wnorm (B,J,6) or NULL.
+ *   mocha_step_graph_mix_segmented : that call for 1 <= S_w <= 16 windows captured into a HIP graph on first use and replayed; idx and wnorm
+ *                             required.  Keyed on the buffer pointers, S_w, J, raw and the generation; the CONTENTS of ids and weights
+ *                             are read by every replay and re-capture nothing.  Before a capture the step runs once eagerly.
+ *   mocha_live_step_mix / mocha_live_step_raw_mix : mocha_live_step / mocha_live_step_raw with that characterize in place of the hard
+ *                             one; ids (S,J) and weights (S,J,6) stand where seg stands, idx is (S,J) and wnorm (S,J,6) follows valid.
+ *                             The session buffer, its size and layout, mocha_live_reset and the warming rule are unchanged.  A stream
+ *                             none of whose components is present (every character retired, every weight 0) sits the step out as a
+ *                             warming one: valid 0, its output rows untouched, its post state not advanced, idx -1, wnorm 0; it resumes
+ *                             when a component is present again.  Each has its own captured graph and the eager pass before a capture. */
+#define MOCHA_MIX_MAX 4
+#define MOCHA_MIX_PARTS 6
+int mocha_match_mix_segmented(mocha_ctx* ctx, const float* query_nm, int Q, const int32_t* ids, const float* weights, int J, int32_t* idx,
+                              float* dist, float* wnorm, float* out, void* stream);
+int mocha_characterize_mix_segmented(mocha_ctx* ctx, const float* src_X, int B, const int32_t* ids, const float* weights, int J,
+                                     const float* cnt_mean, const float* cnt_std, float* Y, int32_t* idx, float* wnorm, int raw, void* stream);
+int mocha_step_graph_mix_segmented(mocha_ctx* ctx, const float* X, int S_w, const int32_t* ids, const float* weights, int J,
+                                   const float* cnt_mean, const float* cnt_std, float* Y, int32_t* idx, float* wnorm, int raw, void* stream);
+int mocha_live_step_mix(mocha_ctx* ctx, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos,
+                        const float* Yvel, const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed,
+                        const unsigned char* contact, const int32_t* ids, const float* weights, int J, const float* cnt_mean,
+                        const float* cnt_std, double* pos, double* rot, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx,
+                        int32_t* valid, float* wnorm, void* stream);
+int mocha_live_step_raw_mix(mocha_ctx* ctx, const mocha_post_cfg* cfg, const mocha_ingest_cfg* icfg_in, void* live, void* ingest, int streams,
+                            const float* rot, const float* pos, const int32_t* ids, const float* weights, int J, const float* cnt_mean,
+                            const float* cnt_std, double* pos_out, double* rot_out, double* ik_rot, double* bvh_pos, double* bvh_euler,
+                            int32_t* idx, int32_t* valid, float* wnorm, void* stream);
+
 /* WHOLE clips through the same preparation, parallel over frames: process_data (preprocess/generate_database.py:86-177) with mirror =
  * False / True and divide_clip(divide=True) (:57-84), the first link of raw clip -> database.bin -> bank (generate_database_bin.py:96-208)
  * and of raw clip pair -> windows -> mocha_characterize_pair.  Every frame of a clip is emitted, frame 0 and the last included: the fits'

@@ -147,6 +147,11 @@ SIGNATURES = {
     "mocha_step_graph_segmented_allow": (_i, [_vp, _vp, _i, _vp, _vp, _i, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "mocha_live_step_allow": (_i, [_vp, _vp, _vp, _i] + [_vp] * 11 + [_i, C.c_float] + [_vp] * 14),
     "mocha_live_step_raw_allow": (_i, [_vp, _vp, _vp, _vp, _vp, _i] + [_vp] * 5 + [_i, C.c_float] + [_vp] * 14),
+    "mocha_match_mix_segmented": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mocha_characterize_mix_segmented": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "mocha_step_graph_mix_segmented": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "mocha_live_step_mix": (_i, [_vp, _vp, _vp, _i] + [_vp] * 10 + [_i] + [_vp] * 11),
+    "mocha_live_step_raw_mix": (_i, [_vp, _vp, _vp, _vp, _vp, _i] + [_vp] * 4 + [_i] + [_vp] * 11),
     "mocha_bank_resident_create": (_i, [_vp, _i64, _i, _i64, _i, _vp]),
     "mocha_bank_resident_add": (_i, [_vp, _i, _vp, _vp, _i64, _vp, C.POINTER(C.c_int32), _vp]),
     "mocha_bank_resident_retire": (_i, [_vp, _i, _vp]),

@@ -562,6 +562,25 @@ hipError_t launch_match_seg_topk(const void* bank, int bank_bf16, const float* q
                                  int32_t* idx0, int32_t* idx_k, float* dist_k, float* w_k, float* out, hipStream_t s,
                                  const SegAllow* al = nullptr,         // al: rows outside a constrained query's mask count as missing
                                  int slot_table = 0);
+// character mixing on a multi-character bank (match_seg_mix.hip): window q carries J <= SEG_MIX_MAX_J components (ids[q][j], six body-part
+// weights weights[q][j][v]); every PRESENT component - a loaded character and at least one weight in (0, FLT_MAX] - is matched exactly in
+// its own character as launch_match_segmented matches (that query, that id); the weights are normalised per part over the present
+// components (a part nobody weighs goes to the lowest present component) and out (Q,D) = sum_j what[j][token % 6] enc[row_j] in
+// launch_match_seg_topk's blend arithmetic.  idx / dist (Q,J): local rows / distances, -1 / +inf where not present; wnorm (Q,J,6): the
+// normalised weights (0); dist, wnorm, out may be null.  A window with no present component: out = enc[0].  gate (or null): Q ints, a
+// window whose gate is negative has no present component (a live stream still warming); valid (or null, live steps): Q ints, rewritten to
+// 1 where a component is present and 0 elsewhere.  Q <= SEG_MIX_Q per launch; partial = match_seg_scratch_words(SEG_MIX_Q * SEG_MIX_MAX_J,
+// largest segment) words, plan = seg_plan_ints(SEG_MIX_Q * SEG_MIX_MAX_J, S) ints, iscr = seg_mix_scratch_ints() ints, fscr =
+// seg_mix_scratch_floats() floats.  D = 90 x 256 (tokens t x 6 + part, 256 channels).
+static constexpr int SEG_MIX_MAX_J = 4;
+static constexpr int SEG_MIX_Q = 16;
+static constexpr int SEG_MIX_PARTS = 6;
+size_t seg_mix_scratch_ints();
+size_t seg_mix_scratch_floats();
+hipError_t launch_match_seg_mix(const void* bank, int bank_bf16, const float* query, const int32_t* ids, const float* weights, int Q, int J,
+                                const int* seg_start, int S, int64_t max_rows, int D, unsigned long long* partial, int* plan, int32_t* iscr,
+                                float* fscr, const float* enc, const int32_t* gate, int32_t* valid, int32_t* idx, float* dist, float* wnorm,
+                                float* out, hipStream_t s, int slot_table = 0);
 // out[q] = src[idx[q]] rows of `cols` floats
 hipError_t launch_gather_rows(const float* src, const int32_t* idx, float* out, int Q, int cols, int64_t nrows, hipStream_t s);
 

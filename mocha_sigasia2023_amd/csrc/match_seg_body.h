@@ -24,13 +24,17 @@ static constexpr int PLAN_STRIDE = 10;
 // ALLOW (action-constrained matching): the distance loop is the plain one; at key time row r is a candidate of query q only if its label's
 // bit is in eff[q] (LDS: the query's effective mask, all ones for an unconstrained query), else its key is ~0.  label: one byte per global
 // row.  ALLOW = false reads neither.
-template <int Q, bool BF16, bool ALLKEYS, bool ALLOW = false>
+// MIX (character mixing, match_seg_mix.hip): the block's entries are PSEUDO-queries - (window, component) pairs - whose query row is
+// qrow[q] (LDS: pseudo-query / components per window) while keys still go to the pseudo-query's own words.  MIX = false never reads qrow.
+template <int Q, bool BF16, bool ALLKEYS, bool ALLOW = false, bool MIX = false>
 __device__ __forceinline__ void seg_scan_body(const void* __restrict__ bank, const float* __restrict__ query, const int* qidx, int nq,
                                               long long seg_lo, long long seg_n, long long row0, int D, float* __restrict__ qs,
                                               unsigned long long (*wbest)[8], unsigned long long* __restrict__ partial, int pstride,
-                                              const unsigned long long* eff = nullptr, const unsigned char* __restrict__ label = nullptr) {
+                                              const unsigned long long* eff = nullptr, const unsigned char* __restrict__ label = nullptr,
+                                              const int* qrow = nullptr) {
     constexpr int MS_CHUNK = BF16 ? MS_CHUNK_BF16 : MS_CHUNK_F32;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int* qsrc = MIX ? qrow : qidx;               // where query q of the block reads its row
     ms_f32x2 acc[MS_ROWS_PER_WAVE][Q];
 #pragma unroll
     for (int r = 0; r < MS_ROWS_PER_WAVE; ++r)
@@ -42,7 +46,7 @@ __device__ __forceinline__ void seg_scan_body(const void* __restrict__ bank, con
         for (int i = tid; i < Q * (MS_CHUNK / 4); i += 256) {
             const int q = i / (MS_CHUNK / 4), o = i - q * (MS_CHUNK / 4);
             ms_f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (q < nq) v = reinterpret_cast<const ms_f32x4*>(query + (size_t)qidx[q] * D + (size_t)ch * MS_CHUNK)[o];
+            if (q < nq) v = reinterpret_cast<const ms_f32x4*>(query + (size_t)qsrc[q] * D + (size_t)ch * MS_CHUNK)[o];
             reinterpret_cast<ms_f32x4*>(qs)[i] = v;
         }
         __syncthreads();
@@ -167,15 +171,17 @@ __device__ __forceinline__ void seg_extent(const int* __restrict__ table, int s,
 // ALLOW: al's masks and tables (kernels.h, SegAllow).  The workgroup forms its queries' effective masks in LDS, and when no query admits
 // any label of its 16 rows (the granule word) it writes ~0 for each query - one minimum, or the 16 row keys, which the finish / top-k
 // kernels read - and returns before the first bank row.
-template <bool BF16, bool ALLKEYS, bool ALLOW = false, bool PAIRS = false>
+// MIX: the plan's entries are pseudo-queries, mix_j of them per query row (seg_scan_body); MIX = false ignores mix_j.
+template <bool BF16, bool ALLKEYS, bool ALLOW = false, bool PAIRS = false, bool MIX = false>
 __device__ __forceinline__ void seg_scan_workgroup(const void* __restrict__ bank, const float* __restrict__ query, const int* __restrict__ plan,
                                                    const int* __restrict__ seg_start, int D, unsigned long long* __restrict__ partial, int pstride,
-                                                   SegAllow al = SegAllow{}) {
+                                                   SegAllow al = SegAllow{}, int mix_j = 1) {
     constexpr int MS_CHUNK = BF16 ? MS_CHUNK_BF16 : MS_CHUNK_F32;
     __shared__ __attribute__((aligned(16))) float qs[8 * MS_CHUNK];
     __shared__ unsigned long long wbest[MS_WAVES][8];
     __shared__ int qidx[8];
     __shared__ unsigned long long eff[ALLOW ? 8 : 1];
+    __shared__ int qrow[MIX ? 8 : 1];
     const int b = blockIdx.y;
     if (b >= plan[0]) return;
     const int* e = plan + 1 + (size_t)b * PLAN_STRIDE;
@@ -185,6 +191,7 @@ __device__ __forceinline__ void seg_scan_workgroup(const void* __restrict__ bank
     const long long x0 = (long long)blockIdx.x * SEG_ROWS;
     if (x0 >= n) return;
     if (threadIdx.x < 8) qidx[threadIdx.x] = threadIdx.x < nq ? e[2 + threadIdx.x] : 0;
+    if (MIX && threadIdx.x < 8) qrow[threadIdx.x] = threadIdx.x < nq ? e[2 + threadIdx.x] / mix_j : 0;
     // (the body's first barrier orders qidx before its use)
     const long long row0 = x0 + (long long)(threadIdx.x >> 6) * MS_ROWS_PER_WAVE;
     if (ALLOW) {
@@ -211,10 +218,10 @@ __device__ __forceinline__ void seg_scan_workgroup(const void* __restrict__ bank
         }
     }
     const unsigned char* lab = ALLOW ? al.label : nullptr;
-    if (nq == 1) seg_scan_body<1, BF16, ALLKEYS, ALLOW>(bank, query, qidx, nq, lo, n, row0, D, qs, wbest, partial, pstride, eff, lab);
-    else if (nq == 2) seg_scan_body<2, BF16, ALLKEYS, ALLOW>(bank, query, qidx, nq, lo, n, row0, D, qs, wbest, partial, pstride, eff, lab);
-    else if (nq <= 4) seg_scan_body<4, BF16, ALLKEYS, ALLOW>(bank, query, qidx, nq, lo, n, row0, D, qs, wbest, partial, pstride, eff, lab);
-    else seg_scan_body<8, BF16, ALLKEYS, ALLOW>(bank, query, qidx, nq, lo, n, row0, D, qs, wbest, partial, pstride, eff, lab);
+    if (nq == 1) seg_scan_body<1, BF16, ALLKEYS, ALLOW, MIX>(bank, query, qidx, nq, lo, n, row0, D, qs, wbest, partial, pstride, eff, lab, qrow);
+    else if (nq == 2) seg_scan_body<2, BF16, ALLKEYS, ALLOW, MIX>(bank, query, qidx, nq, lo, n, row0, D, qs, wbest, partial, pstride, eff, lab, qrow);
+    else if (nq <= 4) seg_scan_body<4, BF16, ALLKEYS, ALLOW, MIX>(bank, query, qidx, nq, lo, n, row0, D, qs, wbest, partial, pstride, eff, lab, qrow);
+    else seg_scan_body<8, BF16, ALLKEYS, ALLOW, MIX>(bank, query, qidx, nq, lo, n, row0, D, qs, wbest, partial, pstride, eff, lab, qrow);
 }
 
 // applied[q] of the finish / blend kernels: 1 constrained, 0 nothing asked, -1 the segment has no row of the asked labels (fell back)
@@ -240,6 +247,57 @@ __device__ __forceinline__ float seg_direct_dist2(const void* __restrict__ bank,
     if ((tid & 63) == 0) red[tid >> 6] = a;
     __syncthreads();
     return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// One finish workgroup (mocha_match_seg_finish, match_segmented.hip): query q's partial minima -> local row, global row (segment start +
+// local row) and the direct-form distance; an id outside the table (or an empty slot): -1 / global row 0 / +inf.
+// MIX (match_seg_mix.hip): q is a pseudo-query, its query row q / mix_j; MIX = false ignores mix_j.
+template <bool BF16, bool PAIRS, bool MIX = false>
+__device__ __forceinline__ void seg_finish_workgroup(const unsigned long long* __restrict__ partial, int pstride, const int32_t* __restrict__ seg, int S,
+                                                     const int* __restrict__ seg_start, const void* __restrict__ bank, const float* __restrict__ query,
+                                                     int D, int32_t* __restrict__ idx, int32_t* __restrict__ gidx, float* __restrict__ dist,
+                                                     const unsigned long long* __restrict__ allow, const unsigned long long* __restrict__ any,
+                                                     int32_t* __restrict__ applied, int mix_j = 1) {
+    __shared__ unsigned long long kred[256];
+    __shared__ float red[4];
+    const int q = blockIdx.x, tid = threadIdx.x;
+    const int s = seg[q];
+    bool none = s < 0 || s >= S;
+    long long lo = 0, n = 0;
+    if (!none) {
+        seg_extent<PAIRS>(seg_start, s, lo, n);
+        if (PAIRS) none = n == 0;
+    }
+    if (none) {                                   // an id outside the table (or an empty slot): no match; the decoder reads row 0
+        if (tid == 0) {
+            if (idx) idx[q] = -1;
+            if (gidx) gidx[q] = 0;
+            if (dist) dist[q] = __builtin_inff();
+            if (applied) applied[q] = 0;
+        }
+        return;
+    }
+    const int nch = (int)((n + SEG_ROWS - 1) / SEG_ROWS);
+    const unsigned long long* pq = partial + (size_t)q * pstride;
+    unsigned long long k = ~0ull;
+    for (int i = tid; i < nch; i += 256) k = pq[i] < k ? pq[i] : k;
+    kred[tid] = k;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) kred[tid] = kred[tid + o] < kred[tid] ? kred[tid + o] : kred[tid];
+        __syncthreads();
+    }
+    unsigned local = (unsigned)(kred[0] & 0xffffffffull);
+    local = (long long)local < n ? local : 0u;     // (a NaN-only segment: the scan still wrote in-segment rows)
+    const size_t row = (size_t)(lo + local);
+    if (tid == 0) {
+        if (idx) idx[q] = (int32_t)local;
+        if (gidx) gidx[q] = (int32_t)row;
+        if (applied) applied[q] = seg_allow_applied(allow[q], any[s]);
+    }
+    if (!dist) return;
+    const float d2 = seg_direct_dist2<BF16>(bank, query + (size_t)(MIX ? q / mix_j : q) * D, row, D, red);
+    if (tid == 0) dist[q] = sqrtf(d2);
 }
 
 }  // namespace mocha

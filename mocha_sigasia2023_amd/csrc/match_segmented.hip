@@ -32,6 +32,9 @@
 // A resident bank (launch_match_segmented with slot_table, kernels.h): the PAIRS = true instances of the scan and finish kernels read the
 // segment as a {first row, rows} pair of a slot table instead of seg_start[s], seg_start[s + 1]; rows = 0 (an empty slot) is an invalid id.
 // The plan kernel is the same (it only needs S).  The PAIRS = false instances are the kernels as they were.
+//
+// Character mixing (match_seg_mix.hip): the MIX form of the scan body and of the finish body (seg_finish_workgroup, match_seg_body.h) runs
+// over (window, component) pseudo-queries that share their window's query row; the kernels here instantiate the MIX = false form.
 #include "kernels.h"
 #include "match_seg_body.h"
 
@@ -100,7 +103,8 @@ __global__ __launch_bounds__(256) void mocha_match_seg_scan_allow(const void* __
     seg_scan_workgroup<BF16, false, true, PAIRS>(bank, query, plan, seg_start, D, partial, (int)gridDim.x, al);
 }
 
-// allow / any / applied: the constrained match's masks and its per-query report (all null for the plain match)
+// allow / any / applied: the constrained match's masks and its per-query report (all null for the plain match); the body is
+// seg_finish_workgroup (match_seg_body.h), shared with the mixing matcher's finish
 // PAIRS (a resident bank's slot table): an empty slot is an invalid id
 template <bool BF16, bool PAIRS = false>
 __global__ __launch_bounds__(256) void mocha_match_seg_finish(const unsigned long long* __restrict__ partial, int pstride, const int32_t* __restrict__ seg, int S,
@@ -108,46 +112,7 @@ __global__ __launch_bounds__(256) void mocha_match_seg_finish(const unsigned lon
                                                               int32_t* __restrict__ idx, int32_t* __restrict__ gidx, float* __restrict__ dist,
                                                               const unsigned long long* __restrict__ allow, const unsigned long long* __restrict__ any,
                                                               int32_t* __restrict__ applied) {
-    __shared__ unsigned long long kred[256];
-    __shared__ float red[4];
-    const int q = blockIdx.x, tid = threadIdx.x;
-    const int s = seg[q];
-    bool none = s < 0 || s >= S;
-    long long lo = 0, n = 0;
-    if (!none) {
-        seg_extent<PAIRS>(seg_start, s, lo, n);
-        if (PAIRS) none = n == 0;
-    }
-    if (none) {                                   // an id outside the table (or an empty slot): no match; the decoder reads row 0
-        if (tid == 0) {
-            if (idx) idx[q] = -1;
-            if (gidx) gidx[q] = 0;
-            if (dist) dist[q] = __builtin_inff();
-            if (applied) applied[q] = 0;
-        }
-        return;
-    }
-    const int nch = (int)((n + SEG_ROWS - 1) / SEG_ROWS);
-    const unsigned long long* pq = partial + (size_t)q * pstride;
-    unsigned long long k = ~0ull;
-    for (int i = tid; i < nch; i += 256) k = pq[i] < k ? pq[i] : k;
-    kred[tid] = k;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) kred[tid] = kred[tid + o] < kred[tid] ? kred[tid + o] : kred[tid];
-        __syncthreads();
-    }
-    unsigned local = (unsigned)(kred[0] & 0xffffffffull);
-    local = (long long)local < n ? local : 0u;     // (a NaN-only segment: the scan still wrote in-segment rows)
-    const size_t row = (size_t)(lo + local);
-    if (tid == 0) {
-        if (idx) idx[q] = (int32_t)local;
-        if (gidx) gidx[q] = (int32_t)row;
-        if (applied) applied[q] = seg_allow_applied(allow[q], any[s]);
-    }
-    if (!dist) return;
-    const float d2 = seg_direct_dist2<BF16>(bank, query + (size_t)q * D, row, D, red);
-    if (tid == 0) dist[q] = sqrtf(d2);
+    seg_finish_workgroup<BF16, PAIRS>(partial, pstride, seg, S, seg_start, bank, query, D, idx, gidx, dist, allow, any, applied);
 }
 
 size_t match_seg_scratch_words(int Q, int64_t max_rows) {       // partial minima of Q queries against segments of up to max_rows rows

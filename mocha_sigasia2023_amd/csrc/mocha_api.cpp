@@ -115,6 +115,14 @@ struct SetScratch {
     // above and nowhere else, i.e. only by mocha_bank_set_segments, which moves the generation for the new bank anyway: BUF_PLAIN, so
     // that the generation counts what it counted before this buffer existed
     DeviceBuffer<unsigned long long> seg_keys;
+    // the mixing matcher's scratch (match_seg_mix.hip) for 16 windows x 4 components: partial minima and plan of the 64 pseudo-queries,
+    // effective ids / rows, normalised weights / distances, and 16 zero ids (the live mix step's push takes them: its gate is then "the
+    // ring is full").  Reserved with seg_keys and nowhere else, BUF_PLAIN for the same reason
+    DeviceBuffer<unsigned long long> mix_partial;
+    DeviceBuffer<int> mix_plan;
+    DeviceBuffer<int32_t> mix_i;
+    DeviceBuffer<float> mix_f;
+    DeviceBuffer<int32_t> mix_zero{BUF_ZEROED};
     const float* amax_enc_of = nullptr; float* amax_enc = nullptr;     // encoder output pointer -> its slot
     const float* amax_dec_of = nullptr; float* amax_dec = nullptr;     // decoder output pointer -> its slot
     const float* amax_tok_of = nullptr; float* amax_tok = nullptr;     // embedding output pointer -> its slot
@@ -182,6 +190,23 @@ struct AllowArg {
     const unsigned long long* allow = nullptr;
     int32_t* applied = nullptr;
     AllowArg at(size_t q0) const { return AllowArg{allow + q0, applied ? applied + q0 : nullptr}; }
+};
+
+// The mix of a segmented call (match_seg_mix.hip): per window J component ids and J x 6 body-part weights (device), and where the (windows,
+// J) local rows / distances and the (windows, J, 6) normalised weights go (each may be null).  gate / valid: the live steps' (per window).
+struct MixArg {
+    const int32_t* ids = nullptr;
+    const float* weights = nullptr;
+    int J = 0;
+    int32_t* idx = nullptr;
+    float* dist = nullptr;
+    float* wnorm = nullptr;
+    const int32_t* gate = nullptr;
+    int32_t* valid = nullptr;
+    MixArg at(size_t q0) const {
+        return MixArg{ids + q0 * J, weights + q0 * J * 6, J, idx ? idx + q0 * J : nullptr, dist ? dist + q0 * J : nullptr,
+                      wnorm ? wnorm + q0 * J * 6 : nullptr, gate ? gate + q0 : nullptr, valid ? valid + q0 : nullptr};
+    }
 };
 
 }  // namespace
@@ -342,7 +367,11 @@ struct mocha_ctx {
         const void* allow[2] = {};
         // mocha_live_step_ours_grouped only: the characters' weight-bank slots (read by every replay)
         const void* cvae_of = nullptr;
+        // the mix steps only: components per window, and the weights / normalised-weight pointers (the ids are `seg`, the (windows, J)
+        // rows `idx`); ids and weights are read by every replay
+        int mix_j = 0; const void* mix[2] = {};
         bool operator==(const StepKey& o) const {
+            if (mix_j != o.mix_j || mix[0] != o.mix[0] || mix[1] != o.mix[1]) return false;
             if (!(x == o.x && mean == o.mean && sd == o.sd && y == o.y && idx == o.idx && seg == o.seg && windows == o.windows && raw == o.raw))
                 return false;
             for (int i = 0; i < 17; ++i) if (live[i] != o.live[i]) return false;
@@ -373,7 +402,8 @@ struct mocha_ctx {
       live_inert_step,                                // mocha_live_step_inert, hard or soft (workspace set 0)
       live_raw_step[3],                               // mocha_live_step_raw: hard, soft, inertialized (workspace set 0)
       seg_allow_step, live_allow_step, live_raw_allow_step,      // mocha_step_graph_segmented_allow, mocha_live_step_allow, mocha_live_step_raw_allow
-      ours_grouped_step;                              // mocha_live_step_ours_grouped (workspace set 0)
+      ours_grouped_step,                              // mocha_live_step_ours_grouped (workspace set 0)
+      mix_step, live_mix_step, live_raw_mix_step;     // mocha_step_graph_mix_segmented, mocha_live_step_mix, mocha_live_step_raw_mix (workspace set 0)
     hipStream_t cap_stream = nullptr;                 // capture happens on this internal stream (the caller's may be the null stream)
     ncclComm_t comm = nullptr; int comm_rank = 0, comm_size = 1;      // mocha_comm_init
     DeviceBuffer<long long> bcast_hdr;                                  // device: {entries, bf16?} header of mocha_bank_broadcast
@@ -1366,6 +1396,11 @@ int ensure_seg_scratch(mocha_ctx* c, int set) {
     int rc = reserve(c, c->sets[set].seg_partial, match_seg_scratch_words(c->seg_q, c->bank.seg_max_rows));
     if (!rc) rc = reserve(c, c->sets[set].seg_plan, seg_plan_ints(c->seg_q, S));
     if (!rc) rc = reserve(c, c->sets[set].seg_keys, match_seg_keys_words(c->bank.seg_max_rows));
+    if (!rc) rc = reserve(c, c->sets[set].mix_partial, match_seg_scratch_words(SEG_MIX_Q * SEG_MIX_MAX_J, c->bank.seg_max_rows));
+    if (!rc) rc = reserve(c, c->sets[set].mix_plan, seg_plan_ints(SEG_MIX_Q * SEG_MIX_MAX_J, S));
+    if (!rc) rc = reserve(c, c->sets[set].mix_i, seg_mix_scratch_ints());
+    if (!rc) rc = reserve(c, c->sets[set].mix_f, seg_mix_scratch_floats());
+    if (!rc) rc = reserve(c, c->sets[set].mix_zero, (size_t)SEG_MIX_Q);
     return rc;
 }
 
@@ -1429,6 +1464,31 @@ int seg_topk(mocha_ctx* c, const float* q, int Q, const int32_t* seg, int k, flo
            launch_match_seg_topk(bank, b16 ? 1 : 0, q, seg, Q, c->bank.seg_dev.p, S, c->bank.seg_max_rows, D, c->sets[set].seg_keys.p,
                                  c->sets[set].seg_plan.p, c->bank.enc, k, temperature, idx0, idx_k, dist_k, w_k, out, s, al ? &sa : nullptr,
                                  c->bank.resident ? 1 : 0));
+    return 0;
+}
+
+// The mixing matcher (match_seg_mix.hip): every window's present components matched in their own characters, the weights normalised per
+// body part, and out (Q,90,256, or null) = the part-wise blend of the matched entries' encoded rows.  q as for seg_match.  The windows
+// are walked SEG_MIX_Q at a time through the mix scratch of the current workspace set; nothing allocates or synchronises.
+int seg_mix(mocha_ctx* c, const float* q, int Q, const MixArg& mx, float* out, hipStream_t s) {
+    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    const int set = c->cur, S = c->bank.segments();
+    const int D = 90 * 256;
+    SetScratch& st = c->sets[set];
+    if (!st.mix_partial.p || !st.mix_plan.p || !st.mix_i.p || !st.mix_f.p)
+        return fail(c, MOCHA_ERR_STATE, "workspace set %d has no segmented-match scratch: call %s after changing the workspaces", set,
+                    c->bank.resident ? "mocha_reserve" : "mocha_bank_set_segments");
+    const bool b16 = c->bank.is_bf16;
+    const void* bank = b16 ? (const void*)c->bank.bf16.p : (const void*)c->bank.cnt;
+    for (int q0 = 0; q0 < Q; q0 += SEG_MIX_Q) {
+        const int n = std::min(SEG_MIX_Q, Q - q0);
+        const MixArg m = mx.at((size_t)q0);
+        LAUNCH(c, s, b16 ? "mocha_match_seg_scan_mix<bf16>" : "mocha_match_seg_scan_mix<f32>", "match.mix", 3.0 * n * m.J * c->bank.seg_max_rows * D,
+               (double)n * m.J * c->bank.seg_max_rows * D * (b16 ? 2.0 : 4.0) + 4.0 * n * (m.J + 2.0) * D,
+               launch_match_seg_mix(bank, b16 ? 1 : 0, q + (size_t)q0 * D, m.ids, m.weights, n, m.J, c->bank.seg_dev.p, S, c->bank.seg_max_rows, D,
+                                    st.mix_partial.p, st.mix_plan.p, st.mix_i.p, st.mix_f.p, c->bank.enc, m.gate, m.valid, m.idx, m.dist, m.wnorm,
+                                    out ? out + (size_t)q0 * D : nullptr, s, c->bank.resident ? 1 : 0));
+    }
     return 0;
 }
 
@@ -1501,7 +1561,8 @@ void mocha_destroy(mocha_ctx* c) {
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     for (auto* g : {&c->step[0], &c->step[1], &c->step[2], &c->seg_step, &c->live_step, &c->ours_step, &c->soft_step, &c->live_soft_step,
                     &c->live_inert_step, &c->live_raw_step[0], &c->live_raw_step[1], &c->live_raw_step[2], &c->seg_allow_step,
-                    &c->live_allow_step, &c->live_raw_allow_step, &c->ours_grouped_step}) {
+                    &c->live_allow_step, &c->live_raw_allow_step, &c->ours_grouped_step, &c->mix_step,
+                    &c->live_mix_step, &c->live_raw_mix_step}) {
         if (g->exec) (void)hipGraphExecDestroy(g->exec);
         if (g->graph) (void)hipGraphDestroy(g->graph);
     }
@@ -2435,6 +2496,100 @@ int mocha_step_graph_soft_segmented(mocha_ctx* c, const float* X, int S_w, const
     }
     // the ids are read by the captured kernels on every replay: new ids in `seg` are not part of the key; k and the temperature are
     return step_replay(c, c->soft_step, key, (hipStream_t)stream, body);
+}
+
+// ------------------------------------------------------------------------------------------- character mixing, multi-character bank
+// A window characterized by up to MOCHA_MIX_MAX (character, six body-part weights) components: each present component is matched exactly in
+// its own character, and the decoder runs on the part-wise weighted blend of the matched entries (the literal flow, as the soft calls).
+// The matcher is match_seg_mix.hip; ids and weights are device data every launch and replay reads.
+static_assert(MOCHA_MIX_MAX == SEG_MIX_MAX_J, "the header's component limit is the kernel's");
+static int mix_args(mocha_ctx* c, const char* what, int J) {
+    if (J < 1 || J > MOCHA_MIX_MAX) return fail(c, MOCHA_ERR_ARG, "%s: 1 <= J <= %d components", what, MOCHA_MIX_MAX);
+    return 0;
+}
+
+// embed -> encoder -> cnt, z-score (bf16 bank: centred queries) -> the mixing matcher's blend into the "sel" workspace -> literal decoder
+// on the blend -> to_mot.  mx.idx / mx.wnorm may be null.  The caller checked J.
+static int characterize_mix_impl(mocha_ctx* c, const float* src_X, int B, const MixArg& mx, const float* cnt_mean, const float* cnt_std, float* Y,
+                                 bool raw, void* stream) {
+    int rc = ready(c, B); if (rc) return rc;
+    if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
+    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (B == 0) return 0;
+    if (!cnt_mean || !cnt_std || !src_X || !Y || !mx.ids || !mx.weights) return fail(c, MOCHA_ERR_ARG, "null argument");
+    const size_t ys = (size_t)60 * c->cfg.V * c->cfg.C_in;
+    const size_t xs = raw ? (size_t)60 * (c->cfg.V + 1) * c->cfg.C_in : ys;
+    return for_chunks(c, B, (hipStream_t)stream, [&](int b0, int b, hipStream_t s) -> int {
+        int r;
+        if ((r = run_embed(c, src_X + b0 * xs, b, WS(c, "x5"), true, s, raw))) return r;
+        if ((r = run_encoder(c, WS(c, "x5"), b, WS(c, "enc_s"), s))) return r;
+        InormExtra ex = IEXW(c, s);
+        if (c->bank.is_bf16) { ex.centre = c->bank.center.p; ex.zc = WS(c, "qc"); }
+        LAUNCH(c, s, "mocha_instnorm", "mvn", 0.0, b * 90.0 * 256 * 4 * (c->bank.is_bf16 ? 3.0 : 2.0), launch_instnorm(WS(c, "enc_s"), nullptr, nullptr, cnt_mean, cnt_std, WS(c, "qnm"), b, 90, s, &ex));
+        if ((r = seg_mix(c, WS(c, c->bank.is_bf16 ? "qc" : "qnm"), b, mx.at((size_t)b0), WS(c, "sel"), s))) return r;
+        if ((r = run_decoder(c, WS(c, "enc_s"), WS(c, "sel"), b, WS(c, "dec"), s))) return r;
+        return run_to_mot(c, WS(c, "dec"), b, Y + b0 * ys, s, raw);
+    });
+}
+
+int mocha_match_mix_segmented(mocha_ctx* c, const float* query_nm, int Q, const int32_t* ids, const float* weights, int J, int32_t* idx,
+                              float* dist, float* wnorm, float* out, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    int rc = mix_args(c, "match_mix_segmented", J); if (rc) return rc;
+    if ((rc = ready(c, 0))) return rc;
+    if (!query_nm || !ids || !weights || !idx || Q < 0) return fail(c, MOCHA_ERR_ARG, "bad match_mix_segmented arguments");
+    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (Q == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int D = 90 * 256;
+    c->cur = 0;
+    const MixArg mx{ids, weights, J, idx, dist, wnorm, nullptr, nullptr};
+    if (!c->bank.is_bf16) return seg_mix(c, query_nm, Q, mx, out, s);
+    // the bf16 copy holds bf16(b - centroid of the union): centred queries, as many at a time as the centred-query buffer holds
+    const int per = (int)std::min<size_t>((size_t)c->seg_q, c->sets[0].match_qc.n / D);
+    for (int q0 = 0; q0 < Q; q0 += per) {
+        const int n = std::min(per, Q - q0);
+        LAUNCH(c, s, "mocha_sub_rows", "match.center", 0.0, 8.0 * n * D, launch_sub_rows(query_nm + (size_t)q0 * D, c->bank.center.p, c->sets[0].match_qc.p, n, D, s));
+        if ((rc = seg_mix(c, c->sets[0].match_qc.p, n, mx.at((size_t)q0), out ? out + (size_t)q0 * D : nullptr, s))) return rc;
+    }
+    return 0;
+}
+
+int mocha_characterize_mix_segmented(mocha_ctx* c, const float* src_X, int B, const int32_t* ids, const float* weights, int J,
+                                     const float* cnt_mean, const float* cnt_std, float* Y, int32_t* idx, float* wnorm, int raw, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    int rc = mix_args(c, "characterize_mix_segmented", J); if (rc) return rc;
+    if (B > 0 && (!ids || !weights)) return fail(c, MOCHA_ERR_ARG, "characterize_mix_segmented: null argument");
+    const MixArg mx{ids, weights, J, idx, nullptr, wnorm, nullptr, nullptr};
+    return characterize_mix_impl(c, src_X, B, mx, cnt_mean, cnt_std, Y, raw != 0, stream);
+}
+
+int mocha_step_graph_mix_segmented(mocha_ctx* c, const float* X, int S_w, const int32_t* ids, const float* weights, int J, const float* cnt_mean,
+                                   const float* cnt_std, float* Y, int32_t* idx, float* wnorm, int raw, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    int rc = mix_args(c, "step_graph_mix_segmented", J); if (rc) return rc;
+    if (S_w < 1 || S_w > 16) return fail(c, MOCHA_ERR_ARG, "step_graph_mix_segmented: 1 <= S_w <= 16 windows");
+    if ((rc = ready(c, S_w))) return rc;
+    if (!X || !ids || !weights || !cnt_mean || !cnt_std || !Y || !idx || !wnorm) return fail(c, MOCHA_ERR_ARG, "null argument");
+    if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
+    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    mocha_ctx::StepKey key; key.x = X; key.mean = cnt_mean; key.sd = cnt_std; key.y = Y; key.idx = idx; key.seg = ids; key.windows = S_w;
+    key.raw = raw != 0; key.mix_j = J; key.mix[0] = weights; key.mix[1] = wnorm;
+    const MixArg mx{ids, weights, J, idx, nullptr, wnorm, nullptr, nullptr};
+    auto body = [&](hipStream_t cs) -> int {
+        c->lane = 0;
+        const int r = characterize_mix_impl(c, X, S_w, mx, cnt_mean, cnt_std, Y, raw != 0, cs);
+        c->cur = 0;
+        return r;
+    };
+    const auto& g = c->mix_step;
+    if (!(g.exec && g.key == key && g.generation == c->generation)) {
+        // Before a capture: the step once, eagerly, so that whatever its kernels make on first use - the plane GEMMs' weight images, the
+        // float64 weights of the literal decoder's style MLP - exists; it writes what the replay then writes again.
+        if ((rc = body((hipStream_t)stream))) return rc;
+    }
+    // ids and weights are read by the captured kernels on every replay: their contents are not part of the key; J is
+    return step_replay(c, c->mix_step, key, (hipStream_t)stream, body);
 }
 
 // ------------------------------------------------------------------------------------------- action-constrained matching
@@ -3506,7 +3661,7 @@ static int live_step_impl(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, i
                           const int32_t* seg, const float* cnt_mean, const float* cnt_std, double* pos, double* rot, double* ik_rot, double* bvh_pos,
                           double* bvh_euler, int32_t* idx, int32_t* valid, int k, float temperature, int32_t* idx_k, float* w_k, void* stream,
                           void* inert = nullptr, const mocha_inert_cfg* icfg = nullptr, const IngestParams* ing = nullptr,
-                          const mocha_ingest_cfg* ing_cfg = nullptr, const AllowArg* al = nullptr) {
+                          const mocha_ingest_cfg* ing_cfg = nullptr, const AllowArg* al = nullptr, const MixArg* mx = nullptr) {
     if (streams < 1 || streams > 16) return fail(c, MOCHA_ERR_ARG, "live_step: 1 <= streams <= 16");
     if (!live || !Yrot || !Ypos || !Yvel || !Yang || !src_rvel || !src_rang || !src_speed || !contact || !seg || !cnt_mean || !cnt_std || !pos ||
         !rot || !ik_rot || !idx || !valid || (!bvh_pos) != (!bvh_euler))
@@ -3516,6 +3671,9 @@ static int live_step_impl(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, i
     if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set_segments first");
     if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
     if (al && !c->bank.labelled) return fail(c, MOCHA_ERR_STATE, "no action labels: call mocha_bank_set_labels first");
+    if (mx && !c->sets[0].mix_zero.p)
+        return fail(c, MOCHA_ERR_STATE, "workspace set 0 has no segmented-match scratch: call %s after changing the workspaces",
+                    c->bank.resident ? "mocha_reserve" : "mocha_bank_set_segments");
     mocha_post_cfg d;
     if (!cfg) { mocha_post_cfg_default(&d); cfg = &d; }
     PostParams p{};
@@ -3543,8 +3701,16 @@ static int live_step_impl(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, i
     const int J = c->cfg.V + 1, V = c->cfg.V;
 
     // the segmented characterize of the S staging windows with the ids in eff: hard, or soft with column 0 of idx_k in idx
+    // the mix steps: the mix characterize of the S windows, gated by the push (eff >= 0: the ring is full and a frame came); with the
+    // step's outputs (ix non-null) the matcher also rewrites valid - a stream none of whose components is present sits the step out
     auto characterize = [&](int32_t* ix, int32_t* ixk, float* wk, hipStream_t cs) -> int {
         c->lane = 0;
+        if (mx) {
+            const MixArg m{mx->ids, mx->weights, mx->J, ix, nullptr, wk, eff, ix ? valid : nullptr};
+            const int r = characterize_mix_impl(c, xraw, streams, m, cnt_mean, cnt_std, ystage, true, cs);
+            c->cur = 0;
+            return r;
+        }
         const int r = k > 0 ? characterize_soft_impl(c, xraw, streams, eff, k, temperature, cnt_mean, cnt_std, ystage, ix, ixk, wk, true, cs, al)
                             : characterize_impl(c, xraw, streams, cnt_mean, cnt_std, ystage, ix, cs, true, eff, al);
         c->cur = 0;
@@ -3557,8 +3723,10 @@ static int live_step_impl(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, i
             LAUNCH(c, cs, "mocha_live_ingest", "live.ingest", 0.0, (double)streams * (V * 7.0 * 4 + J * 13.0 * 4 + 40.0 * 4 * 8 + J * 16.0 * 13 * 8),
                    launch_live_ingest(*ing, streams, cs));
         LAUNCH(c, cs, "mocha_live_push", "live.push", streams * 60.0 * J * 150, streams * (60.0 * J * (13 + 15) + J * 26.0) * 4,
-               launch_live_push(ring, Yrot, Ypos, Yvel, Yang, seg, c->bone_parents.p, xraw, eff, valid, streams, J, cs, ing ? ing->have : nullptr,
-                                c->bank.resident ? c->bank.seg_dev.p : nullptr, c->bank.resident ? c->bank.segments() : 0));
+               launch_live_push(ring, Yrot, Ypos, Yvel, Yang, mx ? c->sets[0].mix_zero.p : seg, c->bone_parents.p, xraw, eff, valid, streams, J, cs,
+                                ing ? ing->have : nullptr, c->bank.resident && !mx ? c->bank.seg_dev.p : nullptr,
+                                c->bank.resident && !mx ? c->bank.segments() : 0));
+        // (a mix step's push takes zero ids and no slot table: its eff is the gate alone; which characters are loaded is the matcher's to read)
         const int r = characterize(idx, idx_k, w_k, cs);
         if (r) return r;
         LAUNCH(c, cs, "mocha_pose_heads", "live.heads", 0.0, streams * (60.0 * 12 + V * 28.0 * 4), launch_pose_heads(ystage, heads, speed, streams, c->cfg.T, V, cs));
@@ -3583,7 +3751,8 @@ static int live_step_impl(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, i
     if (inert) { key.inert = inert; key.inert_halflife = icfg->halflife; key.inert_dt = icfg->dt; }
     if (ing) { key.ingest[0] = ing->state; key.ingest[1] = ing->rot; key.ingest[2] = ing->pos; key.icfg = *ing_cfg; }
     if (al) { key.allow[0] = al->allow; key.allow[1] = al->applied; }
-    mocha_ctx::StepGraph& g = al ? (ing ? c->live_raw_allow_step : c->live_allow_step)
+    if (mx) { key.mix_j = mx->J; key.mix[0] = mx->weights; key.mix[1] = w_k; }
+    mocha_ctx::StepGraph& g = mx ? (ing ? c->live_raw_mix_step : c->live_mix_step) : al ? (ing ? c->live_raw_allow_step : c->live_allow_step)
                                  : ing ? c->live_raw_step[inert ? 2 : k > 0 ? 1 : 0] : inert ? c->live_inert_step : k > 0 ? c->live_soft_step : c->live_step;
     if (!(g.exec && g.key == key && g.generation == c->generation)) {
         // Before a capture: one eager characterize of the staging windows with every id -1 (no bank row is matched, no state of the
@@ -3857,7 +4026,7 @@ static int live_step_raw_impl(mocha_ctx* c, const char* who, const mocha_post_cf
                               int streams, const float* rot, const float* pos, const int32_t* seg, const float* cnt_mean, const float* cnt_std, int k,
                               float temperature, double* pos_out, double* rot_out, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx,
                               int32_t* valid, int32_t* idx_k, float* w_k, void* stream, void* inert, const mocha_inert_cfg* icfg,
-                              const AllowArg* al) {
+                              const AllowArg* al, const MixArg* mx = nullptr) {
     if (!c) return MOCHA_ERR_ARG;
     if (streams < 1 || streams > 16) return fail(c, MOCHA_ERR_ARG, "%s: 1 <= streams <= 16", who);
     if (!ingest || !rot || !pos) return fail(c, MOCHA_ERR_ARG, "%s: null argument", who);
@@ -3881,7 +4050,7 @@ static int live_step_raw_impl(mocha_ctx* c, const char* who, const mocha_post_cf
     p.contact = reinterpret_cast<unsigned char*>(base + l.contact); p.have = reinterpret_cast<int32_t*>(base + l.have);
     return live_step_impl(c, cfg, live, streams, p.Yrot, p.Ypos, p.Yvel, p.Yang, p.src_rvel, p.src_rang, p.src_speed, p.contact, seg, cnt_mean,
                           cnt_std, pos_out, rot_out, ik_rot, bvh_pos, bvh_euler, idx, valid, k, k > 0 ? temperature : 0.f, k > 0 ? idx_k : nullptr,
-                          k > 0 ? w_k : nullptr, stream, inert, inert ? &ic : nullptr, &p, icfg_in, al);
+                          k > 0 || mx ? w_k : nullptr, stream, inert, inert ? &ic : nullptr, &p, icfg_in, al, mx);
 }
 
 int mocha_live_step_raw(mocha_ctx* c, const mocha_post_cfg* cfg, const mocha_ingest_cfg* icfg_in, void* live, void* ingest, int streams,
@@ -3902,6 +4071,32 @@ int mocha_live_step_raw_allow(mocha_ctx* c, const mocha_post_cfg* cfg, const moc
     const AllowArg al{reinterpret_cast<const unsigned long long*>(allow), applied};
     return live_step_raw_impl(c, "live_step_raw_allow", cfg, icfg_in, live, ingest, streams, rot, pos, seg, cnt_mean, cnt_std, k, temperature, pos_out,
                               rot_out, ik_rot, bvh_pos, bvh_euler, idx, valid, idx_k, w_k, stream, inert, icfg, &al);
+}
+
+// The live step with the mix characterize in the place of the hard one (ids (S,J), weights (S,J,6): device data every replay reads; idx
+// (S,J), wnorm (S,J,6)).  mocha_live_step_mix: frames already featurised; mocha_live_step_raw_mix: raw mocap frames through the front end.
+int mocha_live_step_mix(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos, const float* Yvel,
+                        const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed, const unsigned char* contact,
+                        const int32_t* ids, const float* weights, int J, const float* cnt_mean, const float* cnt_std, double* pos, double* rot,
+                        double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx, int32_t* valid, float* wnorm, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    int rc = mix_args(c, "live_step_mix", J); if (rc) return rc;
+    if (!ids || !weights || !idx || !wnorm) return fail(c, MOCHA_ERR_ARG, "live_step_mix: null argument");
+    const MixArg mx{ids, weights, J, idx, nullptr, wnorm, nullptr, nullptr};
+    return live_step_impl(c, cfg, live, streams, Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, ids, cnt_mean, cnt_std, pos, rot,
+                          ik_rot, bvh_pos, bvh_euler, idx, valid, 0, 0.f, nullptr, wnorm, stream, nullptr, nullptr, nullptr, nullptr, nullptr, &mx);
+}
+
+int mocha_live_step_raw_mix(mocha_ctx* c, const mocha_post_cfg* cfg, const mocha_ingest_cfg* icfg_in, void* live, void* ingest, int streams,
+                            const float* rot, const float* pos, const int32_t* ids, const float* weights, int J, const float* cnt_mean,
+                            const float* cnt_std, double* pos_out, double* rot_out, double* ik_rot, double* bvh_pos, double* bvh_euler,
+                            int32_t* idx, int32_t* valid, float* wnorm, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    int rc = mix_args(c, "live_step_raw_mix", J); if (rc) return rc;
+    if (!ids || !weights || !idx || !wnorm) return fail(c, MOCHA_ERR_ARG, "live_step_raw_mix: null argument");
+    const MixArg mx{ids, weights, J, idx, nullptr, wnorm, nullptr, nullptr};
+    return live_step_raw_impl(c, "live_step_raw_mix", cfg, icfg_in, live, ingest, streams, rot, pos, ids, cnt_mean, cnt_std, 0, 0.f, pos_out,
+                              rot_out, ik_rot, bvh_pos, bvh_euler, idx, valid, nullptr, wnorm, stream, nullptr, nullptr, nullptr, &mx);
 }
 
 }  // extern "C"

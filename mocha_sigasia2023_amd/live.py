@@ -19,7 +19,7 @@ import torch
 
 from . import _C
 from .generator import DIM, NTOK, _dev_f32, _ptr, _stream
-from .multi_character import MultiCharacterBank, soft_params
+from .multi_character import MIX_PARTS, MultiCharacterBank, _refuse_with_mix, mix_count, mix_tensors, soft_params
 from .ingest import IngestConfig, reset_ingest
 from .postprocess import PostProcessor
 
@@ -39,12 +39,22 @@ class LiveSession:
     ((S,) int64 on the device; ``push(..., allow=)``, ``set_allow`` or written in place) and is matched among its character's entries of those actions
     (``mocha_live_step_allow`` / ``mocha_live_step_raw_allow``); the outputs gain ``applied`` (S,): 1 constrained, 0 nothing asked or
     warming, -1 the character has no such entry and the whole character was searched.  With zero masks the session gives the plain
-    session's bits.  A change of the allowed actions is not inertialized (``soft=`` softens it)."""
+    session's bits.  A change of the allowed actions is not inertialized (``soft=`` softens it).
+    ``mix=J`` (1 .. 4): every stream is characterized by up to J (character, six body-part weights) components instead of one character
+    (``mocha_live_step_mix`` / ``mocha_live_step_raw_mix``): ``mix_ids`` (S,J) int32 and ``mix_weights`` (S,J,6) float32 are device tensors
+    the captured step reads - ``push(..., mix=(ids, weights))``, ``set_mix`` or written in place, e.g. a weight ramp for a cross-fade or a
+    0/1 mask per body part for a splice; ``characters`` is not used.  ``idx`` is then (S,J) and the outputs gain ``weight`` (S,J,6), the
+    weights normalised per body part.  A stream none of whose components is present (no loaded character with a usable weight) sits the
+    step out as a warming one.  Combines with ``raw=``; not with ``soft``, ``inertial`` or ``constrained``."""
 
     def __init__(self, bank: MultiCharacterBank, cnt_mean, cnt_std, streams: int = 1, post: Optional[PostProcessor] = None, bvh: bool = True,
-                 soft=None, inertial: Optional[float] = None, raw=None, constrained: bool = False):
+                 soft=None, inertial: Optional[float] = None, raw=None, constrained: bool = False, mix=None):
         if not 1 <= int(streams) <= 16:
             raise ValueError("streams must be 1..16")
+        self.mix = None
+        if mix is not None:
+            self.mix = mix_count(mix, "LiveSession")
+            _refuse_with_mix("LiveSession", soft=soft is not None, inertial=inertial is not None, constrained=constrained)
         self.bank, self.model = bank, bank.model
         m, dev = self.model, bank.model.device
         if post is not None and post.model is not m:
@@ -104,6 +114,11 @@ class LiveSession:
                 raise RuntimeError("LiveSession: constrained=True needs a bank with action labels (MultiCharacterBank(labels=))")
             self.allow = torch.zeros((S,), dtype=torch.int64, device=dev)
             self.out["applied"] = torch.zeros((S,), dtype=torch.int32, device=dev)
+        if self.mix is not None:
+            self.mix_ids = torch.full((S, self.mix), -1, dtype=torch.int32, device=dev)
+            self.mix_weights = torch.zeros((S, self.mix, MIX_PARTS), dtype=torch.float32, device=dev)
+            self.out["idx"] = torch.full((S, self.mix), -1, dtype=torch.int32, device=dev)
+            self.out["weight"] = torch.zeros((S, self.mix, MIX_PARTS), dtype=torch.float32, device=dev)
         bank._ensure()
 
     @property
@@ -125,7 +140,21 @@ class LiveSession:
             raise RuntimeError("LiveSession: allow= needs a session created with constrained=True")
         self.allow.copy_(self.bank._allow(allow, self.streams, "LiveSession"), non_blocking=True)
 
-    def push(self, Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, characters=None, allow=None):
+    def set_mix(self, mix):
+        """New (ids, weights) for the next step (mix sessions; see ``mix_tensors``), copied into ``mix_ids`` / ``mix_weights``.
+        ``push(..., mix=)`` calls this; before ``push_raw`` call it yourself (or write the two tensors in place)."""
+        if self.mix is None:
+            raise RuntimeError("LiveSession: mix= needs a session created with mix=J")
+        mids, mw = mix_tensors(mix, self.streams, self.model.device, "LiveSession", self.mix)
+        self.mix_ids.copy_(mids, non_blocking=True)
+        self.mix_weights.copy_(mw, non_blocking=True)
+
+    def _set_characters(self, characters):
+        if self.mix is not None:
+            raise ValueError("LiveSession: a mix session takes mix=, not characters")
+        self.ids.copy_(self.bank._ids(characters, self.streams), non_blocking=True)
+
+    def push(self, Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, characters=None, allow=None, mix=None):
         """The new frame of every stream: Yrot (S,V+1,4) (w,x,y,z), Ypos / Yvel / Yang (S,V+1,3), root bone first; src_rvel / src_rang
         (S,3), src_speed (S,), contact (S,n_contact) of that frame [, characters: one id per stream; default: the ids already set].
         Returns the session's own device tensors - pos (S,V+1,3), rot / ik_rot (S,V+1,4), (bvh_pos / bvh_euler (S,V,3)), idx (S,) the
@@ -134,8 +163,10 @@ class LiveSession:
         an int mask, an iterable of labels or None each, or one int for all; default: the masks already set."""
         if allow is not None:
             self.set_allow(allow)
+        if mix is not None:
+            self.set_mix(mix)
         if characters is not None:
-            self.ids.copy_(self.bank._ids(characters, self.streams), non_blocking=True)
+            self._set_characters(characters)
         for a, buf, name in ((Yrot, self.rot, "Yrot"), (Ypos, self.pos, "Ypos"), (Yvel, self.vel, "Yvel"), (Yang, self.ang, "Yang"),
                              (src_rvel, self.rvel, "src_rvel"), (src_rang, self.rang, "src_rang")):
             self._frame(a, buf, name)
@@ -153,7 +184,7 @@ class LiveSession:
         if self.raw is None:
             raise RuntimeError("LiveSession.push_raw: the session was not created with raw=")
         if characters is not None:
-            self.ids.copy_(self.bank._ids(characters, self.streams), non_blocking=True)
+            self._set_characters(characters)
         self._frame(rot, self.raw_rot, "rot")
         self._frame(pos, self.raw_pos, "pos")
         return self.replay_raw()
@@ -165,6 +196,13 @@ class LiveSession:
         self.bank._ensure()
         o = self.out
         k, t = self.soft if self.soft is not None else (0, 0.0)
+        if self.mix is not None:
+            self.model._ctx.call("mocha_live_step_raw_mix", C.byref(self.post.cfg), C.byref(self.rcfg), _ptr(self.live), _ptr(self.ingest),
+                                 self.streams, _ptr(self.raw_rot), _ptr(self.raw_pos), _ptr(self.mix_ids), _ptr(self.mix_weights), self.mix,
+                                 _ptr(self.mean), _ptr(self.std), _ptr(o["pos"]), _ptr(o["rot"]), _ptr(o["ik_rot"]),
+                                 _ptr(o["bvh_pos"]) if self.bvh else None, _ptr(o["bvh_euler"]) if self.bvh else None, _ptr(o["idx"]),
+                                 _ptr(o["valid"]), _ptr(o["weight"]), _stream())
+            return o
         if self.constrained:
             self.model._ctx.call("mocha_live_step_raw_allow", C.byref(self.post.cfg), C.byref(self.rcfg), _ptr(self.live), _ptr(self.ingest),
                                  self.streams, _ptr(self.raw_rot), _ptr(self.raw_pos), _ptr(self.ids), _ptr(self.mean), _ptr(self.std), k, t,
@@ -185,6 +223,13 @@ class LiveSession:
         """The step on what the fixed buffers hold (a producer on the device may have written them in place)."""
         self.bank._ensure()
         o = self.out
+        if self.mix is not None:
+            self.model._ctx.call("mocha_live_step_mix", C.byref(self.post.cfg), _ptr(self.live), self.streams, _ptr(self.rot), _ptr(self.pos),
+                                 _ptr(self.vel), _ptr(self.ang), _ptr(self.rvel), _ptr(self.rang), _ptr(self.speed), _ptr(self.contact),
+                                 _ptr(self.mix_ids), _ptr(self.mix_weights), self.mix, _ptr(self.mean), _ptr(self.std), _ptr(o["pos"]),
+                                 _ptr(o["rot"]), _ptr(o["ik_rot"]), _ptr(o["bvh_pos"]) if self.bvh else None,
+                                 _ptr(o["bvh_euler"]) if self.bvh else None, _ptr(o["idx"]), _ptr(o["valid"]), _ptr(o["weight"]), _stream())
+            return o
         if self.constrained:
             k, t = self.soft if self.soft is not None else (0, 0.0)
             self.model._ctx.call("mocha_live_step_allow", C.byref(self.post.cfg), _ptr(self.live), self.streams, _ptr(self.rot), _ptr(self.pos),
@@ -298,7 +343,7 @@ class LiveOursSession(LiveSession):
 
     def __init__(self, bank: MultiCharacterBank, cnt_mean, cnt_std, cvae_state_dict, src_cnt_mean, src_cnt_std, cha_encoded_mean,
                  cha_encoded_std, streams: int = 1, post: Optional[PostProcessor] = None, bvh: bool = True, noise: str = "device",
-                 seed: int = 0, soft=None, inertial=None, raw=None, constrained: bool = False, cvaes=None, cvae_of=None):
+                 seed: int = 0, soft=None, inertial=None, raw=None, constrained: bool = False, cvaes=None, cvae_of=None, mix=None):
         if cvaes is None and cvae_of is not None:
             raise ValueError("LiveOursSession: cvae_of needs cvaes=CVAEBank(...)")
         if cvaes is not None:
@@ -316,6 +361,8 @@ class LiveOursSession(LiveSession):
             raise ValueError("LiveOursSession: inertial does not apply - the branch seeds again on a character switch and keeps its own chain state")
         if soft is not None:
             raise ValueError("LiveOursSession: soft matching does not apply - the decoder already reads a sampled character feature")
+        if mix is not None:
+            raise ValueError("LiveOursSession: mix= is not supported - the CVAE branch samples one character's feature per stream")
         if noise not in self.NOISE:
             raise ValueError(f"noise must be one of {sorted(self.NOISE)}")
         super().__init__(bank, cnt_mean, cnt_std, streams=streams, post=post, bvh=bvh)

@@ -10,6 +10,11 @@ Action-constrained matching: a bank built with ``labels`` (one action label 0 ..
 accepts ``allow=`` in ``query`` / ``characterize`` / ``step``: per query a 64-bit mask of admissible actions (``action_mask``).  The match is
 then the exact nearest entry among that character's entries of those actions; a zero mask asks for nothing, and a mask naming no action
 the character has falls back to the whole character (``applied``: 1 / 0 / -1).
+
+Character mixing: ``mix=(ids, weights)`` in ``query`` / ``characterize`` (and ``MultiStreamCharacterizer(mix=J)``, ``LiveSession(mix=J)``)
+characterizes a window by up to 4 components - a character id and six body-part weights each (``skeleton.PART_NAMES``) - instead of one
+character: every present component is matched exactly in its own character and the decoder reads the part-wise weighted blend of the
+matched entries (``mix_tensors``).  It does not combine with ``soft`` or ``allow``.
 """
 from __future__ import annotations
 
@@ -23,6 +28,7 @@ from .generator import DIM, NTOK, Generator, _dev_f32, _ptr, _stream
 
 _BORROW, _BF16, _NO_DEC_CACHE = 1, 2, 4          # mocha_bank_set flags (include/mocha_hip.h)
 SOFT_MAX_K = 8                                   # MOCHA_SOFT_MAX_K
+MIX_MAX, MIX_PARTS = 4, 6                        # MOCHA_MIX_MAX, MOCHA_MIX_PARTS
 
 
 def action_mask(actions) -> int:
@@ -90,6 +96,60 @@ def soft_params(soft, who: str):
     return int(k), float(t)
 
 
+def mix_count(J, who: str) -> int:
+    """``mix=J`` of a streamer or a session checked on the host -> int J in 1 .. MIX_MAX."""
+    if isinstance(J, (bool, np.bool_)) or not isinstance(J, (int, np.integer)) or not 1 <= int(J) <= MIX_MAX:
+        raise ValueError(f"{who}: mix must be an integer in 1 .. {MIX_MAX} (components per window)")
+    return int(J)
+
+
+def mix_tensors(mix, n: int, device, who: str, J: Optional[int] = None):
+    """``mix=(ids, weights)`` -> (ids (n,J) int32, weights (n,J,6) float32) on the device, as the mix calls read them.  ids: (n,J), or
+    (J,) for every window; weights: (n,J,6), (n,J) (one weight per component, broadcast over the six body parts), or (J,6) / (J,) for
+    every window.  1 <= J <= 4 (``J``: the count a streamer or session was built for).  The VALUES are the device's to judge: an id that
+    names no loaded character and a weight that is not in (0, FLT_MAX] simply do not take part."""
+    try:
+        ids, w = mix
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: mix must be an (ids, weights) pair") from None
+    if not isinstance(ids, torch.Tensor):
+        a = np.asarray(ids)
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"{who}: mix ids must be integers, got {a.dtype}")
+        ids = torch.from_numpy(np.ascontiguousarray(a.astype(np.int32)))
+    elif ids.dtype.is_floating_point or ids.dtype == torch.bool:
+        raise ValueError(f"{who}: mix ids must be integers, got {ids.dtype}")
+    if ids.dim() == 1:
+        ids = ids[None].expand(n, -1)
+    if ids.dim() != 2 or ids.shape[0] != n:
+        raise ValueError(f"{who}: mix ids must have shape ({n}, J) or (J,), got {tuple(ids.shape)}")
+    Jn = int(ids.shape[1])
+    if not 1 <= Jn <= MIX_MAX:
+        raise ValueError(f"{who}: {Jn} mix components; 1 .. {MIX_MAX} are served")
+    if J is not None and Jn != J:
+        raise ValueError(f"{who}: {Jn} mix components where mix={J} was asked")
+    if not isinstance(w, torch.Tensor):
+        w = torch.from_numpy(np.ascontiguousarray(np.asarray(w, dtype=np.float32)))
+    shape = tuple(w.shape)
+    if shape == (n, Jn, MIX_PARTS):
+        pass
+    elif shape == (n, Jn):
+        w = w[:, :, None].expand(n, Jn, MIX_PARTS)
+    elif shape == (Jn, MIX_PARTS):
+        w = w[None].expand(n, Jn, MIX_PARTS)
+    elif shape == (Jn,):
+        w = w[None, :, None].expand(n, Jn, MIX_PARTS)
+    else:
+        raise ValueError(f"{who}: mix weights must have shape ({n}, {Jn}, 6), ({n}, {Jn}), ({Jn}, 6) or ({Jn},), got {shape}")
+    return ids.to(device=device, dtype=torch.int32).contiguous(), w.to(device=device, dtype=torch.float32).contiguous()
+
+
+def _refuse_with_mix(who: str, **others):
+    for name, v in others.items():
+        if v:
+            raise ValueError(f"{who}: mix= does not combine with {name} (mix is hard matching per component)")
+
+
 class _SegmentedBank:
     """What ``MultiCharacterBank`` and ``ResidentCharacterBank`` share: the segmented calls on the model's current bank.  A subclass
     provides ``model``, ``S`` (ids are 0 .. S - 1), ``labels`` (None: no action labels) and ``_ensure()``."""
@@ -119,15 +179,31 @@ class _SegmentedBank:
             raise ValueError(f"characters: {ids.shape[0]} ids for {n} queries")
         return ids
 
-    def query(self, query_nm, characters, k: int = 1, allow=None, return_applied: bool = False):
+    def query(self, query_nm, characters=None, k: int = 1, allow=None, return_applied: bool = False, mix=None):
         """Exact 1-NN of each query within its character's rows -> (dist (Q,1), idx (Q,1)), idx local to that character's bank.
         ``k > 1`` (up to 8): the k nearest rows of that character, nearest first, ties to the lower row -> (dist (Q,k), idx (Q,k)); a
         character with fewer than k rows gives idx -1 / dist +inf in the columns it cannot fill (``mocha_match_topk_segmented``).
         ``allow`` (see ``allow_masks``): the match among the rows of each query's admissible actions (``mocha_match_segmented_allow``);
-        fewer than k such rows leave -1 / +inf; ``return_applied`` adds applied (Q,) int32: 1 constrained, 0 nothing asked, -1 fell back."""
+        fewer than k such rows leave -1 / +inf; ``return_applied`` adds applied (Q,) int32: 1 constrained, 0 nothing asked, -1 fell back.
+        ``mix=(ids, weights)`` (see ``mix_tensors``; no ``characters``): every query matched in each of its J components' characters
+        (``mocha_match_mix_segmented``) -> (dist (Q,J), idx (Q,J), weight (Q,J,6) normalised per body part, out (Q,90,256) the part-wise
+        blend of the matched entries' encoded features); a component that is not present has -1 / +inf / 0."""
         self._ensure()
         q = _dev_f32(query_nm, self.model.device, None, "query").reshape(-1, NTOK * DIM)
         Q = q.shape[0]
+        if mix is not None:
+            _refuse_with_mix("query", characters=characters is not None, **{"k > 1": k != 1}, allow=allow is not None, return_applied=return_applied)
+            mids, mw = mix_tensors(mix, Q, q.device, "query")
+            J = mids.shape[1]
+            idx = torch.empty((Q, J), dtype=torch.int32, device=q.device)
+            dist = torch.empty((Q, J), dtype=torch.float32, device=q.device)
+            wn = torch.empty((Q, J, MIX_PARTS), dtype=torch.float32, device=q.device)
+            out = torch.empty((Q, NTOK, DIM), dtype=torch.float32, device=q.device)
+            self.model._ctx.call("mocha_match_mix_segmented", _ptr(q), Q, _ptr(mids), _ptr(mw), J, _ptr(idx), _ptr(dist), _ptr(wn), _ptr(out),
+                                 _stream())
+            return dist, idx, wn, out
+        if characters is None:
+            raise ValueError("query: characters (one id per query) or mix= is needed")
         ids = self._ids(characters, Q)
         if int(k) != k or not 1 <= int(k) <= SOFT_MAX_K:
             raise ValueError(f"query: k must be an integer in 1 .. {SOFT_MAX_K}")
@@ -153,16 +229,32 @@ class _SegmentedBank:
         self.model._ctx.call("mocha_match_segmented", _ptr(q), Q, _ptr(ids), _ptr(idx), _ptr(dist), _stream())
         return dist[:, None], idx[:, None]
 
-    def characterize(self, src_X, characters, cnt_mean, cnt_std, return_index: bool = False, raw: bool = False, soft=None, allow=None):
+    def characterize(self, src_X, characters, cnt_mean, cnt_std, return_index: bool = False, raw: bool = False, soft=None, allow=None,
+                     mix=None):
         """``allow`` (see ``allow_masks``): every window matched among its character's entries of the admissible actions
         (``mocha_characterize_segmented_allow``); with ``return_index`` the outputs gain applied (B,) int32 at the end.
         ``ContextBank.characterize`` with every window matched against its own character: Y (B,T,V,C) [, idx (B,) local rows].
         ``soft=(k, temperature)``: the decoder reads the softmax(-dist / temperature)-weighted blend of the window's k nearest entries
-        instead of the nearest one (``mocha_characterize_soft_segmented``); with ``return_index`` -> (Y, idx_k (B,k), weight (B,k))."""
+        instead of the nearest one (``mocha_characterize_soft_segmented``); with ``return_index`` -> (Y, idx_k (B,k), weight (B,k)).
+        ``mix=(ids, weights)`` (see ``mix_tensors``; ``characters`` is then None): the decoder reads the part-wise weighted blend of the
+        entries matched in each component's character (``mocha_characterize_mix_segmented``); with ``return_index`` -> (Y, idx (B,J),
+        weight (B,J,6)).  It does not combine with ``soft`` or ``allow``."""
         self._ensure()
         m = self.model
         X = m._xraw(src_X, "src_X_raw") if raw else m._x(src_X, "src_X")
         B = X.shape[0]
+        if mix is not None:
+            _refuse_with_mix("characterize", characters=characters is not None, soft=soft is not None, allow=allow is not None)
+            mids, mw = mix_tensors(mix, B, m.device, "characterize")
+            J = mids.shape[1]
+            mean = _dev_f32(cnt_mean, m.device, (NTOK, DIM), "cnt_mean")
+            std = _dev_f32(cnt_std, m.device, (NTOK, DIM), "cnt_std")
+            Y = torch.empty((B, m.cfg["nframes"], m.V, m.cfg["mot_in_dim"]), dtype=torch.float32, device=m.device)
+            idx = torch.empty((B, J), dtype=torch.int32, device=m.device)
+            wn = torch.empty((B, J, MIX_PARTS), dtype=torch.float32, device=m.device)
+            m._ctx.call("mocha_characterize_mix_segmented", _ptr(X), B, _ptr(mids), _ptr(mw), J, _ptr(mean), _ptr(std), _ptr(Y), _ptr(idx),
+                        _ptr(wn), 1 if raw else 0, _stream())
+            return (Y, idx, wn) if return_index else Y
         ids = self._ids(characters, B)
         mean = _dev_f32(cnt_mean, m.device, (NTOK, DIM), "cnt_mean")
         std = _dev_f32(cnt_std, m.device, (NTOK, DIM), "cnt_std")
@@ -395,11 +487,19 @@ class MultiStreamCharacterizer:
     (Y, idx_k (streams,k), weight (streams,k)).
     ``constrained=True``: the action-constrained step (``mocha_step_graph_segmented_allow``); ``allow`` is then a (streams,) int64 device
     tensor of allow masks the graph reads - a producer may write it in place, new masks do not re-capture - and ``step`` returns
-    ``applied`` (streams,) int32 as its last output."""
+    ``applied`` (streams,) int32 as its last output.
+    ``mix=J`` (1 .. 4): the mix characterize (``mocha_step_graph_mix_segmented``); ``mix_ids`` (streams,J) int32 and ``mix_weights``
+    (streams,J,6) float32 are device tensors the graph reads - a producer may write them in place, new ids or weights do not re-capture -
+    and ``step`` returns (Y, idx (streams,J), weight (streams,J,6)).  It does not combine with ``soft`` or ``constrained``."""
 
-    def __init__(self, bank: MultiCharacterBank, cnt_mean, cnt_std, streams: int, raw: bool = False, soft=None, constrained: bool = False):
+    def __init__(self, bank: MultiCharacterBank, cnt_mean, cnt_std, streams: int, raw: bool = False, soft=None, constrained: bool = False,
+                 mix=None):
         if not 1 <= streams <= 16:
             raise ValueError("streams must be 1..16")
+        self.mix = None
+        if mix is not None:
+            self.mix = mix_count(mix, "MultiStreamCharacterizer")
+            _refuse_with_mix("MultiStreamCharacterizer", soft=soft is not None, constrained=constrained)
         self.bank, self.model = bank, bank.model
         m = self.model
         self.streams = int(streams)
@@ -422,6 +522,11 @@ class MultiStreamCharacterizer:
                 raise RuntimeError("MultiStreamCharacterizer: constrained=True needs a bank with action labels")
             self.allow = torch.zeros((self.streams,), dtype=torch.int64, device=m.device)
             self.applied = torch.zeros((self.streams,), dtype=torch.int32, device=m.device)
+        if self.mix is not None:
+            self.mix_ids = torch.full((self.streams, self.mix), -1, dtype=torch.int32, device=m.device)
+            self.mix_weights = torch.zeros((self.streams, self.mix, MIX_PARTS), dtype=torch.float32, device=m.device)
+            self.mix_idx = torch.full((self.streams, self.mix), -1, dtype=torch.int32, device=m.device)
+            self.weight = torch.zeros((self.streams, self.mix, MIX_PARTS), dtype=torch.float32, device=m.device)
         bank._ensure()
 
     @property
@@ -434,10 +539,27 @@ class MultiStreamCharacterizer:
         """The captured step's own character ids (streams,) int32 on the device: a producer may write them in place and call ``step()``."""
         return self.ids
 
-    def step(self, windows: Optional[torch.Tensor] = None, characters=None, allow=None):
+    def step(self, windows: Optional[torch.Tensor] = None, characters=None, allow=None, mix=None):
         """windows (streams, 60, V, 15) [, characters: one id per stream] -> (Y (streams, 60, V, 15) view, idx (streams,) view); both are
         overwritten by the next step.  Without arguments the windows and ids already in ``input`` / ``characters`` are used.
-        ``allow`` (constrained only): new allow masks, one per stream (see ``allow_masks``), copied into ``self.allow``."""
+        ``allow`` (constrained only): new allow masks, one per stream (see ``allow_masks``), copied into ``self.allow``.
+        ``mix`` (mix=J only): new (ids, weights) (see ``mix_tensors``), copied into ``mix_ids`` / ``mix_weights``."""
+        if mix is not None:
+            if self.mix is None:
+                raise RuntimeError("step: mix= needs MultiStreamCharacterizer(mix=J)")
+            mids, mw = mix_tensors(mix, self.streams, self.model.device, "step", self.mix)
+            self.mix_ids.copy_(mids, non_blocking=True)
+            self.mix_weights.copy_(mw, non_blocking=True)
+        if self.mix is not None:
+            if characters is not None:
+                raise ValueError("step: a mix streamer takes mix=, not characters")
+            if windows is not None:
+                self.x.copy_(windows.reshape(self.x.shape), non_blocking=True)
+            self.bank._ensure()
+            self.model._ctx.call("mocha_step_graph_mix_segmented", _ptr(self.x), self.streams, _ptr(self.mix_ids), _ptr(self.mix_weights),
+                                 self.mix, _ptr(self.mean), _ptr(self.std), _ptr(self.y), _ptr(self.mix_idx), _ptr(self.weight),
+                                 1 if self.raw else 0, _stream())
+            return self.y, self.mix_idx, self.weight
         if allow is not None:
             if not self.constrained:
                 raise RuntimeError("step: allow= needs MultiStreamCharacterizer(constrained=True)")

@@ -53,6 +53,11 @@ LAYOUTS = {
     },
 }
 LAYOUT_ID = {"mocha": 0, "mixamo": 1}
+# the six body parts by name, in the column order of the layout's pool matrix: the order of the per-part weights of a character mix
+PART_NAMES = {
+    "mocha": ("Spine", "LeftLeg", "LeftArm", "Neck", "RightArm", "RightLeg"),
+    "mixamo": ("Spine", "Neck", "LeftArm", "RightArm", "RightLeg", "LeftLeg"),
+}
 
 # body-part graph: star, part 0 linked to parts 1..5 (net/graph.py:207-218), same for all layouts
 BODY_PARENTS = [-1, 0, 0, 0, 0, 0]

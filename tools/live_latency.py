@@ -27,6 +27,10 @@ mocha_profile_start / stop, during which the step runs eagerly.
     python tools/live_latency.py --raw 2 [--out profiles/r13/live_raw_step.json]
         the plain live step and the raw step (LiveSession(raw=L) = mocha_live_step_raw: one more launch, mocha_live_ingest, in front of
         the ring push), alternating replay by replay in one process, S = 1 and S = 8, both past their warm-up
+    python tools/live_latency.py --mix 1,2,4 [--out profiles/r20/live_mix_step.json]
+        character mixing: the plain live step, the soft live step at k = J and the mix step (LiveSession(mix=J) = mocha_live_step_mix)
+        with every stream's J components on J different characters, alternating replay by replay in one process, S = 1, 8 and 16, for
+        every listed J; then the mix step's own launches one at a time (profile hooks, eager)
 """
 import argparse
 import json
@@ -225,6 +229,55 @@ def soft(a, dev, model, mb, mean, std, clip, per, J):
     return res
 
 
+def mix(a, dev, model, mb, mean, std, clip, per, J):
+    """--mix J[,J..]: the plain live step, the soft live step at k = J (temperature 2) and the mix step with J components per stream on J
+    different characters, alternating in one process.  The soft step has the same literal decoder and a J-row blend; the mix step adds
+    the scans of J - 1 further characters and one prep launch."""
+    from mocha_sigasia2023_amd import LiveSession
+    res = {"bank": "8 characters x 2048 rows, fp32, segmented", "layout": "mocha (24 joints)",
+           "timing": "HIP events around single graph replays; (a) live step, (b) soft live step with k = J, temperature 2, (c) mix live step "
+                     "with J components per stream on J different characters, alternating; clocks untouched", "streams": {}}
+    for S in (1, 8, 16):
+        ids = torch.tensor([(k * 3) % 8 for k in range(S)], dtype=torch.int32)
+        res["streams"][str(S)] = {}
+        for Jm in a.mix:
+            hard = LiveSession(mb, mean, std, streams=S)
+            sft = LiveSession(mb, mean, std, streams=S, soft=(Jm, 2.0))
+            mx = LiveSession(mb, mean, std, streams=S, mix=Jm)
+            mx.set_mix((np.array([[(k * 3 + 2 * j) % 8 for j in range(Jm)] for k in range(S)], np.int32),
+                        np.array([[(j + 1.0) for j in range(Jm)]] * S, np.float32)))
+            frame = [0]
+
+            def push():
+                f = frame[0] % 644; frame[0] += 1
+                for sess in (hard, sft, mx):
+                    sess.rot.copy_(clip[0][f]); sess.pos.copy_(clip[1][f]); sess.vel.copy_(clip[2][f]); sess.ang.copy_(clip[3][f])
+                    sess.rvel.copy_(per[0][f]); sess.rang.copy_(per[1][f]); sess.speed.copy_(per[2][f]); sess.contact.copy_(per[3][f])
+            for sess in (hard, sft):
+                sess.characters.copy_(ids)
+            for _ in range(max(a.warmup, 70)):
+                push(); hard.replay(); sft.replay(); mx.replay()
+            torch.cuda.synchronize()
+            assert bool((mx.out["valid"] == 1).all()) and bool((mx.out["idx"] >= 0).all()) and bool((sft.out["idx_k"] >= 0).all())
+            ta, tb, tc = [], [], []
+            for _ in range(a.reps):
+                push(); torch.cuda.synchronize()
+                ta.append(event_ms(hard.replay, 1)[0]); tb.append(event_ms(sft.replay, 1)[0]); tc.append(event_ms(mx.replay, 1)[0])
+            e = {"a_live_step": pct(np.asarray(ta)), "b_live_step_soft": pct(np.asarray(tb)), "c_live_step_mix": pct(np.asarray(tc))}
+            e["c_minus_a_p50_ms"] = e["c_live_step_mix"]["p50_ms"] - e["a_live_step"]["p50_ms"]
+            e["c_minus_b_p50_ms"] = e["c_live_step_mix"]["p50_ms"] - e["b_live_step_soft"]["p50_ms"]
+            n = 100                                         # the mix step's kernels, one launch at a time (eager while profiling)
+            model.profile_start()
+            for _ in range(n):
+                mx.replay()
+            prof = model.profile_stop()
+            e["mix_sites_us"] = {k: 1e3 * v["ms"] / n for k, v in prof["sites"].items() if k.split("|")[0] in ("match.mix", "dec.in_cha", "dec.style")}
+            assert bool(torch.isfinite(mx.out["pos"]).all())
+            res["streams"][str(S)]["J=%d" % Jm] = e
+            del hard, sft, mx
+    return res
+
+
 def constrained(a, dev, model, mb, mean, std, clip, per, J):
     """--constrained: the plain live step and the action-constrained one with zero masks (LiveSession(constrained=True) =
     mocha_live_step_allow: the same launches, the scan reads the masks and one granule word), alternating in one process; then the same
@@ -369,7 +422,14 @@ def main():
     ap.add_argument("--inertial", type=float, default=None, metavar="H", help="inertialized switches: live step / live step with half-life H seconds")
     ap.add_argument("--raw", type=int, default=None, metavar="L", help="raw mocap input: live step / raw live step with L frames of lookahead")
     ap.add_argument("--constrained", action="store_true", help="action-constrained matching: live step / constrained live step with zero masks / one action of 16")
+    ap.add_argument("--mix", default=None, metavar="J[,J..]", help="character mixing: live step / soft live step at k = J / mix live step with J components, S = 1, 8, 16")
     a = ap.parse_args()
+    if a.mix is not None:
+        a.mix = [int(x) for x in a.mix.split(",")]
+        if not a.mix or any(not 1 <= j <= 4 for j in a.mix):
+            raise SystemExit("--mix takes component counts in 1 .. 4, comma-separated")
+        if a.out == ap.get_default("out"):
+            a.out = os.path.join(ROOT, "profiles", "r20", "live_mix_step.json")
     if a.constrained and a.out == ap.get_default("out"):
         a.out = os.path.join(ROOT, "profiles", "r15", "live_allow_step.json")
     if a.raw is not None and a.out == ap.get_default("out"):
@@ -403,6 +463,8 @@ def main():
     per = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (rvel, rang, np.linalg.norm(hipvel, axis=-1).mean(-1).astype(np.float32), contact)]
     res = {"bank": "8 characters x 2048 rows, fp32, segmented", "layout": "mocha (24 joints)", "timing": "HIP events around single graph replays, live and baseline alternating",
            "streams": {}}
+    if a.mix is not None:
+        return write_out(a, mix(a, dev, model, mb, mean, std, clip, per, J))
     if a.constrained:
         return write_out(a, constrained(a, dev, model, mb, mean, std, clip, per, J))
     if a.raw is not None:
