@@ -209,6 +209,41 @@ struct MixArg {
     }
 };
 
+// The windows of a characterize: X (B windows, raw = with the root bone and un-normalised) -> Y
+struct SegWindows {
+    const float* X = nullptr; int B = 0; const float *cnt_mean = nullptr, *cnt_std = nullptr; float* Y = nullptr; bool raw = false;
+};
+
+// How a window of the segmented characterize gets its character feature (characterize_segmented_impl).  mix: the mixing matcher on mix->ids
+// (`seg` unused).  Otherwise `seg` names the window's character, and k == 0 is the hard matcher (idx0: the local rows), k >= 1 the soft
+// one (idx0: column 0, idx_k / w_k (B,k)); allow: its action constraint.  Every output may be null.
+struct SegSelect {
+    const int32_t* seg = nullptr;
+    int k = 0; float temperature = 0.f;
+    const AllowArg* allow = nullptr;
+    const MixArg* mix = nullptr;
+    int32_t *idx0 = nullptr, *idx_k = nullptr; float* w_k = nullptr;
+    const int32_t* ids() const { return mix ? mix->ids : seg; }
+    bool literal() const { return mix || k > 0; }      // the decoder runs on the blend in the "sel" workspace, not through the bank's rows
+};
+
+// The two configurations a captured live step carries by value, compared member by member (mocha_post_cfg has tail padding: no memcmp).
+// A member added to either struct changes its size: the assertion then stops the build until the comparison next to it knows the member.
+static_assert(sizeof(mocha_post_cfg) == 72, "mocha_post_cfg changed: update same_cfg(mocha_post_cfg) below, then this size");
+bool same_cfg(const mocha_post_cfg& a, const mocha_post_cfg& b) {
+    for (int i = 0; i < 4; ++i) if (a.contact_bones[i] != b.contact_bones[i]) return false;
+    return a.dt == b.dt && a.ik_max_length_buffer == b.ik_max_length_buffer && a.ik_foot_height == b.ik_foot_height &&
+           a.ik_unlock_radius == b.ik_unlock_radius && a.ik_blending_halflife == b.ik_blending_halflife &&
+           a.ik_enabled == b.ik_enabled && a.n_contact == b.n_contact && a.blend_enabled == b.blend_enabled;
+}
+static_assert(sizeof(mocha_ingest_cfg) == 72, "mocha_ingest_cfg changed: update same_cfg(mocha_ingest_cfg) below, then this size");
+bool same_cfg(const mocha_ingest_cfg& a, const mocha_ingest_cfg& b) {
+    for (int i = 0; i < 3; ++i) if (a.euler_order[i] != b.euler_order[i]) return false;
+    return a.lookahead == b.lookahead && a.rot_format == b.rot_format && a.unit_scale == b.unit_scale && a.fps == b.fps &&
+           a.contact_velocity_threshold == b.contact_velocity_threshold && a.spine == b.spine && a.shoulder_l == b.shoulder_l &&
+           a.shoulder_r == b.shoulder_r && a.upleg_l == b.upleg_l && a.upleg_r == b.upleg_r;
+}
+
 }  // namespace
 
 struct mocha_ctx {
@@ -381,29 +416,25 @@ struct mocha_ctx {
             if (allow[0] != o.allow[0] || allow[1] != o.allow[1]) return false;
             if (cvae_of != o.cvae_of) return false;
             if (inert != o.inert || inert_halflife != o.inert_halflife || inert_dt != o.inert_dt) return false;
-            for (int i = 0; i < 3; ++i) if (ingest[i] != o.ingest[i] || icfg.euler_order[i] != o.icfg.euler_order[i]) return false;
-            if (icfg.lookahead != o.icfg.lookahead || icfg.rot_format != o.icfg.rot_format || icfg.unit_scale != o.icfg.unit_scale ||
-                icfg.fps != o.icfg.fps || icfg.contact_velocity_threshold != o.icfg.contact_velocity_threshold || icfg.spine != o.icfg.spine ||
-                icfg.shoulder_l != o.icfg.shoulder_l || icfg.shoulder_r != o.icfg.shoulder_r || icfg.upleg_l != o.icfg.upleg_l ||
-                icfg.upleg_r != o.icfg.upleg_r)
-                return false;
-            const mocha_post_cfg &a = post, &b = o.post;
-            for (int i = 0; i < 4; ++i) if (a.contact_bones[i] != b.contact_bones[i]) return false;
-            return a.dt == b.dt && a.ik_max_length_buffer == b.ik_max_length_buffer && a.ik_foot_height == b.ik_foot_height &&
-                   a.ik_unlock_radius == b.ik_unlock_radius && a.ik_blending_halflife == b.ik_blending_halflife &&
-                   a.ik_enabled == b.ik_enabled && a.n_contact == b.n_contact && a.blend_enabled == b.blend_enabled;
+            for (int i = 0; i < 3; ++i) if (ingest[i] != o.ingest[i]) return false;
+            return same_cfg(icfg, o.icfg) && same_cfg(post, o.post);
         }
+    };
+    // One captured graph per kind of step: a lane's mocha_step_graph_lane (STEP_LANE + lane, workspace set `lane`), then the steps on
+    // workspace set 0, each named after its entry point
+    enum StepKind {
+        STEP_LANE = 0,
+        STEP_SEG = MAX_SETS, STEP_SEG_SOFT, STEP_SEG_MIX, STEP_SEG_ALLOW,                            // mocha_step_graph_[soft_|mix_]segmented[_allow]
+        STEP_LIVE, STEP_LIVE_SOFT, STEP_LIVE_INERT,                                                  // mocha_live_step, _soft, _inert (hard or soft)
+        STEP_LIVE_RAW, STEP_LIVE_RAW_SOFT, STEP_LIVE_RAW_INERT,                                      // mocha_live_step_raw: hard, soft, inertialized
+        STEP_LIVE_ALLOW, STEP_LIVE_RAW_ALLOW, STEP_LIVE_MIX, STEP_LIVE_RAW_MIX,                      // mocha_live_step[_raw]_allow, mocha_live_step[_raw]_mix
+        STEP_OURS, STEP_OURS_GROUPED,                                                                // mocha_live_step_ours[_grouped]
+        STEP_KINDS
     };
     struct StepGraph {
         hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr;
         StepKey key; int64_t generation = -1;
-    } step[MAX_SETS], seg_step, live_step, ours_step, // seg_step: mocha_step_graph_segmented, live_step: mocha_live_step, ours_step: mocha_live_step_ours (workspace set 0)
-      soft_step, live_soft_step,                      // mocha_step_graph_soft_segmented, mocha_live_step_soft (workspace set 0)
-      live_inert_step,                                // mocha_live_step_inert, hard or soft (workspace set 0)
-      live_raw_step[3],                               // mocha_live_step_raw: hard, soft, inertialized (workspace set 0)
-      seg_allow_step, live_allow_step, live_raw_allow_step,      // mocha_step_graph_segmented_allow, mocha_live_step_allow, mocha_live_step_raw_allow
-      ours_grouped_step,                              // mocha_live_step_ours_grouped (workspace set 0)
-      mix_step, live_mix_step, live_raw_mix_step;     // mocha_step_graph_mix_segmented, mocha_live_step_mix, mocha_live_step_raw_mix (workspace set 0)
+    } steps[STEP_KINDS];
     hipStream_t cap_stream = nullptr;                 // capture happens on this internal stream (the caller's may be the null stream)
     ncclComm_t comm = nullptr; int comm_rank = 0, comm_size = 1;      // mocha_comm_init
     DeviceBuffer<long long> bcast_hdr;                                  // device: {entries, bf16?} header of mocha_bank_broadcast
@@ -415,6 +446,11 @@ struct mocha_ctx {
 };
 
 namespace {
+
+// `g` replays for `key` as it is: no capture needed
+bool step_holds(const mocha_ctx* c, const mocha_ctx::StepGraph& g, const mocha_ctx::StepKey& key) {
+    return g.exec && g.key == key && g.generation == c->generation;
+}
 
 int fail(mocha_ctx* c, int code, const char* fmt, ...) {
     char buf[512];
@@ -1411,6 +1447,12 @@ int refuse_resident(mocha_ctx* c, const char* who) {
     return fail(c, MOCHA_ERR_STATE, "%s: the current bank is a resident bank (mocha_bank_resident_create), which is searched and read per character only", who);
 }
 
+// a segmented matcher finds its scratch missing in workspace set `set`
+int no_seg_scratch(mocha_ctx* c, int set) {
+    return fail(c, MOCHA_ERR_STATE, "workspace set %d has no segmented-match scratch: call %s after changing the workspaces", set,
+                c->bank.resident ? "mocha_reserve" : "mocha_bank_set_segments");
+}
+
 // the kernels' view of a constraint: the caller's masks and report with the current bank's label tables
 SegAllow seg_allow_of(mocha_ctx* c, const AllowArg& a) {
     return SegAllow{a.allow, c->bank.lab_dev.p, c->bank.lab_any.p, c->bank.lab_gran.p, c->bank.lab_gran_start.p, a.applied};
@@ -1425,9 +1467,7 @@ int seg_match(mocha_ctx* c, const float* q, int Q, const int32_t* seg, int32_t* 
     if (al && !c->bank.labelled) return fail(c, MOCHA_ERR_STATE, "no action labels: call mocha_bank_set_labels first");
     const int set = c->cur, S = c->bank.segments();
     const int D = 90 * 256;
-    if (!c->sets[set].seg_partial.p || !c->sets[set].seg_plan.p)
-        return fail(c, MOCHA_ERR_STATE, "workspace set %d has no segmented-match scratch: call %s after changing the workspaces", set,
-                    c->bank.resident ? "mocha_reserve" : "mocha_bank_set_segments");
+    if (!c->sets[set].seg_partial.p || !c->sets[set].seg_plan.p) return no_seg_scratch(c, set);
     const void* bank = c->bank.is_bf16 ? (const void*)c->bank.bf16.p : (const void*)c->bank.cnt;
     for (int q0 = 0; q0 < Q; q0 += c->seg_q) {
         const int n = std::min(c->seg_q, Q - q0);
@@ -1453,9 +1493,7 @@ int seg_topk(mocha_ctx* c, const float* q, int Q, const int32_t* seg, int k, flo
     if (al) sa = seg_allow_of(c, *al);
     const int set = c->cur, S = c->bank.segments();
     const int D = 90 * 256;
-    if (!c->sets[set].seg_keys.p || !c->sets[set].seg_plan.p)
-        return fail(c, MOCHA_ERR_STATE, "workspace set %d has no segmented-match scratch: call %s after changing the workspaces", set,
-                    c->bank.resident ? "mocha_reserve" : "mocha_bank_set_segments");
+    if (!c->sets[set].seg_keys.p || !c->sets[set].seg_plan.p) return no_seg_scratch(c, set);
     const bool b16 = c->bank.is_bf16;
     const void* bank = b16 ? (const void*)c->bank.bf16.p : (const void*)c->bank.cnt;
     const double passes = (Q + SEG_TOPK_Q - 1) / SEG_TOPK_Q;
@@ -1475,9 +1513,7 @@ int seg_mix(mocha_ctx* c, const float* q, int Q, const MixArg& mx, float* out, h
     const int set = c->cur, S = c->bank.segments();
     const int D = 90 * 256;
     SetScratch& st = c->sets[set];
-    if (!st.mix_partial.p || !st.mix_plan.p || !st.mix_i.p || !st.mix_f.p)
-        return fail(c, MOCHA_ERR_STATE, "workspace set %d has no segmented-match scratch: call %s after changing the workspaces", set,
-                    c->bank.resident ? "mocha_reserve" : "mocha_bank_set_segments");
+    if (!st.mix_partial.p || !st.mix_plan.p || !st.mix_i.p || !st.mix_f.p) return no_seg_scratch(c, set);
     const bool b16 = c->bank.is_bf16;
     const void* bank = b16 ? (const void*)c->bank.bf16.p : (const void*)c->bank.cnt;
     for (int q0 = 0; q0 < Q; q0 += SEG_MIX_Q) {
@@ -1488,6 +1524,24 @@ int seg_mix(mocha_ctx* c, const float* q, int Q, const MixArg& mx, float* out, h
                launch_match_seg_mix(bank, b16 ? 1 : 0, q + (size_t)q0 * D, m.ids, m.weights, n, m.J, c->bank.seg_dev.p, S, c->bank.seg_max_rows, D,
                                     st.mix_partial.p, st.mix_plan.p, st.mix_i.p, st.mix_f.p, c->bank.enc, m.gate, m.valid, m.idx, m.dist, m.wnorm,
                                     out ? out + (size_t)q0 * D : nullptr, s, c->bank.resident ? 1 : 0));
+    }
+    return 0;
+}
+
+// fn(q, q0, n) over the Q z-scored queries of a mocha_match_*segmented* call, on workspace set 0, as the matchers above read them: an fp32
+// bank takes them as they are, in one piece; the bf16 copy holds bf16(b - centroid of the union), so its queries are centred, as many at
+// a time as the centred-query buffer holds
+template <class F>
+int for_centred_queries(mocha_ctx* c, const float* query_nm, int Q, hipStream_t s, F&& fn) {
+    const int D = 90 * 256;
+    c->cur = 0;
+    if (!c->bank.is_bf16) return fn(query_nm, 0, Q);
+    const int per = (int)std::min<size_t>((size_t)c->seg_q, c->sets[0].match_qc.n / D);
+    for (int q0 = 0; q0 < Q; q0 += per) {
+        const int n = std::min(per, Q - q0);
+        LAUNCH(c, s, "mocha_sub_rows", "match.center", 0.0, 8.0 * n * D, launch_sub_rows(query_nm + (size_t)q0 * D, c->bank.center.p, c->sets[0].match_qc.p, n, D, s));
+        const int rc = fn(c->sets[0].match_qc.p, q0, n);
+        if (rc) return rc;
     }
     return 0;
 }
@@ -1559,12 +1613,9 @@ void mocha_destroy(mocha_ctx* c) {
     if (c->aux) (void)hipStreamDestroy(c->aux);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    for (auto* g : {&c->step[0], &c->step[1], &c->step[2], &c->seg_step, &c->live_step, &c->ours_step, &c->soft_step, &c->live_soft_step,
-                    &c->live_inert_step, &c->live_raw_step[0], &c->live_raw_step[1], &c->live_raw_step[2], &c->seg_allow_step,
-                    &c->live_allow_step, &c->live_raw_allow_step, &c->ours_grouped_step, &c->mix_step,
-                    &c->live_mix_step, &c->live_raw_mix_step}) {
-        if (g->exec) (void)hipGraphExecDestroy(g->exec);
-        if (g->graph) (void)hipGraphDestroy(g->graph);
+    for (auto& g : c->steps) {
+        if (g.exec) (void)hipGraphExecDestroy(g.exec);
+        if (g.graph) (void)hipGraphDestroy(g.graph);
     }
     if (c->cap_stream) (void)hipStreamDestroy(c->cap_stream);
     if (c->cvb.ev) { (void)hipEventSynchronize(c->cvb.ev); (void)hipEventDestroy(c->cvb.ev); }
@@ -2118,14 +2169,12 @@ int mocha_bank_gather(mocha_ctx* c, const int32_t* idx, int Q, float* out, void*
     return 0;
 }
 
-// seg != null (mocha_characterize_segmented): every window is matched within its own segment of a multi-character bank; idx then receives
-// the local rows and the decoder gathers through the global rows the matcher leaves in the workspace's index buffer
+// The characterize against the bank as ONE set of rows (mocha_characterize, mocha_step_graph)
 static int characterize_impl(mocha_ctx* c, const float* src_X, int B, const float* cnt_mean, const float* cnt_std, float* Y,
-                             int32_t* idx, void* stream, bool raw, const int32_t* seg = nullptr, const AllowArg* al = nullptr) {
+                             int32_t* idx, void* stream, bool raw) {
     int rc = ready(c, B); if (rc) return rc;
-    if (!seg && (rc = refuse_resident(c, "mocha_characterize / mocha_step_graph"))) return rc;
+    if ((rc = refuse_resident(c, "mocha_characterize / mocha_step_graph"))) return rc;
     if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
-    if (seg && !c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
     if (B == 0) return 0;
     if (!cnt_mean || !cnt_std || !src_X || !Y) return fail(c, MOCHA_ERR_ARG, "null argument");
     const size_t ys = (size_t)60 * c->cfg.V * c->cfg.C_in;
@@ -2135,19 +2184,6 @@ static int characterize_impl(mocha_ctx* c, const float* src_X, int B, const floa
         int32_t* ix = idx ? idx + b0 : SET(c).idx_ws.p;
         if ((r = run_embed(c, src_X + b0 * xs, b, WS(c, "x5"), true, s, raw))) return r;
         if ((r = run_encoder(c, WS(c, "x5"), b, WS(c, "enc_s"), s))) return r;
-        if (seg) {
-            // cnt and its z-score (and, bf16 bank, the queries centred on the union's centroid), the segmented matcher, the decoder on the global rows
-            InormExtra ex = IEXW(c, s);
-            if (c->bank.is_bf16) { ex.centre = c->bank.center.p; ex.zc = WS(c, "qc"); }
-            LAUNCH(c, s, "mocha_instnorm", "mvn", 0.0, b * 90.0 * 256 * 4 * (c->bank.is_bf16 ? 3.0 : 2.0), launch_instnorm(WS(c, "enc_s"), nullptr, nullptr, cnt_mean, cnt_std, WS(c, "qnm"), b, 90, s, &ex));
-            int32_t* gx = SET(c).idx_ws.p;
-            AllowArg ab;
-            if (al) ab = al->at(b0);
-            if ((r = seg_match(c, WS(c, c->bank.is_bf16 ? "qc" : "qnm"), b, seg + b0, idx ? idx + b0 : nullptr, gx, nullptr, s, al ? &ab : nullptr))) return r;
-            if ((r = run_decoder(c, WS(c, "enc_s"), nullptr, b, WS(c, "dec"), s, c->bank.enc, gx, c->bank.N,
-                                 c->bank.dec_valid ? c->bank.kin.p : nullptr, c->bank.dec_valid ? c->bank.gb.p : nullptr))) return r;
-            return run_to_mot(c, WS(c, "dec"), b, Y + b0 * ys, s, raw);
-        }
         // cnt, its z-score and - the bank's centroid is known - the matcher's centred queries in one pass
         // (as one bf16 plane where the many-query pass against a bf16 bank will read them: no mocha_center_bf16 launch)
         const bool q16 = c->bank.is_bf16 && b > 8;
@@ -2163,6 +2199,59 @@ static int characterize_impl(mocha_ctx* c, const float* src_X, int B, const floa
                              c->bank.dec_valid ? c->bank.kin.p : nullptr, c->bank.dec_valid ? c->bank.gb.p : nullptr))) return r;
         return run_to_mot(c, WS(c, "dec"), b, Y + b0 * ys, s, raw);
     });
+}
+
+// The segmented characterize, every variant of it: embed -> encoder -> cnt and its z-score (bf16 bank: and the queries centred on the
+// union's centroid) -> the window's character feature as `sel` says -> decoder -> to_mot.  Hard: the matcher leaves the global rows in
+// the workspace's index buffer and the decoder gathers through them, with the bank's per-entry constants.  Soft and mix: the matcher
+// blends into the "sel" workspace and the literal decoder runs on the blend (instance norm and style MLP of the feature per call - the
+// per-entry constants do not apply to a blend).  The caller checked k, the temperature and J.
+static int characterize_segmented_impl(mocha_ctx* c, const SegWindows& w, const SegSelect& sel, void* stream) {
+    int rc = ready(c, w.B); if (rc) return rc;
+    if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
+    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (w.B == 0) return 0;
+    if (!w.cnt_mean || !w.cnt_std || !w.X || !w.Y || !sel.ids() || (sel.mix && !sel.mix->weights)) return fail(c, MOCHA_ERR_ARG, "null argument");
+    const size_t ys = (size_t)60 * c->cfg.V * c->cfg.C_in;
+    const size_t xs = w.raw ? (size_t)60 * (c->cfg.V + 1) * c->cfg.C_in : ys;
+    const bool b16 = c->bank.is_bf16;
+    return for_chunks(c, w.B, (hipStream_t)stream, [&](int b0, int b, hipStream_t s) -> int {
+        int r;
+        if ((r = run_embed(c, w.X + b0 * xs, b, WS(c, "x5"), true, s, w.raw))) return r;
+        if ((r = run_encoder(c, WS(c, "x5"), b, WS(c, "enc_s"), s))) return r;
+        InormExtra ex = IEXW(c, s);
+        if (b16) { ex.centre = c->bank.center.p; ex.zc = WS(c, "qc"); }
+        LAUNCH(c, s, "mocha_instnorm", "mvn", 0.0, b * 90.0 * 256 * 4 * (b16 ? 3.0 : 2.0), launch_instnorm(WS(c, "enc_s"), nullptr, nullptr, w.cnt_mean, w.cnt_std, WS(c, "qnm"), b, 90, s, &ex));
+        const float* q = WS(c, b16 ? "qc" : "qnm");
+        AllowArg ab;
+        if (sel.allow) ab = sel.allow->at(b0);
+        const AllowArg* al = sel.allow ? &ab : nullptr;
+        int32_t* gx = SET(c).idx_ws.p;
+        int32_t* i0 = sel.idx0 ? sel.idx0 + b0 : nullptr;
+        if (sel.mix)
+            r = seg_mix(c, q, b, sel.mix->at((size_t)b0), WS(c, "sel"), s);
+        else if (sel.k > 0)
+            r = seg_topk(c, q, b, sel.seg + b0, sel.k, sel.temperature, i0, sel.idx_k ? sel.idx_k + (size_t)b0 * sel.k : nullptr, nullptr,
+                         sel.w_k ? sel.w_k + (size_t)b0 * sel.k : nullptr, WS(c, "sel"), s, al);
+        else
+            r = seg_match(c, q, b, sel.seg + b0, i0, gx, nullptr, s, al);
+        if (r) return r;
+        if (sel.literal())
+            r = run_decoder(c, WS(c, "enc_s"), WS(c, "sel"), b, WS(c, "dec"), s);
+        else
+            r = run_decoder(c, WS(c, "enc_s"), nullptr, b, WS(c, "dec"), s, c->bank.enc, gx, c->bank.N,
+                            c->bank.dec_valid ? c->bank.kin.p : nullptr, c->bank.dec_valid ? c->bank.gb.p : nullptr);
+        if (r) return r;
+        return run_to_mot(c, WS(c, "dec"), b, w.Y + b0 * ys, s, w.raw);
+    });
+}
+
+// ... on workspace set 0, as the captured steps run it
+static int characterize_segmented_set0(mocha_ctx* c, const SegWindows& w, const SegSelect& sel, hipStream_t s) {
+    c->lane = 0;
+    const int r = characterize_segmented_impl(c, w, sel, s);
+    c->cur = 0;
+    return r;
 }
 
 int mocha_characterize(mocha_ctx* c, const float* src_X, int B, const float* cnt_mean, const float* cnt_std, float* Y,
@@ -2265,8 +2354,7 @@ namespace {
 // stream (mocha_step_graph_lane, mocha_step_graph_segmented).  The caller made sure that nothing inside `body` allocates.
 template <class F>
 int step_replay(mocha_ctx* c, mocha_ctx::StepGraph& g, const mocha_ctx::StepKey& key, hipStream_t s, F&& body) {
-    const bool hit = g.exec && g.key == key && g.generation == c->generation;
-    if (!hit) {
+    if (!step_holds(c, g, key)) {
         if (c->prof_on) return fail(c, MOCHA_ERR_STATE, "mocha_step_graph: stop profiling before capturing");
         if (!c->cap_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking));
         if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
@@ -2287,6 +2375,31 @@ int step_replay(mocha_ctx* c, mocha_ctx::StepGraph& g, const mocha_ctx::StepKey&
     HIPCHK(c, hipGraphLaunch(g.exec, s));
     return 0;
 }
+
+// The captured segmented step of up to 16 windows, every variant (`what` names the entry point in its messages): the shared checks, then
+// graph `kind` replayed, keyed on `key` (the caller filled the variant's own fields) and the windows' pointers.  outputs_ok: the variant's
+// required outputs are there.  Ids, masks and weights are read by the captured kernels on every replay: their contents are not part of
+// the key; k, the temperature and J are.
+int step_segmented(mocha_ctx* c, const char* what, mocha_ctx::StepKind kind, mocha_ctx::StepKey key, const SegWindows& w, const SegSelect& sel,
+                   bool outputs_ok, void* stream) {
+    if (w.B < 1 || w.B > 16) return fail(c, MOCHA_ERR_ARG, "%s: 1 <= S_w <= 16 windows", what);
+    int rc = ready(c, w.B); if (rc) return rc;
+    if (!w.X || !sel.ids() || (sel.mix && !sel.mix->weights) || (sel.allow && !sel.allow->allow) || !w.cnt_mean || !w.cnt_std || !w.Y || !outputs_ok)
+        return fail(c, MOCHA_ERR_ARG, "null argument");
+    if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
+    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (sel.allow && !c->bank.labelled) return fail(c, MOCHA_ERR_STATE, "no action labels: call mocha_bank_set_labels first");
+    key.x = w.X; key.mean = w.cnt_mean; key.sd = w.cnt_std; key.y = w.Y; key.seg = sel.ids(); key.windows = w.B; key.raw = w.raw;
+    mocha_ctx::StepGraph& g = c->steps[kind];
+    auto body = [&](hipStream_t cs) -> int { return characterize_segmented_set0(c, w, sel, cs); };
+    if (sel.literal() && !step_holds(c, g, key)) {
+        // Before a capture: the step once, eagerly, so that whatever its kernels make on first use - the plane GEMMs' weight images, the
+        // float64 weights of the literal decoder's style MLP - exists; it writes what the replay then writes again.  (The hard step is
+        // captured as it comes.)
+        if ((rc = body((hipStream_t)stream))) return rc;
+    }
+    return step_replay(c, g, key, (hipStream_t)stream, body);
+}
 }  // namespace
 
 extern "C" {
@@ -2301,12 +2414,12 @@ int mocha_step_graph_lane(mocha_ctx* c, int lane, const float* X1, const float* 
     if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
     if (c->sets[lane].ws.empty()) return fail(c, MOCHA_ERR_STATE, "lane %d has no workspace", lane);
     mocha_ctx::StepKey key; key.x = X1; key.mean = cnt_mean; key.sd = cnt_std; key.y = Y1; key.idx = idx; key.raw = raw != 0;
-    const auto& g = c->step[lane];
-    if (!(g.exec && g.key == key && g.generation == c->generation)) {
+    mocha_ctx::StepGraph& g = c->steps[mocha_ctx::STEP_LANE + lane];
+    if (!step_holds(c, g, key)) {
         // make sure nothing inside the captured region allocates (scratch for one query against the current bank)
         if ((rc = ensure_match_scratch(c, lane, 8, c->bank, true))) return rc;
     }
-    return step_replay(c, c->step[lane], key, (hipStream_t)stream, [&](hipStream_t cs) -> int {
+    return step_replay(c, g, key, (hipStream_t)stream, [&](hipStream_t cs) -> int {
         c->lane = lane;                                   // the step's kernels use this lane's workspace set and match scratch
         const int r = characterize_impl(c, X1, 1, cnt_mean, cnt_std, Y1, idx, cs, raw != 0);
         c->lane = 0; c->cur = 0;
@@ -2361,84 +2474,37 @@ int mocha_match_segmented(mocha_ctx* c, const float* query_nm, int Q, const int3
     if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
     if (Q == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    const int D = 90 * 256;
-    c->cur = 0;
-    if (!c->bank.is_bf16) return seg_match(c, query_nm, Q, seg, idx, nullptr, dist, s);
-    // the bf16 copy holds bf16(b - centroid of the union): centred queries, as many at a time as the centred-query buffer holds
-    const int per = (int)std::min<size_t>((size_t)c->seg_q, c->sets[0].match_qc.n / D);
-    for (int q0 = 0; q0 < Q; q0 += per) {
-        const int n = std::min(per, Q - q0);
-        LAUNCH(c, s, "mocha_sub_rows", "match.center", 0.0, 8.0 * n * D, launch_sub_rows(query_nm + (size_t)q0 * D, c->bank.center.p, c->sets[0].match_qc.p, n, D, s));
-        if ((rc = seg_match(c, c->sets[0].match_qc.p, n, seg + q0, idx + q0, nullptr, dist ? dist + q0 : nullptr, s))) return rc;
-    }
-    return 0;
+    return for_centred_queries(c, query_nm, Q, s, [&](const float* q, int q0, int n) -> int {
+        return seg_match(c, q, n, seg + q0, idx + q0, nullptr, dist ? dist + q0 : nullptr, s);
+    });
 }
 
 int mocha_characterize_segmented(mocha_ctx* c, const float* src_X, int B, const int32_t* seg, const float* cnt_mean, const float* cnt_std,
                                  float* Y, int32_t* idx, int raw, void* stream) {
     if (!c) return MOCHA_ERR_ARG;
     if (B > 0 && !seg) return fail(c, MOCHA_ERR_ARG, "characterize_segmented: null argument");
-    return characterize_impl(c, src_X, B, cnt_mean, cnt_std, Y, idx, stream, raw != 0, seg);
+    SegSelect sel; sel.seg = seg; sel.idx0 = idx;
+    return characterize_segmented_impl(c, SegWindows{src_X, B, cnt_mean, cnt_std, Y, raw != 0}, sel, stream);
 }
 
 int mocha_step_graph_segmented(mocha_ctx* c, const float* X, int S_w, const int32_t* seg, const float* cnt_mean, const float* cnt_std, float* Y,
                                int32_t* idx, int raw, void* stream) {
     if (!c) return MOCHA_ERR_ARG;
-    if (S_w < 1 || S_w > 16) return fail(c, MOCHA_ERR_ARG, "step_graph_segmented: 1 <= S_w <= 16 windows");
-    int rc = ready(c, S_w); if (rc) return rc;
-    if (!X || !seg || !cnt_mean || !cnt_std || !Y || !idx) return fail(c, MOCHA_ERR_ARG, "null argument");
-    if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
-    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
-    mocha_ctx::StepKey key; key.x = X; key.mean = cnt_mean; key.sd = cnt_std; key.y = Y; key.idx = idx; key.seg = seg; key.windows = S_w;
-    key.raw = raw != 0;
-    // the ids are read by the captured kernels on every replay: new ids in `seg` are not part of the key
-    return step_replay(c, c->seg_step, key, (hipStream_t)stream, [&](hipStream_t cs) -> int {
-        c->lane = 0;
-        const int r = characterize_impl(c, X, S_w, cnt_mean, cnt_std, Y, idx, cs, raw != 0, seg);
-        c->cur = 0;
-        return r;
-    });
+    SegSelect sel; sel.seg = seg; sel.idx0 = idx;
+    mocha_ctx::StepKey key; key.idx = idx;
+    return step_segmented(c, "step_graph_segmented", mocha_ctx::STEP_SEG, key, SegWindows{X, S_w, cnt_mean, cnt_std, Y, raw != 0}, sel,
+                          idx != nullptr, stream);
 }
 
 // ------------------------------------------------------------------------------------------- soft matching, multi-character bank
 // The decoder's character feature as the softmax-weighted blend of the k nearest entries of the window's own segment instead of the one
 // nearest entry: nothing trained, and no pop when two entries are nearly equidistant.  The matcher is match_seg_topk.hip; the decoder runs
-// on the blended feature itself (the literal flow: instance norm and style MLP of the feature per call, as mocha_live_step_ours - the
-// bank's per-entry decoder constants do not apply to a blend).
+// on the blended feature itself (characterize_segmented_impl with k >= 1).
 static_assert(MOCHA_SOFT_MAX_K == SEG_TOPK_MAX_K, "the header's k limit is the kernel's");
 static int soft_args(mocha_ctx* c, const char* what, int k, float temperature) {
     if (k < 1 || k > MOCHA_SOFT_MAX_K) return fail(c, MOCHA_ERR_ARG, "%s: 1 <= k <= %d neighbours", what, MOCHA_SOFT_MAX_K);
     if (!(temperature > 0.f)) return fail(c, MOCHA_ERR_ARG, "%s: temperature must be positive", what);
     return 0;
-}
-
-// embed -> encoder -> cnt, z-score (bf16 bank: centred queries) -> k nearest + weights + blend into the "sel" workspace -> literal decoder on
-// the blend -> to_mot.  idx0 (B) / idx_k, w_k (B,k): each may be null.  The caller checked k and temperature.
-static int characterize_soft_impl(mocha_ctx* c, const float* src_X, int B, const int32_t* seg, int k, float temperature, const float* cnt_mean,
-                                  const float* cnt_std, float* Y, int32_t* idx0, int32_t* idx_k, float* w_k, bool raw, void* stream,
-                                  const AllowArg* al = nullptr) {
-    int rc = ready(c, B); if (rc) return rc;
-    if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
-    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
-    if (B == 0) return 0;
-    if (!cnt_mean || !cnt_std || !src_X || !Y || !seg) return fail(c, MOCHA_ERR_ARG, "null argument");
-    const size_t ys = (size_t)60 * c->cfg.V * c->cfg.C_in;
-    const size_t xs = raw ? (size_t)60 * (c->cfg.V + 1) * c->cfg.C_in : ys;
-    return for_chunks(c, B, (hipStream_t)stream, [&](int b0, int b, hipStream_t s) -> int {
-        int r;
-        if ((r = run_embed(c, src_X + b0 * xs, b, WS(c, "x5"), true, s, raw))) return r;
-        if ((r = run_encoder(c, WS(c, "x5"), b, WS(c, "enc_s"), s))) return r;
-        InormExtra ex = IEXW(c, s);
-        if (c->bank.is_bf16) { ex.centre = c->bank.center.p; ex.zc = WS(c, "qc"); }
-        LAUNCH(c, s, "mocha_instnorm", "mvn", 0.0, b * 90.0 * 256 * 4 * (c->bank.is_bf16 ? 3.0 : 2.0), launch_instnorm(WS(c, "enc_s"), nullptr, nullptr, cnt_mean, cnt_std, WS(c, "qnm"), b, 90, s, &ex));
-        AllowArg ab;
-        if (al) ab = al->at(b0);
-        if ((r = seg_topk(c, WS(c, c->bank.is_bf16 ? "qc" : "qnm"), b, seg + b0, k, temperature, idx0 ? idx0 + b0 : nullptr,
-                          idx_k ? idx_k + (size_t)b0 * k : nullptr, nullptr, w_k ? w_k + (size_t)b0 * k : nullptr, WS(c, "sel"), s,
-                          al ? &ab : nullptr))) return r;
-        if ((r = run_decoder(c, WS(c, "enc_s"), WS(c, "sel"), b, WS(c, "dec"), s))) return r;
-        return run_to_mot(c, WS(c, "dec"), b, Y + b0 * ys, s, raw);
-    });
 }
 
 int mocha_match_topk_segmented(mocha_ctx* c, const float* query_nm, int Q, const int32_t* seg, int k, int32_t* idx, float* dist, void* stream) {
@@ -2449,18 +2515,9 @@ int mocha_match_topk_segmented(mocha_ctx* c, const float* query_nm, int Q, const
     if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
     if (Q == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    const int D = 90 * 256;
-    c->cur = 0;
-    if (!c->bank.is_bf16) return seg_topk(c, query_nm, Q, seg, k, 1.f, nullptr, idx, dist, nullptr, nullptr, s);
-    // the bf16 copy holds bf16(b - centroid of the union): centred queries, as many at a time as the centred-query buffer holds
-    const int per = (int)std::min<size_t>((size_t)c->seg_q, c->sets[0].match_qc.n / D);
-    for (int q0 = 0; q0 < Q; q0 += per) {
-        const int n = std::min(per, Q - q0);
-        LAUNCH(c, s, "mocha_sub_rows", "match.center", 0.0, 8.0 * n * D, launch_sub_rows(query_nm + (size_t)q0 * D, c->bank.center.p, c->sets[0].match_qc.p, n, D, s));
-        if ((rc = seg_topk(c, c->sets[0].match_qc.p, n, seg + q0, k, 1.f, nullptr, idx + (size_t)q0 * k, dist ? dist + (size_t)q0 * k : nullptr, nullptr,
-                           nullptr, s))) return rc;
-    }
-    return 0;
+    return for_centred_queries(c, query_nm, Q, s, [&](const float* q, int q0, int n) -> int {
+        return seg_topk(c, q, n, seg + q0, k, 1.f, nullptr, idx + (size_t)q0 * k, dist ? dist + (size_t)q0 * k : nullptr, nullptr, nullptr, s);
+    });
 }
 
 int mocha_characterize_soft_segmented(mocha_ctx* c, const float* src_X, int B, const int32_t* seg, int k, float temperature, const float* cnt_mean,
@@ -2468,68 +2525,28 @@ int mocha_characterize_soft_segmented(mocha_ctx* c, const float* src_X, int B, c
     if (!c) return MOCHA_ERR_ARG;
     int rc = soft_args(c, "characterize_soft_segmented", k, temperature); if (rc) return rc;
     if (B > 0 && !seg) return fail(c, MOCHA_ERR_ARG, "characterize_soft_segmented: null argument");
-    return characterize_soft_impl(c, src_X, B, seg, k, temperature, cnt_mean, cnt_std, Y, nullptr, idx_k, w_k, raw != 0, stream);
+    SegSelect sel; sel.seg = seg; sel.k = k; sel.temperature = temperature; sel.idx_k = idx_k; sel.w_k = w_k;
+    return characterize_segmented_impl(c, SegWindows{src_X, B, cnt_mean, cnt_std, Y, raw != 0}, sel, stream);
 }
 
 int mocha_step_graph_soft_segmented(mocha_ctx* c, const float* X, int S_w, const int32_t* seg, int k, float temperature, const float* cnt_mean,
                                     const float* cnt_std, float* Y, int32_t* idx_k, float* w_k, int raw, void* stream) {
     if (!c) return MOCHA_ERR_ARG;
     int rc = soft_args(c, "step_graph_soft_segmented", k, temperature); if (rc) return rc;
-    if (S_w < 1 || S_w > 16) return fail(c, MOCHA_ERR_ARG, "step_graph_soft_segmented: 1 <= S_w <= 16 windows");
-    if ((rc = ready(c, S_w))) return rc;
-    if (!X || !seg || !cnt_mean || !cnt_std || !Y || !idx_k || !w_k) return fail(c, MOCHA_ERR_ARG, "null argument");
-    if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
-    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
-    mocha_ctx::StepKey key; key.x = X; key.mean = cnt_mean; key.sd = cnt_std; key.y = Y; key.seg = seg; key.windows = S_w; key.raw = raw != 0;
-    key.soft_k = k; key.soft_t = temperature; key.soft[0] = idx_k; key.soft[1] = w_k;
-    auto body = [&](hipStream_t cs) -> int {
-        c->lane = 0;
-        const int r = characterize_soft_impl(c, X, S_w, seg, k, temperature, cnt_mean, cnt_std, Y, nullptr, idx_k, w_k, raw != 0, cs);
-        c->cur = 0;
-        return r;
-    };
-    const auto& g = c->soft_step;
-    if (!(g.exec && g.key == key && g.generation == c->generation)) {
-        // Before a capture: the step once, eagerly, so that whatever its kernels make on first use - the plane GEMMs' weight images, the
-        // float64 weights of the literal decoder's style MLP - exists; it writes what the replay then writes again.
-        if ((rc = body((hipStream_t)stream))) return rc;
-    }
-    // the ids are read by the captured kernels on every replay: new ids in `seg` are not part of the key; k and the temperature are
-    return step_replay(c, c->soft_step, key, (hipStream_t)stream, body);
+    SegSelect sel; sel.seg = seg; sel.k = k; sel.temperature = temperature; sel.idx_k = idx_k; sel.w_k = w_k;
+    mocha_ctx::StepKey key; key.soft_k = k; key.soft_t = temperature; key.soft[0] = idx_k; key.soft[1] = w_k;
+    return step_segmented(c, "step_graph_soft_segmented", mocha_ctx::STEP_SEG_SOFT, key, SegWindows{X, S_w, cnt_mean, cnt_std, Y, raw != 0}, sel,
+                          idx_k && w_k, stream);
 }
 
 // ------------------------------------------------------------------------------------------- character mixing, multi-character bank
 // A window characterized by up to MOCHA_MIX_MAX (character, six body-part weights) components: each present component is matched exactly in
-// its own character, and the decoder runs on the part-wise weighted blend of the matched entries (the literal flow, as the soft calls).
+// its own character, and the decoder runs on the part-wise weighted blend of the matched entries (characterize_segmented_impl with a MixArg).
 // The matcher is match_seg_mix.hip; ids and weights are device data every launch and replay reads.
 static_assert(MOCHA_MIX_MAX == SEG_MIX_MAX_J, "the header's component limit is the kernel's");
 static int mix_args(mocha_ctx* c, const char* what, int J) {
     if (J < 1 || J > MOCHA_MIX_MAX) return fail(c, MOCHA_ERR_ARG, "%s: 1 <= J <= %d components", what, MOCHA_MIX_MAX);
     return 0;
-}
-
-// embed -> encoder -> cnt, z-score (bf16 bank: centred queries) -> the mixing matcher's blend into the "sel" workspace -> literal decoder
-// on the blend -> to_mot.  mx.idx / mx.wnorm may be null.  The caller checked J.
-static int characterize_mix_impl(mocha_ctx* c, const float* src_X, int B, const MixArg& mx, const float* cnt_mean, const float* cnt_std, float* Y,
-                                 bool raw, void* stream) {
-    int rc = ready(c, B); if (rc) return rc;
-    if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
-    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
-    if (B == 0) return 0;
-    if (!cnt_mean || !cnt_std || !src_X || !Y || !mx.ids || !mx.weights) return fail(c, MOCHA_ERR_ARG, "null argument");
-    const size_t ys = (size_t)60 * c->cfg.V * c->cfg.C_in;
-    const size_t xs = raw ? (size_t)60 * (c->cfg.V + 1) * c->cfg.C_in : ys;
-    return for_chunks(c, B, (hipStream_t)stream, [&](int b0, int b, hipStream_t s) -> int {
-        int r;
-        if ((r = run_embed(c, src_X + b0 * xs, b, WS(c, "x5"), true, s, raw))) return r;
-        if ((r = run_encoder(c, WS(c, "x5"), b, WS(c, "enc_s"), s))) return r;
-        InormExtra ex = IEXW(c, s);
-        if (c->bank.is_bf16) { ex.centre = c->bank.center.p; ex.zc = WS(c, "qc"); }
-        LAUNCH(c, s, "mocha_instnorm", "mvn", 0.0, b * 90.0 * 256 * 4 * (c->bank.is_bf16 ? 3.0 : 2.0), launch_instnorm(WS(c, "enc_s"), nullptr, nullptr, cnt_mean, cnt_std, WS(c, "qnm"), b, 90, s, &ex));
-        if ((r = seg_mix(c, WS(c, c->bank.is_bf16 ? "qc" : "qnm"), b, mx.at((size_t)b0), WS(c, "sel"), s))) return r;
-        if ((r = run_decoder(c, WS(c, "enc_s"), WS(c, "sel"), b, WS(c, "dec"), s))) return r;
-        return run_to_mot(c, WS(c, "dec"), b, Y + b0 * ys, s, raw);
-    });
 }
 
 int mocha_match_mix_segmented(mocha_ctx* c, const float* query_nm, int Q, const int32_t* ids, const float* weights, int J, int32_t* idx,
@@ -2541,18 +2558,10 @@ int mocha_match_mix_segmented(mocha_ctx* c, const float* query_nm, int Q, const 
     if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
     if (Q == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    const int D = 90 * 256;
-    c->cur = 0;
     const MixArg mx{ids, weights, J, idx, dist, wnorm, nullptr, nullptr};
-    if (!c->bank.is_bf16) return seg_mix(c, query_nm, Q, mx, out, s);
-    // the bf16 copy holds bf16(b - centroid of the union): centred queries, as many at a time as the centred-query buffer holds
-    const int per = (int)std::min<size_t>((size_t)c->seg_q, c->sets[0].match_qc.n / D);
-    for (int q0 = 0; q0 < Q; q0 += per) {
-        const int n = std::min(per, Q - q0);
-        LAUNCH(c, s, "mocha_sub_rows", "match.center", 0.0, 8.0 * n * D, launch_sub_rows(query_nm + (size_t)q0 * D, c->bank.center.p, c->sets[0].match_qc.p, n, D, s));
-        if ((rc = seg_mix(c, c->sets[0].match_qc.p, n, mx.at((size_t)q0), out ? out + (size_t)q0 * D : nullptr, s))) return rc;
-    }
-    return 0;
+    return for_centred_queries(c, query_nm, Q, s, [&](const float* q, int q0, int n) -> int {
+        return seg_mix(c, q, n, mx.at((size_t)q0), out ? out + (size_t)q0 * 90 * 256 : nullptr, s);
+    });
 }
 
 int mocha_characterize_mix_segmented(mocha_ctx* c, const float* src_X, int B, const int32_t* ids, const float* weights, int J,
@@ -2561,35 +2570,19 @@ int mocha_characterize_mix_segmented(mocha_ctx* c, const float* src_X, int B, co
     int rc = mix_args(c, "characterize_mix_segmented", J); if (rc) return rc;
     if (B > 0 && (!ids || !weights)) return fail(c, MOCHA_ERR_ARG, "characterize_mix_segmented: null argument");
     const MixArg mx{ids, weights, J, idx, nullptr, wnorm, nullptr, nullptr};
-    return characterize_mix_impl(c, src_X, B, mx, cnt_mean, cnt_std, Y, raw != 0, stream);
+    SegSelect sel; sel.mix = &mx;
+    return characterize_segmented_impl(c, SegWindows{src_X, B, cnt_mean, cnt_std, Y, raw != 0}, sel, stream);
 }
 
 int mocha_step_graph_mix_segmented(mocha_ctx* c, const float* X, int S_w, const int32_t* ids, const float* weights, int J, const float* cnt_mean,
                                    const float* cnt_std, float* Y, int32_t* idx, float* wnorm, int raw, void* stream) {
     if (!c) return MOCHA_ERR_ARG;
     int rc = mix_args(c, "step_graph_mix_segmented", J); if (rc) return rc;
-    if (S_w < 1 || S_w > 16) return fail(c, MOCHA_ERR_ARG, "step_graph_mix_segmented: 1 <= S_w <= 16 windows");
-    if ((rc = ready(c, S_w))) return rc;
-    if (!X || !ids || !weights || !cnt_mean || !cnt_std || !Y || !idx || !wnorm) return fail(c, MOCHA_ERR_ARG, "null argument");
-    if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
-    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
-    mocha_ctx::StepKey key; key.x = X; key.mean = cnt_mean; key.sd = cnt_std; key.y = Y; key.idx = idx; key.seg = ids; key.windows = S_w;
-    key.raw = raw != 0; key.mix_j = J; key.mix[0] = weights; key.mix[1] = wnorm;
     const MixArg mx{ids, weights, J, idx, nullptr, wnorm, nullptr, nullptr};
-    auto body = [&](hipStream_t cs) -> int {
-        c->lane = 0;
-        const int r = characterize_mix_impl(c, X, S_w, mx, cnt_mean, cnt_std, Y, raw != 0, cs);
-        c->cur = 0;
-        return r;
-    };
-    const auto& g = c->mix_step;
-    if (!(g.exec && g.key == key && g.generation == c->generation)) {
-        // Before a capture: the step once, eagerly, so that whatever its kernels make on first use - the plane GEMMs' weight images, the
-        // float64 weights of the literal decoder's style MLP - exists; it writes what the replay then writes again.
-        if ((rc = body((hipStream_t)stream))) return rc;
-    }
-    // ids and weights are read by the captured kernels on every replay: their contents are not part of the key; J is
-    return step_replay(c, c->mix_step, key, (hipStream_t)stream, body);
+    SegSelect sel; sel.mix = &mx;
+    mocha_ctx::StepKey key; key.idx = idx; key.mix_j = J; key.mix[0] = weights; key.mix[1] = wnorm;
+    return step_segmented(c, "step_graph_mix_segmented", mocha_ctx::STEP_SEG_MIX, key, SegWindows{X, S_w, cnt_mean, cnt_std, Y, raw != 0}, sel,
+                          idx && wnorm, stream);
 }
 
 // ------------------------------------------------------------------------------------------- action-constrained matching
@@ -2648,31 +2641,13 @@ int mocha_match_segmented_allow(mocha_ctx* c, const float* query_nm, int Q, cons
     if (!c->bank.labelled) return fail(c, MOCHA_ERR_STATE, "no action labels: call mocha_bank_set_labels first");
     if (Q == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    const int D = 90 * 256;
-    c->cur = 0;
     const AllowArg al{reinterpret_cast<const unsigned long long*>(allow), applied};
-    // k = 1: the hard matcher; k >= 2: the top-k matcher.  q: z-scored (fp32 bank) or centred (bf16 bank) queries
-    auto match = [&](const float* q, int q0, int n) -> int {
+    // k = 1: the hard matcher; k >= 2: the top-k matcher
+    return for_centred_queries(c, query_nm, Q, s, [&](const float* q, int q0, int n) -> int {
         const AllowArg a = al.at(q0);
         if (k == 1) return seg_match(c, q, n, seg + q0, idx + q0, nullptr, dist ? dist + q0 : nullptr, s, &a);
         return seg_topk(c, q, n, seg + q0, k, 1.f, nullptr, idx + (size_t)q0 * k, dist ? dist + (size_t)q0 * k : nullptr, nullptr, nullptr, s, &a);
-    };
-    if (!c->bank.is_bf16) return match(query_nm, 0, Q);
-    // the bf16 copy holds bf16(b - centroid of the union): centred queries, as many at a time as the centred-query buffer holds
-    const int per = (int)std::min<size_t>((size_t)c->seg_q, c->sets[0].match_qc.n / D);
-    for (int q0 = 0; q0 < Q; q0 += per) {
-        const int n = std::min(per, Q - q0);
-        LAUNCH(c, s, "mocha_sub_rows", "match.center", 0.0, 8.0 * n * D, launch_sub_rows(query_nm + (size_t)q0 * D, c->bank.center.p, c->sets[0].match_qc.p, n, D, s));
-        if ((rc = match(c->sets[0].match_qc.p, q0, n))) return rc;
-    }
-    return 0;
-}
-
-// k = 0: the hard characterize (idx_k holds B entries, w_k unused); k >= 1: the soft one
-static int characterize_allow_impl(mocha_ctx* c, const float* X, int B, const int32_t* seg, const AllowArg& al, int k, float temperature,
-                                   const float* cnt_mean, const float* cnt_std, float* Y, int32_t* idx_k, float* w_k, bool raw, void* stream) {
-    if (k == 0) return characterize_impl(c, X, B, cnt_mean, cnt_std, Y, idx_k, stream, raw, seg, &al);
-    return characterize_soft_impl(c, X, B, seg, k, temperature, cnt_mean, cnt_std, Y, nullptr, idx_k, w_k, raw, stream, &al);
+    });
 }
 
 int mocha_characterize_segmented_allow(mocha_ctx* c, const float* src_X, int B, const int32_t* seg, const uint64_t* allow, int k, float temperature,
@@ -2683,7 +2658,9 @@ int mocha_characterize_segmented_allow(mocha_ctx* c, const float* src_X, int B, 
     if (B > 0 && (!seg || !allow)) return fail(c, MOCHA_ERR_ARG, "characterize_segmented_allow: null argument");
     if (c->bank.segmented() && !c->bank.labelled) return fail(c, MOCHA_ERR_STATE, "no action labels: call mocha_bank_set_labels first");
     const AllowArg al{reinterpret_cast<const unsigned long long*>(allow), applied};
-    return characterize_allow_impl(c, src_X, B, seg, al, k, temperature, cnt_mean, cnt_std, Y, idx_k, w_k, raw != 0, stream);
+    SegSelect sel; sel.seg = seg; sel.allow = &al; sel.k = k; sel.temperature = temperature; sel.w_k = w_k;
+    if (k == 0) sel.idx0 = idx_k; else sel.idx_k = idx_k;      // k = 0: the hard characterize, idx_k holds one entry per window and w_k is unused
+    return characterize_segmented_impl(c, SegWindows{src_X, B, cnt_mean, cnt_std, Y, raw != 0}, sel, stream);
 }
 
 int mocha_step_graph_segmented_allow(mocha_ctx* c, const float* X, int S_w, const int32_t* seg, const uint64_t* allow, int k, float temperature,
@@ -2691,29 +2668,14 @@ int mocha_step_graph_segmented_allow(mocha_ctx* c, const float* X, int S_w, cons
                                      void* stream) {
     if (!c) return MOCHA_ERR_ARG;
     if (k != 0) { int rc = soft_args(c, "step_graph_segmented_allow", k, temperature); if (rc) return rc; }
-    if (S_w < 1 || S_w > 16) return fail(c, MOCHA_ERR_ARG, "step_graph_segmented_allow: 1 <= S_w <= 16 windows");
-    int rc = ready(c, S_w); if (rc) return rc;
-    if (!X || !seg || !allow || !cnt_mean || !cnt_std || !Y || !idx_k || (k > 0 && !w_k)) return fail(c, MOCHA_ERR_ARG, "null argument");
-    if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
-    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
-    if (!c->bank.labelled) return fail(c, MOCHA_ERR_STATE, "no action labels: call mocha_bank_set_labels first");
     const AllowArg al{reinterpret_cast<const unsigned long long*>(allow), applied};
-    mocha_ctx::StepKey key; key.x = X; key.mean = cnt_mean; key.sd = cnt_std; key.y = Y; key.seg = seg; key.windows = S_w; key.raw = raw != 0;
+    mocha_ctx::StepKey key;
     key.soft_k = k; key.soft_t = k > 0 ? temperature : 0.f; key.soft[0] = idx_k; key.soft[1] = k > 0 ? w_k : nullptr;
     key.allow[0] = allow; key.allow[1] = applied;
-    auto body = [&](hipStream_t cs) -> int {
-        c->lane = 0;
-        const int r = characterize_allow_impl(c, X, S_w, seg, al, k, temperature, cnt_mean, cnt_std, Y, idx_k, w_k, raw != 0, cs);
-        c->cur = 0;
-        return r;
-    };
-    const auto& g = c->seg_allow_step;
-    if (k > 0 && !(g.exec && g.key == key && g.generation == c->generation)) {
-        // as mocha_step_graph_soft_segmented: the soft step once, eagerly, before a capture (first-use images of its kernels)
-        if ((rc = body((hipStream_t)stream))) return rc;
-    }
-    // the ids and the masks are read by the captured kernels on every replay: new values in `seg` / `allow` are not part of the key
-    return step_replay(c, c->seg_allow_step, key, (hipStream_t)stream, body);
+    SegSelect sel; sel.seg = seg; sel.allow = &al; sel.k = k; sel.temperature = temperature; sel.w_k = w_k;
+    if (k == 0) sel.idx0 = idx_k; else sel.idx_k = idx_k;      // k = 0: the hard characterize, idx_k holds one entry per window and w_k is unused
+    return step_segmented(c, "step_graph_segmented_allow", mocha_ctx::STEP_SEG_ALLOW, key, SegWindows{X, S_w, cnt_mean, cnt_std, Y, raw != 0}, sel,
+                          idx_k && (k == 0 || w_k), stream);
 }
 
 // ------------------------------------------------------------------------------------------- resident multi-character bank
@@ -3621,6 +3583,86 @@ LiveLayout live_layout(const mocha_ctx* c, int S) {
     l.bytes = off;
     return l;
 }
+
+// The arguments of the live steps, in the groups that travel together.  The session: the post configuration (NULL: the demo's), the
+// session buffer, the streams' character ids (a mix step: its component ids) and the z-score
+struct LiveCall {
+    const mocha_post_cfg* cfg = nullptr; void* live = nullptr; int streams = 0; const int32_t* seg = nullptr;
+    const float *cnt_mean = nullptr, *cnt_std = nullptr; void* stream = nullptr;
+};
+// ... the featurised frame of every stream (the raw steps: the front end's staging) ...
+struct LiveFrame {
+    const float *Yrot = nullptr, *Ypos = nullptr, *Yvel = nullptr, *Yang = nullptr, *src_rvel = nullptr, *src_rang = nullptr, *src_speed = nullptr;
+    const unsigned char* contact = nullptr;
+};
+// ... the posed frame and the match the step writes (bvh_pos / bvh_euler: both or neither) ...
+struct LiveOut {
+    double *pos = nullptr, *rot = nullptr, *ik_rot = nullptr, *bvh_pos = nullptr, *bvh_euler = nullptr;
+    int32_t *idx = nullptr, *valid = nullptr;
+};
+// ... and the optional stages of mocha_live_step's family, each checked by its entry point: the soft matcher (k >= 1; a mix step: w_k is
+// its wnorm), the inertializer, the mocap front end in front of the push, the action constraint, the mix
+struct LiveStages {
+    int k = 0; float temperature = 0.f; int32_t* idx_k = nullptr; float* w_k = nullptr;
+    void* inert = nullptr; mocha_inert_cfg icfg{};
+    const IngestParams* ingest = nullptr; const mocha_ingest_cfg* ingest_cfg = nullptr;
+    const AllowArg* allow = nullptr;
+    const MixArg* mix = nullptr;
+};
+
+// A live session's buffer as the steps use it, with what mocha_live_step and mocha_live_step_ours make of their common arguments: the
+// post configuration in force, the post-processing launch's parameters and the key fields every live step has
+struct LiveView {
+    LiveRing ring;
+    float *xraw = nullptr, *ystage = nullptr, *heads = nullptr, *speed = nullptr;
+    int32_t* eff = nullptr;
+    PostParams post{};
+    mocha_ctx::StepKey key;
+};
+
+// the argument checks the live steps share (`who` names the step in the messages) ...
+int live_args(mocha_ctx* c, const char* who, const LiveCall& a, const LiveFrame& f, const LiveOut& o) {
+    if (a.streams < 1 || a.streams > 16) return fail(c, MOCHA_ERR_ARG, "%s: 1 <= streams <= 16", who);
+    if (!a.live || !f.Yrot || !f.Ypos || !f.Yvel || !f.Yang || !f.src_rvel || !f.src_rang || !f.src_speed || !f.contact || !a.seg || !a.cnt_mean ||
+        !a.cnt_std || !o.pos || !o.rot || !o.ik_rot || !o.idx || !o.valid || (!o.bvh_pos) != (!o.bvh_euler))
+        return fail(c, MOCHA_ERR_ARG, "%s: null argument", who);
+    return 0;
+}
+// ... the state checks ...
+int live_state(mocha_ctx* c, const char* who) {
+    if (!c->finalized) return fail(c, MOCHA_ERR_STATE, "weights not finalised: call mocha_finalize_weights first");
+    if (!c->pose_norm.p) return fail(c, MOCHA_ERR_STATE, "%s: no pose norm: call mocha_set_pose_norm first", who);
+    if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set_segments first");
+    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    return 0;
+}
+// ... and the view: everything the captured region needs exists when it returns (the workspaces, the skeleton's parents; the segmented
+// matcher's scratch was sized by mocha_bank_set_segments)
+int live_view(mocha_ctx* c, const LiveCall& a, const LiveFrame& f, const LiveOut& o, LiveView& v) {
+    mocha_post_cfg d;
+    const mocha_post_cfg* cfg = a.cfg;
+    if (!cfg) { mocha_post_cfg_default(&d); cfg = &d; }
+    int rc = post_params(c, cfg, v.post); if (rc) return rc;
+    if ((rc = ready(c, a.streams))) return rc;
+    if ((rc = ensure_bone_parents(c))) return rc;
+    const LiveLayout l = live_layout(c, a.streams);
+    char* base = static_cast<char*>(a.live);
+    auto f32 = [&](size_t at) { return reinterpret_cast<float*>(base + at); };
+    v.ring.counters = reinterpret_cast<int32_t*>(base + l.counters);
+    v.ring.rot = f32(l.rot); v.ring.pos = f32(l.pos); v.ring.vel = f32(l.vel); v.ring.ang = f32(l.ang);
+    v.xraw = f32(l.xraw); v.ystage = f32(l.y); v.heads = f32(l.heads); v.speed = f32(l.speed);
+    v.eff = reinterpret_cast<int32_t*>(base + l.eff);
+    PostParams& p = v.post;
+    p.heads = v.heads; p.speed = v.speed; p.src_rvel = f.src_rvel; p.src_rang = f.src_rang; p.src_speed = f.src_speed; p.contact = f.contact;
+    p.pos = o.pos; p.rot = o.rot; p.ik_rot = o.ik_rot; p.bvh_pos = o.bvh_pos; p.bvh_euler = o.bvh_euler;
+    p.n_clips = a.streams; p.n_frames = 1; p.state = reinterpret_cast<double*>(base + l.post); p.valid = o.valid;
+    mocha_ctx::StepKey& key = v.key;
+    key.x = a.live; key.mean = a.cnt_mean; key.sd = a.cnt_std; key.idx = o.idx; key.seg = a.seg; key.windows = a.streams; key.raw = true;
+    const void* ptrs[14] = {f.Yrot, f.Ypos, f.Yvel, f.Yang, f.src_rvel, f.src_rang, f.src_speed, f.contact, o.pos, o.rot, o.ik_rot, o.bvh_pos, o.bvh_euler, o.valid};
+    for (int i = 0; i < 14; ++i) key.live[i] = ptrs[i];
+    key.post = *cfg;
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -3654,112 +3696,78 @@ int mocha_live_reset(mocha_ctx* c, void* live, int streams, const int32_t* which
     return 0;
 }
 
-// mocha_live_step (k = 0: the hard 1-NN characterize, idx_k / w_k unused) and mocha_live_step_soft (k >= 1: the soft characterize in its place;
-// the caller checked k, the temperature and idx_k / w_k): one body, each with its own captured graph
-static int live_step_impl(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos, const float* Yvel,
-                          const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed, const unsigned char* contact,
-                          const int32_t* seg, const float* cnt_mean, const float* cnt_std, double* pos, double* rot, double* ik_rot, double* bvh_pos,
-                          double* bvh_euler, int32_t* idx, int32_t* valid, int k, float temperature, int32_t* idx_k, float* w_k, void* stream,
-                          void* inert = nullptr, const mocha_inert_cfg* icfg = nullptr, const IngestParams* ing = nullptr,
-                          const mocha_ingest_cfg* ing_cfg = nullptr, const AllowArg* al = nullptr, const MixArg* mx = nullptr) {
-    if (streams < 1 || streams > 16) return fail(c, MOCHA_ERR_ARG, "live_step: 1 <= streams <= 16");
-    if (!live || !Yrot || !Ypos || !Yvel || !Yang || !src_rvel || !src_rang || !src_speed || !contact || !seg || !cnt_mean || !cnt_std || !pos ||
-        !rot || !ik_rot || !idx || !valid || (!bvh_pos) != (!bvh_euler))
-        return fail(c, MOCHA_ERR_ARG, "live_step: null argument");
-    if (!c->finalized) return fail(c, MOCHA_ERR_STATE, "weights not finalised: call mocha_finalize_weights first");
-    if (!c->pose_norm.p) return fail(c, MOCHA_ERR_STATE, "live_step: no pose norm: call mocha_set_pose_norm first");
-    if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set_segments first");
-    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+// The graph of a step of mocha_live_step's family: mix and allow steps have one each per input form (featurised / raw); the others one
+// per input form for the hard, the soft and the inertialized (hard or soft) step
+static mocha_ctx::StepKind live_step_kind(bool mix, bool allow, bool ingest, bool inert, bool soft) {
+    if (mix) return ingest ? mocha_ctx::STEP_LIVE_RAW_MIX : mocha_ctx::STEP_LIVE_MIX;
+    if (allow) return ingest ? mocha_ctx::STEP_LIVE_RAW_ALLOW : mocha_ctx::STEP_LIVE_ALLOW;
+    if (ingest) return inert ? mocha_ctx::STEP_LIVE_RAW_INERT : soft ? mocha_ctx::STEP_LIVE_RAW_SOFT : mocha_ctx::STEP_LIVE_RAW;
+    return inert ? mocha_ctx::STEP_LIVE_INERT : soft ? mocha_ctx::STEP_LIVE_SOFT : mocha_ctx::STEP_LIVE;
+}
+
+// The body of mocha_live_step and of every step of its family (`st`: which optional stages run; the entry points checked them)
+static int live_step_impl(mocha_ctx* c, const LiveCall& a, const LiveFrame& f, const LiveOut& o, const LiveStages& st) {
+    int rc = live_args(c, "live_step", a, f, o); if (rc) return rc;
+    if ((rc = live_state(c, "live_step"))) return rc;
+    const AllowArg* al = st.allow;
+    const MixArg* mx = st.mix;
+    const IngestParams* ing = st.ingest;
     if (al && !c->bank.labelled) return fail(c, MOCHA_ERR_STATE, "no action labels: call mocha_bank_set_labels first");
-    if (mx && !c->sets[0].mix_zero.p)
-        return fail(c, MOCHA_ERR_STATE, "workspace set 0 has no segmented-match scratch: call %s after changing the workspaces",
-                    c->bank.resident ? "mocha_reserve" : "mocha_bank_set_segments");
-    mocha_post_cfg d;
-    if (!cfg) { mocha_post_cfg_default(&d); cfg = &d; }
-    PostParams p{};
-    int rc = post_params(c, cfg, p); if (rc) return rc;
-    // everything the captured region needs exists before capture begins: the workspaces, the skeleton's parents (the segmented matcher's
-    // scratch was sized by mocha_bank_set_segments)
-    if ((rc = ready(c, streams))) return rc;
-    if ((rc = ensure_bone_parents(c))) return rc;
+    if (mx && !c->sets[0].mix_zero.p) return no_seg_scratch(c, 0);
+    LiveView v;
+    if ((rc = live_view(c, a, f, o, v))) return rc;
+    const int streams = a.streams, J = c->cfg.V + 1, V = c->cfg.V;
+    const SegWindows win{v.xraw, streams, a.cnt_mean, a.cnt_std, v.ystage, true};
 
-    const LiveLayout l = live_layout(c, streams);
-    char* base = static_cast<char*>(live);
-    LiveRing ring;
-    ring.counters = reinterpret_cast<int32_t*>(base + l.counters);
-    ring.rot = reinterpret_cast<float*>(base + l.rot); ring.pos = reinterpret_cast<float*>(base + l.pos);
-    ring.vel = reinterpret_cast<float*>(base + l.vel); ring.ang = reinterpret_cast<float*>(base + l.ang);
-    float* xraw = reinterpret_cast<float*>(base + l.xraw);
-    float* ystage = reinterpret_cast<float*>(base + l.y);
-    float* heads = reinterpret_cast<float*>(base + l.heads);
-    float* speed = reinterpret_cast<float*>(base + l.speed);
-    int32_t* eff = reinterpret_cast<int32_t*>(base + l.eff);
-    double* pstate = reinterpret_cast<double*>(base + l.post);
-    p.heads = heads; p.speed = speed; p.src_rvel = src_rvel; p.src_rang = src_rang; p.src_speed = src_speed; p.contact = contact;
-    p.pos = pos; p.rot = rot; p.ik_rot = ik_rot; p.bvh_pos = bvh_pos; p.bvh_euler = bvh_euler;
-    p.n_clips = streams; p.n_frames = 1; p.state = pstate; p.valid = valid;
-    const int J = c->cfg.V + 1, V = c->cfg.V;
-
-    // the segmented characterize of the S staging windows with the ids in eff: hard, or soft with column 0 of idx_k in idx
-    // the mix steps: the mix characterize of the S windows, gated by the push (eff >= 0: the ring is full and a frame came); with the
-    // step's outputs (ix non-null) the matcher also rewrites valid - a stream none of whose components is present sits the step out
+    // The segmented characterize of the S staging windows with the ids in eff: hard, or soft with column 0 of idx_k in idx.  A mix step:
+    // the mix characterize, gated by the push (eff >= 0: the ring is full and a frame came); with the step's outputs (ix non-null) the
+    // matcher also rewrites valid - a stream none of whose components is present sits the step out
     auto characterize = [&](int32_t* ix, int32_t* ixk, float* wk, hipStream_t cs) -> int {
-        c->lane = 0;
-        if (mx) {
-            const MixArg m{mx->ids, mx->weights, mx->J, ix, nullptr, wk, eff, ix ? valid : nullptr};
-            const int r = characterize_mix_impl(c, xraw, streams, m, cnt_mean, cnt_std, ystage, true, cs);
-            c->cur = 0;
-            return r;
-        }
-        const int r = k > 0 ? characterize_soft_impl(c, xraw, streams, eff, k, temperature, cnt_mean, cnt_std, ystage, ix, ixk, wk, true, cs, al)
-                            : characterize_impl(c, xraw, streams, cnt_mean, cnt_std, ystage, ix, cs, true, eff, al);
-        c->cur = 0;
-        return r;
+        MixArg m;
+        SegSelect sel; sel.seg = v.eff; sel.k = st.k; sel.temperature = st.temperature; sel.allow = al; sel.idx0 = ix; sel.idx_k = ixk; sel.w_k = wk;
+        if (mx) { m = MixArg{mx->ids, mx->weights, mx->J, ix, nullptr, wk, v.eff, ix ? o.valid : nullptr}; sel.mix = &m; }
+        return characterize_segmented_set0(c, win, sel, cs);
     };
     // ring push + featurize -> segmented characterize of the S windows with the effective ids -> pose heads -> one post-processing frame
     auto body = [&](hipStream_t cs) -> int {
-        // mocha_live_step_raw: the front end writes the frame the push reads (Yrot .. contact are its staging) and says which streams have one
+        // mocha_live_step_raw: the front end writes the frame the push reads (`f` is its staging) and says which streams have one
         if (ing)
             LAUNCH(c, cs, "mocha_live_ingest", "live.ingest", 0.0, (double)streams * (V * 7.0 * 4 + J * 13.0 * 4 + 40.0 * 4 * 8 + J * 16.0 * 13 * 8),
                    launch_live_ingest(*ing, streams, cs));
         LAUNCH(c, cs, "mocha_live_push", "live.push", streams * 60.0 * J * 150, streams * (60.0 * J * (13 + 15) + J * 26.0) * 4,
-               launch_live_push(ring, Yrot, Ypos, Yvel, Yang, mx ? c->sets[0].mix_zero.p : seg, c->bone_parents.p, xraw, eff, valid, streams, J, cs,
-                                ing ? ing->have : nullptr, c->bank.resident && !mx ? c->bank.seg_dev.p : nullptr,
+               launch_live_push(v.ring, f.Yrot, f.Ypos, f.Yvel, f.Yang, mx ? c->sets[0].mix_zero.p : a.seg, c->bone_parents.p, v.xraw, v.eff, o.valid,
+                                streams, J, cs, ing ? ing->have : nullptr, c->bank.resident && !mx ? c->bank.seg_dev.p : nullptr,
                                 c->bank.resident && !mx ? c->bank.segments() : 0));
         // (a mix step's push takes zero ids and no slot table: its eff is the gate alone; which characters are loaded is the matcher's to read)
-        const int r = characterize(idx, idx_k, w_k, cs);
+        const int r = characterize(o.idx, st.idx_k, st.w_k, cs);
         if (r) return r;
-        LAUNCH(c, cs, "mocha_pose_heads", "live.heads", 0.0, streams * (60.0 * 12 + V * 28.0 * 4), launch_pose_heads(ystage, heads, speed, streams, c->cfg.T, V, cs));
+        LAUNCH(c, cs, "mocha_pose_heads", "live.heads", 0.0, streams * (60.0 * 12 + V * 28.0 * 4), launch_pose_heads(v.ystage, v.heads, v.speed, streams, c->cfg.T, V, cs));
         // mocha_live_step_inert: the staged heads inertialized in place, on the step's effective ids and its valid flags
-        if (inert)
+        if (st.inert)
             LAUNCH(c, cs, "mocha_inertialize", "live.inert", 0.0, (double)streams * (V * 26.0 * 4 + 2.0 * INERT_STATE_DOUBLES * 8),
-                   launch_inertialize(static_cast<double*>(inert), heads, heads, eff, nullptr, valid, streams, V, icfg->halflife, icfg->dt, cs));
+                   launch_inertialize(static_cast<double*>(st.inert), v.heads, v.heads, v.eff, nullptr, o.valid, streams, V, st.icfg.halflife,
+                                      st.icfg.dt, cs));
         LAUNCH(c, cs, "mocha_post_clip", "live.post", 0.0, (double)streams * (V * 13.0 * 4 + J * 11.0 * 8 + 2.0 * POST_STATE_DOUBLES * 8),
-               launch_post_step(p, cs));
+               launch_post_step(v.post, cs));
         return 0;
     };
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = (hipStream_t)a.stream;
     // while profiling (mocha_profile_start) the step runs eagerly, launch by launch, so that every kernel of it is timed
     if (c->prof_on) return body(s);
 
-    mocha_ctx::StepKey key;
-    key.x = live; key.mean = cnt_mean; key.sd = cnt_std; key.idx = idx; key.seg = seg; key.windows = streams; key.raw = true;
-    const void* ptrs[17] = {Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, pos, rot, ik_rot, bvh_pos, bvh_euler, valid, nullptr, nullptr, nullptr};
-    for (int i = 0; i < 17; ++i) key.live[i] = ptrs[i];
-    key.post = *cfg;
-    key.soft_k = k; key.soft_t = k > 0 ? temperature : 0.f; key.soft[0] = k > 0 ? idx_k : nullptr; key.soft[1] = k > 0 ? w_k : nullptr;
-    if (inert) { key.inert = inert; key.inert_halflife = icfg->halflife; key.inert_dt = icfg->dt; }
-    if (ing) { key.ingest[0] = ing->state; key.ingest[1] = ing->rot; key.ingest[2] = ing->pos; key.icfg = *ing_cfg; }
+    mocha_ctx::StepKey& key = v.key;
+    key.soft_k = st.k; key.soft_t = st.k > 0 ? st.temperature : 0.f; key.soft[0] = st.k > 0 ? st.idx_k : nullptr; key.soft[1] = st.k > 0 ? st.w_k : nullptr;
+    if (st.inert) { key.inert = st.inert; key.inert_halflife = st.icfg.halflife; key.inert_dt = st.icfg.dt; }
+    if (ing) { key.ingest[0] = ing->state; key.ingest[1] = ing->rot; key.ingest[2] = ing->pos; key.icfg = *st.ingest_cfg; }
     if (al) { key.allow[0] = al->allow; key.allow[1] = al->applied; }
-    if (mx) { key.mix_j = mx->J; key.mix[0] = mx->weights; key.mix[1] = w_k; }
-    mocha_ctx::StepGraph& g = mx ? (ing ? c->live_raw_mix_step : c->live_mix_step) : al ? (ing ? c->live_raw_allow_step : c->live_allow_step)
-                                 : ing ? c->live_raw_step[inert ? 2 : k > 0 ? 1 : 0] : inert ? c->live_inert_step : k > 0 ? c->live_soft_step : c->live_step;
-    if (!(g.exec && g.key == key && g.generation == c->generation)) {
+    if (mx) { key.mix_j = mx->J; key.mix[0] = mx->weights; key.mix[1] = st.w_k; }
+    mocha_ctx::StepGraph& g = c->steps[live_step_kind(mx, al, ing, st.inert, st.k > 0)];
+    if (!step_holds(c, g, key)) {
         // Before a capture: one eager characterize of the staging windows with every id -1 (no bank row is matched, no state of the
         // session moves), so that whatever the kernels of the step make on first use - the plane GEMMs' weight images, for the soft step
         // the float64 weights of the literal decoder's style MLP - exists and the captured step takes the kernels every later step takes.
-        HIPCHK(c, hipMemsetAsync(xraw, 0, (size_t)streams * 60 * J * c->cfg.C_in * sizeof(float), s));
-        HIPCHK(c, hipMemsetAsync(eff, 0xFF, (size_t)streams * sizeof(int32_t), s));
+        HIPCHK(c, hipMemsetAsync(v.xraw, 0, (size_t)streams * 60 * J * c->cfg.C_in * sizeof(float), s));
+        HIPCHK(c, hipMemsetAsync(v.eff, 0xFF, (size_t)streams * sizeof(int32_t), s));
         if ((rc = characterize(nullptr, nullptr, nullptr, s))) return rc;
     }
     return step_replay(c, g, key, s, body);
@@ -3770,8 +3778,10 @@ int mocha_live_step(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, int str
                     const int32_t* seg, const float* cnt_mean, const float* cnt_std, double* pos, double* rot, double* ik_rot, double* bvh_pos,
                     double* bvh_euler, int32_t* idx, int32_t* valid, void* stream) {
     if (!c) return MOCHA_ERR_ARG;
-    return live_step_impl(c, cfg, live, streams, Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, seg, cnt_mean, cnt_std, pos, rot,
-                          ik_rot, bvh_pos, bvh_euler, idx, valid, 0, 0.f, nullptr, nullptr, stream);
+    LiveCall a; a.cfg = cfg; a.live = live; a.streams = streams; a.seg = seg; a.cnt_mean = cnt_mean; a.cnt_std = cnt_std; a.stream = stream;
+    LiveFrame f; f.Yrot = Yrot; f.Ypos = Ypos; f.Yvel = Yvel; f.Yang = Yang; f.src_rvel = src_rvel; f.src_rang = src_rang; f.src_speed = src_speed; f.contact = contact;
+    LiveOut o; o.pos = pos; o.rot = rot; o.ik_rot = ik_rot; o.bvh_pos = bvh_pos; o.bvh_euler = bvh_euler; o.idx = idx; o.valid = valid;
+    return live_step_impl(c, a, f, o, LiveStages{});
 }
 
 int mocha_live_step_soft(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos, const float* Yvel,
@@ -3781,8 +3791,19 @@ int mocha_live_step_soft(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, in
     if (!c) return MOCHA_ERR_ARG;
     int rc = soft_args(c, "live_step_soft", k, temperature); if (rc) return rc;
     if (!idx_k || !w_k) return fail(c, MOCHA_ERR_ARG, "live_step_soft: null argument");
-    return live_step_impl(c, cfg, live, streams, Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, seg, cnt_mean, cnt_std, pos, rot,
-                          ik_rot, bvh_pos, bvh_euler, idx, valid, k, temperature, idx_k, w_k, stream);
+    LiveCall a; a.cfg = cfg; a.live = live; a.streams = streams; a.seg = seg; a.cnt_mean = cnt_mean; a.cnt_std = cnt_std; a.stream = stream;
+    LiveFrame f; f.Yrot = Yrot; f.Ypos = Ypos; f.Yvel = Yvel; f.Yang = Yang; f.src_rvel = src_rvel; f.src_rang = src_rang; f.src_speed = src_speed; f.contact = contact;
+    LiveOut o; o.pos = pos; o.rot = rot; o.ik_rot = ik_rot; o.bvh_pos = bvh_pos; o.bvh_euler = bvh_euler; o.idx = idx; o.valid = valid;
+    LiveStages st; st.k = k; st.temperature = temperature; st.idx_k = idx_k; st.w_k = w_k;
+    return live_step_impl(c, a, f, o, st);
+}
+
+// the soft stage of the steps that take k = 0 for the hard matcher, as the caller gave it: checked, and cleared when k = 0
+static int live_soft_check(mocha_ctx* c, const char* who, LiveStages& st) {
+    if (st.k == 0) { st.temperature = 0.f; st.idx_k = nullptr; if (!st.mix) st.w_k = nullptr; return 0; }
+    int rc = soft_args(c, who, st.k, st.temperature); if (rc) return rc;
+    if (!st.idx_k || !st.w_k) return fail(c, MOCHA_ERR_ARG, "%s: null argument", who);
+    return 0;
 }
 
 // cfg (NULL = half-life 0.1 s at 60 frames per second) checked and copied into `out`
@@ -3820,16 +3841,14 @@ int mocha_live_step_inert(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, i
                           double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx, int32_t* valid, int32_t* idx_k, float* w_k, void* stream,
                           void* inert, const mocha_inert_cfg* icfg) {
     if (!c) return MOCHA_ERR_ARG;
-    if (k != 0) {
-        int rc = soft_args(c, "live_step_inert", k, temperature); if (rc) return rc;
-        if (!idx_k || !w_k) return fail(c, MOCHA_ERR_ARG, "live_step_inert: null argument");
-    }
+    LiveStages st; st.k = k; st.temperature = temperature; st.idx_k = idx_k; st.w_k = w_k; st.inert = inert;
+    int rc = live_soft_check(c, "live_step_inert", st); if (rc) return rc;
     if (!inert) return fail(c, MOCHA_ERR_ARG, "live_step_inert: null inertializer state");
-    mocha_inert_cfg ic;
-    int rc = inert_cfg(c, "live_step_inert", icfg, ic); if (rc) return rc;
-    return live_step_impl(c, cfg, live, streams, Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, seg, cnt_mean, cnt_std, pos, rot,
-                          ik_rot, bvh_pos, bvh_euler, idx, valid, k, k > 0 ? temperature : 0.f, k > 0 ? idx_k : nullptr, k > 0 ? w_k : nullptr,
-                          stream, inert, &ic);
+    if ((rc = inert_cfg(c, "live_step_inert", icfg, st.icfg))) return rc;
+    LiveCall a; a.cfg = cfg; a.live = live; a.streams = streams; a.seg = seg; a.cnt_mean = cnt_mean; a.cnt_std = cnt_std; a.stream = stream;
+    LiveFrame f; f.Yrot = Yrot; f.Ypos = Ypos; f.Yvel = Yvel; f.Yang = Yang; f.src_rvel = src_rvel; f.src_rang = src_rang; f.src_speed = src_speed; f.contact = contact;
+    LiveOut o; o.pos = pos; o.rot = rot; o.ik_rot = ik_rot; o.bvh_pos = bvh_pos; o.bvh_euler = bvh_euler; o.idx = idx; o.valid = valid;
+    return live_step_impl(c, a, f, o, st);
 }
 
 // mocha_live_step_inert's arguments (inert may be NULL: no inertializer; k = 0: the hard matcher) with the streams' allow masks: the
@@ -3840,17 +3859,16 @@ int mocha_live_step_allow(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, i
                           double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx, int32_t* valid, int32_t* idx_k, float* w_k, void* stream,
                           void* inert, const mocha_inert_cfg* icfg, const uint64_t* allow, int32_t* applied) {
     if (!c) return MOCHA_ERR_ARG;
-    if (k != 0) {
-        int rc = soft_args(c, "live_step_allow", k, temperature); if (rc) return rc;
-        if (!idx_k || !w_k) return fail(c, MOCHA_ERR_ARG, "live_step_allow: null argument");
-    }
+    LiveStages st; st.k = k; st.temperature = temperature; st.idx_k = idx_k; st.w_k = w_k; st.inert = inert;
+    int rc = live_soft_check(c, "live_step_allow", st); if (rc) return rc;
     if (!allow) return fail(c, MOCHA_ERR_ARG, "live_step_allow: null allow masks");
-    mocha_inert_cfg ic{};
-    if (inert) { int rc = inert_cfg(c, "live_step_allow", icfg, ic); if (rc) return rc; }
+    if (inert && (rc = inert_cfg(c, "live_step_allow", icfg, st.icfg))) return rc;
     const AllowArg al{reinterpret_cast<const unsigned long long*>(allow), applied};
-    return live_step_impl(c, cfg, live, streams, Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, seg, cnt_mean, cnt_std, pos, rot,
-                          ik_rot, bvh_pos, bvh_euler, idx, valid, k, k > 0 ? temperature : 0.f, k > 0 ? idx_k : nullptr, k > 0 ? w_k : nullptr,
-                          stream, inert, inert ? &ic : nullptr, nullptr, nullptr, &al);
+    st.allow = &al;
+    LiveCall a; a.cfg = cfg; a.live = live; a.streams = streams; a.seg = seg; a.cnt_mean = cnt_mean; a.cnt_std = cnt_std; a.stream = stream;
+    LiveFrame f; f.Yrot = Yrot; f.Ypos = Ypos; f.Yvel = Yvel; f.Yang = Yang; f.src_rvel = src_rvel; f.src_rang = src_rang; f.src_speed = src_speed; f.contact = contact;
+    LiveOut o; o.pos = pos; o.rot = rot; o.ik_rot = ik_rot; o.bvh_pos = bvh_pos; o.bvh_euler = bvh_euler; o.idx = idx; o.valid = valid;
+    return live_step_impl(c, a, f, o, st);
 }
 
 }  // extern "C"
@@ -4021,26 +4039,20 @@ int mocha_live_ingest_step(mocha_ctx* c, const mocha_ingest_cfg* cfg, const moch
     return 0;
 }
 
-// mocha_live_step_raw (al = null) and mocha_live_step_raw_allow: one body
-static int live_step_raw_impl(mocha_ctx* c, const char* who, const mocha_post_cfg* cfg, const mocha_ingest_cfg* icfg_in, void* live, void* ingest,
-                              int streams, const float* rot, const float* pos, const int32_t* seg, const float* cnt_mean, const float* cnt_std, int k,
-                              float temperature, double* pos_out, double* rot_out, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx,
-                              int32_t* valid, int32_t* idx_k, float* w_k, void* stream, void* inert, const mocha_inert_cfg* icfg,
-                              const AllowArg* al, const MixArg* mx = nullptr) {
+// The raw steps (`who`): the front end's parameters from icfg_in and the raw frame, its staging in `ingest` as the live step's frame.
+// st: the soft stage and the inertializer's state as the caller gave them (icfg: its configuration, NULL = the default), checked here
+static int live_step_raw_impl(mocha_ctx* c, const char* who, const LiveCall& a, const mocha_ingest_cfg* icfg_in, void* ingest, const float* rot,
+                              const float* pos, const LiveOut& o, LiveStages st, const mocha_inert_cfg* icfg) {
     if (!c) return MOCHA_ERR_ARG;
-    if (streams < 1 || streams > 16) return fail(c, MOCHA_ERR_ARG, "%s: 1 <= streams <= 16", who);
+    if (a.streams < 1 || a.streams > 16) return fail(c, MOCHA_ERR_ARG, "%s: 1 <= streams <= 16", who);
     if (!ingest || !rot || !pos) return fail(c, MOCHA_ERR_ARG, "%s: null argument", who);
-    if (k != 0) {
-        int rc = soft_args(c, who, k, temperature); if (rc) return rc;
-        if (!idx_k || !w_k) return fail(c, MOCHA_ERR_ARG, "%s: null argument", who);
-    }
-    mocha_inert_cfg ic{};
-    if (inert) { int rc = inert_cfg(c, who, icfg, ic); if (rc) return rc; }
+    int rc = live_soft_check(c, who, st); if (rc) return rc;
+    if (st.inert && (rc = inert_cfg(c, who, icfg, st.icfg))) return rc;
     IngestParams p{};
-    int rc = ingest_params(c, who, icfg_in, cfg, p); if (rc) return rc;
+    if ((rc = ingest_params(c, who, icfg_in, a.cfg, p))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     if ((rc = ensure_ingest_rows(c))) return rc;
-    const IngestLayout l = ingest_layout(c, streams);
+    const IngestLayout l = ingest_layout(c, a.streams);
     char* base = static_cast<char*>(ingest);
     auto f32 = [&](size_t at) { return reinterpret_cast<float*>(base + at); };
     p.state = reinterpret_cast<double*>(base + l.state);
@@ -4048,17 +4060,19 @@ static int live_step_raw_impl(mocha_ctx* c, const char* who, const mocha_post_cf
     p.rot = rot; p.pos = pos; p.Yrot = f32(l.rot); p.Ypos = f32(l.pos); p.Yvel = f32(l.vel); p.Yang = f32(l.ang);
     p.src_rvel = f32(l.rvel); p.src_rang = f32(l.rang); p.src_speed = f32(l.speed);
     p.contact = reinterpret_cast<unsigned char*>(base + l.contact); p.have = reinterpret_cast<int32_t*>(base + l.have);
-    return live_step_impl(c, cfg, live, streams, p.Yrot, p.Ypos, p.Yvel, p.Yang, p.src_rvel, p.src_rang, p.src_speed, p.contact, seg, cnt_mean,
-                          cnt_std, pos_out, rot_out, ik_rot, bvh_pos, bvh_euler, idx, valid, k, k > 0 ? temperature : 0.f, k > 0 ? idx_k : nullptr,
-                          k > 0 || mx ? w_k : nullptr, stream, inert, inert ? &ic : nullptr, &p, icfg_in, al, mx);
+    LiveFrame f; f.Yrot = p.Yrot; f.Ypos = p.Ypos; f.Yvel = p.Yvel; f.Yang = p.Yang; f.src_rvel = p.src_rvel; f.src_rang = p.src_rang; f.src_speed = p.src_speed; f.contact = p.contact;
+    st.ingest = &p; st.ingest_cfg = icfg_in;
+    return live_step_impl(c, a, f, o, st);
 }
 
 int mocha_live_step_raw(mocha_ctx* c, const mocha_post_cfg* cfg, const mocha_ingest_cfg* icfg_in, void* live, void* ingest, int streams,
                         const float* rot, const float* pos, const int32_t* seg, const float* cnt_mean, const float* cnt_std, int k,
                         float temperature, double* pos_out, double* rot_out, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx,
                         int32_t* valid, int32_t* idx_k, float* w_k, void* stream, void* inert, const mocha_inert_cfg* icfg) {
-    return live_step_raw_impl(c, "live_step_raw", cfg, icfg_in, live, ingest, streams, rot, pos, seg, cnt_mean, cnt_std, k, temperature, pos_out,
-                              rot_out, ik_rot, bvh_pos, bvh_euler, idx, valid, idx_k, w_k, stream, inert, icfg, nullptr);
+    LiveCall a; a.cfg = cfg; a.live = live; a.streams = streams; a.seg = seg; a.cnt_mean = cnt_mean; a.cnt_std = cnt_std; a.stream = stream;
+    LiveOut o; o.pos = pos_out; o.rot = rot_out; o.ik_rot = ik_rot; o.bvh_pos = bvh_pos; o.bvh_euler = bvh_euler; o.idx = idx; o.valid = valid;
+    LiveStages st; st.k = k; st.temperature = temperature; st.idx_k = idx_k; st.w_k = w_k; st.inert = inert;
+    return live_step_raw_impl(c, "live_step_raw", a, icfg_in, ingest, rot, pos, o, st, icfg);
 }
 
 int mocha_live_step_raw_allow(mocha_ctx* c, const mocha_post_cfg* cfg, const mocha_ingest_cfg* icfg_in, void* live, void* ingest, int streams,
@@ -4069,8 +4083,10 @@ int mocha_live_step_raw_allow(mocha_ctx* c, const mocha_post_cfg* cfg, const moc
     if (!c) return MOCHA_ERR_ARG;
     if (!allow) return fail(c, MOCHA_ERR_ARG, "live_step_raw_allow: null allow masks");
     const AllowArg al{reinterpret_cast<const unsigned long long*>(allow), applied};
-    return live_step_raw_impl(c, "live_step_raw_allow", cfg, icfg_in, live, ingest, streams, rot, pos, seg, cnt_mean, cnt_std, k, temperature, pos_out,
-                              rot_out, ik_rot, bvh_pos, bvh_euler, idx, valid, idx_k, w_k, stream, inert, icfg, &al);
+    LiveStages st; st.k = k; st.temperature = temperature; st.idx_k = idx_k; st.w_k = w_k; st.inert = inert; st.allow = &al;
+    LiveCall a; a.cfg = cfg; a.live = live; a.streams = streams; a.seg = seg; a.cnt_mean = cnt_mean; a.cnt_std = cnt_std; a.stream = stream;
+    LiveOut o; o.pos = pos_out; o.rot = rot_out; o.ik_rot = ik_rot; o.bvh_pos = bvh_pos; o.bvh_euler = bvh_euler; o.idx = idx; o.valid = valid;
+    return live_step_raw_impl(c, "live_step_raw_allow", a, icfg_in, ingest, rot, pos, o, st, icfg);
 }
 
 // The live step with the mix characterize in the place of the hard one (ids (S,J), weights (S,J,6): device data every replay reads; idx
@@ -4083,8 +4099,11 @@ int mocha_live_step_mix(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, int
     int rc = mix_args(c, "live_step_mix", J); if (rc) return rc;
     if (!ids || !weights || !idx || !wnorm) return fail(c, MOCHA_ERR_ARG, "live_step_mix: null argument");
     const MixArg mx{ids, weights, J, idx, nullptr, wnorm, nullptr, nullptr};
-    return live_step_impl(c, cfg, live, streams, Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, ids, cnt_mean, cnt_std, pos, rot,
-                          ik_rot, bvh_pos, bvh_euler, idx, valid, 0, 0.f, nullptr, wnorm, stream, nullptr, nullptr, nullptr, nullptr, nullptr, &mx);
+    LiveStages st; st.mix = &mx; st.w_k = wnorm;
+    LiveCall a; a.cfg = cfg; a.live = live; a.streams = streams; a.seg = ids; a.cnt_mean = cnt_mean; a.cnt_std = cnt_std; a.stream = stream;
+    LiveFrame f; f.Yrot = Yrot; f.Ypos = Ypos; f.Yvel = Yvel; f.Yang = Yang; f.src_rvel = src_rvel; f.src_rang = src_rang; f.src_speed = src_speed; f.contact = contact;
+    LiveOut o; o.pos = pos; o.rot = rot; o.ik_rot = ik_rot; o.bvh_pos = bvh_pos; o.bvh_euler = bvh_euler; o.idx = idx; o.valid = valid;
+    return live_step_impl(c, a, f, o, st);
 }
 
 int mocha_live_step_raw_mix(mocha_ctx* c, const mocha_post_cfg* cfg, const mocha_ingest_cfg* icfg_in, void* live, void* ingest, int streams,
@@ -4095,8 +4114,10 @@ int mocha_live_step_raw_mix(mocha_ctx* c, const mocha_post_cfg* cfg, const mocha
     int rc = mix_args(c, "live_step_raw_mix", J); if (rc) return rc;
     if (!ids || !weights || !idx || !wnorm) return fail(c, MOCHA_ERR_ARG, "live_step_raw_mix: null argument");
     const MixArg mx{ids, weights, J, idx, nullptr, wnorm, nullptr, nullptr};
-    return live_step_raw_impl(c, "live_step_raw_mix", cfg, icfg_in, live, ingest, streams, rot, pos, ids, cnt_mean, cnt_std, 0, 0.f, pos_out,
-                              rot_out, ik_rot, bvh_pos, bvh_euler, idx, valid, nullptr, wnorm, stream, nullptr, nullptr, nullptr, &mx);
+    LiveStages st; st.mix = &mx; st.w_k = wnorm;
+    LiveCall a; a.cfg = cfg; a.live = live; a.streams = streams; a.seg = ids; a.cnt_mean = cnt_mean; a.cnt_std = cnt_std; a.stream = stream;
+    LiveOut o; o.pos = pos_out; o.rot = rot_out; o.ik_rot = ik_rot; o.bvh_pos = bvh_pos; o.bvh_euler = bvh_euler; o.idx = idx; o.valid = valid;
+    return live_step_raw_impl(c, "live_step_raw_mix", a, icfg_in, ingest, rot, pos, o, st, nullptr);
 }
 
 }  // extern "C"
@@ -4481,70 +4502,41 @@ int mocha_live_ours_reset(mocha_ctx* c, void* live, void* ours, int streams, con
     return 0;
 }
 
-// The body of mocha_live_step_ours and of mocha_live_step_ours_grouped (grouped: cvae_of is the device table of the characters' weight-bank
-// slots, the weights and statistics come from the weight bank, the step has its own captured graph).
-static int live_step_ours_impl(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos, const float* Yvel,
-                               const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed, const unsigned char* contact,
-                               const int32_t* seg, const float* cnt_mean, const float* cnt_std, void* ours, const mocha_ours_cfg* ocfg, double* pos,
-                               double* rot, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx, int32_t* valid, int32_t* seeded,
-                               void* stream, bool grouped, const int32_t* cvae_of) {
+// The body of mocha_live_step_ours and of mocha_live_step_ours_grouped (cvae_of non-null: the device table of the characters' weight-bank
+// slots; the weights and statistics then come from the weight bank and the step has its own captured graph).
+static int live_step_ours_impl(mocha_ctx* c, const LiveCall& a, const LiveFrame& f, const LiveOut& o, void* ours, const mocha_ours_cfg* ocfg,
+                               int32_t* seeded, bool grouped, const int32_t* cvae_of) {
     if (!c) return MOCHA_ERR_ARG;
-    if (streams < 1 || streams > 16) return fail(c, MOCHA_ERR_ARG, "live_step_ours: 1 <= streams <= 16");
-    if (!live || !Yrot || !Ypos || !Yvel || !Yang || !src_rvel || !src_rang || !src_speed || !contact || !seg || !cnt_mean || !cnt_std || !pos ||
-        !rot || !ik_rot || !idx || !valid || !seeded || (!bvh_pos) != (!bvh_euler))
-        return fail(c, MOCHA_ERR_ARG, "live_step_ours: null argument");
+    int rc = live_args(c, "live_step_ours", a, f, o); if (rc) return rc;
+    if (!seeded) return fail(c, MOCHA_ERR_ARG, "live_step_ours: null argument");
     if (!ours || !ocfg) return fail(c, MOCHA_ERR_ARG, "live_step_ours: null state buffer or configuration");
     if (grouped && !cvae_of) return fail(c, MOCHA_ERR_ARG, "live_step_ours_grouped: null cvae_of");
     if (!grouped && (!ocfg->src_cnt_mean || !ocfg->src_cnt_std || !ocfg->cha_encoded_mean || !ocfg->cha_encoded_std))
         return fail(c, MOCHA_ERR_ARG, "live_step_ours: null statistic");
     if (ocfg->noise < 0 || ocfg->noise > 2) return fail(c, MOCHA_ERR_ARG, "live_step_ours: noise must be 0 (none), 1 (given) or 2 (device)");
     if (ocfg->noise == 1 && !ocfg->eps) return fail(c, MOCHA_ERR_ARG, "live_step_ours: noise 1 needs eps");
+    const int S = a.streams;
     // the branch's stages run on all the streams in one piece (the sampler needs the whole batch between the encoder and the decoder), so
     // the workspace must hold them: mocha_live_step walks a smaller workspace chunk by chunk, this step refuses
-    if (streams > c->max_chunk)
-        return fail(c, MOCHA_ERR_ARG, "live_step_ours: %d streams exceed the workspace limit of %d windows (raise it with mocha_reserve)", streams, c->max_chunk);
+    if (S > c->max_chunk)
+        return fail(c, MOCHA_ERR_ARG, "live_step_ours: %d streams exceed the workspace limit of %d windows (raise it with mocha_reserve)", S, c->max_chunk);
     if (!c->finalized) return fail(c, MOCHA_ERR_STATE, "weights not finalised: call mocha_finalize_weights first");
     if (grouped && !c->cvb.Cw) return fail(c, MOCHA_ERR_STATE, "live_step_ours_grouped: no CVAE weight bank: call mocha_cvae_bank_create first");
     if (!grouped && !c->cvae_ready) return fail(c, MOCHA_ERR_STATE, "live_step_ours: no CVAE on this context: call mocha_cvae_load_weight and mocha_cvae_finalize first");
-    if (!c->pose_norm.p) return fail(c, MOCHA_ERR_STATE, "live_step_ours: no pose norm: call mocha_set_pose_norm first");
-    if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set_segments first");
-    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
-    mocha_post_cfg d;
-    if (!cfg) { mocha_post_cfg_default(&d); cfg = &d; }
-    PostParams p{};
-    int rc = post_params(c, cfg, p); if (rc) return rc;
-    // everything the captured region needs exists before capture begins: both workspaces, the skeleton's parents
-    if ((rc = ready(c, streams))) return rc;
-    if ((rc = ensure_bone_parents(c))) return rc;
-    if ((rc = cvae_ws(c, streams))) return rc;
+    if ((rc = live_state(c, "live_step_ours"))) return rc;
+    LiveView v;
+    if ((rc = live_view(c, a, f, o, v))) return rc;
+    if ((rc = cvae_ws(c, S))) return rc;                    // ... and the sampler's workspace: nothing in the captured region allocates
 
-    const LiveLayout l = live_layout(c, streams);
-    char* base = static_cast<char*>(live);
-    LiveRing ring;
-    ring.counters = reinterpret_cast<int32_t*>(base + l.counters);
-    ring.rot = reinterpret_cast<float*>(base + l.rot); ring.pos = reinterpret_cast<float*>(base + l.pos);
-    ring.vel = reinterpret_cast<float*>(base + l.vel); ring.ang = reinterpret_cast<float*>(base + l.ang);
-    float* xraw = reinterpret_cast<float*>(base + l.xraw);
-    float* ystage = reinterpret_cast<float*>(base + l.y);
-    float* heads = reinterpret_cast<float*>(base + l.heads);
-    float* speed = reinterpret_cast<float*>(base + l.speed);
-    int32_t* eff = reinterpret_cast<int32_t*>(base + l.eff);
-    p.heads = heads; p.speed = speed; p.src_rvel = src_rvel; p.src_rang = src_rang; p.src_speed = src_speed; p.contact = contact;
-    p.pos = pos; p.rot = rot; p.ik_rot = ik_rot; p.bvh_pos = bvh_pos; p.bvh_euler = bvh_euler;
-    p.n_clips = streams; p.n_frames = 1; p.state = reinterpret_cast<double*>(base + l.post); p.valid = valid;
-    const OursLayout ol = ours_layout(streams);
+    const OursLayout ol = ours_layout(S);
     char* ob = static_cast<char*>(ours);
+    auto of32 = [&](size_t at) { return reinterpret_cast<float*>(ob + at); };
     int32_t* ocnt = reinterpret_cast<int32_t*>(ob + ol.counters);
-    float* prev = reinterpret_cast<float*>(ob + ol.prev);
-    float* cnt_o = reinterpret_cast<float*>(ob + ol.cnt);
-    float* cond = reinterpret_cast<float*>(ob + ol.cond);
-    float* vae = reinterpret_cast<float*>(ob + ol.vae);
-    float* eps_o = reinterpret_cast<float*>(ob + ol.eps);
-    float* mu = reinterpret_cast<float*>(ob + ol.mu);
-    float* logvar = reinterpret_cast<float*>(ob + ol.logvar);
+    float *prev = of32(ol.prev), *cnt_o = of32(ol.cnt), *cond = of32(ol.cond), *vae = of32(ol.vae), *eps_o = of32(ol.eps), *mu = of32(ol.mu),
+          *logvar = of32(ol.logvar);
     mocha_ours_cfg oc = *ocfg;
     if (grouped) oc.src_cnt_mean = oc.src_cnt_std = oc.cha_encoded_mean = oc.cha_encoded_std = nullptr;      // ignored: the slot's statistics serve
-    const int J = c->cfg.V + 1, V = c->cfg.V, S = streams;
+    const int J = c->cfg.V + 1, V = c->cfg.V;
     const int nseg = c->bank.segments();
     // grouped: the condition kernel leaves every stream's slot in live_slot, the `which` of the sampler's grouped launches
     const OursGroup grp{cvae_of, c->cvb.stored.p, c->cvb.stats.p, c->cvb.Cw, c->cvb.live_slot.p};
@@ -4554,61 +4546,57 @@ static int live_step_ours_impl(mocha_ctx* c, const mocha_post_cfg* cfg, void* li
     auto tail = [&](const float* cha, hipStream_t cs) -> int {
         int r = run_decoder(c, WS(c, "enc_s"), cha, S, WS(c, "dec"), cs);
         if (r) return r;
-        return run_to_mot(c, WS(c, "dec"), S, ystage, cs, true);
+        return run_to_mot(c, WS(c, "dec"), S, v.ystage, cs, true);
     };
     // ring push + featurize -> embed, encoder, cnt and the z-scored query -> segmented match -> condition (mode per stream, noise) -> CVAE
-    // sampler -> state update -> decoder on the streams' character features -> to_mot -> pose heads -> one post-processing frame
+    // sampler -> state update -> decoder on the streams' character features -> to_mot -> pose heads -> one post-processing frame.  Not
+    // the segmented characterize: the launches are not steps of the walk order (IEX), the instance norm also writes cnt into the state,
+    // and the sampler sits between the encoder and the decoder
     auto body = [&](hipStream_t cs) -> int {
         LAUNCH(c, cs, "mocha_live_push", "live.push", S * 60.0 * J * 150, S * (60.0 * J * (13 + 15) + J * 26.0) * 4,
-               launch_live_push(ring, Yrot, Ypos, Yvel, Yang, seg, c->bone_parents.p, xraw, eff, valid, S, J, cs, nullptr,
+               launch_live_push(v.ring, f.Yrot, f.Ypos, f.Yvel, f.Yang, a.seg, c->bone_parents.p, v.xraw, v.eff, o.valid, S, J, cs, nullptr,
                                 c->bank.resident ? c->bank.seg_dev.p : nullptr, c->bank.resident ? c->bank.segments() : 0));
         c->lane = 0; c->cur = 0;
         int r;
-        if ((r = run_embed(c, xraw, S, WS(c, "x5"), true, cs, true))) return r;
+        if ((r = run_embed(c, v.xraw, S, WS(c, "x5"), true, cs, true))) return r;
         if ((r = run_encoder(c, WS(c, "x5"), S, WS(c, "enc_s"), cs))) return r;
         InormExtra ex = IEX(c);
         if (c->bank.is_bf16) { ex.centre = c->bank.center.p; ex.zc = WS(c, "qc"); }
         LAUNCH(c, cs, "mocha_instnorm", "mvn", 0.0, S * 90.0 * 256 * 4 * (c->bank.is_bf16 ? 4.0 : 3.0),
-               launch_instnorm(WS(c, "enc_s"), cnt_o, nullptr, cnt_mean, cnt_std, WS(c, "qnm"), S, 90, cs, &ex));
+               launch_instnorm(WS(c, "enc_s"), cnt_o, nullptr, a.cnt_mean, a.cnt_std, WS(c, "qnm"), S, 90, cs, &ex));
         int32_t* gx = SET(c).idx_ws.p;
-        if ((r = seg_match(c, WS(c, c->bank.is_bf16 ? "qc" : "qnm"), S, eff, idx, gx, nullptr, cs))) return r;
+        if ((r = seg_match(c, WS(c, c->bank.is_bf16 ? "qc" : "qnm"), S, v.eff, o.idx, gx, nullptr, cs))) return r;
         LAUNCH(c, cs, "mocha_live_ours_condition", "ours.condition", 0.0, S * 180.0 * 256 * 8,
-               launch_live_ours_condition(ocnt, eff, nseg, cnt_o, prev, oc.src_cnt_mean, oc.src_cnt_std, oc.cha_encoded_mean, oc.cha_encoded_std,
+               launch_live_ours_condition(ocnt, v.eff, nseg, cnt_o, prev, oc.src_cnt_mean, oc.src_cnt_std, oc.cha_encoded_mean, oc.cha_encoded_std,
                                           cond, oc.noise, oc.eps, oc.seed, eps_o, S, cs, gp));
         if ((r = cvae_sample_impl(c, cond, S, vae, mu, logvar, oc.noise ? eps_o : nullptr, cs, grouped ? grp.slot : nullptr))) return r;
         LAUNCH(c, cs, "mocha_live_ours_update", "ours.update", 0.0, S * 90.0 * 256 * 12,
-               launch_live_ours_update(ocnt, eff, vae, oc.cha_encoded_mean, oc.cha_encoded_std, c->bank.enc, gx, c->bank.N, prev, seeded, S, cs, gp));
+               launch_live_ours_update(ocnt, v.eff, vae, oc.cha_encoded_mean, oc.cha_encoded_std, c->bank.enc, gx, c->bank.N, prev, seeded, S, cs, gp));
         if ((r = tail(prev, cs))) return r;
-        LAUNCH(c, cs, "mocha_pose_heads", "live.heads", 0.0, S * (60.0 * 12 + V * 28.0 * 4), launch_pose_heads(ystage, heads, speed, S, c->cfg.T, V, cs));
+        LAUNCH(c, cs, "mocha_pose_heads", "live.heads", 0.0, S * (60.0 * 12 + V * 28.0 * 4), launch_pose_heads(v.ystage, v.heads, v.speed, S, c->cfg.T, V, cs));
         LAUNCH(c, cs, "mocha_post_clip", "live.post", 0.0, (double)S * (V * 13.0 * 4 + J * 11.0 * 8 + 2.0 * POST_STATE_DOUBLES * 8),
-               launch_post_step(p, cs));
+               launch_post_step(v.post, cs));
         return 0;
     };
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = (hipStream_t)a.stream;
     if (c->prof_on) return body(s);
 
-    mocha_ctx::StepKey key;
-    key.x = live; key.mean = cnt_mean; key.sd = cnt_std; key.idx = idx; key.seg = seg; key.windows = streams; key.raw = true;
-    const void* ptrs[17] = {Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, pos, rot, ik_rot, bvh_pos, bvh_euler, valid, nullptr, nullptr, nullptr};
-    for (int i = 0; i < 17; ++i) key.live[i] = ptrs[i];
+    mocha_ctx::StepKey& key = v.key;
     const void* optrs[7] = {ours, oc.src_cnt_mean, oc.src_cnt_std, oc.cha_encoded_mean, oc.cha_encoded_std, oc.noise == 1 ? oc.eps : nullptr, seeded};
     for (int i = 0; i < 7; ++i) key.ours[i] = optrs[i];
     key.noise = oc.noise; key.seed = oc.noise == 2 ? oc.seed : 0;
-    key.post = *cfg;
     key.cvae_of = cvae_of;
-    auto& g = grouped ? c->ours_grouped_step : c->ours_step;
-    if (!(g.exec && g.key == key && g.generation == c->generation)) {
+    mocha_ctx::StepGraph& g = c->steps[grouped ? mocha_ctx::STEP_OURS_GROUPED : mocha_ctx::STEP_OURS];
+    if (!step_holds(c, g, key)) {
         // Before a capture: one eager pass over staging alone - mocha_live_step's characterize of zeroed windows with every id -1, then the
         // sampler on a zeroed condition and the literal decoder on its sample - so that whatever the kernels of the step make on first
         // use (the plane GEMMs' weight images, the style MLP's float64 weights) exists.  No counter, ring, `prev` or post state moves.
         // (grouped: the grouped sampler with every slot -1 - no weight is read, the sample is zeros.)
-        HIPCHK(c, hipMemsetAsync(xraw, 0, (size_t)S * 60 * J * c->cfg.C_in * sizeof(float), s));
-        HIPCHK(c, hipMemsetAsync(eff, 0xFF, (size_t)S * sizeof(int32_t), s));
+        HIPCHK(c, hipMemsetAsync(v.xraw, 0, (size_t)S * 60 * J * c->cfg.C_in * sizeof(float), s));
+        HIPCHK(c, hipMemsetAsync(v.eff, 0xFF, (size_t)S * sizeof(int32_t), s));
         HIPCHK(c, hipMemsetAsync(cond, 0, (size_t)S * 180 * 256 * sizeof(float), s));
-        c->lane = 0;
-        rc = characterize_impl(c, xraw, S, cnt_mean, cnt_std, ystage, nullptr, s, true, eff);
-        c->cur = 0;
-        if (rc) return rc;
+        SegSelect hard; hard.seg = v.eff;
+        if ((rc = characterize_segmented_set0(c, SegWindows{v.xraw, S, a.cnt_mean, a.cnt_std, v.ystage, true}, hard, s))) return rc;
         if ((rc = cvae_sample_impl(c, cond, S, vae, mu, logvar, nullptr, s, grouped ? c->cvb.none.p : nullptr))) return rc;
         if ((rc = tail(vae, s))) return rc;
     }
@@ -4620,8 +4608,10 @@ int mocha_live_step_ours(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, in
                          const int32_t* seg, const float* cnt_mean, const float* cnt_std, void* ours, const mocha_ours_cfg* ocfg, double* pos,
                          double* rot, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx, int32_t* valid, int32_t* seeded,
                          void* stream) {
-    return live_step_ours_impl(c, cfg, live, streams, Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, seg, cnt_mean, cnt_std, ours,
-                               ocfg, pos, rot, ik_rot, bvh_pos, bvh_euler, idx, valid, seeded, stream, false, nullptr);
+    LiveCall a; a.cfg = cfg; a.live = live; a.streams = streams; a.seg = seg; a.cnt_mean = cnt_mean; a.cnt_std = cnt_std; a.stream = stream;
+    LiveFrame f; f.Yrot = Yrot; f.Ypos = Ypos; f.Yvel = Yvel; f.Yang = Yang; f.src_rvel = src_rvel; f.src_rang = src_rang; f.src_speed = src_speed; f.contact = contact;
+    LiveOut o; o.pos = pos; o.rot = rot; o.ik_rot = ik_rot; o.bvh_pos = bvh_pos; o.bvh_euler = bvh_euler; o.idx = idx; o.valid = valid;
+    return live_step_ours_impl(c, a, f, o, ours, ocfg, seeded, false, nullptr);
 }
 
 int mocha_live_step_ours_grouped(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos,
@@ -4629,8 +4619,10 @@ int mocha_live_step_ours_grouped(mocha_ctx* c, const mocha_post_cfg* cfg, void* 
                                  const unsigned char* contact, const int32_t* seg, const float* cnt_mean, const float* cnt_std, void* ours,
                                  const mocha_ours_cfg* ocfg, const int32_t* cvae_of, double* pos, double* rot, double* ik_rot, double* bvh_pos,
                                  double* bvh_euler, int32_t* idx, int32_t* valid, int32_t* seeded, void* stream) {
-    return live_step_ours_impl(c, cfg, live, streams, Yrot, Ypos, Yvel, Yang, src_rvel, src_rang, src_speed, contact, seg, cnt_mean, cnt_std, ours,
-                               ocfg, pos, rot, ik_rot, bvh_pos, bvh_euler, idx, valid, seeded, stream, true, cvae_of);
+    LiveCall a; a.cfg = cfg; a.live = live; a.streams = streams; a.seg = seg; a.cnt_mean = cnt_mean; a.cnt_std = cnt_std; a.stream = stream;
+    LiveFrame f; f.Yrot = Yrot; f.Ypos = Ypos; f.Yvel = Yvel; f.Yang = Yang; f.src_rvel = src_rvel; f.src_rang = src_rang; f.src_speed = src_speed; f.contact = contact;
+    LiveOut o; o.pos = pos; o.rot = rot; o.ik_rot = ik_rot; o.bvh_pos = bvh_pos; o.bvh_euler = bvh_euler; o.idx = idx; o.valid = valid;
+    return live_step_ours_impl(c, a, f, o, ours, ocfg, seeded, true, cvae_of);
 }
 
 int mocha_column_stats(mocha_ctx* c, const float* x, int64_t N, float* mean, float* std_, void* stream) {
