@@ -20,7 +20,9 @@ also written to <out>/from_raw.npz.
 
 With --src-bvh A --cha-bvh B the same route starts from two BVH FILES (source, character; the 24-joint 'mocha' skeleton in file order,
 at least 31 frames each): load_bvh reads the hierarchy on the host and parses the MOTION text on the device, and its two arrays go into
-ingest_clips with the files' rotation order and frame rate.  A clip of n frames gives n - 15 windows; --frames is ignored.
+ingest_clips with the files' rotation order and frame rate.  A clip of n frames gives n - 15 windows; --frames is ignored.  The model, its
+windows and the root fits are fixed to 60 frames per second: --resample 60 brings files of another rate there first (slerp / linear on the
+device, load_bvh(fps=60)); without it a file's rate only scales the finite differences.
 
     file  --load_bvh-->  raw clip  --ingest_clips-->  ...  as --from-raw, <out>/from_raw.npz included
 """
@@ -44,9 +46,14 @@ ap.add_argument("--out", default="gpurun_out/demo")
 ap.add_argument("--from-raw", action="store_true", help="start from raw mocap clips: ingest_clips -> clip_windows -> featurize")
 ap.add_argument("--src-bvh", help="the source clip as a BVH file (with --cha-bvh): the --from-raw route on files")
 ap.add_argument("--cha-bvh", help="the character clip as a BVH file")
+ap.add_argument("--resample", type=float, metavar="R",
+                help="with --src-bvh / --cha-bvh: bring files of another frame rate to R frames per second first (load_bvh(fps=R); the model "
+                     "is fixed to 60)")
 a = ap.parse_args()
 if bool(a.src_bvh) != bool(a.cha_bvh):
     ap.error("--src-bvh and --cha-bvh go together")
+if a.resample is not None and not a.src_bvh:
+    ap.error("--resample applies to the --src-bvh / --cha-bvh route")
 if a.src_bvh:
     a.from_raw = True
 os.makedirs(a.out, exist_ok=True)
@@ -70,11 +77,13 @@ if a.from_raw:
     from mocha_sigasia2023_amd import clip_windows, ingest_clips  # noqa: E402
     if a.src_bvh:
         from mocha_sigasia2023_amd import IngestConfig, load_bvh  # noqa: E402
-        files = load_bvh(model, [a.src_bvh, a.cha_bvh])
+        files = load_bvh(model, [a.src_bvh, a.cha_bvh], fps=a.resample)
         if len(files.names) != model.V or min(files.lengths) < 31:
-            ap.error(f"the files must hold the {model.V} joints of the model's skeleton and at least 31 frames each")
+            ap.error(f"the files must hold the {model.V} joints of the model's skeleton and at least 31 frames each"
+                     + (f" at {a.resample:g} fps (they have {files.lengths} from {files.source_fps} fps)" if a.resample else ""))
         lengths, N = files.lengths, files.lengths[0] - 15
-        clips = ingest_clips(model, files.rot, files.pos, lengths, raw=IngestConfig(order=files.order, fps=round(1.0 / files.frametime)))
+        fps = a.resample if a.resample is not None else round(1.0 / files.frametime)
+        clips = ingest_clips(model, files.rot, files.pos, lengths, raw=IngestConfig(order=files.order, fps=fps))
     else:
         if N < 16:
             ap.error("--from-raw needs at least 16 windows per clip: a clip of N + 15 frames gives N windows, and 31 frames are the least")

@@ -3,7 +3,7 @@
 mocap frame at a time through ``LiveSession`` - ring push + featurize, segmented characterize, pose heads and one post-processing
 frame per push, one captured graph - and written as two BVH files.
 
-    python examples/live_demo.py [--frames 180] [--out bench_outputs/live_demo] [--ours [--seed 7]] [--switch 120 [--inertial 0.1]] [--raw L]
+    python examples/live_demo.py [--frames 180] [--out bench_outputs/live_demo] [--ours [--seed 7]] [--switch 120 [--inertial 0.1]] [--raw L [--source-fps R]]
                                  [--actions A,B[:F]] [--load-at F] [--ours-per-character] [--mix a:b:FRAMES | --mix-parts a:b:MASK]
 
 ``--ours`` runs the CVAE ("Ours") branch inside the same graph (``LiveOursSession``): each stream's character feature is seeded with
@@ -22,6 +22,9 @@ the reference's per-bone inertializers on the device).  The size of the largest 
 ``--raw L``: the streams push RAW mocap frames - local Euler rotations in degrees and local positions in centimetres of the 24 joints, as
 a BVH file holds them (a synthetic walk) - and the mocap front end inside the same graph makes the root bone, the velocities and the foot
 contacts (``LiveSession(raw=L)``, ``push_raw``), L = 0..18 frames of lookahead.  The first pose then comes with push 90.
+``--source-fps R`` (with ``--raw``): the producer runs at R frames per second (90, 100, 120, 30 ...) while the model, its window and the
+root fits stay at 60.  A ``StreamResampler`` in front of a quaternion-input session takes one source frame per push and hands over the 0..4
+frames at 60 fps that it completes - one launch in front of the captured step, not inside it; ``--frames`` still counts pushes at 60 fps.
 
 ``--actions A,B[:F]``: the bank's entries carry action labels in runs of 25 (a synthetic stand-in for ``load_bank(path)["action_label"]``:
 200 entries, actions 0 .. 7) and, from frame F on (default: from the start), every stream is matched among its character's entries of the
@@ -49,8 +52,9 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mocha_sigasia2023_amd import (Generator, LiveOursSession, LiveSession, MultiCharacterBank, PostProcessor, ResidentCharacterBank,  # noqa: E402
-                                   build_bank, synthetic, synthetic_state_dict, write_bvh)
+from mocha_sigasia2023_amd import (Generator, IngestConfig, LiveOursSession, LiveSession, MultiCharacterBank, PostProcessor,  # noqa: E402
+                                   ResidentCharacterBank, StreamResampler, build_bank, resample_clips, synthetic, synthetic_state_dict, write_bvh)
+from mocha_sigasia2023_amd.ingest import resample_ratio  # noqa: E402
 from mocha_sigasia2023_amd.skeleton import LAYOUTS  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -63,6 +67,8 @@ ap.add_argument("--soft", nargs=2, metavar=("K", "T"), help="soft matching: the 
 ap.add_argument("--switch", type=int, default=None, metavar="FRAME", help="stream 0 takes character 1 from that frame on")
 ap.add_argument("--inertial", type=float, default=None, metavar="HALFLIFE", help="inertialize character switches with that half-life in seconds")
 ap.add_argument("--raw", type=int, default=None, metavar="L", help="push raw mocap frames; the front end runs in the graph with L frames of lookahead")
+ap.add_argument("--source-fps", type=float, default=None, metavar="R", help="with --raw: the mocap producer runs at R frames per second; a "
+                "StreamResampler in front of the session brings its frames to the model's 60")
 ap.add_argument("--actions", default=None, metavar="A,B[:F]", help="allow only these action labels (0..7 here), from frame F on")
 ap.add_argument("--load-at", type=int, default=None, metavar="FRAME", help="start on a resident bank; at that frame a third character is added in "
                 "place and stream 1 switches to it")
@@ -97,6 +103,8 @@ if a.actions:
     allow_mask, allow_from = action_mask([int(v) for v in spec.split(",")]), int(at) if at else 0
 if a.ours and a.raw is not None:
     raise SystemExit("--raw does not apply to --ours: the CVAE session has no mocap front end")
+if a.source_fps is not None and a.raw is None:
+    raise SystemExit("--source-fps needs --raw: it is the raw mocap producer that runs at another rate")
 if a.ours and a.inertial is not None:
     raise SystemExit("--inertial does not apply to --ours: that branch seeds again on a switch and keeps its own chain state")
 if a.ours and a.soft:
@@ -160,7 +168,8 @@ elif a.ours:                                                          # test_ful
     sess = LiveOursSession(bank, cnt_mean, cnt_std, synthetic_cvae_state_dict(99, 1.0), *stats, streams=S, post=PostProcessor(model),
                            noise="device", seed=a.seed)
 else:
-    sess = LiveSession(bank, cnt_mean, cnt_std, streams=S, post=PostProcessor(model), soft=soft, inertial=a.inertial, raw=a.raw,
+    raw_cfg = a.raw if a.source_fps is None else IngestConfig(lookahead=a.raw, order=None)      # the resampler hands over quaternions
+    sess = LiveSession(bank, cnt_mean, cnt_std, streams=S, post=PostProcessor(model), soft=soft, inertial=a.inertial, raw=raw_cfg,
                        constrained=bool(a.actions), mix=2 if mix_ids else None)
 if mix_ids:
     sess.set_mix((mix_ids, np.stack([mix_mask, 1 - mix_mask]) if mix_mask is not None else [1.0, 0.0]))
@@ -168,6 +177,29 @@ if a.raw is not None:
     raw = [synthetic.raw_walk_clip(LAYOUTS["mocha"]["parents"], F, seed=40 + s) for s in range(S)]
     raw_rot = torch.from_numpy(np.stack([r[0] for r in raw])).to(dev)  # (S, F, 24, 3) degrees, 'zyx'
     raw_pos = torch.from_numpy(np.stack([r[1] for r in raw])).to(dev)  # (S, F, 24, 3) centimetres
+if a.source_fps is not None:
+    # The producer at R frames per second: the same walks sampled at R (whole clips, 60 -> R), then pushed one source frame at a time through
+    # a StreamResampler (R -> 60) in front of the session.  Its outputs are quaternions and positions at 60 fps: F of them per stream.
+    num, den = resample_ratio(a.source_fps, 60)
+    n_src = -(-(F - 1) * num // den) + 1                              # source frames that give at least F outputs
+    need = -(-(n_src - 1) * den // num) + 1                           # 60 fps frames that give n_src source frames
+    raw = [synthetic.raw_walk_clip(LAYOUTS["mocha"]["parents"], max(need, F), seed=40 + s) for s in range(S)]
+    prod_rot, prod_pos, prod_len = resample_clips(model, np.concatenate([r[0] for r in raw]), np.concatenate([r[1] for r in raw]),
+                                                  [len(r[0]) for r in raw], 60, a.source_fps)
+    prod_rot = prod_rot.view(S, prod_len[0], 24, 4)[:, :n_src].contiguous()
+    prod_pos = prod_pos.view(S, prod_len[0], 24, 3)[:, :n_src].contiguous()
+    resampler = StreamResampler(model, a.source_fps, 60, order=None, streams=S)
+
+
+def resampled_frames():
+    """The producer's frames through the StreamResampler: one launch per source frame, 0..4 frames at 60 fps out of each."""
+    for j in range(prod_rot.shape[1]):
+        n_out = resampler.push(prod_rot[:, j], prod_pos[:, j])
+        for e in range(n_out):
+            yield resampler.out["rot"][:, e], resampler.out["pos"][:, e]
+
+
+at_60 = resampled_frames() if a.source_fps is not None else None
 
 
 def push(f, characters=None):
@@ -180,6 +212,8 @@ def push(f, characters=None):
     if a.raw is not None:
         if kw:
             sess.set_allow(kw["allow"])
+        if at_60 is not None:
+            return sess.push_raw(*next(at_60), characters=characters)
         return sess.push_raw(raw_rot[:, f], raw_pos[:, f], characters=characters)
     return sess.push(*[torch.stack([src[s][k][f] for s in range(S)]) for k in range(4)],
                      *[torch.stack([per[s][k][f] for s in range(S)]) for k in range(4)], characters=characters, **kw)
@@ -187,6 +221,9 @@ def push(f, characters=None):
 
 push(0, characters=[0, 1])                                            # the first push captures the step
 sess.reset()
+if a.source_fps is not None:
+    resampler.reset()
+    at_60 = resampled_frames()
 torch.cuda.synchronize(); t0 = time.perf_counter()
 pos, eul, applied, seeded = [], [], [], []
 if a.actions:

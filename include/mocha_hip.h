@@ -851,6 +851,52 @@ int mocha_clip_windows(mocha_ctx* ctx, const float* pos, const float* vel, const
                        float* Yrot, float* Ypos, float* Yvel, float* Yang, unsigned char* Ycontact, void* stream);
 int mocha_mirror_map_default(int layout, int32_t* map);
 
+/* RESAMPLING in front of the calls above: the network, the 60-frame windows, the 15- / 31-tap root fits and the bank are fixed to 60 frames
+ * per second (generate_database.py:148-149, motion/bvh.py:179); cfg->fps only scales the finite differences.  These calls take (rotations,
+ * positions) at a source rate to (unit quaternions w,x,y,z, positions) at the target rate: rot_out / pos_out are what mocha_ingest_clips and
+ * mocha_live_ingest_step read with rot_format = 0 and fps = the target rate.  The reference has no resampler; the definition uses its
+ * quaternion primitives only.  The step between outputs is num / den source frames: source_fps / target_fps reduced, each term 1..4096.
+ *   count    a clip of n >= 1 source frames gives m = floor((n-1) den / num) + 1 outputs.
+ *   output k t = k num in 64-bit integers, i = t div den, a = (double)(t mod den) / (double)den.  q: the clip's quaternions in float64 -
+ *            quat.from_euler(np.radians(e), order) (quat.py:57-67) or the quaternions as given - sign-unrolled along time (quat.unroll,
+ *            :135-141).  a == 0: the output is q[i], p[i] with no arithmetic, and frame i+1 is not read.  Otherwise the rotation is
+ *            mul(from_scaled_angle_axis(a * to_scaled_angle_axis(abs(mul_inv(q[i+1], q[i])))), q[i]) (:18-19, 112-126, 149-164, the eps = 1e-5
+ *            branches kept): the constant angular velocity the reference's difference formula gives the interval; it agrees with the
+ *            textbook slerp to 2.3e-16 and is unit length to 3.4e-16.  The position is p[i] + a (p[i+1] - p[i]) in the file's units (no
+ *            unit scale here: the ingester applies it).  Float64 on the fp32 inputs, rounded to fp32 once at the output.
+ *   mocha_resample_frames     : HOST only.  m for one clip; negative (MOCHA_ERR_ARG) for n < 1, n >= 2^31 or a term outside 1..4096.  m may
+ *                               exceed 2^31.
+ *   mocha_resample_clips      : n_clips clips concatenated along the frame axis (offsets_in as clip_offsets above; a clip may have ONE frame);
+ *                               num / den / offsets_out are host arrays, one ratio per clip, so files of different rates share a call.
+ *                               offsets_out (n_clips + 1) must be the prefix sums of mocha_resample_frames.  rot (F,V,4) or (F,V,3) Euler
+ *                               degrees (rot_format 0 / 1 and euler_order[3] as in mocha_ingest_cfg; euler_order may be NULL for
+ *                               quaternions), pos (F,V,3); rot_out (F',V,4), pos_out (F',V,3), F' = offsets_out[n_clips].  Three launches:
+ *                               the ingester's quaternion and unroll kernels on the context's clip workspace (60 V bytes per source frame),
+ *                               then one thread per (output frame, joint).  Nothing crosses a clip boundary.  NOT capture-safe: waits for
+ *                               `stream` once for its tables and may grow the workspace, as mocha_ingest_clips.
+ *   mocha_resample_state_bytes: the size of the streaming state of `streams` streams: per joint the previous unrolled quaternion, its
+ *                               position and its unroll sign in float64, and two words per stream (fresh, have).  All-zero = no frame seen.
+ *   mocha_resample_reset      : the listed streams (which, n; NULL = all) have seen no frame.  Enqueued on `stream`.
+ *   mocha_resample_step       : ONE source frame of `streams` streams in lockstep, rot (S,V,4|3), pos (S,V,3): push number push_index (from 0)
+ *                               writes the outputs k with floor((push_index-1) den / num) < k <= floor(push_index den / num), the e-th of them
+ *                               to rot_out[s][e] / pos_out[s][e] of rot_out (S,4,V,4), pos_out (S,4,V,3); *n_out = their number (0..4), the
+ *                               same for every stream, computed on the host from the integers alone.  Rows e >= *n_out are not written.
+ *                               A stream without a predecessor (after mocha_resample_reset, or an all-zero state) emits the new frame
+ *                               for every output of that push.  The outputs of pushes 0, 1, 2, ... concatenated are mocha_resample_clips'
+ *                               of the same frames BIT FOR BIT (both kernels call one device function).  One launch, no allocation, no
+ *                               synchronisation, capture-safe (push_index, num, den are baked into a captured launch).
+ * Refusals (MOCHA_ERR_ARG, nothing launched): a NULL required pointer; streams outside 1..16; num or den outside 1..4096; den > 4 num in
+ * the step (more than four outputs per source frame: at a 60 fps target, sources below 15 fps); offsets_out that are not the prefix sums.
+ * What it is not: linear / slerp only (no cubic interpolation), no low-pass filter before decimation, one rate per streaming state. */
+int64_t mocha_resample_frames(int64_t n, int num, int den);
+int mocha_resample_clips(mocha_ctx* ctx, int rot_format, const int* euler_order, const float* rot, const float* pos,
+                         const int32_t* offsets_in, const int32_t* num, const int32_t* den, int n_clips, const int32_t* offsets_out,
+                         float* rot_out, float* pos_out, void* stream);
+int64_t mocha_resample_state_bytes(const mocha_ctx* ctx, int streams);
+int mocha_resample_reset(mocha_ctx* ctx, void* state, int streams, const int32_t* which, int n, void* stream);
+int mocha_resample_step(mocha_ctx* ctx, int rot_format, const int* euler_order, void* state, int streams, const float* rot, const float* pos,
+                        int num, int den, int64_t push_index, float* rot_out, float* pos_out, int32_t* n_out, void* stream);
+
 /* BVH TEXT in front of mocha_ingest_clips: what the reference's loader (motion/bvh.py:22-138) returns - Euler degrees in file channel
  * order and positions in file units per joint - as the two fp32 device arrays mocha_ingest_clips reads.  The hierarchy is read on the
  * host, the numbers of the MOTION block (over 99.9 % of a file) are parsed on the device.

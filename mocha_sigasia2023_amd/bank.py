@@ -23,6 +23,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Optional
 
 import numpy as np
@@ -135,14 +136,27 @@ def build_database_from_clips(model: Generator, clips, style_labels, action_labe
             "content_labels": labels, "action_labels": labels, "contact_states": out["contact"].cpu().numpy().astype(np.int8)}
 
 
-def build_database_from_bvh(model: Generator, paths, style_labels, action_labels, mirror: bool = True, raw=None, post=None, joints=None) -> dict:
+def build_database_from_bvh(model: Generator, paths, style_labels, action_labels, mirror: bool = True, raw=None, post=None, joints=None,
+                            fps=None) -> dict:
     """BVH files -> the motion database: ``bvh.load_bvh`` (the MOTION text parsed on the device) followed by
     ``build_database_from_clips``; the files' numbers reach the database without a host copy.  ``joints``: the file's joints in the model
     layout's order (names or indices; None = all, in file order).  ``raw`` defaults to ``IngestConfig(order=<the files' rotation order>,
-    fps=round(1 / <the first file's frame time>))``."""
+    fps=round(1 / <the first file's frame time>))``.  ``fps=R``: files of another rate are resampled to R on the device first
+    (``load_bvh(fps=R)``) and ``raw`` defaults to ``IngestConfig(order=<what load_bvh returned>, fps=R)``; a clip that falls under 31
+    frames that way raises a ValueError naming the file.  Without it a file's rate only scales the finite differences: a 120 fps file
+    gives windows of half a second."""
     from .bvh import load_bvh
     from .ingest import IngestConfig
-    clips = load_bvh(model, paths, joints=joints)
+    clips = load_bvh(model, paths, joints=joints, fps=fps)
+    if fps is not None:
+        names = [paths] if isinstance(paths, (str, os.PathLike, bytes, bytearray, memoryview)) else list(paths)
+        for i, (n, w) in enumerate(zip(clips.lengths, names)):
+            if n < 31:
+                w = os.fspath(w) if isinstance(w, (str, os.PathLike)) else f"file {i}"
+                raise ValueError(f"build_database_from_bvh: {w} has {n} frames at {fps} fps (source {clips.source_fps[i]} fps); "
+                                 "a clip needs at least 31")
+        if raw is None:
+            raw = IngestConfig(order=clips.order, fps=float(fps))
     if len(clips.names) != model.V:
         raise ValueError(f"build_database_from_bvh: the files give {len(clips.names)} joints, the model's layout has {model.V}: select with joints=")
     if raw is None:

@@ -65,11 +65,13 @@ def read_bvh_header(path_or_bytes) -> BvhHeader:
 class BvhClips:
     """``load_bvh``'s result: ``rot`` / ``pos`` (F,V,3) fp32 on the device, the clips concatenated along the frame axis; ``lengths``
     their frame counts; ``names``, ``parents``, ``offsets`` (V,3) float64 of the selected joints in output order; ``order``;
-    ``frametime`` (the first file's); ``tokens`` / ``slow_tokens``: how many numbers were read, and how many of them the host converted."""
+    ``frametime`` (the first file's); ``tokens`` / ``slow_tokens``: how many numbers were read, and how many of them the host converted;
+    ``source_fps``: each file's frame rate.  After resampling (``load_bvh(fps=R)`` on files of another rate) ``order`` is None, ``rot``
+    is (F',V,4) unit quaternions, ``lengths`` are the new frame counts and ``frametime`` is 1 / R."""
 
-    def __init__(self, rot, pos, lengths, names, parents, offsets, order, frametime, tokens, slow_tokens):
+    def __init__(self, rot, pos, lengths, names, parents, offsets, order, frametime, tokens, slow_tokens, source_fps=None):
         self.rot, self.pos, self.lengths, self.names, self.parents, self.offsets = rot, pos, lengths, names, parents, offsets
-        self.order, self.frametime, self.tokens, self.slow_tokens = order, frametime, tokens, slow_tokens
+        self.order, self.frametime, self.tokens, self.slow_tokens, self.source_fps = order, frametime, tokens, slow_tokens, source_fps
 
     def clips(self):
         """[(rot, pos)] per clip: views of the device arrays, as ``bank.build_database_from_clips`` takes them."""
@@ -95,13 +97,17 @@ def _select(hdr: BvhHeader, joints) -> List[int]:
     return pick
 
 
-def load_bvh(model: Generator, paths: Union[str, os.PathLike, bytes, Sequence], joints: Optional[Sequence] = None) -> BvhClips:
+def load_bvh(model: Generator, paths: Union[str, os.PathLike, bytes, Sequence], joints: Optional[Sequence] = None, fps=None,
+             source_fps=None) -> BvhClips:
     """One or many BVH files (paths, or the files' bytes) -> ``BvhClips`` on ``model``'s device.  All files must share one hierarchy
     (names, parents, channels, rotation order), else ValueError.  ``joints``: names or file joint indices in the order the output should
     have (the model layout's); None = every joint in file order.  The parents of a selection are the nearest selected ancestors.
     With three channels per joint a joint's position is its file's OFFSET (bvh.py:97): files with equal OFFSETs share a call of
     ``mocha_bvh_motion`` (up to 2 GiB of text), a file whose OFFSETs differ starts a new one; ``offsets`` of the result are the first
-    file's.  Waits for the current stream once per call; not for graph capture."""
+    file's.  Waits for the current stream once per call; not for graph capture.
+    ``fps=R``: the clips are brought to R frames per second (``ingest.resample_clips``, one call for all files).  A file's own rate is
+    ``round(1 / frametime)``; ``source_fps`` (one value, or one per file) overrides it.  If every file is at R already the result is the
+    Euler arrays as read; otherwise ``order`` is None, ``rot`` holds quaternions and ``frametime`` is 1 / R.  ``fps=None``: as read."""
     if isinstance(paths, (str, os.PathLike, bytes, bytearray, memoryview)):
         paths = [paths]
     if not len(paths):
@@ -177,5 +183,22 @@ def load_bvh(model: Generator, paths: Union[str, os.PathLike, bytes, Sequence], 
         while q >= 0 and q not in index:
             q = int(h0.parents[q])
         parents.append(index[q] if q >= 0 else -1)
-    return BvhClips(rot, pos, lengths, [h0.names[j] for j in pick], np.array(parents, dtype=np.int64), h0.offsets[pick].copy(), h0.order,
-                    h0.frametime, tokens, slow)
+    if source_fps is None:
+        rates = [int(round(1.0 / h.frametime)) if h.frametime > 0 else 0 for h in hdrs]
+    elif isinstance(source_fps, (list, tuple, np.ndarray)):
+        rates = list(source_fps)
+        if len(rates) != len(hdrs):
+            raise ValueError("load_bvh: source_fps is one value, or one per file")
+    else:
+        rates = [source_fps] * len(hdrs)
+    order, frametime = h0.order, h0.frametime
+    if fps is not None:
+        from .ingest import resample_clips, resample_ratio
+        for r, w in zip(rates, label):
+            if not r > 0:
+                raise ValueError(f"load_bvh: {w} has no usable frame time; pass source_fps=")
+        if any(resample_ratio(r, fps) != (1, 1) for r in rates):
+            rot, pos, lengths = resample_clips(model, rot, pos, lengths, rates, target_fps=fps, order=h0.order)
+            order, frametime = None, 1.0 / float(fps)
+    return BvhClips(rot, pos, lengths, [h0.names[j] for j in pick], np.array(parents, dtype=np.int64), h0.offsets[pick].copy(), order,
+                    frametime, tokens, slow, rates)

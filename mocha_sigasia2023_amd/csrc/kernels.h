@@ -324,6 +324,33 @@ struct ClipWindowParams {
     long long B;
 };
 hipError_t launch_clip_windows(const ClipWindowParams& p, hipStream_t s);
+// The resampler in front of the ingester (resample.hip): (rotations, positions) at a source rate -> (unit quaternions, positions) at the
+// target rate.  The step between outputs is num / den source frames (1..RESAMPLE_MAX_TERM each); output k of a clip sits at t = k num:
+// source frame i = t div den, a = (t mod den) / den; a == 0 gives frame i itself and frame i+1 is not read, else the frame between i and
+// i+1 (resample_body.h).  Whole clips: q / p are the unrolled float64 quaternions and positions mocha_clip_quat (scale 1) and
+// mocha_clip_unroll left in the workspace; clip c = source frames in_off[c] .. in_off[c+1]-1 -> outputs out_off[c] .. out_off[c+1]-1.
+static constexpr int RESAMPLE_MAX_TERM = 4096, RESAMPLE_MAX_OUT = 4;
+struct ClipResampleParams {
+    const double *q, *p;                        // (F,V,4), (F,V,3)
+    const int *in_off, *out_off, *num, *den;    // device: (C+1), (C+1), (C), (C)
+    float *rot_out, *pos_out;                   // (F',V,4), (F',V,3)
+    int C, V;
+    long long F_out;
+};
+hipError_t launch_clip_resample(const ClipResampleParams& p, hipStream_t s);
+// One source frame of S streams in lockstep: outputs k_first .. k_first+count-1 (the host's schedule for this push) of every stream into rot_out
+// (S,RESAMPLE_MAX_OUT,V,4) / pos_out (S,RESAMPLE_MAX_OUT,V,3).  state: (S, RESAMPLE_STATE_DOUBLES) float64 words per stream = fresh | have
+// | per joint: the previous unrolled quaternion, position and unroll sign; fresh != 0 or have == 0 (all-zero state): no predecessor,
+// every output of the push is the new frame.
+static constexpr int RESAMPLE_JOINT_DOUBLES = 8, RESAMPLE_STATE_DOUBLES = 2 + MOCHA_MAX_BONES * RESAMPLE_JOINT_DOUBLES;
+struct ResampleStepParams {
+    double* state;
+    const float *rot, *pos;                     // (S,V,4|3), (S,V,3)
+    float *rot_out, *pos_out;
+    int V, euler, order[3], num, den, count;
+    long long k_first;
+};
+hipError_t launch_resample_step(const ResampleStepParams& p, int S, hipStream_t s);
 // The MOTION blocks of BVH files as text -> rot / pos (F,v_out,3) fp32 (mocha_bvh_motion, bvh_parse.hip).  The text is walked in blocks
 // of BVH_BLOCK bytes; clips start on block boundaries, so a clip's first token ordinal is the token prefix at its first block.
 static constexpr int BVH_BLOCK = 4096, BVH_MAX_TOKEN = 64, BVH_MAX_SLOW = 4096;

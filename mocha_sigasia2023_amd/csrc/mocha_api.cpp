@@ -4275,6 +4275,137 @@ int mocha_clip_windows(mocha_ctx* c, const float* pos, const float* vel, const f
     return 0;
 }
 
+}  // extern "C"
+
+namespace {
+// outputs of a clip of n source frames at a step of num / den source frames: floor((n-1) den / num) + 1
+int64_t resample_count(int64_t n, int num, int den) { return (n - 1) * den / num + 1; }
+
+bool resample_terms_ok(int num, int den) { return num >= 1 && num <= RESAMPLE_MAX_TERM && den >= 1 && den <= RESAMPLE_MAX_TERM; }
+
+// rot_format 0 quaternions / 1 Euler degrees in euler_order, as mocha_ingest_cfg names them
+int resample_format(mocha_ctx* c, const char* who, int rot_format, const int* euler_order, int order[3]) {
+    if (rot_format != 0 && rot_format != 1) return fail(c, MOCHA_ERR_ARG, "%s: rot_format must be 0 (quaternions) or 1 (Euler degrees)", who);
+    order[0] = 2; order[1] = 1; order[2] = 0;
+    if (rot_format == 0) return 0;
+    if (!euler_order) return fail(c, MOCHA_ERR_ARG, "%s: null euler_order", who);
+    int seen = 0;
+    for (int i = 0; i < 3; ++i) {
+        if (euler_order[i] < 0 || euler_order[i] > 2) return fail(c, MOCHA_ERR_ARG, "%s: euler_order must name the axes 0..2", who);
+        seen |= 1 << euler_order[i];
+        order[i] = euler_order[i];
+    }
+    if (seen != 7) return fail(c, MOCHA_ERR_ARG, "%s: euler_order must be a permutation of 0..2", who);
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int64_t mocha_resample_frames(int64_t n, int num, int den) {
+    if (n < 1 || n > 0x7fffffffll || !resample_terms_ok(num, den)) return MOCHA_ERR_ARG;
+    return resample_count(n, num, den);
+}
+
+int mocha_resample_clips(mocha_ctx* c, int rot_format, const int* euler_order, const float* rot, const float* pos, const int32_t* offsets_in,
+                         const int32_t* num, const int32_t* den, int n_clips, const int32_t* offsets_out, float* rot_out, float* pos_out,
+                         void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (!rot || !pos || !num || !den || !offsets_out || !rot_out || !pos_out) return fail(c, MOCHA_ERR_ARG, "resample_clips: null argument");
+    int order[3];
+    int rc = resample_format(c, "resample_clips", rot_format, euler_order, order); if (rc) return rc;
+    if ((rc = clip_offsets_check(c, "resample_clips", offsets_in, n_clips, 1))) return rc;
+    if (offsets_out[0] != 0) return fail(c, MOCHA_ERR_ARG, "resample_clips: offsets_out[0] must be 0");
+    for (int i = 0; i < n_clips; ++i) {
+        if (!resample_terms_ok(num[i], den[i]))
+            return fail(c, MOCHA_ERR_ARG, "resample_clips: clip %d: num and den must be 1..%d", i, RESAMPLE_MAX_TERM);
+        const int64_t m = resample_count((int64_t)offsets_in[i + 1] - offsets_in[i], num[i], den[i]);
+        if ((int64_t)offsets_out[i] + m > 0x7fffffffll) return fail(c, MOCHA_ERR_ARG, "resample_clips: 2^31 output frames or more");
+        if ((int64_t)offsets_out[i + 1] != (int64_t)offsets_out[i] + m)
+            return fail(c, MOCHA_ERR_ARG, "resample_clips: offsets_out[%d] must be offsets_out[%d] + %lld (mocha_resample_frames)", i + 1, i,
+                        (long long)m);
+    }
+    const int V = c->cfg.V, F = offsets_in[n_clips];
+    if (V + 1 > MOCHA_MAX_BONES) return fail(c, MOCHA_ERR_ARG, "resample_clips: at most %d joints", MOCHA_MAX_BONES - 1);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> tab(offsets_in, offsets_in + n_clips + 1);
+    tab.insert(tab.end(), offsets_out, offsets_out + n_clips + 1);
+    tab.insert(tab.end(), num, num + n_clips);
+    tab.insert(tab.end(), den, den + n_clips);
+    const size_t nF = (size_t)F, nq = nF * V * 4, np_ = nF * V * 3;
+    int* tab_dev = nullptr; double* ws = nullptr;
+    if ((rc = clip_tables(c, s, tab, 2 * nq + np_, &tab_dev, &ws))) return rc;
+    ClipParams p{};                                            // launches 0 and 1 of the clip ingester, positions unscaled
+    p.rot = rot; p.pos = pos; p.offsets = tab_dev; p.qraw = ws; p.q = ws + nq; p.p = ws + 2 * nq;
+    p.F = F; p.C = n_clips; p.V = V; p.euler = rot_format; p.scale = 1.0;
+    for (int i = 0; i < 3; ++i) p.order[i] = order[i];
+    ClipResampleParams r{};
+    r.q = p.q; r.p = p.p; r.in_off = tab_dev; r.out_off = tab_dev + n_clips + 1; r.num = r.out_off + n_clips + 1; r.den = r.num + n_clips;
+    r.rot_out = rot_out; r.pos_out = pos_out; r.C = n_clips; r.V = V; r.F_out = offsets_out[n_clips];
+    const double fq = (double)nq * 8, fp = (double)np_ * 8, fin = (double)nF * V * (rot_format ? 6 : 7) * 4;
+    LAUNCH(c, s, "mocha_clip_quat", "resample.quat", 0.0, fin + fq + fp, launch_clip_ingest(p, 0, s));
+    LAUNCH(c, s, "mocha_clip_unroll", "resample.unroll", 0.0, 2 * fq, launch_clip_ingest(p, 1, s));
+    // bytes: an output on a source frame reads that frame, any other its two neighbours, no frame more than once from memory (56 bytes
+    // per joint: quaternion and position in float64); 28 bytes per output joint written
+    double touched = 0.0;
+    for (int i = 0; i < n_clips; ++i) {
+        const int64_t n = (int64_t)offsets_in[i + 1] - offsets_in[i], m = (int64_t)offsets_out[i + 1] - offsets_out[i];
+        const int64_t on_frame = (m - 1) / den[i] + 1;       // k num / den is whole for every den-th output (num / den reduced)
+        touched += (double)std::min(n, on_frame + 2 * (m - on_frame));
+    }
+    LAUNCH(c, s, "mocha_clip_resample", "resample.clips", 0.0, (touched * 56.0 + (double)r.F_out * 28.0) * V, launch_clip_resample(r, s));
+    return 0;
+}
+
+int64_t mocha_resample_state_bytes(const mocha_ctx* c, int streams) {
+    if (!c || streams < 1 || streams > 16) return MOCHA_ERR_ARG;
+    return (int64_t)streams * RESAMPLE_STATE_DOUBLES * (int64_t)sizeof(double);
+}
+
+int mocha_resample_reset(mocha_ctx* c, void* state, int streams, const int32_t* which, int n, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (streams < 1 || streams > 16) return fail(c, MOCHA_ERR_ARG, "resample_reset: 1 <= streams <= 16");
+    if (!state) return fail(c, MOCHA_ERR_ARG, "resample_reset: null argument");
+    if (which && (n < 0 || n > streams)) return fail(c, MOCHA_ERR_ARG, "resample_reset: n must be 0..streams");
+    for (int i = 0; which && i < n; ++i)
+        if (which[i] < 0 || which[i] >= streams)
+            return fail(c, MOCHA_ERR_ARG, "resample_reset: stream %d out of range 0..%d", (int)which[i], streams - 1);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    char* base = static_cast<char*>(state);
+    const size_t row = RESAMPLE_STATE_DOUBLES * sizeof(double);
+    if (!which) { HIPCHK(c, hipMemsetAsync(base, 0, row * streams, s)); return 0; }
+    for (int i = 0; i < n; ++i) HIPCHK(c, hipMemsetAsync(base + row * which[i], 0, row, s));
+    return 0;
+}
+
+int mocha_resample_step(mocha_ctx* c, int rot_format, const int* euler_order, void* state, int streams, const float* rot, const float* pos,
+                        int num, int den, int64_t push_index, float* rot_out, float* pos_out, int32_t* n_out, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (streams < 1 || streams > 16) return fail(c, MOCHA_ERR_ARG, "resample_step: 1 <= streams <= 16");
+    if (!state || !rot || !pos || !rot_out || !pos_out || !n_out) return fail(c, MOCHA_ERR_ARG, "resample_step: null argument");
+    ResampleStepParams p{};
+    int rc = resample_format(c, "resample_step", rot_format, euler_order, p.order); if (rc) return rc;
+    if (!resample_terms_ok(num, den)) return fail(c, MOCHA_ERR_ARG, "resample_step: num and den must be 1..%d", RESAMPLE_MAX_TERM);
+    if (den > RESAMPLE_MAX_OUT * num)
+        return fail(c, MOCHA_ERR_ARG, "resample_step: more than %d outputs per source frame (den / num = %d / %d)", RESAMPLE_MAX_OUT, den, num);
+    if (push_index < 0 || push_index > ((int64_t)1 << 48)) return fail(c, MOCHA_ERR_ARG, "resample_step: push_index must be 0..2^48");
+    if (c->cfg.V + 1 > MOCHA_MAX_BONES) return fail(c, MOCHA_ERR_ARG, "resample_step: at most %d joints", MOCHA_MAX_BONES - 1);
+    // push j brings source frame j: the outputs k with floor((j-1) den / num) < k <= floor(j den / num) - integers alone, so the host knows
+    // the count without asking the device
+    const int64_t last = push_index * den / num, first = push_index == 0 ? 0 : (push_index - 1) * den / num + 1;
+    p.state = static_cast<double*>(state); p.rot = rot; p.pos = pos; p.rot_out = rot_out; p.pos_out = pos_out;
+    p.V = c->cfg.V; p.euler = rot_format; p.num = num; p.den = den; p.count = (int)(last - first + 1); p.k_first = first;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const double V = p.V;
+    LAUNCH(c, s, "mocha_resample_step_k", "resample.step", 0.0,
+           (double)streams * (V * (rot_format ? 6 : 7) * 4 + 2 * V * RESAMPLE_JOINT_DOUBLES * 8 + p.count * V * 28.0), launch_resample_step(p, streams, s));
+    *n_out = p.count;
+    return 0;
+}
+
 int mocha_bvh_motion(mocha_ctx* c, const char* text_dev, int64_t nbytes, const char* text_host, const int64_t* clip_text_begin,
                      const int64_t* clip_text_end, const int32_t* clip_offsets, int n_clips, int n_joints, int channels,
                      const int32_t* joint_map, int v_out, const float* offsets_out, float* rot, float* pos, mocha_bvh_report* report,

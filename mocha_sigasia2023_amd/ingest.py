@@ -216,3 +216,141 @@ def clip_windows(processed, lengths, window: int = 60, step: int = 1, model: Opt
                     len(lengths), int(window), int(step), _ptr(out["Yrot"]), _ptr(out["Ypos"]), _ptr(out["Yvel"]), _ptr(out["Yang"]),
                     _ptr(out["contact"]), _stream())
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- resampling
+def _fraction(x, what):
+    from fractions import Fraction
+    if isinstance(x, Fraction):
+        f = x
+    elif isinstance(x, (int, np.integer)):
+        f = Fraction(int(x))
+    else:
+        f = Fraction(float(x)).limit_denominator(1000)
+    if f <= 0:
+        raise ValueError(f"{what} must be positive")
+    return f
+
+
+def resample_ratio(source_fps, target_fps=60.0):
+    """The step between outputs in source frames, ``source_fps / target_fps`` reduced to (num, den), each 1..4096.  Ints, floats or
+    ``Fraction``s; a float goes through ``Fraction(x).limit_denominator(1000)``."""
+    r = _fraction(source_fps, "source_fps") / _fraction(target_fps, "target_fps")
+    if r.numerator > 4096 or r.denominator > 4096:
+        raise ValueError(f"resampling: {source_fps} -> {target_fps} fps reduces to {r.numerator}/{r.denominator}; each term must be at most 4096")
+    return r.numerator, r.denominator
+
+
+def _ratios(n_clips, source_fps, target_fps):
+    from fractions import Fraction
+    if isinstance(source_fps, (int, float, np.integer, np.floating, Fraction)):
+        source_fps = [source_fps] * n_clips
+    if len(source_fps) != n_clips:
+        raise ValueError("resampling: source_fps is one value, or one per clip")
+    return [resample_ratio(s, target_fps) for s in source_fps]
+
+
+def resample_lengths(lengths, source_fps, target_fps=60.0):
+    """Frames per clip after resampling (``mocha_resample_frames``): ``floor((n-1) * den / num) + 1`` with num/den = source/target."""
+    lib = _C.load_library()
+    out = []
+    for n, (num, den) in zip(lengths, _ratios(len(lengths), source_fps, target_fps)):
+        m = int(lib.mocha_resample_frames(int(n), num, den))
+        if m < 1:
+            raise ValueError(f"resample_lengths: a clip of {n} frames cannot be resampled (every clip needs at least one frame)")
+        out.append(m)
+    return out
+
+
+def resample_clips(model: Generator, rot, pos, lengths, source_fps, target_fps=60.0, order="zyx"):
+    """Whole clips from ``source_fps`` to ``target_fps`` on the device (``mocha_resample_clips``).  ``rot`` (F,V,3) Euler degrees in
+    ``order`` or, with ``order=None``, (F,V,4) quaternions; ``pos`` (F,V,3) in the file's units; the clips concatenated along the frame
+    axis, ``lengths`` their frame counts (a clip may have one frame).  ``source_fps``: one value, or one per clip.  Returns
+    ``(rot_q (F',V,4), pos (F',V,3), new_lengths)``: unit quaternions w,x,y,z sign-unrolled along time and positions, fp32 on the device -
+    what ``ingest_clips(..., raw=IngestConfig(order=None, fps=target_fps))`` takes.  Output k of a clip sits k * source / target source
+    frames in: on a source frame it is that frame, between two it turns at constant angular velocity (slerp) and moves linearly.  No
+    low-pass filter before decimation, no cubic interpolation.  Waits for the current stream once; not for graph capture."""
+    if order is not None and (len(order) != 3 or sorted(order) != ["x", "y", "z"]):
+        raise ValueError("resample_clips: order is a permutation of 'xyz', or None for quaternions")
+    width = 4 if order is None else 3
+    V, dev = model.V, model.device
+    off, F = _offsets(lengths)
+    n = len(lengths)
+    ratios = _ratios(n, source_fps, target_fps)
+    new_lengths = resample_lengths(lengths, source_fps, target_fps)
+    off_out, F_out = _offsets(new_lengths)
+    r = _dev_f32(rot, dev, (V, width), "rot")
+    p = _dev_f32(pos, dev, (V, 3), "pos")
+    if r.numel() != F * V * width or p.numel() != F * V * 3:
+        raise ValueError(f"resample_clips: rot / pos do not hold the {F} frames of lengths")
+    rot_q = torch.empty((F_out, V, 4), dtype=torch.float32, device=dev)
+    pos_o = torch.empty((F_out, V, 3), dtype=torch.float32, device=dev)
+    eo = (C.c_int * 3)(*[AXES[a] for a in (order or "zyx")])
+    model._ctx.call("mocha_resample_clips", 0 if order is None else 1, eo, _ptr(r), _ptr(p), off, (C.c_int32 * n)(*[a for a, _ in ratios]),
+                    (C.c_int32 * n)(*[b for _, b in ratios]), n, off_out, _ptr(rot_q), _ptr(pos_o), _stream())
+    return rot_q, pos_o, new_lengths
+
+
+class StreamResampler:
+    """The streaming form (``mocha_resample_step``; parallel to ``Ingestor`` and ``Inertializer``): ``streams`` streams of one source
+    rate, advancing in lockstep.  ``push(rot, pos)`` takes the new source frame of every stream - rot (S,V,3) Euler degrees in ``order``
+    or, with ``order=None``, (S,V,4) quaternions; pos (S,V,3) - and returns how many output frames it produced (a host int, 0..4, known
+    without asking the device); they are ``out["rot"][:, :n]`` (S,4,V,4) and ``out["pos"][:, :n]`` (S,4,V,3), overwritten by the next push.
+    The outputs of all pushes, concatenated, are ``resample_clips`` of the pushed frames bit for bit.  One launch per push in front of a
+    quaternion-input session: ``for e in range(n): session.push_raw(out["rot"][:, e], out["pos"][:, e])``.  A source more than four times
+    slower than the target is refused."""
+
+    def __init__(self, model: Generator, source_fps, target_fps=60.0, order="zyx", streams: int = 1):
+        if not 1 <= int(streams) <= 16:
+            raise ValueError("streams must be 1..16")
+        if order is not None and (len(order) != 3 or sorted(order) != ["x", "y", "z"]):
+            raise ValueError("StreamResampler: order is a permutation of 'xyz', or None for quaternions")
+        self.model, self.streams, self.order = model, int(streams), order
+        self.num, self.den = resample_ratio(source_fps, target_fps)
+        if self.den > 4 * self.num:
+            raise ValueError(f"StreamResampler: {source_fps} -> {target_fps} fps gives more than 4 outputs per source frame")
+        S, V, dev = self.streams, model.V, model.device
+        nbytes = int(model._ctx.lib.mocha_resample_state_bytes(model._ctx.h, S))
+        if nbytes <= 0:
+            raise RuntimeError("mocha_resample_state_bytes failed")
+        self.state = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)          # zeroed = no frame seen
+        self.width = 4 if order is None else 3
+        f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)    # noqa: E731
+        self.rot, self.pos = f32(S, V, self.width), f32(S, V, 3)
+        self.out = {"rot": f32(S, 4, V, 4), "pos": f32(S, 4, V, 3)}
+        self._order = (C.c_int * 3)(*[AXES[a] for a in (order or "zyx")])
+        self.pushes = 0
+
+    def _frame(self, a, buf, name):
+        t = _dev_f32(a, buf.device, None, name)
+        if t.numel() != buf.numel():
+            raise ValueError(f"StreamResampler.push: {name} has {t.numel()} values, expected {tuple(buf.shape)}")
+        buf.copy_(t.reshape(buf.shape), non_blocking=True)
+
+    def push(self, rot, pos) -> int:
+        self._frame(rot, self.rot, "rot")
+        self._frame(pos, self.pos, "pos")
+        return self.replay()
+
+    def replay(self) -> int:
+        """The push on what the fixed buffers ``rot`` / ``pos`` hold."""
+        n = C.c_int32(0)
+        self.model._ctx.call("mocha_resample_step", 0 if self.order is None else 1, self._order, _ptr(self.state), self.streams,
+                             _ptr(self.rot), _ptr(self.pos), self.num, self.den, self.pushes, _ptr(self.out["rot"]), _ptr(self.out["pos"]),
+                             C.byref(n), _stream())
+        self.pushes += 1
+        return int(n.value)
+
+    def restart(self, streams: Optional[Sequence[int]] = None):
+        """The listed streams (None = all) forget their previous frame: every output of their next push is the new frame itself.  The
+        output schedule goes on in lockstep."""
+        ids = None if streams is None else [int(s) for s in streams]
+        arr = None if ids is None else (C.c_int32 * max(len(ids), 1))(*ids)
+        self.model._ctx.call("mocha_resample_reset", _ptr(self.state), self.streams, arr, 0 if ids is None else len(ids), _stream())
+        return self
+
+    def reset(self):
+        """All streams have seen no frame, and the next push is push 0."""
+        self.restart()
+        self.pushes = 0
+        return self
