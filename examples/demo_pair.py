@@ -49,6 +49,8 @@ ap.add_argument("--cha-bvh", help="the character clip as a BVH file")
 ap.add_argument("--resample", type=float, metavar="R",
                 help="with --src-bvh / --cha-bvh: bring files of another frame rate to R frames per second first (load_bvh(fps=R); the model "
                      "is fixed to 60)")
+ap.add_argument("--world", metavar="OUT.npz", help="save the global bone positions of the source and of the two outputs: what the "
+                                                     "reference hands to animation_plot (world_pose: quat.fk on the device)")
 a = ap.parse_args()
 if bool(a.src_bvh) != bool(a.cha_bvh):
     ap.error("--src-bvh and --cha-bvh go together")
@@ -138,4 +140,13 @@ print(f"{N} windows per clip: featurize + NN branch + Ours branch + post-process
 for k in ("cm_trans.bvh", "ours.bvh"):
     p = os.path.join(a.out, k)
     print(f"  {p}: {os.path.getsize(p)} bytes, {sum(1 for _ in open(p))} lines")
+if a.world:                                                                    # :665-690: quat.fk of every stream, one launch each
+    from mocha_sigasia2023_amd import world_pose  # noqa: E402
+    dv = lambda x: torch.as_tensor(x).to(dev)                                  # noqa: E731
+    glb = {"src": world_pose(model, dv(src_bones[0])[:, -1].contiguous(), dv(src_bones[1])[:, -1].contiguous()),      # fp32 locals
+           "cm_trans": world_pose(model, nn["rot"], nn["pos"]), "ours": world_pose(model, ours["ik_rot"], ours["pos"])}
+    np.savez(a.world, parents=np.asarray([-1] + [p + 1 for p in parents]), **{f"{k}_gpos": v["gpos"].cpu().numpy() for k, v in glb.items()},
+             **{f"{k}_grot": v["grot"].cpu().numpy() for k, v in glb.items()})
+    print(f"  {a.world}: global positions " + ", ".join(f"{k} {tuple(v['gpos'].shape)}" for k, v in glb.items()))
+    assert all(torch.isfinite(v["gpos"]).all() for v in glb.values())
 assert all(torch.isfinite(v).all() for v in nn.values()) and all(torch.isfinite(v).all() for v in ours.values())

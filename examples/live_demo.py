@@ -35,6 +35,9 @@ How many posed frames were constrained is printed.
 in place - its own rows and decoder constants, enqueued on the stream - and stream 1 switches to it.  The captured step keeps replaying:
 the model's generation before and after is printed.
 
+``--world``: every push also returns the pose in world space and the fp32 skinning palette (``LiveSession(world=SkinBind(...))``, one more
+launch behind the captured step); prints the palette's shape and one bone's world position per frame.
+
 ``--mix a:b:FRAMES``: both streams are characterized by a MIX of characters a and b (``LiveSession(mix=2)``): a linear cross-fade from a
 to b over FRAMES frames, starting with the first posed frame - a weight ramp written into the session's device weights, in feature
 space; nothing is captured again.  ``--mix-parts a:b:MASK``: a splice by body part - MASK is six 0/1 characters, one per body part in the
@@ -75,6 +78,7 @@ ap.add_argument("--load-at", type=int, default=None, metavar="FRAME", help="star
 ap.add_argument("--ours-per-character", action="store_true", help="--ours with one CVAE per character from a CVAEBank (synthetic CVAEs)")
 ap.add_argument("--mix", default=None, metavar="a:b:FRAMES", help="cross-fade both streams from character a to b over FRAMES frames")
 ap.add_argument("--mix-parts", default=None, metavar="a:b:MASK", help="splice: body parts with 1 in the six-character MASK from a, the others from b")
+ap.add_argument("--world", action="store_true", help="also produce world-space poses and the skinning palette (LiveSession(world=SkinBind))")
 a = ap.parse_args()
 a.ours = a.ours or a.ours_per_character
 mix_ids = mix_ramp = mix_mask = None
@@ -146,6 +150,13 @@ for s in range(S):
     _, rvel, rang, hipvel, contact = synthetic.postprocess_inputs(5 + s, F)
     per.append([torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in
                 (rvel, rang, np.linalg.norm(hipvel, axis=-1).mean(-1).astype(np.float32), contact)])
+# --world: the mesh is bound in the first source frame's bone offsets, rotations identity; the engine works in centimetres, z up
+world = None
+if a.world:
+    from mocha_sigasia2023_amd import SkinBind
+    world = SkinBind(model, src[0][1][0].double(), None, [[100.0, 0, 0, 0], [0, 0, 100.0, 0], [0, 100.0, 0, 0]])
+
+
 def cvae_stats(seed):
     r = np.random.Generator(np.random.PCG64(seed))
     return [(0.1 * r.standard_normal((90, 256))).astype(np.float32), r.uniform(0.5, 1.5, (90, 256)).astype(np.float32),
@@ -159,18 +170,18 @@ if a.ours_per_character:                                              # train_CV
     for c in range(2):
         cvaes.store(c, synthetic_cvae_state_dict(99 + c, 1.0), *cvae_stats(3 + c))
     sess = LiveOursSession(bank, cnt_mean, cnt_std, None, None, None, None, None, streams=S, post=PostProcessor(model), noise="device",
-                           seed=a.seed, cvaes=cvaes, cvae_of=[0, 1, -1][:bank.S])
+                           seed=a.seed, cvaes=cvaes, cvae_of=[0, 1, -1][:bank.S], world=world)
 elif a.ours:                                                          # test_fullframework.py:52-58, 80-87: the CVAE and its statistics
     from mocha_sigasia2023_amd.weights import synthetic_cvae_state_dict
     r3 = np.random.Generator(np.random.PCG64(3))
     stats = [(0.1 * r3.standard_normal((90, 256))).astype(np.float32), r3.uniform(0.5, 1.5, (90, 256)).astype(np.float32),
              (0.1 * r3.standard_normal((90, 256))).astype(np.float32), r3.uniform(0.5, 1.5, (90, 256)).astype(np.float32)]
     sess = LiveOursSession(bank, cnt_mean, cnt_std, synthetic_cvae_state_dict(99, 1.0), *stats, streams=S, post=PostProcessor(model),
-                           noise="device", seed=a.seed)
+                           noise="device", seed=a.seed, world=world)
 else:
     raw_cfg = a.raw if a.source_fps is None else IngestConfig(lookahead=a.raw, order=None)      # the resampler hands over quaternions
     sess = LiveSession(bank, cnt_mean, cnt_std, streams=S, post=PostProcessor(model), soft=soft, inertial=a.inertial, raw=raw_cfg,
-                       constrained=bool(a.actions), mix=2 if mix_ids else None)
+                       constrained=bool(a.actions), mix=2 if mix_ids else None, world=world)
 if mix_ids:
     sess.set_mix((mix_ids, np.stack([mix_mask, 1 - mix_mask]) if mix_mask is not None else [1.0, 0.0]))
 if a.raw is not None:
@@ -225,7 +236,7 @@ if a.source_fps is not None:
     resampler.reset()
     at_60 = resampled_frames()
 torch.cuda.synchronize(); t0 = time.perf_counter()
-pos, eul, applied, seeded = [], [], [], []
+pos, eul, applied, seeded, head = [], [], [], [], []
 if a.actions:
     sess.allow.zero_()
 gen0 = model._ctx.generation()
@@ -244,6 +255,8 @@ for f in range(F):
         pos.append(o["bvh_pos"].clone()); eul.append(o["bvh_euler"].clone())
         if a.actions:
             applied.append(o["applied"].clone())
+        if a.world:                                                   # the last bone's world position, kept on the device: no synchronisation here
+            head.append(o["gpos"][:, -1].clone())
 torch.cuda.synchronize(); dt = time.perf_counter() - t0
 pos, eul = torch.stack(pos, 1), torch.stack(eul, 1)                   # (S, F - first, V, 3)
 
@@ -252,6 +265,11 @@ for s in range(S):
     p = os.path.join(a.out, f"{'Ours' if a.ours else 'mix' if mix_ids else 'soft' if soft else 'raw' if a.raw is not None else 'live'}_stream{s}.bvh")
     write_bvh(p, names, LAYOUTS["mocha"]["parents"], pos[s], eul[s])
     print(f"  {p}: {os.path.getsize(p)} bytes, {pos.shape[1]} frames")
+if a.world:
+    print(f"  world: palette {tuple(sess.out['palette'].shape)} {sess.out['palette'].dtype}, gpos {tuple(sess.out['gpos'].shape)}, "
+          f"grot {tuple(sess.out['grot'].shape)}: one mocha_world_pose launch behind every captured step; bone {J - 1} of stream 0 in world space:")
+    for f, g in enumerate(torch.stack(head, 1)[0].cpu().tolist()):
+        print(f"    frame {first + f}: {g[0]:9.4f} {g[1]:9.4f} {g[2]:9.4f}")
 if a.ours_per_character:
     sd = torch.stack(seeded, 1).cpu()
     print(f"  one CVAE per character: seed frames per stream {sd.sum(1).tolist()} of {F - first} posed frames; generation {gen0} -> {model._ctx.generation()}")

@@ -897,6 +897,42 @@ int mocha_resample_reset(mocha_ctx* ctx, void* state, int streams, const int32_t
 int mocha_resample_step(mocha_ctx* ctx, int rot_format, const int* euler_order, void* state, int streams, const float* rot, const float* pos,
                         int num, int den, int64_t push_index, float* rot_out, float* pos_out, int32_t* n_out, void* stream);
 
+/* WORLD-SPACE POSES AND SKINNING PALETTES behind the calls above: what the reference's demo computes at its end - quat.fk over every output
+ * stream (test_fullframework.py:672-690), the global positions going to animation_plot (:670) - and what an engine binds per skinned mesh.
+ * Every pose the library emits or takes is LOCAL: rot (..,V+1,4) w,x,y,z and pos (..,V+1,3), parent-relative, the trajectory root bone first.
+ *   fk       For a frame with locals q[b], p[b], b = 0..V, and the context's parents ([-1] + (joint parents + 1), test_fullframework.py:
+ *            101-102: the table mocha_postprocess uses; par[b] < b):  G[0] = q[0], g[0] = p[0];  G[b] = mul(G[par b], q[b]);
+ *            g[b] = mul_vec(G[par b], p[b]) + g[par b]  - quat.fk (motion/quat.py:166-173) with mul (:112-120) and mul_vec (:128-130), in
+ *            float64.  Inputs are taken as given: NO normalisation of pose quaternions.
+ *   palette  For bone b = 1..V (the engine's skeleton is the V bones without the trajectory root, as in the BVH writer's merge) the 3x4 matrix
+ *            P[b] = pre o [to_xform(G[b]) | g[b]] o [to_xform(B[b]) | c[b]]^-1  with to_xform as quat.py:27-40; (B, c) = fk of a rest pose whose
+ *            quaternions are normalised once with quat.normalize (:15-16); the inverse is the rigid one (R^T, -R^T c); pre is any 3x4 affine
+ *            map (unit scale, axis swap, handedness).  Affine maps compose as (R1 R2 | R1 t2 + t1), sums over k = 0, 1, 2 in that order; the
+ *            product is evaluated in float64 left to right as written, rounded ONCE to fp32 and stored row-major as 12 floats
+ *            (r00 r01 r02 t0 | r10 .. | r20 ..).
+ *   mocha_world_bind_bytes : HOST only.  The size of a bind: caller-owned device memory with a private layout (pre and V+1 inverse binds).
+ *   mocha_world_bind       : rest_rot (V+1,4) float64 on the device or NULL = identity rotations, rest_pos (V+1,3) float64 on the device,
+ *                            pre = 12 doubles row-major on the HOST or NULL = identity.  Computes the inverse bind globals on the device
+ *                            with the fk function mocha_world_pose runs; one launch on `stream`.
+ *   mocha_world_pose       : n frames.  rot (n,V+1,4) and pos (n,V+1,3) on the device, float64 (in_f32 = 0: what mocha_postprocess,
+ *                            mocha_postprocess_step and mocha_live_step* emit; pass ik_rot or rot) or fp32 (in_f32 = 1: what
+ *                            mocha_live_ingest_step, mocha_ingest_clips and mocha_resample_clips emit with their root bone; each value is
+ *                            widened on load, the code is otherwise the same, so fp32 inputs give the bits of the same values passed as
+ *                            float64).  Outputs, each may be NULL: gpos (n,V+1,3), grot (n,V+1,4) float64; palette (n,V,12) fp32, which needs
+ *                            `bind`.  valid (n) int32 on the device or NULL: rows with valid[i] == 0 are NOT written (the live step's rule
+ *                            for warming streams).  rot, grot and palette must be 16-byte aligned.  A frame's result does not depend on
+ *                            n, on its index or on which outputs are asked for: n frames in one call are bit for bit the n calls of one
+ *                            frame.  One launch, no allocation, no synchronisation, reads no context state that a later call changes and
+ *                            does not move mocha_generation: capture-safe, and captured steps keep replaying.
+ * Refusals (MOCHA_ERR_ARG, nothing launched): a NULL rot, pos, rest_pos or bind buffer; a palette without a bind; all three outputs NULL;
+ * a pre that is not finite; n < 0; in_f32 outside 0..1; a misaligned array.  n == 0 is a no-op.
+ * What it is not: no mesh skinning (the palette is what a vertex shader multiplies by); no global velocities (quat.fk_vel); no dual
+ * quaternions; one bind per call; mocha_live_step* do not call it inside their captured graph - launch it behind them on the same stream. */
+int64_t mocha_world_bind_bytes(const mocha_ctx* ctx);
+int mocha_world_bind(mocha_ctx* ctx, const double* rest_rot, const double* rest_pos, const double* pre, void* bind, void* stream);
+int mocha_world_pose(mocha_ctx* ctx, const void* rot, const void* pos, int in_f32, int64_t n, const int32_t* valid, const void* bind,
+                     double* gpos, double* grot, float* palette, void* stream);
+
 /* BVH TEXT in front of mocha_ingest_clips: what the reference's loader (motion/bvh.py:22-138) returns - Euler degrees in file channel
  * order and positions in file units per joint - as the two fp32 device arrays mocha_ingest_clips reads.  The hierarchy is read on the
  * host, the numbers of the MOTION block (over 99.9 % of a file) are parsed on the device.

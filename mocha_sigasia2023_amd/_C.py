@@ -166,6 +166,9 @@ SIGNATURES = {
     "mocha_resample_state_bytes": (_i64, [_vp, _i]),
     "mocha_resample_reset": (_i, [_vp, _vp, _i, C.POINTER(C.c_int32), _i, _vp]),
     "mocha_resample_step": (_i, [_vp, _i, C.POINTER(C.c_int), _vp, _i, _vp, _vp, _i, _i, _i64, _vp, _vp, C.POINTER(C.c_int32), _vp]),
+    "mocha_world_bind_bytes": (_i64, [_vp]),
+    "mocha_world_bind": (_i, [_vp, _vp, _vp, C.POINTER(C.c_double), _vp, _vp]),
+    "mocha_world_pose": (_i, [_vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocha_bvh_header": (_i,[_vp, _i64, C.POINTER(mocha_bvh_hdr)]),
     "mocha_bvh_motion": (_i, [_vp, _vp, _i64, _vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_int32), _i, _i, _i, C.POINTER(C.c_int32), _i,
                               C.POINTER(C.c_float), _vp, _vp, C.POINTER(mocha_bvh_report), _vp]),

@@ -10,6 +10,7 @@ from .postprocess import Inertializer, PostProcessor, pose_heads, retarget_clip,
 from .postprocess import BvhValueRefused, format_bvh_motion, write_bvh_clips  # noqa: F401
 from .live import LiveOursSession, LiveSession  # noqa: F401
 from .ingest import IngestConfig, Ingestor, StreamResampler, clip_windows, ingest_clips, resample_clips, resample_lengths  # noqa: F401
+from .world import SkinBind, world_pose  # noqa: F401
 from .bvh import BvhClips, BvhHeader, load_bvh, read_bvh_header  # noqa: F401
 from .skeleton import PART_NAMES, skeleton_constants  # noqa: F401
 from . import synthetic  # noqa: F401
@@ -19,5 +20,5 @@ __all__ = ["Generator", "CVAE", "CVAEBank", "OursSession", "ContextBank", "Strea
            "synthetic_state_dict", "param_shapes", "DEFAULT_CFG", "build_bank", "save_bank", "load_bank", "ShardedContextBank", "BatchPipeline",
            "PostProcessor", "pose_heads", "MultiCharacterBank", "MultiStreamCharacterizer", "ResidentCharacterBank", "action_mask", "retarget_clip", "retarget_clip_ours", "retarget_frame_ours", "write_bvh", "write_bvh_clips", "format_bvh_motion", "BvhValueRefused",
            "LiveSession", "LiveOursSession", "Inertializer", "Ingestor", "IngestConfig", "ingest_clips", "clip_windows",
-           "resample_clips", "resample_lengths", "StreamResampler",
+           "resample_clips", "resample_lengths", "StreamResampler", "SkinBind", "world_pose",
            "PART_NAMES", "read_bvh_header", "load_bvh", "BvhHeader", "BvhClips", "build_database_from_bvh"]

@@ -351,6 +351,31 @@ struct ResampleStepParams {
     long long k_first;
 };
 hipError_t launch_resample_step(const ResampleStepParams& p, int S, hipStream_t s);
+// World-space poses and skinning palettes (world_pose.hip): quat.fk over n frames of (V+1)-bone locals, float64 or fp32 in; gpos (n,V+1,3),
+// grot (n,V+1,4) float64 and palette (n,V,12) fp32 = pre o [to_xform(grot) | gpos] o inverse bind, each may be null.  rot, grot and palette
+// are 16-byte aligned.  bind: WORLD_BIND_DOUBLES(V) float64 words = pre (3x4 row-major) | the inverse bind of bones 0..V (3x4 each), written
+// by launch_world_bind from a rest pose.  anc[b]: bit a set for b and every ancestor a of b.  Frames whose valid entry is 0 are not written.
+static constexpr int WORLD_FPB = 8;                              // frames per workgroup, 32 lanes each
+static constexpr int WORLD_BIND_DOUBLES(int V) { return (V + 2) * 12; }
+struct WorldPoseParams {
+    const void *rot, *pos;          // (n,V+1,4), (n,V+1,3): float64, or fp32 when in_f32
+    const int32_t* valid;           // (n) or null
+    const double* bind;
+    double *gpos, *grot;
+    float* palette;
+    long long n;
+    int V, in_f32;
+    unsigned anc[MOCHA_MAX_BONES];
+};
+hipError_t launch_world_pose(const WorldPoseParams& p, hipStream_t s);
+struct WorldBindParams {
+    const double *rest_rot, *rest_pos;      // (V+1,4) or null = identity, (V+1,3)
+    double* bind;
+    int V;
+    unsigned anc[MOCHA_MAX_BONES];
+    double pre[12];
+};
+hipError_t launch_world_bind(const WorldBindParams& p, hipStream_t s);
 // The MOTION blocks of BVH files as text -> rot / pos (F,v_out,3) fp32 (mocha_bvh_motion, bvh_parse.hip).  The text is walked in blocks
 // of BVH_BLOCK bytes; clips start on block boundaries, so a clip's first token ordinal is the token prefix at its first block.
 static constexpr int BVH_BLOCK = 4096, BVH_MAX_TOKEN = 64, BVH_MAX_SLOW = 4096;

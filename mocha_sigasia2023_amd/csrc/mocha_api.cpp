@@ -4406,6 +4406,70 @@ int mocha_resample_step(mocha_ctx* c, int rot_format, const int* euler_order, vo
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------- world-space poses, skinning palettes
+// anc[b] of the (V+1)-bone skeleton (parents = [-1] + (joint parents + 1), test_fullframework.py:101-102: what post_params gives
+// mocha_postprocess): bit a set for b and each of its ancestors
+static int world_ancestors(mocha_ctx* c, const char* who, unsigned* anc) {
+    const int J = c->cfg.V + 1;
+    if (J > MOCHA_MAX_BONES) return fail(c, MOCHA_ERR_ARG, "%s: at most %d joints", who, MOCHA_MAX_BONES - 1);
+    anc[0] = 1u;
+    for (int b = 1; b < J; ++b) {
+        const int pa = c->sk.parents[b - 1] + 1;
+        if (pa < 0 || pa >= b) return fail(c, MOCHA_ERR_STATE, "%s: bone %d has parent %d: parents must precede their children", who, b, pa);
+        anc[b] = anc[pa] | (1u << b);
+    }
+    return 0;
+}
+
+int64_t mocha_world_bind_bytes(const mocha_ctx* c) {
+    if (!c || c->cfg.V + 1 > MOCHA_MAX_BONES) return MOCHA_ERR_ARG;
+    return (int64_t)WORLD_BIND_DOUBLES(c->cfg.V) * (int64_t)sizeof(double);
+}
+
+int mocha_world_bind(mocha_ctx* c, const double* rest_rot, const double* rest_pos, const double* pre, void* bind, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (!rest_pos || !bind) return fail(c, MOCHA_ERR_ARG, "world_bind: null argument");
+    if (reinterpret_cast<uintptr_t>(bind) % 8) return fail(c, MOCHA_ERR_ARG, "world_bind: bind must be 8-byte aligned");
+    WorldBindParams p{};
+    static const double eye[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    for (int k = 0; k < 12; ++k) {
+        p.pre[k] = pre ? pre[k] : eye[k];
+        if (!std::isfinite(p.pre[k])) return fail(c, MOCHA_ERR_ARG, "world_bind: pre[%d] is not finite", k);
+    }
+    int rc = world_ancestors(c, "world_bind", p.anc); if (rc) return rc;
+    p.rest_rot = rest_rot; p.rest_pos = rest_pos; p.bind = static_cast<double*>(bind); p.V = c->cfg.V;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    LAUNCH(c, s, "mocha_world_bind_k", "world.bind", 0.0, (p.V + 1) * (rest_rot ? 56.0 : 24.0) + WORLD_BIND_DOUBLES(p.V) * 8.0, launch_world_bind(p, s));
+    return 0;
+}
+
+int mocha_world_pose(mocha_ctx* c, const void* rot, const void* pos, int in_f32, int64_t n, const int32_t* valid, const void* bind, double* gpos,
+                     double* grot, float* palette, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (n == 0) return 0;
+    if (n < 0 || (in_f32 != 0 && in_f32 != 1)) return fail(c, MOCHA_ERR_ARG, "world_pose: n must be >= 0 and in_f32 0 or 1");
+    if (!rot || !pos) return fail(c, MOCHA_ERR_ARG, "world_pose: null argument");
+    if (!gpos && !grot && !palette) return fail(c, MOCHA_ERR_ARG, "world_pose: no output asked for");
+    if (palette && !bind) return fail(c, MOCHA_ERR_ARG, "world_pose: a palette needs a bind (mocha_world_bind)");
+    if (reinterpret_cast<uintptr_t>(rot) % 16 || reinterpret_cast<uintptr_t>(grot) % 16 || reinterpret_cast<uintptr_t>(palette) % 16 ||
+        reinterpret_cast<uintptr_t>(pos) % (in_f32 ? 4 : 8) || reinterpret_cast<uintptr_t>(gpos) % 8 || reinterpret_cast<uintptr_t>(bind) % 8)
+        return fail(c, MOCHA_ERR_ARG, "world_pose: rot, grot and palette must be 16-byte aligned, the other arrays to their element");
+    if (n > (int64_t)0x7fffffff * WORLD_FPB) return fail(c, MOCHA_ERR_ARG, "world_pose: at most %lld frames a call", (long long)0x7fffffff * WORLD_FPB);
+    WorldPoseParams p{};
+    int rc = world_ancestors(c, "world_pose", p.anc); if (rc) return rc;
+    p.rot = rot; p.pos = pos; p.valid = valid; p.bind = palette ? static_cast<const double*>(bind) : nullptr;
+    p.gpos = gpos; p.grot = grot; p.palette = palette; p.n = n; p.V = c->cfg.V; p.in_f32 = in_f32;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const double J = p.V + 1;
+    LAUNCH(c, s, "mocha_world_pose_k", "world.pose", 0.0,
+           (double)n * (J * 7 * (in_f32 ? 4.0 : 8.0) + (valid ? 4.0 : 0.0) + (gpos ? J * 24 : 0.0) + (grot ? J * 32 : 0.0) + (palette ? p.V * 48.0 : 0.0)) +
+               (palette ? (double)((n + WORLD_FPB - 1) / WORLD_FPB) * WORLD_BIND_DOUBLES(p.V) * 8.0 : 0.0),      // every workgroup reads the bind
+           launch_world_pose(p, s));
+    return 0;
+}
+
 int mocha_bvh_motion(mocha_ctx* c, const char* text_dev, int64_t nbytes, const char* text_host, const int64_t* clip_text_begin,
                      const int64_t* clip_text_end, const int32_t* clip_offsets, int n_clips, int n_joints, int channels,
                      const int32_t* joint_map, int v_out, const float* offsets_out, float* rot, float* pos, mocha_bvh_report* report,

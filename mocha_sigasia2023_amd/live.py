@@ -22,6 +22,7 @@ from .generator import DIM, NTOK, _dev_f32, _ptr, _stream
 from .multi_character import MIX_PARTS, MultiCharacterBank, _refuse_with_mix, mix_count, mix_tensors, soft_params
 from .ingest import IngestConfig, reset_ingest
 from .postprocess import PostProcessor
+from .world import SkinBind, _launch as _world_launch
 
 
 class LiveSession:
@@ -45,10 +46,17 @@ class LiveSession:
     the captured step reads - ``push(..., mix=(ids, weights))``, ``set_mix`` or written in place, e.g. a weight ramp for a cross-fade or a
     0/1 mask per body part for a splice; ``characters`` is not used.  ``idx`` is then (S,J) and the outputs gain ``weight`` (S,J,6), the
     weights normalised per body part.  A stream none of whose components is present (no loaded character with a usable weight) sits the
-    step out as a warming one.  Combines with ``raw=``; not with ``soft``, ``inertial`` or ``constrained``."""
+    step out as a warming one.  Combines with ``raw=``; not with ``soft``, ``inertial`` or ``constrained``.
+    ``world=SkinBind(...)`` or ``world=True``: every push also gives the frame in WORLD space - the outputs gain ``gpos`` (S,V+1,3) and
+    ``grot`` (S,V+1,4) float64, the reference's ``quat.fk`` of ``pos`` and ``ik_rot``, and with a bind ``palette`` (S,V,12) fp32, the 3x4
+    skinning matrices ``pre . world . inverse(bind)`` of bones 1..V in one buffer a renderer can bind (``world.py``).  ONE
+    ``mocha_world_pose`` launch BEHIND the captured graph, on the same stream, reads ``out["pos"]``, ``out["ik_rot"]`` and ``out["valid"]``
+    - it is not a node of the graph, as the resampler sits in front of the graph and not in it - so the step's capture, its key and every
+    existing output are what they are without ``world``.  Fixed tensors, overwritten by the next push; rows of a warming stream are not
+    written; no host synchronisation.  The default ``None`` leaves everything as it is."""
 
     def __init__(self, bank: MultiCharacterBank, cnt_mean, cnt_std, streams: int = 1, post: Optional[PostProcessor] = None, bvh: bool = True,
-                 soft=None, inertial: Optional[float] = None, raw=None, constrained: bool = False, mix=None):
+                 soft=None, inertial: Optional[float] = None, raw=None, constrained: bool = False, mix=None, world=None):
         if not 1 <= int(streams) <= 16:
             raise ValueError("streams must be 1..16")
         self.mix = None
@@ -119,6 +127,16 @@ class LiveSession:
             self.mix_weights = torch.zeros((S, self.mix, MIX_PARTS), dtype=torch.float32, device=dev)
             self.out["idx"] = torch.full((S, self.mix), -1, dtype=torch.int32, device=dev)
             self.out["weight"] = torch.zeros((S, self.mix, MIX_PARTS), dtype=torch.float32, device=dev)
+        self.world = self.world_bind = None
+        if world is not None and world is not False:
+            if world is not True and not isinstance(world, SkinBind):
+                raise TypeError("LiveSession: world is a SkinBind, True (global poses, no palette) or None")
+            if world is not True and world.model is not m:
+                raise ValueError("LiveSession: world belongs to another model")
+            self.world, self.world_bind = True, (None if world is True else world)
+            self.out["gpos"], self.out["grot"] = f64(S, J, 3), f64(S, J, 4)
+            if self.world_bind is not None:
+                self.out["palette"] = f32(S, V, 12)
         bank._ensure()
 
     @property
@@ -191,6 +209,9 @@ class LiveSession:
 
     def replay_raw(self):
         """The raw step on what ``raw_rot`` / ``raw_pos`` hold (a producer on the device may have written them in place)."""
+        return self._world_pose(self._step_raw())
+
+    def _step_raw(self):
         if self.raw is None:
             raise RuntimeError("LiveSession.replay_raw: the session was not created with raw=")
         self.bank._ensure()
@@ -221,6 +242,15 @@ class LiveSession:
 
     def replay(self):
         """The step on what the fixed buffers hold (a producer on the device may have written them in place)."""
+        return self._world_pose(self._step())
+
+    def _world_pose(self, o):
+        """``world=``: one ``mocha_world_pose`` launch behind the captured step, on its stream, from the frame the step just wrote."""
+        if self.world is not None:
+            _world_launch(self.model, o["ik_rot"], o["pos"], self.streams, o["valid"], self.world_bind, o["gpos"], o["grot"], o.get("palette"))
+        return o
+
+    def _step(self):
         self.bank._ensure()
         o = self.out
         if self.mix is not None:
@@ -343,7 +373,7 @@ class LiveOursSession(LiveSession):
 
     def __init__(self, bank: MultiCharacterBank, cnt_mean, cnt_std, cvae_state_dict, src_cnt_mean, src_cnt_std, cha_encoded_mean,
                  cha_encoded_std, streams: int = 1, post: Optional[PostProcessor] = None, bvh: bool = True, noise: str = "device",
-                 seed: int = 0, soft=None, inertial=None, raw=None, constrained: bool = False, cvaes=None, cvae_of=None, mix=None):
+                 seed: int = 0, soft=None, inertial=None, raw=None, constrained: bool = False, cvaes=None, cvae_of=None, mix=None, world=None):
         if cvaes is None and cvae_of is not None:
             raise ValueError("LiveOursSession: cvae_of needs cvaes=CVAEBank(...)")
         if cvaes is not None:
@@ -365,7 +395,7 @@ class LiveOursSession(LiveSession):
             raise ValueError("LiveOursSession: mix= is not supported - the CVAE branch samples one character's feature per stream")
         if noise not in self.NOISE:
             raise ValueError(f"noise must be one of {sorted(self.NOISE)}")
-        super().__init__(bank, cnt_mean, cnt_std, streams=streams, post=post, bvh=bvh)
+        super().__init__(bank, cnt_mean, cnt_std, streams=streams, post=post, bvh=bvh, world=world)
         m, dev, S = self.model, self.model.device, self.streams
         self.cvaes, self.cvae_of = cvaes, None
         if cvaes is not None:
@@ -407,7 +437,7 @@ class LiveOursSession(LiveSession):
         self.cvae_of[int(character)].fill_(int(slot))
         return self
 
-    def replay(self):
+    def _step(self):
         self.bank._ensure()
         o = self.out
         if self.cvae_of is not None:

@@ -27,6 +27,9 @@ mocha_profile_start / stop, during which the step runs eagerly.
     python tools/live_latency.py --raw 2 [--out profiles/r13/live_raw_step.json]
         the plain live step and the raw step (LiveSession(raw=L) = mocha_live_step_raw: one more launch, mocha_live_ingest, in front of
         the ring push), alternating replay by replay in one process, S = 1 and S = 8, both past their warm-up
+    python tools/live_latency.py --world [--out profiles/r22/live_world_step.json]
+        the plain live step and the one with world=SkinBind (one more launch, mocha_world_pose, behind the captured graph): both p50 in one
+        file, from one run of one tree
     python tools/live_latency.py --mix 1,2,4 [--out profiles/r20/live_mix_step.json]
         character mixing: the plain live step, the soft live step at k = J and the mix step (LiveSession(mix=J) = mocha_live_step_mix)
         with every stream's J components on J different characters, alternating replay by replay in one process, S = 1, 8 and 16, for
@@ -410,6 +413,49 @@ def raw(a, dev, model, mb, mean, std, clip, per, J):
     return res
 
 
+def world(a, dev, model, mb, mean, std, clip, per, J):
+    """--world: the plain live step and the one with world= (one more launch, mocha_world_pose, BEHIND the captured graph on the same
+    stream: global poses and the skinning palette), alternating in one process."""
+    from mocha_sigasia2023_amd import LiveSession, SkinBind
+    res = {"bank": "8 characters x 2048 rows, fp32, segmented", "layout": "mocha (24 joints)",
+           "timing": "HIP events around single pushes' device work; (a) live step = one graph replay, (b) live step with world=SkinBind = the "
+                     "replay and one mocha_world_pose launch behind it, alternating", "streams": {}}
+    rng = np.random.Generator(np.random.PCG64(22))
+    bind = SkinBind(model, rng.uniform(-0.3, 0.3, (J, 3)), rng.standard_normal((J, 4)), [[100.0, 0, 0, 0], [0, 0, 100.0, 0], [0, 100.0, 0, 0]])
+    for S in (1, 8, 16):
+        ids = torch.tensor([(k * 3) % 8 for k in range(S)], dtype=torch.int32)
+        plain, wd = LiveSession(mb, mean, std, streams=S), LiveSession(mb, mean, std, streams=S, world=bind)
+        frame = [0]
+
+        def push():
+            f = frame[0] % 644; frame[0] += 1
+            for sess in (plain, wd):
+                sess.rot.copy_(clip[0][f]); sess.pos.copy_(clip[1][f]); sess.vel.copy_(clip[2][f]); sess.ang.copy_(clip[3][f])
+                sess.rvel.copy_(per[0][f]); sess.rang.copy_(per[1][f]); sess.speed.copy_(per[2][f]); sess.contact.copy_(per[3][f])
+        for sess in (plain, wd):
+            sess.characters.copy_(ids)
+        for _ in range(max(a.warmup, 70)):
+            push(); plain.replay(); wd.replay()
+        torch.cuda.synchronize()
+        assert bool((wd.out["valid"] == 1).all()) and all(torch.equal(wd.out[k], plain.out[k]) for k in plain.out)
+        ta, tb = [], []
+        for _ in range(a.reps):
+            push(); torch.cuda.synchronize()
+            ta.append(event_ms(plain.replay, 1)[0]); tb.append(event_ms(wd.replay, 1)[0])
+        e = {"a_live_step": pct(np.asarray(ta)), "b_live_step_world": pct(np.asarray(tb))}
+        e["b_minus_a_p50_ms"] = e["b_live_step_world"]["p50_ms"] - e["a_live_step"]["p50_ms"]
+        n = 200                                          # the added launch on its own (eager while profiling)
+        model.profile_start()
+        for _ in range(n):
+            wd.replay()
+        prof = model.profile_stop()
+        e["sites_us"] = {k: 1e3 * v["ms"] / v["launches"] for k, v in prof["sites"].items() if k.split("|")[0] == "world.pose"}
+        assert bool(torch.isfinite(wd.out["palette"]).all()) and bool(torch.isfinite(wd.out["gpos"]).all())
+        res["streams"][str(S)] = e
+        del plain, wd
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=1000)
@@ -423,7 +469,10 @@ def main():
     ap.add_argument("--raw", type=int, default=None, metavar="L", help="raw mocap input: live step / raw live step with L frames of lookahead")
     ap.add_argument("--constrained", action="store_true", help="action-constrained matching: live step / constrained live step with zero masks / one action of 16")
     ap.add_argument("--mix", default=None, metavar="J[,J..]", help="character mixing: live step / soft live step at k = J / mix live step with J components, S = 1, 8, 16")
+    ap.add_argument("--world", action="store_true", help="world-space poses: live step / live step with world=SkinBind (one mocha_world_pose launch behind the graph), S = 1, 8, 16")
     a = ap.parse_args()
+    if a.world and a.out == ap.get_default("out"):
+        a.out = os.path.join(ROOT, "profiles", "r22", "live_world_step.json")
     if a.mix is not None:
         a.mix = [int(x) for x in a.mix.split(",")]
         if not a.mix or any(not 1 <= j <= 4 for j in a.mix):
@@ -463,6 +512,8 @@ def main():
     per = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (rvel, rang, np.linalg.norm(hipvel, axis=-1).mean(-1).astype(np.float32), contact)]
     res = {"bank": "8 characters x 2048 rows, fp32, segmented", "layout": "mocha (24 joints)", "timing": "HIP events around single graph replays, live and baseline alternating",
            "streams": {}}
+    if a.world:
+        return write_out(a, world(a, dev, model, mb, mean, std, clip, per, J))
     if a.mix is not None:
         return write_out(a, mix(a, dev, model, mb, mean, std, clip, per, J))
     if a.constrained:
