@@ -51,7 +51,13 @@ ap.add_argument("--resample", type=float, metavar="R",
                      "is fixed to 60)")
 ap.add_argument("--world", metavar="OUT.npz", help="save the global bone positions of the source and of the two outputs: what the "
                                                      "reference hands to animation_plot (world_pose: quat.fk on the device)")
+ap.add_argument("--coherent", type=float, metavar="L", help="coherent context matching for the NN branch: the source windows take a "
+                "jump-penalised path through the character clip's windows (penalty L per transition that is not 'next window of the "
+                "clip') instead of one nearest window each; prints the non-continuations with and without it")
+ap.add_argument("--coherent-relative", action="store_true", help="L in units of the median nearest distance instead of the matcher's")
 a = ap.parse_args()
+if a.coherent_relative and a.coherent is None:
+    ap.error("--coherent-relative goes with --coherent L")
 if bool(a.src_bvh) != bool(a.cha_bvh):
     ap.error("--src-bvh and --cha-bvh go together")
 if a.resample is not None and not a.src_bvh:
@@ -116,11 +122,20 @@ cha_X = model.featurize(*cha_bones)
 # ---- NN branch for the whole clip                                                            :188-194, 271-302, 438-443, 465-467
 Y, idx, cha_enc, cha_nm = model.characterize_pair(src_X, cha_X, cnt_mean, cnt_std, return_index=True, return_bank=True, raw=True)
 bank = ContextBank(model, cha_nm, cha_enc)
+coherent = None
+if a.coherent is not None:
+    from mocha_sigasia2023_amd import CoherentMatch  # noqa: E402
+    coherent = CoherentMatch(a.coherent, relative=a.coherent_relative)
+    hard_idx = idx
+    Y, idx = model.characterize_pair(src_X, cha_X, cnt_mean, cnt_std, return_index=True, raw=True, coherent=coherent)
+    jumps = lambda ix: int(len(ix) - 1 - (ix[1:] == ix[:-1] + 1).sum())       # noqa: E731
+    print(f"non-continuations over {N} windows: hard match {jumps(hard_idx)}, coherent (jump {a.coherent:g}"
+          f"{' x median nearest distance' if a.coherent_relative else ''}) {jumps(idx)}")
 # the reference's "cm_" stream takes the decoded poses as they are: no blending with the previous frame, no foot-lock IK
 # (test_fullframework.py:512-527, 637-641)
 from mocha_sigasia2023_amd import PostProcessor  # noqa: E402
 nn = retarget_clip(bank, src_X, cnt_mean, cnt_std, rvel, rang, src_speed, contact, raw=True,
-                   post=PostProcessor(model, ik_enabled=False, blend=False))
+                   post=PostProcessor(model, ik_enabled=False, blend=False), coherent=coherent)
 # ---- Ours branch: CVAE frame loop seeded with the first matched character feature            :298, 436, 446-457
 src_enc, src_cnt = model.encode(src_X, raw=True)
 sess = OursSession(model, cvae, *stats).reset(cha_enc[int(idx[0])])

@@ -400,6 +400,64 @@ int mocha_characterize_pair_raw(mocha_ctx* ctx, const float* src_X_raw, int B_sr
                                 const float* cnt_mean, const float* cnt_std, float* Y, int32_t* idx, float* cha_encoded,
                                 float* cha_cnt_nm, void* stream);
 
+/* Coherent context matching for clips: a jump-penalised path through the distance matrix instead of one arg-min per window.  The
+ * reference's 'cm_' branch takes the nearest bank entry per frame and carries nothing from one frame to the next
+ * (test_fullframework.py:440-443).  Its banks are stride-1 windows of smooth clips (collect_CVAE_feature_action.py:119-125), so the right
+ * answer for consecutive source windows is almost always a run of consecutive bank rows; the independent arg-min leaves that run whenever
+ * noise makes a far entry marginally nearer.  An extension the reference does not have; it needs nothing trained and changes no other call.
+ * Definition.  d (Q x N) fp32: the Euclidean distance between z-scored query window i and bank row j, the direct-form sum of the library's
+ * matchers (sqrtf of the fp32 squared distance).  Sequence starts 0 = s_0 < s_1 < ... < Q: windows of different sequences are independent.
+ * Bank starts b in [0, N): a row j with j = 0 or j in b has no predecessor (the range_starts every bank file carries).  A jump penalty
+ * lambda, finite and >= 0, in the units of d.  In float64 on the fp32 values of d, with the relative cost R re-based every step:
+ *   first window of a sequence:  R[i][j] = d[i][j]
+ *   otherwise:                   a = R[i-1][j-1] - M[i-1] if row j has a predecessor, else +inf;  cont(i, j) = (a < lambda), strict: a tie
+ *                                jumps;  R[i][j] = d[i][j] + (cont ? a : lambda)
+ *   M[i] = min_j R[i][j], m[i] the lowest j attaining it.
+ *   backtrack per sequence:      path[last] = m[last];  path[i] = path[i+1] - 1 if cont(i+1, path[i+1]), else m[i].
+ * This is the minimum over all row sequences of sum d[i][j_i] + lambda * (transitions that are not "next row of the same clip"), with the
+ * tie rules fixed.  lambda = 0: nothing continues, R[i] = d[i], path[i] is the lowest-index arg-min of row i - the hard match.  Every step
+ * is one float64 subtraction, one exact minimum and one float64 addition, so the device gives the sequential evaluation's path to the bit.
+ *   mocha_match_dist_matrix : dist[i * ld + j] for Q queries (Q, 90*256; DEVICE) against rows [row0, row0 + rows) of the current bank's
+ *                             fp32 rows (also when the bank keeps a bf16 copy), ld >= rows.  Entry (i, j) is bit for bit the distance
+ *                             mocha_match_topk reports for (query i, row row0 + j) on an fp32 bank.  Only takes a row range: works on a
+ *                             plain, a segmented and a resident bank.  Nothing outside [0, Q) x [0, rows) of dist is written.  The
+ *                             all-keys scan behind mocha_match_topk with every group of 8 queries in one launch (ceil(Q / 8) passes over
+ *                             the rows), then one launch that turns keys into distances; 8 bytes of context scratch per entry.
+ *   mocha_match_path        : a pure function of a DEVICE matrix dist (Q x N, leading dimension ld); needs no bank.  seq_start (HOST,
+ *                             n_seq + 1 int32) and bank_start (HOST, n_b int32, sorted; NULL / 0: only row 0 starts a clip) are uploaded
+ *                             by the call.  Outputs (DEVICE): path (Q) int32; dist_out (Q) fp32 = dist[i][path[i]] or NULL; continued (Q)
+ *                             uint8 or NULL: 1 where path[i] == path[i-1] + 1, that row has a predecessor and i is not a sequence start.
+ *                             One workgroup per sequence: SEQUENTIAL in the sequence's length, one workgroup barrier per window, then a
+ *                             backtrack launch with one dependent read per window.  N <= 16 384.
+ *   mocha_characterize_path : mocha_characterize (raw != 0: mocha_characterize_raw) with the path over the whole bank in the matcher's
+ *                             place: encode, z-score, matrix, path, then the decoder and to_mot on the path's rows.  idx (B) the path or
+ *                             NULL; continued (B) or NULL.  A batch of more than one workspace chunk encodes twice (the path spans chunks).
+ *                             lambda = 0 gives mocha_characterize's indices on tie-free data (ties: the lowest row) and its Y.
+ *                             relative != 0: the penalty is lambda x the median over the B windows of their nearest distance (the lower
+ *                             median of the matrix's row minima, taken from the call's own matrix; the call then waits for the stream).
+ *   mocha_characterize_pair_path : mocha_characterize_pair[_raw] likewise, against the transient bank (bank starts index the B_cha rows).
+ * Scratch (the scan's keys, the matrix of the characterize forms, m, the continuation bits - 2 KB per window -, the uploaded lists) is the context's own and
+ * grows on first use; it does not move mocha_generation, so captured steps keep replaying.  These are BATCH calls: they allocate and copy
+ * from host memory and are NOT capture-safe.  The scratch is one set per context whatever the stream: two of these calls on different
+ * streams of one context must be ordered by the caller (as a context is driven from one stream at a time everywhere else).
+ * Refusals, nothing launched: MOCHA_ERR_ARG for a NULL context or required pointer, Q < 0 (Q = 0 returns 0), rows < 1 or a range outside
+ * the bank, ld < rows, lambda negative, NaN or infinite, starts that are unsorted or out of range, seq_start[0] != 0 or a last entry
+ * != Q, more than 16 384 rows; MOCHA_ERR_STATE without a bank, and for mocha_characterize_path on a resident bank.
+ * What it is not: no "stay" or "skip" transitions (time warping), one constant penalty, no online or live form (that needs every row's
+ * distance inside the captured step). */
+#define MOCHA_PATH_MAX_ROWS 16384
+int mocha_match_dist_matrix(mocha_ctx* ctx, const float* query_nm, int Q, int64_t row0, int64_t rows, float* dist, int64_t ld, void* stream);
+int mocha_match_path(mocha_ctx* ctx, const float* dist, int Q, int N, int64_t ld, const int32_t* seq_start, int n_seq,
+                     const int32_t* bank_start, int n_b, double lambda, int32_t* path, float* dist_out, unsigned char* continued,
+                     void* stream);
+int mocha_characterize_path(mocha_ctx* ctx, const float* src_X, int B, const float* cnt_mean, const float* cnt_std, const int32_t* seq_start,
+                            int n_seq, const int32_t* bank_start, int n_b, double lambda, int relative, float* Y, int32_t* idx,
+                            unsigned char* continued, int raw, void* stream);
+int mocha_characterize_pair_path(mocha_ctx* ctx, const float* src_X, int B_src, const float* cha_X, int B_cha, const float* cnt_mean,
+                                 const float* cnt_std, const int32_t* seq_start, int n_seq, const int32_t* bank_start, int n_b,
+                                 double lambda, int relative, float* Y, int32_t* idx, unsigned char* continued, float* cha_encoded,
+                                 float* cha_cnt_nm, int raw, void* stream);
+
 /* CVAE character-feature sampler: CVAE.sample(c) of model_CVAE.py:44-46, i.e.
  * PriorNet (:49-92) then Decoder (:138-165).  Weights by their reference state_dict names
  * ("prior_net.encoder.layers.0.self_attn.in_proj_weight", ...; test_fullframework.py:52-58); the

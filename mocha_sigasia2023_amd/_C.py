@@ -94,6 +94,12 @@ SIGNATURES = {
     "mocha_characterize_raw": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "mocha_characterize_pair": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocha_characterize_pair_raw": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocha_match_dist_matrix": (_i, [_vp, _vp, _i, _i64, _i64, _vp, _i64, _vp]),
+    "mocha_match_path": (_i, [_vp, _vp, _i, _i, _i64, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), _i, C.c_double, _vp, _vp, _vp, _vp]),
+    "mocha_characterize_path": (_i, [_vp, _vp, _i, _vp, _vp, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), _i, C.c_double, _i, _vp, _vp, _vp,
+                                     _i, _vp]),
+    "mocha_characterize_pair_path": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), _i, C.c_double, _i,
+                                          _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "mocha_cvae_load_weight": (_i, [_vp, C.c_char_p, _vp, C.POINTER(_i64), _i]),
     "mocha_cvae_finalize": (_i, [_vp]),
     "mocha_cvae_sample": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -234,6 +234,15 @@ def load_bank(path: str, norm_path: Optional[str] = None) -> dict:
     return out
 
 
+def bank_starts(bank: dict):
+    """The ``range_starts`` of a bank dict (``load_bank``, ``build_bank_from_database``) as the sorted list of rows that begin a clip,
+    which ``ContextBank.query_path`` and ``CoherentMatch`` take as ``bank_starts``; [0] for a bank without ranges."""
+    rs = bank.get("range_starts") if hasattr(bank, "get") else None
+    if rs is None or len(rs) == 0:
+        return [0]
+    return sorted(set(int(v) for v in np.asarray(rs).reshape(-1)))
+
+
 def reduce_matches(dist_local: torch.Tensor, idx_global: torch.Tensor):
     """All-gather per-rank (distance, global index) candidates and keep the nearest per query; ties go to the lowest
     index, as in the single-GPU matcher.  Works on any backend (tested with gloo)."""

@@ -542,6 +542,21 @@ hipError_t launch_match_stream(const void* bank, int bank_bf16, const float* que
 // k nearest rows per query, exact (every row's direct-form distance, then a k-pass selection); keys = 8 * N u64 words of scratch
 hipError_t launch_match_topk(const void* bank, int bank_bf16, const float* query, int Q, int64_t N, int D, int k,
                              unsigned long long* keys, int32_t* idx, float* dist, hipStream_t s);
+// Coherent context matching (match_path.hip).  launch_match_dist: dist[i * ld + j] = the distance launch_match_topk reports for query i
+// and row j of the `rows` fp32 rows at bank_rows, bit for bit; nothing outside [0, Q) x [0, rows) is written.  launch_match_path: the
+// jump-penalised path of include/mocha_hip.h through d (Q x N, leading dimension ld); seq_start_dev (n_seq + 1) and bank_start_dev (n_b)
+// are device lists the caller validated; scratch: start_bits match_path_bits_words(N) 32-bit words, m Q ints, cont
+// match_path_cont_words(Q) 16-bit words.  N <= MATCH_PATH_MAX_ROWS.
+static constexpr int MATCH_PATH_MAX_ROWS = 16384;
+size_t match_dist_keys_words(int Q, int rows);       // u64 words of `keys`
+hipError_t launch_match_dist(const float* bank_rows, const float* query, int Q, int rows, int D, unsigned long long* keys, float* dist, int64_t ld,
+                             hipStream_t s);
+hipError_t launch_path_rowmin(const float* d, int Q, int N, int64_t ld, float* out /*Q*/, hipStream_t s);      // out[i] = min_j d[i][j]
+size_t match_path_bits_words(int N);
+size_t match_path_cont_words(int Q);
+hipError_t launch_match_path(const float* d, int Q, int N, int64_t ld, const int32_t* seq_start_dev, int n_seq, const int32_t* bank_start_dev,
+                             int n_b, double lambda, unsigned* start_bits, int32_t* m, unsigned short* cont, int32_t* path, float* dist_out,
+                             unsigned char* continued, hipStream_t s);
 // out[q] = sum_j softmax_j(-dist[q][j] / temperature) * src[idx[q][j]] over the k neighbours of query q
 hipError_t launch_gather_blend(const float* src, const int32_t* idx, const float* dist, float temperature, float* out, int Q, int k,
                                int cols, int64_t nrows, hipStream_t s);

@@ -359,6 +359,15 @@ struct mocha_ctx {
     // device: the BVH text writer's report, clip byte offsets, uploaded tables and per-block byte counts (mocha_bvh_format).  Grow-only;
     // only that call reads it and it is never captured, so a new allocation does not move the generation.
     DeviceBuffer<unsigned long long> bvhw_ws;
+    // device: coherent matching's scratch (mocha_match_path, mocha_characterize_path, mocha_characterize_pair_path) - the distance matrix
+    // of the characterize forms, the row minima's columns, the continuation bits, the uploaded start lists and the bank starts' bit per
+    // row.  Grow-only; batch calls that are never captured read it, so a new allocation does not move the generation.
+    DeviceBuffer<float> path_d;
+    DeviceBuffer<int32_t> path_m, path_lists;
+    DeviceBuffer<unsigned short> path_cont;
+    DeviceBuffer<unsigned> path_bits;
+    DeviceBuffer<unsigned long long> path_keys;        // the matrix's all-keys scan: one key per entry
+    DeviceBuffer<float> path_min;                      // a relative penalty's row minima
     DeviceBuffer<float> pose_norm;     // [x_mean | x_std | y_mean | y_std], (V+1)*C_in each (norm.npz of the reference)
     bool use_tiled = false;            // option "bank_tiled": -4 % on the cold pass for 2 x the bf16 copy's memory (profiles/r04/c_tiled_loader_ab.txt): off
     DeviceBuffer<unsigned long long> topk_keys{BUF_MOVES_GENERATION};      // every row's key of up to 8 queries (mocha_match_topk)
@@ -2169,6 +2178,80 @@ int mocha_bank_gather(mocha_ctx* c, const int32_t* idx, int Q, float* out, void*
     return 0;
 }
 
+// coherent context matching: what the entry points further down and the pair form share
+}  // extern "C"
+
+namespace {
+// the host lists of a path call: what they must satisfy, with nothing launched when they do not
+struct PathArgs {
+    const int32_t* seq_start = nullptr; int n_seq = 0;
+    const int32_t* bank_start = nullptr; int n_b = 0;
+    double lambda = 0.0;
+    bool relative = false;                             // lambda in units of the median over the windows of their nearest distance
+    unsigned char* continued = nullptr;
+};
+
+int path_check(mocha_ctx* c, const PathArgs& a, int Q, int64_t N, const char* who) {
+    if (!(a.lambda >= 0.0) || !std::isfinite(a.lambda)) return fail(c, MOCHA_ERR_ARG, "%s: the jump penalty must be finite and >= 0", who);
+    if (N < 1) return fail(c, MOCHA_ERR_ARG, "%s: no bank rows", who);
+    if (N > MATCH_PATH_MAX_ROWS) return fail(c, MOCHA_ERR_ARG, "%s: %lld bank rows; a path call serves up to %d", who, (long long)N, MATCH_PATH_MAX_ROWS);
+    if (!a.seq_start || a.n_seq < 1 || a.n_seq > Q) return fail(c, MOCHA_ERR_ARG, "%s: sequence starts: 1 .. Q sequences, n_seq + 1 entries", who);
+    if (a.seq_start[0] != 0 || a.seq_start[a.n_seq] != Q) return fail(c, MOCHA_ERR_ARG, "%s: sequence starts must begin at 0 and end at Q", who);
+    for (int i = 0; i < a.n_seq; ++i)
+        if (a.seq_start[i + 1] <= a.seq_start[i]) return fail(c, MOCHA_ERR_ARG, "%s: sequence starts must increase strictly", who);
+    if (a.n_b < 0 || (a.n_b > 0 && !a.bank_start)) return fail(c, MOCHA_ERR_ARG, "%s: bank starts: a list or none", who);
+    for (int i = 0; i < a.n_b; ++i) {
+        if (a.bank_start[i] < 0 || a.bank_start[i] >= N) return fail(c, MOCHA_ERR_ARG, "%s: bank start %d outside the %lld rows", who, (int)a.bank_start[i], (long long)N);
+        if (i && a.bank_start[i] <= a.bank_start[i - 1]) return fail(c, MOCHA_ERR_ARG, "%s: bank starts must increase strictly", who);
+    }
+    return 0;
+}
+
+// the path through d (Q x N, leading dimension ld; device) -> path, dist_out, continued (device).  The caller ran path_check.
+int path_run(mocha_ctx* c, const float* d, int Q, int N, int64_t ld, const PathArgs& a, int32_t* path, float* dist_out, hipStream_t s) {
+    int rc;
+    if ((rc = reserve(c, c->path_m, (size_t)Q))) return rc;
+    if ((rc = reserve(c, c->path_cont, match_path_cont_words(Q)))) return rc;
+    if ((rc = reserve(c, c->path_bits, match_path_bits_words(N)))) return rc;
+    if ((rc = reserve(c, c->path_lists, (size_t)a.n_seq + 1 + (size_t)std::max(a.n_b, 1)))) return rc;
+    double lambda = a.lambda;
+    if (a.relative) {
+        // the unit comes from the matrix itself: row minima on the device, their (lower) median on the host - a batch call, the stream
+        // is drained here
+        if ((rc = reserve(c, c->path_min, (size_t)Q))) return rc;
+        LAUNCH(c, s, "mocha_path_rowmin", "match.path_unit", 0.0, 4.0 * Q * N, launch_path_rowmin(d, Q, N, ld, c->path_min.p, s));
+        std::vector<float> mins((size_t)Q);
+        HIPCHK(c, hipMemcpyAsync(mins.data(), c->path_min.p, (size_t)Q * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        std::nth_element(mins.begin(), mins.begin() + (Q - 1) / 2, mins.end());
+        lambda = a.lambda * (double)mins[(size_t)(Q - 1) / 2];
+        if (!(lambda >= 0.0) || !std::isfinite(lambda)) return fail(c, MOCHA_ERR_ARG, "relative jump penalty: the distances' median is not finite");
+    }
+    int32_t* seq_dev = c->path_lists.p;
+    int32_t* bank_dev = c->path_lists.p + a.n_seq + 1;
+    // (pageable host memory: the copy is staged before the call returns, the caller's lists are free after it)
+    HIPCHK(c, hipMemcpyAsync(seq_dev, a.seq_start, ((size_t)a.n_seq + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (a.n_b > 0) HIPCHK(c, hipMemcpyAsync(bank_dev, a.bank_start, (size_t)a.n_b * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    LAUNCH(c, s, "mocha_match_path", "match.path", 4.0 * Q * N, 4.0 * Q * N + 2.0 * match_path_cont_words(Q),
+           launch_match_path(d, Q, N, ld, seq_dev, a.n_seq, bank_dev, a.n_b, lambda, c->path_bits.p, c->path_m.p, c->path_cont.p, path, dist_out,
+                             a.continued, s));
+    return 0;
+}
+
+// matrix of Q queries against N fp32 rows into the context's own matrix, then the path through it
+int path_match(mocha_ctx* c, const float* rows, int64_t N, const float* q, int Q, const PathArgs& a, int32_t* path, hipStream_t s) {
+    int rc;
+    const int D = 90 * 256;
+    if ((rc = reserve(c, c->path_d, (size_t)Q * N))) return rc;
+    if ((rc = reserve(c, c->path_keys, match_dist_keys_words(Q, (int)N)))) return rc;
+    LAUNCH(c, s, "mocha_match_dist", "match.dist_matrix", 3.0 * Q * N * D, ((Q + 7) / 8) * (double)N * D * 4.0,
+           launch_match_dist(rows, q, Q, (int)N, D, c->path_keys.p, c->path_d.p, N, s));
+    return path_run(c, c->path_d.p, Q, (int)N, N, a, path, nullptr, s);
+}
+}  // namespace
+
+extern "C" {
+
 // The characterize against the bank as ONE set of rows (mocha_characterize, mocha_step_graph)
 static int characterize_impl(mocha_ctx* c, const float* src_X, int B, const float* cnt_mean, const float* cnt_std, float* Y,
                              int32_t* idx, void* stream, bool raw) {
@@ -2270,7 +2353,7 @@ int mocha_characterize_raw(mocha_ctx* c, const float* src_X_raw, int B, const fl
 // workspace for the duration of the call and the context's own bank (mocha_bank_set) is left untouched.
 static int characterize_pair_impl(mocha_ctx* c, const float* src_X, int B_src, const float* cha_X, int B_cha, const float* cnt_mean,
                                   const float* cnt_std, float* Y, int32_t* idx, float* cha_encoded, float* cha_cnt_nm, void* stream,
-                                  bool raw) {
+                                  bool raw, const PathArgs* path = nullptr) {
     if (!c) return MOCHA_ERR_ARG;
     if (B_src < 0 || B_cha < 1) return fail(c, MOCHA_ERR_ARG, "characterize_pair: needs B_src >= 0 and B_cha >= 1");
     const long long total = (long long)B_src + B_cha;
@@ -2279,6 +2362,7 @@ static int characterize_pair_impl(mocha_ctx* c, const float* src_X, int B_src, c
                     "use mocha_encode + mocha_bank_set + mocha_characterize)", total, c->max_chunk);
     int rc = ready(c, (int)total); if (rc) return rc;
     if (!cnt_mean || !cnt_std || !cha_X || (B_src > 0 && (!src_X || !Y))) return fail(c, MOCHA_ERR_ARG, "null argument");
+    if (path && B_src > 0 && (rc = path_check(c, *path, B_src, B_cha, "mocha_characterize_pair_path"))) return rc;
     hipStream_t s = (hipStream_t)stream;
     c->cur = 0;
     const size_t T = 90 * 256;
@@ -2321,10 +2405,16 @@ static int characterize_pair_impl(mocha_ctx* c, const float* src_X, int B_src, c
     if (B_src == 0) return 0;
     // transient bank: c->pair borrows the workspace rows and keeps its own norms, centroid and packed plane image - the user's current
     // bank (c->bank) and what was derived from it are not touched
-    rc = bank_set_impl(c, c->pair, WS(c, "qnm"), WS(c, "enc_s"), B_cha, MOCHA_BANK_BORROW, stream);
     int32_t* ix = idx ? idx : c->sets[0].idx_ws.p;
-    if (!rc) rc = do_match(c, c->pair, WS(c, "qnm") + (size_t)B_cha * T, B_src, ix, nullptr, s);
-    c->pair.cnt = c->pair.enc = nullptr; c->pair.N = 0;   // the workspace rows were lent for this call only
+    if (path) {
+        // coherent matching needs the rows themselves, none of the transient bank's derived data: the matrix against rows [0, B_cha) of the
+        // workspace, then the path
+        rc = path_match(c, WS(c, "qnm"), B_cha, WS(c, "qnm") + (size_t)B_cha * T, B_src, *path, ix, s);
+    } else {
+        rc = bank_set_impl(c, c->pair, WS(c, "qnm"), WS(c, "enc_s"), B_cha, MOCHA_BANK_BORROW, stream);
+        if (!rc) rc = do_match(c, c->pair, WS(c, "qnm") + (size_t)B_cha * T, B_src, ix, nullptr, s);
+        c->pair.cnt = c->pair.enc = nullptr; c->pair.N = 0;   // the workspace rows were lent for this call only
+    }
     { const int rj = join(); if (!rc) rc = rj; }          // the decoder constants are complete (the caller's stream is never left forked)
     if (rc) return rc;
     // decoder on the matched character rows: the transient bank's encoded rows are rows [0, B_cha) of the workspace, their decoder
@@ -2341,6 +2431,102 @@ int mocha_characterize_pair(mocha_ctx* c, const float* src_X, int B_src, const f
 int mocha_characterize_pair_raw(mocha_ctx* c, const float* src_X_raw, int B_src, const float* cha_X_raw, int B_cha, const float* cnt_mean,
                                 const float* cnt_std, float* Y, int32_t* idx, float* cha_encoded, float* cha_cnt_nm, void* stream) {
     return characterize_pair_impl(c, src_X_raw, B_src, cha_X_raw, B_cha, cnt_mean, cnt_std, Y, idx, cha_encoded, cha_cnt_nm, stream, true);
+}
+
+// ------------------------------------------------------------------------------------------- coherent context matching
+// (include/mocha_hip.h "coherent context matching"; kernels in match_path.hip)
+int mocha_match_dist_matrix(mocha_ctx* c, const float* query_nm, int Q, int64_t row0, int64_t rows, float* dist, int64_t ld, void* stream) {
+    int rc = ready(c, 0); if (rc) return rc;
+    if (Q < 0) return fail(c, MOCHA_ERR_ARG, "mocha_match_dist_matrix: negative query count");
+    if (!c->bank.cnt || c->bank.N <= 0) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
+    if (rows < 1 || row0 < 0 || row0 > c->bank.N || rows > c->bank.N - row0)
+        return fail(c, MOCHA_ERR_ARG, "mocha_match_dist_matrix: rows [%lld, %lld) are not a range of the bank's %lld", (long long)row0,
+                    (long long)(row0 + rows), (long long)c->bank.N);
+    if (rows > INT32_MAX) return fail(c, MOCHA_ERR_ARG, "mocha_match_dist_matrix: too many rows");
+    if (ld < rows) return fail(c, MOCHA_ERR_ARG, "mocha_match_dist_matrix: ld < rows");
+    if (Q == 0) return 0;
+    if (!query_nm || !dist) return fail(c, MOCHA_ERR_ARG, "mocha_match_dist_matrix: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    const int D = 90 * 256;
+    if ((rc = reserve(c, c->path_keys, match_dist_keys_words(Q, (int)rows)))) return rc;
+    LAUNCH(c, s, "mocha_match_dist", "match.dist_matrix", 3.0 * Q * rows * D, ((Q + 7) / 8) * (double)rows * D * 4.0,
+           launch_match_dist(c->bank.cnt + (size_t)row0 * D, query_nm, Q, (int)rows, D, c->path_keys.p, dist, ld, s));
+    return 0;
+}
+
+int mocha_match_path(mocha_ctx* c, const float* dist, int Q, int N, int64_t ld, const int32_t* seq_start, int n_seq, const int32_t* bank_start,
+                     int n_b, double lambda, int32_t* path, float* dist_out, unsigned char* continued, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    if (Q < 0) return fail(c, MOCHA_ERR_ARG, "mocha_match_path: negative window count");
+    if (Q == 0) return 0;
+    if (!dist || !path) return fail(c, MOCHA_ERR_ARG, "mocha_match_path: null argument");
+    if (ld < N) return fail(c, MOCHA_ERR_ARG, "mocha_match_path: ld < N");
+    PathArgs a; a.seq_start = seq_start; a.n_seq = n_seq; a.bank_start = bank_start; a.n_b = n_b; a.lambda = lambda; a.continued = continued;
+    int rc = path_check(c, a, Q, N, "mocha_match_path"); if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return path_run(c, dist, Q, N, ld, a, path, dist_out, (hipStream_t)stream);
+}
+
+// mocha_characterize with the path in the matcher's place.  The path spans the whole batch, so the batch goes through the workspace
+// twice: encoder, z-score and matrix rows chunk by chunk, the path, then the decoder and to_mot chunk by chunk (a batch of more than one
+// chunk runs its embedding and encoder again for the second pass - the workspace holds one chunk's encoder output).
+int mocha_characterize_path(mocha_ctx* c, const float* src_X, int B, const float* cnt_mean, const float* cnt_std, const int32_t* seq_start,
+                            int n_seq, const int32_t* bank_start, int n_b, double lambda, int relative, float* Y, int32_t* idx,
+                            unsigned char* continued, int raw_, void* stream) {
+    int rc = ready(c, B); if (rc) return rc;
+    if ((rc = refuse_resident(c, "mocha_characterize_path"))) return rc;
+    if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set first");
+    if (B == 0) return 0;
+    if (!cnt_mean || !cnt_std || !src_X || !Y) return fail(c, MOCHA_ERR_ARG, "null argument");
+    PathArgs a; a.seq_start = seq_start; a.n_seq = n_seq; a.bank_start = bank_start; a.n_b = n_b; a.lambda = lambda; a.continued = continued;
+    a.relative = relative != 0;
+    const int64_t N = c->bank.N;
+    if ((rc = path_check(c, a, B, N, "mocha_characterize_path"))) return rc;
+    const bool raw = raw_ != 0;
+    const size_t ys = (size_t)60 * c->cfg.V * c->cfg.C_in;
+    const size_t xs = raw ? (size_t)60 * (c->cfg.V + 1) * c->cfg.C_in : ys;
+    const int D = 90 * 256;
+    if ((rc = reserve(c, c->path_d, (size_t)B * N))) return rc;
+    if ((rc = reserve(c, c->path_m, (size_t)2 * B))) return rc;      // (Q minima, then the path when the caller wants no indices)
+    if ((rc = reserve(c, c->path_keys, match_dist_keys_words(B, (int)N)))) return rc;      // (per chunk its own keys: two chunks may be in flight)
+    unsigned long long* keys = c->path_keys.p;
+    int chunks = 0;
+    auto encode = [&](int b0, int b, hipStream_t s) -> int {
+        int r;
+        if ((r = run_embed(c, src_X + b0 * xs, b, WS(c, "x5"), true, s, raw))) return r;
+        return run_encoder(c, WS(c, "x5"), b, WS(c, "enc_s"), s);
+    };
+    rc = for_chunks(c, B, (hipStream_t)stream, [&](int b0, int b, hipStream_t s) -> int {
+        int r;
+        ++chunks;
+        if ((r = encode(b0, b, s))) return r;
+        const InormExtra ex = IEXW(c, s);
+        LAUNCH(c, s, "mocha_instnorm", "mvn", 0.0, b * 90.0 * 256 * 4 * 2.0, launch_instnorm(WS(c, "enc_s"), nullptr, nullptr, cnt_mean, cnt_std, WS(c, "qnm"), b, 90, s, &ex));
+        LAUNCH(c, s, "mocha_match_dist", "match.dist_matrix", 3.0 * b * N * D, ((b + 7) / 8) * (double)N * D * 4.0,
+               launch_match_dist(c->bank.cnt, WS(c, "qnm"), b, (int)N, D, keys + (size_t)b0 * N, c->path_d.p + (size_t)b0 * N, N, s));
+        return 0;
+    });
+    if (rc) return rc;
+    hipStream_t s0 = (hipStream_t)stream;
+    int32_t* ix = idx ? idx : c->path_m.p + B;
+    if ((rc = path_run(c, c->path_d.p, B, (int)N, N, a, ix, nullptr, s0))) return rc;
+    const bool again = chunks > 1;
+    return for_chunks(c, B, s0, [&](int b0, int b, hipStream_t s) -> int {
+        int r;
+        if (again && (r = encode(b0, b, s))) return r;
+        if ((r = run_decoder(c, WS(c, "enc_s"), nullptr, b, WS(c, "dec"), s, c->bank.enc, ix + b0, c->bank.N,
+                             c->bank.dec_valid ? c->bank.kin.p : nullptr, c->bank.dec_valid ? c->bank.gb.p : nullptr))) return r;
+        return run_to_mot(c, WS(c, "dec"), b, Y + b0 * ys, s, raw);
+    });
+}
+
+int mocha_characterize_pair_path(mocha_ctx* c, const float* src_X, int B_src, const float* cha_X, int B_cha, const float* cnt_mean,
+                                 const float* cnt_std, const int32_t* seq_start, int n_seq, const int32_t* bank_start, int n_b, double lambda,
+                                 int relative, float* Y, int32_t* idx, unsigned char* continued, float* cha_encoded, float* cha_cnt_nm, int raw,
+                                 void* stream) {
+    PathArgs a; a.seq_start = seq_start; a.n_seq = n_seq; a.bank_start = bank_start; a.n_b = n_b; a.lambda = lambda; a.continued = continued;
+    a.relative = relative != 0;
+    return characterize_pair_impl(c, src_X, B_src, cha_X, B_cha, cnt_mean, cnt_std, Y, idx, cha_encoded, cha_cnt_nm, stream, raw != 0, &a);
 }
 
 // ------------------------------------------------------------------------------------------- captured per-window step

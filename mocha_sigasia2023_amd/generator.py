@@ -20,6 +20,7 @@ from .skeleton import LAYOUT_ID, skeleton_constants
 from .weights import DEFAULT_CFG, buffer_arrays, param_shapes
 
 NTOK, DIM = 90, 256
+MAX_PATH_ROWS = 16384          # bank rows a path call serves (MOCHA_PATH_MAX_ROWS)
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -96,6 +97,73 @@ class _Context:
                 self.h = None
         except Exception:
             pass
+
+
+class CoherentMatch:
+    """``coherent=`` of the batch routes: coherent context matching (include/mocha_hip.h, "coherent context matching") in place of one
+    nearest entry per window.  ``jump``: the penalty for every transition that is not "next row of the same clip", finite and >= 0, in
+    the units of the matcher's distances - or, with ``relative``, in units of the median over the windows of their nearest distance
+    (distance scales differ per bank; this is the dial to set without knowing them).  ``bank_starts``: the bank rows that begin a clip
+    (``bank.bank_starts``; None: the bank is one clip).  ``src_starts``: the source windows that begin a sequence (None: one sequence).
+    A plain number means ``CoherentMatch(number)``; 0 is the hard match."""
+
+    def __init__(self, jump: float, relative: bool = False, bank_starts=None, src_starts=None):
+        self.jump, self.relative, self.bank_starts, self.src_starts = float(jump), bool(relative), bank_starts, src_starts
+        if not (np.isfinite(self.jump) and self.jump >= 0.0):
+            raise ValueError("CoherentMatch: jump must be finite and >= 0")
+
+    @classmethod
+    def of(cls, coherent) -> "CoherentMatch":
+        if isinstance(coherent, cls):
+            return coherent
+        if isinstance(coherent, (bool, np.bool_)) or not isinstance(coherent, (int, float, np.integer, np.floating)):
+            raise ValueError("coherent must be None, a number (the jump penalty) or a CoherentMatch")
+        return cls(float(coherent))
+
+
+def _i32_starts(values, n: int, name: str, leading_zero: bool):
+    """Host list of starts -> (ctypes int32 array, count): sorted, unique, inside [0, n).  ``leading_zero``: sequence starts, which begin
+    at 0 and get the end ``n`` appended (a given end is accepted)."""
+    a = [] if values is None else [int(v) for v in (values.tolist() if hasattr(values, "tolist") else values)]
+    if leading_zero:
+        if not a:
+            a = [0]
+        if a[-1] == n:
+            a = a[:-1]
+        if not a or a[0] != 0:
+            raise ValueError(f"{name}: the first sequence starts at 0")
+    if any(y <= x for x, y in zip(a, a[1:])) or (a and (a[0] < 0 or a[-1] >= n)):
+        raise ValueError(f"{name}: starts must increase strictly and lie in 0 .. {n - 1}")
+    if leading_zero:
+        a.append(n)
+    arr = (C.c_int32 * max(len(a), 1))(*a)
+    return arr, len(a)
+
+
+def _path_rows(n: int):
+    if n > MAX_PATH_ROWS:
+        raise ValueError(f"coherent matching serves banks of up to {MAX_PATH_ROWS} rows per call, got {n}")
+
+
+def _relative_jump(d: torch.Tensor, jump: float) -> float:
+    """jump x the median over the windows of their nearest distance."""
+    return float(jump) * float(d.min(dim=1).values.median())
+
+
+def _match_path(ctx: "_Context", d: torch.Tensor, jump: float, starts, bank_starts):
+    """``mocha_match_path`` on a device matrix (Q, N) -> (dist (Q,), path (Q,) int32, continued (Q,) uint8)."""
+    Q, N = d.shape
+    path = torch.empty((Q,), dtype=torch.int32, device=d.device)
+    dist = torch.empty((Q,), dtype=torch.float32, device=d.device)
+    cont = torch.empty((Q,), dtype=torch.uint8, device=d.device)
+    if Q == 0:
+        return dist, path, cont
+    _path_rows(N)
+    seq, n_seq = _i32_starts(starts, Q, "starts", True)
+    bst, n_b = _i32_starts(bank_starts, N, "bank_starts", False)
+    ctx.call("mocha_match_path", _ptr(d), Q, N, C.c_int64(d.stride(0)), seq, n_seq - 1, bst if n_b else None, n_b, C.c_double(jump), _ptr(path),
+             _ptr(dist), _ptr(cont), _stream())
+    return dist, path, cont
 
 
 _util_ctx = {}
@@ -336,7 +404,7 @@ class Generator:
         return X
 
     def characterize_pair(self, src_X, cha_X, cnt_mean, cnt_std, return_index: bool = False, return_bank: bool = False,
-                          raw: bool = False):
+                          raw: bool = False, coherent=None):
         """The demo pair in one pass: the character clip becomes the bank and the source clip is characterized against
         it — ``encode(cha)`` + ``ContextBank`` + ``characterize(src)`` with both clips sharing every launch of
         mot_embedding / encoder / cnt (test_fullframework.py:188-194, 271-277, 293-296, 438-443, 465-467).  The bank is
@@ -344,7 +412,10 @@ class Generator:
         Result order: Y[, idx][, cha_encoded, cha_cnt_nm].
         ``cnt_mean`` / ``cnt_std`` may be NumPy arrays (as ``np.load('cnt_norm.npz')`` gives them), but then every call copies them to
         the device - a pageable host copy waits for the stream to drain (measured: 138 µs of idle GPU per call at 585 + 585 windows);
-        in a loop pass device tensors, converted once."""
+        in a loop pass device tensors, converted once.
+        ``coherent`` (a jump penalty or a ``CoherentMatch``): the source windows take a jump-penalised path through the character clip's
+        windows instead of one nearest window each (``mocha_characterize_pair_path``); with ``relative`` the penalty's unit is taken inside the call from its
+        own distance matrix.  None: the hard match, the code as it was."""
         self._need()
         conv = (lambda X, n: self._xraw(X, n)) if raw else (lambda X, n: self._x(X, n))
         s, c = conv(src_X, "src_X"), conv(cha_X, "cha_X")
@@ -357,8 +428,18 @@ class Generator:
         if return_bank:
             enc = torch.empty((Bc, NTOK, DIM), dtype=torch.float32, device=self.device)
             nm = torch.empty_like(enc)
-        self._ctx.call("mocha_characterize_pair_raw" if raw else "mocha_characterize_pair", _ptr(s), Bs, _ptr(c), Bc, _ptr(mean), _ptr(std),
-                       _ptr(Y), _ptr(idx), _ptr(enc) if return_bank else None, _ptr(nm) if return_bank else None, _stream())
+        if coherent is not None and Bs > 0:
+            co = CoherentMatch.of(coherent)
+            _path_rows(Bc)
+            seq, n_seq = _i32_starts(co.src_starts, Bs, "src_starts", True)
+            bst, n_b = _i32_starts(co.bank_starts, Bc, "bank_starts", False)
+            self._ctx.call("mocha_characterize_pair_path", _ptr(s), Bs, _ptr(c), Bc, _ptr(mean), _ptr(std), seq, n_seq - 1,
+                           bst if n_b else None, n_b, C.c_double(co.jump), 1 if co.relative else 0, _ptr(Y), _ptr(idx), None,
+                           _ptr(enc) if return_bank else None,
+                           _ptr(nm) if return_bank else None, 1 if raw else 0, _stream())
+        else:
+            self._ctx.call("mocha_characterize_pair_raw" if raw else "mocha_characterize_pair", _ptr(s), Bs, _ptr(c), Bc, _ptr(mean), _ptr(std),
+                           _ptr(Y), _ptr(idx), _ptr(enc) if return_bank else None, _ptr(nm) if return_bank else None, _stream())
         out = (Y,) + ((idx,) if return_index else ()) + ((enc, nm) if return_bank else ())
         return out[0] if len(out) == 1 else out
 
@@ -383,6 +464,14 @@ class Generator:
         nm = torch.empty_like(enc)
         self._ctx.call(fn, _ptr(X), B, _ptr(enc), _ptr(cnt), _ptr(m), _ptr(sd), _ptr(nm), _stream())
         return enc, cnt, nm
+
+
+def _dist_matrix(model: "Generator", query_nm, row0: int, rows: int) -> torch.Tensor:
+    """``mocha_match_dist_matrix`` against rows [row0, row0 + rows) of the model's current bank -> (Q, rows) fp32."""
+    q = _dev_f32(query_nm, model.device, None, "query").reshape(-1, NTOK * DIM)
+    d = torch.empty((q.shape[0], rows), dtype=torch.float32, device=q.device)
+    model._ctx.call("mocha_match_dist_matrix", _ptr(q), q.shape[0], C.c_int64(row0), C.c_int64(rows), _ptr(d), C.c_int64(rows), _stream())
+    return d
 
 
 class ContextBank:
@@ -464,6 +553,22 @@ class ContextBank:
             return dist[:, None], idx[:, None]
         return idx[:, None]
 
+    def distances(self, query_nm, rows=None):
+        """(Q, N) fp32: the Euclidean distance of every query to every row of the bank's fp32 rows - each entry the number ``query(k > 1)``
+        reports for that pair, bit for bit (``mocha_match_dist_matrix``).  ``rows=(start, stop)``: those rows only."""
+        if getattr(self.model, "_bank", None) is not self:
+            self.activate()
+        return _dist_matrix(self.model, query_nm, 0 if rows is None else int(rows[0]), self.N if rows is None else int(rows[1]) - int(rows[0]))
+
+    def query_path(self, query_nm, jump: float, starts=None, bank_starts=None, relative: bool = False):
+        """Coherent context matching (``CoherentMatch``): the jump-penalised path of the queries - consecutive windows, sequences starting at
+        ``starts`` - through the bank -> (dist (Q,), idx (Q,) int32, continued (Q,) uint8).  ``jump`` = 0 is ``query(k=1)`` with ties to the
+        lowest row.  Sequential in the sequence's length, one workgroup per sequence; banks of up to 16 384 rows.  Not a time warp: the
+        only free transition is "next row of the same clip"."""
+        d = self.distances(query_nm)
+        co = CoherentMatch(jump, relative)
+        return _match_path(self.model._ctx, d, _relative_jump(d, co.jump) if relative and d.shape[0] else co.jump, starts, bank_starts)
+
     def gather_blend(self, idx, dist, temperature: float = 1.0):
         """Soft context matching over the k neighbours of ``query(q, k)``: softmax(-dist / temperature)-weighted sum of their
         ``encoded`` entries, (Q,90,256).  An extension (SURVEY.md §8f N4 "optional"): the reference gathers the single nearest."""
@@ -484,11 +589,14 @@ class ContextBank:
         self.model._ctx.call("mocha_bank_gather", _ptr(idx), idx.shape[0], _ptr(out), _stream())
         return out
 
-    def characterize(self, src_X, cnt_mean, cnt_std, return_index: bool = False, raw: bool = False):
+    def characterize(self, src_X, cnt_mean, cnt_std, return_index: bool = False, raw: bool = False, coherent=None):
         """NN ('cm_') branch of the demo for all source windows at once: encode, z-score,
         1-NN match, gather, decode, to_mot (test_fullframework.py:188-194,438-443,465-467).
         raw=True (after Generator.set_pose_norm): src_X is un-normalised with the root bone,
-        (B,T,V+1,C); the result is de-normalised (B,T,V,C)."""
+        (B,T,V+1,C); the result is de-normalised (B,T,V,C).
+        ``coherent`` (a jump penalty or a ``CoherentMatch``): the windows are consecutive windows of a clip and take the jump-penalised
+        path through the bank instead of one nearest entry each (``mocha_characterize_path``; ``relative``: the unit comes from the
+        call's own distance matrix).  None: the hard match, the code as it was."""
         if getattr(self.model, "_bank", None) is not self:
             self.activate()
         m = self.model
@@ -497,6 +605,14 @@ class ContextBank:
         std = _dev_f32(cnt_std, m.device, (NTOK, DIM), "cnt_std")
         Y = torch.empty((X.shape[0], m.cfg["nframes"], m.V, m.cfg["mot_in_dim"]), dtype=torch.float32, device=m.device)
         idx = torch.empty((X.shape[0],), dtype=torch.int32, device=m.device)
+        if coherent is not None and X.shape[0] > 0:
+            co = CoherentMatch.of(coherent)
+            _path_rows(self.N)
+            seq, n_seq = _i32_starts(co.src_starts, X.shape[0], "src_starts", True)
+            bst, n_b = _i32_starts(co.bank_starts, self.N, "bank_starts", False)
+            m._ctx.call("mocha_characterize_path", _ptr(X), X.shape[0], _ptr(mean), _ptr(std), seq, n_seq - 1, bst if n_b else None, n_b,
+                        C.c_double(co.jump), 1 if co.relative else 0, _ptr(Y), _ptr(idx), None, 1 if raw else 0, _stream())
+            return (Y, idx) if return_index else Y
         m._ctx.call("mocha_characterize_raw" if raw else "mocha_characterize", _ptr(X), X.shape[0], _ptr(mean), _ptr(std),
                     _ptr(Y), _ptr(idx), _stream())
         return (Y, idx) if return_index else Y

@@ -24,7 +24,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .generator import DIM, NTOK, Generator, _dev_f32, _ptr, _stream
+from .generator import DIM, NTOK, CoherentMatch, Generator, _dev_f32, _dist_matrix, _match_path, _ptr, _relative_jump, _stream
 
 _BORROW, _BF16, _NO_DEC_CACHE = 1, 2, 4          # mocha_bank_set flags (include/mocha_hip.h)
 SOFT_MAX_K = 8                                   # MOCHA_SOFT_MAX_K
@@ -228,6 +228,23 @@ class _SegmentedBank:
         dist = torch.empty((Q,), dtype=torch.float32, device=q.device)
         self.model._ctx.call("mocha_match_segmented", _ptr(q), Q, _ptr(ids), _ptr(idx), _ptr(dist), _stream())
         return dist[:, None], idx[:, None]
+
+    def distances(self, query_nm, character: int):
+        """(Q, rows of ``character``) fp32 distances (``ContextBank.distances``) against that character's rows alone."""
+        self._ensure()
+        r0, r1 = self.rows(int(character))
+        if r1 <= r0:
+            raise ValueError(f"character {character} holds no rows")
+        return _dist_matrix(self.model, query_nm, r0, r1 - r0)
+
+    def query_path(self, query_nm, character: int, jump: float, starts=None, bank_starts=None, relative: bool = False):
+        """``ContextBank.query_path`` over the rows of ONE character (a loaded character of a ``MultiCharacterBank``, an occupied slot of a
+        ``ResidentCharacterBank``; the rows come from the host's table) -> (dist (Q,), idx (Q,) int32 GLOBAL rows, continued (Q,) uint8).
+        ``bank_starts`` are local to the character's rows.  It does not combine with ``k``, ``allow`` or ``mix``."""
+        d = self.distances(query_nm, character)
+        lam = _relative_jump(d, CoherentMatch(jump).jump) if relative and d.shape[0] else CoherentMatch(jump).jump
+        dist, idx, cont = _match_path(self.model._ctx, d, lam, starts, bank_starts)
+        return dist, idx + self.rows(int(character))[0], cont
 
     def characterize(self, src_X, characters, cnt_mean, cnt_std, return_index: bool = False, raw: bool = False, soft=None, allow=None,
                      mix=None):

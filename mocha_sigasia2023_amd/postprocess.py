@@ -188,13 +188,14 @@ class Inertializer:
 
 
 def retarget_clip(bank, src_X, cnt_mean, cnt_std, src_rvel, src_rang, src_speed, contact, raw: bool = False,
-                  post: Optional[PostProcessor] = None, bvh: bool = True):
+                  post: Optional[PostProcessor] = None, bvh: bool = True, coherent=None):
     """The NN branch of the demo from featurised source windows to the animated skeleton, all on the device:
     characterize (encode, match, decode, to_mot; test_fullframework.py:438-443, 465-467) -> pose heads (:457-462) ->
     root integration / blending / foot-lock IK (:492-632) -> BVH channels (:677-681, 697).  ``src_X`` must lead to
     de-normalised windows: pass ``raw=True`` after ``Generator.set_pose_norm`` or de-normalise the result yourself.
-    src_speed (N,) is mean_t |src_Yvel[i, t, 1]| (:493)."""
-    Y = bank.characterize(src_X, cnt_mean, cnt_std, raw=raw)
+    src_speed (N,) is mean_t |src_Yvel[i, t, 1]| (:493).  ``coherent``: ``ContextBank.characterize``'s (None: the hard match)."""
+    Y = bank.characterize(src_X, cnt_mean, cnt_std, raw=raw) if coherent is None else \
+        bank.characterize(src_X, cnt_mean, cnt_std, raw=raw, coherent=coherent)
     heads, speed = pose_heads(bank.model, Y)
     return (post or PostProcessor(bank.model)).run(heads, speed, src_rvel, src_rang, src_speed, contact, bvh=bvh)
 
