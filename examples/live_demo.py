@@ -3,7 +3,7 @@
 mocap frame at a time through ``LiveSession`` - ring push + featurize, segmented characterize, pose heads and one post-processing
 frame per push, one captured graph - and written as two BVH files.
 
-    python examples/live_demo.py [--frames 180] [--out bench_outputs/live_demo] [--ours [--seed 7]] [--switch 120 [--inertial 0.1]] [--raw L [--source-fps R]]
+    python examples/live_demo.py [--frames 180] [--out bench_outputs/live_demo] [--ours [--seed 7]] [--switch 120 [--inertial 0.1]] [--raw L [--source-fps R]] [--coherent L]
                                  [--actions A,B[:F]] [--load-at F] [--ours-per-character] [--mix a:b:FRAMES | --mix-parts a:b:MASK]
 
 ``--ours`` runs the CVAE ("Ours") branch inside the same graph (``LiveOursSession``): each stream's character feature is seeded with
@@ -44,6 +44,11 @@ space; nothing is captured again.  ``--mix-parts a:b:MASK``: a splice by body pa
 order of ``PART_NAMES`` (Spine, LeftLeg, LeftArm, Neck, RightArm, RightLeg for this layout): 1 takes the part from a, 0 from b.  Neither
 combines with ``--soft``, ``--inertial``, ``--actions``, ``--switch`` or ``--ours``.
 
+``--coherent L``: coherent matching (``LiveSession(coherent=L)``): a stream keeps to the run of consecutive bank rows it is on unless
+leaving it is cheaper by more than L, in the matcher's distance units (the bank here is stride-1 windows of one clip per character).  The
+number of continued frames and of transitions that are not "next row" is printed.  Combines with ``--raw``, ``--switch``, ``--load-at``
+and ``--world``.
+
 Weights, norms and motions are synthetic (see demo_pair.py for what to replace with real assets).
 """
 import argparse
@@ -78,6 +83,8 @@ ap.add_argument("--load-at", type=int, default=None, metavar="FRAME", help="star
 ap.add_argument("--ours-per-character", action="store_true", help="--ours with one CVAE per character from a CVAEBank (synthetic CVAEs)")
 ap.add_argument("--mix", default=None, metavar="a:b:FRAMES", help="cross-fade both streams from character a to b over FRAMES frames")
 ap.add_argument("--mix-parts", default=None, metavar="a:b:MASK", help="splice: body parts with 1 in the six-character MASK from a, the others from b")
+ap.add_argument("--coherent", type=float, default=None, metavar="L", help="coherent matching: every transition that is not 'next row of the same clip' "
+                "costs L (in the matcher's distance units); LiveSession(coherent=L)")
 ap.add_argument("--world", action="store_true", help="also produce world-space poses and the skinning palette (LiveSession(world=SkinBind))")
 a = ap.parse_args()
 a.ours = a.ours or a.ours_per_character
@@ -98,6 +105,8 @@ if a.mix or a.mix_parts:
         if len(last) != 6 or set(last) - {"0", "1"}:
             raise SystemExit("--mix-parts a:b:MASK: MASK is six 0/1 characters, one per body part")
         mix_mask = np.array([float(ch) for ch in last], np.float32)
+if a.coherent is not None and (a.ours or a.soft or a.inertial is not None or a.actions or a.mix or a.mix_parts):
+    raise SystemExit("--coherent does not combine with --ours, --soft, --inertial, --actions or --mix: it takes the hard matcher's place, alone")
 if a.ours and a.actions:
     raise SystemExit("--actions does not apply to --ours: the branch's seed match searches the whole character")
 allow_from, allow_mask = 0, None
@@ -181,7 +190,7 @@ elif a.ours:                                                          # test_ful
 else:
     raw_cfg = a.raw if a.source_fps is None else IngestConfig(lookahead=a.raw, order=None)      # the resampler hands over quaternions
     sess = LiveSession(bank, cnt_mean, cnt_std, streams=S, post=PostProcessor(model), soft=soft, inertial=a.inertial, raw=raw_cfg,
-                       constrained=bool(a.actions), mix=2 if mix_ids else None, world=world)
+                       constrained=bool(a.actions), mix=2 if mix_ids else None, world=world, coherent=a.coherent)
 if mix_ids:
     sess.set_mix((mix_ids, np.stack([mix_mask, 1 - mix_mask]) if mix_mask is not None else [1.0, 0.0]))
 if a.raw is not None:
@@ -236,7 +245,7 @@ if a.source_fps is not None:
     resampler.reset()
     at_60 = resampled_frames()
 torch.cuda.synchronize(); t0 = time.perf_counter()
-pos, eul, applied, seeded, head = [], [], [], [], []
+pos, eul, applied, seeded, head, rows_, cont_ = [], [], [], [], [], [], []
 if a.actions:
     sess.allow.zero_()
 gen0 = model._ctx.generation()
@@ -255,6 +264,8 @@ for f in range(F):
         pos.append(o["bvh_pos"].clone()); eul.append(o["bvh_euler"].clone())
         if a.actions:
             applied.append(o["applied"].clone())
+        if a.coherent is not None:
+            rows_.append(o["idx"].clone()); cont_.append(o["continued"].clone())
         if a.world:                                                   # the last bone's world position, kept on the device: no synchronisation here
             head.append(o["gpos"][:, -1].clone())
 torch.cuda.synchronize(); dt = time.perf_counter() - t0
@@ -270,6 +281,12 @@ if a.world:
           f"grot {tuple(sess.out['grot'].shape)}: one mocha_world_pose launch behind every captured step; bone {J - 1} of stream 0 in world space:")
     for f, g in enumerate(torch.stack(head, 1)[0].cpu().tolist()):
         print(f"    frame {first + f}: {g[0]:9.4f} {g[1]:9.4f} {g[2]:9.4f}")
+if a.coherent is not None:
+    rw, ct = torch.stack(rows_, 1).cpu(), torch.stack(cont_, 1).cpu()
+    for s in range(S):
+        jumps = int((rw[s, 1:] != rw[s, :-1] + 1).sum())
+        print(f"  coherent matching, jump penalty {a.coherent}: stream {s} continued on {int(ct[s].sum())} of {rw.shape[1]} posed frames, "
+              f"{jumps} transitions that are not 'next row'; generation {gen0} -> {model._ctx.generation()}")
 if a.ours_per_character:
     sd = torch.stack(seeded, 1).cpu()
     print(f"  one CVAE per character: seed frames per stream {sd.sum(1).tolist()} of {F - first} posed frames; generation {gen0} -> {model._ctx.generation()}")

@@ -443,8 +443,8 @@ int mocha_characterize_pair_raw(mocha_ctx* ctx, const float* src_X_raw, int B_sr
  * Refusals, nothing launched: MOCHA_ERR_ARG for a NULL context or required pointer, Q < 0 (Q = 0 returns 0), rows < 1 or a range outside
  * the bank, ld < rows, lambda negative, NaN or infinite, starts that are unsorted or out of range, seq_start[0] != 0 or a last entry
  * != Q, more than 16 384 rows; MOCHA_ERR_STATE without a bank, and for mocha_characterize_path on a resident bank.
- * What it is not: no "stay" or "skip" transitions (time warping), one constant penalty, no online or live form (that needs every row's
- * distance inside the captured step). */
+ * What it is not: no "stay" or "skip" transitions (time warping), one constant penalty.  These calls have no online form; the live one is
+ * "coherent matching in live sessions" below. */
 #define MOCHA_PATH_MAX_ROWS 16384
 int mocha_match_dist_matrix(mocha_ctx* ctx, const float* query_nm, int Q, int64_t row0, int64_t rows, float* dist, int64_t ld, void* stream);
 int mocha_match_path(mocha_ctx* ctx, const float* dist, int Q, int N, int64_t ld, const int32_t* seq_start, int n_seq,
@@ -457,6 +457,71 @@ int mocha_characterize_pair_path(mocha_ctx* ctx, const float* src_X, int B_src, 
                                  const float* cnt_std, const int32_t* seq_start, int n_seq, const int32_t* bank_start, int n_b,
                                  double lambda, int relative, float* Y, int32_t* idx, unsigned char* continued, float* cha_encoded,
                                  float* cha_cnt_nm, int raw, void* stream);
+
+/* Coherent matching in live sessions: one step of the path per pushed frame, state on the device.  The forward recursion above is an
+ * online algorithm with bounded state: R is re-based every step and path[last] = m[last], so the row the forward pass holds after window t
+ * is, to the bit, the last row of mocha_match_path over windows 0..t.  A step needs the previous R (one float64 per row of the stream's
+ * character), M and m.  The emitted row is this FILTERED row m[t] (no lookahead); it may differ from the whole-clip path's row t.
+ * State, per stream, in caller-owned device memory (private layout, mocha_path_state_bytes): `running`, the previous character id, the
+ * previous extent (first row, rows) and the slot epoch; the previously emitted row m_prev and M; two buffers of state_rows float64
+ * switched by a parity word (64 bytes + 16 bytes per row per stream; 8-byte aligned).  A zeroed buffer is a reset state.
+ * d[j]: the fp32 distance between the stream's z-scored query and row j of its character, bit for bit the entry mocha_match_dist_matrix
+ * gives for that row; the fp32 rows are read whatever the bank's flags, as the matrix does.  lambda: finite, >= 0, in the units of d, by
+ * value (part of a captured step's key).  One step of stream s with effective id e:
+ *   e invalid (warming, no frame, id < 0 or outside the table, empty or retired slot): idx = -1, dist = +inf, continued = 0, running = 0;
+ *            the decoder reads global row 0 (as mocha_match_segmented); the stream's R is not touched.
+ *   restart  if !running, e != the previous id, the extent or the epoch changed, or restart[s] != 0:  R[j] = d[j].  restart: optional
+ *            DEVICE int32 per stream, one-shot - the step clears the words it consumed (a stream that sits out consumes nothing).
+ *   otherwise a = R_prev[j-1] - M_prev if row j has a predecessor, else +inf;  cont = (a < lambda), strict: a tie jumps;
+ *            R[j] = d[j] + (cont ? a : lambda).
+ *   M = min_j R[j], m its lowest column.  idx = m (local row); dist = d[m]; continued = 1 iff not a restart, m == m_prev + 1 and row m has
+ *   a predecessor.
+ * float64 on the fp32 d: one subtraction, one exact minimum, one addition - the device returns the sequential evaluation's row.
+ * lambda = 0: the lowest-index arg-min of d, the hard match on an fp32 bank.
+ * Row j has a predecessor iff j > 0 and j is not a bank start; row 0 of every character never has one.
+ * Bank starts: one bit per global bank row and one epoch word per segment / slot, device data that exists, zeroed, from
+ * mocha_bank_set_segments / mocha_bank_resident_create on (its pointer fixed for the bank's life).
+ *   mocha_bank_set_starts          : starts (HOST, global rows, strictly increasing) of a segmented bank replace the table's bits.
+ *   mocha_bank_resident_set_starts : starts (HOST, local rows of `slot`, strictly increasing) replace the bits of that character.
+ *   Both only enqueue on `stream`, move no generation and re-capture nothing.  mocha_bank_resident_add / _retire clear the slot's bits
+ *   and bump its epoch on the caller's stream, so a stream on a replaced character restarts even at the same extent.
+ *   Refusals: MOCHA_ERR_ARG for unsorted starts or starts out of range; MOCHA_ERR_STATE without such a bank or for an empty slot.
+ *   mocha_path_state_bytes   : bytes of a state for `streams` (1..16) streams of up to state_rows (1..MOCHA_PATH_MAX_ROWS) rows; < 0: refused.
+ *   mocha_path_state_reset   : the streams named in `which` (HOST array of n stream ids; NULL: all) stop running: their next valid step
+ *                              restarts.  Only enqueues memsets: graph-safe, like mocha_live_reset.
+ *   mocha_match_path_advance : the pure form, needs no bank: one step on DEVICE rows dist (streams, ld) of distances.  ids (streams): < 0
+ *                              sits out, a change restarts; rows (streams): the row count of each stream (outside 1..min(state_rows, ld):
+ *                              sits out); start_bits (or NULL) a DEVICE table of n_bits bits, row j of stream s starts a clip iff bit
+ *                              bit_off[s] + j (bit_off NULL: j) is set, bits outside the table read 0; restart as above (or NULL).
+ *                              Outputs (DEVICE, per stream): idx int32; dist_out fp32 or NULL; continued uint8 or NULL.
+ *   mocha_match_path_segmented : one step for z-scored queries (streams, 90*256) with ids seg (streams) against the current segmented or
+ *                              resident bank: the plan, the all-keys scan of the fp32 rows (the soft matcher's, through its key buffer)
+ *                              and the step kernel.  Capture-safe: no allocation, no host copy, no synchronisation.  dist_row (streams,
+ *                              ld >= state_rows) or NULL: every d[j] of the step, for tests and tools.
+ *   mocha_characterize_segmented_path : mocha_characterize_segmented with that matcher; B = the state's streams, 1..16 (window s is stream
+ *                              s).  The decoder reads the matched row through the bank's per-entry constants, as the hard call does.
+ *   mocha_live_step_path, mocha_live_step_raw_path : mocha_live_step / mocha_live_step_raw (hard matcher, no inertializer) with that
+ *                              matcher, captured into graphs of their own, plus dist (streams) fp32 and continued (streams) uint8.
+ *                              mocha_live_reset of a stream makes it warm up, so it sits out and then restarts.
+ * Refusals, nothing launched: MOCHA_ERR_ARG for a NULL context or required pointer, streams outside 1..16, lambda negative, NaN or
+ * infinite, state_rows < 1 or > MOCHA_PATH_MAX_ROWS, ld too small; MOCHA_ERR_STATE when the bank's largest character (for a resident bank
+ * its reserved maximum) exceeds state_rows, without a bank or without a segment table.
+ * What it is not: no fixed-lag smoothing (the emitted row is the filtered one); no "stay" or "skip" transitions; one penalty per call; not
+ * combined with the soft, action-constrained, mix, inertialized or Ours steps; no streamed form; fp32 rows are read also on bf16 banks. */
+int mocha_bank_set_starts(mocha_ctx* ctx, const int64_t* starts, int n, void* stream);
+int mocha_bank_resident_set_starts(mocha_ctx* ctx, int slot, const int32_t* starts, int n, void* stream);
+int64_t mocha_path_state_bytes(const mocha_ctx* ctx, int streams, int state_rows);
+int mocha_path_state_reset(mocha_ctx* ctx, void* state, int streams, int state_rows, const int32_t* which, int n, void* stream);
+int mocha_match_path_advance(mocha_ctx* ctx, void* state, int streams, int state_rows, const float* dist, int64_t ld, const int32_t* ids,
+                             const int32_t* rows, const uint32_t* start_bits, int64_t n_bits, const int32_t* bit_off, int32_t* restart,
+                             double lambda, int32_t* idx, float* dist_out, unsigned char* continued, void* stream);
+int mocha_match_path_segmented(mocha_ctx* ctx, void* state, int streams, int state_rows, const float* query_nm, const int32_t* seg,
+                               int32_t* restart, double lambda, int32_t* idx, float* dist, unsigned char* continued, float* dist_row, int64_t ld,
+                               void* stream);
+int mocha_characterize_segmented_path(mocha_ctx* ctx, const float* src_X, int B, const int32_t* seg, const float* cnt_mean, const float* cnt_std,
+                                      void* path_state, int state_rows, double lambda, int32_t* restart, float* Y, int32_t* idx, float* dist,
+                                      unsigned char* continued, int raw, void* stream);
+/* (mocha_live_step_path and mocha_live_step_raw_path are declared with the live steps, below) */
 
 /* CVAE character-feature sampler: CVAE.sample(c) of model_CVAE.py:44-46, i.e.
  * PriorNet (:49-92) then Decoder (:138-165).  Weights by their reference state_dict names
@@ -812,6 +877,20 @@ int mocha_live_step_raw_allow(mocha_ctx* ctx, const mocha_post_cfg* cfg, const m
                               float temperature, double* pos_out, double* rot_out, double* ik_rot, double* bvh_pos, double* bvh_euler,
                               int32_t* idx, int32_t* valid, int32_t* idx_k, float* w_k, void* stream, void* inert,
                               const mocha_inert_cfg* icfg, const uint64_t* allow, int32_t* applied);
+
+/* The live step with the online path in the hard matcher's place ("coherent matching in live sessions", above): mocha_live_step's /
+ * mocha_live_step_raw's arguments (hard matcher, no inertializer), then path_state (mocha_path_state_bytes(ctx, streams, state_rows)),
+ * state_rows, lambda, restart (DEVICE, streams int32, or NULL) and the outputs dist (streams) fp32 and continued (streams) uint8. */
+int mocha_live_step_path(mocha_ctx* ctx, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos,
+                         const float* Yvel, const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed,
+                         const unsigned char* contact, const int32_t* seg, const float* cnt_mean, const float* cnt_std, double* pos,
+                         double* rot, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx, int32_t* valid, void* stream,
+                         void* path_state, int state_rows, double lambda, int32_t* restart, float* dist, unsigned char* continued);
+int mocha_live_step_raw_path(mocha_ctx* ctx, const mocha_post_cfg* cfg, const mocha_ingest_cfg* icfg_in, void* live, void* ingest, int streams,
+                             const float* rot, const float* pos, const int32_t* seg, const float* cnt_mean, const float* cnt_std,
+                             double* pos_out, double* rot_out, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx,
+                             int32_t* valid, void* stream, void* path_state, int state_rows, double lambda, int32_t* restart, float* dist,
+                             unsigned char* continued);
 
 /* Character mixing on a multi-character bank: a window characterized by up to MOCHA_MIX_MAX (character, six body-part weights) components
  * instead of exactly one character - a strength dial ("70 % zombie, 30 % neutral"), a cross-fade (a weight ramp from a to b over n frames, in

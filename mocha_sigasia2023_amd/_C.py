@@ -100,6 +100,15 @@ SIGNATURES = {
                                      _i, _vp]),
     "mocha_characterize_pair_path": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), _i, C.c_double, _i,
                                           _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "mocha_bank_set_starts": (_i, [_vp, C.POINTER(_i64), _i, _vp]),
+    "mocha_bank_resident_set_starts": (_i, [_vp, _i, C.POINTER(C.c_int32), _i, _vp]),
+    "mocha_path_state_bytes": (_i64, [_vp, _i, _i]),
+    "mocha_path_state_reset": (_i, [_vp, _vp, _i, _i, C.POINTER(C.c_int32), _i, _vp]),
+    "mocha_match_path_advance": (_i, [_vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp]),
+    "mocha_match_path_segmented": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "mocha_characterize_segmented_path": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, C.c_double, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "mocha_live_step_path": (_i, [_vp, _vp, _vp, _i] + [_vp] * 19 + [_vp, _i, C.c_double, _vp, _vp, _vp]),
+    "mocha_live_step_raw_path": (_i, [_vp, _vp, _vp, _vp, _vp, _i] + [_vp] * 13 + [_vp, _i, C.c_double, _vp, _vp, _vp]),
     "mocha_cvae_load_weight": (_i, [_vp, C.c_char_p, _vp, C.POINTER(_i64), _i]),
     "mocha_cvae_finalize": (_i, [_vp]),
     "mocha_cvae_sample": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),

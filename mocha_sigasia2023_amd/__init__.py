@@ -4,7 +4,7 @@ own call surface.  The arithmetic lives in ``libmocha_hip.so`` (``csrc/``, C ABI
 ``include/mocha_hip.h``); this package is the thin host-side mirror of the reference interface.
 """
 from .generator import CVAE, CVAEBank, CoherentMatch, ContextBank, Generator, OursSession, StreamingCharacterizer, mean_variance_norm  # noqa: F401
-from .multi_character import MultiCharacterBank, MultiStreamCharacterizer, ResidentCharacterBank, action_mask  # noqa: F401
+from .multi_character import MultiCharacterBank, MultiStreamCharacterizer, OnlinePath, ResidentCharacterBank, action_mask  # noqa: F401
 from .bank import BatchPipeline, ShardedContextBank, bank_starts, build_bank, build_database_from_bvh, load_bank, save_bank  # noqa: F401
 from .postprocess import Inertializer, PostProcessor, pose_heads, retarget_clip, retarget_clip_ours, retarget_frame_ours, write_bvh  # noqa: F401
 from .postprocess import BvhValueRefused, format_bvh_motion, write_bvh_clips  # noqa: F401
@@ -21,4 +21,4 @@ __all__ = ["Generator", "CVAE", "CVAEBank", "OursSession", "ContextBank", "Strea
            "PostProcessor", "pose_heads", "MultiCharacterBank", "MultiStreamCharacterizer", "ResidentCharacterBank", "action_mask", "retarget_clip", "retarget_clip_ours", "retarget_frame_ours", "write_bvh", "write_bvh_clips", "format_bvh_motion", "BvhValueRefused",
            "LiveSession", "LiveOursSession", "Inertializer", "Ingestor", "IngestConfig", "ingest_clips", "clip_windows",
            "resample_clips", "resample_lengths", "StreamResampler", "SkinBind", "world_pose",
-           "CoherentMatch", "bank_starts", "PART_NAMES", "read_bvh_header", "load_bvh", "BvhHeader", "BvhClips", "build_database_from_bvh"]
+           "CoherentMatch", "OnlinePath", "bank_starts", "PART_NAMES", "read_bvh_header", "load_bvh", "BvhHeader", "BvhClips", "build_database_from_bvh"]

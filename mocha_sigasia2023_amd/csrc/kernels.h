@@ -557,6 +557,40 @@ size_t match_path_cont_words(int Q);
 hipError_t launch_match_path(const float* d, int Q, int N, int64_t ld, const int32_t* seq_start_dev, int n_seq, const int32_t* bank_start_dev,
                              int n_b, double lambda, unsigned* start_bits, int32_t* m, unsigned short* cont, int32_t* path, float* dist_out,
                              unsigned char* continued, hipStream_t s);
+// Coherent matching, the online form (match_path_step.hip): one step of the path's forward recursion per stream, the recursion's row in
+// the caller's state buffer.  State: `streams` headers of PATH_STEP_HDR_BYTES, then per stream two buffers of state_rows float64 switched
+// by the header's parity word; all zero = reset.  One launch of `streams` workgroups.
+//   ids (S): the streams' effective ids; negative sits out.  The extent of id e: rows != null (the pure form) {0, rows[s]}, epoch 0; else
+//   seg_table (S + 1 starts, or pairs != 0: a resident bank's slot table) with epochs[e] (or null: 0).  An id outside the table, an empty
+//   slot, or an extent of more than state_rows rows (or more than the loader's stride) sits out: idx -1, gidx 0, dist_out +inf, continued 0,
+//   running = 0, R untouched.
+//   start_bits (or null): bit bit0 + j set = row j starts a clip, bit0 = bit_off[s] (or 0) in the pure form and the extent's first row
+//   otherwise; a bit outside [0, n_bits) reads as not set.  restart (or null): S ints, a non-zero word restarts the stream and is cleared.
+//   Loader: keys != null - the all-keys scan's buffer, stream s at keys + s * kstride - else dist + s * ld.
+//   Outputs: idx (S) local rows; gidx, dist_out, continued, dist_row (S, ld_row >= state_rows: every d[j] of the step) may be null.
+static constexpr int PATH_STEP_MAX_STREAMS = 16;
+static constexpr int PATH_STEP_HDR_BYTES = 64;
+struct PathStepHdr {
+    int32_t running, prev_id, prev_first, prev_rows, prev_epoch, m_prev, parity, pad0;
+    double M, pad1[3];
+};
+struct PathStepArgs {
+    void* state; int streams; int state_rows;
+    const int32_t* ids;
+    const int32_t* rows;
+    const int* seg_table; int S; int pairs; const unsigned* epochs;
+    const unsigned* start_bits; long long n_bits; const int32_t* bit_off;
+    int32_t* restart;
+    double lambda;
+    const float* dist; long long ld;
+    const unsigned long long* keys; int kstride;
+    int32_t* idx; int32_t* gidx; float* dist_out; unsigned char* continued; float* dist_row; long long ld_row;
+};
+size_t path_step_state_bytes(int streams, int state_rows);
+hipError_t launch_match_path_step(const PathStepArgs& a, hipStream_t s);
+// the start bits of rows [first, first + rows) of a table of n_bits bits cleared, then bit first + start_dev[i] set for the n device starts
+// (each inside [0, rows)); epoch (or null): the word is incremented.  rows = 0 with an epoch: the increment alone.
+hipError_t launch_path_starts(unsigned* bits, int64_t n_bits, int64_t first, int64_t rows, const int32_t* start_dev, int n, unsigned* epoch, hipStream_t s);
 // out[q] = sum_j softmax_j(-dist[q][j] / temperature) * src[idx[q][j]] over the k neighbours of query q
 hipError_t launch_gather_blend(const float* src, const int32_t* idx, const float* dist, float temperature, float* out, int Q, int k,
                                int cols, int64_t nrows, hipStream_t s);
@@ -629,6 +663,11 @@ hipError_t launch_match_seg_topk(const void* bank, int bank_bf16, const float* q
                                  int32_t* idx0, int32_t* idx_k, float* dist_k, float* w_k, float* out, hipStream_t s,
                                  const SegAllow* al = nullptr,         // al: rows outside a constrained query's mask count as missing
                                  int slot_table = 0);
+// the plan and the all-keys scan alone, on fp32 rows, for one group of Q <= SEG_TOPK_Q queries: keys[q * match_seg_key_stride(max_rows) +
+// local row] for every row of query q's segment (an id outside the table: nothing written for it)
+int match_seg_key_stride(int64_t max_rows);
+hipError_t launch_match_seg_keys(const float* bank, const float* query, const int32_t* seg, int Q, const int* seg_start, int S, int64_t max_rows, int D,
+                                 unsigned long long* keys, int* plan, hipStream_t s, int slot_table = 0);
 // character mixing on a multi-character bank (match_seg_mix.hip): window q carries J <= SEG_MIX_MAX_J components (ids[q][j], six body-part
 // weights weights[q][j][v]); every PRESENT component - a loaded character and at least one weight in (0, FLT_MAX] - is matched exactly in
 // its own character as launch_match_segmented matches (that query, that id); the weights are normalised per part over the present

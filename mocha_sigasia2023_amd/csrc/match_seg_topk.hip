@@ -157,6 +157,21 @@ static inline int seg_key_stride(int64_t max_rows) { return (int)((max_rows + SE
 
 size_t match_seg_keys_words(int64_t max_rows) { return (size_t)SEG_TOPK_Q * (size_t)seg_key_stride(max_rows); }
 
+int match_seg_key_stride(int64_t max_rows) { return seg_key_stride(max_rows); }
+
+// steps 1 and 2 alone, on fp32 rows, for ONE group of up to SEG_TOPK_Q queries: the online path step reads the keys (match_path_step.hip)
+hipError_t launch_match_seg_keys(const float* bank, const float* query, const int32_t* seg, int Q, const int* seg_start, int S, int64_t max_rows, int D,
+                                 unsigned long long* keys, int* plan, hipStream_t s, int slot_table) {
+    if (Q < 1 || Q > SEG_TOPK_Q || S < 1 || max_rows < 1 || max_rows > 0x7fffffff - SEG_ROWS || D % MS_CHUNK_F32 != 0) return hipErrorInvalidValue;
+    const int kstride = seg_key_stride(max_rows);
+    hipError_t e = launch_seg_plan(seg, Q, S, plan, s);
+    if (e != hipSuccess) return e;
+    const dim3 grid((unsigned)(kstride / SEG_ROWS), (unsigned)seg_blocks_bound(Q, S));
+    if (slot_table) hipLaunchKernelGGL((mocha_match_seg_keys<false, true>), grid, dim3(256), 0, s, bank, query, plan, seg_start, D, keys, kstride);
+    else hipLaunchKernelGGL(mocha_match_seg_keys<false>, grid, dim3(256), 0, s, bank, query, plan, seg_start, D, keys, kstride);
+    return hipGetLastError();
+}
+
 hipError_t launch_match_seg_topk(const void* bank, int bank_bf16, const float* query, const int32_t* seg, int Q, const int* seg_start, int S,
                                  int64_t max_rows, int D, unsigned long long* keys, int* plan, const float* enc, int k, float temperature,
                                  int32_t* idx0, int32_t* idx_k, float* dist_k, float* w_k, float* out, hipStream_t s, const SegAllow* al,

@@ -179,6 +179,11 @@ struct Bank {
     struct Slot { int64_t first = 0, rows = 0; };      // rows = 0: empty
     std::vector<Slot> slot;                            // host mirror of the slot table
     ExtentAlloc extents;                               // units of SEG_GRANULE_ROWS rows
+    // the online path's tables (mocha_bank_set_starts, mocha_bank_resident_set_starts): one bit per global row, "starts a clip", and
+    // one epoch word per segment / slot, which add and retire bump.  They exist, zeroed, from mocha_bank_set_segments /
+    // mocha_bank_resident_create on - calls that move the generation themselves - and are rewritten in stream order after that.
+    DeviceBuffer<unsigned> start_bits, slot_epoch;
+    DeviceBuffer<int32_t> start_list;                  // the uploaded list of a set_starts call
 
     bool segmented() const { return resident || !seg_start.empty(); }                 // the segmented calls serve this bank
     int segments() const { return resident ? (int)slot.size() : (int)seg_start.size() - 1; }
@@ -209,6 +214,15 @@ struct MixArg {
     }
 };
 
+// The online path of a segmented call (match_path_step.hip): window s of the call is stream s of the caller's state (streams = the call's
+// windows, <= 16); the penalty by value; restart (device, one-shot words) and the per-stream outputs may be null.  dist_row (windows, ld):
+// every distance of the step, for tests and tools.
+struct PathStepArg {
+    void* state = nullptr; int state_rows = 0; double lambda = 0.0;
+    int32_t* restart = nullptr; float* dist = nullptr; unsigned char* continued = nullptr;
+    float* dist_row = nullptr; int64_t ld = 0;
+};
+
 // The windows of a characterize: X (B windows, raw = with the root bone and un-normalised) -> Y
 struct SegWindows {
     const float* X = nullptr; int B = 0; const float *cnt_mean = nullptr, *cnt_std = nullptr; float* Y = nullptr; bool raw = false;
@@ -222,6 +236,7 @@ struct SegSelect {
     int k = 0; float temperature = 0.f;
     const AllowArg* allow = nullptr;
     const MixArg* mix = nullptr;
+    const PathStepArg* path = nullptr;                 // the online path in the hard matcher's place (k == 0, no allow, no mix)
     int32_t *idx0 = nullptr, *idx_k = nullptr; float* w_k = nullptr;
     const int32_t* ids() const { return mix ? mix->ids : seg; }
     bool literal() const { return mix || k > 0; }      // the decoder runs on the blend in the "sel" workspace, not through the bank's rows
@@ -414,7 +429,11 @@ struct mocha_ctx {
         // the mix steps only: components per window, and the weights / normalised-weight pointers (the ids are `seg`, the (windows, J)
         // rows `idx`); ids and weights are read by every replay
         int mix_j = 0; const void* mix[2] = {};
+        // the online-path steps only: the path state, the restart words and the dist / continued outputs; the state's rows and the penalty
+        const void* path[4] = {}; int path_rows = 0; double path_lambda = 0.0;
         bool operator==(const StepKey& o) const {
+            for (int i = 0; i < 4; ++i) if (path[i] != o.path[i]) return false;
+            if (path_rows != o.path_rows || path_lambda != o.path_lambda) return false;
             if (mix_j != o.mix_j || mix[0] != o.mix[0] || mix[1] != o.mix[1]) return false;
             if (!(x == o.x && mean == o.mean && sd == o.sd && y == o.y && idx == o.idx && seg == o.seg && windows == o.windows && raw == o.raw))
                 return false;
@@ -438,6 +457,7 @@ struct mocha_ctx {
         STEP_LIVE_RAW, STEP_LIVE_RAW_SOFT, STEP_LIVE_RAW_INERT,                                      // mocha_live_step_raw: hard, soft, inertialized
         STEP_LIVE_ALLOW, STEP_LIVE_RAW_ALLOW, STEP_LIVE_MIX, STEP_LIVE_RAW_MIX,                      // mocha_live_step[_raw]_allow, mocha_live_step[_raw]_mix
         STEP_OURS, STEP_OURS_GROUPED,                                                                // mocha_live_step_ours[_grouped]
+        STEP_LIVE_PATH, STEP_LIVE_RAW_PATH,                                                          // mocha_live_step_path, mocha_live_step_raw_path
         STEP_KINDS
     };
     struct StepGraph {
@@ -1449,6 +1469,18 @@ int ensure_seg_scratch(mocha_ctx* c, int set) {
     return rc;
 }
 
+// The online path's tables of bank `b` (Bank::start_bits, slot_epoch) for N rows in S segments or slots, all zero: no row but a
+// character's first starts a clip, every epoch 0.  Called where the bank is set, which moves the generation itself.
+int path_tables_zeroed(mocha_ctx* c, Bank& b, int64_t N, int S, hipStream_t s) {
+    const size_t words = (size_t)((N + 31) / 32);
+    int rc = reserve(c, b.start_bits, words);
+    if (!rc) rc = reserve(c, b.slot_epoch, (size_t)S);
+    if (rc) return rc;
+    HIPCHK(c, hipMemsetAsync(b.start_bits.p, 0, words * sizeof(unsigned), s));
+    HIPCHK(c, hipMemsetAsync(b.slot_epoch.p, 0, (size_t)S * sizeof(unsigned), s));
+    return 0;
+}
+
 // A call that searches or reads the bank's rows as ONE set: a resident bank has free extents and retired rows among them, and none of the
 // union's derived data (centroid, norms, images) - it serves the segmented and live calls only
 int refuse_resident(mocha_ctx* c, const char* who) {
@@ -1511,6 +1543,47 @@ int seg_topk(mocha_ctx* c, const float* q, int Q, const int32_t* seg, int k, flo
            launch_match_seg_topk(bank, b16 ? 1 : 0, q, seg, Q, c->bank.seg_dev.p, S, c->bank.seg_max_rows, D, c->sets[set].seg_keys.p,
                                  c->sets[set].seg_plan.p, c->bank.enc, k, temperature, idx0, idx_k, dist_k, w_k, out, s, al ? &sa : nullptr,
                                  c->bank.resident ? 1 : 0));
+    return 0;
+}
+
+// what every online-path call checks of its numbers, nothing launched when they fail
+int path_step_check(mocha_ctx* c, const char* who, int streams, int state_rows, double lambda) {
+    if (streams < 1 || streams > PATH_STEP_MAX_STREAMS) return fail(c, MOCHA_ERR_ARG, "%s: 1 <= streams <= %d", who, PATH_STEP_MAX_STREAMS);
+    if (state_rows < 1 || state_rows > MATCH_PATH_MAX_ROWS) return fail(c, MOCHA_ERR_ARG, "%s: 1 <= state_rows <= %d", who, MATCH_PATH_MAX_ROWS);
+    if (!(lambda >= 0.0) || !std::isfinite(lambda)) return fail(c, MOCHA_ERR_ARG, "%s: the jump penalty must be finite and >= 0", who);
+    return 0;
+}
+
+// ... and of the bank, for the forms that read one
+int path_step_bank(mocha_ctx* c, const char* who, int state_rows) {
+    if (!c->bank.cnt) return fail(c, MOCHA_ERR_STATE, "no bank: call mocha_bank_set_segments first");
+    if (!c->bank.segmented()) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (c->bank.seg_max_rows > state_rows)
+        return fail(c, MOCHA_ERR_STATE, "%s: the bank's largest character has %lld rows, the path state holds %d", who, (long long)c->bank.seg_max_rows, state_rows);
+    if (!c->bank.start_bits.p || !c->bank.slot_epoch.p) return fail(c, MOCHA_ERR_STATE, "%s: the bank has no start table", who);
+    return 0;
+}
+
+// One step of the online path for Q <= 16 streams (match_path_step.hip): the plan and the all-keys scan of the bank's fp32 rows - the
+// z-scored queries qnm, whatever the bank's flags - through the key buffer of the current workspace set, then the step kernel on the
+// keys.  idx: local rows (or null), gidx: global rows for the decoder (or null).  Nothing allocates, copies from the host or synchronises.
+// The caller ran path_step_check and path_step_bank.
+int seg_path(mocha_ctx* c, const float* qnm, int Q, const int32_t* seg, const PathStepArg& p, int32_t* idx, int32_t* gidx, hipStream_t s) {
+    const int set = c->cur, S = c->bank.segments();
+    const int D = 90 * 256;
+    if (!c->sets[set].seg_keys.p || !c->sets[set].seg_plan.p) return no_seg_scratch(c, set);
+    LAUNCH(c, s, "mocha_match_seg_keys<f32>", "match.path_keys", 3.0 * Q * c->bank.seg_max_rows * D, (double)c->bank.seg_max_rows * D * 4.0 + 8.0 * Q * c->bank.seg_max_rows,
+           launch_match_seg_keys(c->bank.cnt, qnm, seg, Q, c->bank.seg_dev.p, S, c->bank.seg_max_rows, D, c->sets[set].seg_keys.p, c->sets[set].seg_plan.p, s,
+                                 c->bank.resident ? 1 : 0));
+    PathStepArgs a{};
+    a.state = p.state; a.streams = Q; a.state_rows = p.state_rows;
+    a.ids = seg;
+    a.seg_table = c->bank.seg_dev.p; a.S = S; a.pairs = c->bank.resident ? 1 : 0; a.epochs = c->bank.slot_epoch.p;
+    a.start_bits = c->bank.start_bits.p; a.n_bits = c->bank.N;
+    a.restart = p.restart; a.lambda = p.lambda;
+    a.keys = c->sets[set].seg_keys.p; a.kstride = match_seg_key_stride(c->bank.seg_max_rows);
+    a.idx = idx; a.gidx = gidx; a.dist_out = p.dist; a.continued = p.continued; a.dist_row = p.dist_row; a.ld_row = p.ld;
+    LAUNCH(c, s, "mocha_match_path_step", "match.path_step", 3.0 * Q * c->bank.seg_max_rows, 24.0 * Q * c->bank.seg_max_rows, launch_match_path_step(a, s));
     return 0;
 }
 
@@ -2311,7 +2384,12 @@ static int characterize_segmented_impl(mocha_ctx* c, const SegWindows& w, const 
         const AllowArg* al = sel.allow ? &ab : nullptr;
         int32_t* gx = SET(c).idx_ws.p;
         int32_t* i0 = sel.idx0 ? sel.idx0 + b0 : nullptr;
-        if (sel.mix)
+        if (sel.path) {
+            // the online path: window s is stream s of the state, so the call is one chunk; the z-scored queries against the fp32 rows
+            // also on a bf16 bank; then the hard decoder route below, through the rows the step left in gx
+            if (b != w.B) return fail(c, MOCHA_ERR_STATE, "characterize_segmented_path: the workspace holds fewer windows than the call has streams");
+            r = seg_path(c, WS(c, "qnm"), b, sel.seg, *sel.path, i0, gx, s);
+        } else if (sel.mix)
             r = seg_mix(c, q, b, sel.mix->at((size_t)b0), WS(c, "sel"), s);
         else if (sel.k > 0)
             r = seg_topk(c, q, b, sel.seg + b0, sel.k, sel.temperature, i0, sel.idx_k ? sel.idx_k + (size_t)b0 * sel.k : nullptr, nullptr,
@@ -2465,6 +2543,117 @@ int mocha_match_path(mocha_ctx* c, const float* dist, int Q, int N, int64_t ld, 
     int rc = path_check(c, a, Q, N, "mocha_match_path"); if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     return path_run(c, dist, Q, N, ld, a, path, dist_out, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------- coherent matching, the online form
+// (include/mocha_hip.h "coherent matching in live sessions"; kernels in match_path_step.hip)
+int64_t mocha_path_state_bytes(const mocha_ctx* c, int streams, int state_rows) {
+    if (!c || streams < 1 || streams > PATH_STEP_MAX_STREAMS || state_rows < 1 || state_rows > MATCH_PATH_MAX_ROWS) return MOCHA_ERR_ARG;
+    return (int64_t)path_step_state_bytes(streams, state_rows);
+}
+
+int mocha_path_state_reset(mocha_ctx* c, void* state, int streams, int state_rows, const int32_t* which, int n, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    int rc = path_step_check(c, "path_state_reset", streams, state_rows, 0.0); if (rc) return rc;
+    if (!state) return fail(c, MOCHA_ERR_ARG, "path_state_reset: null argument");
+    if (which && (n < 0 || n > streams)) return fail(c, MOCHA_ERR_ARG, "path_state_reset: n must be 0..streams");
+    for (int i = 0; which && i < n; ++i)
+        if (which[i] < 0 || which[i] >= streams) return fail(c, MOCHA_ERR_ARG, "path_state_reset: stream %d out of range 0..%d", (int)which[i], streams - 1);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    // the headers alone: a stream that is not running never reads its R
+    char* base = static_cast<char*>(state);
+    if (!which) { HIPCHK(c, hipMemsetAsync(base, 0, (size_t)PATH_STEP_HDR_BYTES * streams, s)); return 0; }
+    for (int i = 0; i < n; ++i) HIPCHK(c, hipMemsetAsync(base + (size_t)PATH_STEP_HDR_BYTES * which[i], 0, PATH_STEP_HDR_BYTES, s));
+    return 0;
+}
+
+int mocha_match_path_advance(mocha_ctx* c, void* state, int streams, int state_rows, const float* dist, int64_t ld, const int32_t* ids,
+                             const int32_t* rows, const uint32_t* start_bits, int64_t n_bits, const int32_t* bit_off, int32_t* restart, double lambda,
+                             int32_t* idx, float* dist_out, unsigned char* continued, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    int rc = path_step_check(c, "match_path_advance", streams, state_rows, lambda); if (rc) return rc;
+    if (!state || !dist || !ids || !rows || !idx) return fail(c, MOCHA_ERR_ARG, "match_path_advance: null argument");
+    if (ld < 1) return fail(c, MOCHA_ERR_ARG, "match_path_advance: ld < 1");
+    if (n_bits < 0 || (start_bits && n_bits < 1) || (!start_bits && bit_off)) return fail(c, MOCHA_ERR_ARG, "match_path_advance: start bits: a table of n_bits >= 1 bits, or none");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    PathStepArgs a{};
+    a.state = state; a.streams = streams; a.state_rows = state_rows;
+    a.ids = ids; a.rows = rows;
+    a.start_bits = start_bits; a.n_bits = start_bits ? n_bits : 0; a.bit_off = bit_off;
+    a.restart = restart; a.lambda = lambda;
+    a.dist = dist; a.ld = ld;
+    a.idx = idx; a.dist_out = dist_out; a.continued = continued;
+    LAUNCH(c, s, "mocha_match_path_step", "match.path_step", 3.0 * streams * state_rows, 28.0 * streams * state_rows, launch_match_path_step(a, s));
+    return 0;
+}
+
+int mocha_match_path_segmented(mocha_ctx* c, void* state, int streams, int state_rows, const float* query_nm, const int32_t* seg, int32_t* restart,
+                               double lambda, int32_t* idx, float* dist, unsigned char* continued, float* dist_row, int64_t ld, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    int rc = path_step_check(c, "match_path_segmented", streams, state_rows, lambda); if (rc) return rc;
+    if (!state || !query_nm || !seg || !idx) return fail(c, MOCHA_ERR_ARG, "match_path_segmented: null argument");
+    if (dist_row && ld < state_rows) return fail(c, MOCHA_ERR_ARG, "match_path_segmented: ld < state_rows");
+    if ((rc = ready(c, 0))) return rc;
+    if ((rc = path_step_bank(c, "match_path_segmented", state_rows))) return rc;
+    PathStepArg p; p.state = state; p.state_rows = state_rows; p.lambda = lambda; p.restart = restart; p.dist = dist; p.continued = continued;
+    p.dist_row = dist_row; p.ld = ld;
+    c->cur = 0;
+    return seg_path(c, query_nm, streams, seg, p, idx, nullptr, (hipStream_t)stream);
+}
+
+int mocha_characterize_segmented_path(mocha_ctx* c, const float* src_X, int B, const int32_t* seg, const float* cnt_mean, const float* cnt_std,
+                                      void* path_state, int state_rows, double lambda, int32_t* restart, float* Y, int32_t* idx, float* dist,
+                                      unsigned char* continued, int raw, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    int rc = path_step_check(c, "characterize_segmented_path", B, state_rows, lambda); if (rc) return rc;
+    if (!path_state || !seg) return fail(c, MOCHA_ERR_ARG, "characterize_segmented_path: null argument");
+    if (c->bank.cnt && c->bank.segmented() && (rc = path_step_bank(c, "characterize_segmented_path", state_rows))) return rc;
+    PathStepArg p; p.state = path_state; p.state_rows = state_rows; p.lambda = lambda; p.restart = restart; p.dist = dist; p.continued = continued;
+    SegSelect sel; sel.seg = seg; sel.idx0 = idx; sel.path = &p;
+    return characterize_segmented_impl(c, SegWindows{src_X, B, cnt_mean, cnt_std, Y, raw != 0}, sel, stream);
+}
+
+int mocha_bank_set_starts(mocha_ctx* c, const int64_t* starts, int n, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    Bank& b = c->bank;
+    if (b.resident) return fail(c, MOCHA_ERR_STATE, "bank_set_starts: a resident bank takes its starts per slot (mocha_bank_resident_set_starts)");
+    if (!b.cnt || !b.segmented() || !b.start_bits.p) return fail(c, MOCHA_ERR_STATE, "no segment table: call mocha_bank_set_segments first");
+    if (n < 0 || (n > 0 && !starts)) return fail(c, MOCHA_ERR_ARG, "bank_set_starts: a list or none");
+    for (int i = 0; i < n; ++i) {
+        if (starts[i] < 0 || starts[i] >= b.N) return fail(c, MOCHA_ERR_ARG, "bank_set_starts: start %lld outside the %lld rows", (long long)starts[i], (long long)b.N);
+        if (i && starts[i] <= starts[i - 1]) return fail(c, MOCHA_ERR_ARG, "bank_set_starts: starts must increase strictly");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int32_t> l32(starts, starts + n);
+    int rc = reserve(c, b.start_list, (size_t)std::max(n, 1)); if (rc) return rc;
+    // (pageable host memory: the copy is staged before the call returns)
+    if (n > 0) HIPCHK(c, hipMemcpyAsync(b.start_list.p, l32.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    LAUNCH(c, s, "mocha_path_starts", "bank.starts", 0.0, b.N / 8.0 + 4.0 * n, launch_path_starts(b.start_bits.p, b.N, 0, b.N, b.start_list.p, n, nullptr, s));
+    return 0;
+}
+
+int mocha_bank_resident_set_starts(mocha_ctx* c, int slot, const int32_t* starts, int n, void* stream) {
+    if (!c) return MOCHA_ERR_ARG;
+    Bank& b = c->bank;
+    if (!b.resident) return fail(c, MOCHA_ERR_STATE, "bank_resident_set_starts: no resident bank: call mocha_bank_resident_create first");
+    if (slot < 0 || slot >= b.segments()) return fail(c, MOCHA_ERR_ARG, "bank_resident_set_starts: slot %d out of range 0 .. %d", slot, b.segments() - 1);
+    if (!b.slot[slot].rows) return fail(c, MOCHA_ERR_STATE, "bank_resident_set_starts: slot %d is empty", slot);
+    if (n < 0 || (n > 0 && !starts)) return fail(c, MOCHA_ERR_ARG, "bank_resident_set_starts: a list or none");
+    const int64_t rows = b.slot[slot].rows;
+    for (int i = 0; i < n; ++i) {
+        if (starts[i] < 0 || starts[i] >= rows) return fail(c, MOCHA_ERR_ARG, "bank_resident_set_starts: start %d outside the character's %lld rows", (int)starts[i], (long long)rows);
+        if (i && starts[i] <= starts[i - 1]) return fail(c, MOCHA_ERR_ARG, "bank_resident_set_starts: starts must increase strictly");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    int rc = reserve(c, b.start_list, (size_t)std::max(n, 1)); if (rc) return rc;
+    if (n > 0) HIPCHK(c, hipMemcpyAsync(b.start_list.p, starts, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    LAUNCH(c, s, "mocha_path_starts", "bank.starts", 0.0, rows / 8.0 + 4.0 * n,
+           launch_path_starts(b.start_bits.p, b.N, b.slot[slot].first, rows, b.start_list.p, n, nullptr, s));
+    return 0;
 }
 
 // mocha_characterize with the path in the matcher's place.  The path spans the whole batch, so the batch goes through the workspace
@@ -2648,7 +2837,7 @@ int mocha_bank_set_segments(mocha_ctx* c, const float* cnt_nm, const float* enco
             int r;
             if ((set == 0 || !c->sets[set].ws.empty()) && (r = ensure_seg_scratch(c, set))) return r;
         }
-        return 0;
+        return path_tables_zeroed(c, c->bank, N, S, s);
     }();
     if (rc) { c->bank.seg_start.clear(); c->bank.seg_max_rows = 0; }
     return rc;
@@ -2925,6 +3114,7 @@ int mocha_bank_resident_create(mocha_ctx* c, int64_t capacity_rows, int max_char
     HIPCHK(c, hipMemsetAsync(b.lab_gran.p, 0, G * sizeof(unsigned long long), s));
     HIPCHK(c, hipMemsetAsync(b.lab_gran_start.p, 0, (S + 1) * sizeof(int), s));
     HIPCHK(c, hipMemsetAsync(b.seg_dev.p, 0, 2 * S * sizeof(int), s));
+    if ((rc = path_tables_zeroed(c, b, cap, (int)S, s))) return rc;
     b.slot.assign(S, Bank::Slot{});
     b.extents.reset(cap / SEG_GRANULE_ROWS);
     b.seg_max_rows = max_rows_per_character;
@@ -2979,6 +3169,10 @@ int mocha_bank_resident_add(mocha_ctx* c, int slot, const float* cnt_nm, const f
         }
         LAUNCH(c, s, "mocha_resident_labels", "bank.labels", 0.0, 5.0 * n,
                launch_resident_labels(labels, n, first, b.N, b.lab_dev.p, b.lab_gran.p, b.lab_any.p + slot, s));
+        // the online path's tables: no row of the new character starts a clip yet (mocha_bank_resident_set_starts), and the slot's epoch
+        // moves, so that a stream on this slot restarts even when the new character has the old one's extent
+        LAUNCH(c, s, "mocha_path_starts_clear", "bank.starts", 0.0, n / 8.0 + 8.0,
+               launch_path_starts(b.start_bits.p, b.N, first, n, nullptr, 0, b.slot_epoch.p + slot, s));
         LAUNCH(c, s, "mocha_resident_publish", "bank.publish", 0.0, 12.0,
                launch_resident_publish(b.seg_dev.p, b.lab_gran_start.p, slot, S, first, n, b.N, s));
         return 0;
@@ -2999,6 +3193,8 @@ int mocha_bank_resident_retire(mocha_ctx* c, int slot, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     // row count 0: the slot's id is now an id outside the table; its rows stay as they are and are never read
     LAUNCH(c, s, "mocha_resident_publish", "bank.publish", 0.0, 12.0, launch_resident_publish(b.seg_dev.p, b.lab_gran_start.p, slot, S, 0, 0, b.N, s));
+    LAUNCH(c, s, "mocha_path_starts_clear", "bank.starts", 0.0, b.slot[slot].rows / 8.0 + 8.0,
+           launch_path_starts(b.start_bits.p, b.N, b.slot[slot].first, b.slot[slot].rows, nullptr, 0, b.slot_epoch.p + slot, s));
     (void)b.extents.release(b.slot[slot].first / SEG_GRANULE_ROWS, granule_units(b.slot[slot].rows));
     b.slot[slot] = Bank::Slot{};
     return 0;
@@ -3794,6 +3990,7 @@ struct LiveStages {
     const IngestParams* ingest = nullptr; const mocha_ingest_cfg* ingest_cfg = nullptr;
     const AllowArg* allow = nullptr;
     const MixArg* mix = nullptr;
+    const PathStepArg* path = nullptr;                 // the online path in the hard matcher's place (alone: no soft, inert, allow or mix)
 };
 
 // A live session's buffer as the steps use it, with what mocha_live_step and mocha_live_step_ours make of their common arguments: the
@@ -3884,7 +4081,8 @@ int mocha_live_reset(mocha_ctx* c, void* live, int streams, const int32_t* which
 
 // The graph of a step of mocha_live_step's family: mix and allow steps have one each per input form (featurised / raw); the others one
 // per input form for the hard, the soft and the inertialized (hard or soft) step
-static mocha_ctx::StepKind live_step_kind(bool mix, bool allow, bool ingest, bool inert, bool soft) {
+static mocha_ctx::StepKind live_step_kind(bool mix, bool allow, bool ingest, bool inert, bool soft, bool path = false) {
+    if (path) return ingest ? mocha_ctx::STEP_LIVE_RAW_PATH : mocha_ctx::STEP_LIVE_PATH;
     if (mix) return ingest ? mocha_ctx::STEP_LIVE_RAW_MIX : mocha_ctx::STEP_LIVE_MIX;
     if (allow) return ingest ? mocha_ctx::STEP_LIVE_RAW_ALLOW : mocha_ctx::STEP_LIVE_ALLOW;
     if (ingest) return inert ? mocha_ctx::STEP_LIVE_RAW_INERT : soft ? mocha_ctx::STEP_LIVE_RAW_SOFT : mocha_ctx::STEP_LIVE_RAW;
@@ -3900,6 +4098,7 @@ static int live_step_impl(mocha_ctx* c, const LiveCall& a, const LiveFrame& f, c
     const IngestParams* ing = st.ingest;
     if (al && !c->bank.labelled) return fail(c, MOCHA_ERR_STATE, "no action labels: call mocha_bank_set_labels first");
     if (mx && !c->sets[0].mix_zero.p) return no_seg_scratch(c, 0);
+    if (st.path && (rc = path_step_bank(c, "live_step_path", st.path->state_rows))) return rc;
     LiveView v;
     if ((rc = live_view(c, a, f, o, v))) return rc;
     const int streams = a.streams, J = c->cfg.V + 1, V = c->cfg.V;
@@ -3912,6 +4111,9 @@ static int live_step_impl(mocha_ctx* c, const LiveCall& a, const LiveFrame& f, c
         MixArg m;
         SegSelect sel; sel.seg = v.eff; sel.k = st.k; sel.temperature = st.temperature; sel.allow = al; sel.idx0 = ix; sel.idx_k = ixk; sel.w_k = wk;
         if (mx) { m = MixArg{mx->ids, mx->weights, mx->J, ix, nullptr, wk, v.eff, ix ? o.valid : nullptr}; sel.mix = &m; }
+        // (the characterize before a capture, ix null, is the plain hard one: it must not move the path state, and the path adds no
+        // kernel that makes anything on first use)
+        if (st.path && ix) sel.path = st.path;
         return characterize_segmented_set0(c, win, sel, cs);
     };
     // ring push + featurize -> segmented characterize of the S windows with the effective ids -> pose heads -> one post-processing frame
@@ -3947,7 +4149,11 @@ static int live_step_impl(mocha_ctx* c, const LiveCall& a, const LiveFrame& f, c
     if (ing) { key.ingest[0] = ing->state; key.ingest[1] = ing->rot; key.ingest[2] = ing->pos; key.icfg = *st.ingest_cfg; }
     if (al) { key.allow[0] = al->allow; key.allow[1] = al->applied; }
     if (mx) { key.mix_j = mx->J; key.mix[0] = mx->weights; key.mix[1] = st.w_k; }
-    mocha_ctx::StepGraph& g = c->steps[live_step_kind(mx, al, ing, st.inert, st.k > 0)];
+    if (st.path) {
+        key.path[0] = st.path->state; key.path[1] = st.path->restart; key.path[2] = st.path->dist; key.path[3] = st.path->continued;
+        key.path_rows = st.path->state_rows; key.path_lambda = st.path->lambda;
+    }
+    mocha_ctx::StepGraph& g = c->steps[live_step_kind(mx, al, ing, st.inert, st.k > 0, st.path != nullptr)];
     if (!step_holds(c, g, key)) {
         // Before a capture: one eager characterize of the staging windows with every id -1 (no bank row is matched, no state of the
         // session moves), so that whatever the kernels of the step make on first use - the plane GEMMs' weight images, for the soft step
@@ -4273,6 +4479,44 @@ int mocha_live_step_raw_allow(mocha_ctx* c, const mocha_post_cfg* cfg, const moc
     LiveCall a; a.cfg = cfg; a.live = live; a.streams = streams; a.seg = seg; a.cnt_mean = cnt_mean; a.cnt_std = cnt_std; a.stream = stream;
     LiveOut o; o.pos = pos_out; o.rot = rot_out; o.ik_rot = ik_rot; o.bvh_pos = bvh_pos; o.bvh_euler = bvh_euler; o.idx = idx; o.valid = valid;
     return live_step_raw_impl(c, "live_step_raw_allow", a, icfg_in, ingest, rot, pos, o, st, icfg);
+}
+
+// The live step with the online path in the hard matcher's place: stream s of the session is stream s of the path state.  A stream that is
+// warming, has no frame or names no loaded character has the effective id -1 and sits the path step out.
+static int live_path_arg(mocha_ctx* c, const char* who, int streams, void* path_state, int state_rows, double lambda, int32_t* restart, float* dist,
+                         unsigned char* continued, PathStepArg& p) {
+    int rc = path_step_check(c, who, streams, state_rows, lambda); if (rc) return rc;
+    if (!path_state || !dist || !continued) return fail(c, MOCHA_ERR_ARG, "%s: null argument", who);
+    p.state = path_state; p.state_rows = state_rows; p.lambda = lambda; p.restart = restart; p.dist = dist; p.continued = continued;
+    return 0;
+}
+
+int mocha_live_step_path(mocha_ctx* c, const mocha_post_cfg* cfg, void* live, int streams, const float* Yrot, const float* Ypos, const float* Yvel,
+                         const float* Yang, const float* src_rvel, const float* src_rang, const float* src_speed, const unsigned char* contact,
+                         const int32_t* seg, const float* cnt_mean, const float* cnt_std, double* pos, double* rot, double* ik_rot, double* bvh_pos,
+                         double* bvh_euler, int32_t* idx, int32_t* valid, void* stream, void* path_state, int state_rows, double lambda,
+                         int32_t* restart, float* dist, unsigned char* continued) {
+    if (!c) return MOCHA_ERR_ARG;
+    PathStepArg p;
+    int rc = live_path_arg(c, "live_step_path", streams, path_state, state_rows, lambda, restart, dist, continued, p); if (rc) return rc;
+    LiveStages st; st.path = &p;
+    LiveCall a; a.cfg = cfg; a.live = live; a.streams = streams; a.seg = seg; a.cnt_mean = cnt_mean; a.cnt_std = cnt_std; a.stream = stream;
+    LiveFrame f; f.Yrot = Yrot; f.Ypos = Ypos; f.Yvel = Yvel; f.Yang = Yang; f.src_rvel = src_rvel; f.src_rang = src_rang; f.src_speed = src_speed; f.contact = contact;
+    LiveOut o; o.pos = pos; o.rot = rot; o.ik_rot = ik_rot; o.bvh_pos = bvh_pos; o.bvh_euler = bvh_euler; o.idx = idx; o.valid = valid;
+    return live_step_impl(c, a, f, o, st);
+}
+
+int mocha_live_step_raw_path(mocha_ctx* c, const mocha_post_cfg* cfg, const mocha_ingest_cfg* icfg_in, void* live, void* ingest, int streams,
+                             const float* rot, const float* pos, const int32_t* seg, const float* cnt_mean, const float* cnt_std, double* pos_out,
+                             double* rot_out, double* ik_rot, double* bvh_pos, double* bvh_euler, int32_t* idx, int32_t* valid, void* stream,
+                             void* path_state, int state_rows, double lambda, int32_t* restart, float* dist, unsigned char* continued) {
+    if (!c) return MOCHA_ERR_ARG;
+    PathStepArg p;
+    int rc = live_path_arg(c, "live_step_raw_path", streams, path_state, state_rows, lambda, restart, dist, continued, p); if (rc) return rc;
+    LiveStages st; st.path = &p;
+    LiveCall a; a.cfg = cfg; a.live = live; a.streams = streams; a.seg = seg; a.cnt_mean = cnt_mean; a.cnt_std = cnt_std; a.stream = stream;
+    LiveOut o; o.pos = pos_out; o.rot = rot_out; o.ik_rot = ik_rot; o.bvh_pos = bvh_pos; o.bvh_euler = bvh_euler; o.idx = idx; o.valid = valid;
+    return live_step_raw_impl(c, "live_step_raw_path", a, icfg_in, ingest, rot, pos, o, st, nullptr);
 }
 
 // The live step with the mix characterize in the place of the hard one (ids (S,J), weights (S,J,6): device data every replay reads; idx

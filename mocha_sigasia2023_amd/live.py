@@ -18,8 +18,8 @@ import numpy as np
 import torch
 
 from . import _C
-from .generator import DIM, NTOK, _dev_f32, _ptr, _stream
-from .multi_character import MIX_PARTS, MultiCharacterBank, _refuse_with_mix, mix_count, mix_tensors, soft_params
+from .generator import DIM, NTOK, CoherentMatch, _dev_f32, _ptr, _stream
+from .multi_character import MIX_PARTS, MultiCharacterBank, OnlinePath, _refuse_with_mix, mix_count, mix_tensors, soft_params
 from .ingest import IngestConfig, reset_ingest
 from .postprocess import PostProcessor
 from .world import SkinBind, _launch as _world_launch
@@ -53,12 +53,32 @@ class LiveSession:
     ``mocha_world_pose`` launch BEHIND the captured graph, on the same stream, reads ``out["pos"]``, ``out["ik_rot"]`` and ``out["valid"]``
     - it is not a node of the graph, as the resampler sits in front of the graph and not in it - so the step's capture, its key and every
     existing output are what they are without ``world``.  Fixed tensors, overwritten by the next push; rows of a warming stream are not
-    written; no host synchronisation.  The default ``None`` leaves everything as it is."""
+    written; no host synchronisation.  The default ``None`` leaves everything as it is.
+    ``coherent=jump`` (a number, or a ``CoherentMatch`` without ``relative``): coherent matching, one step of the path per pushed frame
+    (``mocha_live_step_path`` / ``mocha_live_step_raw_path``; ``OnlinePath``).  A session pushes one stride-1 window per step against a bank
+    of stride-1 windows of smooth clips, so the right answer for consecutive pushes is almost always "the next row": every transition
+    that is not "next row of the same clip" pays ``jump``, in the units of the matcher's distances (a live stream has no clip to take a
+    median from, so ``relative=True`` raises: run ``query_path(..., relative=True)`` on a recorded clip for a unit).  The clip starts are
+    the bank's (``MultiCharacterBank(starts=)`` / ``set_starts``, ``ResidentCharacterBank.add(starts=)``).  The outputs gain ``dist`` (S,)
+    fp32 and ``continued`` (S,) uint8; ``self.restart`` (S,) int32 on the device restarts a stream's path where it is non-zero (written
+    in place, cleared by the step).  A stream restarts on its own when its character changes or is replaced and after ``reset``.
+    ``coherent=0`` gives the plain session's bits on an fp32 bank.  Combines with ``raw=`` and ``world=``; not with ``soft``,
+    ``inertial``, ``constrained`` or ``mix``."""
 
     def __init__(self, bank: MultiCharacterBank, cnt_mean, cnt_std, streams: int = 1, post: Optional[PostProcessor] = None, bvh: bool = True,
-                 soft=None, inertial: Optional[float] = None, raw=None, constrained: bool = False, mix=None, world=None):
+                 soft=None, inertial: Optional[float] = None, raw=None, constrained: bool = False, mix=None, world=None, coherent=None):
         if not 1 <= int(streams) <= 16:
             raise ValueError("streams must be 1..16")
+        if coherent is not None:
+            co = CoherentMatch.of(coherent)
+            if co.relative:
+                raise ValueError("LiveSession: coherent= takes an absolute jump penalty - a live stream has no clip to take a median from; "
+                                 "run query_path(..., relative=True) on a recorded clip for the unit")
+            if co.bank_starts is not None or co.src_starts is not None:
+                raise ValueError("LiveSession: the clip starts of a live session are the bank's (MultiCharacterBank(starts=), add(starts=))")
+            for name, v in (("soft", soft is not None), ("inertial", inertial is not None), ("constrained", constrained), ("mix", mix is not None)):
+                if v:
+                    raise ValueError(f"LiveSession: coherent= does not combine with {name}")
         self.mix = None
         if mix is not None:
             self.mix = mix_count(mix, "LiveSession")
@@ -137,6 +157,11 @@ class LiveSession:
             self.out["gpos"], self.out["grot"] = f64(S, J, 3), f64(S, J, 4)
             if self.world_bind is not None:
                 self.out["palette"] = f32(S, V, 12)
+        self.path = None
+        if coherent is not None:
+            self.path = OnlinePath(bank, S, CoherentMatch.of(coherent).jump)
+            self.restart = self.path.restart
+            self.out["dist"], self.out["continued"] = self.path.dist, self.path.continued
         bank._ensure()
 
     @property
@@ -217,6 +242,14 @@ class LiveSession:
         self.bank._ensure()
         o = self.out
         k, t = self.soft if self.soft is not None else (0, 0.0)
+        if self.path is not None:
+            p = self.path
+            self.model._ctx.call("mocha_live_step_raw_path", C.byref(self.post.cfg), C.byref(self.rcfg), _ptr(self.live), _ptr(self.ingest),
+                                 self.streams, _ptr(self.raw_rot), _ptr(self.raw_pos), _ptr(self.ids), _ptr(self.mean), _ptr(self.std),
+                                 _ptr(o["pos"]), _ptr(o["rot"]), _ptr(o["ik_rot"]), _ptr(o["bvh_pos"]) if self.bvh else None,
+                                 _ptr(o["bvh_euler"]) if self.bvh else None, _ptr(o["idx"]), _ptr(o["valid"]), _stream(), _ptr(p.state),
+                                 p.state_rows, C.c_double(p.jump), _ptr(p.restart), _ptr(p.dist), _ptr(p.continued))
+            return o
         if self.mix is not None:
             self.model._ctx.call("mocha_live_step_raw_mix", C.byref(self.post.cfg), C.byref(self.rcfg), _ptr(self.live), _ptr(self.ingest),
                                  self.streams, _ptr(self.raw_rot), _ptr(self.raw_pos), _ptr(self.mix_ids), _ptr(self.mix_weights), self.mix,
@@ -253,6 +286,15 @@ class LiveSession:
     def _step(self):
         self.bank._ensure()
         o = self.out
+        if self.path is not None:
+            p = self.path
+            self.model._ctx.call("mocha_live_step_path", C.byref(self.post.cfg), _ptr(self.live), self.streams, _ptr(self.rot), _ptr(self.pos),
+                                 _ptr(self.vel), _ptr(self.ang), _ptr(self.rvel), _ptr(self.rang), _ptr(self.speed), _ptr(self.contact),
+                                 _ptr(self.ids), _ptr(self.mean), _ptr(self.std), _ptr(o["pos"]), _ptr(o["rot"]), _ptr(o["ik_rot"]),
+                                 _ptr(o["bvh_pos"]) if self.bvh else None, _ptr(o["bvh_euler"]) if self.bvh else None, _ptr(o["idx"]),
+                                 _ptr(o["valid"]), _stream(), _ptr(p.state), p.state_rows, C.c_double(p.jump), _ptr(p.restart), _ptr(p.dist),
+                                 _ptr(p.continued))
+            return o
         if self.mix is not None:
             self.model._ctx.call("mocha_live_step_mix", C.byref(self.post.cfg), _ptr(self.live), self.streams, _ptr(self.rot), _ptr(self.pos),
                                  _ptr(self.vel), _ptr(self.ang), _ptr(self.rvel), _ptr(self.rang), _ptr(self.speed), _ptr(self.contact),

@@ -24,7 +24,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .generator import DIM, NTOK, CoherentMatch, Generator, _dev_f32, _dist_matrix, _match_path, _ptr, _relative_jump, _stream
+from .generator import DIM, MAX_PATH_ROWS, NTOK, CoherentMatch, Generator, _dev_f32, _dist_matrix, _match_path, _ptr, _relative_jump, _stream
 
 _BORROW, _BF16, _NO_DEC_CACHE = 1, 2, 4          # mocha_bank_set flags (include/mocha_hip.h)
 SOFT_MAX_K = 8                                   # MOCHA_SOFT_MAX_K
@@ -150,6 +150,99 @@ def _refuse_with_mix(who: str, **others):
             raise ValueError(f"{who}: mix= does not combine with {name} (mix is hard matching per component)")
 
 
+def _host_starts(starts, n: int, who: str) -> np.ndarray:
+    """A character's clip starts (local rows) checked on the host -> sorted unique int32 array inside [0, n)."""
+    a = np.asarray([] if starts is None else (starts.tolist() if hasattr(starts, "tolist") else list(starts)), dtype=np.int64).reshape(-1)
+    if a.size and (np.any(np.diff(a) <= 0) or a[0] < 0 or a[-1] >= n):
+        raise ValueError(f"{who}: starts must increase strictly and lie in 0 .. {n - 1}")
+    return np.ascontiguousarray(a.astype(np.int32))
+
+
+class OnlinePath:
+    """Coherent matching one window at a time (include/mocha_hip.h, "coherent matching in live sessions"): per stream, the forward
+    recursion of ``query_path`` advanced by one window per ``step``, its row kept on the device.  The row it returns at window t is the
+    last row of the whole-clip path over windows 0 .. t of the same run - the filtered row, no lookahead.  ``bank``: a
+    ``MultiCharacterBank`` or ``ResidentCharacterBank``; ``streams``: 1 .. 16; ``jump``: the penalty, a number or a ``CoherentMatch``
+    without ``relative`` (a live stream has no clip to take a median from: run ``query_path(..., relative=True)`` on a recorded clip for a
+    unit).  The clip starts are the bank's (``MultiCharacterBank(starts=)``, ``set_starts``, ``ResidentCharacterBank.add(starts=)``).
+    A stream restarts when its character changes, when that character is replaced, after ``reset`` and where ``restart`` - a (streams,)
+    int32 device tensor a producer may write in place - is non-zero (the step clears it); a stream whose id names no loaded character
+    sits the step out (idx -1, dist +inf)."""
+
+    def __init__(self, bank, streams: int, jump, state_rows: Optional[int] = None):
+        if not 1 <= int(streams) <= 16:
+            raise ValueError("OnlinePath: streams must be 1..16")
+        co = CoherentMatch.of(jump)
+        if co.relative:
+            raise ValueError("OnlinePath: a relative jump needs a clip to take the median from; use query_path(..., relative=True) on a "
+                             "recorded clip for the unit and pass the absolute penalty")
+        self.bank, self.model = bank, bank.model
+        self.streams, self.jump = int(streams), co.jump
+        self.state_rows = int(state_rows if state_rows is not None else bank.max_rows)
+        ctx, dev = self.model._ctx, self.model.device
+        nbytes = int(ctx.lib.mocha_path_state_bytes(ctx.h, self.streams, self.state_rows))
+        if nbytes <= 0:
+            raise ValueError(f"OnlinePath: a state of {self.state_rows} rows is not served (1 .. {MAX_PATH_ROWS})")
+        self.state = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
+        self.restart = torch.zeros((self.streams,), dtype=torch.int32, device=dev)
+        self.idx = torch.full((self.streams,), -1, dtype=torch.int32, device=dev)
+        self.dist = torch.full((self.streams,), float("inf"), dtype=torch.float32, device=dev)
+        self.continued = torch.zeros((self.streams,), dtype=torch.uint8, device=dev)
+
+    def reset(self, which=None):
+        """The named streams (None: all) stop running: their next step restarts.  Enqueued on the current stream."""
+        if which is None:
+            self.model._ctx.call("mocha_path_state_reset", _ptr(self.state), self.streams, self.state_rows, None, 0, _stream())
+        else:
+            ids = [int(s) for s in which]
+            arr = (C.c_int32 * max(len(ids), 1))(*ids)
+            self.model._ctx.call("mocha_path_state_reset", _ptr(self.state), self.streams, self.state_rows, arr, len(ids), _stream())
+        return self
+
+    def step(self, query_nm, characters, return_distances: bool = False):
+        """One window per stream: query_nm (streams, 90*256) z-scored, characters one id per stream -> (dist (streams,), idx (streams,)
+        int32 local rows, continued (streams,) uint8), views the next step overwrites.  ``return_distances`` adds the (streams,
+        state_rows) matrix of every row's distance (columns past a character's rows are not written)."""
+        self.bank._ensure()
+        q = _dev_f32(query_nm, self.model.device, None, "query").reshape(-1, NTOK * DIM)
+        if q.shape[0] != self.streams:
+            raise ValueError(f"OnlinePath.step: {q.shape[0]} queries for {self.streams} streams")
+        ids = self.bank._ids(characters, self.streams)
+        rows = torch.full((self.streams, self.state_rows), float("nan"), dtype=torch.float32, device=q.device) if return_distances else None
+        self.model._ctx.call("mocha_match_path_segmented", _ptr(self.state), self.streams, self.state_rows, _ptr(q), _ptr(ids), _ptr(self.restart),
+                             C.c_double(self.jump), _ptr(self.idx), _ptr(self.dist), _ptr(self.continued), _ptr(rows), C.c_int64(self.state_rows),
+                             _stream())
+        return (self.dist, self.idx, self.continued, rows) if return_distances else (self.dist, self.idx, self.continued)
+
+    def advance(self, dist_rows, ids, rows, start_bits=None, bit_off=None):
+        """The pure form (``mocha_match_path_advance``), no bank read: dist_rows (streams, ld) fp32 on the device, ids (streams,) int32
+        (negative: sits out; a change restarts), rows (streams,) int32, ``start_bits`` an int32 device tensor of packed bits (bit
+        ``bit_off[s] + j``: row j of stream s starts a clip) -> (dist, idx, continued) as ``step``."""
+        dev = self.model.device
+        d = _dev_f32(dist_rows, dev, None, "dist_rows")
+        if d.dim() != 2 or d.shape[0] != self.streams:
+            raise ValueError(f"OnlinePath.advance: dist_rows must be ({self.streams}, ld)")
+        ids = torch.as_tensor(ids, dtype=torch.int32).to(dev).contiguous()
+        rows = torch.as_tensor(rows, dtype=torch.int32).to(dev).contiguous()
+        if ids.shape != (self.streams,) or rows.shape != (self.streams,):
+            raise ValueError(f"OnlinePath.advance: ids and rows must have {self.streams} entries")
+        bits = off = None
+        n_bits = 0
+        if start_bits is not None:
+            bits = start_bits.to(dev).contiguous()
+            if bits.dtype != torch.int32:
+                raise ValueError("OnlinePath.advance: start_bits must be an int32 tensor of packed bits")
+            n_bits = 32 * bits.numel()
+            if bit_off is not None:
+                off = torch.as_tensor(bit_off, dtype=torch.int32).to(dev).contiguous()
+        elif bit_off is not None:
+            raise ValueError("OnlinePath.advance: bit_off needs start_bits")
+        self.model._ctx.call("mocha_match_path_advance", _ptr(self.state), self.streams, self.state_rows, _ptr(d), C.c_int64(d.stride(0)), _ptr(ids),
+                             _ptr(rows), _ptr(bits), C.c_int64(n_bits), _ptr(off), _ptr(self.restart), C.c_double(self.jump), _ptr(self.idx),
+                             _ptr(self.dist), _ptr(self.continued), _stream())
+        return self.dist, self.idx, self.continued
+
+
 class _SegmentedBank:
     """What ``MultiCharacterBank`` and ``ResidentCharacterBank`` share: the segmented calls on the model's current bank.  A subclass
     provides ``model``, ``S`` (ids are 0 .. S - 1), ``labels`` (None: no action labels) and ``_ensure()``."""
@@ -247,7 +340,7 @@ class _SegmentedBank:
         return dist, idx + self.rows(int(character))[0], cont
 
     def characterize(self, src_X, characters, cnt_mean, cnt_std, return_index: bool = False, raw: bool = False, soft=None, allow=None,
-                     mix=None):
+                     mix=None, coherent=None):
         """``allow`` (see ``allow_masks``): every window matched among its character's entries of the admissible actions
         (``mocha_characterize_segmented_allow``); with ``return_index`` the outputs gain applied (B,) int32 at the end.
         ``ContextBank.characterize`` with every window matched against its own character: Y (B,T,V,C) [, idx (B,) local rows].
@@ -255,11 +348,29 @@ class _SegmentedBank:
         instead of the nearest one (``mocha_characterize_soft_segmented``); with ``return_index`` -> (Y, idx_k (B,k), weight (B,k)).
         ``mix=(ids, weights)`` (see ``mix_tensors``; ``characters`` is then None): the decoder reads the part-wise weighted blend of the
         entries matched in each component's character (``mocha_characterize_mix_segmented``); with ``return_index`` -> (Y, idx (B,J),
-        weight (B,J,6)).  It does not combine with ``soft`` or ``allow``."""
+        weight (B,J,6)).  It does not combine with ``soft`` or ``allow``.
+        ``coherent=OnlinePath``: window s is the next window of stream s of that path (B = its streams) and is matched by one step of it
+        (``mocha_characterize_segmented_path``); with ``return_index`` -> (Y, idx (B,), dist (B,), continued (B,) uint8), views the path's
+        next step overwrites.  It does not combine with ``soft``, ``allow`` or ``mix``."""
         self._ensure()
         m = self.model
         X = m._xraw(src_X, "src_X_raw") if raw else m._x(src_X, "src_X")
         B = X.shape[0]
+        if coherent is not None:
+            if not isinstance(coherent, OnlinePath) or coherent.bank is not self:
+                raise ValueError("characterize: coherent= takes an OnlinePath of this bank (a clip goes through ContextBank.characterize or query_path)")
+            if soft is not None or allow is not None or mix is not None:
+                raise ValueError("characterize: coherent= does not combine with soft, allow or mix")
+            if B != coherent.streams:
+                raise ValueError(f"characterize: {B} windows for an OnlinePath of {coherent.streams} streams")
+            ids = self._ids(characters, B)
+            mean = _dev_f32(cnt_mean, m.device, (NTOK, DIM), "cnt_mean")
+            std = _dev_f32(cnt_std, m.device, (NTOK, DIM), "cnt_std")
+            Y = torch.empty((B, m.cfg["nframes"], m.V, m.cfg["mot_in_dim"]), dtype=torch.float32, device=m.device)
+            p = coherent
+            m._ctx.call("mocha_characterize_segmented_path", _ptr(X), B, _ptr(ids), _ptr(mean), _ptr(std), _ptr(p.state), p.state_rows,
+                        C.c_double(p.jump), _ptr(p.restart), _ptr(Y), _ptr(p.idx), _ptr(p.dist), _ptr(p.continued), 1 if raw else 0, _stream())
+            return (Y, p.idx, p.dist, p.continued) if return_index else Y
         if mix is not None:
             _refuse_with_mix("characterize", characters=characters is not None, soft=soft is not None, allow=allow is not None)
             mids, mw = mix_tensors(mix, B, m.device, "characterize")
@@ -304,10 +415,12 @@ class MultiCharacterBank(_SegmentedBank):
     """``banks``: a sequence of ``(cnt_nm, encoded)`` pairs, one per character (cnt_nm (N_c, 90*256) z-scored with the SAME global
     cnt_mean / cnt_std as every other character, encoded (N_c, 90, 256)).  They are concatenated once into device tensors this object
     owns and lends to the context.  ``bf16`` / ``dec_cache`` mean what they mean for ``ContextBank``.  ``labels``: one integer array
-    (N_c,) of action labels 0 .. 63 per character (``set_labels``)."""
+    (N_c,) of action labels 0 .. 63 per character (``set_labels``).  ``starts``: per character the local rows that begin a clip
+    (``bank_starts(load_bank(path))``; None: the character is one clip), read by ``OnlinePath`` and ``LiveSession(coherent=)``
+    (``set_starts``)."""
 
     def __init__(self, model: Generator, banks: Sequence[Tuple[torch.Tensor, torch.Tensor]], bf16: bool = False, dec_cache: bool = True,
-                 labels=None):
+                 labels=None, starts=None):
         model._need()
         self.model = model
         if len(banks) < 1:
@@ -330,7 +443,33 @@ class MultiCharacterBank(_SegmentedBank):
         self._bf16 = bool(bf16)
         self._dec_cache = bool(dec_cache)
         self.labels = None if labels is None else self._check_labels(labels)
+        if starts is not None and len(starts) != self.S:
+            raise ValueError(f"starts: {len(starts)} lists for {self.S} characters")
+        self.starts = [_host_starts(None if starts is None else starts[c], sizes[c], f"starts[{c}]") for c in range(self.S)]
         self.activate()
+
+    @property
+    def max_rows(self) -> int:
+        """Rows of the largest character: the rows an ``OnlinePath`` state must hold."""
+        return int(np.diff(self.seg_start).max())
+
+    def _send_starts(self):
+        g = np.concatenate([self.starts[c].astype(np.int64) + self.seg_start[c] for c in range(self.S)])
+        if g.size == 0 and not getattr(self, "_starts_sent", False):
+            return                                         # the table is zero from mocha_bank_set_segments on
+        arr = (C.c_int64 * max(g.size, 1))(*g.tolist())
+        self.model._ctx.call("mocha_bank_set_starts", arr, int(g.size), _stream())
+        self._starts_sent = True
+
+    def set_starts(self, character: int, starts):
+        """The local rows of ``character`` that begin a clip (None: none but its first row).  Enqueued on the current stream; a captured
+        step keeps replaying."""
+        r0, r1 = self.rows(int(character))
+        self.starts[int(character)] = _host_starts(starts, r1 - r0, "set_starts")
+        self._ensure()
+        self._starts_sent = True
+        self._send_starts()
+        return self
 
     def rows(self, c: int) -> Tuple[int, int]:
         """(start, stop) of character ``c``'s rows in the concatenated bank."""
@@ -345,6 +484,8 @@ class MultiCharacterBank(_SegmentedBank):
         self.model._ctx.call("mocha_bank_set_segments", _ptr(self.cnt_nm), _ptr(self.encoded), self.N, seg, self.S, flags, _stream())
         self.model._bank = self
         self._send_labels()
+        self._starts_sent = False                          # (mocha_bank_set_segments zeroed the table)
+        self._send_starts()
         return self
 
     def _check_labels(self, labels) -> np.ndarray:
@@ -407,6 +548,11 @@ class ResidentCharacterBank(_SegmentedBank):
         model._bank = self
         self.labels = [None] * self.S                  # per slot: the character's labels as given (None: empty, or added without)
 
+    @property
+    def max_rows(self) -> int:
+        """The reserved maximum of rows per character: the rows an ``OnlinePath`` state must hold."""
+        return self.max_rows_per_character
+
     def _ensure(self):
         if getattr(self.model, "_bank", None) is not self:
             raise RuntimeError("ResidentCharacterBank: another bank has been activated on this model; a resident bank cannot be rebuilt "
@@ -441,10 +587,11 @@ class ResidentCharacterBank(_SegmentedBank):
         """Rows of the largest free extent: the largest character ``add`` can still take (extents never move)."""
         return self._info(-1)[3]
 
-    def add(self, cnt_nm, encoded, labels=None, slot: Optional[int] = None) -> int:
+    def add(self, cnt_nm, encoded, labels=None, slot: Optional[int] = None, starts=None) -> int:
         """One more character: cnt_nm (n, 90*256) z-scored as every other character's, encoded (n, 90, 256), ``labels`` (n,) integer
         action labels 0 .. 63 (host data is range-checked here; a device int32 tensor is taken as it is and read as label & 63) or None:
         action 0 for every entry.  ``slot``: the slot to fill, or None for the lowest empty one.  Returns the slot - the character's id.
+        ``starts``: the local rows that begin a clip (None: the character is one clip), read by ``OnlinePath`` / ``LiveSession(coherent=)``.
         Enqueued on the current stream, no synchronisation; ``RuntimeError`` when the slot is occupied, no slot is empty or no free
         extent holds n rows (the message names the largest one)."""
         self._ensure()
@@ -454,6 +601,7 @@ class ResidentCharacterBank(_SegmentedBank):
         n = int(nm.shape[0])
         if enc.shape[0] != n:
             raise ValueError("add: cnt_nm and encoded have different entry counts")
+        st = _host_starts(starts, n, "add")
         if slot is not None and not 0 <= int(slot) < self.S:
             raise IndexError(f"add: slot {slot} out of range 0 .. {self.S - 1}")
         lab = kept = None
@@ -477,6 +625,8 @@ class ResidentCharacterBank(_SegmentedBank):
         self.model._ctx.call("mocha_bank_resident_add", -1 if slot is None else int(slot), _ptr(nm), _ptr(enc), n, _ptr(lab) if lab is not None else None,
                              C.byref(got), _stream())
         self.labels[got.value] = kept if kept is not None else np.zeros(n, np.int32)
+        if st.size:
+            self.model._ctx.call("mocha_bank_resident_set_starts", int(got.value), st.ctypes.data_as(C.POINTER(C.c_int32)), int(st.size), _stream())
         return int(got.value)
 
     def retire(self, slot: int):
@@ -488,12 +638,12 @@ class ResidentCharacterBank(_SegmentedBank):
         self.labels[int(slot)] = None
         return self
 
-    def replace(self, slot: int, cnt_nm, encoded, labels=None) -> int:
+    def replace(self, slot: int, cnt_nm, encoded, labels=None, starts=None) -> int:
         """Another character under the same id: ``retire(slot)`` (if it holds one) then ``add(..., slot=slot)``, on the current stream."""
         first, stop = self.rows(slot)
         if first != stop:
             self.retire(slot)
-        return self.add(cnt_nm, encoded, labels=labels, slot=slot)
+        return self.add(cnt_nm, encoded, labels=labels, slot=slot, starts=starts)
 
 
 class MultiStreamCharacterizer:

@@ -34,6 +34,11 @@ mocha_profile_start / stop, during which the step runs eagerly.
         character mixing: the plain live step, the soft live step at k = J and the mix step (LiveSession(mix=J) = mocha_live_step_mix)
         with every stream's J components on J different characters, alternating replay by replay in one process, S = 1, 8 and 16, for
         every listed J; then the mix step's own launches one at a time (profile hooks, eager)
+    python tools/live_latency.py --coherent L [--out profiles/r24/live_path_step.json]
+        coherent matching: the plain live step, the soft live step at k = 1 (the same all-keys scan plus a selection launch: the
+        yardstick) and the coherent step (LiveSession(coherent=L) = mocha_live_step_path: the all-keys scan plus the path step),
+        alternating replay by replay in one process, S = 1, 8 and 16; then the coherent step's matcher launches one at a time (profile
+        hooks, eager)
 """
 import argparse
 import json
@@ -281,6 +286,60 @@ def mix(a, dev, model, mb, mean, std, clip, per, J):
     return res
 
 
+def coherent(a, dev, model, mb, mean, std, clip, per, J):
+    """--coherent L: the plain live step, the soft live step at k = 1 and the coherent live step with jump penalty L, alternating in one
+    process.  The soft step at k = 1 runs the same plan and all-keys scan and one selection / blend launch where the coherent step runs
+    the path step; its decoder is the literal one, the coherent step's the hard one through the bank's per-entry constants."""
+    from mocha_sigasia2023_amd import LiveSession
+    res = {"bank": "8 characters x 2048 rows, fp32, segmented", "layout": "mocha (24 joints)", "coherent_jump": a.coherent,
+           "timing": "HIP events around single graph replays; (a) live step, (b) soft live step with k = 1, temperature 2, (c) coherent live "
+                     "step, alternating; clocks untouched", "streams": {}}
+    for S in (1, 8, 16):
+        ids = torch.tensor([(k * 3) % 8 for k in range(S)], dtype=torch.int32)
+        hard = LiveSession(mb, mean, std, streams=S)
+        sft = LiveSession(mb, mean, std, streams=S, soft=(1, 2.0))
+        co = LiveSession(mb, mean, std, streams=S, coherent=a.coherent)
+        frame = [0]
+
+        def push():
+            f = frame[0] % 644; frame[0] += 1
+            for sess in (hard, sft, co):
+                sess.rot.copy_(clip[0][f]); sess.pos.copy_(clip[1][f]); sess.vel.copy_(clip[2][f]); sess.ang.copy_(clip[3][f])
+                sess.rvel.copy_(per[0][f]); sess.rang.copy_(per[1][f]); sess.speed.copy_(per[2][f]); sess.contact.copy_(per[3][f])
+        for sess in (hard, sft, co):
+            sess.characters.copy_(ids)
+        gen = None
+        for i in range(max(a.warmup, 70)):
+            push(); hard.replay(); sft.replay(); co.replay()
+            gen = model._ctx.generation() if i == 1 else gen
+        torch.cuda.synchronize()
+        assert bool((co.out["valid"] == 1).all()) and bool((co.out["idx"] >= 0).all()) and bool(torch.isfinite(co.out["dist"]).all())
+        ta, tb, tc = [], [], []
+        for _ in range(a.reps):
+            push(); torch.cuda.synchronize()
+            ta.append(event_ms(hard.replay, 1)[0]); tb.append(event_ms(sft.replay, 1)[0]); tc.append(event_ms(co.replay, 1)[0])
+        assert model._ctx.generation() == gen                                     # nothing captured again
+        e = {"a_live_step": pct(np.asarray(ta)), "b_live_step_soft_k1": pct(np.asarray(tb)), "c_live_step_path": pct(np.asarray(tc))}
+        e["c_minus_a_p50_ms"] = e["c_live_step_path"]["p50_ms"] - e["a_live_step"]["p50_ms"]
+        e["c_minus_b_p50_ms"] = e["c_live_step_path"]["p50_ms"] - e["b_live_step_soft_k1"]["p50_ms"]
+        e["continued_fraction_last_step"] = float(co.out["continued"].float().mean())
+        n = 100                                         # the coherent step's matcher, one launch at a time (eager while profiling)
+        model.profile_start()
+        for _ in range(n):
+            co.replay()
+        prof = model.profile_stop()
+        e["path_sites_us"] = {k: 1e3 * v["ms"] / n for k, v in prof["sites"].items() if k.split("|")[0] in ("match.path_keys", "match.path_step")}
+        model.profile_start()
+        for _ in range(n):
+            sft.replay()
+        prof = model.profile_stop()
+        e["soft_sites_us"] = {k: 1e3 * v["ms"] / n for k, v in prof["sites"].items() if k.split("|")[0] in ("match.soft", "dec.in_cha", "dec.style")}
+        assert bool(torch.isfinite(co.out["pos"]).all())
+        res["streams"][str(S)] = e
+        del hard, sft, co
+    return res
+
+
 def constrained(a, dev, model, mb, mean, std, clip, per, J):
     """--constrained: the plain live step and the action-constrained one with zero masks (LiveSession(constrained=True) =
     mocha_live_step_allow: the same launches, the scan reads the masks and one granule word), alternating in one process; then the same
@@ -470,7 +529,10 @@ def main():
     ap.add_argument("--constrained", action="store_true", help="action-constrained matching: live step / constrained live step with zero masks / one action of 16")
     ap.add_argument("--mix", default=None, metavar="J[,J..]", help="character mixing: live step / soft live step at k = J / mix live step with J components, S = 1, 8, 16")
     ap.add_argument("--world", action="store_true", help="world-space poses: live step / live step with world=SkinBind (one mocha_world_pose launch behind the graph), S = 1, 8, 16")
+    ap.add_argument("--coherent", type=float, default=None, metavar="L", help="coherent matching: live step / soft live step at k = 1 / coherent live step with jump penalty L, S = 1, 8, 16")
     a = ap.parse_args()
+    if a.coherent is not None and a.out == ap.get_default("out"):
+        a.out = os.path.join(ROOT, "profiles", "r24", "live_path_step.json")
     if a.world and a.out == ap.get_default("out"):
         a.out = os.path.join(ROOT, "profiles", "r22", "live_world_step.json")
     if a.mix is not None:
@@ -512,6 +574,8 @@ def main():
     per = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (rvel, rang, np.linalg.norm(hipvel, axis=-1).mean(-1).astype(np.float32), contact)]
     res = {"bank": "8 characters x 2048 rows, fp32, segmented", "layout": "mocha (24 joints)", "timing": "HIP events around single graph replays, live and baseline alternating",
            "streams": {}}
+    if a.coherent is not None:
+        return write_out(a, coherent(a, dev, model, mb, mean, std, clip, per, J))
     if a.world:
         return write_out(a, world(a, dev, model, mb, mean, std, clip, per, J))
     if a.mix is not None:
